@@ -34,6 +34,8 @@ if REPO not in sys.path:
 
 HBM_PEAK_GBS = 8000.0       # MI355X HBM3E spec (MI355X_MICROARCH.md: 8.0 TB/s; 6.29 TB/s measured copy)
 INT8_MFMA_PEAK_TOPS = 5000.0  # dense int8 = 2x bf16 (~2.5 PF)
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000   # --dump-outputs: all .npy payloads together, under 64 MB with the file headers
+DUMP_SEED = 7919
 
 
 def parse_args():
@@ -81,7 +83,14 @@ def parse_args():
     ap.add_argument("--graph", action="store_true",
                     help="replay the 53 layer calls as one captured hipGraph instead of launching them one by one "
                          "(measured: no gain, the step is not dispatch-bound: 4.684 vs 4.669 ms)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32): every conv "
+                         "layer's output (a fixed, seeded sample of it when the layer is larger than its share of the 64 MB "
+                         "budget; 8-bit packed bytes with --fused-requant), the logits and the top-1 predictions (rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 class Layer:
@@ -286,6 +295,29 @@ def cpu_baseline(layers, args, torch):
                       % (n_img, len(layers), dt)}
 
 
+def dump_outputs(out_dir, layers, mb_layers, logits, pred, torch):
+    """--dump-outputs: the results of the last timed step as float32 .npy files.  A layer's output is written whole when it
+    fits its share of DUMP_BUDGET_BYTES, otherwise as a sorted sample of flat positions drawn from a CPU generator seeded by
+    the layer's index: the positions depend only on the arguments, so two builds' dumps compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    extras = {"logits": logits.float(), "pred": pred.float()}
+    share = max(1, (DUMP_BUDGET_BYTES - sum(4 * t.numel() for t in extras.values())) // (4 * len(layers)))
+    for i, L in enumerate(layers):
+        parts = [m[i] for m in mb_layers] if mb_layers else [L]
+        if getattr(L, "out_q", None) is not None:       # --fused-requant: the packed 8-bit codes the caller receives
+            y = torch.cat([p.out_q for p in parts]).float()
+        else:
+            y = torch.cat([p.out for p in parts])
+        if y.numel() > share:
+            g = torch.Generator().manual_seed(DUMP_SEED + L.idx)
+            pos = torch.randint(y.numel(), (share,), generator=g).sort().values
+            y = y.reshape(-1)[pos.to(y.device)]
+        np.save(os.path.join(out_dir, "%02d_%s.npy" % (L.idx, L.spec.name)), y.cpu().numpy())
+    for name, t in extras.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     args = parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -414,7 +446,7 @@ def main():
             feats = last.out.mean(dim=(2, 3))
         logits = feats @ fc_w.t()
         logits = qdist.gather_logits(logits, equal_shards=True) if world > 1 else logits
-        return logits.argmax(dim=1)
+        return logits, logits.argmax(dim=1)
 
     # --graph: capture the kernel launches of a step (53 convs + 2 gathers; + the weight preps with --per-call-prepare) once into a hipGraph and
     # replay it per step (same kernels, arguments and stream order; only the per-launch dispatch gaps go).
@@ -427,7 +459,7 @@ def main():
     with torch.cuda.stream(stream):
         if args.graph:
             step()                   # first calls outside capture (lazy one-time attribute setup in the library)
-            pred = tail()
+            logits, pred = tail()
             stream.synchronize()
             try:
                 graph = torch.cuda.CUDAGraph()
@@ -448,7 +480,7 @@ def main():
     with torch.cuda.stream(stream):
         for _ in range(args.warmup):
             run_step()
-            pred = tail()
+            logits, pred = tail()
         stream.synchronize()
         if world > 1:
             dist.barrier()
@@ -460,7 +492,7 @@ def main():
             ev0[k].record(stream)
             run_step()
             ev1[k].record(stream)
-            pred = tail()
+            logits, pred = tail()
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -471,6 +503,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert pred.numel() == N * world
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, layers, mb_layers if M > 1 else None, logits, pred, torch)
 
     conv_ms = sum(a.elapsed_time(b) for a, b in zip(ev0, ev1)) / args.steps
     total_bytes = sum(L.bytes for L in layers)

@@ -43,9 +43,12 @@ def _worker(rank, world, port, totals, q):
         # several global batches in ONE process group: 7 -> 8 gives rank 0 the same local shape (4 rows) in both
         # calls while rank 1 goes 3 -> 4 (the round-1 hang: a per-rank cached equal/unequal decision)
         for total in totals:
+            # integer-valued operands: every partial sum is exact in fp32, so the stand-in gives the same bits whatever
+            # batch size or summation order the host BLAS picks (a float matmul of 7 rows and of 13 rows need not agree
+            # in the last bit on every CPU), and the comparison below tests the collective alone
             g = torch.Generator().manual_seed(total)
-            x = torch.randn(total, 3, 4, 4, generator=g)
-            w = torch.randn(48, 10, generator=g)
+            x = torch.randint(-8, 9, (total, 3, 4, 4), generator=g).float()
+            w = torch.randint(-8, 9, (48, 10), generator=g).float()
             mine = qdist.shard_batch(x)
             logits = qdist.gather_logits(_per_image_logits(mine, w))
             full = _per_image_logits(x, w)
