@@ -206,6 +206,30 @@ int qe_quantconv2d_requant_prepared(const qe_qparam *x, const qe_qparam *w, cons
                                     void *workspace, size_t workspace_bytes, qe_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * qe_quantconv2d_residual_prepared -- a residual block's last convolution with the block end fused into it:
+ *   out[n,oc,p] = max(conv(x, w, bias)[n,oc,p] + identity[n,oc,p], 0)          (fp32, NCHW)
+ *   codes       = the consumer's quantiser applied to out, packed (as qe_quantize_pack), when rq != NULL.
+ *   reference: torchvision's Bottleneck / BasicBlock forward (`out += identity; out = relu(out)`) around the runners'
+ *   QuantConv2d (modelzoo/reconstruct.py), followed by the next block's Quantizer + tpack.
+ * out       bit-identical to torch.relu(qe_quantconv2d_prepared(...) + identity): one fp32 add, then max with 0, NaN
+ *           propagating; codes bit-identical to qe_quantize_pack(out, rq->scale, rq->zero, rq->n_param, OH*OW, ...).
+ * identity  fp32, shaped like out.  out == identity (in place) is allowed; any other overlap returns QE_ERR_ARG.
+ *           identity / out 16-byte aligned, codes 4-byte aligned.
+ * out       may be NULL when rq != NULL (codes only).  status as qe_tpack (bit 0: a code out of range, or NaN).
+ * qe_quantconv2d_residual_path: 1 = the conv kernel does it all (1x1 stride-1 resident-tile kernels, 8-bit operands; rq NULL
+ *           or 8-bit per tensor); 0 = two passes inside the call (the conv's fp32 y, then one elementwise pass y + identity ->
+ *           out + codes), which covers every other problem, sub-8-bit codes and per-channel rq.
+ * workspace qe_quantconv2d_residual_workspace_bytes() bytes (0 on path 1), 16-byte aligned.
+ * ------------------------------------------------------------------------- */
+int qe_quantconv2d_residual_path(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq);
+size_t qe_quantconv2d_residual_workspace_bytes(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w,
+                                               const qe_requant *rq);
+int qe_quantconv2d_residual_prepared(const qe_qparam *x, const qe_qparam *w, const float *bias,
+                                     const qe_conv_shape *shape, const void *prepared, size_t prepared_bytes,
+                                     const float *identity, float *out, const qe_requant *rq, uint8_t *codes,
+                                     int32_t *status, void *workspace, size_t workspace_bytes, qe_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * qe_quantconv2d_float_input -- replaces quantconv2d_float_input()/..._cuda
  *   reference: engine/kernels/functions/quantconv2d_float_input.cu:140-220, :45-121.
  * x        fp32[N*IC*H*W], NCHW contiguous.
@@ -272,6 +296,14 @@ int qe_quantlinear_float_input_path(const float *x, const qe_qparam *w, int64_t 
  * contiguous floats.  The reference's models do this in PyTorch (torchvision ResNet: AdaptiveAvgPool2d); bench.py's
  * top-1 tail uses this entry point because torch's reduction reads the (256,2048,7,7) conv output at 1.5 TB/s.     */
 int qe_global_avgpool(const float *x, int64_t n_planes, int32_t P, float *out, qe_stream_t stream);
+
+/* Max pooling of 8-bit stored codes, NCHW, square window / stride / padding (torchvision's stem: 3, 2, 1).  Exact on codes:
+ * the stored code (q, or q + 128 when signed) is order-preserving and the quantiser is non-decreasing, so
+ * maxpool(q(relu(y))) == q(maxpool(relu(y))).  Padding taps are ignored (torch pads with -inf); 2 * padding <= kernel.
+ * x: N*C*H*W bytes, out: N*C*OH*OW bytes.  Sub-8-bit packed streams are not taken (QE_ERR_UNSUPPORTED from the bindings,
+ * which know the stream's width; this entry point sees bytes only). */
+int qe_maxpool2d_codes(const uint8_t *x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t kernel, int32_t stride,
+                       int32_t padding, uint8_t *out, qe_stream_t stream);
 
 #ifdef __cplusplus
 }

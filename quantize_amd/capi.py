@@ -12,6 +12,7 @@ from . import loader
 _lib = None
 
 QE_OK = 0
+QE_ERR_UNSUPPORTED = 7
 DTYPES = {"uint8": 0, "int8": 1, "int16": 2, "int32": 3, "int64": 4,
           "float16": 5, "float32": 6, "float64": 7}
 
@@ -23,7 +24,8 @@ SYMBOLS = ["qe_error_string", "qe_last_hip_error", "qe_version", "qe_target_arch
            "qe_conv_prepare", "qe_quantconv2d_prepared", "qe_quantize_pack", "qe_quantconv2d_float_input_workspace_bytes",
            "qe_quantconv2d_float_input_ws", "qe_conv_f32_prepare", "qe_quantconv2d_float_input_prepared",
            "qe_quantconv2d_float_input_path", "qe_quantconv2d_requant_path", "qe_quantconv2d_requant_workspace_bytes",
-           "qe_quantconv2d_requant_prepared", "qe_conv_prepared_layout"]
+           "qe_quantconv2d_requant_prepared", "qe_conv_prepared_layout", "qe_quantconv2d_residual_path",
+           "qe_quantconv2d_residual_workspace_bytes", "qe_quantconv2d_residual_prepared", "qe_maxpool2d_codes"]
 
 
 class QeConvShape(ctypes.Structure):
@@ -112,6 +114,14 @@ def lib():
     L.qe_quantconv2d_requant_workspace_bytes.argtypes = [ps, pq, pq, pr]
     L.qe_quantconv2d_requant_prepared.restype = i32
     L.qe_quantconv2d_requant_prepared.argtypes = [pq, pq, vp, ps, vp, sz, pr, vp, vp, vp, sz, vp]
+    L.qe_quantconv2d_residual_path.restype = i32
+    L.qe_quantconv2d_residual_path.argtypes = [ps, pq, pq, pr]
+    L.qe_quantconv2d_residual_workspace_bytes.restype = sz
+    L.qe_quantconv2d_residual_workspace_bytes.argtypes = [ps, pq, pq, pr]
+    L.qe_quantconv2d_residual_prepared.restype = i32
+    L.qe_quantconv2d_residual_prepared.argtypes = [pq, pq, vp, ps, vp, sz, vp, vp, pr, vp, vp, vp, sz, vp]
+    L.qe_maxpool2d_codes.restype = i32
+    L.qe_maxpool2d_codes.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]
     _lib = L
     return L
 
@@ -268,6 +278,58 @@ def quantconv2d_requant_prepared(xq, wq, bias, sh, prepared, rq, out=None, statu
                                                 None if workspace is None else workspace.data_ptr(),
                                                 0 if workspace is None else workspace.numel(), _stream(stream)))
     return out, status
+
+
+def residual_path(sh, xq, wq, rq=None):
+    """1: the conv kernel adds the identity, applies the ReLU and writes out / codes itself; 0: two passes inside the call."""
+    return int(lib().qe_quantconv2d_residual_path(ctypes.byref(sh), ctypes.byref(xq), ctypes.byref(wq),
+                                                  None if rq is None else ctypes.byref(rq)))
+
+
+def residual_workspace_bytes(sh, xq, wq, rq=None):
+    return int(lib().qe_quantconv2d_residual_workspace_bytes(ctypes.byref(sh), ctypes.byref(xq), ctypes.byref(wq),
+                                                             None if rq is None else ctypes.byref(rq)))
+
+
+def quantconv2d_residual_prepared(xq, wq, bias, sh, prepared, identity, rq=None, out="new", codes=None, status=None,
+                                  workspace=None, stream=None):
+    """qe_quantconv2d_residual_prepared: out = relu(conv + identity) (fp32) and, with rq, the consumer's codes of out.
+    out="new" allocates it, None skips it (rq required), or pass a tensor (identity itself: in place).
+    Returns (out or None, codes or None, status int32[1] tensor)."""
+    import torch
+    dev = wq._keep[0].device
+    OH, OW = out_hw(sh)
+    assert identity.is_contiguous() and identity.dtype == torch.float32 and identity.numel() == sh.N * sh.OC * OH * OW
+    if isinstance(out, str):
+        out = torch.empty((sh.N, sh.OC, OH, OW), dtype=torch.float32, device=dev)
+    if rq is not None and codes is None:
+        codes = torch.empty(packed_nbytes(sh.N * sh.OC * OH * OW, rq.n_bits), dtype=torch.uint8, device=dev)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    need = residual_workspace_bytes(sh, xq, wq, rq)
+    if workspace is None and need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    check(lib().qe_quantconv2d_residual_prepared(
+        ctypes.byref(xq), ctypes.byref(wq), None if bias is None else bias.data_ptr(), ctypes.byref(sh),
+        prepared.data_ptr() if prepared.numel() else None, prepared.numel(), identity.data_ptr(),
+        None if out is None else out.data_ptr(), None if rq is None else ctypes.byref(rq),
+        None if codes is None else codes.data_ptr(), status.data_ptr(), None if workspace is None else workspace.data_ptr(),
+        0 if workspace is None else workspace.numel(), _stream(stream)))
+    return out, codes, status
+
+
+def maxpool2d_codes(x, n_bits, N, C, H, W, kernel=3, stride=2, padding=1, out=None, stream=None):
+    """qe_maxpool2d_codes on an 8-bit stored-code stream (N*C*H*W bytes) -> N*C*OH*OW bytes.  Sub-8-bit streams are not
+    taken: QeError(QE_ERR_UNSUPPORTED)."""
+    import torch
+    if int(n_bits) != 8:
+        check(QE_ERR_UNSUPPORTED)
+    OH, OW = (H + 2 * padding - kernel) // stride + 1, (W + 2 * padding - kernel) // stride + 1
+    if out is None:
+        out = torch.empty(max(N * C * OH * OW, 0), dtype=torch.uint8, device=x.device)
+    check(lib().qe_maxpool2d_codes(x.data_ptr(), int(N), int(C), int(H), int(W), int(kernel), int(stride), int(padding),
+                                   out.data_ptr(), _stream(stream)))
+    return out
 
 
 def quantize_pack(x, scale, zero, qmin, qmax, n_bits, sign, inner=1, out=None, status=None, stream=None):

@@ -73,6 +73,13 @@ int launch_conv_mfma(const qe_qparam *x, const qe_qparam *w, const float *bias, 
                      size_t prepared_bytes, const RequantHost *rq = nullptr);
 bool mfma_conv_requant_fused(const qe_conv_shape *sh, const qe_qparam *x, const qe_qparam *w, int rq_bits, int rq_n_param);
 
+// qe_conv_pwr.hip (residual block end) and qe_tpack.hip (its two-pass form)
+bool pwr_residual_eligible(const qe_conv_shape *sh, const qe_qparam *x, const qe_qparam *w, int rq_bits, int rq_n_param);
+int launch_pwr(const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *sh, float *out, hipStream_t s,
+               const RequantHost *rq, const float *res);
+int launch_residual_relu_quant(const float *y, const float *identity, float *out, int64_t n, int64_t inner, const qe_requant *rq,
+                               uint8_t *codes, int32_t *status, hipStream_t s);
+
 // qe_conv_f32.hip
 bool f32_conv_eligible(const qe_conv_shape *sh, const qe_qparam *w);
 size_t f32_conv_prepared_bytes(const qe_conv_shape *sh);
@@ -278,6 +285,68 @@ extern "C" int qe_quantconv2d_requant_prepared(const qe_qparam *x, const qe_qpar
                             rq->qmax, rq->n_bits, rq->sign, out, status, stream);
 }
 
+// ---- residual block end: out = relu(conv + identity), optionally with the consumer's codes ----
+extern "C" int qe_quantconv2d_residual_path(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq)
+{
+    if (qe::check_shape(shape) != QE_OK || x == nullptr || w == nullptr) return 0;
+    if (!qe::mfma_conv_eligible(shape, x, w)) return 0;
+    return qe::pwr_residual_eligible(shape, x, w, rq ? rq->n_bits : 0, rq ? rq->n_param : 1) ? 1 : 0;
+}
+
+extern "C" size_t qe_quantconv2d_residual_workspace_bytes(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w,
+                                                          const qe_requant *rq)
+{
+    if (qe::check_shape(shape) != QE_OK || x == nullptr || w == nullptr) return 0;
+    if (qe_quantconv2d_residual_path(shape, x, w, rq)) return 0;      // the conv kernel reads no scratch
+    const size_t conv = (qe_quantconv2d_prepared_workspace_bytes(shape, x->n_bits, w->n_bits) + 255) / 256 * 256;
+    return conv + requant_y_bytes(shape);
+}
+
+extern "C" int qe_quantconv2d_residual_prepared(const qe_qparam *x, const qe_qparam *w, const float *bias,
+                                                const qe_conv_shape *shape, const void *prepared, size_t prepared_bytes,
+                                                const float *identity, float *out, const qe_requant *rq, uint8_t *codes,
+                                                int32_t *status, void *workspace, size_t workspace_bytes, qe_stream_t stream)
+{
+    using namespace qe;
+    int rc = check_shape(shape);
+    if (rc != QE_OK) return rc;
+    if ((rc = check_qparam(x)) != QE_OK) return rc;
+    if ((rc = check_qparam(w)) != QE_OK) return rc;
+    if ((rc = check_nparam(x, w, shape)) != QE_OK) return rc;
+    if (rq != nullptr && (rc = check_requant(rq)) != QE_OK) return rc;
+    if (rq != nullptr && !(rq->n_param == 1 || rq->n_param >= shape->OC)) return QE_ERR_ARG;
+    if (identity == nullptr || (rq != nullptr && codes == nullptr) || (out == nullptr && rq == nullptr)) return QE_ERR_ARG;
+    // 16-byte aligned fp32 tensors, 4-byte aligned codes: what every device allocator returns
+    if (((reinterpret_cast<uintptr_t>(identity) | reinterpret_cast<uintptr_t>(out)) & 15) != 0 ||
+        (reinterpret_cast<uintptr_t>(codes) & 3) != 0)
+        return QE_ERR_ARG;
+    const int64_t OH = (shape->H + 2 * shape->padding - shape->KH) / shape->stride + 1;
+    const int64_t OW = (shape->W + 2 * shape->padding - shape->KW) / shape->stride + 1;
+    if (OH <= 0 || OW <= 0) return QE_ERR_ARG;
+    const int64_t n = (int64_t)shape->N * shape->OC * OH * OW;
+    if (out != nullptr && out != identity) {                 // in place is allowed; any other overlap is not
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), i0 = reinterpret_cast<uintptr_t>(identity);
+        const uintptr_t bytes = (uintptr_t)n * sizeof(float);
+        if (o0 < i0 + bytes && i0 < o0 + bytes) return QE_ERR_ARG;
+    }
+    if (n == 0) return QE_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (qe_quantconv2d_residual_path(shape, x, w, rq)) {
+        if (rq == nullptr) return launch_pwr(x, w, bias, shape, out, s, nullptr, identity);
+        const RequantHost rh{codes, rq->scale, rq->zero, rq->n_param, rq->qmin, rq->qmax, rq->n_bits, rq->sign, status};
+        return launch_pwr(x, w, bias, shape, out, s, &rh, identity);
+    }
+    // two passes: the conv's fp32 y (into out, unless out is NULL or IS the identity: then behind the conv scratch), then
+    // one elementwise pass y + identity -> out and codes
+    const size_t conv_ws = (qe_quantconv2d_prepared_workspace_bytes(shape, x->n_bits, w->n_bits) + 255) / 256 * 256;
+    if (workspace_bytes < conv_ws + requant_y_bytes(shape) || (workspace == nullptr && conv_ws + requant_y_bytes(shape) > 0))
+        return QE_ERR_WORKSPACE;
+    float *y = (out != nullptr && out != identity) ? out : reinterpret_cast<float *>(static_cast<uint8_t *>(workspace) + conv_ws);
+    rc = qe_quantconv2d_prepared(x, w, bias, shape, prepared, prepared_bytes, y, workspace, conv_ws, stream);
+    if (rc != QE_OK) return rc;
+    return launch_residual_relu_quant(y, identity, out, n, OH * OW, rq, codes, status, s);
+}
+
 extern "C" int qe_quantconv2d_float_input(const float *x, const qe_qparam *w, const float *bias,
                                           const qe_conv_shape *shape, float *out, qe_stream_t stream)
 {
@@ -395,6 +464,68 @@ extern "C" int qe_global_avgpool(const float *x, int64_t n_planes, int32_t P, fl
     if (blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(global_avgpool_kernel, dim3((unsigned)blocks), dim3(256), (size_t)AP_PLANES * P * sizeof(float),
                        static_cast<hipStream_t>(stream), x, out, n_planes, (int)P);
+    QE_LAUNCH_CHECK();
+    return QE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Max pooling of 8-bit stored codes (the stem's MaxPool2d after its quantised ReLU).  The stored code (q, or q + 128 when
+// signed) is order-preserving and the quantiser is non-decreasing, so max over codes == code of the max.  A thread makes
+// 16 consecutive outputs of the flat (N, C, OH, OW) tensor and stores them as one 16-byte piece where it can; padding
+// taps are skipped (torch pads with -inf).
+// ---------------------------------------------------------------------------------------------
+namespace qe {
+__global__ __launch_bounds__(256) void maxpool2d_codes_kernel(const uint8_t *__restrict__ x, uint8_t *__restrict__ out, int64_t n_out,
+                                                              int H, int W, int OH, int OW, int k, int stride, int pad, int vec)
+{
+    const int64_t o0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 16;
+    if (o0 >= n_out) return;
+    // the first output's (plane, row, column) once (one 64-bit division per 16 outputs), then walked along the row
+    const int64_t plane0 = o0 / ((int64_t)OH * OW);
+    const int rem = (int)(o0 - plane0 * OH * OW);
+    int oh = rem / OW, ow = rem - oh * OW;
+    const uint8_t *xp = x + plane0 * H * W;
+    uint8_t r[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        uint32_t m = 0;
+        if (o0 + j < n_out) {
+            const int h0 = oh * stride - pad, w0 = ow * stride - pad;
+            const int hlo = h0 < 0 ? 0 : h0, hhi = h0 + k < H ? h0 + k : H;
+            const int wlo = w0 < 0 ? 0 : w0, whi = w0 + k < W ? w0 + k : W;
+            for (int ih = hlo; ih < hhi; ++ih)
+                for (int iw = wlo; iw < whi; ++iw) m = max(m, (uint32_t)xp[ih * W + iw]);
+        }
+        r[j] = (uint8_t)m;
+        if (++ow == OW) {
+            ow = 0;
+            if (++oh == OH) { oh = 0; xp += (int64_t)H * W; }
+        }
+    }
+    if (vec && o0 + 16 <= n_out) {
+        uint4 v;
+        __builtin_memcpy(&v, r, 16);
+        *reinterpret_cast<uint4 *>(out + o0) = v;
+    } else {
+        for (int j = 0; j < 16 && o0 + j < n_out; ++j) out[o0 + j] = r[j];
+    }
+}
+}  // namespace qe
+
+extern "C" int qe_maxpool2d_codes(const uint8_t *x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t kernel, int32_t stride,
+                                  int32_t padding, uint8_t *out, qe_stream_t stream)
+{
+    using namespace qe;
+    if (N < 0 || C < 0 || H <= 0 || W <= 0 || kernel <= 0 || stride <= 0 || padding < 0 || 2 * padding > kernel) return QE_ERR_ARG;
+    const int OH = (H + 2 * padding - kernel) / stride + 1, OW = (W + 2 * padding - kernel) / stride + 1;
+    if (H + 2 * padding < kernel || W + 2 * padding < kernel || OH <= 0 || OW <= 0) return QE_ERR_ARG;
+    const int64_t n_out = (int64_t)N * C * OH * OW;
+    if (n_out == 0) return QE_OK;
+    if (x == nullptr || out == nullptr) return QE_ERR_ARG;
+    const int64_t blocks = (n_out + 16 * 256 - 1) / (16 * 256);
+    if (blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(maxpool2d_codes_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x, out, n_out,
+                       (int)H, (int)W, OH, OW, (int)kernel, (int)stride, (int)padding, (reinterpret_cast<uintptr_t>(out) & 15) == 0 ? 1 : 0);
     QE_LAUNCH_CHECK();
     return QE_OK;
 }

@@ -50,7 +50,60 @@ struct PwrArgs {
     float rq_qmin, rq_qmax, rq_lo, rq_hi;
     unsigned rq_offset;
     int32_t *rq_status;
+    // residual block end (RES instances): out = max(y + res, 0) with res shaped like out; out may be NULL when RQ
+    const float *res;
 };
+
+// RES epilogue (residual block end), software-pipelined by one block of NB 16-byte pieces.  vmcnt is ONE in-order counter
+// for loads and stores: a wait for an identity load issued behind stores waits for those stores' acknowledgements too.  So
+// a block's identity pieces are all requested BEFORE the previous block's stores are issued (its results wait in
+// registers), and the compiler's wait for them names exactly the stores behind them: no store is ever waited for.
+//   res_load   the identity pieces of a block (element offsets e + off[k]; e % 4 == 0, 16-byte aligned bases: host-checked)
+//   res_flush  the pending block's stores: fp32 (unless out is NULL) and, with RQ, 4 codes per piece as one dword
+//   res_make   out = relu(y + identity) exactly as torch computes it (one fp32 add; NaN passes the ReLU), and its codes
+// Lanes past a block's last piece repeat the last piece (same address, same value): no lane-dependent branch, so the
+// compiler's wait counts stay exact.
+template <bool RQ, int NB> struct ResBlock {
+    float4 v[NB];
+    uint32_t pk[RQ ? NB : 1];
+    int64_t e;
+};
+template <int NB>
+__device__ __forceinline__ void res_load(const PwrArgs &a, int64_t e, const uint32_t (&off)[NB], float4 (&id)[NB])
+{
+#pragma unroll
+    for (int k = 0; k < NB; ++k) id[k] = *reinterpret_cast<const float4 *>(a.res + e + off[k]);
+}
+template <bool RQ, int NB>
+__device__ __forceinline__ void res_flush(const PwrArgs &a, const ResBlock<RQ, NB> &b, const uint32_t (&off)[NB])
+{
+    if (a.out != nullptr) {
+#pragma unroll
+        for (int k = 0; k < NB; ++k) *reinterpret_cast<float4 *>(a.out + b.e + off[k]) = b.v[k];
+    }
+    if constexpr (RQ) {
+#pragma unroll
+        for (int k = 0; k < NB; ++k) *reinterpret_cast<uint32_t *>(a.rq_out + b.e + off[k]) = b.pk[k];
+    }
+}
+template <bool RQ>
+__device__ __forceinline__ void res_make(const RqConst &rqc, float4 y, float4 id, float4 &out, uint32_t &pk, bool &bad)
+{
+    float v[4] = {y.x + id.x, y.y + id.y, y.z + id.z, y.w + id.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (v[j] > 0.0f || v[j] != v[j]) ? v[j] : 0.0f;
+    out = make_float4(v[0], v[1], v[2], v[3]);
+    if constexpr (RQ) {
+        pk = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            bool b = false;
+            const float r = rq_value(rqc, v[j], b);
+            bad |= b;
+            pk = __builtin_amdgcn_cvt_pk_u8_f32(r, j, pk);
+        }
+    }
+}
 
 // NT column tiles of 32 pixel slots (odd), of which the first TW pixels are real: every tile of a launch has the same
 // width (the host picks TW | P), so the number of stores per strip is a compile-time constant (see wait_w below).
@@ -82,10 +135,16 @@ template <int NT, int WAVES, int KS, int TW> struct PwrGeom {
 // the transposed accumulator), so a lane owns ONE output channel and 4 consecutive pixels per register quad: its channel
 // constants are its own registers (no table), four codes pack into a dword (v_cvt_pk_u8_f32) and the strip's 32 rows x TW
 // bytes go through the wave's patch once: NRQ = 7 store instructions per strip instead of 28.
-template <int NT, int WAVES, int KS, int TW, bool S2 = false, bool RQ = false>
+// RES: fused residual block end (qe_quantconv2d_residual_prepared): the fp32 form's epilogue, each 16-byte piece of the
+// patch read-back is added to the identity piece at the same position (loaded right next to its store), put through the
+// ReLU and stored as fp32 (unless out is NULL) and, with RQ, as 4 codes (one dword) of the consumer's quantiser.  RQ then
+// keeps the fp32 form's operand roles: the codes come from the value AFTER the add, which only the read-back holds.
+template <int NT, int WAVES, int KS, int TW, bool S2 = false, bool RQ = false, bool RES = false>
 __global__ __launch_bounds__(64 * WAVES, 2) void conv_pwr_kernel(const PwrArgs a)
 {
     using G = PwrGeom<NT, WAVES, KS, TW>;
+    static_assert(!(S2 && RES), "the residual epilogue has stride-1 instances only");
+    constexpr bool RQT = RQ && !RES;                          // the transposed re-quantising epilogue
     static_assert(TW % 4 == 0 && TW <= 32 * NT && TW > 32 * (NT - 1), "tile width");
     constexpr int RS = G::RS, PXW = G::PXW;
     static_assert((NT & 1) == 1, "row stride must be an odd multiple of 32 B");
@@ -230,12 +289,24 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_pwr_kernel(const PwrArgs a
         rb_off[k] = f < 8 * G::PPR ? (uint32_t)row * (uint32_t)P + 4u * (uint32_t)pc : 0u;
     }
 
+    // RES: the same pieces, lanes past the last one clamped to it (see res_load)
+    uint32_t rs_off[RES ? NRB : 1], rs_lds[RES ? NRB : 1];
+    if constexpr (RES) {
+#pragma unroll
+        for (int k = 0; k < NRB; ++k) {
+            const int f = (64 * k + lane) < 8 * G::PPR ? 64 * k + lane : 8 * G::PPR - 1;
+            const int row = f / G::PPR, pc = f - row * G::PPR;
+            rs_off[k] = (uint32_t)row * (uint32_t)P + 4u * (uint32_t)pc;
+            rs_lds[k] = 4u * (uint32_t)f;
+        }
+    }
+
     // RQ: piece f = 64 k + lane of the strip's 32 x TW bytes of codes.  Tile = whole plane: the 32 rows are ONE contiguous
     // run of the output, copied flat as aligned pieces; else row f / PPRB, piece f % PPRB, the last piece of a row shifted
     // back to end at the row's end (dword-aligned 16-byte stores; the bytes two pieces share hold the same codes).
-    uint32_t rq_lds[RQ ? G::NRQ : 1], rq_glb[RQ ? G::NRQ : 1];
-    bool rq_live[RQ ? G::NRQ : 1];
-    if constexpr (RQ) {
+    uint32_t rq_lds[RQT ? G::NRQ : 1], rq_glb[RQT ? G::NRQ : 1];
+    bool rq_live[RQT ? G::NRQ : 1];
+    if constexpr (RQT) {
 #pragma unroll
         for (int k = 0; k < G::NRQ; ++k) {
             const int f = 64 * k + lane;
@@ -318,7 +389,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_pwr_kernel(const PwrArgs a
 #pragma unroll
                     for (int j = 0; j < 4; ++j) sxacc[t] = __builtin_amdgcn_sdot4(xf[j], 0x01010101, sxacc[t], false);
                 }
-                if constexpr (RQ) acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xf, wk, acc[t], 0, 0, 0);
+                if constexpr (RQT) acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xf, wk, acc[t], 0, 0, 0);
                 else acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(wk, xf, acc[t], 0, 0, 0);
             }
         }
@@ -331,11 +402,13 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_pwr_kernel(const PwrArgs a
     // epilogue of the strip whose sums sit in acc / swacc; (e_sw, e_zw, e_bi) = its lane's channel constants.
     // next >= 0: the next strip's weights are requested in front of this strip's N_YOUNGER stores (vmcnt is a 6-bit in-order
     // counter: the wait for the weights names the stores issued behind them).
-    constexpr int N_YOUNGER = RQ ? G::NRQ : 4 * NRB;
+    // RES: the epilogue waits for its identity loads itself (the compiler's waits, in issue order), and they were issued
+    // after the weights: the weights have landed by then, so the statement below need not wait for anything (vmcnt(63)).
+    constexpr int N_YOUNGER = RES ? 63 : (RQ ? G::NRQ : 4 * NRB);
     static_assert(N_YOUNGER <= 63, "vmcnt is a 6-bit counter");
     auto epilogue = [&](int strip, float e_sw, float e_zw, float e_bi, bool need_sx) __attribute__((always_inline)) {
         const int oc0 = strip * 32;
-        if constexpr (RQ) {
+        if constexpr (RQT) {
             // lane col owns channel oc0 + col (its own constants); register 4 gq + j of column tile t = pixel 32 t + 8 gq + 4 h + j.
             // The fp32 value is computed exactly as in the fp32 form below, then quantised as quantize_pack would.
             const float zwp = e_zw - zw_shift;
@@ -408,6 +481,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_pwr_kernel(const PwrArgs a
             }
         }
         float *out_s = a.out + ((int64_t)n0 * a.OC + oc0) * P + p0;      // wave-uniform
+        ResBlock<RQ, RES ? NRB : 1> pend;                                  // RES: the previous 8-row block, stores pending
 #pragma unroll
         for (int gq = 0; gq < 4; ++gq) {
             // rows 8 gq + 4 h + j, j = 0..3 of the strip <-> registers 4 gq + j
@@ -440,6 +514,17 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_pwr_kernel(const PwrArgs a
             }
             // read the 8 x TW block back flat and store 16-byte pieces of its rows (one contiguous run when TW == P).
             // Exactly NRB store instructions per register quad, whatever the tile: wait_w counts on it.
+            if constexpr (RES) {
+                const int64_t e_g = ((int64_t)n0 * a.OC + oc0 + 8 * gq) * P + p0;   // element offset of the 8-row block
+                float4 id[NRB];
+                res_load(a, e_g, rs_off, id);
+                if (gq > 0) res_flush(a, pend, rs_off);                            // behind this block's identity requests
+#pragma unroll
+                for (int k = 0; k < NRB; ++k)
+                    res_make<RQ>(rqc, *reinterpret_cast<const float4 *>(patch + rs_lds[k]), id[k], pend.v[k], pend.pk[RQ ? k : 0], bad);
+                pend.e = e_g;
+                continue;
+            }
             float *out_g = out_s + (int64_t)(8 * gq) * P;
 #pragma unroll
             for (int k = 0; k < NRB; ++k) {
@@ -447,6 +532,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_pwr_kernel(const PwrArgs a
                 if (64 * k + 64 <= 8 * G::PPR || 64 * k + lane < 8 * G::PPR) *reinterpret_cast<float4 *>(out_g + rb_off[k]) = o4;
             }
         }
+        if constexpr (RES) res_flush(a, pend, rs_off);
     };
 
     // strip s + 1's weights are requested, strip s is stored, strip s + 1 is multiplied.  The wait for the weights leaves
@@ -514,9 +600,12 @@ template <int KS, int GI> struct Pwr7Geom {
 // RQ: fused re-quantisation (qe_quantconv2d_requant_prepared): the strip's 32 planes x 49 codes of an image are ONE contiguous,
 // 16-byte aligned 1,568-byte run of the output; the wave lays the codes out in its patch as they stand in memory (byte writes)
 // and copies the run flat: 2 store instructions per image and strip instead of 7.
-template <int KS, int GI, bool RQ = false>
+// RES: fused residual block end, as in conv_pwr_kernel: each 16-byte piece of the fp32 run is added to the identity piece
+// at the same position, put through the ReLU and stored as fp32 (unless out is NULL) and, with RQ, as one dword of codes.
+template <int KS, int GI, bool RQ = false, bool RES = false>
 __global__ __launch_bounds__(512, 2) void conv_pwr7_kernel(const PwrArgs a)
 {
+    constexpr bool RQT = RQ && !RES;                          // the byte-run re-quantising epilogue
     using G = Pwr7Geom<KS, GI>;
     constexpr int WAVES = 8, NT = G::NT, PXW = G::PXW, NRB = G::NRB, P = 49;
     static_assert(G::XINSTR % WAVES == 0, "every wave issues the same number of tile pieces");
@@ -666,9 +755,16 @@ __global__ __launch_bounds__(512, 2) void conv_pwr7_kernel(const PwrArgs a)
         rqc.chk = __builtin_amdgcn_readfirstlane(rqc.chk);
         rq_fast_u = rq_fast_ok(rqc);
     }
+    // RES: the 392 pieces of an image's run, lanes past the last one clamped to it (see res_load)
+    uint32_t rs_off[RES ? NRB : 1];
+    if constexpr (RES) {
+#pragma unroll
+        for (int k = 0; k < NRB; ++k) rs_off[k] = 4u * (uint32_t)((64 * k + lane) < 392 ? 64 * k + lane : 391);
+    }
     auto epilogue = [&](int strip, float e_sw, float e_zw, float e_bi, bool need_sx) __attribute__((always_inline)) {
         const int oc0 = strip * 32;
         bool fast = false;
+        ResBlock<RQ, RES ? NRB : 1> pend;                                  // RES: the previous image's run, stores pending
         {
             const float zwp = e_zw - zw_shift;
             const int sw_sum = swacc + __shfl_xor(swacc, 32);
@@ -679,9 +775,10 @@ __global__ __launch_bounds__(512, 2) void conv_pwr7_kernel(const PwrArgs a)
                 tab[64 + col] = e_bi;
                 tab[96 + col] = zwp;
             }
-            if constexpr (RQ) fast = rq_fast_u && __builtin_amdgcn_ballot_w64(!rq_bounded(sx * e_sw, cst, e_bi, zwp)) == 0ull;
+            if constexpr (RQT) fast = rq_fast_u && __builtin_amdgcn_ballot_w64(!rq_bounded(sx * e_sw, cst, e_bi, zwp)) == 0ull;
         }
-        if constexpr (RQ) {
+        (void)fast;
+        if constexpr (RQT) {
             uint8_t *bp = reinterpret_cast<uint8_t *>(patch);                  // [32][49] codes of one image, as in memory
 #pragma unroll
             for (int gi = 0; gi < GI; ++gi) {
@@ -769,6 +866,17 @@ __global__ __launch_bounds__(512, 2) void conv_pwr7_kernel(const PwrArgs a)
                 }
             }
             // the run of image n0 + gi: 32 rows x 49 floats = 392 16-byte pieces, copied flat (NRB stores, the last one 8 lanes wide)
+            if constexpr (RES) {
+                const int64_t e_g = ((int64_t)(n0 + gi) * a.OC + oc0) * P;
+                float4 id[NRB];
+                res_load(a, e_g, rs_off, id);
+                if (gi > 0) res_flush(a, pend, rs_off);                            // behind this run's identity requests
+#pragma unroll
+                for (int k = 0; k < NRB; ++k)
+                    res_make<RQ>(rqc, *reinterpret_cast<const float4 *>(patch + rs_off[k]), id[k], pend.v[k], pend.pk[RQ ? k : 0], bad);
+                pend.e = e_g;
+                continue;
+            }
             float *dst = a.out + ((int64_t)(n0 + gi) * a.OC + oc0) * P;
 #pragma unroll
             for (int k = 0; k < NRB; ++k) {
@@ -776,6 +884,7 @@ __global__ __launch_bounds__(512, 2) void conv_pwr7_kernel(const PwrArgs a)
                 if (64 * k + 64 <= 392 || 64 * k + lane < 392) *reinterpret_cast<float4 *>(dst + 4 * (64 * k + lane)) = o4;
             }
         }
+        if constexpr (RES) res_flush(a, pend, rs_off);
     };
 
     bool sx_cur = __builtin_amdgcn_ballot_w64((c_zw - zw_shift) != 0.0f) != 0ull;
@@ -784,7 +893,7 @@ __global__ __launch_bounds__(512, 2) void conv_pwr7_kernel(const PwrArgs a)
         const float e_sw = c_sw, e_zw = c_zw, e_bi = c_bi;
         load_w(strip0 + (s + 1) * WAVES);
         epilogue(strip0 + s * WAVES, e_sw, e_zw, e_bi, sx_cur);
-        QE_PWR7_WAIT((RQ ? 2 : NRB) * GI);                    // the strip's stores stay in flight
+        QE_PWR7_WAIT(RES ? 63 : (RQ ? 2 : NRB) * GI);         // the strip's stores stay in flight (RES: see conv_pwr_kernel)
         sx_cur = __builtin_amdgcn_ballot_w64((c_zw - zw_shift) != 0.0f) != 0ull;
         if (sx_cur) mma_strip(std::true_type{}); else mma_strip(std::false_type{});
     }
@@ -875,17 +984,31 @@ bool pwr_eligible(const qe_conv_shape *sh, const qe_qparam *x, const qe_qparam *
     return pwr_plan(sh, x, w, &pl) || pwr7_plan(sh, x, w, &g) != 0;
 }
 
+// residual block end (qe_quantconv2d_residual_prepared): stride-1 layers of either kernel; rq: 8-bit codes, one scale
+bool pwr_residual_eligible(const qe_conv_shape *sh, const qe_qparam *x, const qe_qparam *w, int rq_bits, int rq_n_param)
+{
+    if (rq_bits != 0 && (rq_bits != 8 || rq_n_param != 1)) return false;
+    if (sh->stride != 1) return false;
+    PwrPlan pl;
+    int g;
+    // 7x7 planes: the 512-channel form only (512 -> 2048, the last stage's block end); the 4-image-tile instances spill
+    // with the residual epilogue's registers on top (RQ + RES: 16 bytes of scratch)
+    return pwr_plan(sh, x, w, &pl) || (sh->IC == 512 && pwr7_plan(sh, x, w, &g) != 0);
+}
+
 static int launch_pwr7(const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *sh, float *out, hipStream_t s,
-                       const RequantHost *rq)
+                       const RequantHost *rq, const float *res)
 {
     int groups = 1;
     const int gi = pwr7_plan(sh, x, w, &groups);
-    if (gi == 0 || (rq == nullptr && (reinterpret_cast<uintptr_t>(out) & 15) != 0)) return QE_ERR_UNSUPPORTED;
+    if (res != nullptr && sh->IC != 512) return QE_ERR_UNSUPPORTED;
+    if (gi == 0 || ((rq == nullptr || res != nullptr) && (reinterpret_cast<uintptr_t>(out) & 15) != 0)) return QE_ERR_UNSUPPORTED;
     PwrArgs a;
+    a.res = res;
     a.rq_out = nullptr; a.rq_scale = nullptr; a.rq_zero = nullptr; a.rq_status = nullptr;
     a.rq_qmin = a.rq_qmax = a.rq_lo = a.rq_hi = 0.0f; a.rq_offset = 0;
     if (rq != nullptr) {
-        if (!pwr_eligible(sh, x, w, rq)) return QE_ERR_UNSUPPORTED;
+        if (res == nullptr && !pwr_eligible(sh, x, w, rq)) return QE_ERR_UNSUPPORTED;
         a.rq_out = rq->out; a.rq_scale = rq->scale; a.rq_zero = rq->zero;
         a.rq_qmin = rq->qmin; a.rq_qmax = rq->qmax; a.rq_status = rq->status;
         a.rq_offset = rq->sign ? 128u : 0u;                       // tpack.cu:108-111
@@ -906,33 +1029,40 @@ static int launch_pwr7(const qe_qparam *x, const qe_qparam *w, const float *bias
     const int64_t runs = ((int64_t)a.n_pix_tiles + a.chunk - 1) / a.chunk;
     const int64_t blocks = (runs + 7) / 8 * a.chunk * 8 * a.n_groups;
     if (blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
-#define QE_PWR7_LAUNCH2(KSV, GIV, RQV)                                                                                      \
+#define QE_PWR7_LAUNCH3(KSV, GIV, RQV, RESV)                                                                                \
     do {                                                                                                                    \
-        static const bool ok_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_pwr7_kernel<KSV, GIV, RQV>),      \
+        static const bool ok_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_pwr7_kernel<KSV, GIV, RQV, RESV>), \
                                                     hipFuncAttributeMaxDynamicSharedMemorySize, Pwr7Geom<KSV, GIV>::LDS) == hipSuccess; \
         (void)ok_;                                                                                                          \
         constexpr size_t lds_ = Pwr7Geom<KSV, GIV>::LDS;                                                                    \
-        hipLaunchKernelGGL((conv_pwr7_kernel<KSV, GIV, RQV>), dim3((unsigned)blocks), dim3(512), lds_, s, a);               \
+        hipLaunchKernelGGL((conv_pwr7_kernel<KSV, GIV, RQV, RESV>), dim3((unsigned)blocks), dim3(512), lds_, s, a);         \
     } while (0)
+#define QE_PWR7_LAUNCH2(KSV, GIV, RQV) QE_PWR7_LAUNCH3(KSV, GIV, RQV, false)
 #define QE_PWR7_LAUNCH(KSV, GIV) do { if (rq != nullptr) QE_PWR7_LAUNCH2(KSV, GIV, true); else QE_PWR7_LAUNCH2(KSV, GIV, false); } while (0)
-    if (sh->IC == 512) QE_PWR7_LAUNCH(16, 2); else if (sh->IC == 256) QE_PWR7_LAUNCH(8, 4); else QE_PWR7_LAUNCH(4, 4);
+    if (res != nullptr) {
+        if (rq != nullptr) QE_PWR7_LAUNCH3(16, 2, true, true); else QE_PWR7_LAUNCH3(16, 2, false, true);
+    } else if (sh->IC == 512) QE_PWR7_LAUNCH(16, 2); else if (sh->IC == 256) QE_PWR7_LAUNCH(8, 4); else QE_PWR7_LAUNCH(4, 4);
 #undef QE_PWR7_LAUNCH
 #undef QE_PWR7_LAUNCH2
+#undef QE_PWR7_LAUNCH3
     QE_LAUNCH_CHECK();
     return QE_OK;
 }
 
+// res != nullptr: the residual block end (RES instances, stride 1 only): out (may be NULL when rq) = relu(y + res)
 int launch_pwr(const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *sh, float *out, hipStream_t s,
-               const RequantHost *rq)
+               const RequantHost *rq, const float *res)
 {
-    if (sh->H * sh->W == 49) return launch_pwr7(x, w, bias, sh, out, s, rq);
+    if (sh->H * sh->W == 49) return launch_pwr7(x, w, bias, sh, out, s, rq, res);
     PwrPlan pl;
     if (!pwr_plan(sh, x, w, &pl)) return QE_ERR_UNSUPPORTED;
+    if (res != nullptr && pl.s2) return QE_ERR_UNSUPPORTED;
     PwrArgs a;
+    a.res = res;
     a.rq_out = nullptr; a.rq_scale = nullptr; a.rq_zero = nullptr; a.rq_status = nullptr;
     a.rq_qmin = a.rq_qmax = a.rq_lo = a.rq_hi = 0.0f; a.rq_offset = 0;
     if (rq != nullptr) {
-        if (!pwr_eligible(sh, x, w, rq)) return QE_ERR_UNSUPPORTED;
+        if (res == nullptr && !pwr_eligible(sh, x, w, rq)) return QE_ERR_UNSUPPORTED;
         a.rq_out = rq->out; a.rq_scale = rq->scale; a.rq_zero = rq->zero;
         a.rq_qmin = rq->qmin; a.rq_qmax = rq->qmax; a.rq_status = rq->status;
         a.rq_offset = rq->sign ? 128u : 0u;                       // tpack.cu:108-111
@@ -968,7 +1098,19 @@ int launch_pwr(const qe_qparam *x, const qe_qparam *w, const float *bias, const 
         hipLaunchKernelGGL((conv_pwr_kernel<7, WV, KSV, TWV, S2V, RQV>), dim3((unsigned)blocks), dim3(64 * WV), lds_, s, a); \
     } while (0)
 #define QE_PWR_LAUNCH1(WV, KSV, TWV, S2V) do { if (rq != nullptr) QE_PWR_LAUNCH2(WV, KSV, TWV, S2V, true); else QE_PWR_LAUNCH2(WV, KSV, TWV, S2V, false); } while (0)
-#define QE_PWR_LAUNCH(WV, KSV, TWV) do { if (pl.s2) QE_PWR_LAUNCH1(WV, KSV, TWV, true); else QE_PWR_LAUNCH1(WV, KSV, TWV, false); } while (0)
+#define QE_PWR_LAUNCHR(WV, KSV, TWV, RQV)                                                                                   \
+    do {                                                                                                                    \
+        static const bool ok_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_pwr_kernel<7, WV, KSV, TWV, false, RQV, true>), \
+                                                    hipFuncAttributeMaxDynamicSharedMemorySize, PwrGeom<7, WV, KSV, TWV>::LDS) == hipSuccess; \
+        (void)ok_;                                                                                                          \
+        constexpr size_t lds_ = PwrGeom<7, WV, KSV, TWV>::LDS;                                                              \
+        hipLaunchKernelGGL((conv_pwr_kernel<7, WV, KSV, TWV, false, RQV, true>), dim3((unsigned)blocks), dim3(64 * WV), lds_, s, a); \
+    } while (0)
+#define QE_PWR_LAUNCH(WV, KSV, TWV)                                                                                         \
+    do {                                                                                                                    \
+        if (res != nullptr) { if (rq != nullptr) QE_PWR_LAUNCHR(WV, KSV, TWV, true); else QE_PWR_LAUNCHR(WV, KSV, TWV, false); } \
+        else if (pl.s2) QE_PWR_LAUNCH1(WV, KSV, TWV, true); else QE_PWR_LAUNCH1(WV, KSV, TWV, false);                      \
+    } while (0)
     if (pl.tw == 224) {
         if (pl.ks == 2) QE_PWR_LAUNCH(4, 2, 224); else if (pl.ks == 4) QE_PWR_LAUNCH(4, 4, 224); else QE_PWR_LAUNCH(8, 8, 224);
     } else {
@@ -976,6 +1118,7 @@ int launch_pwr(const qe_qparam *x, const qe_qparam *w, const float *bias, const 
     }
 #undef QE_PWR_LAUNCH1
 #undef QE_PWR_LAUNCH2
+#undef QE_PWR_LAUNCHR
 #undef QE_PWR_LAUNCH
     QE_LAUNCH_CHECK();
     return QE_OK;

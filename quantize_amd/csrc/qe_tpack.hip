@@ -354,6 +354,100 @@ extern "C" int qe_quantize_pack(const float *x, int64_t n, const float *scale, c
 }
 
 namespace qe {
+// ---------------------------------------------------------------------------------------------
+// Residual block end, second pass (qe_quantconv2d_residual_prepared, path 0): out = relu(y + identity) in fp32 and the
+// consumer's codes of out, in ONE pass over y and identity.  A thread owns a group of 8 consecutive elements: two 16-byte
+// loads of each input, two 16-byte stores of out, and the group's 8 b-bit codes are exactly b whole bytes of the packed
+// stream (element i occupies bits [i b, (i + 1) b)).  The codes are tp_quantize + tp_code, i.e. quantize_pack's own
+// arithmetic: bit-identical to qe_quantize_pack(out, ...).
+// ---------------------------------------------------------------------------------------------
+struct ResEw {
+    const float *y, *identity;
+    float *out;                  // may be NULL (codes only)
+    uint8_t *codes;              // may be NULL (fp32 only)
+    int32_t *status;
+    int64_t n;
+    TpQuant q;                   // n_ch == 1: per tensor
+    float lo, hi;
+    unsigned offset, mask;
+    int n_bits, vec;             // vec: y, identity and out are 16-byte aligned
+};
+
+__global__ __launch_bounds__(256) void residual_relu_quant_kernel(const ResEw a)
+{
+    const int64_t n_groups = (a.n + 7) / 8;
+    bool bad = false;
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n_groups; g += (int64_t)gridDim.x * 256) {
+        const int64_t e0 = 8 * g;
+        const int cnt = (a.n - e0) < 8 ? (int)(a.n - e0) : 8;
+        float v[8];
+        if (a.vec && cnt == 8) {
+            const float4 y0 = *reinterpret_cast<const float4 *>(a.y + e0), y1 = *reinterpret_cast<const float4 *>(a.y + e0 + 4);
+            const float4 i0 = *reinterpret_cast<const float4 *>(a.identity + e0), i1 = *reinterpret_cast<const float4 *>(a.identity + e0 + 4);
+            v[0] = y0.x + i0.x; v[1] = y0.y + i0.y; v[2] = y0.z + i0.z; v[3] = y0.w + i0.w;
+            v[4] = y1.x + i1.x; v[5] = y1.y + i1.y; v[6] = y1.z + i1.z; v[7] = y1.w + i1.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = j < cnt ? a.y[e0 + j] + a.identity[e0 + j] : 0.0f;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (v[j] > 0.0f || v[j] != v[j]) ? v[j] : 0.0f;   // torch.relu: NaN passes
+        if (a.out != nullptr) {
+            if (a.vec && cnt == 8) {
+                *reinterpret_cast<float4 *>(a.out + e0) = make_float4(v[0], v[1], v[2], v[3]);
+                *reinterpret_cast<float4 *>(a.out + e0 + 4) = make_float4(v[4], v[5], v[6], v[7]);
+            } else {
+                for (int j = 0; j < cnt; ++j) a.out[e0 + j] = v[j];
+            }
+        }
+        if (a.codes == nullptr) continue;
+        uint64_t bits = 0;
+        for (int j = 0; j < cnt; ++j) {
+            const float sc = a.q.n_ch == 1 ? a.q.scale[0] : a.q.scale[((e0 + j) / a.q.inner) % a.q.n_ch];
+            const float zr = a.q.n_ch == 1 ? a.q.zero[0] : a.q.zero[((e0 + j) / a.q.inner) % a.q.n_ch];
+            bits |= (uint64_t)tp_code<float>(tp_quantize(v[j], sc, zr, a.q.qmin, a.q.qmax), a.lo, a.hi, a.offset, a.mask, bad)
+                    << (j * a.n_bits);
+        }
+        uint8_t *dst = a.codes + g * a.n_bits;
+        const int nb = (cnt * a.n_bits + 7) / 8;                 // the last group: the stream ends inside it
+        if (a.n_bits == 8 && cnt == 8 && (reinterpret_cast<uintptr_t>(dst) & 7) == 0) *reinterpret_cast<uint64_t *>(dst) = bits;
+        else for (int k = 0; k < nb; ++k) dst[k] = (uint8_t)(bits >> (8 * k));
+    }
+    if (__builtin_amdgcn_ballot_w64(bad) != 0 && (threadIdx.x & 63) == 0 && a.status != nullptr) atomicOr(a.status, 1);
+}
+
+// y + identity -> out (nullable) and the codes of rq (nullable: fp32 only).  inner: elements per channel plane.
+int launch_residual_relu_quant(const float *y, const float *identity, float *out, int64_t n, int64_t inner, const qe_requant *rq,
+                               uint8_t *codes, int32_t *status, hipStream_t s)
+{
+    if (n <= 0) return QE_OK;
+    ResEw a;
+    a.y = y; a.identity = identity; a.out = out; a.codes = rq != nullptr ? codes : nullptr; a.status = status; a.n = n;
+    a.q = TpQuant{nullptr, nullptr, 0.0f, 0.0f, 1u, 1u};
+    a.lo = a.hi = 0.0f; a.offset = a.mask = 0u; a.n_bits = 8;
+    if (rq != nullptr) {
+        a.q = TpQuant{rq->scale, rq->zero, rq->qmin, rq->qmax, 1u, (uint32_t)rq->n_param};
+        if (rq->n_param > 1) {
+            if (inner < 1 || inner >= (1ll << 31)) return QE_ERR_ARG;
+            a.q.inner = (uint32_t)inner;
+        }
+        a.n_bits = rq->n_bits;
+        a.offset = rq->sign ? (1u << (rq->n_bits - 1)) : 0u;     // as launch_tpack_t
+        a.mask = (1u << rq->n_bits) - 1u;
+        a.lo = rq->sign ? -(float)(1 << (rq->n_bits - 1)) : 0.0f;
+        a.hi = rq->sign ? (float)((1 << (rq->n_bits - 1)) - 1) : (float)((1 << rq->n_bits) - 1);
+    }
+    a.vec = ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(identity) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+    const int64_t groups = (n + 7) / 8;
+    const int64_t want = (groups + 255) / 256;
+    const int blocks = (int)(want < TP_MAX_BLOCKS * 4 ? want : TP_MAX_BLOCKS * 4);
+    hipLaunchKernelGGL(residual_relu_quant_kernel, dim3(blocks), dim3(256), 0, s, a);
+    QE_LAUNCH_CHECK();
+    return QE_OK;
+}
+}  // namespace qe
+
+namespace qe {
 // Sub-8-bit packed stream -> one byte per element holding the SIGNED 8-bit stored code q + 128 (what tpack(q, 8, true)
 // would have produced).  The conv front end uses it to run b < 8 activations on the 8-bit MFMA kernels.  Same kernel
 // as tunpack: it computes (code - offset) mod 256, and q + 128 == code - offset + 128 == code - (offset + 128) mod 256.
