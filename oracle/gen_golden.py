@@ -577,10 +577,220 @@ def gen_g7():
     np.savez_compressed(os.path.join(OUT, "g7_mha_module.npz"), **out)
 
 
+# --------------------------------------------------------------------------------------
+# G8: a whole packed ResNet from the reference's own modules.  torchvision is absent, so the generator defines the
+# torchvision layout itself (conv1 / bn1 / relu / maxpool, layerS.B.{conv1, bn1, ..., downsample.0, downsample.1},
+# avgpool, fc), replaces every conv + BatchNorm pair with QuantConv2d(bn_folding=...) and the fc with QuantLinear (as
+# modelzoo/reconstruct.py does), calibrates and packs.  The whole model's state_dict then gets exact-grid values --
+# power-of-two scales, weight codes clipped to the 2^24 budget and re-packed by the reference packer, biases on their grids
+# (tests/resnet_exact.py) -- and is loaded into a fresh model (the reference's own tunpack).  Its packed forward runs on
+# the CPU with every layer's fp32 result asserted equal to float64; the state_dict, images, layer4 features and logits
+# are stored.  Width 8 at 64 x 64: the final 2 x 2 average pooling is exact too.
+class _G8Bottleneck(torch.nn.Module):
+    expansion = 4
+
+    def __init__(self, inplanes, planes, stride, downsample):
+        super().__init__()
+        nn = torch.nn
+        self.conv1, self.bn1 = nn.Conv2d(inplanes, planes, 1, bias=False), nn.BatchNorm2d(planes)
+        self.conv2, self.bn2 = nn.Conv2d(planes, planes, 3, stride, 1, bias=False), nn.BatchNorm2d(planes)
+        self.conv3, self.bn3 = nn.Conv2d(planes, planes * 4, 1, bias=False), nn.BatchNorm2d(planes * 4)
+        self.relu, self.downsample = nn.ReLU(inplace=True), downsample
+
+    def forward(self, x):
+        identity = x
+        out = self.relu(self.bn1(self.conv1(x)))
+        out = self.relu(self.bn2(self.conv2(out)))
+        out = self.bn3(self.conv3(out))
+        if self.downsample is not None:
+            identity = self.downsample(x)
+        return self.relu(out + identity)
+
+
+class _G8BasicBlock(torch.nn.Module):
+    expansion = 1
+
+    def __init__(self, inplanes, planes, stride, downsample):
+        super().__init__()
+        nn = torch.nn
+        self.conv1, self.bn1 = nn.Conv2d(inplanes, planes, 3, stride, 1, bias=False), nn.BatchNorm2d(planes)
+        self.conv2, self.bn2 = nn.Conv2d(planes, planes, 3, 1, 1, bias=False), nn.BatchNorm2d(planes)
+        self.relu, self.downsample = nn.ReLU(inplace=True), downsample
+
+    def forward(self, x):
+        identity = x
+        out = self.relu(self.bn1(self.conv1(x)))
+        out = self.bn2(self.conv2(out))
+        if self.downsample is not None:
+            identity = self.downsample(x)
+        return self.relu(out + identity)
+
+
+class _G8ResNet(torch.nn.Module):
+    def __init__(self, block, layers, width, num_classes):
+        super().__init__()
+        nn = torch.nn
+        self.conv1, self.bn1 = nn.Conv2d(3, width, 7, 2, 3, bias=False), nn.BatchNorm2d(width)
+        self.relu, self.maxpool = nn.ReLU(inplace=True), nn.MaxPool2d(3, 2, 1)
+        inplanes = width
+        for S, nb in enumerate(layers, start=1):
+            planes, stride = width << (S - 1), (1 if S == 1 else 2)
+            blocks = []
+            for B in range(nb):
+                s = stride if B == 0 else 1
+                ds = None
+                if B == 0 and (s != 1 or inplanes != planes * block.expansion):
+                    ds = nn.Sequential(nn.Conv2d(inplanes, planes * block.expansion, 1, s, bias=False),
+                                       nn.BatchNorm2d(planes * block.expansion))
+                blocks.append(block(inplanes, planes, s, ds))
+                inplanes = planes * block.expansion
+            setattr(self, "layer%d" % S, nn.Sequential(*blocks))
+        self.avgpool, self.fc = nn.AdaptiveAvgPool2d(1), nn.Linear(inplanes, num_classes)
+        for m in self.modules():           # BatchNorm statistics a trained network could have
+            if isinstance(m, nn.BatchNorm2d):
+                m.weight.data.uniform_(0.5, 1.5)
+                m.bias.data.normal_(0, 0.1)
+                m.running_mean.normal_(0, 0.1)
+                m.running_var.uniform_(0.5, 1.5)
+
+    def features(self, x):
+        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        for S in range(1, 5):
+            x = getattr(self, "layer%d" % S)(x)
+        return x
+
+    def forward(self, x):
+        self.feat = self.features(x)
+        return self.fc(torch.flatten(self.avgpool(self.feat), 1))
+
+
+def _g8_quantize(model, mm):
+    """Every conv + BatchNorm pair -> QuantConv2d(bn_folding=...) (BatchNorm -> Identity), the fc -> QuantLinear."""
+    nn = torch.nn
+    w_set = dict(n_bits=8, symmetric=True, signed=True, granularity="channel", range={"name": "minmax"})
+    a_unsigned = dict(n_bits=8, symmetric=True, signed=False, granularity="layer", range={"name": "minmax"})
+    a_signed = dict(n_bits=8, symmetric=True, signed=True, granularity="layer", range={"name": "minmax"})
+
+    def fold(parent, cname, bname, a_set):
+        conv, bn = getattr(parent, cname), getattr(parent, bname)
+        q = mm.QuantConv2d(conv.in_channels, conv.out_channels, conv.kernel_size, stride=conv.stride, padding=conv.padding,
+                           w_setting=dict(w_set), a_setting=dict(a_set),
+                           bn_folding={"running_mean": bn.running_mean.clone(), "running_var": bn.running_var.clone(),
+                                       "weight": bn.weight.detach().clone(), "bias": bn.bias.detach().clone(),
+                                       "eps": torch.tensor(bn.eps)},
+                           _parameters={"weight": conv.weight.detach().clone(), "bias": None})
+        setattr(parent, cname, q)
+        setattr(parent, bname, nn.Identity())
+
+    fold(model, "conv1", "bn1", a_signed)
+    for S in range(1, 5):
+        for blk in getattr(model, "layer%d" % S):
+            for i in (1, 2, 3):
+                if hasattr(blk, "conv%d" % i):
+                    fold(blk, "conv%d" % i, "bn%d" % i, a_unsigned)
+            if blk.downsample is not None:
+                fold(blk.downsample, "0", "1", a_unsigned)
+    fc = model.fc
+    model.fc = mm.QuantLinear(fc.in_features, fc.out_features, w_setting=dict(w_set), a_setting=dict(a_unsigned),
+                              _parameters={"weight": fc.weight.detach().clone(), "bias": fc.bias.detach().clone()})
+    return model
+
+
+def _g8_set_quant(model, mm, on):
+    for mod in model.modules():
+        if isinstance(mod, mm.Quantizer):
+            mod.quant(on)
+
+
+def gen_g8():
+    import copy
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import resnet_exact as rx
+    mm = import_ref_modules()
+    out, index = {}, []
+    torch.manual_seed(23)
+    for name, block, layers in (("bottleneck", _G8Bottleneck, [2, 1, 1, 1]), ("basic", _G8BasicBlock, [2, 1, 1, 1])):
+        fmodel = _G8ResNet(block, layers, 8, 10).eval()
+        images = torch.randn(2, 3, 64, 64)
+        with torch.no_grad():
+            m = _g8_quantize(copy.deepcopy(fmodel), mm).eval()
+            for mod in m.modules():
+                if isinstance(mod, (mm.QuantConv2d, mm.QuantLinear)):
+                    mod.calibrating = True
+            m(images)
+            for mod in m.modules():
+                if isinstance(mod, (mm.QuantConv2d, mm.QuantLinear)):
+                    mod.calibrating = False
+                    mod.pack()
+            sd = {k: v.clone() for k, v in m.state_dict().items()}
+            # exact-grid values: codes clipped to the 2^24 budget (re-packed by the reference packer), power-of-two
+            # weight scales; then activation scales by max on the float64 model and biases snapped to their grids
+            for k in [k for k in sd if k.endswith(".w_des")]:
+                p = k[:-len("w_des")]
+                des = sd[k].numpy()
+                K = int(np.prod(des[3:]))
+                a_qmin, a_qmax = float(sd[p + "a_quantizer.qmin"]), float(sd[p + "a_quantizer.qmax"])
+                cap = rx.weight_cap(K, int(max(abs(a_qmin), abs(a_qmax))), int(des[0]))
+                codes = ref_unpack(sd[p + "weight"].numpy(), des).astype(np.float32)
+                codes = np.clip(codes, -cap, cap)
+                sd[p + "weight"] = torch.from_numpy(ref_pack(codes, int(des[0]), bool(des[1]))[0])
+                ws = sd[p + "w_scale"]
+                sd[p + "w_scale"] = torch.exp2(torch.round(torch.log2(ws.abs()))) * torch.sign(ws)
+                assert bool((sd[p + "w_zero"] == 0).all())
+            f64 = rx.Float64ResNet(sd)
+            f64.forward(images, calibrate={})
+            f64.write_back(sd)
+            ref = rx.Float64ResNet(sd).forward(images)
+            m2 = _g8_quantize(copy.deepcopy(fmodel), mm).eval()
+            m2.load_state_dict(sd)               # QuantConv2d / QuantLinear._load_from_state_dict -> tunpack
+            _g8_set_quant(m2, mm, True)
+            checked = []
+
+            def hook(mod, inp, outp):
+                # this layer's fp32 result against float64 on the same input
+                x = inp[0].double()
+                qz = mod.a_quantizer
+                s, z = qz.scale.double().reshape(-1), qz.zero.double().reshape(-1)
+                assert s.numel() == 1 and z.numel() == 1
+                s, z = s[0], z[0]
+                q = (x / s - z).round().clamp(float(qz.qmin), float(qz.qmax))
+                w = (mod.weight.double() + mod.w_zero.double()) * mod.w_scale.double()
+                xd = (q + z) * s
+                if isinstance(mod, mm.QuantConv2d):
+                    y = F.conv2d(xd, w, mod.bias.double(), mod.stride, mod.padding)
+                else:
+                    y = F.linear(xd, w, mod.bias.double())
+                assert torch.equal(outp.double(), y), "G8 %s: a layer's fp32 result is not exact" % name
+                assert torch.equal(y, y.float().double())
+                checked.append(1)
+            for mod in m2.modules():
+                if isinstance(mod, (mm.QuantConv2d, mm.QuantLinear)):
+                    mod.register_forward_hook(hook)
+            logits = m2(images)
+            feat = m2.feat
+        n_layers = sum(1 for mod in m2.modules() if isinstance(mod, (mm.QuantConv2d, mm.QuantLinear)))
+        assert len(checked) == n_layers
+        assert torch.equal(feat.double(), ref.features) and torch.equal(logits.double(), ref.logits)
+        key = "m_" + name
+        for k, v in sd.items():
+            out[key + "_sd_" + k] = v.numpy()
+        out[key + "_images"] = images.numpy()
+        out[key + "_features"] = feat.numpy()
+        out[key + "_logits"] = logits.numpy()
+        index.append(key)
+        print("G8 %s: %d packed layers, %d state_dict keys, %d exact ties, logits std %.3g" % (
+            name, n_layers, len(sd), ref.ties, float(logits.std())))
+    out["index"] = np.array(index)
+    np.savez_compressed(os.path.join(OUT, "g8_resnet_module.npz"), **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     if "--only-g7" in sys.argv:      # added in round 3: leaves the earlier fixtures byte for byte as committed
         gen_g7()
+        sys.exit(0)
+    if "--only-g8" in sys.argv:      # leaves G1-G7 byte for byte as committed
+        gen_g8()
         sys.exit(0)
     gen_g1()
     gen_g3()
@@ -588,5 +798,6 @@ if __name__ == "__main__":
     gen_g5()
     gen_g6()
     gen_g7()
+    gen_g8()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))

@@ -1,0 +1,57 @@
+"""CPU: the exact-arithmetic ResNet construction and the float64 model, tied to the reference itself.  G8 holds whole
+packed ResNets written by the reference's own modules (calibrate -> pack() -> state_dict, exact-grid values, reloaded
+through the reference's tunpack) with the features and logits of the reference's packed forward: PackedResNet must
+discover and consume every key of them, and Float64ResNet must reproduce the reference's outputs bit for bit."""
+import pytest
+import torch
+
+from quantize_amd.packed_resnet import PackedResNet
+from resnet_exact import Float64ResNet, check_code_spread, exact_state_dict, load_g8, weight_cap
+
+LAYER_KEYS = ("weight", "w_des", "w_scale", "w_zero", "bias", "a_quantizer.scale", "a_quantizer.zero",
+              "a_quantizer.qmin", "a_quantizer.qmax")
+IGNORED = set()          # keys the reference writes that PackedResNet has no use for: none for these modules
+
+
+@pytest.fixture(scope="module")
+def g8():
+    return load_g8()
+
+
+def test_weight_caps():
+    """ResNet-50 at 8 bits: the per-layer weight-code caps that keep K * 255 * cap + bias units below 2^24."""
+    assert [weight_cap(K, 255, 8) for K in (4608, 2304, 1152, 512, 147)] == [14, 28, 57, 127, 127]
+    assert weight_cap(4608, 255, 4) == 7
+
+
+@pytest.mark.parametrize("case,kind,stages", [("m_bottleneck", "bottleneck", [2, 1, 1, 1]), ("m_basic", "basic", [2, 1, 1, 1])])
+def test_g8_discovered_and_every_key_consumed(g8, case, kind, stages):
+    sd = g8[case][0]
+    m = PackedResNet.from_state_dict(sd)
+    assert m.kind == kind and [len(s) for s in m.stages] == stages
+    ds = [b.downsample is not None for b in m.blocks()]
+    assert True in ds and False in ds                         # blocks with and without a downsample
+    consumed = {c.name + "." + k for c in m.convs() for k in LAYER_KEYS} | {"fc." + k for k in LAYER_KEYS}
+    assert set(sd) - IGNORED == consumed
+
+
+@pytest.mark.parametrize("case", ["m_bottleneck", "m_basic"])
+def test_float64_model_reproduces_reference(g8, case):
+    sd, images, feat, logits = g8[case]
+    ref = Float64ResNet(sd).forward(images)
+    assert torch.equal(ref.features, feat.double())
+    assert torch.equal(ref.logits, logits.double())
+    assert not bool(ref.near_tie.any())                       # 2 x 2 pooling: exact
+    assert logits.std() > 0
+
+
+def test_exact_construction_small():
+    """The construction keeps every intermediate exact, meets .5 ties and spreads its codes (a small ResNet-18)."""
+    sd = exact_state_dict("resnet18", seed=5, width=16, num_classes=10, image_size=64)
+    g = torch.Generator().manual_seed(6)
+    ref = Float64ResNet(sd).forward(torch.randn(2, 3, 64, 64, generator=g))
+    check_code_spread(ref)
+    assert ref.ties > 0 and ref.logits.std() > 0
+    for k in [k for k in sd if k.endswith("scale")]:          # every scale a power of two
+        v = sd[k].double()
+        assert torch.equal(torch.exp2(torch.round(torch.log2(v))), v), k
