@@ -1,6 +1,7 @@
 // qe_api.hip -- C-ABI entry points that are not tied to one kernel file:
 // error strings, version, and the conv dispatch (generic fp32 vs int8 MFMA).
 #include "qe_common.h"
+#include "qe_conv_plan.hpp"
 
 #include <atomic>
 #include <cstring>
@@ -63,20 +64,7 @@ const char *env_get(const char *name)
 int launch_conv_generic(bool packed_in, const void *x, const qe_qparam *xq, const qe_qparam *w,
                         const float *bias, const qe_conv_shape *sh, float *out, hipStream_t s);
 
-// qe_conv_mfma.hip
-bool mfma_conv_eligible(const qe_conv_shape *sh, const qe_qparam *x, const qe_qparam *w);
-size_t mfma_conv_workspace_bytes(const qe_conv_shape *sh, int x_bits, int w_bits);
-size_t mfma_conv_prepared_bytes(const qe_conv_shape *sh, int x_bits, int w_bits);
-uint64_t mfma_conv_prepared_layout(const qe_conv_shape *sh, int x_bits, int w_bits);
-int launch_conv_mfma(const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *sh,
-                     float *out, void *workspace, size_t workspace_bytes, hipStream_t s, int mode, void *prepared,
-                     size_t prepared_bytes, const RequantHost *rq = nullptr);
-bool mfma_conv_requant_fused(const qe_conv_shape *sh, const qe_qparam *x, const qe_qparam *w, int rq_bits, int rq_n_param);
-
-// qe_conv_pwr.hip (residual block end) and qe_tpack.hip (its two-pass form)
-bool pwr_residual_eligible(const qe_conv_shape *sh, const qe_qparam *x, const qe_qparam *w, int rq_bits, int rq_n_param);
-int launch_pwr(const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *sh, float *out, hipStream_t s,
-               const RequantHost *rq, const float *res);
+// qe_tpack.hip: the two-pass form of the residual block end
 int launch_residual_relu_quant(const float *y, const float *identity, float *out, int64_t n, int64_t inner, const qe_requant *rq,
                                uint8_t *codes, int32_t *status, hipStream_t s);
 
@@ -141,16 +129,30 @@ extern "C" void qe_debug_reload_env(void)
 extern "C" const char *qe_version(void) { return "quantize_amd 0.1.0"; }
 extern "C" const char *qe_target_arch(void) { return "gfx950"; }
 
+// ---- packed-activation convolutions: every entry point plans once (plan_conv, qe_conv_plan.hip) and reads the plan ----
+namespace qe {
+// a request that names only the operands' bits (workspace queries)
+static ConvPlan plan_bits(const qe_conv_shape *sh, int x_bits, int w_bits)
+{
+    qe_qparam x{}, w{};
+    x.n_bits = x_bits; x.n_param = 1;
+    w.n_bits = w_bits; w.n_param = 1;
+    return plan_conv({sh, &x, &w});
+}
+// scratch of a run on a prepared buffer, rounded up to 256 bytes (the two-pass epilogues put the fp32 y behind it)
+static size_t scratch_bytes(const ConvPlan &p) { return (p.m.total - p.m.prep_total + 255) / 256 * 256; }
+}  // namespace qe
+
 extern "C" size_t qe_quantconv2d_workspace_bytes(const qe_conv_shape *shape, int x_bits, int w_bits)
 {
     if (qe::check_shape(shape) != QE_OK) return 0;
-    return qe::mfma_conv_workspace_bytes(shape, x_bits, w_bits);
+    return qe::plan_bits(shape, x_bits, w_bits).m.total;
 }
 
 extern "C" int qe_quantconv2d_path(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w)
 {
     if (qe::check_shape(shape) != QE_OK || x == nullptr || w == nullptr) return 0;
-    return qe::mfma_conv_eligible(shape, x, w) ? 1 : 0;
+    return qe::plan_conv({shape, x, w}).route != qe::ConvRoute::Generic ? 1 : 0;
 }
 
 extern "C" int qe_quantconv2d(const qe_qparam *x, const qe_qparam *w, const float *bias,
@@ -165,27 +167,28 @@ extern "C" int qe_quantconv2d(const qe_qparam *x, const qe_qparam *w, const floa
     if ((rc = check_nparam(x, w, shape)) != QE_OK) return rc;
     if (out == nullptr) return QE_ERR_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (mfma_conv_eligible(shape, x, w))
-        return launch_conv_mfma(x, w, bias, shape, out, workspace, workspace_bytes, s, 0, nullptr, 0);
-    return launch_conv_generic(true, x->data, x, w, bias, shape, out, s);
+    const ConvPlan p = plan_conv({shape, x, w, reinterpret_cast<uintptr_t>(out)});
+    if (p.route == ConvRoute::Generic) return launch_conv_generic(true, x->data, x, w, bias, shape, out, s);
+    return launch_conv_mfma(p, x, w, bias, shape, out, workspace, workspace_bytes, nullptr, 0, false, s, nullptr, nullptr);
 }
 
 extern "C" size_t qe_conv_prepared_bytes(const qe_conv_shape *shape, int x_bits, int w_bits)
 {
     if (qe::check_shape(shape) != QE_OK) return 0;
-    return qe::mfma_conv_prepared_bytes(shape, x_bits, w_bits);
+    return qe::plan_prepared(shape, x_bits, w_bits).prep_total;
 }
 
 extern "C" uint64_t qe_conv_prepared_layout(const qe_conv_shape *shape, int x_bits, int w_bits)
 {
     if (qe::check_shape(shape) != QE_OK) return 0;
-    return qe::mfma_conv_prepared_layout(shape, x_bits, w_bits);
+    return qe::prepared_layout(qe::plan_prepared(shape, x_bits, w_bits), shape);
 }
 
 extern "C" size_t qe_quantconv2d_prepared_workspace_bytes(const qe_conv_shape *shape, int x_bits, int w_bits)
 {
     if (qe::check_shape(shape) != QE_OK) return 0;
-    return qe::mfma_conv_workspace_bytes(shape, x_bits, w_bits) - qe::mfma_conv_prepared_bytes(shape, x_bits, w_bits);
+    const qe::ConvPlan p = qe::plan_bits(shape, x_bits, w_bits);
+    return p.m.total - p.m.prep_total;
 }
 
 extern "C" int qe_conv_prepare(const qe_qparam *w, const float *bias, const qe_conv_shape *shape, int x_bits,
@@ -197,10 +200,8 @@ extern "C" int qe_conv_prepare(const qe_qparam *w, const float *bias, const qe_c
     if ((rc = check_qparam(w)) != QE_OK) return rc;
     if ((rc = check_nparam(nullptr, w, shape)) != QE_OK) return rc;
     if (!(x_bits > 0 && x_bits <= 8)) return QE_ERR_NBITS;
-    if (mfma_conv_prepared_bytes(shape, x_bits, w->n_bits) == 0) return QE_OK;     // nothing to prepare for this problem
-    qe_qparam x = *w;                      // only n_bits / n_param of the activations select the plan
-    x.n_bits = x_bits; x.n_param = 1;
-    return launch_conv_mfma(&x, w, bias, shape, nullptr, nullptr, 0, static_cast<hipStream_t>(stream), 1, prepared, prepared_bytes);
+    return prepare_conv_tables(plan_prepared(shape, x_bits, w->n_bits), w, bias, shape, prepared, prepared_bytes,
+                               static_cast<hipStream_t>(stream));
 }
 
 extern "C" int qe_quantconv2d_prepared(const qe_qparam *x, const qe_qparam *w, const float *bias,
@@ -215,9 +216,11 @@ extern "C" int qe_quantconv2d_prepared(const qe_qparam *x, const qe_qparam *w, c
     if ((rc = check_nparam(x, w, shape)) != QE_OK) return rc;
     if (out == nullptr) return QE_ERR_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (mfma_conv_eligible(shape, x, w))
-        return launch_conv_mfma(x, w, bias, shape, out, workspace, workspace_bytes, s, 2, const_cast<void *>(prepared), prepared_bytes);
-    return launch_conv_generic(true, x->data, x, w, bias, shape, out, s);   // per-channel activation scales: nothing is prepared
+    const ConvPlan p = plan_conv({shape, x, w, reinterpret_cast<uintptr_t>(out)});
+    if (p.route == ConvRoute::Generic)   // per-channel activation scales: nothing is prepared
+        return launch_conv_generic(true, x->data, x, w, bias, shape, out, s);
+    return launch_conv_mfma(p, x, w, bias, shape, out, workspace, workspace_bytes, prepared, prepared_bytes, true, s, nullptr,
+                            nullptr);
 }
 
 // ---- fused re-quantisation (conv-epilogue form) ----
@@ -228,26 +231,29 @@ static int check_requant(const qe_requant *rq)
     if (rq->n_param < 1) return QE_ERR_ARG;
     return QE_OK;
 }
-static size_t requant_y_bytes(const qe_conv_shape *sh)
+
+static qe::ConvPlan plan_requant(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq,
+                                 const uint8_t *out)
 {
-    const int64_t OH = (sh->H + 2 * sh->padding - sh->KH) / sh->stride + 1, OW = (sh->W + 2 * sh->padding - sh->KW) / sh->stride + 1;
-    if (OH <= 0 || OW <= 0) return 0;
-    return ((size_t)sh->N * sh->OC * OH * OW * sizeof(float) + 255) / 256 * 256;
+    qe::ConvRequest r{shape, x, w};
+    r.rq_out = reinterpret_cast<uintptr_t>(out);
+    r.rq_bits = rq->n_bits;
+    r.rq_n_param = rq->n_param;
+    return qe::plan_conv(r);
 }
 
 extern "C" int qe_quantconv2d_requant_path(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq)
 {
     if (qe::check_shape(shape) != QE_OK || x == nullptr || w == nullptr || rq == nullptr) return 0;
-    if (!qe::mfma_conv_eligible(shape, x, w)) return 0;
-    return qe::mfma_conv_requant_fused(shape, x, w, rq->n_bits, rq->n_param) ? 1 : 0;
+    return plan_requant(shape, x, w, rq, nullptr).fused ? 1 : 0;
 }
 
 extern "C" size_t qe_quantconv2d_requant_workspace_bytes(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w,
                                                          const qe_requant *rq)
 {
     if (qe::check_shape(shape) != QE_OK || x == nullptr || w == nullptr || rq == nullptr) return 0;
-    const size_t conv = (qe_quantconv2d_prepared_workspace_bytes(shape, x->n_bits, w->n_bits) + 255) / 256 * 256;
-    return qe_quantconv2d_requant_path(shape, x, w, rq) ? conv : conv + requant_y_bytes(shape);
+    const qe::ConvPlan p = plan_requant(shape, x, w, rq, nullptr);
+    return p.fused ? qe::scratch_bytes(p) : qe::scratch_bytes(p) + p.y_bytes;
 }
 
 extern "C" int qe_quantconv2d_requant_prepared(const qe_qparam *x, const qe_qparam *w, const float *bias,
@@ -264,42 +270,48 @@ extern "C" int qe_quantconv2d_requant_prepared(const qe_qparam *x, const qe_qpar
     if ((rc = check_requant(rq)) != QE_OK) return rc;
     if (out == nullptr) return QE_ERR_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t OH = (shape->H + 2 * shape->padding - shape->KH) / shape->stride + 1;
-    const int64_t OW = (shape->W + 2 * shape->padding - shape->KW) / shape->stride + 1;
-    if (OH <= 0 || OW <= 0) return QE_ERR_ARG;
+    const ConvPlan p = plan_requant(shape, x, w, rq, out);
+    if (p.OH <= 0 || p.OW <= 0) return QE_ERR_ARG;
     if (shape->N == 0 || shape->OC == 0) return QE_OK;
-    const size_t conv_ws = (qe_quantconv2d_prepared_workspace_bytes(shape, x->n_bits, w->n_bits) + 255) / 256 * 256;
-    if (qe_quantconv2d_requant_path(shape, x, w, rq)) {
+    if (p.fused) {
         const RequantHost rh{out, rq->scale, rq->zero, rq->n_param, rq->qmin, rq->qmax, rq->n_bits, rq->sign, status};
-        rc = launch_conv_mfma(x, w, bias, shape, nullptr, workspace, workspace_bytes, s, 2, const_cast<void *>(prepared),
-                              prepared_bytes, &rh);
-        return rc;   // (a kernel without the epilogue here would contradict qe_quantconv2d_requant_path: surface it)
+        return launch_conv_mfma(p, x, w, bias, shape, nullptr, workspace, workspace_bytes, prepared, prepared_bytes, true, s, &rh,
+                                nullptr);
     }
     // two passes: y in fp32 behind the conv scratch, then the fused quantise + pack kernel (bit-identical by construction)
-    const size_t ybytes = requant_y_bytes(shape);
-    if (workspace == nullptr || workspace_bytes < conv_ws + ybytes) return QE_ERR_WORKSPACE;
+    const size_t conv_ws = scratch_bytes(p);
+    if (workspace == nullptr || workspace_bytes < conv_ws + p.y_bytes) return QE_ERR_WORKSPACE;
     float *y = reinterpret_cast<float *>(static_cast<uint8_t *>(workspace) + conv_ws);
     rc = qe_quantconv2d_prepared(x, w, bias, shape, prepared, prepared_bytes, y, workspace, conv_ws, stream);
     if (rc != QE_OK) return rc;
-    return qe_quantize_pack(y, (int64_t)shape->N * shape->OC * OH * OW, rq->scale, rq->zero, rq->n_param, OH * OW, rq->qmin,
+    const int64_t plane = (int64_t)p.OH * p.OW;
+    return qe_quantize_pack(y, (int64_t)shape->N * shape->OC * plane, rq->scale, rq->zero, rq->n_param, plane, rq->qmin,
                             rq->qmax, rq->n_bits, rq->sign, out, status, stream);
 }
 
 // ---- residual block end: out = relu(conv + identity), optionally with the consumer's codes ----
+static qe::ConvPlan plan_residual(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq,
+                                  const float *out, const uint8_t *codes)
+{
+    qe::ConvRequest r{shape, x, w, reinterpret_cast<uintptr_t>(out), reinterpret_cast<uintptr_t>(codes)};
+    r.rq_bits = rq ? rq->n_bits : 0;
+    r.rq_n_param = rq ? rq->n_param : 1;
+    r.residual = true;
+    return qe::plan_conv(r);
+}
+
 extern "C" int qe_quantconv2d_residual_path(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq)
 {
     if (qe::check_shape(shape) != QE_OK || x == nullptr || w == nullptr) return 0;
-    if (!qe::mfma_conv_eligible(shape, x, w)) return 0;
-    return qe::pwr_residual_eligible(shape, x, w, rq ? rq->n_bits : 0, rq ? rq->n_param : 1) ? 1 : 0;
+    return plan_residual(shape, x, w, rq, nullptr, nullptr).fused ? 1 : 0;
 }
 
 extern "C" size_t qe_quantconv2d_residual_workspace_bytes(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w,
                                                           const qe_requant *rq)
 {
     if (qe::check_shape(shape) != QE_OK || x == nullptr || w == nullptr) return 0;
-    if (qe_quantconv2d_residual_path(shape, x, w, rq)) return 0;      // the conv kernel reads no scratch
-    const size_t conv = (qe_quantconv2d_prepared_workspace_bytes(shape, x->n_bits, w->n_bits) + 255) / 256 * 256;
-    return conv + requant_y_bytes(shape);
+    const qe::ConvPlan p = plan_residual(shape, x, w, rq, nullptr, nullptr);
+    return p.fused ? 0 : qe::scratch_bytes(p) + p.y_bytes;   // the fused kernel reads no scratch
 }
 
 extern "C" int qe_quantconv2d_residual_prepared(const qe_qparam *x, const qe_qparam *w, const float *bias,
@@ -320,10 +332,9 @@ extern "C" int qe_quantconv2d_residual_prepared(const qe_qparam *x, const qe_qpa
     if (((reinterpret_cast<uintptr_t>(identity) | reinterpret_cast<uintptr_t>(out)) & 15) != 0 ||
         (reinterpret_cast<uintptr_t>(codes) & 3) != 0)
         return QE_ERR_ARG;
-    const int64_t OH = (shape->H + 2 * shape->padding - shape->KH) / shape->stride + 1;
-    const int64_t OW = (shape->W + 2 * shape->padding - shape->KW) / shape->stride + 1;
-    if (OH <= 0 || OW <= 0) return QE_ERR_ARG;
-    const int64_t n = (int64_t)shape->N * shape->OC * OH * OW;
+    const ConvPlan p = plan_residual(shape, x, w, rq, out, codes);
+    if (p.OH <= 0 || p.OW <= 0) return QE_ERR_ARG;
+    const int64_t n = (int64_t)shape->N * shape->OC * p.OH * p.OW;
     if (out != nullptr && out != identity) {                 // in place is allowed; any other overlap is not
         const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), i0 = reinterpret_cast<uintptr_t>(identity);
         const uintptr_t bytes = (uintptr_t)n * sizeof(float);
@@ -331,20 +342,19 @@ extern "C" int qe_quantconv2d_residual_prepared(const qe_qparam *x, const qe_qpa
     }
     if (n == 0) return QE_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (qe_quantconv2d_residual_path(shape, x, w, rq)) {
-        if (rq == nullptr) return launch_pwr(x, w, bias, shape, out, s, nullptr, identity);
+    if (p.fused) {
+        if (rq == nullptr) return launch_pwr(p, x, w, bias, out, s, nullptr, identity);
         const RequantHost rh{codes, rq->scale, rq->zero, rq->n_param, rq->qmin, rq->qmax, rq->n_bits, rq->sign, status};
-        return launch_pwr(x, w, bias, shape, out, s, &rh, identity);
+        return launch_pwr(p, x, w, bias, out, s, &rh, identity);
     }
     // two passes: the conv's fp32 y (into out, unless out is NULL or IS the identity: then behind the conv scratch), then
     // one elementwise pass y + identity -> out and codes
-    const size_t conv_ws = (qe_quantconv2d_prepared_workspace_bytes(shape, x->n_bits, w->n_bits) + 255) / 256 * 256;
-    if (workspace_bytes < conv_ws + requant_y_bytes(shape) || (workspace == nullptr && conv_ws + requant_y_bytes(shape) > 0))
-        return QE_ERR_WORKSPACE;
+    const size_t conv_ws = scratch_bytes(p);
+    if (workspace_bytes < conv_ws + p.y_bytes || (workspace == nullptr && conv_ws + p.y_bytes > 0)) return QE_ERR_WORKSPACE;
     float *y = (out != nullptr && out != identity) ? out : reinterpret_cast<float *>(static_cast<uint8_t *>(workspace) + conv_ws);
     rc = qe_quantconv2d_prepared(x, w, bias, shape, prepared, prepared_bytes, y, workspace, conv_ws, stream);
     if (rc != QE_OK) return rc;
-    return launch_residual_relu_quant(y, identity, out, n, OH * OW, rq, codes, status, s);
+    return launch_residual_relu_quant(y, identity, out, n, (int64_t)p.OH * p.OW, rq, codes, status, s);
 }
 
 extern "C" int qe_quantconv2d_float_input(const float *x, const qe_qparam *w, const float *bias,

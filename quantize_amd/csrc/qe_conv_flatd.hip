@@ -26,8 +26,8 @@
 // size is not a multiple of 16: pure-garbage slots fetch the tensor's last 16 bytes instead, and the one slot that is
 // partly valid is left out of the DMA (lane masked off) and written by its thread from a register.
 #include "qe_conv_mfma_kernel.hpp"
+#include "qe_conv_plan.hpp"
 
-#include <cstdlib>
 #include <utility>
 
 namespace qe {
@@ -49,7 +49,6 @@ struct FlatdArgs {
     int32_t *rq_status;
 };
 
-constexpr int FD_CK = 64;              // channels per stage
 constexpr int FD_RING_DEFAULT = 3;      // slots of the ring (RING - 1 stages in flight); 6 = one workgroup per CU with 5 in flight
 // output channels per workgroup = 32 per wave: 4 waves (128 channels, two workgroups per CU) or 8 waves (256 channels, one
 // workgroup per CU: the activations of a pixel tile cross the CU's memory path once per 256 output channels instead of
@@ -507,35 +506,13 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_flatd_kernel(const FlatdAr
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-// tile variant: 0 = none, 5 / 7 = WIDE with that many column tiles, 8 = SMALL
-int flatd_variant(const qe_conv_shape *sh, const qe_qparam *x, const qe_qparam *w)
+// p.route == Flatd: tile variant p.fd_var, 8-wave workgroups when p.fd_w8; rq != nullptr: the re-quantising SMALL instances
+int launch_flatd(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, float *out, hipStream_t s,
+                 const RequantHost *rq)
 {
-    if (sh->KH != 1 || sh->KW != 1 || sh->stride != 1 || sh->padding != 0) return 0;
-    if (x->n_bits != 8 || w->n_bits != 8 || x->n_param != 1) return 0;
-    if (sh->IC % FD_CK != 0 || sh->IC < 2 * FD_CK || sh->OC < 1 || sh->N < 1) return 0;
-    const int64_t P = (int64_t)sh->H * sh->W;
-    if ((int64_t)sh->N * sh->IC * P < 16 || (int64_t)sh->OC * P >= (1ll << 29) || (int64_t)sh->IC * P >= (1ll << 31)) return 0;
-    if ((reinterpret_cast<uintptr_t>(w->data) & 15) != 0) return 0;      // weight rows are fetched as aligned 16-byte pieces
-    if (P == 49 && sh->OC % 4 == 0 && (reinterpret_cast<uintptr_t>(x->data) & 15) == 0) return 8;
-    if ((P % 16 != 0 && P % 16 != 4) || P < 160) return 0;     // a row's last slot holds 16 or 4 valid bytes
-    if ((reinterpret_cast<uintptr_t>(x->data) & 3) != 0) return 0;
-    auto waste = [&](int t) { return (double)((P + 32 * t - 1) / (32 * t)) * (32 * t) / (double)P; };
-    return waste(5) < waste(7) - 0.03 ? 5 : 7;
-}
-
-// rq != nullptr: the re-quantising instances (7x7 planes, whole 32-channel strips: OC % 32 == 0, 8-bit codes, one scale)
-bool flatd_requant_ok(const qe_conv_shape *sh, const qe_qparam *x, const qe_qparam *w, const RequantHost *rq)
-{
-    return rq != nullptr && flatd_variant(sh, x, w) == 8 && sh->OC % 32 == 0 && rq->n_bits == 8 && rq->n_param == 1 && rq->out != nullptr &&
-           (reinterpret_cast<uintptr_t>(rq->out) & 15) == 0 && !(env_get("QE_FLATD_RQ") && atoi(env_get("QE_FLATD_RQ")) == 0);
-}
-
-int launch_flatd(const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *sh, float *out,
-                 hipStream_t s, const RequantHost *rq)
-{
-    const int var = flatd_variant(sh, x, w);
-    if (var == 0) return QE_ERR_UNSUPPORTED;
-    if (rq != nullptr && !flatd_requant_ok(sh, x, w, rq)) return QE_ERR_UNSUPPORTED;
+    const qe_conv_shape *sh = &p.run;
+    const int var = p.fd_var;
+    const bool w8 = p.fd_w8;
     FlatdArgs a;
     a.rq_out = nullptr; a.rq_scale = nullptr; a.rq_zero = nullptr; a.rq_status = nullptr;
     a.rq_qmin = a.rq_qmax = a.rq_lo = a.rq_hi = 0.0f; a.rq_offset = 0;
@@ -549,24 +526,11 @@ int launch_flatd(const qe_qparam *x, const qe_qparam *w, const float *bias, cons
     a.x_scale = x->scale; a.x_zero = x->zero; a.w_scale = w->scale; a.w_zero = w->zero; a.bias = bias;
     a.x_sign = x->sign; a.w_sign = w->sign; a.w_per_tensor = (w->n_param == 1);
     a.out = out; a.N = sh->N; a.IC = sh->IC; a.OC = sh->OC; a.P = sh->H * sh->W;
-    // 8-wave / 256-channel workgroups: measured (profiles/r02l_flatd_w8.txt) -9 % on 512->2048 @7x7, +-3 % on the 14x14
-    // layers, +15 % on 2048->512 @7x7 -- halving the activation re-reads does NOT give the -14..-26 % a bytes-through-the-CU
-    // model predicts.  On for wide 7x7 layers only; QE_FLATD8=0 | 1 overrides.
-    bool w8 = var == 8 && sh->OC >= 1024;
-    if (const char *e8 = env_get("QE_FLATD8")) w8 = atoi(e8) != 0 && sh->OC > 128;
-    const int MT = w8 ? 256 : 128;
-    a.n_oc_tiles = (sh->OC + MT - 1) / MT;
-    if (var == 8) { a.tiles_per_image = 1; a.n_pix_tiles = (sh->N + 3) / 4; }
-    else { a.tiles_per_image = (a.P + 32 * var - 1) / (32 * var); a.n_pix_tiles = sh->N * a.tiles_per_image; }
-    const int64_t per_xcd = ((int64_t)a.n_pix_tiles + 7) / 8;
-    a.chunk = (int)(per_xcd < 1 ? 1 : per_xcd);
-    if (const char *ci = env_get("QE_CHUNK_IMAGES")) {
-        const int64_t k = (int64_t)atoi(ci) * a.tiles_per_image;
-        a.chunk = (int)(k < 1 ? 1 : (k < per_xcd ? k : per_xcd));
-    }
-    const int64_t runs = ((int64_t)a.n_pix_tiles + a.chunk - 1) / a.chunk;
-    const int64_t blocks = (runs + 7) / 8 * a.chunk * 8 * a.n_oc_tiles;
-    if (blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
+    a.n_oc_tiles = p.n_oc_tiles;
+    a.tiles_per_image = p.tiles_h;
+    a.n_pix_tiles = p.n_pix_tiles;
+    a.chunk = p.chunk;
+    const int64_t blocks = p.blocks;
     // ring depth 3 = two stages in flight, two workgroups per CU.  A 6-slot ring (one workgroup per CU, five stages in flight)
     // was 25-60 % slower on every layer (profiles/r02i_flatd_ring.txt): the K loop is not bound by prefetch depth.
 #define QE_FD_LAUNCH(NTV, SM, RG, WV)                                                                                      \

@@ -2277,6 +2277,15 @@ __global__ __launch_bounds__(MF_THREADS, 2) void conv_mfma_flatg_kernel(const Mf
     }
 }
 
+// Which re-quantising lane = pixel kernels have a PATCH instance (codes through the workgroup's LDS byte patch): the halo
+// kernel <WM 4, NIW 7, KK 9, 8-bit, NS 1>, the stem kernels with NIW 7 and every sm2 kernel.  The planner sets rq_patch only
+// where this holds; the launchers instantiate PATCH from it.
+enum class MfKind { Halo, Stem, Sm2 };
+constexpr bool mfma_has_patch(MfKind k, int wm, int niw, int kkt, bool x8, int ns)
+{
+    return k == MfKind::Sm2 || (k == MfKind::Stem && niw == 7) || (k == MfKind::Halo && wm == 4 && niw == 7 && kkt == 9 && x8 && ns == 1);
+}
+
 // launchers, one translation unit per wave layout (qe_conv_mfma_i*.hip)
 void launch_mfma_cfg0(const MfmaArgs &a, int niw, int ns, int KK, bool x8, unsigned blocks, size_t lds, hipStream_t s);
 void launch_mfma_cfg1(const MfmaArgs &a, int niw, int ns, int KK, bool x8, unsigned blocks, size_t lds, hipStream_t s);
@@ -2290,8 +2299,9 @@ void launch_mfma_flat_x4(const MfmaArgs &a, int niw, int ns, unsigned blocks, si
 
 #define QE_MFMA_K(WM, WN, NIW, KKT, X8, NS)                                                                                     \
     do {                                                                                                                        \
-        if (a.rq_out != nullptr && a.rq_patch && (WM) == 4 && (NIW) == 7 && (KKT) == 9 && (X8) && (NS) == 1)                    \
-            hipLaunchKernelGGL((conv_mfma_kernel<WM, WN, NIW, KKT, X8, NS, true, (WM) == 4 && (NIW) == 7 && (KKT) == 9 && (X8) && (NS) == 1>), dim3(blocks), dim3(MF_THREADS), lds, s, a); \
+        constexpr bool patch_ = mfma_has_patch(MfKind::Halo, WM, NIW, KKT, X8, NS);                                          \
+        if (a.rq_out != nullptr && a.rq_patch)                                                                                  \
+            hipLaunchKernelGGL((conv_mfma_kernel<WM, WN, NIW, KKT, X8, NS, true, patch_>), dim3(blocks), dim3(MF_THREADS), lds, s, a); \
         else if (a.rq_out != nullptr)                                                                                           \
             hipLaunchKernelGGL((conv_mfma_kernel<WM, WN, NIW, KKT, X8, NS, true>), dim3(blocks), dim3(MF_THREADS), lds, s, a);  \
         else                                                                                                                    \

@@ -1,0 +1,104 @@
+// qe_conv_plan.hpp -- the host-side plan of one packed-activation (int8 engine) convolution.
+//
+// plan_conv (qe_conv_plan.hip) decides everything about a request once: the pre-pass (4-bit expansion, strided gather),
+// the route (resident-tile pwr / pwr7, LDS-DMA ring flatd, one of the MFMA families, or the generic VALU kernel), the
+// epilogue (fused re-quantisation, LDS byte patch, border-class table), every LDS size, the grid and the workspace
+// layout.  It is the only reader of the int8-conv QE_* knobs.  The C-ABI queries answer from the plan, and the launchers
+// (launch_conv_mfma, launch_pwr, launch_flatd) build kernel arguments from it without re-deciding anything.
+//
+// The prepared part (re-laid-out weights, per-channel constants, tap-sum tables) comes from plan_prepared: shape without
+// the batch size, and bits.  It never depends on a pointer, on N or on the route a run takes.
+#pragma once
+#include "qe_common.h"
+
+namespace qe {
+
+struct RequantHost;
+
+constexpr int FD_CK = 64;   // flatd: input channels per stage
+
+// MFMA family, pre-pass and workspace [prepared tables | scratch] of one problem
+struct MfmaPlan {
+    bool ok = false;
+    int cfg = 0;       // 0: 4x1 waves (MT 128), 1: 2x2 (MT 64), 2: 1x4 (MT 32)
+    int MT = 0, OCP = 0, NCH = 0, NG = 0, KK = 0, OH = 0, OW = 0;
+    int TH = 0, ni = 0, niw = 0, IHT = 0, IWP = 0, ROWMUL = 1, COLMUL = 1;
+    bool smallic = false;
+    int GI = 1, NS = 1;
+    bool flat = false, wraw = false, ws = false, s2 = false, sm2 = false;
+    bool expand = false;       // sub-8-bit activations are expanded to 8-bit codes in the workspace first
+    bool x4 = false;           // 4-bit activations read from the packed stream by the flat kernel itself
+    size_t xe_off = 0;
+    bool flatg = false;        // flat 1x1 kernel for small planes (several whole images per tile)
+    bool sub = false;          // strided 1x1: the sampled pixels are gathered into a dense tensor first
+    bool sub_x4 = false;       // ... straight from the 4-bit stream (subsample_x4_kernel), no expansion pass
+    size_t sub_off = 0;
+    int PADW = 0;
+    size_t lds = 0;
+    size_t wt_bytes = 0, ep_off = 0, ws_off = 0, total = 0;
+    size_t prep_total = 0;     // leading part of the workspace the prep pass fills (x-independent: can be kept across calls)
+};
+
+enum class ConvRoute { Generic, Pwr, Pwr7, Flatd, Mfma };
+enum class PrePass { None, SubX4, Sub2, SubWide, SubNarrow };   // the strided gathers (m.expand: the 8-bit expansion)
+
+// What is asked.  Pointers only count through their alignment; a query passes 0 for the ones it does not know (out,
+// rq_out), which reads as aligned.
+struct ConvRequest {
+    const qe_conv_shape *sh;
+    const qe_qparam *x, *w;    // bits, sign, n_param; the alignment of x->data, w->data and w->scale
+    uintptr_t out = 0;         // fp32 output
+    uintptr_t rq_out = 0;      // codes of a fused re-quantisation
+    int rq_bits = 0;           // > 0: re-quantise the output to rq_bits with rq_n_param parameters
+    int rq_n_param = 1;
+    bool residual = false;     // block end: relu(conv + identity), with codes when rq_bits > 0
+};
+
+struct ConvPlan {
+    ConvRoute route = ConvRoute::Generic;
+    bool fused = false;        // the requested epilogue (re-quantisation, residual) runs inside the conv kernel
+    int OH = 0, OW = 0;        // output plane (<= 0: empty)
+    size_t y_bytes = 0;        // the fp32 output, rounded up to 256 bytes (the two-pass epilogues keep it in the workspace)
+    MfmaPlan m;
+    qe_conv_shape run{};       // the problem the conv kernel sees (the dense one after a strided gather)
+
+    PrePass pre = PrePass::None;
+    int64_t pre_blocks = 0;
+    int sub2_log_up = 0, sub2_log_nq = 0;
+
+    // XCD-aware block map shared by every route: `chunk` consecutive pixel tiles per XCD run
+    int64_t blocks = 0;
+    int chunk = 1, n_pix_tiles = 0, n_oc_tiles = 0, tiles_h = 0;
+    size_t lds = 0;            // dynamic LDS of the MFMA-family launch (pwr and flatd size theirs at compile time)
+
+    // pwr / pwr7
+    int pwr_tw = 0, pwr_ks = 0, pwr_groups = 1, pwr7_gi = 0;
+    bool pwr_s2 = false;
+    // flatd
+    int fd_var = 0;            // 5 / 7: WIDE with that many column tiles, 8: SMALL (7x7 planes)
+    bool fd_w8 = false;        // 8-wave / 256-channel workgroups
+    // MFMA families
+    bool wide8 = false, deep8 = false;   // flat kernel with 256-channel workgroups (QE_FLAT8), its deep-prefetch form
+    bool rq_patch = false;     // re-quantised codes leave through the LDS byte patch (PATCH instances only)
+    bool ctab = false;
+    int ptab_off = 0;
+    int n_top = 0, n_bot = 0, n_lft = 0, n_rgt = 0;
+    int split = 1;             // sm2 / ws: channel slices of the staging threads
+};
+
+ConvPlan plan_conv(const ConvRequest &rq);
+MfmaPlan plan_prepared(const qe_conv_shape *sh, int x_bits, int w_bits);
+uint64_t prepared_layout(const MfmaPlan &p, const qe_conv_shape *sh);
+
+// launchers of the routes (the plan was made for these operands)
+int launch_conv_mfma(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *sh,
+                     float *out, void *workspace, size_t workspace_bytes, const void *prepared, size_t prepared_bytes,
+                     bool use_prepared, hipStream_t s, const RequantHost *rq, const float *res);
+int prepare_conv_tables(const MfmaPlan &p, const qe_qparam *w, const float *bias, const qe_conv_shape *sh, void *prepared,
+                        size_t prepared_bytes, hipStream_t s);
+int launch_pwr(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, float *out, hipStream_t s,
+               const RequantHost *rq, const float *res);
+int launch_flatd(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, float *out, hipStream_t s,
+                 const RequantHost *rq);
+
+}  // namespace qe

@@ -26,8 +26,8 @@
 //     (8 rows x 784 B = 49 lines), which the 8-rows-x-128-B pieces of the flat kernels cannot give on 784-byte rows
 //     (store-only probes: 3.6 TB/s against 5.1-5.6, profiles/r02c_probe_store_occ.txt).
 #include "qe_conv_mfma_kernel.hpp"
+#include "qe_conv_plan.hpp"
 
-#include <cstdlib>
 #include <utility>
 
 namespace qe {
@@ -907,128 +907,38 @@ __global__ __launch_bounds__(512, 2) void conv_pwr7_kernel(const PwrArgs a)
 // ---------------------------------------------------------------------------------------------
 extern unsigned long long *g_mfma_dbg;   // qe_conv_mfma.hip (diagnostic builds)
 
-struct PwrPlan {
-    int tw = 0, waves = 0, ks = 0, groups = 1;
-    bool s2 = false;
-};
-
-// QE_PWR=0 disables the kernel, QE_PWR_GROUPS overrides the channel split (tuning).
-static bool pwr_plan(const qe_conv_shape *sh, const qe_qparam *x, const qe_qparam *w, PwrPlan *pl)
+static void rq_args(PwrArgs &a, const RequantHost *rq)
 {
-    // QE_PWR=0: never; QE_PWR=1: only layers whose planes are ONE tile (14x14: the tile is fetched once instead of OC/128
-    // times and every strip leaves as one contiguous run: -20..25 % against the flat kernels, profiles/r03a_ab_pwr.txt) and
-    // the stride-2 layers (the strided rows fetched once per tile instead of once per 128 output channels); default (2):
-    // every eligible layer -- on stride-1 28x28 / 56x56 planes both kernels sit near the same store rate layer by layer
-    // (+-3 %, inside the noise of isolated timings), over the whole step this form is 1.2 % ahead (three alternating pairs of
-    // 200-step runs on one box, profiles/r03t_ab_pwr_stack.txt)
-    int mode = 2;
-    if (const char *e = env_get("QE_PWR")) mode = atoi(e);
-    if (mode == 0) return false;
-    if (sh->KH != 1 || sh->KW != 1 || sh->padding != 0 || (sh->stride != 1 && sh->stride != 2)) return false;
-    if (x->n_bits != 8 || w->n_bits != 8 || x->n_param != 1) return false;
-    if (sh->IC != 64 && sh->IC != 128 && sh->IC != 256) return false;
-    if (sh->OC % 32 != 0 || sh->OC < 128 || sh->N < 1) return false;
-    const bool s2 = sh->stride == 2;
-    if (s2 && ((sh->H & 1) || (sh->W & 7) || sh->W > 64 || (env_get("QE_PWR_S2") && atoi(env_get("QE_PWR_S2")) == 0))) return false;
-    const int OH = s2 ? sh->H / 2 : sh->H, OW = s2 ? sh->W / 2 : sh->W;
-    const int64_t P = (int64_t)OH * OW;                       // output plane
-    // tiles of 224 or 196 pixels that divide the plane (56x56: 14 x 224; 28x28: 4 x 196; 14x14: the plane itself)
-    const int tw = (P % 224 == 0) ? 224 : ((P % 196 == 0) ? 196 : 0);
-    if (tw == 0) return false;
-    if (s2 && (tw % OW != 0 || tw / OW > 8)) return false;    // whole output rows per tile
-    if (mode == 1 && !s2 && P != tw) return false;
-    if ((int64_t)sh->N * sh->IC * sh->H * sh->W < 16 || (int64_t)sh->OC * P >= (1ll << 29) || (int64_t)sh->IC * sh->H * sh->W >= (1ll << 31)) return false;
-    if ((reinterpret_cast<uintptr_t>(w->data) & 15) != 0 || (reinterpret_cast<uintptr_t>(x->data) & (s2 ? 7 : 3)) != 0) return false;
-    if ((reinterpret_cast<uintptr_t>(w->scale) & 3) != 0) return false;
-    const int ks = sh->IC / 32;
-    const int waves = ks == 8 ? 8 : 4;                        // IC = 256: 56 KB of tile -> one 8-wave workgroup per CU
-    if (sh->OC < 64 * waves) return false;                    // fewer than two strips per wave: the flat kernels' tiling fits better (256 -> 128 @56x56: +19 %)
-    int groups = 1;
-    const int strips = sh->OC / 32;
-    if (const char *e = env_get("QE_PWR_GROUPS")) { const int v = atoi(e); if (v >= 1 && strips % v == 0) groups = v; }
-    pl->tw = tw; pl->waves = waves; pl->ks = ks; pl->groups = groups; pl->s2 = s2;
-    return true;
-}
-
-// 7x7 planes: 0 = not eligible, else images per tile
-static int pwr7_plan(const qe_conv_shape *sh, const qe_qparam *x, const qe_qparam *w, int *groups)
-{
-    int mode = 2;
-    if (const char *e = env_get("QE_PWR")) mode = atoi(e);
-    if (mode == 0 || (env_get("QE_PWR7") && atoi(env_get("QE_PWR7")) == 0)) return 0;
-    if (sh->KH != 1 || sh->KW != 1 || sh->stride != 1 || sh->padding != 0 || sh->H * sh->W != 49) return 0;
-    if (x->n_bits != 8 || w->n_bits != 8 || x->n_param != 1) return 0;
-    if (sh->IC != 128 && sh->IC != 256 && sh->IC != 512) return 0;
-    const int gi = sh->IC == 512 ? 2 : 4;                     // 64 KB of tile
-    if (sh->OC % 32 != 0 || sh->OC < 512 || sh->N < gi || sh->N % gi != 0) return 0;   // >= 2 strips per wave; whole tiles only
-    if ((int64_t)sh->N * sh->IC * 49 >= (1ll << 31) || (int64_t)sh->OC * 49 >= (1ll << 29)) return 0;
-    if ((reinterpret_cast<uintptr_t>(w->data) & 15) != 0 || (reinterpret_cast<uintptr_t>(x->data) & 15) != 0) return 0;
-    const int tiles = sh->N / gi, strips = sh->OC / 32;
-    int g = 1;
-    while (tiles * g < kNumCU && strips % (2 * g) == 0 && strips / (2 * g) >= 8) g *= 2;   // about one workgroup per CU, >= 1 strip per wave
-    if (const char *e = env_get("QE_PWR_GROUPS")) { const int v = atoi(e); if (v >= 1 && strips % v == 0) g = v; }
-    *groups = g;
-    return gi;
-}
-
-// rq != nullptr: the fused re-quantising form (8-bit codes, one scale: what the kernels' epilogue covers)
-bool pwr_eligible(const qe_conv_shape *sh, const qe_qparam *x, const qe_qparam *w, const RequantHost *rq)
-{
-    PwrPlan pl;
-    int g;
-    if (rq != nullptr) {
-        if (rq->n_bits != 8 || rq->n_param != 1 || rq->out == nullptr || (reinterpret_cast<uintptr_t>(rq->out) & 15) != 0) return false;
-        if (env_get("QE_PWR_RQ") && atoi(env_get("QE_PWR_RQ")) == 0) return false;
-        return pwr_plan(sh, x, w, &pl) || pwr7_plan(sh, x, w, &g) != 0;
-    }
-    return pwr_plan(sh, x, w, &pl) || pwr7_plan(sh, x, w, &g) != 0;
-}
-
-// residual block end (qe_quantconv2d_residual_prepared): stride-1 layers of either kernel; rq: 8-bit codes, one scale
-bool pwr_residual_eligible(const qe_conv_shape *sh, const qe_qparam *x, const qe_qparam *w, int rq_bits, int rq_n_param)
-{
-    if (rq_bits != 0 && (rq_bits != 8 || rq_n_param != 1)) return false;
-    if (sh->stride != 1) return false;
-    PwrPlan pl;
-    int g;
-    // 7x7 planes: the 512-channel form only (512 -> 2048, the last stage's block end); the 4-image-tile instances spill
-    // with the residual epilogue's registers on top (RQ + RES: 16 bytes of scratch)
-    return pwr_plan(sh, x, w, &pl) || (sh->IC == 512 && pwr7_plan(sh, x, w, &g) != 0);
-}
-
-static int launch_pwr7(const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *sh, float *out, hipStream_t s,
-                       const RequantHost *rq, const float *res)
-{
-    int groups = 1;
-    const int gi = pwr7_plan(sh, x, w, &groups);
-    if (res != nullptr && sh->IC != 512) return QE_ERR_UNSUPPORTED;
-    if (gi == 0 || ((rq == nullptr || res != nullptr) && (reinterpret_cast<uintptr_t>(out) & 15) != 0)) return QE_ERR_UNSUPPORTED;
-    PwrArgs a;
-    a.res = res;
     a.rq_out = nullptr; a.rq_scale = nullptr; a.rq_zero = nullptr; a.rq_status = nullptr;
     a.rq_qmin = a.rq_qmax = a.rq_lo = a.rq_hi = 0.0f; a.rq_offset = 0;
     if (rq != nullptr) {
-        if (res == nullptr && !pwr_eligible(sh, x, w, rq)) return QE_ERR_UNSUPPORTED;
         a.rq_out = rq->out; a.rq_scale = rq->scale; a.rq_zero = rq->zero;
         a.rq_qmin = rq->qmin; a.rq_qmax = rq->qmax; a.rq_status = rq->status;
         a.rq_offset = rq->sign ? 128u : 0u;                       // tpack.cu:108-111
         a.rq_lo = rq->sign ? -128.0f : 0.0f; a.rq_hi = rq->sign ? 127.0f : 255.0f;
     }
+}
+
+// p.route == Pwr7: 7x7 planes, p.pwr7_gi images per tile (the residual block end: the 512-channel form only)
+static void launch_pwr7(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, float *out, hipStream_t s,
+                        const RequantHost *rq, const float *res)
+{
+    const qe_conv_shape *sh = &p.run;
+    PwrArgs a;
+    a.res = res;
+    rq_args(a, rq);
     a.W_in = 7; a.PIN = 49; a.OW = 7;
     a.x = static_cast<const uint8_t *>(x->data); a.w = static_cast<const uint8_t *>(w->data);
     a.x_scale = x->scale; a.x_zero = x->zero; a.w_scale = w->scale; a.w_zero = w->zero; a.bias = bias;
     a.x_sign = x->sign; a.w_sign = w->sign; a.w_per_tensor = (w->n_param == 1);
     a.out = out; a.N = sh->N; a.IC = sh->IC; a.OC = sh->OC; a.P = 49;
     a.tiles_per_image = 1;
-    a.n_pix_tiles = sh->N / gi;
-    a.n_groups = groups;
-    a.strips_per_group = sh->OC / 32 / groups;
+    a.n_pix_tiles = p.n_pix_tiles;
+    a.n_groups = p.pwr_groups;
+    a.strips_per_group = sh->OC / 32 / p.pwr_groups;
     a.dbg = g_mfma_dbg;
-    const int64_t per_xcd = ((int64_t)a.n_pix_tiles + 7) / 8;
-    a.chunk = (int)(per_xcd < 1 ? 1 : per_xcd);
-    const int64_t runs = ((int64_t)a.n_pix_tiles + a.chunk - 1) / a.chunk;
-    const int64_t blocks = (runs + 7) / 8 * a.chunk * 8 * a.n_groups;
-    if (blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
+    a.chunk = p.chunk;
+    const int64_t blocks = p.blocks;
 #define QE_PWR7_LAUNCH3(KSV, GIV, RQV, RESV)                                                                                \
     do {                                                                                                                    \
         static const bool ok_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_pwr7_kernel<KSV, GIV, RQV, RESV>), \
@@ -1045,50 +955,35 @@ static int launch_pwr7(const qe_qparam *x, const qe_qparam *w, const float *bias
 #undef QE_PWR7_LAUNCH
 #undef QE_PWR7_LAUNCH2
 #undef QE_PWR7_LAUNCH3
-    QE_LAUNCH_CHECK();
-    return QE_OK;
 }
 
 // res != nullptr: the residual block end (RES instances, stride 1 only): out (may be NULL when rq) = relu(y + res)
-int launch_pwr(const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *sh, float *out, hipStream_t s,
+int launch_pwr(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, float *out, hipStream_t s,
                const RequantHost *rq, const float *res)
 {
-    if (sh->H * sh->W == 49) return launch_pwr7(x, w, bias, sh, out, s, rq, res);
-    PwrPlan pl;
-    if (!pwr_plan(sh, x, w, &pl)) return QE_ERR_UNSUPPORTED;
-    if (res != nullptr && pl.s2) return QE_ERR_UNSUPPORTED;
+    if (p.route == ConvRoute::Pwr7) {
+        launch_pwr7(p, x, w, bias, out, s, rq, res);
+        QE_LAUNCH_CHECK();
+        return QE_OK;
+    }
+    const qe_conv_shape *sh = &p.run;
     PwrArgs a;
     a.res = res;
-    a.rq_out = nullptr; a.rq_scale = nullptr; a.rq_zero = nullptr; a.rq_status = nullptr;
-    a.rq_qmin = a.rq_qmax = a.rq_lo = a.rq_hi = 0.0f; a.rq_offset = 0;
-    if (rq != nullptr) {
-        if (res == nullptr && !pwr_eligible(sh, x, w, rq)) return QE_ERR_UNSUPPORTED;
-        a.rq_out = rq->out; a.rq_scale = rq->scale; a.rq_zero = rq->zero;
-        a.rq_qmin = rq->qmin; a.rq_qmax = rq->qmax; a.rq_status = rq->status;
-        a.rq_offset = rq->sign ? 128u : 0u;                       // tpack.cu:108-111
-        a.rq_lo = rq->sign ? -128.0f : 0.0f; a.rq_hi = rq->sign ? 127.0f : 255.0f;
-    }
+    rq_args(a, rq);
     a.x = static_cast<const uint8_t *>(x->data); a.w = static_cast<const uint8_t *>(w->data);
     a.x_scale = x->scale; a.x_zero = x->zero; a.w_scale = w->scale; a.w_zero = w->zero; a.bias = bias;
     a.x_sign = x->sign; a.w_sign = w->sign; a.w_per_tensor = (w->n_param == 1);
     a.out = out; a.N = sh->N; a.IC = sh->IC; a.OC = sh->OC;
     a.W_in = sh->W; a.PIN = sh->H * sh->W;
-    a.OW = pl.s2 ? sh->W / 2 : sh->W;
-    a.P = pl.s2 ? (sh->H / 2) * (sh->W / 2) : sh->H * sh->W;
-    a.tiles_per_image = a.P / pl.tw;
-    a.n_pix_tiles = sh->N * a.tiles_per_image;
-    a.n_groups = pl.groups;
-    a.strips_per_group = sh->OC / 32 / pl.groups;
+    a.OW = p.pwr_s2 ? sh->W / 2 : sh->W;
+    a.P = p.pwr_s2 ? (sh->H / 2) * (sh->W / 2) : sh->H * sh->W;
+    a.tiles_per_image = p.tiles_h;
+    a.n_pix_tiles = p.n_pix_tiles;
+    a.n_groups = p.pwr_groups;
+    a.strips_per_group = sh->OC / 32 / p.pwr_groups;
     a.dbg = g_mfma_dbg;
-    const int64_t per_xcd = ((int64_t)a.n_pix_tiles + 7) / 8;
-    a.chunk = (int)(per_xcd < 1 ? 1 : per_xcd);
-    if (const char *ci = env_get("QE_CHUNK_IMAGES")) {
-        const int64_t k = (int64_t)atoi(ci) * a.tiles_per_image;
-        a.chunk = (int)(k < 1 ? 1 : (k < per_xcd ? k : per_xcd));
-    }
-    const int64_t runs = ((int64_t)a.n_pix_tiles + a.chunk - 1) / a.chunk;
-    const int64_t blocks = (runs + 7) / 8 * a.chunk * 8 * a.n_groups;
-    if (blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
+    a.chunk = p.chunk;
+    const int64_t blocks = p.blocks;
 #define QE_PWR_LAUNCH2(WV, KSV, TWV, S2V, RQV)                                                                             \
     do {                                                                                                                    \
         static const bool ok_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_pwr_kernel<7, WV, KSV, TWV, S2V, RQV>), \
@@ -1109,12 +1004,12 @@ int launch_pwr(const qe_qparam *x, const qe_qparam *w, const float *bias, const 
 #define QE_PWR_LAUNCH(WV, KSV, TWV)                                                                                         \
     do {                                                                                                                    \
         if (res != nullptr) { if (rq != nullptr) QE_PWR_LAUNCHR(WV, KSV, TWV, true); else QE_PWR_LAUNCHR(WV, KSV, TWV, false); } \
-        else if (pl.s2) QE_PWR_LAUNCH1(WV, KSV, TWV, true); else QE_PWR_LAUNCH1(WV, KSV, TWV, false);                      \
+        else if (p.pwr_s2) QE_PWR_LAUNCH1(WV, KSV, TWV, true); else QE_PWR_LAUNCH1(WV, KSV, TWV, false);                      \
     } while (0)
-    if (pl.tw == 224) {
-        if (pl.ks == 2) QE_PWR_LAUNCH(4, 2, 224); else if (pl.ks == 4) QE_PWR_LAUNCH(4, 4, 224); else QE_PWR_LAUNCH(8, 8, 224);
+    if (p.pwr_tw == 224) {
+        if (p.pwr_ks == 2) QE_PWR_LAUNCH(4, 2, 224); else if (p.pwr_ks == 4) QE_PWR_LAUNCH(4, 4, 224); else QE_PWR_LAUNCH(8, 8, 224);
     } else {
-        if (pl.ks == 2) QE_PWR_LAUNCH(4, 2, 196); else if (pl.ks == 4) QE_PWR_LAUNCH(4, 4, 196); else QE_PWR_LAUNCH(8, 8, 196);
+        if (p.pwr_ks == 2) QE_PWR_LAUNCH(4, 2, 196); else if (p.pwr_ks == 4) QE_PWR_LAUNCH(4, 4, 196); else QE_PWR_LAUNCH(8, 8, 196);
     }
 #undef QE_PWR_LAUNCH1
 #undef QE_PWR_LAUNCH2

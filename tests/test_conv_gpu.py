@@ -305,6 +305,7 @@ def test_kernel_variants_forced_by_env(engine, env):
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
+        capi.reload_env()
 
 
 @pytest.mark.parametrize("expand,x4", [("0", "1"), ("1", "1"), ("1", "0")])
@@ -334,6 +335,7 @@ def test_sub8_activation_paths(engine, expand, x4):
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
+        capi.reload_env()
 
 
 def test_4bit_weights_on_flat_kernels(engine):
@@ -476,6 +478,7 @@ def test_4bit_activations_on_strided_1x1(engine, sub_x4):
             os.environ.pop("QE_SUB_X4", None)
         else:
             os.environ["QE_SUB_X4"] = old
+        capi.reload_env()
 
 
 def test_resnet50_shapes_w4a4(engine):
@@ -534,3 +537,28 @@ def test_batch_independence_w4a4_families(engine):
                                         bias.cpu().numpy(), s, p, mode="f64", return_f64=True)
             assert np.abs(y[255:256].cpu().numpy().astype(np.float64) - o64).max() <= 1e-5, (IC, OC, K, s, H)
         del qx, y, xp
+
+
+def test_unaligned_fp32_out_falls_back(engine):
+    """A 7x7 layer whose fp32 `out` starts 4 bytes past a 16-byte boundary (default knobs): the resident-tile kernel that
+    takes the aligned call stores 16-byte pieces, so the plan picks another kernel instead of failing, and the result meets
+    the oracle."""
+    capi.reload_env()
+    rng = np.random.RandomState(405)
+    case = _random_case(rng, 4, 512, 7, 7, 2048, 1, 1, 0, 8, 1, 8, 1, w_pc=True, a_pc=False, zeros=False, bias=True)
+    wp, wd, sw, zw = case["w"]
+    xp, xd, sx, zx = case["x"]
+    sh = capi.conv_shape(4, 512, 7, 7, 2048, 1, 1, 1, 0)
+    xq = capi.qparam(_t(xp), int(xd[0]), int(xd[1]), _t(sx), _t(zx))
+    wq = capi.qparam(_t(wp), int(wd[0]), int(wd[1]), _t(sw), _t(zw))
+    n = 4 * 2048 * 49
+    buf = torch.zeros(n + 4, dtype=torch.float32, device=DEV)
+    out = buf[1:1 + n].view(4, 2048, 7, 7)
+    assert out.data_ptr() % 16 == 4
+    y = capi.quantconv2d(xq, wq, _t(case["bias"]), sh, out=out)
+    torch.cuda.synchronize()
+    chains = [oracle.quantconv2d(xp, xd, sx, zx, wp, wd, sw, zw, case["bias"], 1, 0, mode=m) for m in ("fp32", "fp32_fma")]
+    _, o64 = oracle.quantconv2d(xp, xd, sx, zx, wp, wd, sw, zw, case["bias"], 1, 0, mode="f64", return_f64=True)
+    y = y.cpu().numpy()
+    assert np.isfinite(y).all()
+    _assert_conv_close(y, o64, chains[0], "unaligned out", chains[1])

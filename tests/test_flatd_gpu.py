@@ -52,3 +52,4 @@ def test_flatd_vs_oracle(engine, flatd):
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
+        capi.reload_env()

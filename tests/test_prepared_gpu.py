@@ -127,3 +127,47 @@ def test_prepared_entry_is_shared_across_batch_sizes(engine):
         _, ref = oracle.quantconv2d(xpn, xdn, sx, zx, wp, wd, sw, zw, big["bias"], 1, 1, mode="f64", return_f64=True)
         assert np.abs(y.cpu().numpy().astype(np.float64) - ref).max() <= 1e-5, n
     assert quant_engine.cache_stats()[3] == misses0 + 1      # prepared once for all five calls
+
+
+def test_prepared_tables_serve_every_batch_size():
+    """qe_conv_prepare writes the tables whenever the layer has any, whatever kernel its own batch size would run.  A 1x1
+    512 -> 2048 layer on 7x7 planes with the small-plane flat and ring kernels off runs the resident-tile kernel at N = 4
+    (no tables) and the halo kernel at N = 3 (reads them): prepared once at N = 4 into a buffer of 0xFF bytes, both
+    batch sizes meet the oracle."""
+    import ctypes
+    import os
+    from conftest import conv_tolerance
+    knobs = {"QE_FLATG": "0", "QE_FLATD": "0"}
+    old = {k: os.environ.get(k) for k in knobs}
+    os.environ.update(knobs)
+    capi.reload_env()
+    try:
+        rng = np.random.RandomState(404)
+        case = _random_case(rng, 4, 512, 7, 7, 2048, 1, 1, 0, 8, 1, 8, 1, w_pc=True, a_pc=False, zeros=False, bias=True)
+        wp, wd, sw, zw = case["w"]
+        xp, xd, sx, zx = case["x"]
+        qx = oracle.tunpack(xp, xd)
+        wq = capi.qparam(_t(wp), int(wd[0]), int(wd[1]), _t(sw), _t(zw))
+        bias = _t(case["bias"])
+        sh4 = capi.conv_shape(4, 512, 7, 7, 2048, 1, 1, 1, 0)
+        need = int(capi.lib().qe_conv_prepared_bytes(ctypes.byref(sh4), 8, 8))
+        assert need > 0
+        prepared = torch.full((need,), 0xFF, dtype=torch.uint8, device="cuda")
+        capi.check(capi.lib().qe_conv_prepare(ctypes.byref(wq), bias.data_ptr(), ctypes.byref(sh4), 8, prepared.data_ptr(),
+                                              need, capi._stream()))
+        for n in (3, 4):
+            xpn, xdn = oracle.tpack(qx[:n], 8, 1)
+            sh = capi.conv_shape(n, 512, 7, 7, 2048, 1, 1, 1, 0)
+            xq = capi.qparam(_t(xpn), 8, 1, _t(sx), _t(zx))
+            y = capi.quantconv2d_prepared(xq, wq, bias, sh, prepared).cpu().numpy()
+            chains = [oracle.quantconv2d(xpn, xdn, sx, zx, wp, wd, sw, zw, case["bias"], 1, 0, mode=m) for m in ("fp32", "fp32_fma")]
+            _, o64 = oracle.quantconv2d(xpn, xdn, sx, zx, wp, wd, sw, zw, case["bias"], 1, 0, mode="f64", return_f64=True)
+            err, allowed = conv_tolerance(y, o64, *chains)
+            assert (err <= allowed).all(), "N=%d: worst err %.3g (allowed %.3g)" % (n, float(np.nanmax(err)), allowed)   # NaN fails
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+        capi.reload_env()

@@ -42,6 +42,7 @@ SHAPES = [
 def _with_env(env, fn):
     old = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
+    capi.reload_env()
     try:
         return fn()
     finally:
@@ -50,6 +51,7 @@ def _with_env(env, fn):
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
+        capi.reload_env()      # the library snapshots the QE_* knobs: no stale value may reach a later test
 
 
 @pytest.mark.parametrize("pwr", ["1", "0"])
@@ -83,11 +85,13 @@ def test_pwr_channel_groups(engine, groups):
     _with_env({"QE_PWR": "2", "QE_PWR_GROUPS": groups}, run)
 
 
-def test_pwr_batch256_independence(engine, monkeypatch):
+def test_pwr_batch256_independence(engine):
     """The batch-256 launch geometry (256 / 1024 / 3584 workgroups): image i of the batched call == the same image alone."""
+    _with_env({"QE_PWR": "2"}, lambda: _batch256_independence(engine))
+
+
+def _batch256_independence(engine):
     import torch
-    monkeypatch.setenv("QE_PWR", "2")
-    capi.reload_env()
     rng = np.random.RandomState(5)
     for (ic, hw, oc) in [(256, 14, 1024), (128, 28, 512), (64, 56, 256)]:
         n = 256
@@ -123,7 +127,7 @@ WIDE_SHAPES = [
 
 @pytest.mark.parametrize("flat8", ["1", "0"])
 def test_wide_flat_kernel_vs_oracle(engine, flat8):
-    """conv_mfma_flat_kernel<8, 1, NIW, 4>: 256 output channels per workgroup (launch_conv_mfma: wide8) against the oracle and,
+    """conv_mfma_flat_kernel<8, 1, NIW, 4>: 256 output channels per workgroup (plan_conv: wide8) against the oracle and,
     bit for bit, against the 4-wave instances (same integer sums, same epilogue operation order)."""
     rng = np.random.RandomState(808)
 
