@@ -245,7 +245,7 @@ def _pack(q, bits):
 def exact_state_dict(arch="resnet50", w_bits=8, a_bits=8, seed=0, width=64, num_classes=1000, calib_images=None,
                      image_size=224, variants=None):
     """A packed ResNet state_dict in synthetic_state_dict's key layout with exact fp32 arithmetic (module docstring),
-    calibrated on Float64ResNet.  variants = {layer name: spec} changes one consumer's activation quantiser:
+    calibrated on Float64ResNet at image_size (one side, or (H, W)).  variants = {layer name: spec} changes one consumer's activation quantiser:
       signed=True        qmin / qmax signed (no ReLU fold);
       zero=<int>         a non-zero integer zero point;
       per_channel=True   per-channel activation scales;
@@ -308,7 +308,8 @@ def exact_state_dict(arch="resnet50", w_bits=8, a_bits=8, seed=0, width=64, num_
                "fc.a_quantizer.qmin": torch.tensor(float(qmin)), "fc.a_quantizer.qmax": torch.tensor(float(qmax))})
     if calib_images is None:
         g = torch.Generator(device="cpu").manual_seed(seed + 1)
-        calib_images = torch.randn(2, 3, image_size, image_size, generator=g)
+        H, W = (image_size, image_size) if isinstance(image_size, int) else image_size
+        calib_images = torch.randn(2, 3, H, W, generator=g)
     model = Float64ResNet(sd)
     model.forward(calib_images, calibrate=variants)
     return model.write_back(sd)

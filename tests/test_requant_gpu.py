@@ -3,13 +3,16 @@ SURVEY.md section 8 row f-2) must equal qe_quantize_pack(qe_quantconv2d_prepared
 the oracle's tpack of round(y / s - z).clamp(qmin, qmax) computed on the host from the engine's own fp32 y -- for every
 kernel family (flat, stride-2 flat, 7x7 small-plane, halo, two-strip, warp-specialised, stem), ragged tiles, symmetric
 and asymmetric operands, signed and unsigned codes, plus the two-pass route (sub-8-bit codes, per-channel scale)."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
 
 import oracle
 from quantize_amd import capi
-from test_conv_gpu import _random_case, _t, engine  # noqa: F401
+import pwr_instances
+from test_conv_gpu import DEV, _assert_conv_close, _random_case, _t, engine  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -34,8 +37,8 @@ SHAPES = [
     (1, 256, 28, 28, 512, 1, 1, 0),     # 8 waves
     (3, 256, 56, 56, 512, 1, 2, 0),     # its stride-2 form
     (2, 64, 28, 64, 256, 1, 2, 0),      # stride 2, 224-byte row pieces
-    (40, 64, 14, 14, 192, 1, 1, 0),     # whole-plane tiles: a strip's 32 planes are one 6272-byte run; more tiles than XCDs
-    (3, 128, 14, 14, 160, 1, 1, 0),     # 5 strips on 4 waves
+    (40, 64, 14, 14, 192, 1, 1, 0),     # more tiles than XCDs; 6 strips on 4 waves: the flat kernels' epilogue
+    (3, 128, 14, 14, 160, 1, 1, 0),     # 5 strips on 4 waves: fewer than two per wave, the flat kernels' epilogue
     (4, 512, 7, 7, 2048, 1, 1, 0),      # the 7x7-plane form: a strip's 32 planes x 49 codes of an image are one 1568-byte run
     (8, 256, 7, 7, 768, 1, 1, 0),       # 4 images per tile, 3 strips per wave
     (8, 128, 7, 7, 1024, 1, 1, 0),
@@ -95,6 +98,77 @@ def test_requant_equals_conv_then_quantize_pack(engine, sign, pwr_rq, monkeypatc
             yq = np.clip(np.rint(y.cpu().numpy() / np.float32(s.item()) - np.float32(z.item())), qmin, qmax)
             op, _ = oracle.tpack(yq.astype(np.int64), 8, sign)
             assert np.array_equal(g, op), shp
+
+
+def _oracle_chains(case):
+    """(fp32 chain, contracted fp32 chain, float64 exact) of the oracle on the case's operands."""
+    xp, xd, sx, zx = case["x"]
+    wp, wd, sw, zw = case["w"]
+    args = (xp, xd, sx, zx, wp, wd, sw, zw, case["bias"], case["stride"], case["pad"])
+    o32, fma = [oracle.quantconv2d(*args, mode=m) for m in ("fp32", "fp32_fma")]
+    return o32, fma, oracle.quantconv2d(*args, mode="f64", return_f64=True)[1]
+
+
+def test_requant_every_pwr_instance(engine):
+    """Every row of the instance table through its re-quantising instance: the codes equal quantize_pack of the fp32 result
+    bit for bit, and that fp32 result meets the oracle.  Signed and unsigned codes, zero points that are not zero,
+    symmetric and asymmetric operands and no bias take turns over the rows."""
+    rng = np.random.RandomState(4343)
+    for i, (shp, base, note, env) in enumerate(pwr_instances.ROWS):
+        sign, zeros, has_bias = i % 2 == 0, i % 3 == 1, i % 4 != 3
+        what = "%s %s (%s)" % (pwr_instances.kernel_name(base + (True, False)), shp, note)
+        case = _random_case(rng, *shp, 8, 1, 8, 0 if zeros else 1, w_pc=True, a_pc=False, zeros=zeros, bias=has_bias)
+        sh, xq, wq, bias = _case_tensors(case)
+        with pwr_instances.knobs(env):
+            prepared = capi.conv_prepare(wq, bias, sh, 8)
+            y = capi.quantconv2d_prepared(xq, wq, bias, sh, prepared)
+            torch.cuda.synchronize()
+            qmin, qmax = (-128.0, 127.0) if sign else (0.0, 255.0)
+            s = torch.tensor([float(y.abs().max()) / 100.0], device=DEV)     # clips a few percent of the values
+            z = torch.tensor([[0.37, -2.0, 5.5][i % 3] if sign else [-117.25, -3.0, -64.5][i % 3]], device=DEV)
+            rq = capi.requant(s, z, qmin, qmax, 8, sign)
+            assert capi.requant_path(sh, xq, wq, rq) == 1, what
+            got, status = capi.quantconv2d_requant_prepared(xq, wq, bias, sh, prepared, rq)
+            ref, st2 = capi.quantize_pack(y, s, z, qmin, qmax, 8, sign)
+            torch.cuda.synchronize()
+        assert int(status.item()) == 0 and int(st2.item()) == 0, what
+        g, r = got.cpu().numpy(), ref.cpu().numpy()
+        bad = np.nonzero(g != r)[0]
+        assert bad.size == 0, "%s: %d of %d codes differ, first at %d (%d vs %d)" % (what, bad.size, g.size, bad[0], g[bad[0]],
+                                                                                    r[bad[0]])
+        o32, fma, o64 = _oracle_chains(case)
+        _assert_conv_close(y.cpu().numpy(), o64, o32, what, fma)
+
+
+@pytest.mark.parametrize("shape", [(2, 128, 28, 28, 512, 1, 1, 0), (2, 64, 56, 56, 256, 1, 2, 0), (4, 512, 7, 7, 2048, 1, 1, 0)],
+                         ids=["pwr", "pwr_s2", "7x7"])
+def test_requant_unaligned_codes(engine, shape):
+    """Codes `out` 1, 4 and 8 bytes past a 16-byte boundary: the resident-tile and 7x7 ring kernels store 16-byte pieces, so
+    the plan takes another kernel.  The codes still equal quantize_pack's, nothing outside `out` is written, and the
+    workspace requant_workspace_bytes asks for (the query knows no pointer) covers the call."""
+    rng = np.random.RandomState(55)
+    case = _random_case(rng, *shape, 8, 1, 8, 1, w_pc=True, a_pc=False, zeros=False, bias=True)
+    sh, xq, wq, bias = _case_tensors(case)
+    prepared = capi.conv_prepare(wq, bias, sh, 8)
+    y = capi.quantconv2d_prepared(xq, wq, bias, sh, prepared)
+    s = torch.tensor([float(y.abs().max()) / 100.0], device=DEV)
+    z = torch.tensor([-1.5], device=DEV)
+    rq = capi.requant(s, z, -128.0, 127.0, 8, True)
+    ref, _ = capi.quantize_pack(y, s, z, -128.0, 127.0, 8, True)
+    need = int(capi.lib().qe_quantconv2d_requant_workspace_bytes(ctypes.byref(sh), ctypes.byref(xq), ctypes.byref(wq),
+                                                                  ctypes.byref(rq)))
+    n = ref.numel()
+    for off in (1, 4, 8):
+        buf = torch.full((n + 32,), 0xA5, dtype=torch.uint8, device=DEV)
+        out = buf[off:off + n]
+        assert out.data_ptr() % 16 == off
+        ws = torch.empty(need, dtype=torch.uint8, device=DEV) if need else None       # exactly what the query asked for
+        got, status = capi.quantconv2d_requant_prepared(xq, wq, bias, sh, prepared, rq, out=out, workspace=ws)
+        torch.cuda.synchronize()
+        assert int(status.item()) == 0
+        assert torch.equal(got, ref), "%s codes + %d bytes: %d codes differ" % (shape, off, int((got != ref).sum()))
+        b = buf.cpu()
+        assert bool((b[:off] == 0xA5).all()) and bool((b[off + n:] == 0xA5).all()), "%s + %d: written outside out" % (shape, off)
 
 
 def test_requant_two_pass_routes(engine):

@@ -1,12 +1,16 @@
 """GPU: the residual block end (qe_quantconv2d_residual_prepared) -- out = relu(conv + identity) and the consumer's codes
 of out -- equals torch.relu(qe_quantconv2d_prepared(...) + identity) and qe_quantize_pack(out) BIT FOR BIT, on the conv
-kernel's own epilogue (path 1: the four ResNet-50 block-end shapes) and on the two-pass route (everything else)."""
+kernel's own epilogue (path 1: the four ResNet-50 block-end shapes and every RES instance of the resident-tile kernels,
+tests/pwr_instances.py) and on the two-pass route (everything else)."""
 import numpy as np
 import pytest
 import torch
 
+import oracle
+import pwr_instances
 from quantize_amd import capi
 from quantize_amd.packed_resnet import pack_codes
+from test_conv_gpu import _assert_conv_close
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -22,7 +26,8 @@ def _t(a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
-def _case(N, IC, H, W, OC, K=1, stride=1, pad=0, x_signed=False, w_signed=True, asym=False, bias=True, seed=0):
+def _case(N, IC, H, W, OC, K=1, stride=1, pad=0, x_signed=False, w_signed=True, asym=False, bias=True, seed=0, host=None):
+    """host: a dict to receive the operands as host arrays (for the oracle)."""
     rng = np.random.RandomState(seed)
     xlo, xhi = (-128, 128) if x_signed else (0, 256)
     qx = rng.randint(xlo, xhi, size=(N, IC, H, W))
@@ -32,6 +37,9 @@ def _case(N, IC, H, W, OC, K=1, stride=1, pad=0, x_signed=False, w_signed=True, 
     sw = _t(rng.uniform(2e-4, 6e-4, size=OC).astype(np.float32))
     zw = _t((rng.randint(-3, 4, size=OC) if asym else np.zeros(OC) + (0 if w_signed else 128)).astype(np.float32))
     b = _t(rng.normal(0, 0.1, size=OC).astype(np.float32)) if bias else None
+    if host is not None:
+        host.update(qx=qx, qw=qw, x_signed=x_signed, w_signed=w_signed, sx=sx.cpu().numpy(), zx=zx.cpu().numpy(),
+                    sw=sw.cpu().numpy(), zw=zw.cpu().numpy(), b=None if b is None else b.cpu().numpy(), stride=stride, pad=pad)
     sh = capi.conv_shape(N, IC, H, W, OC, K, K, stride, pad)
     xq = capi.qparam(_t(pack_codes(qx, 8, x_signed)), 8, x_signed, sx, zx)
     wq = capi.qparam(_t(pack_codes(qw, 8, w_signed)), 8, w_signed, sw, zw)
@@ -92,6 +100,62 @@ def test_block_end_fused(shape, x_signed, asym, bias):
     _check(*c, rq=None, expect_path=1)                                  # fp32 only
     _check(*c, rq=_rq(ref), expect_path=1, out=None)                    # codes only (stage boundaries)
     _check(*c, rq=_rq(ref), expect_path=1, out="identity")              # in place
+
+
+def _assert_y_meets_oracle(y, host, n_img, what):
+    """The engine's plain conv y (what the block end adds the identity to) on the first n_img images against the oracle."""
+    xp, xd = oracle.tpack(host["qx"][:n_img], 8, host["x_signed"])
+    wp, wd = oracle.tpack(host["qw"], 8, host["w_signed"])
+    args = (xp, xd, host["sx"], host["zx"], wp, wd, host["sw"], host["zw"], host["b"], host["stride"], host["pad"])
+    o32, fma = [oracle.quantconv2d(*args, mode=m) for m in ("fp32", "fp32_fma")]
+    _, o64 = oracle.quantconv2d(*args, mode="f64", return_f64=True)
+    _assert_conv_close(y[:n_img].cpu().numpy(), o64, o32, what, fma)
+
+
+RES_ROWS = pwr_instances.res_rows()
+
+
+@pytest.mark.parametrize("k", range(len(RES_ROWS)), ids=["%s-%s" % ("x".join(map(str, r[0][:5])), "g" if r[3] else "")
+                                                         for r in RES_ROWS])
+def test_block_end_every_instance(k):
+    """Every stride-1 row of the instance table through its RES instances (fp32 + codes, fp32 only, codes only, in place;
+    signed and unsigned codes, a zero point that is not zero), and the conv y it adds to against the float64 oracle."""
+    shp, base, note, env = RES_ROWS[k]
+    x_signed, asym, bias = [(False, False, True), (True, True, True), (False, True, False)][k % 3]
+    host = {}
+    with pwr_instances.knobs(env):
+        c = _case(*shp[:5], x_signed=x_signed, asym=asym, bias=bias, seed=100 + k, host=host)
+        ref = torch.relu(c[5] + c[6])
+        _check(*c, rq=_rq(ref), expect_path=1)                          # fp32 + unsigned codes
+        _check(*c, rq=_rq(ref, signed=True), expect_path=1)             # signed codes
+        _check(*c, rq=_rq(ref, zero=-2.0), expect_path=1)               # non-zero zero point
+        _check(*c, rq=None, expect_path=1)                              # fp32 only
+        _check(*c, rq=_rq(ref, signed=True, zero=1.5), expect_path=1, out=None)    # codes only
+        _check(*c, rq=_rq(ref), expect_path=1, out="identity")          # in place
+    _assert_y_meets_oracle(c[5], host, min(shp[0], 4), "%s %s (%s)" % (pwr_instances.kernel_name(base + (False, True)), shp,
+                                                                        note))
+
+
+def test_batch_256_block_end_is_batch_independent_196x2():
+    """A batch-256 launch of the 64 -> 256 @28x28 block end (<7, 4, 2, 196>, RES): each image's rows equal a batch-2
+    launch on that image, and image 255's conv meets the oracle."""
+    host = {}
+    sh, xq, wq, b, prep, y, identity = _case(256, 64, 28, 28, 256, seed=14, host=host)
+    ref = torch.relu(y + identity)
+    rq = _rq(ref, signed=True, zero=-1.0)
+    assert capi.residual_path(sh, xq, wq, rq) == 1
+    o, codes, _ = capi.quantconv2d_residual_prepared(xq, wq, b, sh, prep, identity, rq=rq)
+    assert torch.equal(o, ref)
+    x_all = xq._keep[0].view(256, -1)
+    per = 256 * 784
+    for i in (0, 101, 254):
+        sh2 = capi.conv_shape(2, 64, 28, 28, 256, 1, 1, 1, 0)
+        x2 = capi.qparam(x_all[i:i + 2].contiguous().view(-1), 8, False, xq._keep[1], xq._keep[2])
+        o2, c2, _ = capi.quantconv2d_residual_prepared(x2, wq, b, sh2, prep, identity[i:i + 2].contiguous(), rq=rq)
+        assert torch.equal(o2, o[i:i + 2])
+        assert torch.equal(c2, codes[i * per:(i + 2) * per])
+    host["qx"] = host["qx"][255:]
+    _assert_y_meets_oracle(y[255:], host, 1, "batch 256, image 255")
 
 
 @pytest.mark.parametrize("shape", [(3, 512, 7, 7, 2048), (2, 64, 30, 30, 256), (1, 96, 14, 14, 256)])
@@ -184,3 +248,24 @@ def test_argument_checks():
         capi.quantconv2d_residual_prepared(xq, wq, b, sh, prep, flat[:identity.numel()], out=flat[16:16 + identity.numel()])
     with pytest.raises(capi.QeError):           # neither out nor codes
         capi.quantconv2d_residual_prepared(xq, wq, b, sh, prep, identity, rq=None, out=None)
+
+
+@pytest.mark.parametrize("ident_off,out_off,codes_off", [(1, 0, 0), (3, 0, 0), (0, 1, 0), (0, 2, 0), (0, 0, 1), (0, 0, 2)])
+def test_argument_alignment(ident_off, out_off, codes_off):
+    """identity or out not 16-byte aligned, or codes not 4-byte aligned: QE_ERR_ARG (qe_quantconv2d_residual_prepared's
+    contract), and neither out nor codes is written.  Offsets in elements: 4 bytes per fp32, 1 per code."""
+    sh, xq, wq, b, prep, y, identity = _case(2, 128, 28, 28, 512, seed=2)
+    rq = _rq(torch.relu(y + identity))
+    n = identity.numel()
+    ibuf = torch.zeros(n + 16, device=DEV)
+    ident = ibuf[ident_off:ident_off + n].view(identity.shape)
+    ident.copy_(identity)
+    obuf = torch.full((n + 16,), -7.5, device=DEV)
+    cbuf = torch.full((n + 16,), 0xA5, dtype=torch.uint8, device=DEV)
+    out = obuf[out_off:out_off + n].view(identity.shape)
+    codes = cbuf[codes_off:codes_off + n]
+    with pytest.raises(capi.QeError, match="invalid argument"):
+        capi.quantconv2d_residual_prepared(xq, wq, b, sh, prep, ident, rq=rq, out=out, codes=codes)
+    torch.cuda.synchronize()
+    assert bool((obuf == -7.5).all()) and bool((cbuf == 0xA5).all())
+    assert torch.equal(ident, identity)

@@ -55,3 +55,20 @@ def test_exact_construction_small():
     for k in [k for k in sd if k.endswith("scale")]:          # every scale a power of two
         v = sd[k].double()
         assert torch.equal(torch.exp2(torch.round(torch.log2(v))), v), k
+
+
+@pytest.mark.parametrize("kw,size,paths", [(dict(image_size=(224, 320)), (224, 320), [1] * 7 + [0] * 9),
+                                           (dict(width=32), (224, 224), [0] * 3 + [1] * 10 + [0] * 3),
+                                           (dict(image_size=200), (200, 200), [0] * 13 + [1] * 3)])
+def test_block_end_plans_off_the_224_geometry(kw, size, paths):
+    """The host-side plan of every block end of the exact ResNet-50 models the GPU tests run at other geometries (no device
+    work: the plan reads shapes and alignments only), and the block-end shapes it is made for."""
+    sd = exact_state_dict("resnet50", seed=20, **kw)
+    model = PackedResNet.from_state_dict(sd)
+    assert model.residual_paths(2, *size) == paths
+    H, W = (size[0] + 3) // 4, (size[1] + 3) // 4          # stem and maxpool: stride 2 each, both rounding up
+    shapes = model.block_end_shapes(2, *size)
+    for i, (b, sh) in enumerate(shapes):
+        if b.stride == 2:
+            H, W = (H + 1) // 2, (W + 1) // 2
+        assert (sh.N, sh.H, sh.W, sh.OC) == (2, H, W, b.convs[-1].OC), (b.name, sh.H, sh.W)

@@ -42,8 +42,10 @@ def _engine(sd):
 
 
 def _images(N, seed, size=224):
+    """N x 3 x H x W normal images; size is one side or (H, W)."""
+    H, W = (size, size) if isinstance(size, int) else size
     g = torch.Generator(device="cpu").manual_seed(seed)
-    return torch.randn(N, 3, size, size, generator=g)
+    return torch.randn(N, 3, H, W, generator=g)
 
 
 def _first_departure(model, ref, x):
@@ -153,6 +155,31 @@ def test_resnet50_batch256(r50):
             assert torch.equal(lf[i:i + 1], ref.logits.float()), "batch-256 row %d: logits differ from float64" % i
     assert ties > 0
     print("h: ResNet-50 W8A8 N=256, rows 0 / 131 / 255: %d exact ties" % ties)
+
+
+# Off the 224 x 224 ResNet-50 geometry: non-square images, a narrower network and odd plane sizes move the block ends onto
+# other resident-tile instances or off them.  Each model is calibrated at the geometry it runs.
+GEOMETRIES = [
+    # label, exact_state_dict arguments, image size, block-end paths at N = 2
+    ("i: ResNet-50 at 224x320", dict(image_size=(224, 320)), (224, 320),
+     [1] * 7 + [0] * 9),             # layer1 56x80 on <4,2,224>, layer2 28x40 on <4,4,224>; 14x20 and 7x10: two passes
+    ("j: ResNet-50 width 32", dict(width=32), (224, 224),
+     [0] * 3 + [1] * 10 + [0] * 3),  # IC = 32 and 256 -> 1024 @7x7 take two passes; layer2 on <4,2,196>, layer3 <4,4,196>
+    ("k: ResNet-50 at 200x200", dict(image_size=200), (200, 200),
+     [0] * 13 + [1] * 3),            # planes 50 / 25 / 13 / 7: every stride-2 layer rounds; only layer4 (pwr7) fuses
+]
+
+
+@pytest.mark.parametrize("label,kw,size,paths", GEOMETRIES, ids=["224x320", "width32", "200x200"])
+def test_resnet50_other_geometries(label, kw, size, paths):
+    sd = exact_state_dict("resnet50", seed=20, **kw)
+    model = _engine(sd)
+    assert model.residual_paths(2, *size) == paths
+    ref = _check(model, Float64ResNet(sd), _images(2, 21, size), label)
+    H, W = size
+    for _ in range(5):
+        H, W = (H + 1) // 2, (W + 1) // 2
+    assert tuple(ref.features.shape[2:]) == (H, W)
 
 
 @pytest.mark.parametrize("case", ["m_bottleneck", "m_basic"])
