@@ -291,6 +291,82 @@ int qe_quantlinear_path(const qe_qparam *x, const qe_qparam *w, int64_t B, int32
  * fp32 accumulation rounding of the exact sum; QE_LIN_F32_MFMA=0 disables it). */
 int qe_quantlinear_float_input_path(const float *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O);
 
+/* ---- fused ViT forms ---------------------------------------------------------------------------
+ * What runs between the GEMMs of a ViT encoder block (torchvision's EncoderBlock around the reference's QuantLinear /
+ * QuantMultiheadAttention: x + attn(ln_1(x)), then y + mlp(ln_2(y)) with mlp = fc1, GELU, fc2) fused into the linears'
+ * epilogues or into one pass over a row.  Activation functions applied in front of a consumer's quantiser:          */
+enum qe_act { QE_ACT_NONE = 0, QE_ACT_GELU = 1 };   /* GELU: torch's exact form x * 0.5 * (1 + erf(x / sqrt(2))), fp32 */
+
+/* qe_quantize_pack_act -- qe_quantize_pack of act(x).
+ * y      optional fp32[n] output of act(x) (NULL: codes only); y == x (in place) or disjoint.
+ * out    the codes: bit-identical to qe_quantize_pack(act(x), ...) (same per-element fp32 arithmetic); with
+ *        act == QE_ACT_NONE and y == NULL this IS qe_quantize_pack.  Other arguments and `status` as qe_quantize_pack. */
+int qe_quantize_pack_act(const float *x, int64_t n, int32_t act, const float *scale, const float *zero, int32_t n_param,
+                         int64_t inner, float qmin, float qmax, int n_bits, int sign, uint8_t *out, float *y,
+                         int32_t *status, qe_stream_t stream);
+
+/* qe_quantlinear_requant -- qe_quantlinear with the consumer's quantiser (and optionally GELU) fused into the epilogue:
+ *   codes = qe_quantize_pack_act(qe_quantlinear(x, w, bias, B, K, O), act, rq)      (bit for bit; B x O row-major elements)
+ * rq     module convention (q = round(v / scale - zero).clamp(qmin, qmax)); n_param 1 (per tensor) or O (per output
+ *        feature).  codes: qe_packed_nbytes(B * O, rq->n_bits) bytes.  status as qe_tpack.
+ * qe_quantlinear_requant_path: 1 = the int8 MFMA kernel stores the codes itself (qe_quantlinear_path == 1, rq 8-bit per
+ *        tensor, codes 16-byte aligned, QE_LIN_EPI not 0); 0 = two passes inside the call (qe_quantlinear into the
+ *        workspace, then qe_quantize_pack_act).
+ * workspace  qe_quantlinear_requant_workspace_bytes() bytes (0 on path 1), 16-byte aligned.                           */
+int qe_quantlinear_requant_path(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O,
+                                const qe_requant *rq, const uint8_t *codes);
+size_t qe_quantlinear_requant_workspace_bytes(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O,
+                                              const qe_requant *rq, const uint8_t *codes);
+int qe_quantlinear_requant(const qe_qparam *x, const qe_qparam *w, const float *bias, int64_t B, int32_t K, int32_t O,
+                           int32_t act, const qe_requant *rq, uint8_t *codes, int32_t *status,
+                           void *workspace, size_t workspace_bytes, qe_stream_t stream);
+
+/* qe_quantlinear_residual / qe_quantlinear_float_input_residual -- a linear with the residual add fused into the epilogue:
+ *   out = qe_quantlinear(...) + residual       (resp. qe_quantlinear_float_input; one fp32 add, bit for bit)
+ * residual, out  fp32[B * O]; out == residual (in place) is allowed, any other overlap returns QE_ERR_ARG.
+ * _path: 1 = the MFMA kernel adds the residual in its epilogue (qe_quantlinear_path == 1, resp.
+ *        qe_quantlinear_float_input_path == 1, and QE_LIN_EPI not 0); 0 = the linear into the workspace, then one
+ *        elementwise add.  workspace: _workspace_bytes() bytes (0 on path 1), 16-byte aligned.                         */
+int qe_quantlinear_residual_path(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O);
+size_t qe_quantlinear_residual_workspace_bytes(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O);
+int qe_quantlinear_residual(const qe_qparam *x, const qe_qparam *w, const float *bias, int64_t B, int32_t K, int32_t O,
+                            const float *residual, float *out, void *workspace, size_t workspace_bytes, qe_stream_t stream);
+int qe_quantlinear_float_input_residual_path(const float *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O);
+size_t qe_quantlinear_float_input_residual_workspace_bytes(const float *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O);
+int qe_quantlinear_float_input_residual(const float *x, const qe_qparam *w, const float *bias, int64_t B, int32_t K, int32_t O,
+                                        const float *residual, float *out, void *workspace, size_t workspace_bytes,
+                                        qe_stream_t stream);
+
+/* qe_layernorm_quantize_pack -- torch's F.layer_norm over the last dimension of fp32 rows (rows x E, contiguous) and the
+ * codes of up to 3 consumer quantisers of the result (q / k / v projections: each its own), reading each row once.
+ *   ln = (x - mean) * rstd * gamma + beta, mean = sum(x) / E, var = sum((x - mean)^2) / E (centred: not E[x^2] - mean^2),
+ *   rstd = 1 / sqrtf(var + eps) (correctly rounded division and square root).
+ * gamma, beta   fp32[E] (NULL: 1 and 0).
+ * n_out, rq[], codes[]  n_out in 0..3 host arrays: rq[i] (module convention, per tensor or n_param == E) and codes[i]
+ *        (device, qe_packed_nbytes(rows * E, rq[i].n_bits) bytes).  codes[i] is bit-identical to
+ *        qe_quantize_pack(ln, rq[i]) of the fp32 ln this call computes.
+ * ln_out optional fp32[rows * E] (NULL: codes only).  status as qe_tpack.
+ * Supported: E % 4 == 0, 4 <= E <= QE_LN_MAX_E; other shapes return QE_ERR_UNSUPPORTED.
+ * _path: 1 = one pass (every rq 8-bit per tensor, codes 4-byte aligned); 0 = the fp32 ln (into ln_out, or the workspace
+ *        when ln_out is NULL) and then qe_quantize_pack per consumer.  workspace: _workspace_bytes() bytes, 16-byte aligned. */
+#define QE_LN_MAX_E 2048
+int qe_layernorm_quantize_pack_path(int64_t rows, int32_t E, int32_t n_out, const qe_requant *rq, uint8_t *const *codes);
+size_t qe_layernorm_quantize_pack_workspace_bytes(int64_t rows, int32_t E, int32_t n_out, const qe_requant *rq,
+                                                  uint8_t *const *codes, const float *ln_out);
+int qe_layernorm_quantize_pack(const float *x, int64_t rows, int32_t E, const float *gamma, const float *beta, float eps,
+                               int32_t n_out, const qe_requant *rq, uint8_t *const *codes, float *ln_out, int32_t *status,
+                               void *workspace, size_t workspace_bytes, qe_stream_t stream);
+
+/* qe_quantize_patchify -- the image quantiser of a ViT's patch embedding (conv_proj: kernel = stride = p, no padding) and
+ * the unfold, in one pass: fp32 NCHW images (N, C, H, W; H % p == W % p == 0) -> packed codes of the (N*(H/p)*(W/p)) x
+ * (C*p*p) patch matrix, row n*(H/p)*(W/p) + ph*(W/p) + pw, column c*p*p + kh*p + kw -- the OIHW K order of the conv's
+ * packed weights, so qe_quantlinear(codes, conv weights) is conv_proj with its output already in token order.
+ * Bit-identical to qe_quantize_pack of the unfolded fp32 matrix.  scale/zero: n_param 1 (per tensor) or C (per input
+ * channel); any n_bits.  status as qe_tpack.                                                                            */
+int qe_quantize_patchify(const float *x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t patch, const float *scale,
+                         const float *zero, int32_t n_param, float qmin, float qmax, int n_bits, int sign, uint8_t *out,
+                         int32_t *status, qe_stream_t stream);
+
 /* ---- auxiliary (no counterpart in the reference's extension) ---------------------------------
  * Global average pool of an fp32 NCHW tensor: out[plane] = mean(x[plane][0..P)) for n_planes = N*C planes of P
  * contiguous floats.  The reference's models do this in PyTorch (torchvision ResNet: AdaptiveAvgPool2d); bench.py's

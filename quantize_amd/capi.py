@@ -25,7 +25,14 @@ SYMBOLS = ["qe_error_string", "qe_last_hip_error", "qe_version", "qe_target_arch
            "qe_quantconv2d_float_input_ws", "qe_conv_f32_prepare", "qe_quantconv2d_float_input_prepared",
            "qe_quantconv2d_float_input_path", "qe_quantconv2d_requant_path", "qe_quantconv2d_requant_workspace_bytes",
            "qe_quantconv2d_requant_prepared", "qe_conv_prepared_layout", "qe_quantconv2d_residual_path",
-           "qe_quantconv2d_residual_workspace_bytes", "qe_quantconv2d_residual_prepared", "qe_maxpool2d_codes"]
+           "qe_quantconv2d_residual_workspace_bytes", "qe_quantconv2d_residual_prepared", "qe_maxpool2d_codes",
+           "qe_quantize_pack_act", "qe_quantlinear_requant_path", "qe_quantlinear_requant_workspace_bytes", "qe_quantlinear_requant",
+           "qe_quantlinear_residual_path", "qe_quantlinear_residual_workspace_bytes", "qe_quantlinear_residual",
+           "qe_quantlinear_float_input_residual_path", "qe_quantlinear_float_input_residual_workspace_bytes",
+           "qe_quantlinear_float_input_residual", "qe_layernorm_quantize_pack_path", "qe_layernorm_quantize_pack_workspace_bytes",
+           "qe_layernorm_quantize_pack", "qe_quantize_patchify"]
+
+ACTS = {None: 0, "none": 0, "gelu": 1}
 
 
 class QeConvShape(ctypes.Structure):
@@ -122,6 +129,36 @@ def lib():
     L.qe_quantconv2d_residual_prepared.argtypes = [pq, pq, vp, ps, vp, sz, vp, vp, pr, vp, vp, vp, sz, vp]
     L.qe_maxpool2d_codes.restype = i32
     L.qe_maxpool2d_codes.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]
+    f32 = ctypes.c_float
+    L.qe_quantize_pack_act.restype = i32
+    L.qe_quantize_pack_act.argtypes = [vp, i64, i32, vp, vp, i32, i64, f32, f32, i32, i32, vp, vp, vp, vp]
+    L.qe_quantlinear_requant_path.restype = i32
+    L.qe_quantlinear_requant_path.argtypes = [pq, pq, i64, i32, i32, pr, vp]
+    L.qe_quantlinear_requant_workspace_bytes.restype = sz
+    L.qe_quantlinear_requant_workspace_bytes.argtypes = [pq, pq, i64, i32, i32, pr, vp]
+    L.qe_quantlinear_requant.restype = i32
+    L.qe_quantlinear_requant.argtypes = [pq, pq, vp, i64, i32, i32, i32, pr, vp, vp, vp, sz, vp]
+    L.qe_quantlinear_residual_path.restype = i32
+    L.qe_quantlinear_residual_path.argtypes = [pq, pq, i64, i32, i32]
+    L.qe_quantlinear_residual_workspace_bytes.restype = sz
+    L.qe_quantlinear_residual_workspace_bytes.argtypes = [pq, pq, i64, i32, i32]
+    L.qe_quantlinear_residual.restype = i32
+    L.qe_quantlinear_residual.argtypes = [pq, pq, vp, i64, i32, i32, vp, vp, vp, sz, vp]
+    L.qe_quantlinear_float_input_residual_path.restype = i32
+    L.qe_quantlinear_float_input_residual_path.argtypes = [vp, pq, i64, i32, i32]
+    L.qe_quantlinear_float_input_residual_workspace_bytes.restype = sz
+    L.qe_quantlinear_float_input_residual_workspace_bytes.argtypes = [vp, pq, i64, i32, i32]
+    L.qe_quantlinear_float_input_residual.restype = i32
+    L.qe_quantlinear_float_input_residual.argtypes = [vp, pq, vp, i64, i32, i32, vp, vp, vp, sz, vp]
+    ppc = ctypes.POINTER(ctypes.c_void_p)
+    L.qe_layernorm_quantize_pack_path.restype = i32
+    L.qe_layernorm_quantize_pack_path.argtypes = [i64, i32, i32, pr, ppc]
+    L.qe_layernorm_quantize_pack_workspace_bytes.restype = sz
+    L.qe_layernorm_quantize_pack_workspace_bytes.argtypes = [i64, i32, i32, pr, ppc, vp]
+    L.qe_layernorm_quantize_pack.restype = i32
+    L.qe_layernorm_quantize_pack.argtypes = [vp, i64, i32, vp, vp, f32, i32, pr, ppc, vp, vp, vp, sz, vp]
+    L.qe_quantize_patchify.restype = i32
+    L.qe_quantize_patchify.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, f32, f32, i32, i32, vp, vp, vp]
     _lib = L
     return L
 
@@ -428,3 +465,140 @@ def global_avgpool(x, out=None, stream=None):
         out = torch.empty((N, C), dtype=torch.float32, device=x.device)
     check(lib().qe_global_avgpool(x.data_ptr(), N * C, H * W, out.data_ptr(), _stream(stream)))
     return out
+
+
+# ---- fused ViT forms ----------------------------------------------------------------------------------------------
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _ws(need, dev):
+    import torch
+    return torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+
+
+def _status(status, dev):
+    import torch
+    return torch.zeros(1, dtype=torch.int32, device=dev) if status is None else status
+
+
+def quantize_pack_act(x, scale, zero, qmin, qmax, n_bits, sign, act=None, inner=1, out=None, y=None, status=None, stream=None):
+    """qe_quantize_pack_act: codes of act(x) (act None | "gelu"); y: optional fp32 output of act(x) (a tensor, or "new").
+    Returns (codes, y or None, status)."""
+    import torch
+    assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and scale.numel() == zero.numel()
+    n = x.numel()
+    if out is None:
+        out = torch.empty(packed_nbytes(n, n_bits), dtype=torch.uint8, device=x.device)
+    if isinstance(y, str):
+        y = torch.empty_like(x)
+    status = _status(status, x.device)
+    check(lib().qe_quantize_pack_act(x.data_ptr(), n, ACTS[act], scale.data_ptr(), zero.data_ptr(), int(scale.numel()), int(inner),
+                                     float(qmin), float(qmax), int(n_bits), 1 if sign else 0, out.data_ptr(), _ptr(y),
+                                     status.data_ptr(), _stream(stream)))
+    return out, y, status
+
+
+def linear_requant_path(xq, wq, B, K, O, rq, codes=None):
+    """1: the MFMA kernel writes the codes itself.  codes=None asks for a 16-byte aligned buffer (torch allocations are)."""
+    return int(lib().qe_quantlinear_requant_path(ctypes.byref(xq), ctypes.byref(wq), int(B), int(K), int(O), ctypes.byref(rq),
+                                                 codes.data_ptr() if codes is not None else 256))
+
+
+def quantlinear_requant(xq, wq, bias, B, K, O, rq, act=None, codes=None, status=None, stream=None):
+    """qe_quantlinear_requant: the consumer's codes of act(quantlinear(...)) (B x O elements).  Returns (codes, status)."""
+    import torch
+    dev = wq._keep[0].device
+    if codes is None:
+        codes = torch.empty(packed_nbytes(B * O, rq.n_bits), dtype=torch.uint8, device=dev)
+    status = _status(status, dev)
+    need = int(lib().qe_quantlinear_requant_workspace_bytes(ctypes.byref(xq), ctypes.byref(wq), int(B), int(K), int(O),
+                                                            ctypes.byref(rq), codes.data_ptr()))
+    ws = _ws(need, dev)
+    check(lib().qe_quantlinear_requant(ctypes.byref(xq), ctypes.byref(wq), _ptr(bias), int(B), int(K), int(O), ACTS[act],
+                                       ctypes.byref(rq), codes.data_ptr(), status.data_ptr(), _ptr(ws), need, _stream(stream)))
+    return codes, status
+
+
+def linear_residual_path(xq, wq, B, K, O):
+    return int(lib().qe_quantlinear_residual_path(ctypes.byref(xq), ctypes.byref(wq), int(B), int(K), int(O)))
+
+
+def quantlinear_residual(xq, wq, bias, B, K, O, residual, out=None, stream=None):
+    """qe_quantlinear_residual: out = quantlinear(...) + residual (out=None: a new tensor; out=residual: in place)."""
+    import torch
+    assert residual.is_contiguous() and residual.dtype == torch.float32 and residual.numel() == B * O
+    dev = residual.device
+    if out is None:
+        out = torch.empty((B, O), dtype=torch.float32, device=dev)
+    need = int(lib().qe_quantlinear_residual_workspace_bytes(ctypes.byref(xq), ctypes.byref(wq), int(B), int(K), int(O)))
+    ws = _ws(need, dev)
+    check(lib().qe_quantlinear_residual(ctypes.byref(xq), ctypes.byref(wq), _ptr(bias), int(B), int(K), int(O), residual.data_ptr(),
+                                        out.data_ptr(), _ptr(ws), need, _stream(stream)))
+    return out
+
+
+def linear_float_input_residual_path(x, wq, B, K, O):
+    return int(lib().qe_quantlinear_float_input_residual_path(x.data_ptr(), ctypes.byref(wq), int(B), int(K), int(O)))
+
+
+def quantlinear_float_input_residual(x, wq, bias, O, residual, out=None, stream=None):
+    """qe_quantlinear_float_input_residual: out = quantlinear_float_input(x, ...) + residual."""
+    import torch
+    assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and x.dim() == 2
+    B, K = x.shape
+    assert residual.is_contiguous() and residual.dtype == torch.float32 and residual.numel() == B * O
+    if out is None:
+        out = torch.empty((B, O), dtype=torch.float32, device=x.device)
+    need = int(lib().qe_quantlinear_float_input_residual_workspace_bytes(x.data_ptr(), ctypes.byref(wq), int(B), int(K), int(O)))
+    ws = _ws(need, x.device)
+    check(lib().qe_quantlinear_float_input_residual(x.data_ptr(), ctypes.byref(wq), _ptr(bias), int(B), int(K), int(O),
+                                                    residual.data_ptr(), out.data_ptr(), _ptr(ws), need, _stream(stream)))
+    return out
+
+
+def _rq_array(rqs):
+    arr = (QeRequant * max(1, len(rqs)))(*rqs) if rqs else None
+    return arr
+
+
+def layernorm_path(rows, E, rqs, codes):
+    arr = _rq_array(rqs)
+    cp = (ctypes.c_void_p * max(1, len(codes)))(*[c.data_ptr() for c in codes])
+    return int(lib().qe_layernorm_quantize_pack_path(int(rows), int(E), len(rqs), arr, cp))
+
+
+def layernorm_quantize_pack(x, gamma, beta, eps, rqs=(), ln_out=None, codes=None, status=None, stream=None):
+    """qe_layernorm_quantize_pack over the last dimension of x: the codes of every quantiser in rqs (a list of capi.requant),
+    and the fp32 LayerNorm when ln_out is a tensor or "new".  Returns (list of codes, ln_out or None, status)."""
+    import torch
+    assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32
+    E = x.shape[-1]
+    rows = x.numel() // E
+    rqs = list(rqs)
+    if isinstance(ln_out, str):
+        ln_out = torch.empty_like(x)
+    if codes is None:
+        codes = [torch.empty(packed_nbytes(rows * E, r.n_bits), dtype=torch.uint8, device=x.device) for r in rqs]
+    status = _status(status, x.device)
+    arr = _rq_array(rqs)
+    cp = (ctypes.c_void_p * max(1, len(codes)))(*[c.data_ptr() for c in codes])
+    need = int(lib().qe_layernorm_quantize_pack_workspace_bytes(int(rows), int(E), len(rqs), arr, cp, _ptr(ln_out)))
+    ws = _ws(need, x.device)
+    check(lib().qe_layernorm_quantize_pack(x.data_ptr(), int(rows), int(E), _ptr(gamma), _ptr(beta), float(eps), len(rqs), arr, cp,
+                                           _ptr(ln_out), status.data_ptr(), _ptr(ws), need, _stream(stream)))
+    return codes, ln_out, status
+
+
+def quantize_patchify(x, patch, scale, zero, qmin, qmax, n_bits, sign, out=None, status=None, stream=None):
+    """qe_quantize_patchify: NCHW images -> packed codes of the (N (H/p) (W/p)) x (C p p) patch matrix.  Returns (codes, status)."""
+    import torch
+    assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and x.dim() == 4 and scale.numel() == zero.numel()
+    N, C, H, W = x.shape
+    if out is None:
+        out = torch.empty(packed_nbytes(x.numel(), n_bits), dtype=torch.uint8, device=x.device)
+    status = _status(status, x.device)
+    check(lib().qe_quantize_patchify(x.data_ptr(), N, C, H, W, int(patch), scale.data_ptr(), zero.data_ptr(), int(scale.numel()),
+                                     float(qmin), float(qmax), int(n_bits), 1 if sign else 0, out.data_ptr(), status.data_ptr(),
+                                     _stream(stream)))
+    return out, status

@@ -14,6 +14,7 @@
 // goes to an order-preserving fp32 kernel that reproduces the reference's k-sequential chain bit for bit
 // (with fused multiply-add, as nvcc contracts it).
 #include "qe_common.h"
+#include "qe_elementwise.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -61,7 +62,45 @@ struct LinArgs {
     int K, O;
     float *out;
     unsigned long long *dbg;
+    // fused epilogues of the MFMA kernels (template parameter EPI; the LIN_F32 instances never read these)
+    const float *res;       // LIN_RES: out = y + res (res == out allowed)
+    uint8_t *codes;         // LIN_CODES*: B x O stored 8-bit codes of a per-tensor consumer quantiser
+    int32_t *status;        // LIN_CODES*: bit 0 set when a code fails the range test (NaN included)
+    QeRq rq;
 };
+
+// Epilogue of an MFMA linear kernel, a template parameter and never a runtime branch: what leaves
+// the kernel is y (LIN_F32), y + res in fp32 (LIN_RES), or the consumer's 8-bit codes of y / gelu(y) (LIN_CODES,
+// LIN_CODES_GELU), computed with qe_elementwise.hpp's functions -- the ones qe_quantize_pack_act runs -- so each fused form
+// is bit-identical to its two-pass form.  Codes go through the wave's LDS patch and leave as 16-byte row pieces.
+enum { LIN_F32 = 0, LIN_CODES = 1, LIN_CODES_GELU = 2, LIN_RES = 3 };
+template <int EPI> constexpr bool lin_codes() { return EPI == LIN_CODES || EPI == LIN_CODES_GELU; }
+template <int EPI> constexpr int lin_act() { return EPI == LIN_CODES_GELU ? QE_ACT_GELU : QE_ACT_NONE; }
+// 16 consecutive outputs in LDS (p[0..15]) -> their 16 stored codes.  Plain codes: four float4 reads, unrolled.  GELU: a loop
+// that is NOT unrolled, one value per trip -- unrolled, the erf bodies (each with its own branch and exp) of every tile
+// spilled the live accumulators to scratch -- the codes shifted in from the top of the 16-byte piece.
+template <int EPI>
+__device__ __forceinline__ uint4 lin_codes16(const float *p, float sc, float zr, const QeRq &q, bool &bad)
+{
+    if constexpr (lin_act<EPI>() == QE_ACT_GELU) {
+        uint32_t x = 0, y = 0, z = 0, w = 0;
+#pragma unroll 1
+        for (int t = 0; t < 16; ++t) {
+            const uint32_t c = qe_rq_code(qe_gelu(p[t]), sc, zr, q, bad);
+            x = (x >> 8) | (y << 24); y = (y >> 8) | (z << 24); z = (z >> 8) | (w << 24); w = (w >> 8) | (c << 24);
+        }
+        return make_uint4(x, y, z, w);
+    } else {
+        uint32_t cw[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float4 f = *reinterpret_cast<const float4 *>(p + 4 * k);
+            cw[k] = qe_rq_code(f.x, sc, zr, q, bad) | (qe_rq_code(f.y, sc, zr, q, bad) << 8) |
+                    (qe_rq_code(f.z, sc, zr, q, bad) << 16) | (qe_rq_code(f.w, sc, zr, q, bad) << 24);
+        }
+        return make_uint4(cw[0], cw[1], cw[2], cw[3]);
+    }
+}
 
 // ---------------------------------------------------------------------------------------------
 // Order-preserving fp32 kernel.  32x32 output tile per 256 threads (4 outputs per thread), 32-deep K
@@ -150,7 +189,7 @@ constexpr int L_PA = LM * (LK / 16) / 256;   // A pieces per thread per stage (2
 constexpr int L_RING = 3;
 
 // NJ = column tiles per wave: 4 (tile 128 x 256, 2 workgroups per CU) or 2 (tile 128 x 128, 3 per CU).
-template <int NJ>
+template <int NJ, int EPI = LIN_F32>
 __global__ __launch_bounds__(256, 2) void linear_mfma_kernel(const LinArgs a)
 {
     constexpr int LN = 64 * NJ;
@@ -293,9 +332,16 @@ __global__ __launch_bounds__(256, 2) void linear_mfma_kernel(const LinArgs a)
     // dword store of two 128-byte row pieces, and the store phase (128 instructions per lane) was 40 % of a wave's
     // life.  Each wave therefore turns its 32 x 32 tiles through a private LDS patch (the operand ring is free
     // now) and writes 8 rows x 128 contiguous bytes per global_store_dwordx4: 4x fewer store instructions.
-    const bool vec4 = (a.O & 3) == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0;
+    bool vec4;
+    if constexpr (lin_codes<EPI>()) vec4 = (a.O & 15) == 0 && (reinterpret_cast<uintptr_t>(a.codes) & 15) == 0;
+    else if constexpr (EPI == LIN_RES)
+        vec4 = (a.O & 3) == 0 && ((reinterpret_cast<uintptr_t>(a.out) | reinterpret_cast<uintptr_t>(a.res)) & 15) == 0;
+    else vec4 = (a.O & 3) == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0;
     float *patch = reinterpret_cast<float *>(lsm) + wave * (32 * 36);
     const int rrow = lane >> 3, rq = lane & 7;
+    bool bad = false;                                     // LIN_CODES*: range flag of this lane's codes
+    float rsc = 0.0f, rzr = 0.0f;
+    if constexpr (lin_codes<EPI>()) { rsc = a.rq.scale[0]; rzr = a.rq.zero[0]; }
     // Two instances, the choice made once per workgroup: a (wave-uniform) bounds test per tile is a branch per tile, and hipcc
     // opens every block behind a branch with s_waitcnt vmcnt(0) in kernels with LDS-DMA in a loop -- a drain of all outstanding
     // stores in front of every tile (found in linear_mfma8_kernel's epilogue, see there).
@@ -321,15 +367,37 @@ __global__ __launch_bounds__(256, 2) void linear_mfma_kernel(const LinArgs a)
                     v[r] = fmaf(rc.x * cc.x, t, cc.z);
                 }
                 const int64_t row0 = m0 + wm * 64 + i * 32;
-                if constexpr (FULL) {
+                if constexpr (lin_codes<EPI>()) {
+                    // y through the fp32 patch; lane (row lane >> 1, half lane & 1) turns 16 consecutive values of its row into
+                    // codes (lin_codes16) and stores them as one piece
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) patch[((r & 3) + 8 * (r >> 2) + 4 * h) * 36 + col] = v[r];
+                    const uint4 c16 = lin_codes16<EPI>(patch + (lane >> 1) * 36 + 16 * (lane & 1), rsc, rzr, a.rq, bad);
+                    const int64_t row = row0 + (lane >> 1);
+                    const int cb = n0 + wn * 32 * NJ + j * 32 + 16 * (lane & 1);
+                    uint8_t *dst = a.codes + row * a.O + cb;
+                    if constexpr (FULL) *reinterpret_cast<uint4 *>(dst) = c16;
+                    else if (row < a.B) {
+                        if (vec4 && cb + 16 <= a.O) *reinterpret_cast<uint4 *>(dst) = c16;
+                        else {
+                            const uint32_t ww[4] = {c16.x, c16.y, c16.z, c16.w};
+                            for (int b = 0; b < 16 && cb + b < a.O; ++b) dst[b] = (uint8_t)(ww[b >> 2] >> ((b & 3) * 8));
+                        }
+                    }
+                } else if constexpr (FULL) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) patch[((r & 3) + 8 * (r >> 2) + 4 * h) * 36 + col] = v[r];
                     const int c4 = n0 + wn * 32 * NJ + j * 32 + 4 * rq;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         const int rt = 8 * k + rrow;
-                        const float4 o4 = *reinterpret_cast<const float4 *>(patch + rt * 36 + 4 * rq);
+                        float4 o4 = *reinterpret_cast<const float4 *>(patch + rt * 36 + 4 * rq);
+                        if constexpr (EPI == LIN_RES) {
+                            const float4 r4 = *reinterpret_cast<const float4 *>(a.res + (row0 + rt) * a.O + c4);
+                            o4.x += r4.x; o4.y += r4.y; o4.z += r4.z; o4.w += r4.w;
+                        }
                         *reinterpret_cast<float4 *>(a.out + (row0 + rt) * a.O + c4) = o4;
+                        if constexpr (EPI == LIN_RES) __builtin_amdgcn_sched_barrier(0);   // one residual piece in flight (else scratch)
                     }
                 } else if (vec4) {
 #pragma unroll
@@ -338,15 +406,26 @@ __global__ __launch_bounds__(256, 2) void linear_mfma_kernel(const LinArgs a)
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         const int rt = 8 * k + rrow;
-                        const float4 o4 = *reinterpret_cast<const float4 *>(patch + rt * 36 + 4 * rq);
+                        float4 o4 = *reinterpret_cast<const float4 *>(patch + rt * 36 + 4 * rq);
                         const int64_t row = row0 + rt;
-                        if (row < a.B && c4 < a.O) *reinterpret_cast<float4 *>(a.out + row * a.O + c4) = o4;
+                        if (row < a.B && c4 < a.O) {
+                            if constexpr (EPI == LIN_RES) {
+                                const float4 r4 = *reinterpret_cast<const float4 *>(a.res + row * a.O + c4);
+                                o4.x += r4.x; o4.y += r4.y; o4.z += r4.z; o4.w += r4.w;
+                            }
+                            *reinterpret_cast<float4 *>(a.out + row * a.O + c4) = o4;
+                        }
+                        if constexpr (EPI == LIN_RES) __builtin_amdgcn_sched_barrier(0);
                     }
                 } else {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int64_t row = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                        if (row < a.B && c < a.O) a.out[row * a.O + c] = v[r];
+                        if (row < a.B && c < a.O) {
+                            if constexpr (EPI == LIN_RES) a.out[row * a.O + c] = v[r] + a.res[row * a.O + c];
+                            else a.out[row * a.O + c] = v[r];
+                        }
+                        if constexpr (EPI == LIN_RES) __builtin_amdgcn_sched_barrier(0);   // one residual load in flight (else scratch)
                     }
                 }
             }
@@ -354,6 +433,9 @@ __global__ __launch_bounds__(256, 2) void linear_mfma_kernel(const LinArgs a)
     };
     // (a wave's own LDS operations complete in order: its reads see its writes, a later tile's writes cannot overtake them)
     if (vec4 && m0 + LM <= a.B && n0 + LN <= a.O) tiles(std::true_type{}); else tiles(std::false_type{});
+    if constexpr (lin_codes<EPI>()) {
+        if (__builtin_amdgcn_ballot_w64(bad) != 0ull && lane == 0 && a.status != nullptr) atomicOr(a.status, 1);
+    }
 #ifdef QE_STAMP
     LIN_ST(6);   // epilogue issue
     __builtin_amdgcn_s_waitcnt(0x0f70);
@@ -399,7 +481,7 @@ template <int WMW> struct L8Geom {
     static constexpr size_t LDS = (size_t)RING * STAGE + (TM + L8_TN) * sizeof(float4);
 };
 
-template <int WMW>
+template <int WMW, int EPI = LIN_F32>
 __global__ __launch_bounds__(256 * WMW, WMW == 2 ? 1 : 2) void linear_mfma8_kernel(const LinArgs a)
 {
     using G = L8Geom<WMW>;
@@ -631,9 +713,34 @@ __global__ __launch_bounds__(256 * WMW, WMW == 2 ? 1 : 2) void linear_mfma8_kern
     float *patch0 = reinterpret_cast<float *>(lsm) + wave * (32 * 64);
     const int r4 = lane >> 4, q16 = lane & 15;
     const uint32_t voff = (uint32_t)r4 * (uint32_t)a.O + 4u * (uint32_t)q16;   // elements; r4 O + 64 < 2^31 (O < 2^29)
+    bool bad = false;                                     // LIN_CODES*: range flag of this lane's codes
+    float rsc = 0.0f, rzr = 0.0f;
+    if constexpr (lin_codes<EPI>()) { rsc = a.rq.scale[0]; rzr = a.rq.zero[0]; }
     auto tiles = [&](auto fast_tag, auto full_tag) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < 5; ++i) {
+            if constexpr (lin_codes<EPI>()) {
+                // the wave's 32 rows x 64 values of row tile i through the fp32 patch; lane (row 16 k + (lane >> 2), piece
+                // lane & 3) turns 16 consecutive values into codes (lin_codes16) and stores them with one instruction
+                // (O % 256 == 0 and codes 16-byte aligned: host)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    float v[16];
+                    convert(i, j, v, fast_tag);
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) patch0[((r & 3) + 8 * (r >> 2) + 4 * h) * 64 + j * 32 + col] = v[r];
+                }
+                const int64_t row0 = m0 + wm * 160 + i * 32;
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const int rr = 16 * k + (lane >> 2);
+                    const uint4 c16 = lin_codes16<EPI>(patch0 + rr * 64 + 16 * (lane & 3), rsc, rzr, a.rq, bad);
+                    uint8_t *dst = a.codes + (row0 + rr) * (int64_t)a.O + (n0 + wn * 64 + 16 * (lane & 3));
+                    if constexpr (decltype(full_tag)::value) *reinterpret_cast<uint4 *>(dst) = c16;
+                    else if (row0 + rr < a.B) *reinterpret_cast<uint4 *>(dst) = c16;
+                }
+                continue;
+            }
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 float v[16];
@@ -647,6 +754,13 @@ __global__ __launch_bounds__(256 * WMW, WMW == 2 ? 1 : 2) void linear_mfma8_kern
                 const float4 o4 = *reinterpret_cast<const float4 *>(patch0 + (4 * k + r4) * 64 + 4 * q16);
                 // wave-uniform base (scalar registers) + ONE per-lane 32-bit offset for all 40 stores of the wave
                 float *base = a.out + (row0 + 4 * k) * (int64_t)a.O + (n0 + wn * 64);
+                if constexpr (EPI == LIN_RES) {
+                    const float *rbase = a.res + (row0 + 4 * k) * (int64_t)a.O + (n0 + wn * 64);
+                    if (decltype(full_tag)::value || row0 + 4 * k + r4 < a.B) {
+                        const float4 r4v = *reinterpret_cast<const float4 *>(rbase + voff);
+                        *reinterpret_cast<float4 *>(base + voff) = make_float4(o4.x + r4v.x, o4.y + r4v.y, o4.z + r4v.z, o4.w + r4v.w);
+                    }
+                } else
                 if constexpr (decltype(full_tag)::value) *reinterpret_cast<float4 *>(base + voff) = o4;
                 else if (row0 + 4 * k + r4 < a.B) *reinterpret_cast<float4 *>(base + voff) = o4;
             }
@@ -655,6 +769,9 @@ __global__ __launch_bounds__(256 * WMW, WMW == 2 ? 1 : 2) void linear_mfma8_kern
     // O % 256 == 0 and `out` 16-byte aligned (host); only the LAST row tile can be ragged: it alone takes the form with a row test
     if (m0 + L8_TM <= a.B) { if (fast) tiles(std::true_type{}, std::true_type{}); else tiles(std::false_type{}, std::true_type{}); }
     else tiles(std::false_type{}, std::false_type{});
+    if constexpr (lin_codes<EPI>()) {
+        if (__builtin_amdgcn_ballot_w64(bad) != 0ull && lane == 0 && a.status != nullptr) atomicOr(a.status, 1);
+    }
 #ifdef QE_STAMP
     LIN_ST(6);   // epilogue issue
     __builtin_amdgcn_s_waitcnt(0x0f70);
@@ -686,6 +803,7 @@ constexpr int LF_T = 128, LF_K = 32;
 constexpr int LF_PLANE = LF_T * LF_K * 2;                 // bytes of one [128][32] bf16 image (8 KB)
 constexpr size_t linf_lds_bytes() { return (size_t)4 * LF_PLANE + LF_T * sizeof(float) + 2 * LF_T * sizeof(float4); }
 
+template <int EPI = LIN_F32>   // LIN_F32 | LIN_RES
 __global__ __launch_bounds__(256, 2) void linear_f32_mfma_kernel(const LinArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lsm[];   // 3 activation split images, 1 weight image, row sums, column constants
@@ -820,7 +938,10 @@ __global__ __launch_bounds__(256, 2) void linear_f32_mfma_kernel(const LinArgs a
                 const int rl = wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
                 const int64_t row = m0 + rl;
                 const float v = fmaf(cc.x, fmaf(-cc.y, rowsum[rl], acc[i][j][r]), cc.z);
-                if (row < a.B && c < a.O) a.out[row * a.O + c] = v;
+                if (row < a.B && c < a.O) {
+                    if constexpr (EPI == LIN_RES) a.out[row * a.O + c] = v + a.res[row * a.O + c];
+                    else a.out[row * a.O + c] = v;
+                }
             }
         }
     }
@@ -850,6 +971,59 @@ static bool lin_mfma_eligible(const qe_qparam *x, const qe_qparam *w, int64_t B,
 
 }  // namespace qe
 
+namespace qe {
+// The int8 MFMA forms of quantlinear (lin_mfma_eligible problems), one choice of kernel for every epilogue.  dst_aligned:
+// the epilogue's destination (out, or codes) is 16-byte aligned.
+template <int EPI>
+static int launch_lin_mfma(const LinArgs &a, bool dst_aligned, hipStream_t s)
+{
+    const int64_t B = a.B;
+    const int K = a.K, O = a.O;
+    // tile width: 256 columns unless that leaves the chip under-filled; QE_LIN_NJ=2|4 overrides (tuning)
+    int nj = 4;
+    if (((B + LM - 1) / LM) * ((O + 255) / 256) < kNumCU) nj = 2;   // under-filled chip (the ViT head: 8 workgroups): twice as many, half as wide (17.8 -> 11.5 us)
+    if (const char *e = env_get("QE_LIN_NJ")) nj = atoi(e) == 2 ? 2 : 4;
+    const int ln = 64 * nj;
+    const int64_t blocks = ((B + LM - 1) / LM) * ((O + ln - 1) / ln);
+    if (blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
+    // more than 64 KB of dynamic LDS needs the attribute once
+    static const bool raised =
+        hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_mfma_kernel<4, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lin_lds_bytes<4>()) == hipSuccess &&
+        hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_mfma_kernel<2, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lin_lds_bytes<2>()) == hipSuccess;
+    (void)raised;
+    // 128-deep stages: 320 x 256 tiles (one 8-wave workgroup per CU) when the reduction is deep, 160 x 256 tiles (two 4-wave
+    // workgroups per CU) when the layer is bound by its stores (K <= 1024) -- either when the problem fills the chip with
+    // them (O % 256 == 0: whole column tiles).  QE_LIN8=0: never, 1: the 8-wave form, 2: the 4-wave form
+    int big = 0;
+    if ((K % L8_K) == 0 && (O % L8_TN) == 0 && dst_aligned && B * (int64_t)K < (1ll << 32) &&
+        (int64_t)O * K < (1ll << 32) && O < (1 << 28)) {
+        // thresholds from tools/bench_linear.py at 256 / 64 / 16 images (profiles/r03zz_lin_small_batches.txt): the big tiles
+        // still win at 12,608 rows (120 / 237 tiles), the 64-deep kernel's smaller tiles at 3,152 rows unless O is wide
+        if (K > 1024 && (B / 320) * (O / L8_TN) >= kNumCU / 3) big = 1;
+        else if (K <= 1024 && (B / 160) * (O / L8_TN) >= kNumCU / 2) big = 2;
+        if (const char *e = env_get("QE_LIN8")) big = atoi(e);
+        if (big < 0 || big > 2) big = 0;
+    }
+    if (big != 0 && !env_get("QE_LIN_NJ")) {
+        static const bool raised8 =
+            hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_mfma8_kernel<2, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L8Geom<2>::LDS) == hipSuccess &&
+            hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_mfma8_kernel<1, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L8Geom<1>::LDS) == hipSuccess;
+        (void)raised8;
+        const int tm = big == 1 ? 320 : 160;
+        const int64_t blocks8 = ((B + tm - 1) / tm) * (O / L8_TN);
+        if (blocks8 > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
+        if (big == 1) hipLaunchKernelGGL((linear_mfma8_kernel<2, EPI>), dim3((unsigned)blocks8), dim3(512), L8Geom<2>::LDS, s, a);
+        else          hipLaunchKernelGGL((linear_mfma8_kernel<1, EPI>), dim3((unsigned)blocks8), dim3(256), L8Geom<1>::LDS, s, a);
+    } else
+    if (nj == 4) hipLaunchKernelGGL((linear_mfma_kernel<4, EPI>), dim3((unsigned)blocks), dim3(256), lin_lds_bytes<4>(), s, a);
+    else         hipLaunchKernelGGL((linear_mfma_kernel<2, EPI>), dim3((unsigned)blocks), dim3(256), lin_lds_bytes<2>(), s, a);
+    QE_LAUNCH_CHECK();
+    return QE_OK;
+}
+}  // namespace qe
+
 extern "C" int qe_quantlinear_path(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O)
 {
     if (x == nullptr || w == nullptr) return 0;
@@ -866,7 +1040,7 @@ extern "C" int qe_quantlinear(const qe_qparam *x, const qe_qparam *w, const floa
     if ((rc = check_lin_q(w, O)) != QE_OK) return rc;
     if (out == nullptr && B * O > 0) return QE_ERR_ARG;
     if (B == 0 || O == 0) return QE_OK;
-    LinArgs a;
+    LinArgs a = {};
     a.x = static_cast<const uint8_t *>(x->data); a.xf = nullptr; a.w = static_cast<const uint8_t *>(w->data);
     a.x_scale = x->scale; a.x_zero = x->zero; a.w_scale = w->scale; a.w_zero = w->zero; a.bias = bias;
     a.x_bits = x->n_bits; a.x_sign = x->sign; a.x_per_tensor = x->n_param == 1;
@@ -874,46 +1048,8 @@ extern "C" int qe_quantlinear(const qe_qparam *x, const qe_qparam *w, const floa
     a.B = B; a.K = K; a.O = O; a.out = out; a.dbg = g_mfma_dbg;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (lin_mfma_eligible(x, w, B, K, O)) {
-        // tile width: 256 columns unless that leaves the chip under-filled; QE_LIN_NJ=2|4 overrides (tuning)
-        int nj = 4;
-        if (((B + LM - 1) / LM) * ((O + 255) / 256) < kNumCU) nj = 2;   // under-filled chip (the ViT head: 8 workgroups): twice as many, half as wide (17.8 -> 11.5 us)
-        if (const char *e = env_get("QE_LIN_NJ")) nj = atoi(e) == 2 ? 2 : 4;
-        const int ln = 64 * nj;
-        const int64_t blocks = ((B + LM - 1) / LM) * ((O + ln - 1) / ln);
-        if (blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
-        // more than 64 KB of dynamic LDS needs the attribute once
-        static const bool raised =
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_mfma_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lin_lds_bytes<4>()) == hipSuccess &&
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_mfma_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lin_lds_bytes<2>()) == hipSuccess;
-        (void)raised;
-        // 128-deep stages: 320 x 256 tiles (one 8-wave workgroup per CU) when the reduction is deep, 160 x 256 tiles (two 4-wave
-        // workgroups per CU) when the layer is bound by its stores (K <= 1024) -- either when the problem fills the chip with
-        // them (O % 256 == 0: whole column tiles).  QE_LIN8=0: never, 1: the 8-wave form, 2: the 4-wave form
-        int big = 0;
-        if ((K % L8_K) == 0 && (O % L8_TN) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && B * (int64_t)K < (1ll << 32) &&
-            (int64_t)O * K < (1ll << 32) && O < (1 << 28)) {
-            // thresholds from tools/bench_linear.py at 256 / 64 / 16 images (profiles/r03zz_lin_small_batches.txt): the big tiles
-            // still win at 12,608 rows (120 / 237 tiles), the 64-deep kernel's smaller tiles at 3,152 rows unless O is wide
-            if (K > 1024 && (B / 320) * (O / L8_TN) >= kNumCU / 3) big = 1;
-            else if (K <= 1024 && (B / 160) * (O / L8_TN) >= kNumCU / 2) big = 2;
-            if (const char *e = env_get("QE_LIN8")) big = atoi(e);
-            if (big < 0 || big > 2) big = 0;
-        }
-        if (big != 0 && !env_get("QE_LIN_NJ")) {
-            static const bool raised8 =
-                hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_mfma8_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L8Geom<2>::LDS) == hipSuccess &&
-                hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_mfma8_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L8Geom<1>::LDS) == hipSuccess;
-            (void)raised8;
-            const int tm = big == 1 ? 320 : 160;
-            const int64_t blocks8 = ((B + tm - 1) / tm) * (O / L8_TN);
-            if (blocks8 > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
-            if (big == 1) hipLaunchKernelGGL(linear_mfma8_kernel<2>, dim3((unsigned)blocks8), dim3(512), L8Geom<2>::LDS, s, a);
-            else          hipLaunchKernelGGL(linear_mfma8_kernel<1>, dim3((unsigned)blocks8), dim3(256), L8Geom<1>::LDS, s, a);
-        } else
-        if (nj == 4) hipLaunchKernelGGL(linear_mfma_kernel<4>, dim3((unsigned)blocks), dim3(256), lin_lds_bytes<4>(), s, a);
-        else         hipLaunchKernelGGL(linear_mfma_kernel<2>, dim3((unsigned)blocks), dim3(256), lin_lds_bytes<2>(), s, a);
+        a.res = nullptr; a.codes = nullptr; a.status = nullptr;
+        return launch_lin_mfma<LIN_F32>(a, (reinterpret_cast<uintptr_t>(out) & 15) == 0, s);
     } else {
         const int64_t blocks = ((B + 31) / 32) * ((O + 31) / 32);
         if (blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
@@ -922,6 +1058,21 @@ extern "C" int qe_quantlinear(const qe_qparam *x, const qe_qparam *w, const floa
     QE_LAUNCH_CHECK();
     return QE_OK;
 }
+
+namespace qe {
+template <int EPI>
+static int launch_linf_mfma(const LinArgs &a, hipStream_t s)
+{
+    const int64_t blocks_m = ((a.B + LF_T - 1) / LF_T) * ((a.O + LF_T - 1) / LF_T);
+    if (blocks_m > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
+    static const bool raised_f = hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_f32_mfma_kernel<EPI>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)linf_lds_bytes()) == hipSuccess;
+    (void)raised_f;
+    hipLaunchKernelGGL(linear_f32_mfma_kernel<EPI>, dim3((unsigned)blocks_m), dim3(256), linf_lds_bytes(), s, a);
+    QE_LAUNCH_CHECK();
+    return QE_OK;
+}
+}  // namespace qe
 
 extern "C" int qe_quantlinear_float_input(const float *x, const qe_qparam *w, const float *bias,
                                           int64_t B, int32_t K, int32_t O, float *out, qe_stream_t stream)
@@ -932,21 +1083,15 @@ extern "C" int qe_quantlinear_float_input(const float *x, const qe_qparam *w, co
     if ((rc = check_lin_q(w, O)) != QE_OK) return rc;
     if ((x == nullptr && B * K > 0) || (out == nullptr && B * O > 0)) return QE_ERR_ARG;
     if (B == 0 || O == 0) return QE_OK;
-    LinArgs a;
+    LinArgs a = {};
     a.x = nullptr; a.xf = x; a.w = static_cast<const uint8_t *>(w->data);
     a.x_scale = nullptr; a.x_zero = nullptr; a.w_scale = w->scale; a.w_zero = w->zero; a.bias = bias;
     a.x_bits = 0; a.x_sign = 0; a.x_per_tensor = 1;
     a.w_bits = w->n_bits; a.w_sign = w->sign; a.w_per_tensor = w->n_param == 1;
     a.B = B; a.K = K; a.O = O; a.out = out; a.dbg = nullptr;
     if (linf_mfma_eligible(x, w, B, K, O)) {
-        const int64_t blocks_m = ((B + LF_T - 1) / LF_T) * ((O + LF_T - 1) / LF_T);
-        if (blocks_m > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
-        static const bool raised_f = hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_f32_mfma_kernel),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)linf_lds_bytes()) == hipSuccess;
-        (void)raised_f;
-        hipLaunchKernelGGL(linear_f32_mfma_kernel, dim3((unsigned)blocks_m), dim3(256), linf_lds_bytes(), static_cast<hipStream_t>(stream), a);
-        QE_LAUNCH_CHECK();
-        return QE_OK;
+        a.res = nullptr; a.codes = nullptr; a.status = nullptr;
+        return launch_linf_mfma<LIN_F32>(a, static_cast<hipStream_t>(stream));
     }
     const int64_t blocks = ((B + 31) / 32) * ((O + 31) / 32);
     if (blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
@@ -960,4 +1105,194 @@ extern "C" int qe_quantlinear_float_input_path(const float *x, const qe_qparam *
 {
     if (w == nullptr) return 0;
     return qe::linf_mfma_eligible(x, w, B, K, O) ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Fused ViT forms (include/quant_engine.h): the consumer's codes of y / gelu(y), and y + residual.  Path 1 is an MFMA
+// kernel with the epilogue compiled in; path 0 runs qe_quantlinear(_float_input) into the workspace and then the
+// elementwise pass whose arithmetic the epilogue shares.  QE_LIN_EPI=0 sends every call to path 0.
+// ---------------------------------------------------------------------------------------------
+namespace qe {
+static bool lin_epi_enabled()
+{
+    if (const char *e = env_get("QE_LIN_EPI")) return atoi(e) != 0;
+    return true;
+}
+
+static bool rq_fusable(const qe_requant *rq)
+{
+    return rq != nullptr && rq->n_bits == 8 && rq->n_param == 1 && rq->scale != nullptr && rq->zero != nullptr;
+}
+
+static QeRq make_rq(const qe_requant *rq)
+{
+    QeRq q;
+    q.scale = rq->scale; q.zero = rq->zero; q.qmin = rq->qmin; q.qmax = rq->qmax;
+    q.offset = rq->sign ? (1u << (rq->n_bits - 1)) : 0u;         // as launch_tpack_t
+    q.mask = (1u << rq->n_bits) - 1u;
+    q.lo = rq->sign ? -(float)(1 << (rq->n_bits - 1)) : 0.0f;
+    q.hi = rq->sign ? (float)((1 << (rq->n_bits - 1)) - 1) : (float)((1 << rq->n_bits) - 1);
+    return q;
+}
+
+// out = y + res, one fp32 add per element (path 0 of the residual forms); out may be res
+__global__ __launch_bounds__(256) void add_residual_kernel(const float *y, const float *res, float *out, int64_t n, int vec)
+{
+    const int64_t n4 = vec ? n / 4 : 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const float4 a = reinterpret_cast<const float4 *>(y)[i], b = reinterpret_cast<const float4 *>(res)[i];
+        reinterpret_cast<float4 *>(out)[i] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+    }
+    for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = y[i] + res[i];
+}
+
+static int launch_add_residual(const float *y, const float *res, float *out, int64_t n, hipStream_t s)
+{
+    if (n <= 0) return QE_OK;
+    const int vec = ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+    const int64_t want = ((vec ? n / 4 : n) + 255) / 256;
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, kNumCU * 16));
+    hipLaunchKernelGGL(add_residual_kernel, dim3(blocks), dim3(256), 0, s, y, res, out, n, vec);
+    QE_LAUNCH_CHECK();
+    return QE_OK;
+}
+
+// residual and out: the same buffer or disjoint
+static bool res_overlap_ok(const float *res, const float *out, int64_t n)
+{
+    return res == out || res + n <= out || out + n <= res;
+}
+
+static size_t ws_f32(int64_t B, int O) { return (size_t)B * (size_t)O * sizeof(float); }
+}  // namespace qe
+
+extern "C" int qe_quantlinear_requant_path(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O,
+                                           const qe_requant *rq, const uint8_t *codes)
+{
+    using namespace qe;
+    if (x == nullptr || w == nullptr || rq == nullptr) return 0;
+    return lin_epi_enabled() && lin_mfma_eligible(x, w, B, K, O) && rq_fusable(rq) &&
+           (reinterpret_cast<uintptr_t>(codes) & 15) == 0 ? 1 : 0;
+}
+
+extern "C" size_t qe_quantlinear_requant_workspace_bytes(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O,
+                                                         const qe_requant *rq, const uint8_t *codes)
+{
+    if (B <= 0 || O <= 0) return 0;
+    return qe_quantlinear_requant_path(x, w, B, K, O, rq, codes) ? 0 : qe::ws_f32(B, O);
+}
+
+extern "C" int qe_quantlinear_requant(const qe_qparam *x, const qe_qparam *w, const float *bias, int64_t B, int32_t K, int32_t O,
+                                      int32_t act, const qe_requant *rq, uint8_t *codes, int32_t *status,
+                                      void *workspace, size_t workspace_bytes, qe_stream_t stream)
+{
+    using namespace qe;
+    if (B < 0 || K < 0 || O < 0 || rq == nullptr || (act != QE_ACT_NONE && act != QE_ACT_GELU)) return QE_ERR_ARG;
+    if (!(rq->n_bits > 0 && rq->n_bits <= 8)) return QE_ERR_NBITS;
+    if (rq->n_param != 1 && rq->n_param != O) return QE_ERR_ARG;
+    int rc;
+    if ((rc = check_lin_q(x, B)) != QE_OK) return rc;
+    if ((rc = check_lin_q(w, O)) != QE_OK) return rc;
+    if (B == 0 || O == 0) return QE_OK;
+    if (codes == nullptr) return QE_ERR_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (qe_quantlinear_requant_path(x, w, B, K, O, rq, codes)) {
+        LinArgs a = {};
+        a.x = static_cast<const uint8_t *>(x->data); a.w = static_cast<const uint8_t *>(w->data);
+        a.x_scale = x->scale; a.x_zero = x->zero; a.w_scale = w->scale; a.w_zero = w->zero; a.bias = bias;
+        a.x_bits = x->n_bits; a.x_sign = x->sign; a.x_per_tensor = x->n_param == 1;
+        a.w_bits = w->n_bits; a.w_sign = w->sign; a.w_per_tensor = w->n_param == 1;
+        a.B = B; a.K = K; a.O = O; a.out = nullptr; a.dbg = nullptr;
+        a.codes = codes; a.status = status; a.rq = make_rq(rq);
+        return act == QE_ACT_GELU ? launch_lin_mfma<LIN_CODES_GELU>(a, true, s) : launch_lin_mfma<LIN_CODES>(a, true, s);
+    }
+    if (workspace == nullptr || workspace_bytes < ws_f32(B, O) || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0)
+        return QE_ERR_WORKSPACE;
+    float *y = static_cast<float *>(workspace);
+    if ((rc = qe_quantlinear(x, w, bias, B, K, O, y, stream)) != QE_OK) return rc;
+    // per-channel rq: channel = output feature o, element (b, o) -> (i / 1) % O
+    return qe_quantize_pack_act(y, B * (int64_t)O, act, rq->scale, rq->zero, rq->n_param, 1, rq->qmin, rq->qmax, rq->n_bits,
+                                rq->sign, codes, nullptr, status, stream);
+}
+
+extern "C" int qe_quantlinear_residual_path(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O)
+{
+    using namespace qe;
+    if (x == nullptr || w == nullptr) return 0;
+    return lin_epi_enabled() && lin_mfma_eligible(x, w, B, K, O) ? 1 : 0;
+}
+
+extern "C" size_t qe_quantlinear_residual_workspace_bytes(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O)
+{
+    if (B <= 0 || O <= 0) return 0;
+    return qe_quantlinear_residual_path(x, w, B, K, O) ? 0 : qe::ws_f32(B, O);
+}
+
+extern "C" int qe_quantlinear_residual(const qe_qparam *x, const qe_qparam *w, const float *bias, int64_t B, int32_t K, int32_t O,
+                                       const float *residual, float *out, void *workspace, size_t workspace_bytes, qe_stream_t stream)
+{
+    using namespace qe;
+    if (B < 0 || K < 0 || O < 0) return QE_ERR_ARG;
+    int rc;
+    if ((rc = check_lin_q(x, B)) != QE_OK) return rc;
+    if ((rc = check_lin_q(w, O)) != QE_OK) return rc;
+    if (B == 0 || O == 0) return QE_OK;
+    if (residual == nullptr || out == nullptr || !res_overlap_ok(residual, out, B * (int64_t)O)) return QE_ERR_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (qe_quantlinear_residual_path(x, w, B, K, O)) {
+        LinArgs a = {};
+        a.x = static_cast<const uint8_t *>(x->data); a.w = static_cast<const uint8_t *>(w->data);
+        a.x_scale = x->scale; a.x_zero = x->zero; a.w_scale = w->scale; a.w_zero = w->zero; a.bias = bias;
+        a.x_bits = x->n_bits; a.x_sign = x->sign; a.x_per_tensor = x->n_param == 1;
+        a.w_bits = w->n_bits; a.w_sign = w->sign; a.w_per_tensor = w->n_param == 1;
+        a.B = B; a.K = K; a.O = O; a.out = out; a.dbg = nullptr; a.res = residual;
+        const bool al = ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(residual)) & 15) == 0;
+        return launch_lin_mfma<LIN_RES>(a, al, s);
+    }
+    if (workspace == nullptr || workspace_bytes < ws_f32(B, O) || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0)
+        return QE_ERR_WORKSPACE;
+    float *y = static_cast<float *>(workspace);
+    if ((rc = qe_quantlinear(x, w, bias, B, K, O, y, stream)) != QE_OK) return rc;
+    return launch_add_residual(y, residual, out, B * (int64_t)O, s);
+}
+
+extern "C" int qe_quantlinear_float_input_residual_path(const float *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O)
+{
+    using namespace qe;
+    if (w == nullptr) return 0;
+    return lin_epi_enabled() && linf_mfma_eligible(x, w, B, K, O) ? 1 : 0;
+}
+
+extern "C" size_t qe_quantlinear_float_input_residual_workspace_bytes(const float *x, const qe_qparam *w, int64_t B, int32_t K,
+                                                                     int32_t O)
+{
+    if (B <= 0 || O <= 0) return 0;
+    return qe_quantlinear_float_input_residual_path(x, w, B, K, O) ? 0 : qe::ws_f32(B, O);
+}
+
+extern "C" int qe_quantlinear_float_input_residual(const float *x, const qe_qparam *w, const float *bias, int64_t B, int32_t K,
+                                                   int32_t O, const float *residual, float *out, void *workspace,
+                                                   size_t workspace_bytes, qe_stream_t stream)
+{
+    using namespace qe;
+    if (B < 0 || K < 0 || O < 0) return QE_ERR_ARG;
+    int rc;
+    if ((rc = check_lin_q(w, O)) != QE_OK) return rc;
+    if (B == 0 || O == 0) return QE_OK;
+    if (x == nullptr || residual == nullptr || out == nullptr || !res_overlap_ok(residual, out, B * (int64_t)O)) return QE_ERR_ARG;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (qe_quantlinear_float_input_residual_path(x, w, B, K, O)) {
+        LinArgs a = {};
+        a.x = nullptr; a.xf = x; a.w = static_cast<const uint8_t *>(w->data);
+        a.w_scale = w->scale; a.w_zero = w->zero; a.bias = bias;
+        a.x_bits = 0; a.x_sign = 0; a.x_per_tensor = 1;
+        a.w_bits = w->n_bits; a.w_sign = w->sign; a.w_per_tensor = w->n_param == 1;
+        a.B = B; a.K = K; a.O = O; a.out = out; a.dbg = nullptr; a.res = residual;
+        return launch_linf_mfma<LIN_RES>(a, s);
+    }
+    if (workspace == nullptr || workspace_bytes < ws_f32(B, O) || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0)
+        return QE_ERR_WORKSPACE;
+    float *y = static_cast<float *>(workspace);
+    if ((rc = qe_quantlinear_float_input(x, w, bias, B, K, O, y, stream)) != QE_OK) return rc;
+    return launch_add_residual(y, residual, out, B * (int64_t)O, s);
 }

@@ -20,6 +20,7 @@
 // HBM-bound: algorithmic bytes per element = sizeof(T) + b/8 (pack),
 // b/8 + 1 (unpack).  LDS traffic is 2 B/element, far below the LDS roof.
 #include "qe_common.h"
+#include "qe_elementwise.hpp"
 
 namespace qe {
 
@@ -33,34 +34,12 @@ struct alignas((sizeof(T) * 4 > 16) ? 16 : sizeof(T) * 4) Vec4 {
     T v[4];
 };
 
-// (char)x of tpack.cu:50 for in-range values, plus the range test of tpack.cu:211-215
-// evaluated on the value as float (x.min().item<float>()).
-template <typename T>
-__device__ __forceinline__ unsigned tp_code(T v, float lo, float hi, unsigned offset, unsigned mask, bool &bad)
-{
-    const float f = (float)v;
-    bad |= !(f >= lo && f <= hi);  // NaN fails both comparisons, like TORCH_CHECK
-    const int iv = (int)v;         // truncation toward zero == (char)v while in range
-    return ((unsigned)iv + offset) & mask;
-}
-
-// Fused activation quantisation: the Quantizer's
-//   q = round(x / scale - zero).clamp(qmin, qmax)      (modelzoo/modules/quantizer.py:31, :215; zero in the MODULE's
-// convention, i.e. subtracted here and added back on dequantisation) in front of the packer, so the fp32 integer-valued
-// tensor the reference materialises between Quantizer and tpack (4 B/element written + read again) never exists.
-// Same fp32 operations in the same order as torch: IEEE division, subtraction, round-half-even, clamp (NaN passes
-// through the clamp and trips the range flag like it trips CHECK_RANGE).
+// tp_code / tp_quantize / qe_gelu: qe_elementwise.hpp (shared with the linear epilogues and the ViT kernels).
 struct TpQuant {
     const float *scale, *zero;   // 1 element, or one per channel
     float qmin, qmax;
     uint32_t inner, n_ch;        // per channel: channel of element i = (i / inner) % n_ch
 };
-__device__ __forceinline__ float tp_quantize(float v, float sc, float zr, float qmin, float qmax)
-{
-    const float r = rintf(v / sc - zr);
-    return (r != r) ? r : fminf(fmaxf(r, qmin), qmax);
-}
-
 // QM: 0 = plain tpack, 1 = quantise with per-tensor scale/zero, 2 = per channel (T = float for 1 and 2)
 template <typename T, int B, int QM>
 __global__ __launch_bounds__(TP_THREADS) void tpack_kernel(
@@ -503,6 +482,102 @@ extern "C" int qe_tunpack(const uint8_t *packed, int64_t n, int n_bits, int sign
         default: return QE_ERR_NBITS;
     }
 #undef QE_TU_CASE
+    QE_LAUNCH_CHECK();
+    return QE_OK;
+}
+
+namespace qe {
+// ---------------------------------------------------------------------------------------------
+// qe_quantize_pack_act: y = act(x) (fp32, optionally stored), then the consumer's codes of y -- quantize_pack's arithmetic
+// (tp_quantize + tp_code of qe_elementwise.hpp) on act's fp32 result, so the codes are bit-identical to
+// qe_quantize_pack(act(x)).  A thread owns a group of 8 consecutive elements: their 8 b-bit codes are b whole bytes.
+// (act = none without an fp32 output is qe_quantize_pack itself: the entry point calls it.)
+// ---------------------------------------------------------------------------------------------
+struct ActEw {
+    const float *x;
+    float *y;                    // may be NULL
+    uint8_t *codes;
+    int32_t *status;
+    int64_t n;
+    TpQuant q;                   // n_ch == 1: per tensor
+    float lo, hi;
+    unsigned offset, mask;
+    int n_bits, vec;             // vec: x and y 16-byte aligned
+};
+
+template <int ACT>
+__global__ __launch_bounds__(256) void act_quant_kernel(const ActEw a)
+{
+    const int64_t n_groups = (a.n + 7) / 8;
+    bool bad = false;
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n_groups; g += (int64_t)gridDim.x * 256) {
+        const int64_t e0 = 8 * g;
+        const int cnt = (a.n - e0) < 8 ? (int)(a.n - e0) : 8;
+        float v[8];
+        if (a.vec && cnt == 8) {
+            const float4 x0 = *reinterpret_cast<const float4 *>(a.x + e0), x1 = *reinterpret_cast<const float4 *>(a.x + e0 + 4);
+            v[0] = x0.x; v[1] = x0.y; v[2] = x0.z; v[3] = x0.w; v[4] = x1.x; v[5] = x1.y; v[6] = x1.z; v[7] = x1.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = j < cnt ? a.x[e0 + j] : 0.0f;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = qe_act<ACT>(v[j]);
+        if (a.y != nullptr) {
+            if (a.vec && cnt == 8) {
+                *reinterpret_cast<float4 *>(a.y + e0) = make_float4(v[0], v[1], v[2], v[3]);
+                *reinterpret_cast<float4 *>(a.y + e0 + 4) = make_float4(v[4], v[5], v[6], v[7]);
+            } else {
+                for (int j = 0; j < cnt; ++j) a.y[e0 + j] = v[j];
+            }
+        }
+        uint64_t bits = 0;
+        for (int j = 0; j < cnt; ++j) {
+            const float sc = a.q.n_ch == 1 ? a.q.scale[0] : a.q.scale[((e0 + j) / a.q.inner) % a.q.n_ch];
+            const float zr = a.q.n_ch == 1 ? a.q.zero[0] : a.q.zero[((e0 + j) / a.q.inner) % a.q.n_ch];
+            bits |= (uint64_t)tp_code<float>(tp_quantize(v[j], sc, zr, a.q.qmin, a.q.qmax), a.lo, a.hi, a.offset, a.mask, bad)
+                    << (j * a.n_bits);
+        }
+        uint8_t *dst = a.codes + g * a.n_bits;
+        const int nb = (cnt * a.n_bits + 7) / 8;
+        if (a.n_bits == 8 && cnt == 8 && (reinterpret_cast<uintptr_t>(dst) & 7) == 0) *reinterpret_cast<uint64_t *>(dst) = bits;
+        else for (int k = 0; k < nb; ++k) dst[k] = (uint8_t)(bits >> (8 * k));
+    }
+    if (__builtin_amdgcn_ballot_w64(bad) != 0 && (threadIdx.x & 63) == 0 && a.status != nullptr) atomicOr(a.status, 1);
+}
+}  // namespace qe
+
+extern "C" int qe_quantize_pack_act(const float *x, int64_t n, int32_t act, const float *scale, const float *zero,
+                                    int32_t n_param, int64_t inner, float qmin, float qmax, int n_bits, int sign,
+                                    uint8_t *out, float *y, int32_t *status, qe_stream_t stream)
+{
+    using namespace qe;
+    if (!(n_bits > 0 && n_bits <= 8)) return QE_ERR_NBITS;
+    if (n < 0 || n_param < 1 || (act != QE_ACT_NONE && act != QE_ACT_GELU)) return QE_ERR_ARG;
+    if (n == 0) return QE_OK;
+    if (x == nullptr || out == nullptr || scale == nullptr || zero == nullptr) return QE_ERR_ARG;
+    if (act == QE_ACT_NONE && y == nullptr)
+        return qe_quantize_pack(x, n, scale, zero, n_param, inner, qmin, qmax, n_bits, sign, out, status, stream);
+    if (y != nullptr && y != x && y < x + n && x < y + n) return QE_ERR_ARG;   // in place (y == x) or disjoint
+    ActEw a;
+    a.x = x; a.y = y; a.codes = out; a.status = status; a.n = n;
+    a.q = TpQuant{scale, zero, qmin, qmax, 1u, (uint32_t)n_param};
+    if (n_param > 1) {
+        if (inner < 1 || inner >= (1ll << 31)) return QE_ERR_ARG;
+        a.q.inner = (uint32_t)inner;
+    }
+    a.n_bits = n_bits;
+    a.offset = sign ? (1u << (n_bits - 1)) : 0u;                 // as launch_tpack_t
+    a.mask = (1u << n_bits) - 1u;
+    a.lo = sign ? -(float)(1 << (n_bits - 1)) : 0.0f;
+    a.hi = sign ? (float)((1 << (n_bits - 1)) - 1) : (float)((1 << n_bits) - 1);
+    a.vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
+    const int64_t groups = (n + 7) / 8;
+    const int64_t want = (groups + 255) / 256;
+    const int blocks = (int)(want < TP_MAX_BLOCKS * 4 ? want : TP_MAX_BLOCKS * 4);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (act == QE_ACT_GELU) hipLaunchKernelGGL(act_quant_kernel<QE_ACT_GELU>, dim3(blocks), dim3(256), 0, s, a);
+    else                    hipLaunchKernelGGL(act_quant_kernel<QE_ACT_NONE>, dim3(blocks), dim3(256), 0, s, a);
     QE_LAUNCH_CHECK();
     return QE_OK;
 }

@@ -149,6 +149,42 @@ class PackedLinear(_PackedBase):
             raise ValueError("route must be 'packed' or 'float'")
         return y.reshape(*lead, y.shape[-1])
 
+    # ---- packed in, packed out: the linear-epilogue forms ----
+    def call_packed(self, xq, x_des, consumer=None, act=None, residual=None):
+        """Activations as (packed stream, des [n_bits, sign, rows, in_features]) -- what quantize() or an earlier
+        call_packed() returned.  consumer=None: the fp32 (rows, out_features) output, plus `residual` when given
+        (qe_quantlinear_residual: the add in the kernel's epilogue; bit-identical to self.call_packed(xq, x_des) + residual).
+        consumer = the Packed* layer that reads this layer's output: returns the (packed, des) pair of ITS activation quantiser
+        of act(y) (act None or "gelu"), written by this layer's kernel itself where it can (qe_quantlinear_requant):
+        bit-identical to consumer.quantize(act(self.call_packed(xq, x_des))) with act applied in fp32 as F.gelu does."""
+        from . import capi
+        d = [int(v) for v in x_des.tolist()]
+        n_bits, sign = d[0], d[1]
+        K = d[-1]
+        B = 1
+        for v in d[2:-1]:
+            B *= v
+        wd = [int(v) for v in self.w_des.tolist()]
+        O = wd[2]
+        if self.a_scale.numel() != 1:
+            raise ValueError("quantlinear takes a per-tensor or per-row activation scale")
+        x = capi.qparam(xq, n_bits, sign, self.a_scale, self.a_zero)            # quantlinear: (q + zero)
+        w = capi.qparam(self.weight, wd[0], wd[1], self.w_scale.reshape(-1), self.w_zero.reshape(-1))
+        if consumer is None:
+            if act is not None:
+                raise ValueError("act applies to the consumer's codes; the fp32 output is y itself")
+            if residual is None:
+                return capi.quantlinear(x, w, self.bias, B, K, O)
+            return capi.quantlinear_residual(x, w, self.bias, B, K, O, residual.contiguous().reshape(B, O))
+        if residual is not None:
+            raise ValueError("residual and consumer are exclusive")
+        rq = capi.requant(consumer.a_scale, consumer.a_zero, consumer.a_qmin, consumer.a_qmax, consumer.a_bits, consumer.a_signed)
+        codes, status = capi.quantlinear_requant(x, w, self.bias, B, K, O, rq, act=act)
+        if int(status.item()) != 0:
+            raise RuntimeError("The input tensor is out of range.")     # tpack.cu:14, as engine.tpack raises it
+        des = torch.tensor([consumer.a_bits, 1 if consumer.a_signed else 0, B, O], dtype=torch.int32, device=xq.device)
+        return codes, des
+
 
 class PackedMultiheadAttention:
     """A packed QuantMultiheadAttention's forward on the engine (modelzoo/modules/quantmultiheadattention.py:262-...).

@@ -1,0 +1,433 @@
+"""A packed torchvision ViT run end to end on the engine.
+
+torchvision's VisionTransformer with the reference's quant modules in it: conv_proj a QuantConv2d (kernel = stride = patch),
+each EncoderBlock x = x + attn(ln_1(x)); x = x + mlp(ln_2(x)) with a QuantMultiheadAttention (separate q / k / v projections
+after pack()) and mlp = QuantLinear, GELU, QuantLinear; the final LayerNorm on the class token and a QuantLinear head.
+PackedViT takes the state_dict of such a model after pack() and runs it two ways:
+
+  route="layers"  the reference's dataflow with the engine plugged in: conv_proj as quantize_pack of the unfolded image
+                  + quantlinear, torch F.layer_norm,
+                  PackedLinear for q / k / v, the attention core, quantlinear_float_input for out_proj, torch `+`, F.gelu
+                  and PackedLinear for the two MLP linears, the final LayerNorm and the head;
+  route="fused"   the image quantiser and the unfold in one pass (qe_quantize_patchify) and the patch embedding as a GEMM
+                  on the int8 matrix cores; per block one pass of LayerNorm + the q / k / v codes
+                  (qe_layernorm_quantize_pack), the three projections, the attention core, out_proj with the residual
+                  add in its epilogue, LayerNorm + fc1's codes, fc1 with GELU + fc2's codes in its epilogue
+                  (qe_quantlinear_requant) and fc2 with the residual add in its epilogue (qe_quantlinear_residual).
+
+Both routes call the same attention core, _attention: fp32 F.scaled_dot_product_attention on (N, H, L, d) -- what
+F.multi_head_attention_forward runs for need_weights=False.  The C entry points take their two-pass form wherever the
+fused form is not eligible (sub-8-bit or per-channel consumer codes, non-MFMA shapes, QE_LIN_EPI=0), so every step of
+the fused route exists for every model the layers route runs.  With check=False the fused route makes no device -> host
+copy or synchronisation: every range flag accumulates in one device int32, read once at the end when check=True.
+"""
+import re
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from . import capi
+from .packed import PackedConv2d, PackedLinear, PackedMultiheadAttention
+from .packed_resnet import pack_codes
+
+OUT_OF_RANGE = "The input tensor is out of range."    # tpack.cu:14
+
+
+def _attention(Q, K, V, N, L, H):
+    """(N L, E) fp32 projections -> (N L, E) context: softmax(Q K^T / sqrt(d)) V per head, fp32."""
+    E = Q.shape[-1]
+    d = E // H
+    q, k, v = (t.reshape(N, L, H, d).transpose(1, 2) for t in (Q, K, V))
+    ctx = F.scaled_dot_product_attention(q, k, v)
+    return ctx.transpose(1, 2).reshape(N * L, E).contiguous()
+
+
+class _Lin:
+    """A PackedLinear plus its host-side operand descriptions."""
+
+    def __init__(self, m, name):
+        self.m, self.name = m, name
+        wd = [int(v) for v in m.w_des.tolist()]
+        self.w_bits, self.w_sign, self.O, self.K = wd[0], wd[1], wd[2], wd[-1]
+        if m.a_scale.numel() != 1:
+            raise ValueError("%s: a per-channel activation quantiser (%d scales) on a linear: the packed x packed kernel scales "
+                             "by batch row, so only a per-tensor quantiser is supported" % (name, m.a_scale.numel()))
+
+    def xq(self, codes):
+        m = self.m
+        return capi.qparam(codes, m.a_bits, m.a_signed, m.a_scale, m.a_zero)         # quantlinear: (q + zero)
+
+    def wq(self):
+        m = self.m
+        return capi.qparam(m.weight, self.w_bits, self.w_sign, m.w_scale.reshape(-1), m.w_zero.reshape(-1))
+
+    def requant(self):
+        m = self.m
+        return capi.requant(m.a_scale, m.a_zero, m.a_qmin, m.a_qmax, m.a_bits, m.a_signed)
+
+
+class _Block:
+    def __init__(self, name, ln1, attn, ln2, fc1, fc2):
+        self.name, self.ln1, self.attn, self.ln2 = name, ln1, attn, ln2
+        self.q, self.k, self.v = (_Lin(p, name + ".self_attention." + n) for p, n in ((attn.q, "q"), (attn.k, "k"), (attn.v, "v")))
+        self.fc1, self.fc2 = _Lin(fc1, name + ".mlp.0"), _Lin(fc2, name + ".mlp.3")
+        od = [int(v) for v in attn.out_des.tolist()]
+        self.out_bits, self.out_sign = od[0], od[1]
+
+
+class PackedViT:
+    """A packed torchvision ViT (B/16, L/16, ... or any depth / width / patch) on the engine."""
+
+    def __init__(self, conv, class_token, pos, blocks, ln, head, num_heads, eps):
+        self.conv, self.class_token, self.pos, self.blocks = conv, class_token, pos, blocks
+        self.ln, self.head, self.num_heads, self.eps = ln, head, int(num_heads), float(eps)
+        wd = [int(v) for v in conv.w_des.tolist()]
+        self._conv_wd = wd
+        self.E, self.C, self.patch = wd[2], wd[3], wd[4]
+        if wd[4] != wd[5]:
+            raise ValueError("conv_proj: a %dx%d kernel; a ViT's patch embedding is square" % (wd[4], wd[5]))
+        self.head_lin = _Lin(head, "heads.head")
+        if conv.a_scale.numel() != 1:
+            raise ValueError("conv_proj: a per-channel image quantiser (%d scales): the patch embedding runs as a GEMM whose "
+                             "activations are scaled by row, so only a per-tensor image quantiser is supported" % conv.a_scale.numel())
+
+    @classmethod
+    def from_state_dict(cls, sd, num_heads, eps=1e-6, prefix=""):
+        sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+
+        def need(k):
+            if k not in sd:
+                raise KeyError("packed ViT state_dict: missing %s%s" % (prefix, k))
+            return sd[k]
+
+        need("conv_proj.w_des")
+        kh = int(sd["conv_proj.w_des"][4])
+        conv = PackedConv2d.from_state_dict(sd, "conv_proj.", stride=kh, padding=0)
+        idx = sorted({int(m.group(1)) for k in sd for m in [re.match(r"encoder\.layers\.encoder_layer_(\d+)\.", k)] if m})
+        if not idx or idx != list(range(len(idx))):
+            raise KeyError("packed ViT state_dict: encoder layers encoder_layer_0.. not found (have %s)" % idx)
+        blocks = []
+        for i in idx:
+            pre = "encoder.layers.encoder_layer_%d." % i
+            need(pre + "self_attention.q_proj_des")
+            need(pre + "mlp.0.w_des")
+            need(pre + "mlp.3.w_des")
+            attn = PackedMultiheadAttention.from_state_dict(sd, pre + "self_attention.", num_heads)
+            ln1 = (need(pre + "ln_1.weight"), need(pre + "ln_1.bias"))
+            ln2 = (need(pre + "ln_2.weight"), need(pre + "ln_2.bias"))
+            blocks.append(_Block(pre[:-1], ln1, attn, ln2, PackedLinear.from_state_dict(sd, pre + "mlp.0."),
+                                 PackedLinear.from_state_dict(sd, pre + "mlp.3.")))
+        ln = (need("encoder.ln.weight"), need("encoder.ln.bias"))
+        need("heads.head.w_des")
+        head = PackedLinear.from_state_dict(sd, "heads.head.")
+        return cls(conv, need("class_token"), need("encoder.pos_embedding"), blocks, ln, head, num_heads, eps)
+
+    # ---- introspection ----
+    @property
+    def depth(self):
+        return len(self.blocks)
+
+    @property
+    def mlp_dim(self):
+        return self.blocks[0].fc1.O
+
+    def linears(self):
+        out = []
+        for b in self.blocks:
+            out += [b.q, b.k, b.v, b.fc1, b.fc2]
+        return out + [self.head_lin]
+
+    # ---- the two routes ----
+    def __call__(self, images, route="fused", check=True):
+        return self.forward(images, route, check)[0]
+
+    def forward(self, images, route="fused", check=True, keep_blocks=False):
+        """(logits, [block outputs (N, L, E)] if keep_blocks else None)."""
+        if route not in ("fused", "layers"):
+            raise ValueError("route must be 'fused' or 'layers'")
+        images = images.contiguous()
+        N = images.shape[0]
+        status = torch.zeros(1, dtype=torch.int32, device=images.device)
+        x = self.embed(images, route, status)
+        outs = [] if keep_blocks else None
+        for b in self.blocks:
+            x = self.block(b, x, N, route, status)
+            if keep_blocks:
+                outs.append(x.reshape(N, -1, self.E).clone())
+        cls_rows = x.reshape(N, -1, self.E)[:, 0].contiguous()
+        y = F.layer_norm(cls_rows, (self.E,), self.ln[0], self.ln[1], self.eps)
+        if route == "layers":
+            logits = self.head(y, route="packed")
+        else:
+            h = self.head_lin
+            codes = capi.quantize_pack(y, h.m.a_scale, h.m.a_zero, h.m.a_qmin, h.m.a_qmax, h.m.a_bits, h.m.a_signed, status=status)[0]
+            logits = capi.quantlinear(h.xq(codes), h.wq(), h.m.bias, N, h.K, h.O)
+            if check and int(status.item()) != 0:
+                raise RuntimeError(OUT_OF_RANGE)
+        return logits, outs
+
+    def embed(self, images, route, status):
+        """Patch embedding + class token + position embedding: (N L, E) fp32 rows."""
+        N, C, H, W = images.shape
+        p = self.patch
+        c = self.conv
+        rows = N * (H // p) * (W // p)
+        if route == "layers":
+            # the Quantizer on the unfolded image, then the conv as the GEMM it is (the engine's direct convolution has
+            # no kernel for a 16 x 16 filter of 768 taps)
+            u = images.reshape(N, C, H // p, p, W // p, p).permute(0, 2, 4, 1, 3, 5).reshape(rows, C * p * p).contiguous()
+            codes = capi.quantize_pack(u, c.a_scale, c.a_zero, c.a_qmin, c.a_qmax, c.a_bits, c.a_signed)[0]
+        else:
+            codes = capi.quantize_patchify(images, p, c.a_scale, c.a_zero, c.a_qmin, c.a_qmax, c.a_bits, c.a_signed,
+                                           status=status)[0]
+        # quantlinear's convention: (q + zero) with the module's zero -- the conv's (q - zero') with zero' = -zero
+        xq = capi.qparam(codes, c.a_bits, c.a_signed, c.a_scale, c.a_zero)
+        wq = capi.qparam(c.weight, self._conv_wd[0], self._conv_wd[1], c.w_scale.reshape(-1), c.w_zero.reshape(-1))
+        t = capi.quantlinear(xq, wq, c.bias, rows, C * p * p, self.E).reshape(N, -1, self.E)
+        x = torch.cat([self.class_token.expand(N, -1, -1), t], dim=1) + self.pos
+        return x.reshape(-1, self.E).contiguous()
+
+    def block(self, b, x, N, route, status=None):
+        """One encoder block on (N L, E) fp32 rows -> (N L, E).  The fused route updates x in place."""
+        E, H = self.E, self.num_heads
+        L = x.shape[0] // N
+        if route == "layers":
+            y = F.layer_norm(x, (E,), b.ln1[0], b.ln1[1], self.eps)
+            Q, K, V = (lin.m(y, route="packed") for lin in (b.q, b.k, b.v))
+            ctx = _attention(Q, K, V, N, L, H)
+            a = b.attn
+            oq = capi.qparam(a.out_weight, b.out_bits, b.out_sign, a.out_scale, a._neg_out_zero)
+            x = x + capi.quantlinear_float_input(ctx, oq, a.out_bias, E)
+            y = F.layer_norm(x, (E,), b.ln2[0], b.ln2[1], self.eps)
+            h = F.gelu(b.fc1.m(y, route="packed"))
+            return x + b.fc2.m(h, route="packed")
+        if status is None:
+            status = torch.zeros(1, dtype=torch.int32, device=x.device)
+        rows = x.shape[0]
+        codes = capi.layernorm_quantize_pack(x, b.ln1[0], b.ln1[1], self.eps, [b.q.requant(), b.k.requant(), b.v.requant()],
+                                             status=status)[0]
+        Q, K, V = (capi.quantlinear(lin.xq(c), lin.wq(), lin.m.bias, rows, lin.K, lin.O) for lin, c in zip((b.q, b.k, b.v), codes))
+        ctx = _attention(Q, K, V, N, L, H)
+        a = b.attn
+        oq = capi.qparam(a.out_weight, b.out_bits, b.out_sign, a.out_scale, a._neg_out_zero)
+        x = capi.quantlinear_float_input_residual(ctx, oq, a.out_bias, E, x, out=x)
+        c1 = capi.layernorm_quantize_pack(x, b.ln2[0], b.ln2[1], self.eps, [b.fc1.requant()], status=status)[0][0]
+        c2 = capi.quantlinear_requant(b.fc1.xq(c1), b.fc1.wq(), b.fc1.m.bias, rows, b.fc1.K, b.fc1.O, b.fc2.requant(), act="gelu",
+                                      status=status)[0]
+        return capi.quantlinear_residual(b.fc2.xq(c2), b.fc2.wq(), b.fc2.m.bias, rows, b.fc2.K, b.fc2.O, x, out=x)
+
+    # ---- calibration (synthetic models, tests, tools) ----
+    def calibrate(self, images):
+        """Set every activation quantiser from what reaches it in one `layers` pass: signed ones max|x| / qmax, the
+        unsigned ones (fc2's, after the GELU) asymmetric over [min, max] with zero = round(min / scale)."""
+        def set_q(m, t):
+            if m.a_signed:
+                m.a_scale = torch.clamp(t.abs().max() / m.a_qmax, min=1e-8).reshape(1).float().contiguous()
+            else:
+                lo, hi = t.min(), t.max()
+                s = torch.clamp((hi - lo) / (m.a_qmax - m.a_qmin), min=1e-8)
+                m.a_scale = s.reshape(1).float().contiguous()
+                m.a_zero = torch.round(lo / s).reshape(1).float().contiguous()
+            m._neg_a_zero = (-m.a_zero).contiguous()
+        with torch.no_grad():
+            N = images.shape[0]
+            set_q(self.conv, images)
+            x = self.embed(images, "layers", None)
+            for b in self.blocks:
+                y = F.layer_norm(x, (self.E,), b.ln1[0], b.ln1[1], self.eps)
+                for lin in (b.q, b.k, b.v):
+                    set_q(lin.m, y)
+                L = x.shape[0] // N
+                ctx = _attention(*(lin.m(y, route="packed") for lin in (b.q, b.k, b.v)), N, L, self.num_heads)
+                a = b.attn
+                oq = capi.qparam(a.out_weight, b.out_bits, b.out_sign, a.out_scale, a._neg_out_zero)
+                x = x + capi.quantlinear_float_input(ctx, oq, a.out_bias, self.E)
+                y = F.layer_norm(x, (self.E,), b.ln2[0], b.ln2[1], self.eps)
+                set_q(b.fc1.m, y)
+                h = F.gelu(b.fc1.m(y, route="packed"))
+                set_q(b.fc2.m, h)
+                x = x + b.fc2.m(h, route="packed")
+            y = F.layer_norm(x.reshape(N, -1, self.E)[:, 0], (self.E,), self.ln[0], self.ln[1], self.eps)
+            set_q(self.head, y)
+        return self
+
+    def state_dict_quantizers(self):
+        """{key: tensor} of every activation quantiser's scale and zero, in the state_dict's key layout."""
+        out = {}
+
+        def put(prefix, m):
+            out[prefix + "scale"], out[prefix + "zero"] = m.a_scale, m.a_zero
+        put("conv_proj.a_quantizer.", self.conv)
+        for b in self.blocks:
+            for n, lin in (("q", b.q), ("k", b.k), ("v", b.v)):
+                put(b.name + ".self_attention.%s_quantizer." % n, lin.m)
+            put(b.name + ".mlp.0.a_quantizer.", b.fc1.m)
+            put(b.name + ".mlp.3.a_quantizer.", b.fc2.m)
+        put("heads.head.a_quantizer.", self.head)
+        return out
+
+
+# ---------------------------------------------------------------------------------------------
+# From a calibrated reference ViT to this engine
+# ---------------------------------------------------------------------------------------------
+def _qbits(qmin, qmax):
+    qmin, qmax = float(qmin), float(qmax)
+    return max(1, int(round(qmax - qmin)).bit_length()), qmin < 0
+
+
+def _pack_weight(w, scale, zero, qmin, qmax, static_scale=None):
+    """Quantizer.pack() of a weight (quantizer.py:228-250) + tpack: round(w / scale - zero).clamp(qmin, qmax) in fp32, the
+    stored b-bit stream, des [n_bits, sign, *shape], and (scale * static_scale, zero)."""
+    n_bits, signed = _qbits(qmin, qmax)
+    w = w.detach().float().cpu()
+    scale, zero = scale.detach().float().cpu(), zero.detach().float().cpu()
+    q = (w / scale - zero).round().clamp(float(qmin), float(qmax))
+    packed = torch.from_numpy(pack_codes(q.numpy().astype(np.int64), n_bits, signed))
+    des = torch.tensor([n_bits, 1 if signed else 0] + list(w.shape), dtype=torch.int32)
+    s = scale if static_scale is None else scale * static_scale.detach().float().cpu()
+    return packed, des, s, zero
+
+
+def pack_vit_state_dict(sd):
+    """The state_dict a calibrated (unpacked) reference ViT would have after pack() -- which the reference cannot produce
+    itself: QuantMultiheadAttention.pack() reads the None q_proj_weight when kdim == embed_dim (its in_proj_weight form).
+    QuantConv2d / QuantLinear: weight -> packed stream, w_des, w_scale = scale * static_scale, w_zero
+    (quantconv2d.py:187-192, quantlinear.py:123-148); QuantMultiheadAttention: in_proj_weight packed per chunk with the
+    q / k / v projection quantisers, out_proj.weight with out_proj_quantizer (quantmultiheadattention.py:165-223).
+    Activation quantisers, biases, LayerNorms, class token and position embedding pass through.  Every key of `sd` is
+    consumed: an unknown key raises ValueError.  Returns host tensors in PackedViT.from_state_dict's layout."""
+    sd = {k: v for k, v in sd.items()}
+    out, used = {}, set()
+
+    def take(k):
+        used.add(k)
+        return sd[k]
+
+    def wq(prefix):
+        st = sd.get(prefix + "_static_scale")
+        if st is not None:
+            used.add(prefix + "_static_scale")
+        return take(prefix + "scale"), take(prefix + "zero"), take(prefix + "qmin"), take(prefix + "qmax"), st
+
+    for k in sorted(sd):
+        if k.endswith(".w_quantizer.scale"):
+            pre = k[:-len("w_quantizer.scale")]
+            packed, des, s, z = _pack_weight(take(pre + "weight"), *wq(pre + "w_quantizer."))
+            out[pre + "weight"], out[pre + "w_des"], out[pre + "w_scale"], out[pre + "w_zero"] = packed, des, s, z
+        elif k.endswith(".q_proj_quantizer.scale"):
+            pre = k[:-len("q_proj_quantizer.scale")]
+            if pre + "in_proj_weight" in sd:
+                chunks = take(pre + "in_proj_weight").chunk(3)
+            else:
+                chunks = [take(pre + n + "_proj_weight") for n in ("q", "k", "v")]
+            for n, w in zip(("q", "k", "v"), chunks):
+                packed, des, s, z = _pack_weight(w, *wq(pre + n + "_proj_quantizer."))
+                out[pre + n + "_proj_weight"], out[pre + n + "_proj_des"] = packed, des
+                out[pre + n + "_proj_scale"], out[pre + n + "_proj_zero"] = s, z
+            packed, des, s, z = _pack_weight(take(pre + "out_proj.weight"), *wq(pre + "out_proj_quantizer."))
+            out[pre + "out_proj.weight"], out[pre + "out_proj_des"], out[pre + "out_proj_scale"], out[pre + "out_proj_zero"] = \
+                packed, des, s, z
+    for k, v in sd.items():
+        if k in used:
+            continue
+        if re.search(r"(a_quantizer|[qkv]_quantizer)\.(scale|zero|qmin|qmax)$", k) or \
+                re.search(r"(\.bias|ln_[12]\.weight|ln\.weight|class_token|pos_embedding)$", k) or k.endswith("in_proj_bias"):
+            out[k] = v.detach().cpu() if torch.is_tensor(v) else v
+            used.add(k)
+    left = sorted(set(sd) - used)
+    if left:
+        raise ValueError("pack_vit_state_dict: keys of no known ViT layer: %s" % left[:8])
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Synthetic packed ViTs (tests and tools/bench_vit_forward.py share this construction)
+# ---------------------------------------------------------------------------------------------
+CONFIGS = {
+    "vit_b_16": dict(image_size=224, patch=16, width=768, heads=12, mlp=3072, depth=12, num_classes=1000),
+    "vit_tiny_test": dict(image_size=32, patch=8, width=64, heads=4, mlp=256, depth=2, num_classes=10),
+}
+
+
+def _lin_entries(rng, O, K, w_bits, bias, signed_act=True, a_bits=8):
+    lim = (1 << (w_bits - 1)) - 1
+    q = rng.randint(-lim, lim + 1, size=(O, K))
+    std_q = np.sqrt(((2 * lim + 1) ** 2 - 1) / 12.0)
+    ws = np.sqrt(1.0 / K) / std_q * rng.uniform(0.8, 1.2, size=(O, 1))
+    qmin, qmax = (-(1 << (a_bits - 1)), (1 << (a_bits - 1)) - 1) if signed_act else (0, (1 << a_bits) - 1)
+    e = {"weight": torch.from_numpy(pack_codes(q, w_bits, True)),
+         "w_des": torch.tensor([w_bits, 1, O, K], dtype=torch.int32),
+         "w_scale": torch.from_numpy(ws.astype(np.float32)),
+         "w_zero": torch.zeros((O, 1), dtype=torch.float32),
+         "a_quantizer.scale": torch.tensor([1.0], dtype=torch.float32),
+         "a_quantizer.zero": torch.tensor([0.0], dtype=torch.float32),
+         "a_quantizer.qmin": torch.tensor(float(qmin)), "a_quantizer.qmax": torch.tensor(float(qmax))}
+    if bias:
+        e["bias"] = torch.from_numpy(rng.normal(0, 0.02, size=O).astype(np.float32))
+    return e
+
+
+def synthetic_state_dict(arch="vit_b_16", w_bits=8, a_bits=8, seed=0, **over):
+    """A packed ViT state_dict in the key layout pack() leaves (host tensors, activation scales not calibrated: 1.0).
+    Random b-bit weights scaled to unit gain, LayerNorm affine parameters near (1, 0); every activation quantiser signed
+    per tensor except fc2's (after the GELU): unsigned and asymmetric once calibrated.  See calibrated_state_dict."""
+    cfg = dict(CONFIGS[arch])
+    cfg.update(over)
+    rng = np.random.RandomState(seed)
+    E, p, C, M = cfg["width"], cfg["patch"], 3, cfg["mlp"]
+    L = (cfg["image_size"] // p) ** 2 + 1
+    sd = {}
+
+    def put(prefix, entries):
+        for k, v in entries.items():
+            sd[prefix + k] = v
+
+    conv = _lin_entries(rng, E, C * p * p, w_bits, True, True, a_bits)
+    conv["w_des"] = torch.tensor([w_bits, 1, E, C, p, p], dtype=torch.int32)
+    conv["w_scale"] = conv["w_scale"].reshape(E, 1, 1, 1)
+    conv["w_zero"] = conv["w_zero"].reshape(E, 1, 1, 1)
+    put("conv_proj.", conv)
+    sd["class_token"] = torch.from_numpy(rng.normal(0, 0.02, size=(1, 1, E)).astype(np.float32))
+    sd["encoder.pos_embedding"] = torch.from_numpy(rng.normal(0, 0.02, size=(1, L, E)).astype(np.float32))
+    for i in range(cfg["depth"]):
+        pre = "encoder.layers.encoder_layer_%d." % i
+        for ln in ("ln_1", "ln_2"):
+            sd[pre + ln + ".weight"] = torch.from_numpy(rng.uniform(0.8, 1.2, size=E).astype(np.float32))
+            sd[pre + ln + ".bias"] = torch.from_numpy(rng.normal(0, 0.05, size=E).astype(np.float32))
+        att = pre + "self_attention."
+        for n in ("q", "k", "v"):
+            e = _lin_entries(rng, E, E, w_bits, False, True, a_bits)
+            sd[att + n + "_proj_weight"], sd[att + n + "_proj_des"] = e["weight"], e["w_des"]
+            sd[att + n + "_proj_scale"], sd[att + n + "_proj_zero"] = e["w_scale"], e["w_zero"]
+            for k in ("scale", "zero", "qmin", "qmax"):
+                sd[att + n + "_quantizer." + k] = e["a_quantizer." + k]
+        sd[att + "in_proj_bias"] = torch.from_numpy(rng.normal(0, 0.02, size=3 * E).astype(np.float32))
+        o = _lin_entries(rng, E, E, w_bits, True)
+        o["w_scale"] = o["w_scale"] * 0.5            # residual branches at half gain: activations stay O(1) through the depth
+        sd[att + "out_proj.weight"], sd[att + "out_proj_des"] = o["weight"], o["w_des"]
+        sd[att + "out_proj_scale"], sd[att + "out_proj_zero"] = o["w_scale"], o["w_zero"]
+        sd[att + "out_proj.bias"] = o["bias"]
+        put(pre + "mlp.0.", _lin_entries(rng, M, E, w_bits, True, True, a_bits))
+        f2 = _lin_entries(rng, E, M, w_bits, True, False, a_bits)
+        f2["w_scale"] = f2["w_scale"] * 0.5
+        put(pre + "mlp.3.", f2)
+    sd["encoder.ln.weight"] = torch.ones(E, dtype=torch.float32)
+    sd["encoder.ln.bias"] = torch.zeros(E, dtype=torch.float32)
+    put("heads.head.", _lin_entries(rng, cfg["num_classes"], E, w_bits, True, True, a_bits))
+    return sd
+
+
+def calibrated_state_dict(arch="vit_b_16", device="cuda", calib_images=None, calib_batch=2, **kw):
+    """synthetic_state_dict on `device` with every activation quantiser calibrated from one `layers` pass."""
+    cfg = dict(CONFIGS[arch])
+    cfg.update({k: v for k, v in kw.items() if k in cfg})
+    sd = {k: v.to(device) for k, v in synthetic_state_dict(arch, **kw).items()}
+    if calib_images is None:
+        g = torch.Generator(device="cpu").manual_seed(kw.get("seed", 0) + 1)
+        s = cfg["image_size"]
+        calib_images = torch.randn(calib_batch, 3, s, s, generator=g).to(device)
+    model = PackedViT.from_state_dict(sd, cfg["heads"]).calibrate(calib_images)
+    for k, v in model.state_dict_quantizers().items():
+        sd[k] = v.detach().clone()
+    return sd

@@ -1,0 +1,70 @@
+"""Time a packed ViT-B/16 forward (W8A8, 224 x 224) end to end on the engine, both routes of PackedViT in one process,
+alternating, with device events, at each batch size; print one JSON line.
+
+  route="layers"  the reference's dataflow with the engine plugged in (torch LayerNorm, per-linear quantise + pack, fp32
+                  linear outputs, torch GELU and residual adds);
+  route="fused"   LayerNorm + q / k / v codes in one pass, GELU + codes and the residual adds in the linears' epilogues,
+                  the patch embedding as a GEMM on the matrix cores, no host synchronisation (check=False).
+
+The HBM bytes reported are ALGORITHMIC (the byte model below, per token row outside the attention core and the GEMM
+operands both routes share), not counters.  usage: python tools/bench_vit_forward.py [--batches 64 256] [--steps 10]
+[--warmup 2]"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def byte_model(N, E=768, M=3072, depth=12, tokens=197):
+    """(layers, fused) HBM bytes per forward between the GEMMs of the encoder blocks (fp32 = 4 B, codes = 1 B).
+    layers, per block and row: LN1 (read 4E, write 4E), three quantize_pack passes (3 x (4E + E)), out_proj output + the
+    add (4E write, 3 x 4E add), LN2 (8E), fc1's quantize_pack (5E), fc1 output 4M written, GELU (8M), fc2's quantize_pack
+    (5M), fc2 output + the add (4E + 12E).  fused: LN1 + 3 codes (4E + 3E), out_proj's epilogue add (4E read + 4E write),
+    LN2 + codes (4E + E), fc1's codes (M written), fc2's epilogue add (8E)."""
+    rows = N * tokens
+    lay = (8 * E + 15 * E + 16 * E + 8 * E + 5 * E + 4 * M + 8 * M + 5 * M + 16 * E) * rows * depth
+    fus = (7 * E + 8 * E + 5 * E + M + 8 * E) * rows * depth
+    return lay, fus
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", type=int, nargs="+", default=[64, 256])
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    args = ap.parse_args()
+    import torch
+    from quantize_amd.packed_vit import CONFIGS, PackedViT, calibrated_state_dict
+
+    dev = "cuda:0"
+    sd = calibrated_state_dict("vit_b_16", device=dev, seed=0)
+    model = PackedViT.from_state_dict(sd, CONFIGS["vit_b_16"]["heads"])
+    res = {"metric": "vit_b_16_forward", "unit": "ms", "batches": {}}
+    for N in args.batches:
+        g = torch.Generator(device="cpu").manual_seed(N)
+        x = torch.randn(N, 3, 224, 224, generator=g).to(dev)
+        times = {"fused": [], "layers": []}
+        with torch.no_grad():
+            for i in range(args.warmup + args.steps):
+                for route in ("fused", "layers"):
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    model(x, route, check=False) if route == "fused" else model(x, route)
+                    b.record()
+                    torch.cuda.synchronize()
+                    if i >= args.warmup:
+                        times[route].append(a.elapsed_time(b))
+        lay, fus = byte_model(N)
+        med = {r: sorted(t)[len(t) // 2] for r, t in times.items()}
+        res["batches"][str(N)] = {"fused_ms": med["fused"], "layers_ms": med["layers"],
+                                  "fused_img_s": N / med["fused"] * 1e3, "layers_img_s": N / med["layers"] * 1e3,
+                                  "byte_model_layers_GB": lay / 1e9, "byte_model_fused_GB": fus / 1e9}
+        del x
+        torch.cuda.empty_cache()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
