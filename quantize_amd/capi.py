@@ -20,7 +20,7 @@ DTYPES = {"uint8": 0, "int8": 1, "int16": 2, "int32": 3, "int64": 4,
 SYMBOLS = ["qe_error_string", "qe_last_hip_error", "qe_version", "qe_target_arch", "qe_packed_nbytes",
            "qe_tpack", "qe_tunpack", "qe_quantconv2d_workspace_bytes", "qe_quantconv2d",
            "qe_quantconv2d_float_input", "qe_quantconv2d_path", "qe_quantlinear", "qe_quantlinear_float_input",
-           "qe_quantlinear_path", "qe_quantlinear_float_input_path", "qe_global_avgpool", "qe_conv_prepared_bytes", "qe_quantconv2d_prepared_workspace_bytes",
+           "qe_quantlinear_path", "qe_quantlinear_form", "qe_quantlinear_float_input_path", "qe_global_avgpool", "qe_conv_prepared_bytes", "qe_quantconv2d_prepared_workspace_bytes",
            "qe_conv_prepare", "qe_quantconv2d_prepared", "qe_quantize_pack", "qe_quantconv2d_float_input_workspace_bytes",
            "qe_quantconv2d_float_input_ws", "qe_conv_f32_prepare", "qe_quantconv2d_float_input_prepared",
            "qe_quantconv2d_float_input_path", "qe_quantconv2d_requant_path", "qe_quantconv2d_requant_workspace_bytes",
@@ -89,6 +89,8 @@ def lib():
     L.qe_quantlinear_float_input.argtypes = [vp, ctypes.POINTER(QeQParam), vp, i64, i32, i32, vp, vp]
     L.qe_quantlinear_path.restype = i32
     L.qe_quantlinear_path.argtypes = [ctypes.POINTER(QeQParam), ctypes.POINTER(QeQParam), i64, i32, i32]
+    L.qe_quantlinear_form.restype = i32
+    L.qe_quantlinear_form.argtypes = [ctypes.POINTER(QeQParam), ctypes.POINTER(QeQParam), i64, i32, i32, i32]
     L.qe_quantlinear_float_input_path.restype = i32
     L.qe_quantlinear_float_input_path.argtypes = [vp, ctypes.POINTER(QeQParam), i64, i32, i32]
     L.qe_global_avgpool.restype = i32
@@ -429,6 +431,16 @@ def quantconv2d_float_input_prepared(x, wq, bias, sh, prepared, out=None, stream
 
 def linear_path(xq, wq, B, K, O):
     return int(lib().qe_quantlinear_path(ctypes.byref(xq), ctypes.byref(wq), int(B), int(K), int(O)))
+
+
+# qe_quantlinear_form: the kernel an int8 linear problem runs on
+LINEAR_FORMS = {0: "fp32 chain", 1: "64-deep 128x128", 2: "64-deep 128x256", 3: "8-wave 320x256", 4: "4-wave 160x256"}
+
+
+def linear_form(xq, wq, B, K, O, dst_aligned=True):
+    """qe_quantlinear_form (host-only): 0 = order-preserving fp32 kernel, 1 = 64-deep 128 x 128, 2 = 64-deep 128 x 256,
+    3 = 8-wave 320 x 256, 4 = 4-wave 160 x 256 -- with the QE_LIN8 / QE_LIN_NJ knobs of the last reload_env()."""
+    return int(lib().qe_quantlinear_form(ctypes.byref(xq), ctypes.byref(wq), int(B), int(K), int(O), 1 if dst_aligned else 0))
 
 
 def quantlinear(xq, wq, bias, B, K, O, out=None, stream=None):

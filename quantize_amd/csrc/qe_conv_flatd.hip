@@ -223,7 +223,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_flatd_kernel(const FlatdAr
     for (int i = 0; i < PXW; ++i) {
         const int e = 64 * (wave + WAVES * i) + lane;
         int64_t src;
-        bool last_row;
+        bool last_row, pad = false;
         int j;
         if constexpr (SMALL) {
             const int img = e >> 8, c = (e >> 2) & 63, jj = e & 3;
@@ -231,6 +231,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_flatd_kernel(const FlatdAr
             const int n = n0 + img < a.N ? n0 + img : a.N - 1;
             src = ((int64_t)n * a.IC + c) * P + 16 * j;
             last_row = (n0 + img == a.N - 1) && c == FD_CK - 1;
+            pad = n0 + img >= a.N;                         // an image past the batch in its last tile: computed, never stored
         } else {
             const int c = e / (RS / 16);
             j = e - c * (RS / 16);
@@ -239,7 +240,9 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_flatd_kernel(const FlatdAr
         }
         // stage s adds s * 64 planes: only the last stage of the last image can run past the tensor
         const int64_t lim = x_last16 - (int64_t)(a.IC - FD_CK) * P;
-        if (last_row && src > lim) {
+        if (pad) {
+            src = lim;      // its slots would repeat the last image's, whose last plane runs up to 15 bytes past the tensor
+        } else if (last_row && src > lim) {
             const int pos = (SMALL ? 0 : p0) + 16 * j;            // first plane byte this slot should hold
             if (pos < P && e < G::XBYTES / 16) {
                 // partly valid (P - pos = 4 or 1 bytes): in the last stage this lane is masked out of the DMA (see

@@ -2,8 +2,8 @@
 // image quantiser of the patch embedding fused with the unfold.
 //
 // qe_layernorm_quantize_pack: one wave per row, the row held in registers (NV float4 per lane, E <= 256 NV), read once.
-// Two wave reductions: the sum (mean = sum / E), then the CENTRED sum of squares (var = sum((x - mean)^2) / E: no
-// cancellation of E[x^2] - mean^2), rstd = 1 / sqrtf(var + eps) with the correctly rounded division and square root hipcc
+// Two wave reductions: the sum of x - x0 (x0 the row's first value; mean = x0 + sum / E), then the CENTRED sum of squares
+// (var = sum((x - mean)^2) / E: no cancellation of E[x^2] - mean^2), rstd = 1 / sqrtf(var + eps) with the correctly rounded division and square root hipcc
 // emits by default.  Each lane then writes its values' fp32 LayerNorm (optional) and 4 codes per float4 for every consumer
 // (qe_elementwise.hpp: the arithmetic of qe_quantize_pack on the same fp32 value, so the codes are bit-identical to
 // quantize_pack of the fp32 output).  Bytes per row: 4 E in, 3 E of codes out (q / k / v), instead of 4 E + 4 E (torch's LN)
@@ -44,14 +44,22 @@ __global__ __launch_bounds__(256) void layernorm_quant_kernel(const LnArgs a)
     const int E4 = a.E >> 2;
     const float4 *xr = reinterpret_cast<const float4 *>(a.x + row * a.E);
     float4 v[NV];
-    float s = 0.0f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const int idx = lane + 64 * i;
         v[i] = idx < E4 ? xr[idx] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     }
-    const float mean = wave_sum(s) / (float)a.E;
+    // the row is shifted by its first value x0 before it is summed: under a large mean offset the terms x - x0 are small
+    // (and exact where x is within a factor of two of x0), so the sum keeps the spread that sum(x) would round away
+    const float x0 = __shfl(v[0].x, 0);
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        if (lane + 64 * i < E4) { v[i].x -= x0; v[i].y -= x0; v[i].z -= x0; v[i].w -= x0; }
+    }
+    float s = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);   // lanes past the row hold zeros
+    const float mean = wave_sum(s) / (float)a.E;        // of x - x0
     float ss = 0.0f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {

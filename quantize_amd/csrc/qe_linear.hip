@@ -788,7 +788,8 @@ __global__ __launch_bounds__(256 * WMW, WMW == 2 ? 1 : 2) void linear_mfma8_kern
 
 // ---------------------------------------------------------------------------------------------
 // quantlinear_float_input on the matrix cores (round 3): fp32 activations x 8-bit weight codes, K % 32 == 0.
-//   out[b,o] = bias[o] + sw[o] ( S_xq[b,o] - zw[o] S_x[b] ),   S_xq = sum_k x q_w,   S_x = sum_k x
+//   out[b,o] = bias[o] + sw[o] ( S_xq[b,o] - (zw[o] - c[o]) S_x[b] ),   S_xq = sum_k x (q_w - c),   S_x = sum_k x
+// with c = rint(zw) per column (linf_centre), so a large zero point does not enter as a term that cancels.
 // S_xq runs on v_mfma_f32_32x32x16_bf16 with the EXACT three-way split of the activations the float-input convolution
 // uses (qe_conv_f32.hip): x = x1 + x2 + x3, each part's significand <= 8 bits (bf16), every product with an integer code
 // |q| <= 255 (bf16-exact) exact in fp32; only the fp32 accumulation rounds.  (A non-finite x gives NaN in the remainder
@@ -803,12 +804,22 @@ constexpr int LF_T = 128, LF_K = 32;
 constexpr int LF_PLANE = LF_T * LF_K * 2;                 // bytes of one [128][32] bf16 image (8 KB)
 constexpr size_t linf_lds_bytes() { return (size_t)4 * LF_PLANE + LF_T * sizeof(float) + 2 * LF_T * sizeof(float4); }
 
+// The integer c a column's weight codes are centred on before the bf16 conversion: rint(zw), clamped to the code range so
+// that |q - c| <= 255 stays exact in bf16.  The MFMAs then sum x (q - c), and the epilogue subtracts only (zw - c) S_x: with
+// zw itself there (zw ~ 128 for unsigned codes, asymmetric weights) the two fp32 terms sw (S_xq - zw S_x) are large and
+// cancel, and their rounding error was many times the reference chain's on non-zero-mean activations.
+__device__ __forceinline__ float linf_centre(float zw, int w_sign)
+{
+    const float c = rintf(zw);
+    return w_sign ? fminf(fmaxf(c, -128.0f), 127.0f) : fminf(fmaxf(c, 0.0f), 255.0f);
+}
+
 template <int EPI = LIN_F32>   // LIN_F32 | LIN_RES
 __global__ __launch_bounds__(256, 2) void linear_f32_mfma_kernel(const LinArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lsm[];   // 3 activation split images, 1 weight image, row sums, column constants
     float *rowsum = reinterpret_cast<float *>(lsm + 4 * LF_PLANE);
-    float4 *colc = reinterpret_cast<float4 *>(rowsum + LF_T);        // sw, zw, bias, 0
+    float4 *colc = reinterpret_cast<float4 *>(rowsum + LF_T);        // sw, zw - c, bias, 0
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -822,7 +833,8 @@ __global__ __launch_bounds__(256, 2) void linear_f32_mfma_kernel(const LinArgs a
 
     if (tid < LF_T) {
         const int cc = (n0 + tid < a.O) ? n0 + tid : a.O - 1;
-        colc[tid] = make_float4(a.w_per_tensor ? a.w_scale[0] : a.w_scale[cc], a.w_per_tensor ? a.w_zero[0] : a.w_zero[cc],
+        const float zw = a.w_per_tensor ? a.w_zero[0] : a.w_zero[cc];
+        colc[tid] = make_float4(a.w_per_tensor ? a.w_scale[0] : a.w_scale[cc], zw - linf_centre(zw, a.w_sign),
                                 a.bias ? a.bias[cc] : 0.0f, 0.0f);
     }
 
@@ -837,8 +849,10 @@ __global__ __launch_bounds__(256, 2) void linear_f32_mfma_kernel(const LinArgs a
     }
     // weights: thread <-> (column c = tid >> 1, 16-code half hh = tid & 1)
     const int wc = tid >> 1, whh = tid & 1;
-    const uint8_t *wrow = a.w + (int64_t)((n0 + wc < a.O) ? n0 + wc : a.O - 1) * a.K + 16 * whh;
-    const float wshift = a.w_sign ? 128.0f : 0.0f;       // stored u -> q = u - 128 (signed) | u
+    const int wcc = (n0 + wc < a.O) ? n0 + wc : a.O - 1;
+    const uint8_t *wrow = a.w + (int64_t)wcc * a.K + 16 * whh;
+    // stored u -> q = u - 128 (signed) | u, centred: q - c = u - wshift with wshift an integer in [0, 255]
+    const float wshift = (a.w_sign ? 128.0f : 0.0f) + linf_centre(a.w_per_tensor ? a.w_zero[0] : a.w_zero[wcc], a.w_sign);
 
     float4 xv[4];
     uint4 wv;
@@ -874,7 +888,7 @@ __global__ __launch_bounds__(256, 2) void linear_f32_mfma_kernel(const LinArgs a
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const uint32_t b0 = (ww[j >> 1] >> (16 * (j & 1))) & 0xffu, b1 = (ww[j >> 1] >> (16 * (j & 1) + 8)) & 0xffu;
-            const float f0 = (float)b0 - wshift, f1 = (float)b1 - wshift;   // |q| <= 255: exact in bf16
+            const float f0 = (float)b0 - wshift, f1 = (float)b1 - wshift;   // |q - c| <= 255: exact in bf16
             pk[j] = __builtin_amdgcn_perm(__float_as_uint(f1), __float_as_uint(f0), 0x07060302u);
         }
         uint8_t *wd = lsm + 3 * LF_PLANE + wc * 64;
@@ -972,27 +986,15 @@ static bool lin_mfma_eligible(const qe_qparam *x, const qe_qparam *w, int64_t B,
 }  // namespace qe
 
 namespace qe {
-// The int8 MFMA forms of quantlinear (lin_mfma_eligible problems), one choice of kernel for every epilogue.  dst_aligned:
-// the epilogue's destination (out, or codes) is 16-byte aligned.
-template <int EPI>
-static int launch_lin_mfma(const LinArgs &a, bool dst_aligned, hipStream_t s)
+// The int8 MFMA kernel of a lin_mfma_eligible problem, one choice for every epilogue (qe_quantlinear_form numbers them; 0 is
+// the order-preserving fp32 kernel).  dst_aligned: the epilogue's destination (out, or codes) is 16-byte aligned.
+enum { LIN_FORM_NJ2 = 1, LIN_FORM_NJ4 = 2, LIN_FORM_W8 = 3, LIN_FORM_W4 = 4 };
+static int lin_mfma_form(int64_t B, int K, int O, bool dst_aligned)
 {
-    const int64_t B = a.B;
-    const int K = a.K, O = a.O;
-    // tile width: 256 columns unless that leaves the chip under-filled; QE_LIN_NJ=2|4 overrides (tuning)
+    // tile width: 256 columns unless that leaves the chip under-filled; QE_LIN_NJ=2|4 overrides (tuning), big tiles included
+    if (const char *e = env_get("QE_LIN_NJ")) return atoi(e) == 2 ? LIN_FORM_NJ2 : LIN_FORM_NJ4;
     int nj = 4;
     if (((B + LM - 1) / LM) * ((O + 255) / 256) < kNumCU) nj = 2;   // under-filled chip (the ViT head: 8 workgroups): twice as many, half as wide (17.8 -> 11.5 us)
-    if (const char *e = env_get("QE_LIN_NJ")) nj = atoi(e) == 2 ? 2 : 4;
-    const int ln = 64 * nj;
-    const int64_t blocks = ((B + LM - 1) / LM) * ((O + ln - 1) / ln);
-    if (blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
-    // more than 64 KB of dynamic LDS needs the attribute once
-    static const bool raised =
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_mfma_kernel<4, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lin_lds_bytes<4>()) == hipSuccess &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_mfma_kernel<2, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lin_lds_bytes<2>()) == hipSuccess;
-    (void)raised;
     // 128-deep stages: 320 x 256 tiles (one 8-wave workgroup per CU) when the reduction is deep, 160 x 256 tiles (two 4-wave
     // workgroups per CU) when the layer is bound by its stores (K <= 1024) -- either when the problem fills the chip with
     // them (O % 256 == 0: whole column tiles).  QE_LIN8=0: never, 1: the 8-wave form, 2: the 4-wave form
@@ -1006,19 +1008,41 @@ static int launch_lin_mfma(const LinArgs &a, bool dst_aligned, hipStream_t s)
         if (const char *e = env_get("QE_LIN8")) big = atoi(e);
         if (big < 0 || big > 2) big = 0;
     }
-    if (big != 0 && !env_get("QE_LIN_NJ")) {
+    if (big == 1) return LIN_FORM_W8;
+    if (big == 2) return LIN_FORM_W4;
+    return nj == 4 ? LIN_FORM_NJ4 : LIN_FORM_NJ2;
+}
+
+template <int EPI>
+static int launch_lin_mfma(const LinArgs &a, bool dst_aligned, hipStream_t s)
+{
+    const int64_t B = a.B;
+    const int O = a.O;
+    const int form = lin_mfma_form(B, a.K, O, dst_aligned);
+    if (form == LIN_FORM_W8 || form == LIN_FORM_W4) {
         static const bool raised8 =
             hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_mfma8_kernel<2, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L8Geom<2>::LDS) == hipSuccess &&
             hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_mfma8_kernel<1, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L8Geom<1>::LDS) == hipSuccess;
         (void)raised8;
-        const int tm = big == 1 ? 320 : 160;
+        const int tm = form == LIN_FORM_W8 ? 320 : 160;
         const int64_t blocks8 = ((B + tm - 1) / tm) * (O / L8_TN);
         if (blocks8 > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
-        if (big == 1) hipLaunchKernelGGL((linear_mfma8_kernel<2, EPI>), dim3((unsigned)blocks8), dim3(512), L8Geom<2>::LDS, s, a);
-        else          hipLaunchKernelGGL((linear_mfma8_kernel<1, EPI>), dim3((unsigned)blocks8), dim3(256), L8Geom<1>::LDS, s, a);
-    } else
-    if (nj == 4) hipLaunchKernelGGL((linear_mfma_kernel<4, EPI>), dim3((unsigned)blocks), dim3(256), lin_lds_bytes<4>(), s, a);
-    else         hipLaunchKernelGGL((linear_mfma_kernel<2, EPI>), dim3((unsigned)blocks), dim3(256), lin_lds_bytes<2>(), s, a);
+        if (form == LIN_FORM_W8) hipLaunchKernelGGL((linear_mfma8_kernel<2, EPI>), dim3((unsigned)blocks8), dim3(512), L8Geom<2>::LDS, s, a);
+        else                     hipLaunchKernelGGL((linear_mfma8_kernel<1, EPI>), dim3((unsigned)blocks8), dim3(256), L8Geom<1>::LDS, s, a);
+    } else {
+        const int ln = form == LIN_FORM_NJ4 ? 256 : 128;
+        const int64_t blocks = ((B + LM - 1) / LM) * ((O + ln - 1) / ln);
+        if (blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
+        // more than 64 KB of dynamic LDS needs the attribute once
+        static const bool raised =
+            hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_mfma_kernel<4, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lin_lds_bytes<4>()) == hipSuccess &&
+            hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_mfma_kernel<2, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lin_lds_bytes<2>()) == hipSuccess;
+        (void)raised;
+        if (form == LIN_FORM_NJ4) hipLaunchKernelGGL((linear_mfma_kernel<4, EPI>), dim3((unsigned)blocks), dim3(256), lin_lds_bytes<4>(), s, a);
+        else                      hipLaunchKernelGGL((linear_mfma_kernel<2, EPI>), dim3((unsigned)blocks), dim3(256), lin_lds_bytes<2>(), s, a);
+    }
     QE_LAUNCH_CHECK();
     return QE_OK;
 }
@@ -1028,6 +1052,12 @@ extern "C" int qe_quantlinear_path(const qe_qparam *x, const qe_qparam *w, int64
 {
     if (x == nullptr || w == nullptr) return 0;
     return qe::lin_mfma_eligible(x, w, B, K, O) ? 1 : 0;
+}
+
+extern "C" int qe_quantlinear_form(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O, int32_t dst_aligned)
+{
+    if (x == nullptr || w == nullptr || !qe::lin_mfma_eligible(x, w, B, K, O)) return 0;
+    return qe::lin_mfma_form(B, K, O, dst_aligned != 0);
 }
 
 extern "C" int qe_quantlinear(const qe_qparam *x, const qe_qparam *w, const float *bias,

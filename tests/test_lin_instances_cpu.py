@@ -1,0 +1,73 @@
+"""CPU: the linear instance table (tests/lin_instances.py) names the kernel the planner picks for each row (qe_quantlinear_form,
+qe_quantlinear_float_input_path: host-only queries), and together its rows reach every instance the linear launchers can
+select: 16 int8 MFMA instances (four kernels x F32 / CODES / CODES_GELU / RES), both linear_f32_mfma_kernel instances and
+both linear_generic_kernel instances."""
+import ctypes
+
+import lin_instances as li
+from quantize_amd import capi
+
+ALIGNED = 1 << 20        # a 16-byte aligned stand-in address: the queries look at alignment only
+
+
+def _q():
+    return capi.QeQParam(ALIGNED, 8, 1, ALIGNED, ALIGNED, 1)
+
+
+def test_rows_name_their_planned_kernel():
+    for B, K, O, env, form, note in li.ROWS:
+        with li.knobs(env, capi.reload_env):
+            got = capi.linear_form(_q(), _q(), B, K, O)
+        assert got == form, "%s (%s, env %s): the planner picks %s, the row says %s" % (
+            (B, K, O), note, env, capi.LINEAR_FORMS[got], capi.LINEAR_FORMS[form])
+
+
+def test_float_input_rows_name_their_kernel():
+    L = capi.lib()
+    for B, K, O, env, form, note in li.F_ROWS:
+        with li.knobs(env, capi.reload_env):
+            got = int(L.qe_quantlinear_float_input_path(ALIGNED, ctypes.byref(_q()), B, K, O))
+        assert got == form, ((B, K, O), note, env, got)
+
+
+def test_rows_cover_every_instance():
+    every = li.every_instance()
+    assert len(every) == 20
+    missing = every - li.covered()
+    assert not missing, "no row reaches %s" % sorted(missing)
+    assert li.covered() <= every
+    print("linear instances reached: %d of %d" % (len(li.covered()), len(every)))
+
+
+def test_rows_reach_the_edges():
+    by_form = lambda f: [r for r in li.ROWS if r[4] == f]
+    for f in (1, 2, 3, 4):
+        rows = by_form(f)
+        tm = {1: 128, 2: 128, 3: 320, 4: 160}[f]
+        stage = 64 if f in (1, 2) else 128
+        assert any(B == 1 for B, *_ in rows), f
+        assert any(1 < B < tm for B, *_ in rows), f
+        assert any(B > tm and B % tm != 0 for B, *_ in rows), f
+        assert any(K == stage for _, K, *_ in rows), f
+        assert any(K >= 3072 for _, K, *_ in rows), f
+        if f in (1, 2):
+            assert any(O % 16 != 0 for _, _, O, *_ in rows) and any(O < 64 for _, _, O, *_ in rows), f
+    assert {3072, 4096, 5120} <= {K for _, K, *_ in li.ROWS}
+    # the two layers a 64-image ViT-B/16 batch runs on the big tiles, placed by the planner
+    assert (12608, 768, 3072, None, 4) in [r[:5] for r in li.ROWS]
+    assert (12608, 3072, 768, None, 3) in [r[:5] for r in li.ROWS]
+    # every MFMA form sees each activation quantiser (signed / unsigned codes, per-row / per-tensor, asymmetric)
+    for f in (1, 2, 3, 4):
+        assert {li.XQ[i % 3] for i, r in enumerate(li.ROWS) if r[4] == f} == set(li.XQ), f
+
+
+def test_query_follows_the_knobs():
+    q = _q()
+    with li.knobs({"QE_LIN_NJ": "2", "QE_LIN8": "1"}, capi.reload_env):
+        assert capi.linear_form(q, q, 12608, 3072, 768) == 1        # QE_LIN_NJ rules out the big tiles
+    with li.knobs({"QE_LIN8": "0"}, capi.reload_env):
+        assert capi.linear_form(q, q, 12608, 3072, 768) == 2
+    assert capi.linear_form(q, q, 12608, 3072, 768, dst_aligned=False) == 2   # big tiles store whole 16-byte pieces
+    assert capi.linear_form(q, q, 12608, 3000, 768) == 0                       # K % 64 != 0
+    bits4 = capi.QeQParam(ALIGNED, 4, 1, ALIGNED, ALIGNED, 1)
+    assert capi.linear_form(bits4, q, 64, 256, 256) == 0

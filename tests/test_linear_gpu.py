@@ -85,18 +85,34 @@ def test_g6_reference_module_capture(engine, g6):
         assert np.abs(y2.cpu().numpy() - ref).max() <= 2e-5 * scale, key
 
 
-def _random_case(rng, B, K, O, wb, wsgn, ab, asgn, w_pc, a_pr, zeros, bias):
+def _context(rng, B, K):
+    """Attention-context-like activations: convex mixtures (softmax rows) of positive-mean values."""
+    logits = rng.normal(0, 3, size=(B, 64))
+    p = np.exp(logits - logits.max(1, keepdims=True))
+    p /= p.sum(1, keepdims=True)
+    return p @ rng.normal(0.5, 1, size=(64, K))
+
+
+def _random_case(rng, B, K, O, wb, wsgn, ab, asgn, w_pc, a_pr, zeros, bias, zw_range=None, xdist="normal"):
+    """zw_range: per-column weight zero points |zw| uniform in it, random sign on signed codes (default |zw| <= 3);
+    xdist (fp32 activations): "normal" N(0, 1), "abs" |N(0, 1)|, "context" (_context)."""
     rngq = lambda b, s: (-(1 << (b - 1)), (1 << (b - 1)) - 1) if s else (0, (1 << b) - 1)
     wlo, whi = rngq(wb, wsgn)
     qw = rng.randint(wlo, whi + 1, size=(O, K))
     n_ws = O if w_pc else 1
     sw = rng.uniform(2.5e-4, 7.5e-4, size=n_ws).astype(np.float32)
     zw = rng.uniform(-3, 3, size=n_ws).astype(np.float32) if zeros else np.zeros(n_ws, np.float32)
+    if zw_range is not None:
+        # asymmetric weights as a quantiser leaves them: each column's codes spread about its zero point
+        zw = rng.uniform(*zw_range, size=n_ws) * (rng.choice([-1.0, 1.0], size=n_ws) if wsgn else 1.0)
+        zw = zw.astype(np.float32)
+        qw = np.clip(np.rint(zw.reshape(-1, 1) + rng.normal(0, 40, size=(O, K))), wlo, whi).astype(np.int64)
     wp, wd = oracle.tpack(qw.astype(np.float32), wb, bool(wsgn))
     b = rng.normal(0, 0.1, size=O).astype(np.float32) if bias else None
     case = dict(B=B, K=K, O=O, wp=wp, wd=wd, sw=sw, zw=zw, bias=b, wb=wb, wsgn=wsgn, ab=ab, asgn=asgn)
     if ab == 0:
-        x = rng.normal(0, 1, size=(B, K)).astype(np.float32)
+        x = {"normal": lambda: rng.normal(0, 1, size=(B, K)), "abs": lambda: np.abs(rng.normal(0, 1, size=(B, K))),
+             "context": lambda: _context(rng, B, K)}[xdist]().astype(np.float32)
         case["x"] = x
         case["o32"] = oracle.quantlinear_float_input(x, wp, wd, sw, zw, b, mode="fp32")
         case["fma"] = oracle.quantlinear_float_input(x, wp, wd, sw, zw, b, mode="fp32_fma")
@@ -173,6 +189,19 @@ def test_float_input_mfma_vit_shapes(engine, monkeypatch):
         assert path == 2
         err = np.abs(y.cpu().numpy().astype(np.float64) - c["o64"]).max()
         assert err <= max(1e-5, np.abs(c["o32"].astype(np.float64) - c["o64"]).max()), (B, K, O, err)   # the conv rule: no headroom factor
+    # large zero points (unsigned codes about 128, asymmetric signed weights) with non-zero-mean activations (post-GELU-like,
+    # attention-context-like): the regime where sw (S_xq - zw S_x) would cancel; F32 and RES against the oracle's chains
+    for (B, K, O, wsgn, zr, xdist) in [(197, 768, 768, 0, (120, 136), "abs"), (333, 3072, 256, 0, (120, 136), "context"),
+                                       (197, 3072, 768, 1, (95, 105), "context"), (333, 768, 320, 1, (95, 105), "abs")]:
+        cz = _random_case(rng, B, K, O, 8, wsgn, 0, 0, w_pc=True, a_pr=False, zeros=True, bias=True, zw_range=zr, xdist=xdist)
+        y, path = _run(engine, cz, True)
+        assert path == 2
+        _close(y.cpu().numpy(), cz["o64"], cz["o32"], "large zw %s" % ((B, K, O, wsgn, xdist),), cz["fma"])
+        xt, res = _t(cz["x"]), torch.randn(B, O, device=DEV)
+        wq = capi.qparam(_t(cz["wp"]), 8, wsgn, _t(cz["sw"]), _t(cz["zw"]))
+        assert capi.linear_float_input_residual_path(xt, wq, B, K, O) == 1
+        out = capi.quantlinear_float_input_residual(xt, wq, _t(cz["bias"]), O, res)
+        assert torch.equal(out, y + res)
     monkeypatch.setenv("QE_LIN_F32_MFMA", "0")
     capi.reload_env()
     y0, path0 = _run(engine, c, True)

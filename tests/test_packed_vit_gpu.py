@@ -16,17 +16,26 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
+# ViT-B/16 layouts at other widths (224 x 224 images): ViT-S/16's (E 384: LayerNorm's NV = 2 instance) and ViT-H/14's (E 1280:
+# NV = 8; a 14 x 14 patch, so the patch GEMM has K = 588 and runs on the fp32 kernel), at reduced depth
+SHAPED = {"vit_s16_shape": dict(width=384, heads=6, mlp=1536, depth=2),
+          "vit_h14_shape": dict(width=1280, heads=16, mlp=5120, patch=14, depth=1)}
+
+
 @pytest.fixture(scope="module")
 def models():
     out = {}
     for arch in ("vit_tiny_test", "vit_b_16"):
         sd = calibrated_state_dict(arch, device=DEV, seed=0)
         out[arch] = PackedViT.from_state_dict(sd, CONFIGS[arch]["heads"])
+    for name, kw in SHAPED.items():
+        sd = calibrated_state_dict("vit_b_16", device=DEV, seed=0, **kw)
+        out[name] = PackedViT.from_state_dict(sd, kw["heads"])
     return out
 
 
 def _images(N, arch, seed):
-    s = CONFIGS[arch]["image_size"]
+    s = CONFIGS.get(arch, CONFIGS["vit_b_16"])["image_size"]
     g = torch.Generator(device="cpu").manual_seed(seed)
     return torch.randn(N, 3, s, s, generator=g).to(DEV)
 
@@ -39,7 +48,8 @@ def _epi(on):
     capi.reload_env()
 
 
-@pytest.mark.parametrize("arch,N", [("vit_tiny_test", 2), ("vit_tiny_test", 5), ("vit_b_16", 1), ("vit_b_16", 2), ("vit_b_16", 3)])
+@pytest.mark.parametrize("arch,N", [("vit_tiny_test", 2), ("vit_tiny_test", 5), ("vit_b_16", 1), ("vit_b_16", 2), ("vit_b_16", 3),
+                                    ("vit_s16_shape", 3), ("vit_h14_shape", 2)])
 def test_fused_epilogues_equal_two_pass(models, arch, N):
     m = models[arch]
     x = _images(N, arch, N)
@@ -63,7 +73,7 @@ def test_fused_epilogues_equal_two_pass(models, arch, N):
 BLOCK_REL_TOL = 2e-2
 
 
-@pytest.mark.parametrize("arch,N", [("vit_tiny_test", 3), ("vit_b_16", 2)])
+@pytest.mark.parametrize("arch,N", [("vit_tiny_test", 3), ("vit_b_16", 2), ("vit_s16_shape", 2), ("vit_h14_shape", 2)])
 def test_block_fused_vs_layers(models, arch, N):
     m = models[arch]
     x = m.embed(_images(N, arch, 11), "layers", None)
@@ -100,6 +110,27 @@ def test_logits_fused_vs_layers_and_wiring(models):
             b.q, b.k = b.k, b.q
     mut = float((lm - ll).abs().max())
     print("logits: fused vs layers %.3g, q/k swapped %.3g, scale %.3g" % (gap, mut, float(ll.abs().max())))
+    assert gap <= 0.05 * float(ll.abs().max())
+    assert mut > 5 * gap
+
+
+@pytest.mark.parametrize("arch", list(SHAPED))
+def test_wiring_on_other_widths(models, arch):
+    """The q / k swap of test_logits_fused_vs_layers_and_wiring on the ViT-S/16- and ViT-H/14-shaped models: the swap moves the
+    logits far more than the fused and layers routes differ."""
+    m = models[arch]
+    x = _images(2, arch, 5)
+    lf, ll = m(x, "fused"), m(x, "layers")
+    gap = float((lf - ll).abs().max())
+    for b in m.blocks:
+        b.q, b.k = b.k, b.q
+    try:
+        lm = m(x, "fused")
+    finally:
+        for b in m.blocks:
+            b.q, b.k = b.k, b.q
+    mut = float((lm - ll).abs().max())
+    print("%s logits: fused vs layers %.3g, q/k swapped %.3g, scale %.3g" % (arch, gap, mut, float(ll.abs().max())))
     assert gap <= 0.05 * float(ll.abs().max())
     assert mut > 5 * gap
 

@@ -7,6 +7,7 @@
   * qe_layernorm_quantize_pack: fp32 error at most 2x torch F.layer_norm's, codes == qe_quantize_pack of its own output;
   * qe_quantize_patchify == qe_quantize_pack of the unfolded images, and the patch GEMM computes conv_proj."""
 import contextlib
+import ctypes
 import os
 
 import numpy as np
@@ -210,6 +211,157 @@ def test_layernorm_quantize_pack(E):
         assert torch.equal(c, capi.quantize_pack(ln, r._keep[0], r._keep[1], r.qmin, r.qmax, r.n_bits, r.sign)[0])
     codes_ws, _, _ = capi.layernorm_quantize_pack(x, gamma, beta, 1e-6, rqs_all)
     assert all(torch.equal(a, b) for a, b in zip(codes, codes_ws))
+
+
+# Every LayerNorm instance (NV = 1, 2, 4, 8 float4 per lane: E up to 256, 512, 1024, 2048), partial float4 groups (E / 4 not a
+# multiple of 64), and the row counts of a single row, a few, a ragged last workgroup and ViT-B/16 at 256 images.
+LN_E = [4, 64, 100, 260, 384, 516, 768, 1028, 1280, 2044, 2048]
+LN_ROWS = [1, 3, 5, 777, 50432]
+EPS32 = 2.0 ** -23
+
+
+def _ln_input(rows, E, seed):
+    """Rows of N(0, 9) around a per-row offset N(0, 400); the first rows adversarial: a large mean offset with a small spread,
+    a constant row (0.75: its sum and mean are exact, so x - mean is 0 and the row's LayerNorm is beta), a single outlier."""
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    x = torch.randn(rows, E, generator=g, device=DEV) * 3 + torch.randn(rows, 1, generator=g, device=DEV) * 20
+    gamma = 1 + 0.2 * torch.randn(E, generator=g, device=DEV)
+    beta = 0.1 * torch.randn(E, generator=g, device=DEV)
+    x[0] = 300.0 + 0.05 * torch.randn(E, generator=g, device=DEV)
+    if rows > 1:
+        x[1] = 0.75
+    if rows > 2:
+        x[2] = torch.randn(E, generator=g, device=DEV)
+        x[2, E // 3] = 1e4
+    return x, gamma, beta
+
+
+def _ln64(x, gamma, beta, eps):
+    x64 = x.double()
+    m = x64.mean(-1, keepdim=True)
+    y = (x64 - m) / torch.sqrt(((x64 - m) ** 2).mean(-1, keepdim=True) + eps)
+    return y if gamma is None else y * gamma.double() + beta.double()
+
+
+def _ln_bound(ref, x, gamma, beta, eps):
+    """Per-row error bound: 2x torch F.layer_norm's error on that row, floored at 8 ulp of the row's largest |LayerNorm|, and
+    never looser than today's whole-tensor rule, 2x torch's largest error.  The floor: where torch happens to land within an
+    ulp or two on a row, the kernel's different but equally valid reduction order still rounds.  Each output is
+    (x - mean) * rstd * gamma + beta: half an ulp for each of the subtraction, the two products and the add, about one for the
+    mean, and two to three for rstd (the fp32 sum of squares, the division, the square root): 5 to 6 ulp, 8 with margin."""
+    e_t = (F.layer_norm(x, (x.shape[-1],), gamma, beta, eps).double() - ref).abs().amax(-1)
+    big = ref.abs().amax(-1).float()
+    ulp = (torch.nextafter(big, torch.full_like(big, float("inf"))) - big).double()
+    return torch.minimum(torch.maximum(2 * e_t, 8 * ulp), 2 * e_t.max())
+
+
+def _check_ln_codes_f64(codes, r, ref, bound, what):
+    """codes (stored, 8-bit) == the float64 codes of ref, except flips of one where ref / sc - zr is within the fp32 error
+    bound (bound on the value, then the division and subtraction) of a half-integer."""
+    sc, zr = float(r._keep[0][0]), float(r._keep[1][0])
+    t = ref / sc - zr
+    q64 = torch.clamp(torch.round(t), r.qmin, r.qmax)
+    q = codes.view(ref.shape).to(torch.int32) - (128 if r.sign else 0)
+    d = (q.double() - q64).abs()
+    band = bound[:, None] / sc + 4 * EPS32 * (t.abs() + abs(zr))
+    near_tie = ((t - torch.floor(t)) - 0.5).abs() <= band
+    bad = (d > 1) | ((d == 1) & ~near_tie)
+    assert not bool(bad.any()), "%s: %d codes off the float64 codes outside the tie band" % (what, int(bad.sum()))
+
+
+@pytest.mark.parametrize("E", LN_E)
+def test_layernorm_vs_float64(E):
+    rqs = [_rq(0.02, 0.0, 8, True), _rq(0.03, -120.0, 8, False)]
+    for rows in LN_ROWS:
+        x, gamma, beta = _ln_input(rows, E, seed=rows * 4096 + E)
+        codes, ln, st = capi.layernorm_quantize_pack(x, gamma, beta, 1e-6, rqs, ln_out="new")
+        assert capi.layernorm_path(rows, E, rqs, codes) == 1 and int(st.item()) == 0
+        ref = _ln64(x, gamma, beta, 1e-6)
+        bound = _ln_bound(ref, x, gamma, beta, 1e-6)
+        e_k = (ln.double() - ref).abs().amax(-1)
+        worst = int(torch.argmax(e_k - bound))
+        assert bool((e_k <= bound).all()), "E %d rows %d: row %d error %.3g > %.3g" % (E, rows, worst, float(e_k[worst]), float(bound[worst]))
+        if rows > 1:
+            assert torch.equal(ln[1], beta)                       # the constant row
+        for c, r in zip(codes, rqs):
+            assert torch.equal(c, capi.quantize_pack(ln, r._keep[0], r._keep[1], r.qmin, r.qmax, r.n_bits, r.sign)[0])
+            _check_ln_codes_f64(c, r, ref, bound, "E %d rows %d" % (E, rows))
+    # gamma / beta NULL: the plain normalisation
+    codes, ln1, _ = capi.layernorm_quantize_pack(x, None, None, 1e-6, rqs, ln_out="new")
+    ref1 = _ln64(x, None, None, 1e-6)
+    bound1 = _ln_bound(ref1, x, None, None, 1e-6)
+    assert bool(((ln1.double() - ref1).abs().amax(-1) <= bound1).all())
+    for c, r in zip(codes, rqs):
+        assert torch.equal(c, capi.quantize_pack(ln1, r._keep[0], r._keep[1], r.qmin, r.qmax, r.n_bits, r.sign)[0])
+    # n_out = 0, only ln_out: the same fp32 LayerNorm
+    none, ln0, _ = capi.layernorm_quantize_pack(x, gamma, beta, 1e-6, [], ln_out="new")
+    assert none == [] and torch.equal(ln0, ln)
+    # two-pass form with a per-feature consumer (n_param == E) and ln_out NULL (the workspace holds the LayerNorm): the
+    # channel of element (row, e) is e
+    g = torch.Generator(device=DEV).manual_seed(E)
+    s = torch.rand(E, generator=g, device=DEV) * 0.03 + 0.01
+    z = torch.rand(E, generator=g, device=DEV) * 6 - 3
+    pf = capi.requant(s, z, -128, 127, 8, True)
+    assert capi.layernorm_path(x.shape[0], E, [pf], [torch.empty(x.numel(), dtype=torch.uint8, device=DEV)]) == 0
+    (cpf,), none, st = capi.layernorm_quantize_pack(x, gamma, beta, 1e-6, [pf])
+    assert none is None and int(st.item()) == 0
+    want = (torch.clamp(torch.round(ln / s - z), -128, 127).to(torch.int32) + 128).to(torch.uint8).flatten()
+    assert torch.equal(cpf, want)
+
+
+@pytest.mark.parametrize("E", [100, 384, 768, 2048])
+def test_layernorm_non_finite_rows(E):
+    rows = 37
+    x, gamma, beta = _ln_input(rows, E, seed=E + 1)
+    rqs = [_rq(0.02, 0.0, 8, True)]
+    codes, ln, st = capi.layernorm_quantize_pack(x, gamma, beta, 1e-6, rqs, ln_out="new")
+    assert int(st.item()) == 0
+    bad_rows = [5, 17, 36]
+    for r, v in zip(bad_rows, (float("nan"), float("inf"), float("-inf"))):
+        y = x.clone()
+        y[r, E // 2] = v
+        c2, ln2, st2 = capi.layernorm_quantize_pack(y, gamma, beta, 1e-6, rqs, ln_out="new")
+        assert int(st2.item()) == 1, (r, v)
+        keep = torch.ones(rows, dtype=torch.bool, device=DEV)
+        keep[r] = False
+        assert torch.equal(ln2[keep], ln[keep])
+        assert torch.equal(c2[0].view(rows, E)[keep], codes[0].view(rows, E)[keep])
+
+
+def test_layernorm_rejections():
+    L = capi.lib()
+    E, rows = 64, 8
+    x, gamma, beta = _ln_input(rows, E + 4, seed=3)
+    xs, gs, bs = x[:, :E].contiguous(), gamma[:E].contiguous(), beta[:E].contiguous()
+    rq = _rq(0.02, 0.0, 8, True)
+    arr = (capi.QeRequant * 1)(rq)
+
+    def call(xp, n, e, gp, bp, lnp, codes):
+        cp = (ctypes.c_void_p * 1)(codes.data_ptr())
+        return L.qe_layernorm_quantize_pack(xp, n, e, gp, bp, 1e-6, 1, arr, cp, lnp, None, None, 0, None)
+
+    codes = torch.full((rows * E + 16,), 0xAB, dtype=torch.uint8, device=DEV)
+    ln = torch.full((rows * E + 8,), 7.0, device=DEV)
+    # rows = 0: a no-op
+    assert call(xs.data_ptr(), 0, E, gs.data_ptr(), bs.data_ptr(), ln.data_ptr(), codes) == 0
+    # misaligned x, gamma or ln_out (one float off a 16-byte boundary): QE_ERR_ARG, nothing written
+    xm = torch.empty(rows * E + 4, device=DEV)
+    xm[1:1 + rows * E] = xs.flatten()
+    gm = torch.empty(E + 4, device=DEV)
+    gm[1:1 + E] = gs
+    assert call(xm.data_ptr() + 4, rows, E, gs.data_ptr(), bs.data_ptr(), ln.data_ptr(), codes) == 4
+    assert call(xs.data_ptr(), rows, E, gm.data_ptr() + 4, bs.data_ptr(), ln.data_ptr(), codes) == 4
+    assert call(xs.data_ptr(), rows, E, gs.data_ptr(), bs.data_ptr(), ln.data_ptr() + 4, codes) == 4
+    torch.cuda.synchronize()
+    assert bool((codes == 0xAB).all()) and bool((ln == 7.0).all())
+    # widths outside E % 4 == 0, 4 <= E <= QE_LN_MAX_E: QE_ERR_UNSUPPORTED
+    big = torch.zeros(rows * 2052, device=DEV)
+    for e in (2, 66, 2052):
+        assert call(big.data_ptr(), rows, e, None, None, None, codes) == 7, e
+    # the aligned call itself is accepted and writes both outputs
+    assert call(xs.data_ptr(), rows, E, gs.data_ptr(), bs.data_ptr(), ln.data_ptr(), codes) == 0
+    torch.cuda.synchronize()
+    assert not bool((codes[:rows * E] == 0xAB).all()) and not bool((ln[:rows * E] == 7.0).all())
 
 
 def test_layernorm_rejects_shapes():
