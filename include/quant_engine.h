@@ -374,6 +374,29 @@ int qe_quantize_patchify(const float *x, int32_t N, int32_t C, int32_t H, int32_
                          const float *zero, int32_t n_param, float qmin, float qmax, int n_bits, int sign, uint8_t *out,
                          int32_t *status, qe_stream_t stream);
 
+/* qe_attention -- the fp32 attention core of a ViT encoder block / nn.MultiheadAttention (need_weights=False, no mask):
+ *   out[n, t, h] = sum_s softmax_s(scale * q[n, t, h] . k[n, s, h]) v[n, s, h]      per image n < N, head h < H
+ * for query tokens t < L and key tokens s < S (S != L allowed).  Every tensor is rows of H*d floats; the row of
+ * (image n, token t) is n*rn + t*rt, and head h is columns h*d .. h*d + d - 1 of it: token-major (N L, E) rows are
+ * rn = L, rt = 1 (the ViT), sequence-major (L N, E) rows are rn = 1, rt = N (nn.MultiheadAttention, batch_first=False).
+ * Both are read and written in place: no transposes, no workspace, and the score matrix is never stored.
+ * q, k, v, out   device pointers, 16-byte aligned; k and v share kv_rn / kv_rt; out must not overlap q, k or v
+ *                (QE_ERR_ARG, as are non-positive sizes and negative strides -- answered before any device work).
+ * scale          multiplies q once as it is loaded (fp32); 1 / sqrt(d) gives torch's default.
+ * Numerics: scores are fp32 products and sums (fmaf chains); the softmax is online over key tiles with a running row max
+ * m, p = exp2f((score - m) * log2(e)) (the max-subtracted score scaled by log2(e), then exp2f); P.V products, their
+ * sums and the row sum in fp32; one division by the row sum at the end.
+ * Non-finite inputs: a NaN in a query row poisons only that row of that head; a NaN in a key or value row poisons only
+ * that (image, head).
+ * qe_attention_path (host only): 1 = the fp32 MFMA kernel (v_mfma_f32_32x32x2_f32: d % 16 == 0, d <= 128),
+ * 0 = the fp32 VALU kernel (every other d <= 256, and every shape under QE_ATTN=0), -1 = no kernel (d > 256, where
+ * qe_attention returns QE_ERR_UNSUPPORTED, or a non-positive size).                                                  */
+int qe_attention_path(int32_t L, int32_t S, int32_t H, int32_t d);
+int qe_attention(const float *q, const float *k, const float *v, float *out,
+                 int32_t N, int32_t L, int32_t S, int32_t H, int32_t d,
+                 int64_t q_rn, int64_t q_rt, int64_t kv_rn, int64_t kv_rt, int64_t o_rn, int64_t o_rt,
+                 float scale, qe_stream_t stream);
+
 /* ---- auxiliary (no counterpart in the reference's extension) ---------------------------------
  * Global average pool of an fp32 NCHW tensor: out[plane] = mean(x[plane][0..P)) for n_planes = N*C planes of P
  * contiguous floats.  The reference's models do this in PyTorch (torchvision ResNet: AdaptiveAvgPool2d); bench.py's

@@ -30,7 +30,7 @@ SYMBOLS = ["qe_error_string", "qe_last_hip_error", "qe_version", "qe_target_arch
            "qe_quantlinear_residual_path", "qe_quantlinear_residual_workspace_bytes", "qe_quantlinear_residual",
            "qe_quantlinear_float_input_residual_path", "qe_quantlinear_float_input_residual_workspace_bytes",
            "qe_quantlinear_float_input_residual", "qe_layernorm_quantize_pack_path", "qe_layernorm_quantize_pack_workspace_bytes",
-           "qe_layernorm_quantize_pack", "qe_quantize_patchify"]
+           "qe_layernorm_quantize_pack", "qe_quantize_patchify", "qe_attention_path", "qe_attention"]
 
 ACTS = {None: 0, "none": 0, "gelu": 1}
 
@@ -161,6 +161,10 @@ def lib():
     L.qe_layernorm_quantize_pack.argtypes = [vp, i64, i32, vp, vp, f32, i32, pr, ppc, vp, vp, vp, sz, vp]
     L.qe_quantize_patchify.restype = i32
     L.qe_quantize_patchify.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, f32, f32, i32, i32, vp, vp, vp]
+    L.qe_attention_path.restype = i32
+    L.qe_attention_path.argtypes = [i32, i32, i32, i32]
+    L.qe_attention.restype = i32
+    L.qe_attention.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, i64, i64, f32, vp]
     _lib = L
     return L
 
@@ -614,3 +618,35 @@ def quantize_patchify(x, patch, scale, zero, qmin, qmax, n_bits, sign, out=None,
                                      float(qmin), float(qmax), int(n_bits), 1 if sign else 0, out.data_ptr(), status.data_ptr(),
                                      _stream(stream)))
     return out, status
+
+
+def attention_path(L, S, H, d):
+    """qe_attention_path: 1 = the fp32 MFMA kernel, 0 = the fp32 VALU kernel, -1 = no kernel for the shape."""
+    return int(lib().qe_attention_path(int(L), int(S), int(H), int(d)))
+
+
+def attention(q, k, v, N, L, H, S=None, layout="token", scale=None, out=None, stream=None):
+    """qe_attention: softmax(scale q k^T) v per (image, head) on fp32 rows of E = H d floats, read in place.
+    layout "token": q / out are (N L, E) and k / v (N S, E) rows (a ViT's projections); "seq": (L N, E) and (S N, E)
+    (nn.MultiheadAttention with batch_first=False).  S defaults to L, scale to d ** -0.5.  Returns out, shaped like q
+    (a new tensor when out is None).  No host synchronisation."""
+    import torch
+    S = L if S is None else int(S)
+    N, L, H = int(N), int(L), int(H)
+    for t, rows in ((q, N * L), (k, N * S), (v, N * S)):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() % rows == 0
+    E = q.numel() // (N * L)
+    assert k.numel() == N * S * E and v.numel() == N * S * E and E % H == 0
+    d = E // H
+    if layout == "token":
+        q_rn, q_rt, kv_rn, kv_rt = L, 1, S, 1
+    elif layout == "seq":
+        q_rn, q_rt, kv_rn, kv_rt = 1, N, 1, N
+    else:
+        raise ValueError("layout must be 'token' or 'seq'")
+    if out is None:
+        out = torch.empty_like(q)
+    assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == q.numel()
+    check(lib().qe_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), N, L, S, H, d, q_rn, q_rt, kv_rn, kv_rt,
+                             q_rn, q_rt, float(d ** -0.5 if scale is None else scale), _stream(stream)))
+    return out

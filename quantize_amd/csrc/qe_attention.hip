@@ -1,0 +1,344 @@
+// qe_attention.hip -- the fp32 attention core of a ViT / nn.MultiheadAttention for gfx950 (MI355X):
+//   out[n, t, h*d + c] = sum_s softmax_s(scale * q[n, t, h] . k[n, s, h]) v[n, s, h*d + c]
+// read in place from rows of H*d floats (row n*rn + t*rt), never storing the L x S score matrix.
+//
+// attn_mfma_kernel<D> (d % 16 == 0, d <= 128): flash-style forward on the exact fp32 matrix pipe (v_mfma_f32_32x32x2_f32:
+// a k-ordered fmaf chain, one rounding per product).  A wave owns 32 query rows of one (image, head); a workgroup holds up to
+// 8 such waves of the same head, so the K / V rows they all stream are shared in the CU's L1.  Per 32-key tile:
+//   S^T = K Q^T   A = K (lane: key lane&31), B = Q^T (lane: query lane&31); the k order is permuted (step s takes dim s from
+//                 lane half 0, dim s + d/2 from half 1: both operands use the same pairing, and a sum over k is order-free),
+//                 so each lane loads d/2 CONTIGUOUS floats of its row.  The accumulator gives lane l the 16 scores of query
+//                 l&31 for keys crow(r, l>>5) = (r&3) + 8(r>>2) + 4(l>>5): a row max is 15 fmaxf and one exchange with
+//                 lane l^32.
+//   online softmax  m' = max(m, tile max); p = exp2f((s - m') log2e); l = l alpha + sum p; O = O alpha with
+//                 alpha = exp2f((m - m') log2e).  The row sum stays split between the two lane halves until the end.
+//   O^T += V^T P^T  A = V^T (lane: column lane&31 of a 32-column block, key crow(s, l>>5)), B = P^T: register s of the score
+//                 accumulator IS the B operand of k-step s -- no lane movement.  O^T has the query on the lane, so the
+//                 rescale by alpha and the final division by l are lane-local; the store is 4 float4 per 32-column block.
+// K for the next tile is loaded while the softmax and P.V of this one run, V while S^T is computed.
+// attn_valu_kernel<NO> (every d <= 256; QE_ATTN=0 takes it for every shape): one wave per query row, 64 keys per step (a
+// lane per key: an fmaf chain over c = 0..d-1), the same online softmax, column c of the output on lane c % 64.
+//
+// Numerics (both kernels): q is multiplied by `scale` once as it is loaded (fp32); scores are fp32 fmaf sums; the softmax
+// uses exp2f with the log2(e) factor applied to the max-subtracted score, (s - m) * log2e, so the subtraction stays exact
+// near the max; products P.V and the row sum in fp32; one division by the row sum at the end.
+// Non-finite inputs: fmaxf skips a NaN score, and exp2f(NaN) = NaN reaches that row's sum and output: a NaN in a query
+// row poisons that row of that head only, a NaN in a key or value row that (image, head) only.
+#include "qe_common.h"
+
+#include <algorithm>
+#include <cstdlib>
+
+namespace qe {
+
+struct AttnArgs {
+    const float *q, *k, *v;
+    float *out;
+    int64_t q_rn, q_rt, kv_rn, kv_rt, o_rn, o_rt;    // in rows of H*d floats
+    int N, L, S, H, d;
+    int qgroups;                                     // workgroups per (image, head)
+    float scale;
+};
+
+constexpr float kLog2e = 1.4426950408889634f;
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+template <int D>
+__global__ __launch_bounds__(D <= 64 ? 512 : 256) void attn_mfma_kernel(const AttnArgs a)
+{
+    constexpr int HALF = D / 2;                 // k-steps of S^T; dims [h*HALF, h*HALF + HALF) on lane half h
+    constexpr int NB = (D + 31) / 32;           // 32-column blocks of O^T
+    constexpr int WPB = D <= 64 ? 8 : 4;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int lo = lane & 31, hi = lane >> 5;
+    const int64_t bid = blockIdx.x;
+    const int qg = (int)(bid % a.qgroups);
+    const int64_t nh = bid / a.qgroups;
+    const int h = (int)(nh % a.H);
+    const int n = (int)(nh / a.H);
+    const int q0 = (qg * WPB + wave) * 32;
+    if (q0 >= a.L) return;                      // wave-uniform; no barrier in this kernel
+    const int64_t E = (int64_t)a.H * a.d;
+    const int64_t col = (int64_t)h * a.d;
+
+    // Q^T operand: lane holds q[query q0 + lo][hi*HALF + s] * scale
+    float qr[HALF];
+    {
+        const int t = q0 + lo;
+        if (t < a.L) {
+            const float4 *src = reinterpret_cast<const float4 *>(a.q + (n * a.q_rn + t * a.q_rt) * E + col + hi * HALF);
+#pragma unroll
+            for (int i = 0; i < HALF / 4; ++i) {
+                const float4 x = src[i];
+                qr[4 * i] = x.x * a.scale; qr[4 * i + 1] = x.y * a.scale; qr[4 * i + 2] = x.z * a.scale; qr[4 * i + 3] = x.w * a.scale;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < HALF; ++i) qr[i] = 0.0f;
+        }
+    }
+    const float *kbase = a.k + n * a.kv_rn * E + col;
+    const float *vbase = a.v + n * a.kv_rn * E + col;
+    const int64_t kv_step = a.kv_rt * E;
+
+    float kr[HALF];
+    auto load_k = [&](int k0) {
+        const int key = k0 + lo;
+        if (key < a.S) {
+            const float4 *src = reinterpret_cast<const float4 *>(kbase + key * kv_step + hi * HALF);
+#pragma unroll
+            for (int i = 0; i < HALF / 4; ++i) {
+                const float4 x = src[i];
+                kr[4 * i] = x.x; kr[4 * i + 1] = x.y; kr[4 * i + 2] = x.z; kr[4 * i + 3] = x.w;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < HALF; ++i) kr[i] = 0.0f;
+        }
+    };
+
+    f32x16 o[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[b][r] = 0.0f;
+    float m = -INFINITY, lsum = 0.0f;
+
+    load_k(0);
+    for (int k0 = 0; k0 < a.S; k0 += 32) {
+        // V^T operand of this tile: vr[s][b] = v[key k0 + crow(s, hi)][32 b + lo]
+        float vr[16][NB];
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            const int key = k0 + (s & 3) + 8 * (s >> 2) + 4 * hi;
+            const float *src = vbase + key * kv_step;
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                const int c = 32 * b + lo;
+                vr[s][b] = (key < a.S && c < D) ? src[c] : 0.0f;
+            }
+        }
+        f32x16 sc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sc[r] = 0.0f;
+#pragma unroll
+        for (int s = 0; s < HALF; ++s) sc = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[s], qr[s], sc, 0, 0, 0);
+        if (k0 + 32 < a.S) load_k(k0 + 32);
+
+        // online softmax over this tile's 32 keys of query q0 + lo
+        float tmax = -INFINITY;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+            if (key >= a.S) sc[r] = -INFINITY;
+            tmax = fmaxf(tmax, sc[r]);
+        }
+        tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
+        const float mn = fmaxf(m, tmax);
+        const float alpha = exp2f((m - mn) * kLog2e);
+        m = mn;
+        float psum = 0.0f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            sc[r] = exp2f((sc[r] - mn) * kLog2e);
+            psum += sc[r];
+        }
+        lsum = lsum * alpha + psum;
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[b][r] *= alpha;
+#pragma unroll
+            for (int s = 0; s < 16; ++s) o[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(vr[s][b], sc[s], o[b], 0, 0, 0);
+        }
+    }
+
+    const int t = q0 + lo;
+    const float l = lsum + __shfl_xor(lsum, 32);
+    if (t >= a.L) return;
+    float *dst = a.out + (n * a.o_rn + t * a.o_rt) * E + col;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int c = 32 * b + 8 * g + 4 * hi;       // O^T rows (r&3) + 8(r>>2) + 4 hi of register r = 4 g + j
+            if (c < D)
+                *reinterpret_cast<float4 *>(dst + c) =
+                    make_float4(o[b][4 * g] / l, o[b][4 * g + 1] / l, o[b][4 * g + 2] / l, o[b][4 * g + 3] / l);
+        }
+    }
+}
+
+__device__ __forceinline__ float wave_max(float v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
+    return v;
+}
+
+__device__ __forceinline__ float wave_sum(float v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+template <int NO>
+__global__ __launch_bounds__(256) void attn_valu_kernel(const AttnArgs a)
+{
+    __shared__ float qs[4][NO * 64];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int64_t row = (int64_t)blockIdx.x * 4 + wave;      // over N * H * L
+    const int64_t rows = (int64_t)a.N * a.H * a.L;
+    const bool live = row < rows;
+    const int t = live ? (int)(row % a.L) : 0;
+    const int h = live ? (int)((row / a.L) % a.H) : 0;
+    const int n = live ? (int)(row / ((int64_t)a.L * a.H)) : 0;
+    const int64_t E = (int64_t)a.H * a.d;
+    const int64_t col = (int64_t)h * a.d;
+    const float *qrow = a.q + (n * a.q_rn + t * a.q_rt) * E + col;
+#pragma unroll
+    for (int i = 0; i < NO; ++i) {
+        const int c = lane + 64 * i;
+        qs[wave][c] = (live && c < a.d) ? qrow[c] * a.scale : 0.0f;
+    }
+    __syncthreads();
+    if (!live) return;                                        // wave-uniform, after the only barrier
+    const float *kbase = a.k + n * a.kv_rn * E + col;
+    const float *vbase = a.v + n * a.kv_rn * E + col;
+    const int64_t kv_step = a.kv_rt * E;
+    float o[NO];
+#pragma unroll
+    for (int i = 0; i < NO; ++i) o[i] = 0.0f;
+    float m = -INFINITY, l = 0.0f;
+    for (int k0 = 0; k0 < a.S; k0 += 64) {
+        const int key = k0 + lane;
+        float s = -INFINITY;
+        if (key < a.S) {
+            const float *kr = kbase + key * kv_step;
+            s = 0.0f;
+            for (int c = 0; c < a.d; ++c) s = fmaf(qs[wave][c], kr[c], s);
+        }
+        const float mn = fmaxf(m, wave_max(s));
+        const float alpha = exp2f((m - mn) * kLog2e);
+        m = mn;
+        const float p = key < a.S ? exp2f((s - mn) * kLog2e) : 0.0f;
+        l = l * alpha + wave_sum(p);
+#pragma unroll
+        for (int i = 0; i < NO; ++i) o[i] *= alpha;
+        const int nk = min(64, a.S - k0);
+        for (int j = 0; j < nk; ++j) {
+            const float pj = __shfl(p, j);
+            const float *vr = vbase + (k0 + j) * kv_step;
+#pragma unroll
+            for (int i = 0; i < NO; ++i) {
+                const int c = lane + 64 * i;
+                if (c < a.d) o[i] = fmaf(pj, vr[c], o[i]);
+            }
+        }
+    }
+    float *dst = a.out + (n * a.o_rn + t * a.o_rt) * E + col;
+#pragma unroll
+    for (int i = 0; i < NO; ++i) {
+        const int c = lane + 64 * i;
+        if (c < a.d) dst[c] = o[i] / l;
+    }
+}
+
+static int attn_path(int L, int S, int H, int d)
+{
+    if (L <= 0 || S <= 0 || H <= 0 || d <= 0 || d > 256) return -1;
+    if (d % 16 != 0 || d > 128) return 0;
+    if (const char *e = env_get("QE_ATTN")) { if (atoi(e) == 0) return 0; }
+    return 1;
+}
+
+template <int D>
+static void launch_mfma(const AttnArgs &a, hipStream_t s)
+{
+    constexpr int WPB = D <= 64 ? 8 : 4;
+    AttnArgs b = a;
+    const int tiles = ceil_div(a.L, 32);
+    const int wpb = std::min(WPB, tiles);        // a short sequence launches only the waves it has rows for
+    b.qgroups = ceil_div(tiles, WPB);
+    const int64_t blocks = (int64_t)b.qgroups * a.H * a.N;
+    hipLaunchKernelGGL(attn_mfma_kernel<D>, dim3((unsigned)blocks), dim3(64 * (b.qgroups == 1 ? wpb : WPB)), 0, s, b);
+}
+
+template <int NO>
+static void launch_valu(const AttnArgs &a, hipStream_t s)
+{
+    const int64_t blocks = ceil_div64((int64_t)a.N * a.H * a.L, 4);
+    hipLaunchKernelGGL(attn_valu_kernel<NO>, dim3((unsigned)blocks), dim3(256), 0, s, a);
+}
+
+// [lo, hi) byte range the rows of (n < N, t < T) span
+static void row_span(const float *p, int N, int T, int64_t rn, int64_t rt, int64_t E, uintptr_t &lo, uintptr_t &hi)
+{
+    const int64_t last = (int64_t)(N - 1) * rn + (int64_t)(T - 1) * rt;
+    lo = reinterpret_cast<uintptr_t>(p);
+    hi = lo + (uintptr_t)((last + 1) * E) * sizeof(float);
+}
+
+}  // namespace qe
+
+extern "C" int qe_attention_path(int32_t L, int32_t S, int32_t H, int32_t d)
+{
+    return qe::attn_path(L, S, H, d);
+}
+
+extern "C" int qe_attention(const float *q, const float *k, const float *v, float *out, int32_t N, int32_t L, int32_t S,
+                            int32_t H, int32_t d, int64_t q_rn, int64_t q_rt, int64_t kv_rn, int64_t kv_rt, int64_t o_rn,
+                            int64_t o_rt, float scale, qe_stream_t stream)
+{
+    using namespace qe;
+    if (N <= 0 || L <= 0 || S <= 0 || H <= 0 || d <= 0) return QE_ERR_ARG;
+    if (q_rn < 0 || q_rt < 0 || kv_rn < 0 || kv_rt < 0 || o_rn < 0 || o_rt < 0) return QE_ERR_ARG;
+    if (q == nullptr || k == nullptr || v == nullptr || out == nullptr) return QE_ERR_ARG;
+    if (((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
+          reinterpret_cast<uintptr_t>(out)) & 15) != 0)
+        return QE_ERR_ARG;
+    const int path = attn_path(L, S, H, d);
+    if (path < 0) return QE_ERR_UNSUPPORTED;
+    const int64_t E = (int64_t)H * d;
+    uintptr_t olo, ohi;
+    row_span(out, N, L, o_rn, o_rt, E, olo, ohi);
+    const float *ins[3] = {q, k, v};
+    const int64_t rn[3] = {q_rn, kv_rn, kv_rn}, rt[3] = {q_rt, kv_rt, kv_rt};
+    const int len[3] = {L, S, S};
+    for (int i = 0; i < 3; ++i) {
+        uintptr_t lo, hi;
+        row_span(ins[i], N, len[i], rn[i], rt[i], E, lo, hi);
+        if (lo < ohi && olo < hi) return QE_ERR_ARG;
+    }
+    const int64_t rows = (int64_t)N * H * L;
+    if ((int64_t)N * H * ceil_div(L, 32) > 0x7fffffffLL || ceil_div64(rows, 4) > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
+    AttnArgs a = {};
+    a.q = q; a.k = k; a.v = v; a.out = out;
+    a.q_rn = q_rn; a.q_rt = q_rt; a.kv_rn = kv_rn; a.kv_rt = kv_rt; a.o_rn = o_rn; a.o_rt = o_rt;
+    a.N = N; a.L = L; a.S = S; a.H = H; a.d = d; a.scale = scale;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (path == 1) {
+        switch (d) {
+        case 16: launch_mfma<16>(a, s); break;
+        case 32: launch_mfma<32>(a, s); break;
+        case 48: launch_mfma<48>(a, s); break;
+        case 64: launch_mfma<64>(a, s); break;
+        case 80: launch_mfma<80>(a, s); break;
+        case 96: launch_mfma<96>(a, s); break;
+        case 112: launch_mfma<112>(a, s); break;
+        default: launch_mfma<128>(a, s); break;
+        }
+    } else {
+        const int no = ceil_div(d, 64);
+        if (no == 1) launch_valu<1>(a, s);
+        else if (no == 2) launch_valu<2>(a, s);
+        else if (no == 3) launch_valu<3>(a, s);
+        else launch_valu<4>(a, s);
+    }
+    QE_LAUNCH_CHECK();
+    return QE_OK;
+}

@@ -227,10 +227,23 @@ class PackedMultiheadAttention:
                 setattr(self, name, val.to(device))
         return self
 
-    def __call__(self, query, key, value, route="packed", need_weights=True):
+    def __call__(self, query, key, value, route="packed", need_weights=True, attention="torch"):
+        """attention="torch": the core as torch bmm / softmax / bmm (the reference's own arithmetic).  "engine": the fp32
+        qe_attention kernel reads the three projections in their (L N, E) / (S N, E) layout and writes the context in
+        place for out_proj -- no score matrix, so need_weights must be False."""
+        if attention not in ("torch", "engine"):
+            raise ValueError("attention must be 'torch' or 'engine'")
         L, N, E = query.shape
         S = key.shape[0]
         H, d = self.num_heads, E // self.num_heads
+        if attention == "engine":
+            if need_weights:
+                raise ValueError("attention='engine' materialises no attention weights: pass need_weights=False")
+            from . import capi
+            Q, K, V = (p(x, route).reshape(-1, E).contiguous() for p, x in ((self.q, query), (self.k, key), (self.v, value)))
+            ctx = capi.attention(Q, K, V, N, L, H, S=S, layout="seq")
+            out = quantlinear_forward(ctx, (self.out_weight, self.out_des, self.out_scale, self._neg_out_zero), self.out_bias)
+            return out.reshape(L, N, E), None
         Q = self.q(query, route).reshape(L, N * H, d).transpose(0, 1)      # (N H, L, d), as F.multi_head_attention_forward splits heads
         K = self.k(key, route).reshape(S, N * H, d).transpose(0, 1)
         V = self.v(value, route).reshape(S, N * H, d).transpose(0, 1)

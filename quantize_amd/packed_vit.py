@@ -15,9 +15,10 @@ PackedViT takes the state_dict of such a model after pack() and runs it two ways
                   add in its epilogue, LayerNorm + fc1's codes, fc1 with GELU + fc2's codes in its epilogue
                   (qe_quantlinear_requant) and fc2 with the residual add in its epilogue (qe_quantlinear_residual).
 
-Both routes call the same attention core, _attention: fp32 F.scaled_dot_product_attention on (N, H, L, d) -- what
-F.multi_head_attention_forward runs for need_weights=False.  The C entry points take their two-pass form wherever the
-fused form is not eligible (sub-8-bit or per-channel consumer codes, non-MFMA shapes, QE_LIN_EPI=0), so every step of
+Both routes call the same attention core, _attention: by default fp32 F.scaled_dot_product_attention on (N, H, L, d) --
+what F.multi_head_attention_forward runs for need_weights=False; with attention="engine" the fp32 qe_attention kernel,
+which reads the three projections in their (N L, E) buffers and writes the context straight into out_proj's input.
+The C entry points take their two-pass form wherever the fused form is not eligible (sub-8-bit or per-channel consumer codes, non-MFMA shapes, QE_LIN_EPI=0), so every step of
 the fused route exists for every model the layers route runs.  With check=False the fused route makes no device -> host
 copy or synchronisation: every range flag accumulates in one device int32, read once at the end when check=True.
 """
@@ -34,8 +35,18 @@ from .packed_resnet import pack_codes
 OUT_OF_RANGE = "The input tensor is out of range."    # tpack.cu:14
 
 
-def _attention(Q, K, V, N, L, H):
+ATTENTION = ("torch", "engine")
+
+
+def _check_attention(attention):
+    if attention not in ATTENTION:
+        raise ValueError("attention must be 'torch' or 'engine'")
+
+
+def _attention(Q, K, V, N, L, H, attention="torch"):
     """(N L, E) fp32 projections -> (N L, E) context: softmax(Q K^T / sqrt(d)) V per head, fp32."""
+    if attention == "engine":
+        return capi.attention(Q, K, V, N, L, H)
     E = Q.shape[-1]
     d = E // H
     q, k, v = (t.reshape(N, L, H, d).transpose(1, 2) for t in (Q, K, V))
@@ -139,20 +150,23 @@ class PackedViT:
         return out + [self.head_lin]
 
     # ---- the two routes ----
-    def __call__(self, images, route="fused", check=True):
-        return self.forward(images, route, check)[0]
+    def __call__(self, images, route="fused", check=True, attention="torch"):
+        return self.forward(images, route, check, attention=attention)[0]
 
-    def forward(self, images, route="fused", check=True, keep_blocks=False):
-        """(logits, [block outputs (N, L, E)] if keep_blocks else None)."""
+    def forward(self, images, route="fused", check=True, keep_blocks=False, attention="torch"):
+        """(logits, [block outputs (N, L, E)] if keep_blocks else None).  attention: "torch" (F.scaled_dot_product_attention)
+        or "engine" (the qe_attention kernel), in either route."""
         if route not in ("fused", "layers"):
             raise ValueError("route must be 'fused' or 'layers'")
+        _check_attention(attention)
+        kw = {} if attention == "torch" else {"attention": attention}    # the default keeps block()'s five-argument call
         images = images.contiguous()
         N = images.shape[0]
         status = torch.zeros(1, dtype=torch.int32, device=images.device)
         x = self.embed(images, route, status)
         outs = [] if keep_blocks else None
         for b in self.blocks:
-            x = self.block(b, x, N, route, status)
+            x = self.block(b, x, N, route, status, **kw)
             if keep_blocks:
                 outs.append(x.reshape(N, -1, self.E).clone())
         cls_rows = x.reshape(N, -1, self.E)[:, 0].contiguous()
@@ -188,14 +202,15 @@ class PackedViT:
         x = torch.cat([self.class_token.expand(N, -1, -1), t], dim=1) + self.pos
         return x.reshape(-1, self.E).contiguous()
 
-    def block(self, b, x, N, route, status=None):
+    def block(self, b, x, N, route, status=None, attention="torch"):
         """One encoder block on (N L, E) fp32 rows -> (N L, E).  The fused route updates x in place."""
+        _check_attention(attention)
         E, H = self.E, self.num_heads
         L = x.shape[0] // N
         if route == "layers":
             y = F.layer_norm(x, (E,), b.ln1[0], b.ln1[1], self.eps)
             Q, K, V = (lin.m(y, route="packed") for lin in (b.q, b.k, b.v))
-            ctx = _attention(Q, K, V, N, L, H)
+            ctx = _attention(Q, K, V, N, L, H, attention)
             a = b.attn
             oq = capi.qparam(a.out_weight, b.out_bits, b.out_sign, a.out_scale, a._neg_out_zero)
             x = x + capi.quantlinear_float_input(ctx, oq, a.out_bias, E)
@@ -208,7 +223,7 @@ class PackedViT:
         codes = capi.layernorm_quantize_pack(x, b.ln1[0], b.ln1[1], self.eps, [b.q.requant(), b.k.requant(), b.v.requant()],
                                              status=status)[0]
         Q, K, V = (capi.quantlinear(lin.xq(c), lin.wq(), lin.m.bias, rows, lin.K, lin.O) for lin, c in zip((b.q, b.k, b.v), codes))
-        ctx = _attention(Q, K, V, N, L, H)
+        ctx = _attention(Q, K, V, N, L, H, attention)
         a = b.attn
         oq = capi.qparam(a.out_weight, b.out_bits, b.out_sign, a.out_scale, a._neg_out_zero)
         x = capi.quantlinear_float_input_residual(ctx, oq, a.out_bias, E, x, out=x)

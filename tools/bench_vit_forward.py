@@ -7,8 +7,9 @@ alternating, with device events, at each batch size; print one JSON line.
                   the patch embedding as a GEMM on the matrix cores, no host synchronisation (check=False).
 
 The HBM bytes reported are ALGORITHMIC (the byte model below, per token row outside the attention core and the GEMM
-operands both routes share), not counters.  usage: python tools/bench_vit_forward.py [--batches 64 256] [--steps 10]
-[--warmup 2]"""
+operands both routes share), not counters.  --attention torch engine also times both routes with the engine's attention
+core (keys fused_engine_ms, layers_engine_ms, ...); the default, torch, keeps the output as it was.
+usage: python tools/bench_vit_forward.py [--batches 64 256] [--steps 10] [--warmup 2] [--attention torch [engine]]"""
 import argparse
 import json
 import os
@@ -34,6 +35,7 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[64, 256])
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--attention", nargs="+", choices=["torch", "engine"], default=["torch"])
     args = ap.parse_args()
     import torch
     from quantize_amd.packed_vit import CONFIGS, PackedViT, calibrated_state_dict
@@ -45,22 +47,27 @@ def main():
     for N in args.batches:
         g = torch.Generator(device="cpu").manual_seed(N)
         x = torch.randn(N, 3, 224, 224, generator=g).to(dev)
-        times = {"fused": [], "layers": []}
+        runs = [(route, att) for att in args.attention for route in ("fused", "layers")]
+        times = {r: [] for r in runs}
         with torch.no_grad():
             for i in range(args.warmup + args.steps):
-                for route in ("fused", "layers"):
+                for route, att in runs:
                     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     a.record()
-                    model(x, route, check=False) if route == "fused" else model(x, route)
+                    model(x, route, check=False, attention=att) if route == "fused" else model(x, route, attention=att)
                     b.record()
                     torch.cuda.synchronize()
                     if i >= args.warmup:
-                        times[route].append(a.elapsed_time(b))
+                        times[(route, att)].append(a.elapsed_time(b))
         lay, fus = byte_model(N)
-        med = {r: sorted(t)[len(t) // 2] for r, t in times.items()}
-        res["batches"][str(N)] = {"fused_ms": med["fused"], "layers_ms": med["layers"],
-                                  "fused_img_s": N / med["fused"] * 1e3, "layers_img_s": N / med["layers"] * 1e3,
-                                  "byte_model_layers_GB": lay / 1e9, "byte_model_fused_GB": fus / 1e9}
+        out = {}
+        for (route, att), t in times.items():
+            med = sorted(t)[len(t) // 2]
+            sfx = "" if att == "torch" else "_" + att
+            out["%s%s_ms" % (route, sfx)] = med
+            out["%s%s_img_s" % (route, sfx)] = N / med * 1e3
+        out.update({"byte_model_layers_GB": lay / 1e9, "byte_model_fused_GB": fus / 1e9})
+        res["batches"][str(N)] = out
         del x
         torch.cuda.empty_cache()
     print(json.dumps(res))
