@@ -286,11 +286,11 @@ int qe_quantlinear_float_input(const float *x, const qe_qparam *w, const float *
 /* 0 = order-preserving fp32 kernel, 1 = int8 MFMA GEMM (8-bit x 8-bit operands, K % 64 == 0, 16-byte aligned streams). */
 int qe_quantlinear_path(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O);
 
-/* The kernel qe_quantlinear and its fused forms (qe_quantlinear_requant, qe_quantlinear_residual) run a problem on, honouring
- * QE_LIN8 and QE_LIN_NJ as the launcher does: 0 = order-preserving fp32 kernel, 1 = 64-deep int8 MFMA kernel on 128 x 128
- * tiles, 2 = the same on 128 x 256 tiles, 3 = 128-deep 8-wave kernel on 320 x 256 tiles, 4 = 128-deep 4-wave kernel on
- * 160 x 256 tiles.  dst_aligned: the epilogue's destination (out, codes; out and residual) is 16-byte aligned -- the
- * re-quantising form's fused path requires it.  Host-only: no device work. */
+/* The kernel qe_quantlinear and its fused forms (qe_quantlinear_requant, qe_quantlinear_residual) run a problem on, from the
+ * one plan that every linear query and launch reads (QE_LIN8 and QE_LIN_NJ included): 0 = order-preserving fp32 kernel,
+ * 1 = 64-deep int8 MFMA kernel on 128 x 128 tiles, 2 = the same on 128 x 256 tiles, 3 = 128-deep 8-wave kernel on 320 x 256
+ * tiles, 4 = 128-deep 4-wave kernel on 160 x 256 tiles.  dst_aligned: the epilogue's destination (out, codes; out and
+ * residual) is 16-byte aligned -- the re-quantising form's fused path requires it.  Host-only: no device work. */
 int qe_quantlinear_form(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O, int32_t dst_aligned);
 
 /* quantlinear_float_input: 0 = order-preserving fp32 kernel (bit-identical to the reference's fused chain), 1 = bf16 MFMA

@@ -961,197 +961,129 @@ __global__ __launch_bounds__(256, 2) void linear_f32_mfma_kernel(const LinArgs a
     }
 }
 
-static bool linf_mfma_eligible(const float *x, const qe_qparam *w, int64_t B, int K, int O)
-{
-    if (const char *e = env_get("QE_LIN_F32_MFMA")) { if (atoi(e) == 0) return false; }
-    return w->n_bits == 8 && (K % LF_K) == 0 && K >= LF_K && B > 0 && O > 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-           (reinterpret_cast<uintptr_t>(w->data) & 15) == 0;
-}
-
-static int check_lin_q(const qe_qparam *q, int64_t n_expected)
-{
-    if (q == nullptr || q->data == nullptr || q->scale == nullptr || q->zero == nullptr) return QE_ERR_ARG;
-    if (!(q->n_bits > 0 && q->n_bits <= 8)) return QE_ERR_NBITS;
-    if (q->n_param != 1 && q->n_param != n_expected) return QE_ERR_ARG;
-    return QE_OK;
-}
-
-static bool lin_mfma_eligible(const qe_qparam *x, const qe_qparam *w, int64_t B, int K, int O)
-{
-    // K < 2^17: int32 accumulation of products up to 2^14 cannot overflow (deeper reductions take the fp32 kernel, as the reference's fp32 sum does)
-    return x->n_bits == 8 && w->n_bits == 8 && (K % LK) == 0 && K >= LK && K < (1 << 17) && B > 0 && O > 0 &&
-           (reinterpret_cast<uintptr_t>(x->data) & 15) == 0 && (reinterpret_cast<uintptr_t>(w->data) & 15) == 0;
-}
-
-}  // namespace qe
-
-namespace qe {
-// The int8 MFMA kernel of a lin_mfma_eligible problem, one choice for every epilogue (qe_quantlinear_form numbers them; 0 is
-// the order-preserving fp32 kernel).  dst_aligned: the epilogue's destination (out, or codes) is 16-byte aligned.
-enum { LIN_FORM_NJ2 = 1, LIN_FORM_NJ4 = 2, LIN_FORM_W8 = 3, LIN_FORM_W4 = 4 };
-static int lin_mfma_form(int64_t B, int K, int O, bool dst_aligned)
-{
-    // tile width: 256 columns unless that leaves the chip under-filled; QE_LIN_NJ=2|4 overrides (tuning), big tiles included
-    if (const char *e = env_get("QE_LIN_NJ")) return atoi(e) == 2 ? LIN_FORM_NJ2 : LIN_FORM_NJ4;
-    int nj = 4;
-    if (((B + LM - 1) / LM) * ((O + 255) / 256) < kNumCU) nj = 2;   // under-filled chip (the ViT head: 8 workgroups): twice as many, half as wide (17.8 -> 11.5 us)
-    // 128-deep stages: 320 x 256 tiles (one 8-wave workgroup per CU) when the reduction is deep, 160 x 256 tiles (two 4-wave
-    // workgroups per CU) when the layer is bound by its stores (K <= 1024) -- either when the problem fills the chip with
-    // them (O % 256 == 0: whole column tiles).  QE_LIN8=0: never, 1: the 8-wave form, 2: the 4-wave form
-    int big = 0;
-    if ((K % L8_K) == 0 && (O % L8_TN) == 0 && dst_aligned && B * (int64_t)K < (1ll << 32) &&
-        (int64_t)O * K < (1ll << 32) && O < (1 << 28)) {
-        // thresholds from tools/bench_linear.py at 256 / 64 / 16 images (profiles/r03zz_lin_small_batches.txt): the big tiles
-        // still win at 12,608 rows (120 / 237 tiles), the 64-deep kernel's smaller tiles at 3,152 rows unless O is wide
-        if (K > 1024 && (B / 320) * (O / L8_TN) >= kNumCU / 3) big = 1;
-        else if (K <= 1024 && (B / 160) * (O / L8_TN) >= kNumCU / 2) big = 2;
-        if (const char *e = env_get("QE_LIN8")) big = atoi(e);
-        if (big < 0 || big > 2) big = 0;
-    }
-    if (big == 1) return LIN_FORM_W8;
-    if (big == 2) return LIN_FORM_W4;
-    return nj == 4 ? LIN_FORM_NJ4 : LIN_FORM_NJ2;
-}
-
-template <int EPI>
-static int launch_lin_mfma(const LinArgs &a, bool dst_aligned, hipStream_t s)
-{
-    const int64_t B = a.B;
-    const int O = a.O;
-    const int form = lin_mfma_form(B, a.K, O, dst_aligned);
-    if (form == LIN_FORM_W8 || form == LIN_FORM_W4) {
-        static const bool raised8 =
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_mfma8_kernel<2, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L8Geom<2>::LDS) == hipSuccess &&
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_mfma8_kernel<1, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L8Geom<1>::LDS) == hipSuccess;
-        (void)raised8;
-        const int tm = form == LIN_FORM_W8 ? 320 : 160;
-        const int64_t blocks8 = ((B + tm - 1) / tm) * (O / L8_TN);
-        if (blocks8 > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
-        if (form == LIN_FORM_W8) hipLaunchKernelGGL((linear_mfma8_kernel<2, EPI>), dim3((unsigned)blocks8), dim3(512), L8Geom<2>::LDS, s, a);
-        else                     hipLaunchKernelGGL((linear_mfma8_kernel<1, EPI>), dim3((unsigned)blocks8), dim3(256), L8Geom<1>::LDS, s, a);
-    } else {
-        const int ln = form == LIN_FORM_NJ4 ? 256 : 128;
-        const int64_t blocks = ((B + LM - 1) / LM) * ((O + ln - 1) / ln);
-        if (blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
-        // more than 64 KB of dynamic LDS needs the attribute once
-        static const bool raised =
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_mfma_kernel<4, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lin_lds_bytes<4>()) == hipSuccess &&
-            hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_mfma_kernel<2, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lin_lds_bytes<2>()) == hipSuccess;
-        (void)raised;
-        if (form == LIN_FORM_NJ4) hipLaunchKernelGGL((linear_mfma_kernel<4, EPI>), dim3((unsigned)blocks), dim3(256), lin_lds_bytes<4>(), s, a);
-        else                      hipLaunchKernelGGL((linear_mfma_kernel<2, EPI>), dim3((unsigned)blocks), dim3(256), lin_lds_bytes<2>(), s, a);
-    }
-    QE_LAUNCH_CHECK();
-    return QE_OK;
-}
-}  // namespace qe
-
-extern "C" int qe_quantlinear_path(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O)
-{
-    if (x == nullptr || w == nullptr) return 0;
-    return qe::lin_mfma_eligible(x, w, B, K, O) ? 1 : 0;
-}
-
-extern "C" int qe_quantlinear_form(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O, int32_t dst_aligned)
-{
-    if (x == nullptr || w == nullptr || !qe::lin_mfma_eligible(x, w, B, K, O)) return 0;
-    return qe::lin_mfma_form(B, K, O, dst_aligned != 0);
-}
-
-extern "C" int qe_quantlinear(const qe_qparam *x, const qe_qparam *w, const float *bias,
-                              int64_t B, int32_t K, int32_t O, float *out, qe_stream_t stream)
-{
-    using namespace qe;
-    if (B < 0 || K < 0 || O < 0) return QE_ERR_ARG;
-    int rc;
-    if ((rc = check_lin_q(x, B)) != QE_OK) return rc;
-    if ((rc = check_lin_q(w, O)) != QE_OK) return rc;
-    if (out == nullptr && B * O > 0) return QE_ERR_ARG;
-    if (B == 0 || O == 0) return QE_OK;
-    LinArgs a = {};
-    a.x = static_cast<const uint8_t *>(x->data); a.xf = nullptr; a.w = static_cast<const uint8_t *>(w->data);
-    a.x_scale = x->scale; a.x_zero = x->zero; a.w_scale = w->scale; a.w_zero = w->zero; a.bias = bias;
-    a.x_bits = x->n_bits; a.x_sign = x->sign; a.x_per_tensor = x->n_param == 1;
-    a.w_bits = w->n_bits; a.w_sign = w->sign; a.w_per_tensor = w->n_param == 1;
-    a.B = B; a.K = K; a.O = O; a.out = out; a.dbg = g_mfma_dbg;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (lin_mfma_eligible(x, w, B, K, O)) {
-        a.res = nullptr; a.codes = nullptr; a.status = nullptr;
-        return launch_lin_mfma<LIN_F32>(a, (reinterpret_cast<uintptr_t>(out) & 15) == 0, s);
-    } else {
-        const int64_t blocks = ((B + 31) / 32) * ((O + 31) / 32);
-        if (blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
-        hipLaunchKernelGGL(linear_generic_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, a);
-    }
-    QE_LAUNCH_CHECK();
-    return QE_OK;
-}
-
-namespace qe {
-template <int EPI>
-static int launch_linf_mfma(const LinArgs &a, hipStream_t s)
-{
-    const int64_t blocks_m = ((a.B + LF_T - 1) / LF_T) * ((a.O + LF_T - 1) / LF_T);
-    if (blocks_m > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
-    static const bool raised_f = hipFuncSetAttribute(reinterpret_cast<const void *>(&linear_f32_mfma_kernel<EPI>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)linf_lds_bytes()) == hipSuccess;
-    (void)raised_f;
-    hipLaunchKernelGGL(linear_f32_mfma_kernel<EPI>, dim3((unsigned)blocks_m), dim3(256), linf_lds_bytes(), s, a);
-    QE_LAUNCH_CHECK();
-    return QE_OK;
-}
-}  // namespace qe
-
-extern "C" int qe_quantlinear_float_input(const float *x, const qe_qparam *w, const float *bias,
-                                          int64_t B, int32_t K, int32_t O, float *out, qe_stream_t stream)
-{
-    using namespace qe;
-    if (B < 0 || K < 0 || O < 0) return QE_ERR_ARG;
-    int rc;
-    if ((rc = check_lin_q(w, O)) != QE_OK) return rc;
-    if ((x == nullptr && B * K > 0) || (out == nullptr && B * O > 0)) return QE_ERR_ARG;
-    if (B == 0 || O == 0) return QE_OK;
-    LinArgs a = {};
-    a.x = nullptr; a.xf = x; a.w = static_cast<const uint8_t *>(w->data);
-    a.x_scale = nullptr; a.x_zero = nullptr; a.w_scale = w->scale; a.w_zero = w->zero; a.bias = bias;
-    a.x_bits = 0; a.x_sign = 0; a.x_per_tensor = 1;
-    a.w_bits = w->n_bits; a.w_sign = w->sign; a.w_per_tensor = w->n_param == 1;
-    a.B = B; a.K = K; a.O = O; a.out = out; a.dbg = nullptr;
-    if (linf_mfma_eligible(x, w, B, K, O)) {
-        a.res = nullptr; a.codes = nullptr; a.status = nullptr;
-        return launch_linf_mfma<LIN_F32>(a, static_cast<hipStream_t>(stream));
-    }
-    const int64_t blocks = ((B + 31) / 32) * ((O + 31) / 32);
-    if (blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(linear_generic_kernel<true>, dim3((unsigned)blocks), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), a);
-    QE_LAUNCH_CHECK();
-    return QE_OK;
-}
-
-extern "C" int qe_quantlinear_float_input_path(const float *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O)
-{
-    if (w == nullptr) return 0;
-    return qe::linf_mfma_eligible(x, w, B, K, O) ? 1 : 0;
-}
-
 // ---------------------------------------------------------------------------------------------
-// Fused ViT forms (include/quant_engine.h): the consumer's codes of y / gelu(y), and y + residual.  Path 1 is an MFMA
-// kernel with the epilogue compiled in; path 0 runs qe_quantlinear(_float_input) into the workspace and then the
-// elementwise pass whose arithmetic the epilogue shares.  QE_LIN_EPI=0 sends every call to path 0.
+// Host side.  plan_linear decides everything about one linear problem once: the kernel, whether the requested epilogue
+// runs inside it or as a second pass over the workspace, the grid, block, dynamic LDS and workspace.  It is the only reader
+// of the QE_LIN_* knobs and makes no HIP call (the CPU suite asks the queries on a machine without a GPU).  The C-ABI
+// queries answer from the plan; every entry point validates its arguments, plans and runs the plan.
 // ---------------------------------------------------------------------------------------------
-namespace qe {
-static bool lin_epi_enabled()
+
+// The kernel of a plan.  0..4 are qe_quantlinear_form's numbers (0: the order-preserving fp32 kernel, 1..4: the int8 MFMA
+// kernels, one choice for every epilogue); the fp32-activation problems run one of the last two.
+enum { LIN_FORM_CHAIN = 0, LIN_FORM_NJ2 = 1, LIN_FORM_NJ4 = 2, LIN_FORM_W8 = 3, LIN_FORM_W4 = 4,
+       LIN_FORM_CHAIN_F = 5, LIN_FORM_BF16 = 6 };   // linear_generic_kernel<true>, linear_f32_mfma_kernel
+
+// What is asked.  The plan reads the operands' alignment only; a query leaves the pointers it does not know null, which
+// reads as aligned.
+struct LinRequest {
+    bool f32_x = false;                 // fp32 activations at xf, else the packed activations x
+    const qe_qparam *x = nullptr, *w = nullptr;
+    const float *xf = nullptr;
+    int64_t B = 0;
+    int K = 0, O = 0;
+    int epi = LIN_F32;                  // LIN_CODES*: the consumer's quantiser rq, codes and status; LIN_RES: out = y + res
+    const qe_requant *rq = nullptr;
+    const float *bias = nullptr, *res = nullptr;
+    float *out = nullptr; uint8_t *codes = nullptr; int32_t *status = nullptr;
+};
+
+struct LinPlan {
+    int form = LIN_FORM_CHAIN;
+    bool two_pass = false;   // the kernel writes y into the workspace, then the elementwise pass applies the epilogue
+    int epi = LIN_F32;       // the epilogue compiled into the kernel that runs
+    int64_t blocks = 0; int threads = 256; size_t lds = 0;   // grid, block, dynamic LDS
+    size_t ws = 0;           // workspace bytes: y of a two-pass form
+};
+
+static LinRequest lin_req(const qe_qparam *x, const qe_qparam *w, int64_t B, int K, int O, int epi = LIN_F32,
+                          const qe_requant *rq = nullptr, const uint8_t *codes = nullptr)
 {
-    if (const char *e = env_get("QE_LIN_EPI")) return atoi(e) != 0;
-    return true;
+    LinRequest r;
+    r.x = x; r.w = w; r.B = B; r.K = K; r.O = O; r.epi = epi; r.rq = rq; r.codes = const_cast<uint8_t *>(codes);
+    return r;
 }
 
-static bool rq_fusable(const qe_requant *rq)
+static LinRequest linf_req(const float *x, const qe_qparam *w, int64_t B, int K, int O, int epi = LIN_F32)
 {
-    return rq != nullptr && rq->n_bits == 8 && rq->n_param == 1 && rq->scale != nullptr && rq->zero != nullptr;
+    LinRequest r = lin_req(nullptr, w, B, K, O, epi);
+    r.f32_x = true; r.xf = x;
+    return r;
+}
+
+// The checks every entry point starts with, in this order
+static int check_lin(const LinRequest &r)
+{
+    const auto check_q = [](const qe_qparam *q, int64_t n_expected) {
+        if (q == nullptr || q->data == nullptr || q->scale == nullptr || q->zero == nullptr) return QE_ERR_ARG;
+        if (!(q->n_bits > 0 && q->n_bits <= 8)) return QE_ERR_NBITS;
+        return q->n_param != 1 && q->n_param != n_expected ? QE_ERR_ARG : QE_OK;
+    };
+    if (r.B < 0 || r.K < 0 || r.O < 0) return QE_ERR_ARG;
+    if (int rc = r.f32_x ? QE_OK : check_q(r.x, r.B)) return rc;
+    return check_q(r.w, r.O);
+}
+
+static LinPlan plan_linear(const LinRequest &r)
+{
+    const auto ad = [](const void *p) { return reinterpret_cast<uintptr_t>(p); };
+    const auto al16 = [](uintptr_t a) { return (a & 15) == 0; };
+    const int64_t B = r.B;
+    const int K = r.K, O = r.O;
+    const char *e;
+    bool mfma = r.w != nullptr && r.w->n_bits == 8 && B > 0 && O > 0 && al16(ad(r.w->data));
+    if (r.f32_x)   // bf16 MFMA on the split activations, whole 32-deep stages; QE_LIN_F32_MFMA=0: the fp32 chain kernel only
+        mfma = mfma && (K % LF_K) == 0 && K >= LF_K && al16(ad(r.xf)) && !((e = env_get("QE_LIN_F32_MFMA")) && atoi(e) == 0);
+    else           // K < 2^17: int32 accumulation of products up to 2^14 cannot overflow (deeper reductions take the fp32
+                   // kernel, as the reference's fp32 sum does)
+        mfma = mfma && r.x != nullptr && r.x->n_bits == 8 && (K % LK) == 0 && K >= LK && K < (1 << 17) && al16(ad(r.x->data));
+
+    // Fused epilogues run in the MFMA kernels: the residual add, or 8-bit per-tensor codes at a 16-byte aligned address.
+    // Anything else, and every call under QE_LIN_EPI=0, takes two passes: the linear into the workspace, then the
+    // elementwise pass whose arithmetic the epilogue shares.
+    LinPlan p;
+    const qe_requant *rq = r.rq;
+    const bool rq_ok = rq != nullptr && rq->n_bits == 8 && rq->n_param == 1 && rq->scale != nullptr && rq->zero != nullptr &&
+                       al16(ad(r.codes));
+    p.two_pass = r.epi != LIN_F32 && !(mfma && !((e = env_get("QE_LIN_EPI")) && atoi(e) == 0) && (r.epi == LIN_RES || rq_ok));
+    p.epi = p.two_pass ? LIN_F32 : r.epi;
+    p.ws = p.two_pass && B > 0 && O > 0 ? (size_t)B * (size_t)O * sizeof(float) : 0;
+
+    if (r.f32_x) {
+        p.form = mfma ? LIN_FORM_BF16 : LIN_FORM_CHAIN_F;
+    } else if (mfma) {
+        // The epilogue's destination: y in the 16-byte aligned workspace, out, or out and res.  The codes count as aligned,
+        // as qe_quantlinear_requant has always passed them (its fused form requires aligned codes in any case).
+        const bool dst_aligned = p.two_pass || r.epi == LIN_CODES || r.epi == LIN_CODES_GELU || al16(ad(r.out) | ad(r.res));
+        // tile width: 256 columns unless that leaves the chip under-filled (the ViT head: 8 workgroups): twice as many,
+        // half as wide (17.8 -> 11.5 us)
+        p.form = ((B + LM - 1) / LM) * ((O + 255) / 256) < kNumCU ? LIN_FORM_NJ2 : LIN_FORM_NJ4;
+        // 128-deep stages: 320 x 256 tiles (one 8-wave workgroup per CU) when the reduction is deep, 160 x 256 tiles (two 4-wave
+        // workgroups per CU) when the layer is bound by its stores (K <= 1024) -- either when the problem fills the chip with
+        // them (O % 256 == 0: whole column tiles).  QE_LIN8=0: never, 1: the 8-wave form, 2: the 4-wave form
+        int big = 0;
+        if ((K % L8_K) == 0 && (O % L8_TN) == 0 && dst_aligned && B * (int64_t)K < (1ll << 32) &&
+            (int64_t)O * K < (1ll << 32) && O < (1 << 28)) {
+            // thresholds from tools/bench_linear.py at 256 / 64 / 16 images (profiles/r03zz_lin_small_batches.txt): the big
+            // tiles still win at 12,608 rows (120 / 237 tiles), the 64-deep kernel's smaller tiles at 3,152 rows unless O is wide
+            if (K > 1024 && (B / 320) * (O / L8_TN) >= kNumCU / 3) big = 1;
+            else if (K <= 1024 && (B / 160) * (O / L8_TN) >= kNumCU / 2) big = 2;
+            if ((e = env_get("QE_LIN8"))) big = atoi(e);
+            if (big == 1) p.form = LIN_FORM_W8;
+            if (big == 2) p.form = LIN_FORM_W4;
+        }
+        // QE_LIN_NJ=2|4 overrides (tuning), big tiles included
+        if ((e = env_get("QE_LIN_NJ"))) p.form = atoi(e) == 2 ? LIN_FORM_NJ2 : LIN_FORM_NJ4;
+    }
+
+    // rows x columns of a workgroup's tile, threads and dynamic LDS of each kernel (the 128-deep ones only run whole column tiles)
+    static constexpr struct { int tm, tn, threads; size_t lds; } geom[] = {
+        {32, 32, 256, 0}, {LM, 128, 256, lin_lds_bytes<2>()}, {LM, 256, 256, lin_lds_bytes<4>()}, {320, L8_TN, 512, L8Geom<2>::LDS},
+        {160, L8_TN, 256, L8Geom<1>::LDS}, {32, 32, 256, 0}, {LF_T, LF_T, 256, linf_lds_bytes()}};
+    const auto &g = geom[p.form];
+    p.blocks = ((B + g.tm - 1) / g.tm) * ((O + g.tn - 1) / g.tn);
+    p.threads = g.threads;
+    p.lds = g.lds;
+    return p;
 }
 
 static QeRq make_rq(const qe_requant *rq)
@@ -1163,6 +1095,54 @@ static QeRq make_rq(const qe_requant *rq)
     q.lo = rq->sign ? -(float)(1 << (rq->n_bits - 1)) : 0.0f;
     q.hi = rq->sign ? (float)((1 << (rq->n_bits - 1)) - 1) : (float)((1 << rq->n_bits) - 1);
     return q;
+}
+
+// The kernel arguments of a request whose linear writes `out` (r.out, or y in the workspace)
+static LinArgs lin_args(const LinRequest &r, float *out)
+{
+    LinArgs a = {};
+    if (r.f32_x) {
+        a.xf = r.xf; a.x_per_tensor = 1;
+    } else {
+        a.x = static_cast<const uint8_t *>(r.x->data); a.x_scale = r.x->scale; a.x_zero = r.x->zero;
+        a.x_bits = r.x->n_bits; a.x_sign = r.x->sign; a.x_per_tensor = r.x->n_param == 1;
+    }
+    a.w = static_cast<const uint8_t *>(r.w->data); a.w_scale = r.w->scale; a.w_zero = r.w->zero; a.bias = r.bias;
+    a.w_bits = r.w->n_bits; a.w_sign = r.w->sign; a.w_per_tensor = r.w->n_param == 1;
+    a.B = r.B; a.K = r.K; a.O = r.O; a.out = out; a.dbg = g_mfma_dbg;
+    a.res = r.res; a.codes = r.codes; a.status = r.status;
+    if (r.rq != nullptr) a.rq = make_rq(r.rq);
+    return a;
+}
+
+// One template instance; more than 64 KB of dynamic LDS needs the attribute, raised once per instance
+template <auto KERNEL>
+static void launch_instance(const LinPlan &p, const LinArgs &a, hipStream_t s)
+{
+    if (p.lds > 0) {
+        static const bool raised = hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                       (int)p.lds) == hipSuccess;
+        (void)raised;
+    }
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)p.blocks), dim3(p.threads), p.lds, s, a);
+}
+
+template <int EPI>
+static void launch_epi(const LinPlan &p, const LinArgs &a, hipStream_t s)
+{
+    switch (p.form) {
+    case LIN_FORM_NJ2: return launch_instance<&linear_mfma_kernel<2, EPI>>(p, a, s);
+    case LIN_FORM_NJ4: return launch_instance<&linear_mfma_kernel<4, EPI>>(p, a, s);
+    case LIN_FORM_W8: return launch_instance<&linear_mfma8_kernel<2, EPI>>(p, a, s);
+    case LIN_FORM_W4: return launch_instance<&linear_mfma8_kernel<1, EPI>>(p, a, s);
+    }
+    // the bf16 kernel has F32 and RES instances, the order-preserving kernels F32 only (the plan sends the rest to two passes)
+    if constexpr (EPI == LIN_F32 || EPI == LIN_RES)
+        if (p.form == LIN_FORM_BF16) return launch_instance<&linear_f32_mfma_kernel<EPI>>(p, a, s);
+    if constexpr (EPI == LIN_F32) {
+        if (p.form == LIN_FORM_CHAIN) return launch_instance<&linear_generic_kernel<false>>(p, a, s);
+        if (p.form == LIN_FORM_CHAIN_F) return launch_instance<&linear_generic_kernel<true>>(p, a, s);
+    }
 }
 
 // out = y + res, one fp32 add per element (path 0 of the residual forms); out may be res
@@ -1187,29 +1167,90 @@ static int launch_add_residual(const float *y, const float *res, float *out, int
     return QE_OK;
 }
 
+// Plan a validated, non-empty request and run it: one launch, or the linear into the workspace and then the elementwise pass
+static int run_linear(const LinRequest &r, void *workspace, size_t workspace_bytes, qe_stream_t stream)
+{
+    const LinPlan p = plan_linear(r);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (p.two_pass && (workspace == nullptr || workspace_bytes < p.ws || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0))
+        return QE_ERR_WORKSPACE;
+    if (p.blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
+    float *y = p.two_pass ? static_cast<float *>(workspace) : r.out;
+    const LinArgs a = lin_args(r, y);
+    if (p.epi == LIN_CODES) launch_epi<LIN_CODES>(p, a, s);
+    else if (p.epi == LIN_CODES_GELU) launch_epi<LIN_CODES_GELU>(p, a, s);
+    else if (p.epi == LIN_RES) launch_epi<LIN_RES>(p, a, s);
+    else launch_epi<LIN_F32>(p, a, s);
+    QE_LAUNCH_CHECK();
+    if (!p.two_pass) return QE_OK;
+    const int64_t n = r.B * (int64_t)r.O;
+    if (r.epi == LIN_RES) return launch_add_residual(y, r.res, r.out, n, s);
+    // per-channel rq: channel = output feature o, element (b, o) -> (i / 1) % O
+    const qe_requant *rq = r.rq;
+    return qe_quantize_pack_act(y, n, r.epi == LIN_CODES_GELU ? QE_ACT_GELU : QE_ACT_NONE, rq->scale, rq->zero, rq->n_param, 1,
+                                rq->qmin, rq->qmax, rq->n_bits, rq->sign, r.codes, nullptr, r.status, stream);
+}
+
 // residual and out: the same buffer or disjoint
 static bool res_overlap_ok(const float *res, const float *out, int64_t n)
 {
     return res == out || res + n <= out || out + n <= res;
 }
-
-static size_t ws_f32(int64_t B, int O) { return (size_t)B * (size_t)O * sizeof(float); }
 }  // namespace qe
 
+extern "C" int qe_quantlinear_path(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O)
+{
+    return qe::plan_linear(qe::lin_req(x, w, B, K, O)).form != qe::LIN_FORM_CHAIN;
+}
+
+extern "C" int qe_quantlinear_form(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O, int32_t dst_aligned)
+{
+    qe::LinRequest r = qe::lin_req(x, w, B, K, O);
+    r.out = reinterpret_cast<float *>(dst_aligned != 0 ? 0 : 4);   // a stand-in address of that alignment
+    return qe::plan_linear(r).form;
+}
+
+extern "C" int qe_quantlinear(const qe_qparam *x, const qe_qparam *w, const float *bias,
+                              int64_t B, int32_t K, int32_t O, float *out, qe_stream_t stream)
+{
+    using namespace qe;
+    LinRequest r = lin_req(x, w, B, K, O);
+    r.bias = bias; r.out = out;
+    if (int rc = check_lin(r)) return rc;
+    if (out == nullptr && B * O > 0) return QE_ERR_ARG;
+    if (B == 0 || O == 0) return QE_OK;
+    return run_linear(r, nullptr, 0, stream);
+}
+
+extern "C" int qe_quantlinear_float_input(const float *x, const qe_qparam *w, const float *bias,
+                                          int64_t B, int32_t K, int32_t O, float *out, qe_stream_t stream)
+{
+    using namespace qe;
+    LinRequest r = linf_req(x, w, B, K, O);
+    r.bias = bias; r.out = out;
+    if (int rc = check_lin(r)) return rc;
+    if ((x == nullptr && B * K > 0) || (out == nullptr && B * O > 0)) return QE_ERR_ARG;
+    if (B == 0 || O == 0) return QE_OK;
+    return run_linear(r, nullptr, 0, stream);
+}
+
+extern "C" int qe_quantlinear_float_input_path(const float *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O)
+{
+    return qe::plan_linear(qe::linf_req(x, w, B, K, O)).form == qe::LIN_FORM_BF16;
+}
+
+// Fused ViT forms (include/quant_engine.h): the consumer's codes of y / gelu(y), and y + residual.  Path 1 is an MFMA kernel
+// with the epilogue compiled in, path 0 the plan's two passes.
 extern "C" int qe_quantlinear_requant_path(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O,
                                            const qe_requant *rq, const uint8_t *codes)
 {
-    using namespace qe;
-    if (x == nullptr || w == nullptr || rq == nullptr) return 0;
-    return lin_epi_enabled() && lin_mfma_eligible(x, w, B, K, O) && rq_fusable(rq) &&
-           (reinterpret_cast<uintptr_t>(codes) & 15) == 0 ? 1 : 0;
+    return !qe::plan_linear(qe::lin_req(x, w, B, K, O, qe::LIN_CODES, rq, codes)).two_pass;
 }
 
 extern "C" size_t qe_quantlinear_requant_workspace_bytes(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O,
                                                          const qe_requant *rq, const uint8_t *codes)
 {
-    if (B <= 0 || O <= 0) return 0;
-    return qe_quantlinear_requant_path(x, w, B, K, O, rq, codes) ? 0 : qe::ws_f32(B, O);
+    return qe::plan_linear(qe::lin_req(x, w, B, K, O, qe::LIN_CODES, rq, codes)).ws;
 }
 
 extern "C" int qe_quantlinear_requant(const qe_qparam *x, const qe_qparam *w, const float *bias, int64_t B, int32_t K, int32_t O,
@@ -1220,84 +1261,45 @@ extern "C" int qe_quantlinear_requant(const qe_qparam *x, const qe_qparam *w, co
     if (B < 0 || K < 0 || O < 0 || rq == nullptr || (act != QE_ACT_NONE && act != QE_ACT_GELU)) return QE_ERR_ARG;
     if (!(rq->n_bits > 0 && rq->n_bits <= 8)) return QE_ERR_NBITS;
     if (rq->n_param != 1 && rq->n_param != O) return QE_ERR_ARG;
-    int rc;
-    if ((rc = check_lin_q(x, B)) != QE_OK) return rc;
-    if ((rc = check_lin_q(w, O)) != QE_OK) return rc;
+    LinRequest r = lin_req(x, w, B, K, O, act == QE_ACT_GELU ? LIN_CODES_GELU : LIN_CODES, rq, codes);
+    r.bias = bias; r.status = status;
+    if (int rc = check_lin(r)) return rc;
     if (B == 0 || O == 0) return QE_OK;
     if (codes == nullptr) return QE_ERR_ARG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (qe_quantlinear_requant_path(x, w, B, K, O, rq, codes)) {
-        LinArgs a = {};
-        a.x = static_cast<const uint8_t *>(x->data); a.w = static_cast<const uint8_t *>(w->data);
-        a.x_scale = x->scale; a.x_zero = x->zero; a.w_scale = w->scale; a.w_zero = w->zero; a.bias = bias;
-        a.x_bits = x->n_bits; a.x_sign = x->sign; a.x_per_tensor = x->n_param == 1;
-        a.w_bits = w->n_bits; a.w_sign = w->sign; a.w_per_tensor = w->n_param == 1;
-        a.B = B; a.K = K; a.O = O; a.out = nullptr; a.dbg = nullptr;
-        a.codes = codes; a.status = status; a.rq = make_rq(rq);
-        return act == QE_ACT_GELU ? launch_lin_mfma<LIN_CODES_GELU>(a, true, s) : launch_lin_mfma<LIN_CODES>(a, true, s);
-    }
-    if (workspace == nullptr || workspace_bytes < ws_f32(B, O) || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0)
-        return QE_ERR_WORKSPACE;
-    float *y = static_cast<float *>(workspace);
-    if ((rc = qe_quantlinear(x, w, bias, B, K, O, y, stream)) != QE_OK) return rc;
-    // per-channel rq: channel = output feature o, element (b, o) -> (i / 1) % O
-    return qe_quantize_pack_act(y, B * (int64_t)O, act, rq->scale, rq->zero, rq->n_param, 1, rq->qmin, rq->qmax, rq->n_bits,
-                                rq->sign, codes, nullptr, status, stream);
+    return run_linear(r, workspace, workspace_bytes, stream);
 }
 
 extern "C" int qe_quantlinear_residual_path(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O)
 {
-    using namespace qe;
-    if (x == nullptr || w == nullptr) return 0;
-    return lin_epi_enabled() && lin_mfma_eligible(x, w, B, K, O) ? 1 : 0;
+    return !qe::plan_linear(qe::lin_req(x, w, B, K, O, qe::LIN_RES)).two_pass;
 }
 
 extern "C" size_t qe_quantlinear_residual_workspace_bytes(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O)
 {
-    if (B <= 0 || O <= 0) return 0;
-    return qe_quantlinear_residual_path(x, w, B, K, O) ? 0 : qe::ws_f32(B, O);
+    return qe::plan_linear(qe::lin_req(x, w, B, K, O, qe::LIN_RES)).ws;
 }
 
 extern "C" int qe_quantlinear_residual(const qe_qparam *x, const qe_qparam *w, const float *bias, int64_t B, int32_t K, int32_t O,
                                        const float *residual, float *out, void *workspace, size_t workspace_bytes, qe_stream_t stream)
 {
     using namespace qe;
-    if (B < 0 || K < 0 || O < 0) return QE_ERR_ARG;
-    int rc;
-    if ((rc = check_lin_q(x, B)) != QE_OK) return rc;
-    if ((rc = check_lin_q(w, O)) != QE_OK) return rc;
+    LinRequest r = lin_req(x, w, B, K, O, LIN_RES);
+    r.bias = bias; r.res = residual; r.out = out;
+    if (int rc = check_lin(r)) return rc;
     if (B == 0 || O == 0) return QE_OK;
     if (residual == nullptr || out == nullptr || !res_overlap_ok(residual, out, B * (int64_t)O)) return QE_ERR_ARG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (qe_quantlinear_residual_path(x, w, B, K, O)) {
-        LinArgs a = {};
-        a.x = static_cast<const uint8_t *>(x->data); a.w = static_cast<const uint8_t *>(w->data);
-        a.x_scale = x->scale; a.x_zero = x->zero; a.w_scale = w->scale; a.w_zero = w->zero; a.bias = bias;
-        a.x_bits = x->n_bits; a.x_sign = x->sign; a.x_per_tensor = x->n_param == 1;
-        a.w_bits = w->n_bits; a.w_sign = w->sign; a.w_per_tensor = w->n_param == 1;
-        a.B = B; a.K = K; a.O = O; a.out = out; a.dbg = nullptr; a.res = residual;
-        const bool al = ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(residual)) & 15) == 0;
-        return launch_lin_mfma<LIN_RES>(a, al, s);
-    }
-    if (workspace == nullptr || workspace_bytes < ws_f32(B, O) || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0)
-        return QE_ERR_WORKSPACE;
-    float *y = static_cast<float *>(workspace);
-    if ((rc = qe_quantlinear(x, w, bias, B, K, O, y, stream)) != QE_OK) return rc;
-    return launch_add_residual(y, residual, out, B * (int64_t)O, s);
+    return run_linear(r, workspace, workspace_bytes, stream);
 }
 
 extern "C" int qe_quantlinear_float_input_residual_path(const float *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O)
 {
-    using namespace qe;
-    if (w == nullptr) return 0;
-    return lin_epi_enabled() && linf_mfma_eligible(x, w, B, K, O) ? 1 : 0;
+    return !qe::plan_linear(qe::linf_req(x, w, B, K, O, qe::LIN_RES)).two_pass;
 }
 
 extern "C" size_t qe_quantlinear_float_input_residual_workspace_bytes(const float *x, const qe_qparam *w, int64_t B, int32_t K,
                                                                      int32_t O)
 {
-    if (B <= 0 || O <= 0) return 0;
-    return qe_quantlinear_float_input_residual_path(x, w, B, K, O) ? 0 : qe::ws_f32(B, O);
+    return qe::plan_linear(qe::linf_req(x, w, B, K, O, qe::LIN_RES)).ws;
 }
 
 extern "C" int qe_quantlinear_float_input_residual(const float *x, const qe_qparam *w, const float *bias, int64_t B, int32_t K,
@@ -1305,24 +1307,10 @@ extern "C" int qe_quantlinear_float_input_residual(const float *x, const qe_qpar
                                                    size_t workspace_bytes, qe_stream_t stream)
 {
     using namespace qe;
-    if (B < 0 || K < 0 || O < 0) return QE_ERR_ARG;
-    int rc;
-    if ((rc = check_lin_q(w, O)) != QE_OK) return rc;
+    LinRequest r = linf_req(x, w, B, K, O, LIN_RES);
+    r.bias = bias; r.res = residual; r.out = out;
+    if (int rc = check_lin(r)) return rc;
     if (B == 0 || O == 0) return QE_OK;
     if (x == nullptr || residual == nullptr || out == nullptr || !res_overlap_ok(residual, out, B * (int64_t)O)) return QE_ERR_ARG;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (qe_quantlinear_float_input_residual_path(x, w, B, K, O)) {
-        LinArgs a = {};
-        a.x = nullptr; a.xf = x; a.w = static_cast<const uint8_t *>(w->data);
-        a.w_scale = w->scale; a.w_zero = w->zero; a.bias = bias;
-        a.x_bits = 0; a.x_sign = 0; a.x_per_tensor = 1;
-        a.w_bits = w->n_bits; a.w_sign = w->sign; a.w_per_tensor = w->n_param == 1;
-        a.B = B; a.K = K; a.O = O; a.out = out; a.dbg = nullptr; a.res = residual;
-        return launch_linf_mfma<LIN_RES>(a, s);
-    }
-    if (workspace == nullptr || workspace_bytes < ws_f32(B, O) || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0)
-        return QE_ERR_WORKSPACE;
-    float *y = static_cast<float *>(workspace);
-    if ((rc = qe_quantlinear_float_input(x, w, bias, B, K, O, y, stream)) != QE_OK) return rc;
-    return launch_add_residual(y, residual, out, B * (int64_t)O, s);
+    return run_linear(r, workspace, workspace_bytes, stream);
 }

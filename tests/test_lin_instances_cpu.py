@@ -71,3 +71,38 @@ def test_query_follows_the_knobs():
     assert capi.linear_form(q, q, 12608, 3000, 768) == 0                       # K % 64 != 0
     bits4 = capi.QeQParam(ALIGNED, 4, 1, ALIGNED, ALIGNED, 1)
     assert capi.linear_form(bits4, q, 64, 256, 256) == 0
+
+
+def test_queries_answer_from_one_plan():
+    """The path and workspace queries of the fused forms agree with qe_quantlinear_form / _float_input_path on every row:
+    path 1 exactly when the row runs an MFMA kernel (and needs no workspace), two passes through B*O floats otherwise."""
+    L = capi.lib()
+    q = _q()
+    rq = lambda bits, n_param: capi.QeRequant(ALIGNED, ALIGNED, n_param, -128.0, 127.0, bits, 1)
+    rq_path = lambda B, K, O, r, codes=ALIGNED: int(L.qe_quantlinear_requant_path(q, q, B, K, O, r, codes))
+    for B, K, O, env, form, note in li.ROWS:
+        row = ((B, K, O), note, env)
+        with li.knobs(env, capi.reload_env):
+            fused = int(form != 0)
+            assert capi.linear_path(q, q, B, K, O) == fused, row
+            assert rq_path(B, K, O, rq(8, 1)) == fused, row
+            assert capi.linear_residual_path(q, q, B, K, O) == fused, row
+            ws = 0 if fused else B * O * 4
+            assert int(L.qe_quantlinear_requant_workspace_bytes(q, q, B, K, O, rq(8, 1), ALIGNED)) == ws, row
+            assert int(L.qe_quantlinear_residual_workspace_bytes(q, q, B, K, O)) == ws, row
+            # what the fused epilogue cannot store: per-channel or sub-8-bit codes, codes off a 16-byte boundary
+            assert rq_path(B, K, O, rq(8, O)) == (fused if O == 1 else 0), row
+            assert rq_path(B, K, O, rq(4, 1)) == 0, row
+            assert rq_path(B, K, O, rq(8, 1), ALIGNED + 4) == 0, row
+            assert int(L.qe_quantlinear_requant_workspace_bytes(q, q, B, K, O, rq(4, 1), ALIGNED)) == B * O * 4, row
+        with li.knobs(dict(env or {}, QE_LIN_EPI="0"), capi.reload_env):
+            assert rq_path(B, K, O, rq(8, 1)) == 0 and capi.linear_residual_path(q, q, B, K, O) == 0, row
+            assert int(L.qe_quantlinear_residual_workspace_bytes(q, q, B, K, O)) == B * O * 4, row
+    for B, K, O, env, form, note in li.F_ROWS:
+        row = ((B, K, O), note, env)
+        with li.knobs(env, capi.reload_env):
+            assert int(L.qe_quantlinear_float_input_residual_path(ALIGNED, q, B, K, O)) == form, row
+            ws = int(L.qe_quantlinear_float_input_residual_workspace_bytes(ALIGNED, q, B, K, O))
+            assert ws == (0 if form else B * O * 4), row
+        with li.knobs(dict(env or {}, QE_LIN_EPI="0"), capi.reload_env):
+            assert int(L.qe_quantlinear_float_input_residual_path(ALIGNED, q, B, K, O)) == 0, row
