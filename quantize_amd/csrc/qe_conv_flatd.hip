@@ -8,6 +8,8 @@
 // What differs is how the operands reach LDS.  The register-staged flat kernel keeps ONE stage of loads in flight per
 // workgroup (its staging registers), and a layer with a long K loop and small planes (1024->256 @14x14, 2048->512 @7x7)
 // pays one memory round trip per stage: 2.8 TB/s and 1.0 TB/s in the ResNet-50 stack, bound by neither HBM nor MFMA.
+// This kernel serves the 7x7 planes (2048->512 and 512->2048 in the last stage); on larger planes it tied or lost against the
+// register-staged kernels.
 // Here both operands of a 64-channel stage are written into a ring of 3 LDS buffers by global_load_lds_dwordx4 (no
 // staging registers, nothing to transpose or convert on the way), two stages ahead of the MFMAs, with one raw
 // s_barrier and a counted vmcnt per stage (a __syncthreads() would drain the DMA queue).  The u ^ 0x80 recode moves to
@@ -15,13 +17,10 @@
 //
 // LDS image of the activations = what ds_read_b64_tr_b8 wants: rows = channels, 16-pixel groups at 8-byte aligned
 // addresses, row stride an odd multiple of 32 B (conflict-free).  LDS-DMA writes lane-linear 16-byte slots, but the
-// GLOBAL address is per lane, so slot (channel c, j) simply fetches plane bytes [16 j, 16 j + 16) of channel c:
-//   WIDE  (planes >= 160 pixels; tile = 32 NT pixels of one plane, NT = 5 | 7): row stride 32 NT bytes, 2 NT slots per row;
-//         a 14x14 plane (196 B) is one 224-pixel tile whose rows start 4-byte aligned in global memory -- LDS-DMA takes
-//         that (tools/probe_dma_align.hip) -- and whose last 28 bytes per row are the next channel's (never stored);
-//   SMALL (planes <= 64 pixels: 7x7; tile = 4 whole images x 2 column tiles): 64-byte rows [image][channel][64], byte-aligned
-//         sources, slot position XOR 2 for channels with bit 2 set so that the 8 rows x 2 pixel groups of a transposed read
-//         cover all 64 banks once.
+// GLOBAL address is per lane, so slot (channel c, j) simply fetches plane bytes [16 j, 16 j + 16) of channel c.  A tile is
+// 4 whole images x 2 column tiles: 64-byte rows [image][channel][64], byte-aligned sources (LDS-DMA takes any source
+// alignment: tools/probe_dma_align.hip), slot position XOR 2 for channels with bit 2 set so that the 8 rows x 2 pixel
+// groups of a transposed read cover all 64 banks once.
 // The only bytes such slots could read past the tensor are those behind the LAST plane of the LAST image when the plane
 // size is not a multiple of 16: pure-garbage slots fetch the tensor's last 16 bytes instead, and the one slot that is
 // partly valid is left out of the DMA (lane masked off) and written by its thread from a register.
@@ -39,7 +38,7 @@ struct FlatdArgs {
     int x_sign, w_sign, w_per_tensor;
     float *out;                // [N][OC][P] fp32
     int N, IC, OC, P;
-    int tiles_per_image;       // WIDE: pixel tiles per plane; SMALL: unused
+    int tiles_per_image;       // unused (a tile is 4 whole images)
     int n_pix_tiles, n_oc_tiles, chunk;
     // fused re-quantisation (7x7 planes, RQ instances): the 8-bit code of the consumer's quantiser instead of fp32, fields as in MfmaArgs
     uint8_t *rq_out;
@@ -54,16 +53,16 @@ constexpr int FD_RING_DEFAULT = 3;      // slots of the ring (RING - 1 stages in
 // workgroup per CU: the activations of a pixel tile cross the CU's memory path once per 256 output channels instead of
 // once per 128 -- the bytes that bound these layers)
 
-template <int NT, bool SMALL, int RING = FD_RING_DEFAULT, int WAVES = 4> struct FdGeom {
+template <int RING = FD_RING_DEFAULT, int WAVES = 4> struct FdGeom {
     static constexpr int MT = 32 * WAVES;
     static constexpr int THREADS = 64 * WAVES;
     static constexpr int FD_WBYTES = MT * FD_CK;
-    static constexpr int RS = SMALL ? 64 : 32 * NT;                  // LDS bytes per channel row (WIDE: NT odd)
-    static constexpr int XBYTES = SMALL ? 4 * FD_CK * 64 : FD_CK * RS;
+    static constexpr int NT = 8;                                     // column tiles: 4 images x 2
+    static constexpr int XBYTES = 4 * FD_CK * 64;                    // [image][channel][64 bytes]
     static constexpr int STAGE = XBYTES + FD_WBYTES;
     static constexpr int XINSTR = XBYTES / 1024;                     // wave-level DMA instructions per stage
     static constexpr int NTP = 32 * NT;
-    static constexpr int PATCH = SMALL ? WAVES * 32 * 49 * 4 : WAVES * 32 * 36 * 4;
+    static constexpr int PATCH = WAVES * 32 * 49 * 4;
     static constexpr int RING_BYTES = RING * STAGE > PATCH ? RING * STAGE : PATCH;
     static constexpr int LDS = RING_BYTES + WAVES * NTP * 4 /* S_x, one copy per wave */;
 };
@@ -78,49 +77,8 @@ template <int NT, bool SMALL, int RING = FD_RING_DEFAULT, int WAVES = 4> struct 
 // output register right behind the statement that declares it, i.e. before the data has arrived (seen: v_mov of
 // not-yet-loaded patch rows -> garbage in rows 16-31 of every tile).
 // ---------------------------------------------------------------------------------------------
-// all fragment reads of one 32-channel chunk of a WIDE stage: weight fragment + NT x (8 + 8 channels) transposed reads
-template <int NT> __device__ __forceinline__ void fd_reads_wide(uint32_t tr_addr, uint32_t wf_addr, v4i &wf, v2i (&lo)[NT], v2i (&hi)[NT]);
-template <> __device__ __forceinline__ void fd_reads_wide<5>(uint32_t tr_addr, uint32_t wf_addr, v4i &wf, v2i (&lo)[5], v2i (&hi)[5])
-{
-    asm volatile(
-        "ds_read_b128 %0, %12\n\t"
-        "ds_read_b64_tr_b8 %1, %11 offset:0\n\t"
-        "ds_read_b64_tr_b8 %6, %11 offset:1280\n\t"
-        "ds_read_b64_tr_b8 %2, %11 offset:32\n\t"
-        "ds_read_b64_tr_b8 %7, %11 offset:1312\n\t"
-        "ds_read_b64_tr_b8 %3, %11 offset:64\n\t"
-        "ds_read_b64_tr_b8 %8, %11 offset:1344\n\t"
-        "ds_read_b64_tr_b8 %4, %11 offset:96\n\t"
-        "ds_read_b64_tr_b8 %9, %11 offset:1376\n\t"
-        "ds_read_b64_tr_b8 %5, %11 offset:128\n\t"
-        "ds_read_b64_tr_b8 %10, %11 offset:1408\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&v"(wf), "=&v"(lo[0]), "=&v"(lo[1]), "=&v"(lo[2]), "=&v"(lo[3]), "=&v"(lo[4]), "=&v"(hi[0]), "=&v"(hi[1]), "=&v"(hi[2]), "=&v"(hi[3]), "=&v"(hi[4])
-        : "v"(tr_addr), "v"(wf_addr));
-}
-template <> __device__ __forceinline__ void fd_reads_wide<7>(uint32_t tr_addr, uint32_t wf_addr, v4i &wf, v2i (&lo)[7], v2i (&hi)[7])
-{
-    asm volatile(
-        "ds_read_b128 %0, %16\n\t"
-        "ds_read_b64_tr_b8 %1, %15 offset:0\n\t"
-        "ds_read_b64_tr_b8 %8, %15 offset:1792\n\t"
-        "ds_read_b64_tr_b8 %2, %15 offset:32\n\t"
-        "ds_read_b64_tr_b8 %9, %15 offset:1824\n\t"
-        "ds_read_b64_tr_b8 %3, %15 offset:64\n\t"
-        "ds_read_b64_tr_b8 %10, %15 offset:1856\n\t"
-        "ds_read_b64_tr_b8 %4, %15 offset:96\n\t"
-        "ds_read_b64_tr_b8 %11, %15 offset:1888\n\t"
-        "ds_read_b64_tr_b8 %5, %15 offset:128\n\t"
-        "ds_read_b64_tr_b8 %12, %15 offset:1920\n\t"
-        "ds_read_b64_tr_b8 %6, %15 offset:160\n\t"
-        "ds_read_b64_tr_b8 %13, %15 offset:1952\n\t"
-        "ds_read_b64_tr_b8 %7, %15 offset:192\n\t"
-        "ds_read_b64_tr_b8 %14, %15 offset:1984\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&v"(wf), "=&v"(lo[0]), "=&v"(lo[1]), "=&v"(lo[2]), "=&v"(lo[3]), "=&v"(lo[4]), "=&v"(lo[5]), "=&v"(lo[6]), "=&v"(hi[0]), "=&v"(hi[1]), "=&v"(hi[2]), "=&v"(hi[3]), "=&v"(hi[4]), "=&v"(hi[5]), "=&v"(hi[6])
-        : "v"(tr_addr), "v"(wf_addr));
-}
-// SMALL: tile T = image T / 2 (4096 bytes apart), column tile T % 2 (slot position differs by XOR 2: second base)
+// all fragment reads of one 32-channel chunk: weight fragment + 8 x (8 + 8 channels) transposed reads.  Column tile T =
+// image T / 2 (4096 bytes apart), column tile T % 2 (slot position differs by XOR 2: second base)
 __device__ __forceinline__ void fd_reads_small(uint32_t tr_addr0, uint32_t tr_addr1, uint32_t wf_addr, v4i &wf, v2i (&lo)[8], v2i (&hi)[8])
 {
     asm volatile(
@@ -171,15 +129,13 @@ __device__ __forceinline__ void fd_wait_vmcnt(int n)   // n wave-uniform, 0..31
 #undef QE_VMW
 }
 
-template <int NT, bool SMALL, int FD_RING, int WAVES, bool RQ = false>
+template <int FD_RING, int WAVES, bool RQ = false>
 __global__ __launch_bounds__(64 * WAVES, 2) void conv_flatd_kernel(const FlatdArgs a)
 {
-    using G = FdGeom<NT, SMALL, FD_RING, WAVES>;
+    using G = FdGeom<FD_RING, WAVES>;
     constexpr int AHEAD = FD_RING - 1;
     constexpr int FD_MT = G::MT, THREADS = G::THREADS;
-    constexpr int RS = G::RS;
-    static_assert(SMALL || (NT & 1) == 1, "WIDE tiles need an odd tile count (row stride = odd multiple of 32 B)");
-    static_assert(!SMALL || NT == 8, "SMALL tiles are 4 images x 2 column tiles");
+    constexpr int NT = G::NT;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -198,9 +154,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_flatd_kernel(const FlatdAr
         pt = (c * 8 + (bid & 7)) * a.chunk + (j - c * a.chunk);
     }
     if (pt >= a.n_pix_tiles) return;
-    int n0, p0;
-    if constexpr (SMALL) { n0 = pt * 4; p0 = 0; }
-    else { n0 = pt / a.tiles_per_image; p0 = (pt - n0 * a.tiles_per_image) * G::NTP; }
+    const int n0 = pt * 4;
 
     // ---- epilogue constants of this lane's output channel ------------------------------------------------------
     const int oc = ot * FD_MT + wave * 32 + col;
@@ -222,28 +176,18 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_flatd_kernel(const FlatdAr
 #pragma unroll
     for (int i = 0; i < PXW; ++i) {
         const int e = 64 * (wave + WAVES * i) + lane;
-        int64_t src;
-        bool last_row, pad = false;
-        int j;
-        if constexpr (SMALL) {
-            const int img = e >> 8, c = (e >> 2) & 63, jj = e & 3;
-            j = jj ^ (2 * ((c >> 2) & 1));
-            const int n = n0 + img < a.N ? n0 + img : a.N - 1;
-            src = ((int64_t)n * a.IC + c) * P + 16 * j;
-            last_row = (n0 + img == a.N - 1) && c == FD_CK - 1;
-            pad = n0 + img >= a.N;                         // an image past the batch in its last tile: computed, never stored
-        } else {
-            const int c = e / (RS / 16);
-            j = e - c * (RS / 16);
-            src = ((int64_t)n0 * a.IC + c) * P + p0 + 16 * j;
-            last_row = (n0 == a.N - 1) && c == FD_CK - 1;
-        }
+        const int img = e >> 8, c = (e >> 2) & 63;
+        const int j = (e & 3) ^ (2 * ((c >> 2) & 1));
+        const int n = n0 + img < a.N ? n0 + img : a.N - 1;
+        int64_t src = ((int64_t)n * a.IC + c) * P + 16 * j;
+        const bool last_row = (n0 + img == a.N - 1) && c == FD_CK - 1;
+        const bool pad = n0 + img >= a.N;                  // an image past the batch in its last tile: computed, never stored
         // stage s adds s * 64 planes: only the last stage of the last image can run past the tensor
         const int64_t lim = x_last16 - (int64_t)(a.IC - FD_CK) * P;
         if (pad) {
             src = lim;      // its slots would repeat the last image's, whose last plane runs up to 15 bytes past the tensor
         } else if (last_row && src > lim) {
-            const int pos = (SMALL ? 0 : p0) + 16 * j;            // first plane byte this slot should hold
+            const int pos = 16 * j;                                // first plane byte this slot should hold
             if (pos < P && e < G::XBYTES / 16) {
                 // partly valid (P - pos = 4 or 1 bytes): in the last stage this lane is masked out of the DMA (see
                 // issue()) and stores the valid bytes itself; in every earlier stage the slot is an ordinary in-bounds
@@ -309,17 +253,11 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_flatd_kernel(const FlatdAr
     // fragment addressing (32-bit LDS byte addresses for the hand-written transposed reads)
     const int i16 = lane & 15;
     const uint32_t smem_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t *)smem;
-    uint32_t tr_b0, tr_b1;
-    if constexpr (SMALL) {
-        // row (16 h + i16/2) of [image][channel][64]; logical slot 2 tt + (lane>>4)&1 sits at position slot ^ 2 for rows 4-7
-        const int sm_sl = ((lane >> 4) & 1) ^ (2 * (i16 >> 3));
-        const uint32_t rowb = (uint32_t)((16 * h + (i16 >> 1)) * 64 + 8 * (i16 & 1));
-        tr_b0 = rowb + 16u * (uint32_t)sm_sl;
-        tr_b1 = rowb + 16u * (uint32_t)(sm_sl ^ 2);
-    } else {
-        tr_b0 = (uint32_t)((16 * h + (i16 >> 1)) * RS + 16 * ((lane >> 4) & 1) + 8 * (i16 & 1));
-        tr_b1 = tr_b0;
-    }
+    // row (16 h + i16/2) of [image][channel][64]; logical slot 2 tt + (lane>>4)&1 sits at position slot ^ 2 for rows 4-7
+    const int sm_sl = ((lane >> 4) & 1) ^ (2 * (i16 >> 3));
+    const uint32_t rowb = (uint32_t)((16 * h + (i16 >> 1)) * 64 + 8 * (i16 & 1));
+    const uint32_t tr_b0 = rowb + 16u * (uint32_t)sm_sl;
+    const uint32_t tr_b1 = rowb + 16u * (uint32_t)(sm_sl ^ 2);
     const int wf_base = G::XBYTES + (wave * 32 + col) * FD_CK;
     const int wswz = (col >> 2) & 3;
 
@@ -334,7 +272,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_flatd_kernel(const FlatdAr
                 __builtin_amdgcn_s_waitcnt(0x0f70);
                 if (fix_lds >= 0) {
                     uint8_t *dst = smem + (s % FD_RING) * G::STAGE + fix_lds;
-                    if constexpr (SMALL) *dst = (uint8_t)fix_val; else *reinterpret_cast<uint32_t *>(dst) = fix_val;
+                    *dst = (uint8_t)fix_val;
                     __builtin_amdgcn_s_waitcnt(0xc07f);
                 }
             }
@@ -347,8 +285,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_flatd_kernel(const FlatdAr
                 v2i lo[NT], hi[NT];
                 v4i wf;
                 const uint32_t wfa = xb + (uint32_t)(wf_base + 16 * ((2 * k + h) ^ wswz));
-                if constexpr (SMALL) fd_reads_small(xb + tr_b0 + k * 32 * 64, xb + tr_b1 + k * 32 * 64, wfa, wf, lo, hi);
-                else fd_reads_wide<NT>(xb + tr_b0 + k * 32 * RS, wfa, wf, lo, hi);
+                fd_reads_small(xb + tr_b0 + k * 32 * 64, xb + tr_b1 + k * 32 * 64, wfa, wf, lo, hi);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     wf[j] ^= (int)0x80808080;         // u - 128: signed q, or unsigned q - 128
@@ -383,51 +320,10 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_flatd_kernel(const FlatdAr
         }
     }
     __syncthreads();          // every wave is done with the ring (it becomes the store patches)
-    if constexpr (!SMALL) {
-        // each wave turns its 32 oc x 32 px tiles through a private patch: one global_store_dwordx4 = 8 rows x 128 B
-        const int NTv = min(G::NTP, P - p0);
-        float *out_w = a.out + ((int64_t)n0 * a.OC + ot * FD_MT + wave * 32) * P + p0;
-        float *patch = reinterpret_cast<float *>(smem) + wave * (32 * 36);
-        const int rrow = lane >> 3, rq = lane & 7;
-        const uint32_t voff = (uint32_t)rrow * (uint32_t)P + 4u * (uint32_t)rq;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int q0 = t * 32;
-#pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {
-                float v[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float f = (float)acc[t][4 * gq + j] + cst;
-                    if (need_sx) f = fmaf(-zwp, (float)sxp[q0 + 8 * gq + 4 * h + j], f);
-                    v[j] = fmaf(alpha, f, bia);
-                }
-                *reinterpret_cast<float4 *>(patch + col * 36 + 8 * gq + 4 * h) = make_float4(v[0], v[1], v[2], v[3]);
-            }
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            const bool px_ok = q0 + 4 * rq < NTv;
-            if (q0 + 32 <= NTv && ot * FD_MT + wave * 32 + 32 <= a.OC) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float4 o4 = *reinterpret_cast<const float4 *>(patch + (8 * i + rrow) * 36 + 4 * rq);
-                    *reinterpret_cast<float4 *>(out_w + (int64_t)(8 * i) * P + q0 + voff) = o4;
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int row = 8 * i + rrow;
-                    const float4 o4 = *reinterpret_cast<const float4 *>(patch + row * 36 + 4 * rq);
-                    if (px_ok && ot * FD_MT + wave * 32 + row < a.OC)
-                        *reinterpret_cast<float4 *>(out_w + (int64_t)(8 * i) * P + q0 + voff) = o4;
-                }
-            }
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-        }
-    } else if constexpr (RQ) {
+    if constexpr (RQ) {
         // fused re-quantisation: a wave's 32 channels x 49 codes of one image are ONE contiguous 1,568-byte run of the output
         // (16-byte aligned: oc0 % 32 == 0 and OC % 32 == 0, host) -- laid out in the patch as in memory, copied flat.  The
         // fp32 value is computed exactly as below, then quantised as quantize_pack would (rq_value / rq_fast2).
-        static_assert(SMALL, "re-quantising instances exist for the 7x7 form only");
         uint8_t *bp = smem + wave * (32 * 49 * 4);
         const int oc0 = ot * FD_MT + wave * 32;
         RqConst rqc = rq_setup(a);
@@ -509,13 +405,11 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_flatd_kernel(const FlatdAr
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-// p.route == Flatd: tile variant p.fd_var, 8-wave workgroups when p.fd_w8; rq != nullptr: the re-quantising SMALL instances
+// p.route == Flatd: 8-wave workgroups when p.fd_w8; rq != nullptr: the re-quantising instances
 int launch_flatd(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, float *out, hipStream_t s,
                  const RequantHost *rq)
 {
     const qe_conv_shape *sh = &p.run;
-    const int var = p.fd_var;
-    const bool w8 = p.fd_w8;
     FlatdArgs a;
     a.rq_out = nullptr; a.rq_scale = nullptr; a.rq_zero = nullptr; a.rq_status = nullptr;
     a.rq_qmin = a.rq_qmax = a.rq_lo = a.rq_hi = 0.0f; a.rq_offset = 0;
@@ -536,29 +430,18 @@ int launch_flatd(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, cons
     const int64_t blocks = p.blocks;
     // ring depth 3 = two stages in flight, two workgroups per CU.  A 6-slot ring (one workgroup per CU, five stages in flight)
     // was 25-60 % slower on every layer (profiles/r02i_flatd_ring.txt): the K loop is not bound by prefetch depth.
-#define QE_FD_LAUNCH(NTV, SM, RG, WV)                                                                                      \
+#define QE_FD_LAUNCH(WV, RQ)                                                                                                \
     do {                                                                                                                    \
-        static const bool ok_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_flatd_kernel<NTV, SM, RG, WV>),   \
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, FdGeom<NTV, SM, RG, WV>::LDS) == hipSuccess; \
+        static const bool ok_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_flatd_kernel<3, WV, RQ>),          \
+                                                    hipFuncAttributeMaxDynamicSharedMemorySize, FdGeom<3, WV>::LDS) == hipSuccess; \
         (void)ok_;                                                                                                          \
-        constexpr size_t lds_ = FdGeom<NTV, SM, RG, WV>::LDS;                                                               \
-        hipLaunchKernelGGL((conv_flatd_kernel<NTV, SM, RG, WV>), dim3((unsigned)blocks), dim3(64 * WV), lds_, s, a);        \
+        constexpr size_t lds_ = FdGeom<3, WV>::LDS;                                                                         \
+        hipLaunchKernelGGL((conv_flatd_kernel<3, WV, RQ>), dim3((unsigned)blocks), dim3(64 * WV), lds_, s, a);              \
     } while (0)
     if (rq != nullptr) {
-#define QE_FD_LAUNCH_RQ(WV)                                                                                                 \
-    do {                                                                                                                    \
-        static const bool ok_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_flatd_kernel<8, true, 3, WV, true>), \
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, FdGeom<8, true, 3, WV>::LDS) == hipSuccess; \
-        (void)ok_;                                                                                                          \
-        constexpr size_t lds_ = FdGeom<8, true, 3, WV>::LDS;                                                                \
-        hipLaunchKernelGGL((conv_flatd_kernel<8, true, 3, WV, true>), dim3((unsigned)blocks), dim3(64 * WV), lds_, s, a);   \
-    } while (0)
-        if (w8) QE_FD_LAUNCH_RQ(8); else QE_FD_LAUNCH_RQ(4);
-#undef QE_FD_LAUNCH_RQ
-    } else if (w8) {
-        if (var == 8) QE_FD_LAUNCH(8, true, 3, 8); else if (var == 5) QE_FD_LAUNCH(5, false, 3, 8); else QE_FD_LAUNCH(7, false, 3, 8);
+        if (p.fd_w8) QE_FD_LAUNCH(8, true); else QE_FD_LAUNCH(4, true);
     } else {
-        if (var == 8) QE_FD_LAUNCH(8, true, 3, 4); else if (var == 5) QE_FD_LAUNCH(5, false, 3, 4); else QE_FD_LAUNCH(7, false, 3, 4);
+        if (p.fd_w8) QE_FD_LAUNCH(8, false); else QE_FD_LAUNCH(4, false);
     }
 #undef QE_FD_LAUNCH
     QE_LAUNCH_CHECK();

@@ -457,7 +457,7 @@ int launch_conv_mfma(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, 
     a.TH = m.TH; a.tiles_h = p.tiles_h; a.n_pix_tiles = p.n_pix_tiles; a.n_oc_tiles = p.n_oc_tiles;
     a.IHT = m.IHT; a.IWP = m.IWP; a.ROWMUL = m.ROWMUL; a.COLMUL = m.COLMUL; a.ni = m.ni;
     a.GI = m.GI;
-    a.PADW = m.ws ? m.PADW : rs->padding;
+    a.PADW = rs->padding;
     a.chunk = p.chunk;
     a.ptab_off = p.ptab_off; a.ctab = p.ctab ? 1 : 0;
     a.n_top = p.n_top; a.n_bot = p.n_bot; a.n_lft = p.n_lft; a.n_rgt = p.n_rgt;
@@ -476,14 +476,13 @@ int launch_conv_mfma(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, 
     const unsigned blocks = (unsigned)p.blocks;
     if (m.flatg) launch_mfma_flatg(a, m.NS, m.wraw, blocks, p.lds, s);
     else if (m.flat && m.x4) launch_mfma_flat_x4(a, m.niw, m.NS, blocks, p.lds, s);
-    else if (m.flat && p.wide8) launch_mfma_flat(a, p.deep8 ? 4 : 3, m.niw, m.NS, true, false, blocks, p.lds, s);
     else if (m.flat) launch_mfma_flat(a, m.cfg, m.niw, m.NS, m.wraw, m.s2, blocks, p.lds, s);
     else if (m.sm2) launch_mfma_sm2(a, m.cfg == 0 ? 2 : 1, p.split, blocks, p.lds, s);
     else if (m.ws) launch_mfma_ws(a, m.niw, p.split, blocks, p.lds, s);
-    else if (m.smallic) launch_mfma_smallic(a, m.cfg, m.niw, blocks, p.lds, s);
-    else if (m.cfg == 0) launch_mfma_cfg0(a, m.niw, m.NS, m.KK, xr.n_bits == 8, blocks, p.lds, s);
-    else if (m.cfg == 1) launch_mfma_cfg1(a, m.niw, m.NS, m.KK, xr.n_bits == 8, blocks, p.lds, s);
-    else launch_mfma_cfg2(a, m.niw, m.NS, m.KK, xr.n_bits == 8, blocks, p.lds, s);
+    else if (m.smallic) launch_mfma_smallic(a, m.cfg, blocks, p.lds, s);
+    else if (m.cfg == 0) launch_mfma_cfg0(a, m.niw, m.NS, m.KK, blocks, p.lds, s);
+    else if (m.cfg == 1) launch_mfma_cfg1(a, m.niw, m.NS, m.KK, blocks, p.lds, s);
+    else launch_mfma_cfg2(a, m.niw, m.NS, m.KK, blocks, p.lds, s);
     QE_LAUNCH_CHECK();
     return QE_OK;
 }

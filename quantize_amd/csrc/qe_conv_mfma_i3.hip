@@ -5,7 +5,7 @@ namespace qe {
 
 #define QE_SMALLIC(WM, WN, NIW)                                                                                          \
     do {                                                                                                                \
-        constexpr bool patch_ = mfma_has_patch(MfKind::Stem, WM, NIW, 0, true, 1);                                       \
+        constexpr bool patch_ = mfma_has_patch(MfKind::Stem, WM, NIW, 0, 1);                                             \
         if (a.rq_out != nullptr && a.rq_patch)                                                                          \
             hipLaunchKernelGGL((conv_mfma_smallic_kernel<WM, WN, NIW, true, patch_>), dim3(blocks), dim3(MF_THREADS), lds, s, a);  \
         else if (a.rq_out != nullptr)                                                                                   \
@@ -14,15 +14,11 @@ namespace qe {
             hipLaunchKernelGGL((conv_mfma_smallic_kernel<WM, WN, NIW, false>), dim3(blocks), dim3(MF_THREADS), lds, s, a); \
     } while (0)
 
-void launch_mfma_smallic(const MfmaArgs &a, int cfg, int niw, unsigned blocks, size_t lds, hipStream_t s)
+void launch_mfma_smallic(const MfmaArgs &a, int cfg, unsigned blocks, size_t lds, hipStream_t s)
 {
-    if (cfg == 1 && niw == 7) {   // 64 output channels, 448-pixel tiles (4 rows of the 112-wide stem output)
-        QE_SMALLIC(2, 2, 7);
-        return;
-    }
     switch (cfg) {
         case 0: QE_SMALLIC(4, 1, 7); break;
-        case 1: QE_SMALLIC(2, 2, 4); break;
+        case 1: QE_SMALLIC(2, 2, 7); break;   // 64 output channels, 448-pixel tiles (4 rows of the 112-wide stem output)
         default: QE_SMALLIC(1, 4, 2); break;
     }
 }

@@ -15,7 +15,7 @@ static void launch_rq(const MfmaArgs &a, unsigned blocks, size_t lds, hipStream_
 template <int WMS, int SPLIT>
 static void launch_one(const MfmaArgs &a, unsigned blocks, size_t lds, hipStream_t s)
 {
-    if (a.rq_out != nullptr && a.rq_patch) launch_rq<WMS, SPLIT, true, mfma_has_patch(MfKind::Sm2, 2 * WMS, 4, 9, true, 1)>(a, blocks, lds, s);
+    if (a.rq_out != nullptr && a.rq_patch) launch_rq<WMS, SPLIT, true, mfma_has_patch(MfKind::Sm2, 2 * WMS, 4, 9, 1)>(a, blocks, lds, s);
     else if (a.rq_out != nullptr) launch_rq<WMS, SPLIT, true>(a, blocks, lds, s);
     else launch_rq<WMS, SPLIT, false>(a, blocks, lds, s);
 }

@@ -32,7 +32,7 @@ struct MfmaArgs {
     int TH, tiles_h, n_pix_tiles, n_oc_tiles;
     int IHT, IWP, ROWMUL, COLMUL, ni;
     int GI;                    // whole images per pixel tile (> 1 only for small feature maps, TH == OH)
-    int PADW;                  // ws kernel: left padding columns materialised in LDS (0 = unpadded rows + lane masks)
+    int PADW;                  // ws kernel: left padding columns materialised in LDS (= pad)
     int chunk;                 // consecutive pixel tiles one XCD takes before the next XCD's run starts
     int ptab_off;              // byte offset in dynamic LDS of the epilogue's S_w table (0 = none)
     int ctab;                  // 1: that table is the per-(border class, channel) correction (stage_ctab), 0: prefix rows
@@ -155,38 +155,6 @@ __host__ __device__ __forceinline__ int code_bias(int n_bits, int sign)
 __host__ __device__ __forceinline__ float zero_shift(int n_bits, int sign)
 {
     return (!sign && n_bits == 8) ? 128.0f : 0.0f;
-}
-
-// 4 consecutive elements of one channel row -> 4 int8 operands in a dword.  `xi` is the image's
-// base (wave-uniform), `off` the element offset inside the image (32-bit), `lim` the last offset at
-// which a full-width read still ends inside the stream.  Branch-free: the read is clamped and the
-// value shifted back; whatever is shifted in belongs to elements that are never valid pixels.
-template <bool X8>
-__device__ __forceinline__ uint32_t fetch_quad(const uint8_t *__restrict__ xi, int off, int64_t lim,
-                                               int n_bits, int cb)
-{
-    if constexpr (X8) {
-        const int offc = off < (int)lim ? off : (int)lim;
-        uint32_t v;
-        __builtin_memcpy(&v, xi + (uint32_t)offc, 4);  // one (possibly unaligned) global_load_dword
-        v >>= 8 * (off - offc);
-        return v ^ 0x80808080u;                        // u - 128 per byte: signed q, or unsigned q - 128
-    } else {
-        const int64_t bit = (int64_t)off * n_bits;
-        const int64_t byte = bit >> 3;
-        const int64_t bc = byte < lim ? byte : lim;
-        uint64_t v;
-        __builtin_memcpy(&v, xi + bc, 8);
-        v >>= ((int)(bit & 7) + 8 * (int)(byte - bc));
-        const uint32_t mask = (1u << n_bits) - 1u;
-        uint32_t r = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t c = (uint32_t)(v >> (j * n_bits)) & mask;
-            r |= ((c - (uint32_t)cb) & 0xffu) << (8 * j);
-        }
-        return r;
-    }
 }
 
 #ifdef QE_STAMP
@@ -571,11 +539,11 @@ __device__ __forceinline__ bool decode_tile(const MfmaArgs &a, int &pt, int &ot,
 
 // ---------------------------------------------------------------------------------------------
 // Main kernel.  WM x WN waves over (oc strips, pixel column tiles); NIW column tiles per wave;
-// KKT = taps known at compile time (1, 9 = 3x3) or 0 for a runtime tap loop; X8 = 8-bit
-// activations; NS = 32-channel chunks per stage: the 256 threads split into NS groups that each
+// KKT = taps known at compile time (1, 9 = 3x3) or 0 for a runtime tap loop; 8-bit activations;
+// NS = 32-channel chunks per stage: the 256 threads split into NS groups that each
 // fetch one chunk of the stage, so one HBM round trip feeds NS*KK MFMA steps per column tile.
 // ---------------------------------------------------------------------------------------------
-template <int WM, int WN, int NIW, int KKT, bool X8, int NS, bool RQ = false, bool PATCH = false>
+template <int WM, int WN, int NIW, int KKT, int NS, bool RQ = false, bool PATCH = false>
 __global__ __launch_bounds__(MF_THREADS, 2) void conv_mfma_kernel(const MfmaArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -646,15 +614,13 @@ __global__ __launch_bounds__(MF_THREADS, 2) void conv_mfma_kernel(const MfmaArgs
             u_lds[j] = pok ? (gi * a.IHT + l) * a.IWP + clc : -1;
         }
     }
-    const uint8_t *xi = a.x + (X8 ? img_off : 0);   // 8-bit: image base (uniform); sub-8-bit: stream base
-    const int64_t lim8 = a.x_bytes - 8;             // sub-8-bit: last byte offset of a full 8-byte read
+    const uint8_t *xi = a.x + img_off;              // image base (uniform)
 
     // ---- weight fragment pointer: lane (row col, half h) reads Wt[tap][2c + h][oc][16 B] ------
     const int8_t *a_base = a.wt + (int64_t)(ot * MT + wm * 32) * 16;  // wave-uniform
     const uint32_t a_voff = (uint32_t)(h * a.OCP + col) * 16u;           // per lane
     const int64_t grp_stride = (int64_t)a.OCP * 16;            // one 16-channel group
     const int64_t tap_stride = (int64_t)a.NG * grp_stride;     // one tap
-    const int cbx = code_bias(a.x_bits, a.x_sign);
 
     v16i acc[NIW];
 #pragma unroll
@@ -684,25 +650,10 @@ __global__ __launch_bounds__(MF_THREADS, 2) void conv_mfma_kernel(const MfmaArgs
             for (int i = 0; i < 16; ++i) {
                 const int ic = c * 32 + u * 16 + i;                 // wave-uniform
                 const int icc = ic < a.IC ? ic : a.IC - 1;
-                if constexpr (X8) {
-                    const uint8_t *plane = xi + (int64_t)icc * HW;  // scalar base
-                    uint32_t v;
-                    __builtin_memcpy(&v, plane + (uint32_t)u_off, 4);  // one (possibly unaligned) global_load_dword
-                    d[u][i] = v;
-                } else {
-                    const int64_t bit = (img_off + (int64_t)icc * HW + u_off) * a.x_bits + (u_sh / 8) * a.x_bits;
-                    const int64_t byte = bit >> 3;
-                    const int64_t bc = byte < lim8 ? byte : lim8;
-                    uint64_t v;
-                    __builtin_memcpy(&v, xi + bc, 8);
-                    v >>= ((int)(bit & 7) + 8 * (int)(byte - bc));
-                    const uint32_t mask = (1u << a.x_bits) - 1u;
-                    uint32_t r = 0;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        r |= ((((uint32_t)(v >> (j * a.x_bits)) & mask) - (uint32_t)cbx) & 0xffu) << (8 * j);
-                    d[u][i] = r;
-                }
+                const uint8_t *plane = xi + (int64_t)icc * HW;  // scalar base
+                uint32_t v;
+                __builtin_memcpy(&v, plane + (uint32_t)u_off, 4);  // one (possibly unaligned) global_load_dword
+                d[u][i] = v;
             }
         }
     };
@@ -710,10 +661,8 @@ __global__ __launch_bounds__(MF_THREADS, 2) void conv_mfma_kernel(const MfmaArgs
         const int c = s * NS + sub;
 #pragma unroll
         for (int u = 0; u < MF_UNITS; ++u) {
-            if constexpr (X8) {
 #pragma unroll
-                for (int i = 0; i < 16; ++i) d[u][i] = (d[u][i] >> u_sh) ^ 0x80808080u;  // u - 128: signed q / unsigned q - 128
-            }
+            for (int i = 0; i < 16; ++i) d[u][i] = (d[u][i] >> u_sh) ^ 0x80808080u;  // u - 128: signed q / unsigned q - 128
             uint32_t o[4][4];
 #pragma unroll
             for (int m = 0; m < 4; ++m)
@@ -1123,7 +1072,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void conv_mfma_sm2_kernel(const Mfma
 // independent accumulators can keep the matrix pipe issuing back to back).
 // Tile, LDS image layout, operand roles and epilogue are the halo kernel's (4x1 consumer waves).
 // ---------------------------------------------------------------------------------------------
-template <int NIW, int KKT, int SPLIT, bool NOPAD, bool RQ = false>
+template <int NIW, int KKT, int SPLIT, bool RQ = false>
 __global__ __launch_bounds__(2 * MF_THREADS, 2) void conv_mfma_ws_kernel(const MfmaArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -1143,13 +1092,8 @@ __global__ __launch_bounds__(2 * MF_THREADS, 2) void conv_mfma_ws_kernel(const M
     if (!decode_tile(a, pt, ot, g, th)) return;
     const int NT = g.NT;
     const int ih0 = g.oh0 * a.stride - a.pad;
-    // Unpadded-row mode (PADW = 0, stride-1 layers): LDS rows hold exactly W pixels, so the 32 lanes of a
-    // column tile read 32 CONSECUTIVE 16-byte slots for every tap (conflict-free; with W+2-pixel rows the
-    // 14- and 7-pixel-wide maps hit every bank twice and the kernel is LDS-bound).  A tap that would fall
-    // left/right of the image then reads a neighbouring row's pixel: those lanes zero their fragment.
-    const int GD = NOPAD ? a.pad : 0;        // guard slots in front of / behind each group image (PADW = 0 iff NOPAD)
     const int ISZ = a.IHT * a.IWP;
-    const int GSZ = a.GI * ISZ + 2 * GD;     // slots of one 16-channel group
+    const int GSZ = a.GI * ISZ;              // slots of one 16-channel group
     const int BUF = 2 * GSZ;                 // uint4 slots of one buffer (2 groups = 32 channels)
     const int trash = 2 * BUF + lane;
     int *sxp = reinterpret_cast<int *>(Xs + 2 * BUF + MF_TRASH);
@@ -1200,7 +1144,7 @@ __global__ __launch_bounds__(2 * MF_THREADS, 2) void conv_mfma_ws_kernel(const M
                 const int cl = iw + a.PADW;
                 const int clc = cl / a.COLMUL;
                 const bool pok = ok && iw < a.W && (clc * a.COLMUL == cl) && clc < a.IWP;
-                u_lds[j] = pok ? GD + (gi * a.IHT + l) * a.IWP + clc : -1;
+                u_lds[j] = pok ? (gi * a.IHT + l) * a.IWP + clc : -1;
             }
         }
         const int ch0 = sub * CPT;                 // first channel of this thread's slice inside the chunk
@@ -1311,22 +1255,13 @@ __global__ __launch_bounds__(2 * MF_THREADS, 2) void conv_mfma_ws_kernel(const M
     // ==================================== consumers ==========================================
     const int RS = a.stride / a.ROWMUL, CS = a.stride / a.COLMUL;
     int pixidx[NIW];
-    unsigned km[NIW];        // bit kw set: tap column kw of this lane's pixel is inside the image row
 #pragma unroll
     for (int t = 0; t < NIW; ++t) {
         const int q = t * 32 + col;
         const int gi = (a.GI > 1) ? q / g.OHWt : 0;
         const int rq = q - gi * g.OHWt;
         const int r = rq / a.OW, c = rq - r * a.OW;
-        // origin of the receptive field: LDS column c*CS - GD (the guard slots absorb the -GD of row 0)
         pixidx[t] = h * GSZ + ((q < NT) ? gi * ISZ + (r * RS) * a.IWP + c * CS : 0);
-        unsigned m = 0;
-#pragma unroll
-        for (int kw = 0; kw < KW_T; ++kw) {
-            const int iw = c * a.stride - a.pad + kw;
-            if (!NOPAD || (iw >= 0 && iw < a.W)) m |= 1u << kw;
-        }
-        km[t] = m;
     }
     const int8_t *a_base = a.wt + (int64_t)(ot * MT + cw * 32) * 16;   // wave-uniform
     const uint32_t a_voff = (uint32_t)(h * a.OCP + col) * 16u;
@@ -1365,17 +1300,7 @@ __global__ __launch_bounds__(2 * MF_THREADS, 2) void conv_mfma_ws_kernel(const M
                 for (int t = 0; t < NIW; ++t) bq[nxt][t] = *reinterpret_cast<const v4i *>(&Xs[pixidx[t] + off]);
             }
 #pragma unroll
-            for (int t = 0; t < NIW; ++t) {
-                v4i bf = bq[cur][t];
-                if constexpr (NOPAD && (KW_T == 3)) {
-                    if ((tap % KW_T) != 1) {             // 3x3 / pad 1: the centre column is always inside
-                        const int keep = ((km[t] >> (tap % KW_T)) & 1u) ? -1 : 0;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) bf[k] &= keep;
-                    }
-                }
-                acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(afr[tap], bf, acc[t], 0, 0, 0);
-            }
+            for (int t = 0; t < NIW; ++t) acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(afr[tap], bq[cur][t], acc[t], 0, 0, 0);
             afr[tap] = *reinterpret_cast<const v4i *>(a_n + tap * tap_stride + a_voff);   // next stage's fragment
             if (tap + 1 < KKT) {
 #pragma unroll
@@ -1397,8 +1322,7 @@ __global__ __launch_bounds__(2 * MF_THREADS, 2) void conv_mfma_ws_kernel(const M
         sxs[t] = 0;
         if (need_sx) {
             const int pbase = pixidx[t] - h * GSZ;
-            for (int tap = 0; tap < KKT; ++tap)
-                if ((km[t] >> (tap % KW_T)) & 1u) sxs[t] += sxp[pbase + (tap / KW_T) * a.IWP + (tap % KW_T)];
+            for (int tap = 0; tap < KKT; ++tap) sxs[t] += sxp[pbase + (tap / KW_T) * a.IWP + (tap % KW_T)];
         }
     }
     mfma_epilogue<WM, WN, NIW, RQ>(a, acc, sxs, need_sx, g, ot, cw, 0, col, h, KKT, nullptr, ctab);
@@ -1591,14 +1515,10 @@ typedef int v2i __attribute__((ext_vector_type(2)));
 
 // X4: 4-bit activations consumed straight from the packed stream (a piece = 16 pixels = 8 bytes, nibbles spread to bytes
 // in the staging registers) instead of being expanded to 8-bit codes by a pass of their own first.
-// NSTAGES > 0 (8-wave instances): the K loop fully unrolled over exactly NSTAGES stages with the activations requested TWO
-// stages ahead (two register sets of PPT pieces: 4 each with 512 threads) and the weights one stage ahead, so a request is in
-// flight at every moment of a stage -- with one set the time from a stage's arrival to the next request (LDS writes, barrier)
-// plus a full memory round trip is serial in every stage.
-template <int WM, int WN, int NIW, int NS, bool WRAW, bool S2, bool X4 = false, int NSTAGES = 0>
-__global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4) ? 1 : 2) void conv_mfma_flat_kernel(const MfmaArgs a)
+template <int WM, int WN, int NIW, int NS, bool WRAW, bool S2, bool X4 = false>
+__global__ __launch_bounds__(64 * WM * WN, 2) void conv_mfma_flat_kernel(const MfmaArgs a)
 {
-    constexpr int THR = 64 * WM * WN;           // 4 waves; 8 (WM = 8: 256 output channels per workgroup, one workgroup per CU)
+    constexpr int THR = 64 * WM * WN;           // 4 waves
     static_assert(!(X4 && S2), "the stride-2 staging takes 8-bit codes");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 
@@ -1844,55 +1764,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN > 4) ? 1 : 2) void conv_mfma
         QE_ST(5);   // barrier 2
     };
 
-    if constexpr (NSTAGES > 0) {
-        static_assert(WRAW && !S2 && !X4, "deep-prefetch form: packed 8-bit weights, stride 1");
-        DT d2[PPT];
-        v4i wfa[NS], wfb[NS];
-        auto load_w = [&](int s, v4i (&wf)[NS]) __attribute__((always_inline)) {
-#pragma unroll
-            for (int k = 0; k < NS; ++k) __builtin_memcpy(&wf[k], w_lane + (2 * (s * NS + k) + h) * 16, 16);   // IC == NSTAGES * CK: no padding
-        };
-        auto mma = [&](v4i (&wf)[NS]) __attribute__((always_inline)) {
-#pragma unroll
-            for (int k = 0; k < NS; ++k) {
-                v4i f = wf[k];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    f[j] ^= (int)0x80808080;
-                    swacc = __builtin_amdgcn_sdot4(f[j], 0x01010101, swacc, false);
-                }
-#pragma unroll
-                for (int t = 0; t < NIW; ++t) {
-                    const uint8_t *src = Xs + tr_base + (k * 32) * RSTR + (wn + t * WN) * 32;
-                    const v2i lo = __builtin_amdgcn_ds_read_tr8_b64_v2i32((v2i __attribute__((address_space(3))) *)(src));
-                    const v2i hi = __builtin_amdgcn_ds_read_tr8_b64_v2i32((v2i __attribute__((address_space(3))) *)(src + 8 * RSTR));
-                    const v4i xf = {lo[0], lo[1], hi[0], hi[1]};
-                    acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(xf, f, acc[t], 0, 0, 0);
-                }
-            }
-        };
-        if constexpr (NSTAGES > 1) issue_x(1, d2);
-        load_w(0, wfa);
-        QE_ST(0);
-#pragma unroll
-        for (int s = 0; s < NSTAGES; ++s) {
-            if (s & 1) stage_x(s, d2); else stage_x(s, d);
-            QE_ST(1);
-            __syncthreads();
-            QE_ST(2);
-            if (s + 2 < NSTAGES) { if (s & 1) issue_x(s + 2, d2); else issue_x(s + 2, d); }
-            if (s + 1 < NSTAGES) { if (s & 1) load_w(s + 1, wfa); else load_w(s + 1, wfb); }
-            QE_ST(3);
-            if (s & 1) mma(wfb); else mma(wfa);
-            QE_ST(4);
-            __syncthreads();
-            QE_ST(5);
-        }
-    } else {
     const int n_stages = (a.IC + CK - 1) / CK;
     for (int s = 0; s < n_stages - 1; ++s) stage(s, std::true_type{});
     stage(n_stages - 1, std::false_type{});
-    }
 
     // ---- epilogue: lane = output channel, 4 consecutive registers = 4 consecutive pixels ------
     const int sw_sum = swacc + __shfl_xor(swacc, 32);   // both channel halves
@@ -2278,50 +2152,47 @@ __global__ __launch_bounds__(MF_THREADS, 2) void conv_mfma_flatg_kernel(const Mf
 }
 
 // Which re-quantising lane = pixel kernels have a PATCH instance (codes through the workgroup's LDS byte patch): the halo
-// kernel <WM 4, NIW 7, KK 9, 8-bit, NS 1>, the stem kernels with NIW 7 and every sm2 kernel.  The planner sets rq_patch only
+// kernel <WM 4, NIW 7, KK 9, NS 1>, the stem kernels with NIW 7 and every sm2 kernel.  The planner sets rq_patch only
 // where this holds; the launchers instantiate PATCH from it.
 enum class MfKind { Halo, Stem, Sm2 };
-constexpr bool mfma_has_patch(MfKind k, int wm, int niw, int kkt, bool x8, int ns)
+constexpr bool mfma_has_patch(MfKind k, int wm, int niw, int kkt, int ns)
 {
-    return k == MfKind::Sm2 || (k == MfKind::Stem && niw == 7) || (k == MfKind::Halo && wm == 4 && niw == 7 && kkt == 9 && x8 && ns == 1);
+    return k == MfKind::Sm2 || (k == MfKind::Stem && niw == 7) || (k == MfKind::Halo && wm == 4 && niw == 7 && kkt == 9 && ns == 1);
 }
 
 // launchers, one translation unit per wave layout (qe_conv_mfma_i*.hip)
-void launch_mfma_cfg0(const MfmaArgs &a, int niw, int ns, int KK, bool x8, unsigned blocks, size_t lds, hipStream_t s);
-void launch_mfma_cfg1(const MfmaArgs &a, int niw, int ns, int KK, bool x8, unsigned blocks, size_t lds, hipStream_t s);
-void launch_mfma_cfg2(const MfmaArgs &a, int niw, int ns, int KK, bool x8, unsigned blocks, size_t lds, hipStream_t s);
-void launch_mfma_smallic(const MfmaArgs &a, int cfg, int niw, unsigned blocks, size_t lds, hipStream_t s);
+void launch_mfma_cfg0(const MfmaArgs &a, int niw, int ns, int KK, unsigned blocks, size_t lds, hipStream_t s);
+void launch_mfma_cfg1(const MfmaArgs &a, int niw, int ns, int KK, unsigned blocks, size_t lds, hipStream_t s);
+void launch_mfma_cfg2(const MfmaArgs &a, int niw, int ns, int KK, unsigned blocks, size_t lds, hipStream_t s);
+void launch_mfma_smallic(const MfmaArgs &a, int cfg, unsigned blocks, size_t lds, hipStream_t s);
 void launch_mfma_ws(const MfmaArgs &a, int niw, int split, unsigned blocks, size_t lds, hipStream_t s);
 void launch_mfma_sm2(const MfmaArgs &a, int wms, int split, unsigned blocks, size_t lds, hipStream_t s);
 void launch_mfma_flatg(const MfmaArgs &a, int ns, bool wraw, unsigned blocks, size_t lds, hipStream_t s);
 void launch_mfma_flat(const MfmaArgs &a, int cfg, int niw, int ns, bool wraw, bool s2, unsigned blocks, size_t lds, hipStream_t s);
 void launch_mfma_flat_x4(const MfmaArgs &a, int niw, int ns, unsigned blocks, size_t lds, hipStream_t s);
 
-#define QE_MFMA_K(WM, WN, NIW, KKT, X8, NS)                                                                                     \
+#define QE_MFMA_K(WM, WN, NIW, KKT, NS)                                                                                         \
     do {                                                                                                                        \
-        constexpr bool patch_ = mfma_has_patch(MfKind::Halo, WM, NIW, KKT, X8, NS);                                          \
+        constexpr bool patch_ = mfma_has_patch(MfKind::Halo, WM, NIW, KKT, NS);                                                 \
         if (a.rq_out != nullptr && a.rq_patch)                                                                                  \
-            hipLaunchKernelGGL((conv_mfma_kernel<WM, WN, NIW, KKT, X8, NS, true, patch_>), dim3(blocks), dim3(MF_THREADS), lds, s, a); \
+            hipLaunchKernelGGL((conv_mfma_kernel<WM, WN, NIW, KKT, NS, true, patch_>), dim3(blocks), dim3(MF_THREADS), lds, s, a); \
         else if (a.rq_out != nullptr)                                                                                           \
-            hipLaunchKernelGGL((conv_mfma_kernel<WM, WN, NIW, KKT, X8, NS, true>), dim3(blocks), dim3(MF_THREADS), lds, s, a);  \
+            hipLaunchKernelGGL((conv_mfma_kernel<WM, WN, NIW, KKT, NS, true>), dim3(blocks), dim3(MF_THREADS), lds, s, a);      \
         else                                                                                                                    \
-            hipLaunchKernelGGL((conv_mfma_kernel<WM, WN, NIW, KKT, X8, NS, false>), dim3(blocks), dim3(MF_THREADS), lds, s, a); \
+            hipLaunchKernelGGL((conv_mfma_kernel<WM, WN, NIW, KKT, NS, false>), dim3(blocks), dim3(MF_THREADS), lds, s, a);     \
     } while (0)
 
-// 1x1 convolutions get the multi-chunk stages (ns = 1, 2, 4); sub-8-bit activations only ns = 1
+// 1x1 convolutions get the multi-chunk stages (ns = 1, 2, 4)
 #define QE_MFMA_LAUNCH(WM, WN, NIW)                                                   \
     do {                                                                              \
         if (KK == 1) {                                                                \
-            if (!x8)           QE_MFMA_K(WM, WN, NIW, 1, false, 1);                   \
-            else if (ns == 4)  QE_MFMA_K(WM, WN, NIW, 1, true, 4);                    \
-            else if (ns == 2)  QE_MFMA_K(WM, WN, NIW, 1, true, 2);                    \
-            else               QE_MFMA_K(WM, WN, NIW, 1, true, 1);                    \
+            if (ns == 4)       QE_MFMA_K(WM, WN, NIW, 1, 4);                          \
+            else if (ns == 2)  QE_MFMA_K(WM, WN, NIW, 1, 2);                          \
+            else               QE_MFMA_K(WM, WN, NIW, 1, 1);                          \
         } else if (KK == 9 && a.KW == 3) {                                            \
-            if (x8) QE_MFMA_K(WM, WN, NIW, 9, true, 1);                               \
-            else    QE_MFMA_K(WM, WN, NIW, 9, false, 1);                              \
+            QE_MFMA_K(WM, WN, NIW, 9, 1);                                             \
         } else {                                                                      \
-            if (x8) QE_MFMA_K(WM, WN, NIW, 0, true, 1);                               \
-            else    QE_MFMA_K(WM, WN, NIW, 0, false, 1);                              \
+            QE_MFMA_K(WM, WN, NIW, 0, 1);                                             \
         }                                                                             \
     } while (0)
 

@@ -20,7 +20,8 @@ static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static const int kNiw[3][3] = {{7, 4, 2}, {4, 2, 1}, {2, 1, 0}};
 static const int kWN[3] = {1, 2, 4};
 
-static MfmaPlan make_plan8(const qe_conv_shape *sh, int x_bits, int w_bits, bool x4 = false)
+// the MFMA family of a problem with 8-bit activations (make_plan expands narrower ones first)
+static MfmaPlan make_plan8(const qe_conv_shape *sh, int w_bits, bool x4 = false)
 {
     MfmaPlan p;
     p.OH = (sh->H + 2 * sh->padding - sh->KH) / sh->stride + 1;
@@ -43,18 +44,18 @@ static MfmaPlan make_plan8(const qe_conv_shape *sh, int x_bits, int w_bits, bool
     p.OCP = (sh->OC + p.MT - 1) / p.MT * p.MT;
     const int NQ = (sh->W + 3) / 4;
     const int P = sh->H * sh->W;
-    p.flat = p.KK == 1 && sh->stride == 1 && sh->padding == 0 && x_bits == 8 && (P % 4) == 0 && P >= 64 && sh->IC >= 16;
+    p.flat = p.KK == 1 && sh->stride == 1 && sh->padding == 0 && (P % 4) == 0 && P >= 64 && sh->IC >= 16;
     // 1x1 / stride 2 / no padding (the downsample branches): same GEMM over the flat OUTPUT pixels, the
     // staging keeps the even columns of the even input rows.  224-pixel tiles must hold whole output rows.
     const int POUT = p.OH * p.OW;
-    if (!p.flat && p.KK == 1 && sh->stride == 2 && sh->padding == 0 && x_bits == 8 && p.cfg == 0 && sh->IC >= 64 &&
+    if (!p.flat && p.KK == 1 && sh->stride == 2 && sh->padding == 0 && p.cfg == 0 && sh->IC >= 64 &&
         (POUT % 4) == 0 && POUT >= 64 && 224 % p.OW == 0 && sh->W >= 16 && (sh->W % 4) == 0 && knob("QE_FLAT_S2", 1) != 0) {
         const int rt = 224 / p.OW, seg = (sh->W + 15) / 16;
         if (64 * rt * seg <= 8 * MF_THREADS) { p.flat = true; p.s2 = true; }
     }
     // 1x1 / stride 1 / no padding on 49..56-pixel planes (7x7 maps): the flat kernel's small-plane variant
     // (conv_mfma_flatg_kernel).  QE_FLATG=0 leaves these layers on the halo kernel.
-    if (!p.flat && p.KK == 1 && sh->stride == 1 && sh->padding == 0 && x_bits == 8 && p.cfg == 0 && sh->IC >= 64 &&
+    if (!p.flat && p.KK == 1 && sh->stride == 1 && sh->padding == 0 && p.cfg == 0 && sh->IC >= 64 &&
         (P + 7) / 8 == 7 && (int64_t)sh->N * sh->IC * P < (1ll << 32) && knob("QE_FLATG", 1) != 0) {
         const int nch = (sh->IC + 31) / 32;
         p.flatg = true;
@@ -119,14 +120,14 @@ static MfmaPlan make_plan8(const qe_conv_shape *sh, int x_bits, int w_bits, bool
         p.wt_bytes = p.wraw ? 0 : (size_t)p.NG * p.OCP * 16;
         p.IHT = (P + ntp - 1) / ntp;   // pixel tiles per image
     } else
-    p.smallic = sh->IC <= 4 && sh->KW <= 8 && sh->KH <= 8 && x_bits == 8;
+    p.smallic = sh->IC <= 4 && sh->KW <= 8 && sh->KH <= 8;
     // 3x3, 8-bit activations, more than 32 output channels: two strips per wave, weights through LDS
     // (conv_mfma_sm2_kernel).  Measured against the halo / warp-specialised kernels on ResNet-50 (tools/ab_env.sh
     // QE_SM2 0 1): 56x56 64->64 0.083 -> 0.068 ms, 14x14 256->256 0.050 -> 0.048, 28x28 +4 %, 7x7 maps and the
     // stride-2 layers +15 % (the warp-specialised kernel / bigger halo tiles win there).  Default: stride 1 and a
     // tile that is either 64 channels wide or a whole image; QE_SM2=1 forces it wherever it fits, QE_SM2=0 never.
     const int sm2_env = knob("QE_SM2", -1);
-    if (!p.flat && !p.flatg && !p.smallic && p.KK == 9 && sh->KW == 3 && sh->KH == 3 && x_bits == 8 && p.cfg <= 1 && sm2_env != 0) {
+    if (!p.flat && !p.flatg && !p.smallic && p.KK == 9 && sh->KW == 3 && sh->KH == 3 && p.cfg <= 1 && sm2_env != 0) {
         const int max_px = 32 * (p.cfg == 0 ? 8 : 16);
         int GI = 1;
         if (p.OH * p.OW <= max_px / 2) GI = std::max(1, std::min((int)sh->N, max_px / (p.OH * p.OW)));
@@ -164,8 +165,8 @@ static MfmaPlan make_plan8(const qe_conv_shape *sh, int x_bits, int w_bits, bool
         p.niw = kNiw[p.cfg][0];
         int stem_tiles = max_tiles;
         // 64-channel workgroups (the ResNet stem): 7 column tiles per wave = 4 output rows per tile instead of 2
-        // (fewer, larger workgroups: less halo re-read, prologue amortised).  QE_STEM_NIW=4 restores the old tiles.
-        if (p.cfg == 1 && knob("QE_STEM_NIW", 0) != 4 && p.OW <= 32 * 14) {
+        // (fewer, larger workgroups: less halo re-read, prologue amortised)
+        if (p.cfg == 1) {
             p.niw = 7;
             stem_tiles = 14;
         }
@@ -188,7 +189,7 @@ static MfmaPlan make_plan8(const qe_conv_shape *sh, int x_bits, int w_bits, bool
         // barrier pair are amortised over 7 column tiles instead of 2
         if (p.OH * p.OW <= max_px / 2) p.GI = std::max(1, std::min((int)sh->N, max_px / (p.OH * p.OW)));
         int TH = (p.GI > 1) ? p.OH : std::min(p.OH, max_px / p.OW);
-        const bool multi = p.KK == 1 && x_bits == 8;   // 1x1, 8-bit: several chunks per stage
+        const bool multi = p.KK == 1;   // 1x1: several chunks per stage
         for (;;) {
             const int IHT = (p.ROWMUL > 1) ? TH : (TH - 1) * sh->stride + sh->KH;
             const int IWP = (p.COLMUL > 1) ? p.OW : (p.OW - 1) * sh->stride + sh->KW;
@@ -229,14 +230,10 @@ static MfmaPlan make_plan8(const qe_conv_shape *sh, int x_bits, int w_bits, bool
         // than one specialised one (stamps: the consumer issues one MFMA per ~60 cycles; its weight loads queue
         // behind the producers' HBM misses in the CU's in-order vector-memory path).  QE_WS=1 forces it on.
         const bool ws_default = p.GI > 1 || p.OH * p.OW <= 64;
-        if (p.KK == 9 && sh->KW == 3 && x_bits == 8 && p.cfg == 0 && p.NS == 1 && knob("QE_WS", ws_default) != 0) {
-            // stride 1 with padding 1: unpadded LDS rows (conflict-free fragment reads) + lane masks
-            const bool nopad = sh->stride == 1 && sh->padding == 1 && knob("QE_WS_NOPAD", 0) == 1;   // off by default
-            const int iwp = nopad ? sh->W : p.IWP;
-            const int gd = nopad ? sh->padding : 0;
-            const size_t gsz = (size_t)p.GI * p.IHT * iwp + 2 * gd;
+        if (p.KK == 9 && sh->KW == 3 && p.cfg == 0 && p.NS == 1 && knob("QE_WS", ws_default) != 0) {
+            const size_t gsz = (size_t)p.GI * p.IHT * p.IWP;
             const size_t lds = ((size_t)4 * gsz + MF_TRASH) * 16 + gsz * 4;
-            if (lds <= (size_t)MF_MAX_LDS) { p.ws = true; p.lds = lds; p.IWP = iwp; p.PADW = nopad ? 0 : sh->padding; }
+            if (lds <= (size_t)MF_MAX_LDS) { p.ws = true; p.lds = lds; }
         }
     }
     if ((p.flat || p.flatg) && p.wraw) { p.total = 0; p.ok = true; return p; }
@@ -257,14 +254,12 @@ static qe_conv_shape dense_shape(const qe_conv_shape *sh)
     return d;
 }
 
-// Sub-8-bit activations: the halo kernel can decode them on the fly (8-byte clamped reads + shifts per 4 pixels),
-// but that path is 3-4x slower than the 8-bit kernels (ResNet-50 W4A4: 16.0 ms vs 4.7 ms per batch-256).  Instead
-// the stream is expanded once to signed 8-bit stored codes in the workspace (one pass at HBM rate: b/8 + 1 bytes per
-// element) and every fast 8-bit kernel applies.  QE_EXPAND=0 keeps the in-kernel decode (tuning / tests).
+// Sub-8-bit activations: the stream is expanded once to signed 8-bit stored codes in the workspace (one pass at HBM rate:
+// b/8 + 1 bytes per element) and every fast 8-bit kernel applies.  Decoding them inside the halo kernel was 3-4x slower
+// (ResNet-50 W4A4: 16.0 ms vs 4.7 ms per batch-256).
 static MfmaPlan make_plan(const qe_conv_shape *sh, int x_bits, int w_bits)
 {
-    const bool expand = x_bits < 8 && knob("QE_EXPAND", 1) != 0;
-    const int xb = expand ? 8 : x_bits;
+    const bool expand = x_bits < 8;
     // Strided 1x1 (the ResNet downsample branches): gather the sampled pixels once (read every other row, write 1/s^2 of
     // the bytes) and run the stride-1 kernels on the dense tensor, instead of staging 2-4x the needed bytes in every
     // one of the OC/128 workgroups that share a pixel tile.  QE_SUBSAMPLE=0 keeps the in-kernel strided staging.
@@ -275,22 +270,22 @@ static MfmaPlan make_plan(const qe_conv_shape *sh, int x_bits, int w_bits)
     const int p_out = ((sh->H - 1) / std::max(1, (int)sh->stride) + 1) * ((sh->W - 1) / std::max(1, (int)sh->stride) + 1);
     // 4-bit activations, stride 2: ONE pass reads the even nibbles of the even rows and writes dense 8-bit codes
     // (subsample_x4_kernel) instead of expanding the whole tensor first -- there the gather pays on every plane size
-    const bool sub_x4 = x_bits == 4 && expand && sh->stride == 2 && (sh->W % 2) == 0 && ((int64_t)sh->H * sh->W % 2) == 0 &&
+    const bool sub_x4 = x_bits == 4 && sh->stride == 2 && (sh->W % 2) == 0 && ((int64_t)sh->H * sh->W % 2) == 0 &&
                         knob("QE_SUB_X4", 1) != 0;
-    const bool sub = sh->KH == 1 && sh->KW == 1 && sh->stride > 1 && sh->padding == 0 && xb == 8 && sub_env != 0 &&
+    const bool sub = sh->KH == 1 && sh->KW == 1 && sh->stride > 1 && sh->padding == 0 && sub_env != 0 &&
                      (sub_env > 0 || p_out <= 256 || sub_x4);
     const qe_conv_shape ds = dense_shape(sh);
     // 4-bit activations on a stride-1 1x1 layer with 128-channel workgroups: the flat kernel unpacks the nibbles in its
     // staging registers (QE_X4=0: expansion pass + 8-bit kernel as for every other sub-8-bit case)
-    if (x_bits == 4 && expand && !sub && knob("QE_X4", 1) != 0) {
-        MfmaPlan q = make_plan8(sh, 8, w_bits, true);
+    if (x_bits == 4 && !sub && knob("QE_X4", 1) != 0) {
+        MfmaPlan q = make_plan8(sh, w_bits, true);
         if (q.ok && q.flat && !q.s2 && !q.flatg && q.cfg == 0) {
             q.x4 = true;
             q.prep_total = q.total;
             return q;
         }
     }
-    MfmaPlan p = make_plan8(sub ? &ds : sh, xb, w_bits);
+    MfmaPlan p = make_plan8(sub ? &ds : sh, w_bits);
     p.prep_total = p.ok ? p.total : 0;
     if (p.ok && sub) {
         p.sub = true;
@@ -298,7 +293,7 @@ static MfmaPlan make_plan(const qe_conv_shape *sh, int x_bits, int w_bits)
         p.sub_off = align_up(p.total, 256);
         p.total = p.sub_off + align_up((size_t)ds.N * ds.IC * ds.H * ds.W, 256);
     } else if (sub) {
-        p = make_plan8(sh, xb, w_bits);
+        p = make_plan8(sh, w_bits);
         p.prep_total = p.ok ? p.total : 0;
     }
     if (p.ok && expand) {
@@ -393,22 +388,17 @@ static int pwr7_plan(const qe_conv_shape *sh, const qe_qparam *x, const qe_qpara
     return gi;
 }
 
-// ---- LDS-DMA ring kernel (qe_conv_flatd.hip): tile variant 0 = none, 5 / 7 = WIDE with that many column tiles, 8 = SMALL ----
-static int flatd_variant(const qe_conv_shape *sh, const qe_qparam *x, const qe_qparam *w, uintptr_t xa)
+// ---- LDS-DMA ring kernel (qe_conv_flatd.hip): 1x1 layers on 7x7 planes ----
+static bool flatd_plan(const qe_conv_shape *sh, const qe_qparam *x, const qe_qparam *w, uintptr_t xa)
 {
-    if (sh->KH != 1 || sh->KW != 1 || sh->stride != 1 || sh->padding != 0) return 0;
-    if (x->n_bits != 8 || w->n_bits != 8 || x->n_param != 1) return 0;
-    if (sh->IC % FD_CK != 0 || sh->IC < 2 * FD_CK || sh->OC < 1 || sh->N < 1) return 0;
+    if (sh->KH != 1 || sh->KW != 1 || sh->stride != 1 || sh->padding != 0) return false;
+    if (x->n_bits != 8 || w->n_bits != 8 || x->n_param != 1) return false;
+    if (sh->IC % FD_CK != 0 || sh->IC < 2 * FD_CK || sh->OC < 1 || sh->N < 1) return false;
     const int64_t P = (int64_t)sh->H * sh->W;
-    if ((int64_t)sh->N * sh->IC * P < 16 || (int64_t)sh->OC * P >= (1ll << 29) || (int64_t)sh->IC * P >= (1ll << 31)) return 0;
-    if ((reinterpret_cast<uintptr_t>(w->data) & 15) != 0) return 0;      // weight rows are fetched as aligned 16-byte pieces
-    if (P == 49 && sh->OC % 4 == 0 && (xa & 15) == 0) return 8;
-    if ((P % 16 != 0 && P % 16 != 4) || P < 160) return 0;     // a row's last slot holds 16 or 4 valid bytes
-    if ((xa & 3) != 0) return 0;
-    auto waste = [&](int t) { return (double)((P + 32 * t - 1) / (32 * t)) * (32 * t) / (double)P; };
-    return waste(5) < waste(7) - 0.03 ? 5 : 7;
+    if ((int64_t)sh->N * sh->IC * P < 16 || (int64_t)sh->OC * P >= (1ll << 29) || (int64_t)sh->IC * P >= (1ll << 31)) return false;
+    if ((reinterpret_cast<uintptr_t>(w->data) & 15) != 0) return false;      // weight rows are fetched as aligned 16-byte pieces
+    return P == 49 && sh->OC % 4 == 0 && (xa & 15) == 0;
 }
-constexpr int QE_FLATD_DEFAULT = 4;   // 7x7 planes only: -17..-20 % there; the wide variants tie or lose to the register-staged kernels (profiles/r02b_ab_flatd.txt)
 
 // block map: XCD runs of `chunk` pixel tiles (block_to_tile).  Default: each XCD owns one contiguous eighth of the tiles
 // (sum over the ResNet-50 layers 4.13 -> 4.07 ms against single-tile interleaving); QE_CHUNK_IMAGES = k overrides with runs
@@ -423,35 +413,24 @@ static int64_t block_map(ConvPlan &p, int64_t n_units, int per_image, int64_t pe
 }
 
 // the LDS byte patch of a re-quantising lane = pixel kernel: only the instances mfma_has_patch names exist
-static bool plan_rq_patch(const MfmaPlan &m, const ConvRequest &r, bool x8)
+static bool plan_rq_patch(const MfmaPlan &m, const ConvRequest &r)
 {
     if (m.flat || m.flatg || m.ws || m.GI != 1 || (m.OH * m.OW) % 4 != 0 || (m.TH * m.OW) % 4 != 0) return false;
     if ((r.rq_out & 3) != 0 || knob("QE_RQ_PATCH", 1) == 0) return false;
     const int wm = m.cfg == 0 ? 4 : (m.cfg == 1 ? 2 : 1);
     const int kkt = m.KK == 1 ? 1 : ((m.KK == 9 && r.sh->KW == 3) ? 9 : 0);
-    if (m.sm2) return mfma_has_patch(MfKind::Sm2, wm, m.niw, kkt, x8, m.NS);
-    return mfma_has_patch(m.smallic ? MfKind::Stem : MfKind::Halo, wm, m.niw, kkt, x8, m.NS);
+    if (m.sm2) return mfma_has_patch(MfKind::Sm2, wm, m.niw, kkt, m.NS);
+    return mfma_has_patch(m.smallic ? MfKind::Stem : MfKind::Halo, wm, m.niw, kkt, m.NS);
 }
 
 // the MFMA-family launch: tiles, grid, epilogue tables and dynamic LDS
-static void plan_mfma_launch(ConvPlan &p, const ConvRequest &r, bool rq, bool x8)
+static void plan_mfma_launch(ConvPlan &p, const ConvRequest &r, bool rq)
 {
     const MfmaPlan &m = p.m;
     const qe_conv_shape *sh = &p.run;
     p.tiles_h = (m.OH + m.TH - 1) / m.TH;
     p.n_pix_tiles = ((sh->N + m.GI - 1) / m.GI) * p.tiles_h;
     p.n_oc_tiles = m.OCP / m.MT;
-    // flat 1x1, deep reductions into >= 256 output channels (1024 -> 256 @14x14, 512 -> 256 @28x28, ...): 8-wave workgroups
-    // that own 256 output channels of a pixel tile, so the tile's activations cross the CU's memory path OC / 256 times
-    // instead of OC / 128 (these layers are bound by the bytes through that path).  Weights straight
-    // from the packed tensor only (no prepared-table layout depends on the channel tile).  Opt-in (QE_FLAT8=1; 3: IC = 1024
-    // only; 2: without the deep prefetch): cold per-layer A/B -7 % on 1024 -> 256 @14x14, but the step as a whole does not
-    // gain (profiles/r03w_ab_flat8*.txt).
-    const int flat8 = knob("QE_FLAT8", 0);
-    p.wide8 = m.flat && !m.s2 && !m.x4 && !m.flatg && m.cfg == 0 && m.wraw && !rq && m.NS == 4 && (m.niw == 7 || m.niw == 5) &&
-              sh->IC >= 512 && sh->OC % 256 == 0 && flat8 != 0 && (flat8 != 3 || sh->IC == 1024);
-    p.deep8 = p.wide8 && (sh->IC == 512 || sh->IC == 1024) && flat8 != 2;
-    if (p.wide8) p.n_oc_tiles = sh->OC / 256;
     if (m.flatg) {
         p.tiles_h = 1;                           // one tile = GI whole images
         p.n_pix_tiles = (sh->N + m.GI - 1) / m.GI;
@@ -478,13 +457,12 @@ static void plan_mfma_launch(ConvPlan &p, const ConvRequest &r, bool rq, bool x8
             p.ptab_off = (int)align_up(m.lds, 16);
             p.lds = p.ptab_off + (m.flatg ? (size_t)m.GI * m.MT * sh->H * sh->W : (size_t)m.MT * 32 * m.ni);
         }
-        if (p.wide8) p.lds = std::max((size_t)(32 * m.NS) * (32 * (m.ni | 1)), (size_t)8 * 32 * 36 * 4) + (size_t)(32 * m.ni) * 4;
         return;
     }
     // lane = pixel kernels (halo, sm2, stem) with fused re-quantisation, one image per tile: the codes leave through a
     // workgroup byte patch at the START of the dynamic LDS (<= 32 KB: MT x pixel slots; the staging image is dead by then)
     // instead of as byte stores of 32-byte runs; the epilogue's tables sit behind it.  QE_RQ_PATCH=0: byte stores.
-    p.rq_patch = rq && plan_rq_patch(m, r, x8);
+    p.rq_patch = rq && plan_rq_patch(m, r);
     const size_t stage_bytes = p.rq_patch ? std::max(m.lds, (size_t)32 * 1024) : m.lds;
     // LDS room for the epilogue's copy of the tile's S_w prefix rows (asymmetric activations; stage_ptab)
     size_t lds_e = stage_bytes;
@@ -576,17 +554,14 @@ ConvPlan plan_conv(const ConvRequest &r)
         // 128 | 256 | 512): the resident-tile kernels.  Their re-quantising forms store codes as aligned 16-byte pieces
         // (QE_PWR_RQ=0: off); the plain 7x7 form stores fp32 the same way.  QE_PWR=0 keeps the kernels below.
         const bool pwr_ok = rq ? (r.rq_out & 15) == 0 && knob("QE_PWR_RQ", 1) != 0 : true;
-        const int var = flatd_variant(rs, &xr, r.w, xa);
-        // 1x1 / stride 1 layers with 8-bit operands and IC % 64 == 0: the LDS-DMA ring kernel.  QE_FLATD=0 keeps the
-        // register-staged flat kernels; QE_FLATD=<bitmask> enables it per tile variant (1: 224-pixel tiles, 2: 160-pixel
-        // tiles, 4: 7x7 planes); default from the per-layer A/B in DESIGN.md.  Re-quantising: 7x7 planes, whole 32-channel
-        // strips, codes as aligned 16-byte pieces (QE_FLATD_RQ=0: off).
-        const int bit = var == 7 ? 1 : (var == 5 ? 2 : (var == 8 ? 4 : 0));
-        const bool fd_ok = var != 0 && (knob("QE_FLATD", QE_FLATD_DEFAULT) & bit) &&
-                           (!rq || (var == 8 && rs->OC % 32 == 0 && (r.rq_out & 15) == 0 && knob("QE_FLATD_RQ", 1) != 0));
+        // 1x1 / stride 1 layers on 7x7 planes with 8-bit operands and IC % 64 == 0: the LDS-DMA ring kernel (-17..-20 % against
+        // the register-staged kernels there, profiles/r02b_ab_flatd.txt).  QE_FLATD=0 keeps the register-staged flat kernels.
+        // Re-quantising: whole 32-channel strips, codes as aligned 16-byte pieces (QE_FLATD_RQ=0: off).
+        const bool fd_ok = flatd_plan(rs, &xr, r.w, xa) && knob("QE_FLATD", 1) != 0 &&
+                           (!rq || (rs->OC % 32 == 0 && (r.rq_out & 15) == 0 && knob("QE_FLATD_RQ", 1) != 0));
         if (pwr_ok && pwr_plan(rs, &xr, r.w, xa, &pf)) p.route = ConvRoute::Pwr;
         else if (pwr_ok && (rq || (r.out & 15) == 0) && (p.pwr7_gi = pwr7_plan(rs, &xr, r.w, xa, &g7)) != 0) p.route = ConvRoute::Pwr7;
-        else if (fd_ok) { p.route = ConvRoute::Flatd; p.fd_var = var; }
+        else if (fd_ok) p.route = ConvRoute::Flatd;
         else p.route = ConvRoute::Mfma;
     }
 
@@ -607,15 +582,14 @@ ConvPlan plan_conv(const ConvRequest &r)
         // layers, +15 % on 2048->512 @7x7 -- halving the activation re-reads does NOT give the -14..-26 % a bytes-through-the-CU
         // model predicts.  On for wide 7x7 layers only; QE_FLATD8=0 | 1 overrides.
         const char *e8 = env_get("QE_FLATD8");
-        p.fd_w8 = e8 ? atoi(e8) != 0 && rs->OC > 128 : p.fd_var == 8 && rs->OC >= 1024;
+        p.fd_w8 = e8 ? atoi(e8) != 0 && rs->OC > 128 : rs->OC >= 1024;
         const int MT = p.fd_w8 ? 256 : 128;
         p.n_oc_tiles = (rs->OC + MT - 1) / MT;
-        const int P = rs->H * rs->W;
-        p.tiles_h = p.fd_var == 8 ? 1 : (P + 32 * p.fd_var - 1) / (32 * p.fd_var);
-        p.n_pix_tiles = p.fd_var == 8 ? (rs->N + 3) / 4 : rs->N * p.tiles_h;
+        p.tiles_h = 1;                           // one tile = 4 whole images
+        p.n_pix_tiles = (rs->N + 3) / 4;
         p.blocks = block_map(p, p.n_pix_tiles, p.tiles_h, p.n_oc_tiles);
     } else {
-        plan_mfma_launch(p, r, p.fused, xr.n_bits == 8);
+        plan_mfma_launch(p, r, p.fused);
     }
     if (p.blocks > 0x7fffffffLL) { p.route = ConvRoute::Generic; p.fused = false; }
     return p;

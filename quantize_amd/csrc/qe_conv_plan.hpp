@@ -33,7 +33,6 @@ struct MfmaPlan {
     bool sub = false;          // strided 1x1: the sampled pixels are gathered into a dense tensor first
     bool sub_x4 = false;       // ... straight from the 4-bit stream (subsample_x4_kernel), no expansion pass
     size_t sub_off = 0;
-    int PADW = 0;
     size_t lds = 0;
     size_t wt_bytes = 0, ep_off = 0, ws_off = 0, total = 0;
     size_t prep_total = 0;     // leading part of the workspace the prep pass fills (x-independent: can be kept across calls)
@@ -75,10 +74,8 @@ struct ConvPlan {
     int pwr_tw = 0, pwr_ks = 0, pwr_groups = 1, pwr7_gi = 0;
     bool pwr_s2 = false;
     // flatd
-    int fd_var = 0;            // 5 / 7: WIDE with that many column tiles, 8: SMALL (7x7 planes)
     bool fd_w8 = false;        // 8-wave / 256-channel workgroups
     // MFMA families
-    bool wide8 = false, deep8 = false;   // flat kernel with 256-channel workgroups (QE_FLAT8), its deep-prefetch form
     bool rq_patch = false;     // re-quantised codes leave through the LDS byte patch (PATCH instances only)
     bool ctab = false;
     int ptab_off = 0;

@@ -697,7 +697,7 @@ __global__ __launch_bounds__(512, 2) void conv_pwr7_kernel(const PwrArgs a)
     __syncthreads();
     if (n_my <= 0) return;
 
-    // transposed-read bases (qe_conv_flatd.hip, SMALL): row (16 h + i16 / 2) of a 32-channel step; logical slot 2 tt + ((lane >> 4) & 1)
+    // transposed-read bases (as qe_conv_flatd.hip): row (16 h + i16 / 2) of a 32-channel step; logical slot 2 tt + ((lane >> 4) & 1)
     // sits at position slot ^ 2 for rows 4-7 of every 8
     const int i16 = lane & 15;
     const int sm_sl = ((lane >> 4) & 1) ^ (2 * (i16 >> 3));

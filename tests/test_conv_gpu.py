@@ -280,12 +280,13 @@ def test_conv_error_messages(engine):
     assert tuple(y.shape) == (1, 6, 8, 8) and float(y.abs().max()) == 0.0
 
 
-@pytest.mark.parametrize("env", [{"QE_SM2": "0", "QE_WS": "1"}, {"QE_SM2": "0", "QE_WS": "1", "QE_WS_NOPAD": "1"},
-                                 {"QE_SM2": "0", "QE_WS": "0"}, {"QE_SM2": "1"}, {"QE_FLAT_NIW": "4"}, {"QE_FLAT_NIW": "5"},
-                                 {"QE_FLAT_NIW": "7"}, {"QE_CHUNK_IMAGES": "0"}, {"QE_CHUNK_IMAGES": "1"}, {"QE_SUBSAMPLE": "0"}, {"QE_SUBSAMPLE": "1"}, {"QE_FLATG": "0"}, {"QE_CTAB": "0"}])
+# ids keep the numbering the sets have always had (env1, the unpadded-row warp-specialised kernel, was removed with it)
+@pytest.mark.parametrize("env", [{"QE_SM2": "0", "QE_WS": "1"}, {"QE_SM2": "0", "QE_WS": "0"}, {"QE_SM2": "1"}, {"QE_FLAT_NIW": "4"}, {"QE_FLAT_NIW": "5"},
+                                 {"QE_FLAT_NIW": "7"}, {"QE_CHUNK_IMAGES": "0"}, {"QE_CHUNK_IMAGES": "1"}, {"QE_SUBSAMPLE": "0"}, {"QE_SUBSAMPLE": "1"}, {"QE_FLATG": "0"}, {"QE_CTAB": "0"}],
+                         ids=["env0"] + ["env%d" % i for i in range(2, 13)])
 def test_kernel_variants_forced_by_env(engine, env):
-    """The tuning knobs select other kernel variants (two-strip / warp-specialised (padded, unpadded LDS rows) /
-    single-role 3x3, flat tile widths, block maps); every variant must meet the same parity bar."""
+    """The tuning knobs select other kernel variants (two-strip / warp-specialised / single-role 3x3, flat tile widths,
+    block maps); every variant must meet the same parity bar."""
     import os
     rng = np.random.RandomState(17)
     old = {k: os.environ.get(k) for k in env}
@@ -308,16 +309,14 @@ def test_kernel_variants_forced_by_env(engine, env):
         capi.reload_env()
 
 
-@pytest.mark.parametrize("expand,x4", [("0", "1"), ("1", "1"), ("1", "0")])
-def test_sub8_activation_paths(engine, expand, x4):
-    """b < 8 activations either decode inside the halo kernel (QE_EXPAND=0), or are expanded once to 8-bit codes in
-    the workspace and run on the 8-bit kernels (default), or -- 4-bit activations on stride-1 1x1 layers -- are unpacked
-    by the flat kernel's own staging (QE_X4, default on); all meet the parity bar, incl. asymmetric zero points."""
+@pytest.mark.parametrize("x4", ["1", "0"])
+def test_sub8_activation_paths(engine, x4):
+    """b < 8 activations are expanded once to 8-bit codes in the workspace and run on the 8-bit kernels, or -- 4-bit
+    activations on stride-1 1x1 layers -- are unpacked by the flat kernel's own staging (QE_X4, default on; QE_X4=0:
+    the expansion pass there too); both meet the parity bar, incl. asymmetric zero points."""
     import os
     rng = np.random.RandomState(23)
-    old = os.environ.get("QE_EXPAND")
     oldx = os.environ.get("QE_X4")
-    os.environ["QE_EXPAND"] = expand
     os.environ["QE_X4"] = x4
     try:
         for shp in [(2, 64, 28, 28, 160, 1, 1, 0), (2, 128, 14, 14, 130, 3, 1, 1), (3, 64, 56, 56, 64, 3, 1, 1),
@@ -328,9 +327,9 @@ def test_sub8_activation_paths(engine, expand, x4):
                     case = _random_case(rng, *shp, wb, wsgn, ab, asgn, w_pc=True, a_pc=False, zeros=zeros, bias=True)
                     y, o32, o64 = _run_case(engine, case, via_capi=True)
                     assert case["path"] == 1
-                    _assert_conv_close(y, o64, o32, "expand=%s %s %s zeros=%s" % (expand, shp, (wb, wsgn, ab, asgn), zeros), case["fma"])
+                    _assert_conv_close(y, o64, o32, "x4=%s %s %s zeros=%s" % (x4, shp, (wb, wsgn, ab, asgn), zeros), case["fma"])
     finally:
-        for k, v in (("QE_EXPAND", old), ("QE_X4", oldx)):
+        for k, v in (("QE_X4", oldx),):
             if v is None:
                 os.environ.pop(k, None)
             else:
