@@ -374,7 +374,8 @@ int qe_quantize_patchify(const float *x, int32_t N, int32_t C, int32_t H, int32_
                          const float *zero, int32_t n_param, float qmin, float qmax, int n_bits, int sign, uint8_t *out,
                          int32_t *status, qe_stream_t stream);
 
-/* qe_attention -- the fp32 attention core of a ViT encoder block / nn.MultiheadAttention (need_weights=False, no mask):
+/* qe_attention -- the fp32 attention core of a ViT encoder block / nn.MultiheadAttention (need_weights=False, no mask;
+ * qe_attention_masked below takes the masks):
  *   out[n, t, h] = sum_s softmax_s(scale * q[n, t, h] . k[n, s, h]) v[n, s, h]      per image n < N, head h < H
  * for query tokens t < L and key tokens s < S (S != L allowed).  Every tensor is rows of H*d floats; the row of
  * (image n, token t) is n*rn + t*rt, and head h is columns h*d .. h*d + d - 1 of it: token-major (N L, E) rows are
@@ -396,6 +397,39 @@ int qe_attention(const float *q, const float *k, const float *v, float *out,
                  int32_t N, int32_t L, int32_t S, int32_t H, int32_t d,
                  int64_t q_rn, int64_t q_rt, int64_t kv_rn, int64_t kv_rt, int64_t o_rn, int64_t o_rt,
                  float scale, qe_stream_t stream);
+
+/* qe_attention_masked -- qe_attention with up to three optional operands on the score:
+ *   score[n, h, t, s] = scale * q[n, t, h] . k[n, s, h] + mask[n, h, t, s] + key_bias[n, s],   s <= t only when causal
+ * and everything after it (online softmax, P.V, one division) as qe_attention.  q .. scale as there.
+ * mask           fp32 device pointer or NULL: rows of S contiguous floats, row t of (image n, head h) at
+ *                mask + n*mask_sn + h*mask_sh + t*S (element strides, >= 0; 0 broadcasts).  torch's 2-D (L, S) mask is
+ *                (0, 0), nn.MultiheadAttention's 3-D (N*H, L, S) is (H*L*S, L*S), a per-image (N, L, S) is (L*S, 0).
+ *                Values are finite or -inf; they are added to the scaled score, not multiplied by scale (torch's convention).
+ * key_bias       fp32 (N, S) device pointer or NULL: the key-padding mask as an additive row (-inf = padded key), kept
+ *                apart from mask so that padding never needs an N*H*L*S tensor.
+ * causal         non-zero: key s is visible to query t iff s <= t -- top-left aligned for S != L, torch.ones(L, S).tril(),
+ *                the is_causal convention of F.scaled_dot_product_attention.  Key tiles wholly above the diagonal of a
+ *                wave's queries are not visited (no K / V load); the diagonal tile is masked by index, no memory read.
+ * mask == NULL && key_bias == NULL && !causal is qe_attention: the same kernel instance.  Each combination of operands is
+ * its own instance of the two kernels (a template parameter, no branch in the tile loop); 16-byte mask loads where
+ * S % 4 == 0 and both strides % 4 == 0, 4-byte loads otherwise: any S works.  No workspace, no host synchronisation.
+ * QE_ERR_ARG (before any device work) additionally for: a negative mask stride; mask or key_bias not 16-byte aligned;
+ * out overlapping mask or key_bias; a non-zero mask_sn / mask_sh with mask == NULL.
+ * Declared behaviours:
+ *  - a key tile in which every key of a row is masked, followed by visible keys (padding at the front, a window, holes),
+ *    is exact: while the row's running max is -inf the rescale factor is 1 and p = 0.
+ *  - a row with NO visible key is NaN in that row of that head (0 / 0 of the final division) and affects nothing else:
+ *    what torch.softmax over an all -inf row gives (nn.MultiheadAttention's math path; torch's fused SDPA returns 0).
+ *  - non-finite q / k / v at masked positions are unspecified: an additive -inf does not hide a NaN score, a key tile
+ *    skipped under causal does.
+ * qe_attention_masked_path (host only): the kernel a call with these operands takes, 1 MFMA / 0 VALU / -1 none; the
+ * operands select an instance of the kernel qe_attention_path names, never another kernel.                           */
+int qe_attention_masked_path(int32_t L, int32_t S, int32_t H, int32_t d, int has_mask, int has_key_bias, int causal);
+int qe_attention_masked(const float *q, const float *k, const float *v, float *out,
+                        int32_t N, int32_t L, int32_t S, int32_t H, int32_t d,
+                        int64_t q_rn, int64_t q_rt, int64_t kv_rn, int64_t kv_rt, int64_t o_rn, int64_t o_rt,
+                        float scale, const float *mask, int64_t mask_sn, int64_t mask_sh, const float *key_bias,
+                        int causal, qe_stream_t stream);
 
 /* ---- auxiliary (no counterpart in the reference's extension) ---------------------------------
  * Global average pool of an fp32 NCHW tensor: out[plane] = mean(x[plane][0..P)) for n_planes = N*C planes of P

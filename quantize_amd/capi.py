@@ -30,7 +30,8 @@ SYMBOLS = ["qe_error_string", "qe_last_hip_error", "qe_version", "qe_target_arch
            "qe_quantlinear_residual_path", "qe_quantlinear_residual_workspace_bytes", "qe_quantlinear_residual",
            "qe_quantlinear_float_input_residual_path", "qe_quantlinear_float_input_residual_workspace_bytes",
            "qe_quantlinear_float_input_residual", "qe_layernorm_quantize_pack_path", "qe_layernorm_quantize_pack_workspace_bytes",
-           "qe_layernorm_quantize_pack", "qe_quantize_patchify", "qe_attention_path", "qe_attention"]
+           "qe_layernorm_quantize_pack", "qe_quantize_patchify", "qe_attention_path", "qe_attention",
+           "qe_attention_masked_path", "qe_attention_masked"]
 
 ACTS = {None: 0, "none": 0, "gelu": 1}
 
@@ -165,6 +166,11 @@ def lib():
     L.qe_attention_path.argtypes = [i32, i32, i32, i32]
     L.qe_attention.restype = i32
     L.qe_attention.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, i64, i64, f32, vp]
+    L.qe_attention_masked_path.restype = i32
+    L.qe_attention_masked_path.argtypes = [i32, i32, i32, i32, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    L.qe_attention_masked.restype = i32
+    L.qe_attention_masked.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, i64, i64, f32,
+                                      vp, i64, i64, vp, ctypes.c_int, vp]
     _lib = L
     return L
 
@@ -625,11 +631,21 @@ def attention_path(L, S, H, d):
     return int(lib().qe_attention_path(int(L), int(S), int(H), int(d)))
 
 
-def attention(q, k, v, N, L, H, S=None, layout="token", scale=None, out=None, stream=None):
+def attention_masked_path(L, S, H, d, has_mask=False, has_key_bias=False, causal=False):
+    """qe_attention_masked_path: the kernel a masked call takes (1 MFMA, 0 VALU, -1 none)."""
+    return int(lib().qe_attention_masked_path(int(L), int(S), int(H), int(d), int(bool(has_mask)), int(bool(has_key_bias)),
+                                              int(bool(causal))))
+
+
+def attention(q, k, v, N, L, H, S=None, layout="token", scale=None, out=None, stream=None, mask=None, key_bias=None,
+              causal=False):
     """qe_attention: softmax(scale q k^T) v per (image, head) on fp32 rows of E = H d floats, read in place.
     layout "token": q / out are (N L, E) and k / v (N S, E) rows (a ViT's projections); "seq": (L N, E) and (S N, E)
     (nn.MultiheadAttention with batch_first=False).  S defaults to L, scale to d ** -0.5.  Returns out, shaped like q
-    (a new tensor when out is None).  No host synchronisation."""
+    (a new tensor when out is None).  No host synchronisation.
+    mask / key_bias / causal (qe_attention_masked): the score becomes scale q.k + mask + key_bias, keys s <= t only under
+    causal (top-left aligned).  mask: contiguous fp32, additive (finite or -inf), of shape (L, S), (N, L, S), (N, H, L, S) or
+    (N*H, L, S); key_bias: contiguous fp32 (N, S).  A row with no visible key comes out NaN."""
     import torch
     S = L if S is None else int(S)
     N, L, H = int(N), int(L), int(H)
@@ -647,6 +663,29 @@ def attention(q, k, v, N, L, H, S=None, layout="token", scale=None, out=None, st
     if out is None:
         out = torch.empty_like(q)
     assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == q.numel()
-    check(lib().qe_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), N, L, S, H, d, q_rn, q_rt, kv_rn, kv_rt,
-                             q_rn, q_rt, float(d ** -0.5 if scale is None else scale), _stream(stream)))
+    scale = float(d ** -0.5 if scale is None else scale)
+    if mask is None and key_bias is None and not causal:
+        check(lib().qe_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), N, L, S, H, d, q_rn, q_rt, kv_rn,
+                                 kv_rt, q_rn, q_rt, scale, _stream(stream)))
+        return out
+    mask_sn = mask_sh = 0
+    if mask is not None:
+        if not (torch.is_tensor(mask) and mask.is_cuda and mask.is_contiguous() and mask.dtype == torch.float32):
+            raise ValueError("mask must be a contiguous fp32 CUDA tensor (additive: finite or -inf)")
+        shape = tuple(mask.shape)
+        if shape == (L, S):
+            pass
+        elif shape == (N, H, L, S) or shape == (N * H, L, S):
+            mask_sn, mask_sh = H * L * S, L * S
+        elif shape == (N, L, S):
+            mask_sn = L * S
+        else:
+            raise ValueError("mask must be (L, S), (N, L, S), (N, H, L, S) or (N*H, L, S); got %s" % (shape,))
+    if key_bias is not None:
+        if not (torch.is_tensor(key_bias) and key_bias.is_cuda and key_bias.is_contiguous()
+                and key_bias.dtype == torch.float32 and tuple(key_bias.shape) == (N, S)):
+            raise ValueError("key_bias must be a contiguous fp32 CUDA tensor of shape (N, S)")
+    check(lib().qe_attention_masked(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), N, L, S, H, d, q_rn, q_rt, kv_rn,
+                                    kv_rt, q_rn, q_rt, scale, None if mask is None else mask.data_ptr(), mask_sn, mask_sh,
+                                    None if key_bias is None else key_bias.data_ptr(), 1 if causal else 0, _stream(stream)))
     return out

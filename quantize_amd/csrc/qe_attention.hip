@@ -24,6 +24,15 @@
 // near the max; products P.V and the row sum in fp32; one division by the row sum at the end.
 // Non-finite inputs: fmaxf skips a NaN score, and exp2f(NaN) = NaN reaches that row's sum and output: a NaN in a query
 // row poisons that row of that head only, a NaN in a key or value row that (image, head) only.
+//
+// Masked form (qe_attention_masked): the score becomes scale q.k + mask[n, h, t, s] + key_bias[n, s], restricted to
+// s <= t under `causal`.  Which operands exist is the template parameter MODE of both kernels (kMask | kBias | kCausal,
+// plus kVec4 where every mask / bias run of four keys is 16-byte aligned), never a branch in the tile loop: MODE 0 is the
+// unmasked kernel, instruction for instruction.  In the MFMA kernel a lane's 16 scores are four runs of four consecutive
+// keys of ONE query row, so the mask adds lane-locally; its loads are issued with the K prefetch, a tile ahead.  Causal
+// waves stop at the diagonal tile (the tiles above it are never loaded) and mask that tile by index.  While a row's
+// running max is still -inf (every key so far masked) the rescale factor is 1 and p is 0, so a later visible key starts
+// the row cleanly; a row with no visible key at all ends as 0 / 0 = NaN, that row of that head only.
 #include "qe_common.h"
 
 #include <algorithm>
@@ -38,15 +47,21 @@ struct AttnArgs {
     int N, L, S, H, d;
     int qgroups;                                     // workgroups per (image, head)
     float scale;
+    const float *mask, *key_bias;                    // masked instances only (MODE != 0)
+    int64_t mask_sn, mask_sh;                        // element strides of the (L, S) mask block per image / head
 };
+
+enum : int { kMask = 1, kBias = 2, kCausal = 4, kVec4 = 8 };
 
 constexpr float kLog2e = 1.4426950408889634f;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-template <int D>
+template <int D, int MODE = 0>
 __global__ __launch_bounds__(D <= 64 ? 512 : 256) void attn_mfma_kernel(const AttnArgs a)
 {
+    constexpr bool MASK = (MODE & kMask) != 0, BIAS = (MODE & kBias) != 0, CAUSAL = (MODE & kCausal) != 0;
+    constexpr bool VEC4 = (MODE & kVec4) != 0;
     constexpr int HALF = D / 2;                 // k-steps of S^T; dims [h*HALF, h*HALF + HALF) on lane half h
     constexpr int NB = (D + 31) / 32;           // 32-column blocks of O^T
     constexpr int WPB = D <= 64 ? 8 : 4;
@@ -83,8 +98,44 @@ __global__ __launch_bounds__(D <= 64 ? 512 : 256) void attn_mfma_kernel(const At
     const float *vbase = a.v + n * a.kv_rn * E + col;
     const int64_t kv_step = a.kv_rt * E;
 
+    // additive operands of a tile, in the score accumulator's own order: ar[r] belongs to key crow(r, hi) of query q0 + lo
+    const float *mrow = nullptr, *brow = nullptr;
+    if constexpr (MASK) mrow = a.mask + n * a.mask_sn + h * a.mask_sh + (int64_t)(q0 + lo < a.L ? q0 + lo : 0) * a.S;
+    if constexpr (BIAS) brow = a.key_bias + (int64_t)n * a.S;
+    float ar[(MASK || BIAS) ? 16 : 1];
+    auto load_add = [&](int k0) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int key = k0 + 8 * g + 4 * hi;
+            if constexpr (VEC4) {                   // S % 4 == 0: a run lies wholly below S or wholly beyond it
+                float4 x = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (key < a.S) {
+                    if constexpr (MASK) x = *reinterpret_cast<const float4 *>(mrow + key);
+                    if constexpr (BIAS) {
+                        const float4 y = *reinterpret_cast<const float4 *>(brow + key);
+                        if constexpr (MASK) { x.x += y.x; x.y += y.y; x.z += y.z; x.w += y.w; } else x = y;
+                    }
+                }
+                ar[4 * g] = x.x; ar[4 * g + 1] = x.y; ar[4 * g + 2] = x.z; ar[4 * g + 3] = x.w;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float x = 0.0f;
+                    if (key + j < a.S) {
+                        if constexpr (MASK) x = mrow[key + j];
+                        if constexpr (BIAS) { if constexpr (MASK) x += brow[key + j]; else x = brow[key + j]; }
+                    }
+                    ar[4 * g + j] = x;
+                }
+            }
+        }
+    };
+    // causal: the last tile that holds a key <= q0 + 31 is the wave's diagonal tile; the tiles above it are not visited
+    const int kend = CAUSAL ? min(a.S, q0 + 32) : a.S;
+
     float kr[HALF];
     auto load_k = [&](int k0) {
+        if constexpr (MASK || BIAS) load_add(k0);
         const int key = k0 + lo;
         if (key < a.S) {
             const float4 *src = reinterpret_cast<const float4 *>(kbase + key * kv_step + hi * HALF);
@@ -107,7 +158,7 @@ __global__ __launch_bounds__(D <= 64 ? 512 : 256) void attn_mfma_kernel(const At
     float m = -INFINITY, lsum = 0.0f;
 
     load_k(0);
-    for (int k0 = 0; k0 < a.S; k0 += 32) {
+    for (int k0 = 0; k0 < kend; k0 += 32) {
         // V^T operand of this tile: vr[s][b] = v[key k0 + crow(s, hi)][32 b + lo]
         float vr[16][NB];
 #pragma unroll
@@ -125,7 +176,11 @@ __global__ __launch_bounds__(D <= 64 ? 512 : 256) void attn_mfma_kernel(const At
         for (int r = 0; r < 16; ++r) sc[r] = 0.0f;
 #pragma unroll
         for (int s = 0; s < HALF; ++s) sc = __builtin_amdgcn_mfma_f32_32x32x2f32(kr[s], qr[s], sc, 0, 0, 0);
-        if (k0 + 32 < a.S) load_k(k0 + 32);
+        if constexpr (MASK || BIAS) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) sc[r] += ar[r];
+        }
+        if (k0 + 32 < kend) load_k(k0 + 32);
 
         // online softmax over this tile's 32 keys of query q0 + lo
         float tmax = -INFINITY;
@@ -133,16 +188,21 @@ __global__ __launch_bounds__(D <= 64 ? 512 : 256) void attn_mfma_kernel(const At
         for (int r = 0; r < 16; ++r) {
             const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
             if (key >= a.S) sc[r] = -INFINITY;
+            if constexpr (CAUSAL) { if (key > q0 + lo) sc[r] = -INFINITY; }
             tmax = fmaxf(tmax, sc[r]);
         }
         tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
         const float mn = fmaxf(m, tmax);
-        const float alpha = exp2f((m - mn) * kLog2e);
+        float alpha = exp2f((m - mn) * kLog2e);
+        float msub = mn;
+        if constexpr (MASK || BIAS) {              // every key so far masked: -inf - -inf is NaN; keep the empty state
+            if (mn == -INFINITY) { alpha = 1.0f; msub = 0.0f; }
+        }
         m = mn;
         float psum = 0.0f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            sc[r] = exp2f((sc[r] - mn) * kLog2e);
+            sc[r] = exp2f((sc[r] - msub) * kLog2e);
             psum += sc[r];
         }
         lsum = lsum * alpha + psum;
@@ -185,9 +245,10 @@ __device__ __forceinline__ float wave_sum(float v)
     return v;
 }
 
-template <int NO>
+template <int NO, int MODE = 0>
 __global__ __launch_bounds__(256) void attn_valu_kernel(const AttnArgs a)
 {
+    constexpr bool MASK = (MODE & kMask) != 0, BIAS = (MODE & kBias) != 0, CAUSAL = (MODE & kCausal) != 0;
     __shared__ float qs[4][NO * 64];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -214,22 +275,32 @@ __global__ __launch_bounds__(256) void attn_valu_kernel(const AttnArgs a)
 #pragma unroll
     for (int i = 0; i < NO; ++i) o[i] = 0.0f;
     float m = -INFINITY, l = 0.0f;
-    for (int k0 = 0; k0 < a.S; k0 += 64) {
+    const float *mrow = nullptr, *brow = nullptr;
+    if constexpr (MASK) mrow = a.mask + n * a.mask_sn + h * a.mask_sh + (int64_t)t * a.S;
+    if constexpr (BIAS) brow = a.key_bias + (int64_t)n * a.S;
+    const int kend = CAUSAL ? min(a.S, t + 1) : a.S;           // causal: keys above the diagonal are not visited
+    for (int k0 = 0; k0 < kend; k0 += 64) {
         const int key = k0 + lane;
         float s = -INFINITY;
-        if (key < a.S) {
+        if (key < kend) {
             const float *kr = kbase + key * kv_step;
             s = 0.0f;
             for (int c = 0; c < a.d; ++c) s = fmaf(qs[wave][c], kr[c], s);
+            if constexpr (MASK) s += mrow[key];
+            if constexpr (BIAS) s += brow[key];
         }
         const float mn = fmaxf(m, wave_max(s));
-        const float alpha = exp2f((m - mn) * kLog2e);
+        float alpha = exp2f((m - mn) * kLog2e);
+        float msub = mn;
+        if constexpr (MASK || BIAS) {              // every key so far masked: keep the empty state (see the MFMA kernel)
+            if (mn == -INFINITY) { alpha = 1.0f; msub = 0.0f; }
+        }
         m = mn;
-        const float p = key < a.S ? exp2f((s - mn) * kLog2e) : 0.0f;
+        const float p = key < kend ? exp2f((s - msub) * kLog2e) : 0.0f;
         l = l * alpha + wave_sum(p);
 #pragma unroll
         for (int i = 0; i < NO; ++i) o[i] *= alpha;
-        const int nk = min(64, a.S - k0);
+        const int nk = min(64, kend - k0);
         for (int j = 0; j < nk; ++j) {
             const float pj = __shfl(p, j);
             const float *vr = vbase + (k0 + j) * kv_step;
@@ -256,7 +327,7 @@ static int attn_path(int L, int S, int H, int d)
     return 1;
 }
 
-template <int D>
+template <int D, int MODE>
 static void launch_mfma(const AttnArgs &a, hipStream_t s)
 {
     constexpr int WPB = D <= 64 ? 8 : 4;
@@ -265,14 +336,38 @@ static void launch_mfma(const AttnArgs &a, hipStream_t s)
     const int wpb = std::min(WPB, tiles);        // a short sequence launches only the waves it has rows for
     b.qgroups = ceil_div(tiles, WPB);
     const int64_t blocks = (int64_t)b.qgroups * a.H * a.N;
-    hipLaunchKernelGGL(attn_mfma_kernel<D>, dim3((unsigned)blocks), dim3(64 * (b.qgroups == 1 ? wpb : WPB)), 0, s, b);
+    hipLaunchKernelGGL((attn_mfma_kernel<D, MODE>), dim3((unsigned)blocks), dim3(64 * (b.qgroups == 1 ? wpb : WPB)), 0, s, b);
 }
 
-template <int NO>
+template <int NO, int MODE>
 static void launch_valu(const AttnArgs &a, hipStream_t s)
 {
     const int64_t blocks = ceil_div64((int64_t)a.N * a.H * a.L, 4);
-    hipLaunchKernelGGL(attn_valu_kernel<NO>, dim3((unsigned)blocks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((attn_valu_kernel<NO, MODE>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+}
+
+template <int MODE>
+static void launch_mode(const AttnArgs &a, int path, hipStream_t s)
+{
+    if (path == 1) {
+        switch (a.d) {
+        case 16: launch_mfma<16, MODE>(a, s); break;
+        case 32: launch_mfma<32, MODE>(a, s); break;
+        case 48: launch_mfma<48, MODE>(a, s); break;
+        case 64: launch_mfma<64, MODE>(a, s); break;
+        case 80: launch_mfma<80, MODE>(a, s); break;
+        case 96: launch_mfma<96, MODE>(a, s); break;
+        case 112: launch_mfma<112, MODE>(a, s); break;
+        default: launch_mfma<128, MODE>(a, s); break;
+        }
+    } else {
+        constexpr int VM = MODE & ~kVec4;        // the VALU kernel reads one float per lane: no 16-byte form
+        const int no = ceil_div(a.d, 64);
+        if (no == 1) launch_valu<1, VM>(a, s);
+        else if (no == 2) launch_valu<2, VM>(a, s);
+        else if (no == 3) launch_valu<3, VM>(a, s);
+        else launch_valu<4, VM>(a, s);
+    }
 }
 
 // [lo, hi) byte range the rows of (n < N, t < T) span
@@ -283,24 +378,19 @@ static void row_span(const float *p, int N, int T, int64_t rn, int64_t rt, int64
     hi = lo + (uintptr_t)((last + 1) * E) * sizeof(float);
 }
 
-}  // namespace qe
-
-extern "C" int qe_attention_path(int32_t L, int32_t S, int32_t H, int32_t d)
+static int attn_run(const float *q, const float *k, const float *v, float *out, int32_t N, int32_t L, int32_t S, int32_t H,
+                    int32_t d, int64_t q_rn, int64_t q_rt, int64_t kv_rn, int64_t kv_rt, int64_t o_rn, int64_t o_rt, float scale,
+                    const float *mask, int64_t mask_sn, int64_t mask_sh, const float *key_bias, int causal, qe_stream_t stream)
 {
-    return qe::attn_path(L, S, H, d);
-}
-
-extern "C" int qe_attention(const float *q, const float *k, const float *v, float *out, int32_t N, int32_t L, int32_t S,
-                            int32_t H, int32_t d, int64_t q_rn, int64_t q_rt, int64_t kv_rn, int64_t kv_rt, int64_t o_rn,
-                            int64_t o_rt, float scale, qe_stream_t stream)
-{
-    using namespace qe;
     if (N <= 0 || L <= 0 || S <= 0 || H <= 0 || d <= 0) return QE_ERR_ARG;
     if (q_rn < 0 || q_rt < 0 || kv_rn < 0 || kv_rt < 0 || o_rn < 0 || o_rt < 0) return QE_ERR_ARG;
     if (q == nullptr || k == nullptr || v == nullptr || out == nullptr) return QE_ERR_ARG;
     if (((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
           reinterpret_cast<uintptr_t>(out)) & 15) != 0)
         return QE_ERR_ARG;
+    if (mask_sn < 0 || mask_sh < 0) return QE_ERR_ARG;
+    if (mask == nullptr && (mask_sn != 0 || mask_sh != 0)) return QE_ERR_ARG;
+    if (((reinterpret_cast<uintptr_t>(mask) | reinterpret_cast<uintptr_t>(key_bias)) & 15) != 0) return QE_ERR_ARG;
     const int path = attn_path(L, S, H, d);
     if (path < 0) return QE_ERR_UNSUPPORTED;
     const int64_t E = (int64_t)H * d;
@@ -314,31 +404,74 @@ extern "C" int qe_attention(const float *q, const float *k, const float *v, floa
         row_span(ins[i], N, len[i], rn[i], rt[i], E, lo, hi);
         if (lo < ohi && olo < hi) return QE_ERR_ARG;
     }
+    if (mask != nullptr) {                       // the (L, S) blocks of (n < N, h < H) span up to this many floats
+        const uintptr_t lo = reinterpret_cast<uintptr_t>(mask);
+        const uintptr_t hi = lo + (uintptr_t)((N - 1) * mask_sn + (H - 1) * mask_sh + (int64_t)L * S) * sizeof(float);
+        if (lo < ohi && olo < hi) return QE_ERR_ARG;
+    }
+    if (key_bias != nullptr) {
+        const uintptr_t lo = reinterpret_cast<uintptr_t>(key_bias);
+        const uintptr_t hi = lo + (uintptr_t)((int64_t)N * S) * sizeof(float);
+        if (lo < ohi && olo < hi) return QE_ERR_ARG;
+    }
     const int64_t rows = (int64_t)N * H * L;
     if ((int64_t)N * H * ceil_div(L, 32) > 0x7fffffffLL || ceil_div64(rows, 4) > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
     AttnArgs a = {};
     a.q = q; a.k = k; a.v = v; a.out = out;
     a.q_rn = q_rn; a.q_rt = q_rt; a.kv_rn = kv_rn; a.kv_rt = kv_rt; a.o_rn = o_rn; a.o_rt = o_rt;
     a.N = N; a.L = L; a.S = S; a.H = H; a.d = d; a.scale = scale;
+    a.mask = mask; a.key_bias = key_bias; a.mask_sn = mask_sn; a.mask_sh = mask_sh;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (path == 1) {
-        switch (d) {
-        case 16: launch_mfma<16>(a, s); break;
-        case 32: launch_mfma<32>(a, s); break;
-        case 48: launch_mfma<48>(a, s); break;
-        case 64: launch_mfma<64>(a, s); break;
-        case 80: launch_mfma<80>(a, s); break;
-        case 96: launch_mfma<96>(a, s); break;
-        case 112: launch_mfma<112>(a, s); break;
-        default: launch_mfma<128>(a, s); break;
-        }
-    } else {
-        const int no = ceil_div(d, 64);
-        if (no == 1) launch_valu<1>(a, s);
-        else if (no == 2) launch_valu<2>(a, s);
-        else if (no == 3) launch_valu<3>(a, s);
-        else launch_valu<4>(a, s);
+    int mode = (mask != nullptr ? kMask : 0) | (key_bias != nullptr ? kBias : 0) | (causal ? kCausal : 0);
+    // every run of four keys a lane reads starts at a multiple of four floats from a 16-byte aligned base
+    if ((mode & (kMask | kBias)) != 0 && S % 4 == 0 && mask_sn % 4 == 0 && mask_sh % 4 == 0) mode |= kVec4;
+    switch (mode) {
+    case 0: launch_mode<0>(a, path, s); break;
+    case kMask: launch_mode<kMask>(a, path, s); break;
+    case kBias: launch_mode<kBias>(a, path, s); break;
+    case kMask | kBias: launch_mode<kMask | kBias>(a, path, s); break;
+    case kCausal: launch_mode<kCausal>(a, path, s); break;
+    case kCausal | kMask: launch_mode<kCausal | kMask>(a, path, s); break;
+    case kCausal | kBias: launch_mode<kCausal | kBias>(a, path, s); break;
+    case kCausal | kMask | kBias: launch_mode<kCausal | kMask | kBias>(a, path, s); break;
+    case kVec4 | kMask: launch_mode<kVec4 | kMask>(a, path, s); break;
+    case kVec4 | kBias: launch_mode<kVec4 | kBias>(a, path, s); break;
+    case kVec4 | kMask | kBias: launch_mode<kVec4 | kMask | kBias>(a, path, s); break;
+    case kVec4 | kCausal | kMask: launch_mode<kVec4 | kCausal | kMask>(a, path, s); break;
+    case kVec4 | kCausal | kBias: launch_mode<kVec4 | kCausal | kBias>(a, path, s); break;
+    default: launch_mode<kVec4 | kCausal | kMask | kBias>(a, path, s); break;
     }
     QE_LAUNCH_CHECK();
     return QE_OK;
+}
+
+}  // namespace qe
+
+extern "C" int qe_attention_path(int32_t L, int32_t S, int32_t H, int32_t d)
+{
+    return qe::attn_path(L, S, H, d);
+}
+
+// the operands choose the kernel's instance, not the kernel: the answer is qe_attention_path's for every combination
+extern "C" int qe_attention_masked_path(int32_t L, int32_t S, int32_t H, int32_t d, int has_mask, int has_key_bias, int causal)
+{
+    (void)has_mask; (void)has_key_bias; (void)causal;
+    return qe::attn_path(L, S, H, d);
+}
+
+extern "C" int qe_attention(const float *q, const float *k, const float *v, float *out, int32_t N, int32_t L, int32_t S,
+                            int32_t H, int32_t d, int64_t q_rn, int64_t q_rt, int64_t kv_rn, int64_t kv_rt, int64_t o_rn,
+                            int64_t o_rt, float scale, qe_stream_t stream)
+{
+    return qe::attn_run(q, k, v, out, N, L, S, H, d, q_rn, q_rt, kv_rn, kv_rt, o_rn, o_rt, scale, nullptr, 0, 0, nullptr, 0,
+                        stream);
+}
+
+extern "C" int qe_attention_masked(const float *q, const float *k, const float *v, float *out, int32_t N, int32_t L, int32_t S,
+                                   int32_t H, int32_t d, int64_t q_rn, int64_t q_rt, int64_t kv_rn, int64_t kv_rt,
+                                   int64_t o_rn, int64_t o_rt, float scale, const float *mask, int64_t mask_sn,
+                                   int64_t mask_sh, const float *key_bias, int causal, qe_stream_t stream)
+{
+    return qe::attn_run(q, k, v, out, N, L, S, H, d, q_rn, q_rt, kv_rn, kv_rt, o_rn, o_rt, scale, mask, mask_sn, mask_sh,
+                        key_bias, causal, stream);
 }

@@ -192,7 +192,7 @@ class PackedMultiheadAttention:
     zero,des} beside them and one activation quantiser per input (:165-223); the reference's packed forward dequantises
     all four and calls F.multi_head_attention_forward.  Here the three input projections run as packed linears (either
     route of PackedLinear, each with its own activation quantiser and its slice of in_proj_bias), the attention core
-    softmax(Q K^T / sqrt(d)) V stays fp32 torch as in the reference, and out_proj -- whose input has no quantiser in the
+    softmax(Q K^T / sqrt(d) + masks) V stays fp32 as in the reference (torch, or the engine core), and out_proj -- whose input has no quantiser in the
     reference -- takes the fp32 x packed-weight operator (quantlinear_float_input).  Inputs are (L, N, E) / (S, N, kdim)
     (batch_first=False, the module's default); returns (attn_output, averaged attention weights or None)."""
 
@@ -227,27 +227,74 @@ class PackedMultiheadAttention:
                 setattr(self, name, val.to(device))
         return self
 
-    def __call__(self, query, key, value, route="packed", need_weights=True, attention="torch"):
+    @staticmethod
+    def _additive_masks(attn_mask, key_padding_mask, N, H, L, S):
+        """nn.MultiheadAttention's mask arguments, validated, as additive fp32: attn_mask (L, S) or (N*H, L, S),
+        key_padding_mask (N, S); bool True = masked -> -inf, float as given."""
+        if key_padding_mask is not None:
+            if key_padding_mask.dtype != torch.bool and not torch.is_floating_point(key_padding_mask):
+                raise AssertionError("only bool and floating types of key_padding_mask are supported")
+            if tuple(key_padding_mask.shape) != (N, S):
+                raise ValueError("key_padding_mask must be (N, S) = %s; got %s" % ((N, S), tuple(key_padding_mask.shape)))
+        if attn_mask is not None:
+            if attn_mask.dtype != torch.bool and not torch.is_floating_point(attn_mask):
+                raise ValueError("only bool and floating types of attn_mask are supported")
+            if tuple(attn_mask.shape) not in ((L, S), (N * H, L, S)):
+                raise ValueError("attn_mask must be (L, S) = %s or (N*H, L, S) = %s; got %s"
+                                 % ((L, S), (N * H, L, S), tuple(attn_mask.shape)))
+
+        def additive(m):
+            if m is None:
+                return None
+            if m.dtype == torch.bool:
+                return torch.zeros(m.shape, dtype=torch.float32, device=m.device).masked_fill_(m, float("-inf"))
+            return m.to(torch.float32).contiguous()
+        return additive(attn_mask), additive(key_padding_mask)
+
+    def __call__(self, query, key, value, route="packed", need_weights=True, attention="torch", attn_mask=None,
+                 key_padding_mask=None, is_causal=False):
         """attention="torch": the core as torch bmm / softmax / bmm (the reference's own arithmetic).  "engine": the fp32
         qe_attention kernel reads the three projections in their (L N, E) / (S N, E) layout and writes the context in
-        place for out_proj -- no score matrix, so need_weights must be False."""
+        place for out_proj -- no score matrix, so need_weights must be False.
+        attn_mask ((L, S) or (N*H, L, S)) and key_padding_mask ((N, S)) follow nn.MultiheadAttention: bool (True = not
+        allowed / ignored key) or float (added to the scores).  is_causal=True without attn_mask is the top-left aligned
+        tril mask.  The engine core takes attn_mask with its broadcast strides and key_padding_mask as a key bias row:
+        no merged (N, H, L, S) tensor.  A row with no visible key is NaN in both cores."""
         if attention not in ("torch", "engine"):
             raise ValueError("attention must be 'torch' or 'engine'")
         L, N, E = query.shape
         S = key.shape[0]
         H, d = self.num_heads, E // self.num_heads
+        masked = attn_mask is not None or key_padding_mask is not None or is_causal
+        if masked:
+            attn_mask, key_padding_mask = self._additive_masks(attn_mask, key_padding_mask, N, H, L, S)
         if attention == "engine":
             if need_weights:
                 raise ValueError("attention='engine' materialises no attention weights: pass need_weights=False")
             from . import capi
             Q, K, V = (p(x, route).reshape(-1, E).contiguous() for p, x in ((self.q, query), (self.k, key), (self.v, value)))
-            ctx = capi.attention(Q, K, V, N, L, H, S=S, layout="seq")
+            if masked:
+                ctx = capi.attention(Q, K, V, N, L, H, S=S, layout="seq", mask=attn_mask, key_bias=key_padding_mask,
+                                     causal=bool(is_causal) and attn_mask is None)
+            else:
+                ctx = capi.attention(Q, K, V, N, L, H, S=S, layout="seq")
             out = quantlinear_forward(ctx, (self.out_weight, self.out_des, self.out_scale, self._neg_out_zero), self.out_bias)
             return out.reshape(L, N, E), None
         Q = self.q(query, route).reshape(L, N * H, d).transpose(0, 1)      # (N H, L, d), as F.multi_head_attention_forward splits heads
         K = self.k(key, route).reshape(S, N * H, d).transpose(0, 1)
         V = self.v(value, route).reshape(S, N * H, d).transpose(0, 1)
-        attn = torch.softmax(torch.bmm(Q * (float(d) ** -0.5), K.transpose(1, 2)), dim=-1)
+        if masked:
+            scores = torch.bmm(Q * (float(d) ** -0.5), K.transpose(1, 2))
+            if attn_mask is None and is_causal:
+                attn_mask = torch.zeros(L, S, dtype=torch.float32, device=scores.device).masked_fill_(
+                    torch.ones(L, S, dtype=torch.bool, device=scores.device).tril().logical_not(), float("-inf"))
+            if attn_mask is not None:
+                scores = scores + attn_mask
+            if key_padding_mask is not None:
+                scores = (scores.view(N, H, L, S) + key_padding_mask.view(N, 1, 1, S)).view(N * H, L, S)
+            attn = torch.softmax(scores, dim=-1)
+        else:
+            attn = torch.softmax(torch.bmm(Q * (float(d) ** -0.5), K.transpose(1, 2)), dim=-1)
         ctx = torch.bmm(attn, V).transpose(0, 1).reshape(L * N, E).contiguous()
         out = quantlinear_forward(ctx, (self.out_weight, self.out_des, self.out_scale, self._neg_out_zero), self.out_bias)
         return out.reshape(L, N, E), (attn.reshape(N, H, L, S).mean(dim=1) if need_weights else None)

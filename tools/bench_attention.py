@@ -4,7 +4,11 @@
 passes it.  The two alternate step by step, timed with device events after a warm-up; medians are reported.
 Useful TFLOP/s counts 4 N H L S d (QK^T and PV, padding not counted); `of_peak` is the share of the 157.3 TFLOP/s fp32
 matrix-pipe peak.  Prints one JSON line.
-usage: python tools/bench_attention.py [--steps 20] [--warmup 3] [--batches 64 256]"""
+--mask gives both the same mask: `causal` (the engine's flag, torch's is_causal), `causal-additive` (the -inf tril as an
+(L, L) float mask), `additive2d` (a finite (L, L) float mask), `padding` (ragged key padding: the engine reads an (N, L) key
+bias, torch the merged (N, 1, 1, L) mask it would build itself).  The FLOP count stays the unmasked one, so a causal row's
+TFLOP/s is an equivalent rate, not work done.
+usage: python tools/bench_attention.py [--steps 20] [--warmup 3] [--batches 64 256] [--mask none] [--shapes clip_text ...]"""
 import argparse
 import json
 import os
@@ -13,7 +17,9 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 PEAK_TF = 157.3
-SHAPES = {"vit_b_16": (197, 12, 64), "vit_l_16": (197, 16, 64), "vit_h_14": (257, 16, 80), "vit_b_32": (50, 12, 64)}
+SHAPES = {"vit_b_16": (197, 12, 64), "vit_l_16": (197, 16, 64), "vit_h_14": (257, 16, 80), "vit_b_32": (50, 12, 64),
+          "clip_text": (77, 8, 64)}
+MASKS = ["none", "causal", "causal-additive", "additive2d", "padding"]
 
 
 def main():
@@ -21,14 +27,18 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batches", type=int, nargs="+", default=[64, 256])
+    ap.add_argument("--mask", choices=MASKS, default="none")
+    ap.add_argument("--shapes", nargs="+", choices=list(SHAPES), default=list(SHAPES))
     args = ap.parse_args()
     import torch
     import torch.nn.functional as F
     from quantize_amd import capi
 
     dev = "cuda:0"
-    res = {"metric": "attention_core_fp32", "unit": "ms", "peak_tflops": PEAK_TF, "path": {}, "shapes": {}}
-    for name, (L, H, d) in SHAPES.items():
+    res = {"metric": "attention_core_fp32", "unit": "ms", "peak_tflops": PEAK_TF, "mask": args.mask, "path": {},
+           "shapes": {}}
+    for name in args.shapes:
+        L, H, d = SHAPES[name]
         res["path"][name] = capi.attention_path(L, L, H, d)
         for N in args.batches:
             E = H * d
@@ -36,6 +46,19 @@ def main():
             q, k, v = (torch.randn(N * L, E, generator=g).to(dev) for _ in range(3))
             out = torch.empty_like(q)
             views = [t.view(N, L, H, d).transpose(1, 2) for t in (q, k, v)]
+            ekw, tkw = {}, {}
+            if args.mask == "causal":
+                ekw, tkw = dict(causal=True), dict(is_causal=True)
+            elif args.mask in ("causal-additive", "additive2d"):
+                if args.mask == "additive2d":
+                    m = (2.0 * torch.randn(L, L, generator=g)).to(dev)
+                else:
+                    m = torch.full((L, L), float("-inf")).triu_(1).to(dev)
+                ekw, tkw = dict(mask=m), dict(attn_mask=m)
+            elif args.mask == "padding":
+                lengths = torch.randint(L // 2, L + 1, (N,), generator=g)
+                kb = torch.zeros(N, L).masked_fill_(torch.arange(L)[None, :] >= lengths[:, None], float("-inf")).to(dev)
+                ekw, tkw = dict(key_bias=kb), dict(attn_mask=kb.view(N, 1, 1, L))
             times = {"engine": [], "torch": []}
             with torch.no_grad():
                 for i in range(args.warmup + args.steps):
@@ -43,9 +66,9 @@ def main():
                         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                         a.record()
                         if who == "engine":
-                            capi.attention(q, k, v, N, L, H, out=out)
+                            capi.attention(q, k, v, N, L, H, out=out, **ekw)
                         else:
-                            ref = F.scaled_dot_product_attention(*views)
+                            ref = F.scaled_dot_product_attention(*views, **tkw)
                         b.record()
                         torch.cuda.synchronize()
                         if i >= args.warmup:
