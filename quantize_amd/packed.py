@@ -19,43 +19,101 @@ Two routes per layer, as the operator's dtype dispatch offers them (quantconv2do
   route="float"   the form the reference's TODO names first ("only support float input and packed weight"): the
                   fake-quantised fp32 activations (q + zero) * scale with the packed weights.
 """
+import functools
+
 import torch
 
-from . import engine
+from . import capi, engine
 from .operator import quantconv2d_forward, quantlinear_forward
+
+OUT_OF_RANGE = "The input tensor is out of range."    # tpack.cu:14, as engine.tpack raises it
 
 
 def _first(v):
     return int(v[0]) if isinstance(v, (tuple, list)) else int(v)
 
 
+def quantizer_bits(qmin, qmax):
+    """(n_bits, signed) of a quantiser whose codes span [qmin, qmax]."""
+    qmin, qmax = float(qmin), float(qmax)
+    return max(1, int(round(qmax - qmin)).bit_length()), qmin < 0
+
+
+def _host_des(des):
+    """A (packed, des) pair's description as host integers: one device -> host read when it is a tensor."""
+    return [int(v) for v in (des.tolist() if torch.is_tensor(des) else des)]
+
+
 class _PackedBase:
-    def __init__(self, weight, w_des, w_scale, w_zero, bias, a_scale, a_zero, a_qmin, a_qmax, a_bits, a_signed):
+    LINEAR = False      # True: the layer's own op is the packed x packed quantlinear, which takes (q + zero)
+
+    def __init__(self, weight, w_des, w_scale, w_zero, bias, a_scale, a_zero, a_qmin, a_qmax, a_bits, a_signed, name=None):
         assert weight.dtype == torch.uint8 and weight.dim() == 1, "weight must be the packed 1-D uint8 stream pack() stores"
-        self.weight, self.w_des, self.bias = weight, w_des, bias
+        self.weight, self.w_des, self.bias, self.name = weight, w_des, bias, name
+        # parsed once, here, where the state_dict tensors normally still live on the host
+        wd = [int(v) for v in w_des.tolist()]
+        self.w_bits, self.w_signed, self.w_shape = wd[0], bool(wd[1]), wd[2:]
         self.w_scale, self.w_zero = w_scale.contiguous(), w_zero.contiguous()            # module convention (q + zero)
-        self.a_scale = a_scale.reshape(-1).contiguous().float()
-        self.a_zero = a_zero.reshape(-1).contiguous().float()
+        self._neg_w_zero = (-self.w_zero).contiguous()       # kernel convention, built once (tensors stay alive: cache keys)
         self.a_qmin, self.a_qmax = float(a_qmin), float(a_qmax)
         self.a_bits, self.a_signed = int(a_bits), bool(a_signed)
-        self._neg_w_zero = (-self.w_zero).contiguous()       # kernel convention, built once (tensors stay alive: cache keys)
-        self._neg_a_zero = (-self.a_zero).contiguous()
+        self._set_quantizer(a_scale, a_zero)
 
     @classmethod
     def _state(cls, sd, prefix):
         g = lambda k: sd[prefix + k]
         qmin, qmax = float(g("a_quantizer.qmin")), float(g("a_quantizer.qmax"))
-        n_levels = int(round(qmax - qmin)) + 1
-        a_bits = max(1, (n_levels - 1).bit_length())
+        a_bits, a_signed = quantizer_bits(qmin, qmax)
         return dict(weight=g("weight"), w_des=g("w_des"), w_scale=g("w_scale"), w_zero=g("w_zero"),
                     bias=sd.get(prefix + "bias"), a_scale=g("a_quantizer.scale"), a_zero=g("a_quantizer.zero"),
-                    a_qmin=qmin, a_qmax=qmax, a_bits=a_bits, a_signed=qmin < 0)
+                    a_qmin=qmin, a_qmax=qmax, a_bits=a_bits, a_signed=a_signed, name=prefix.rstrip("."))
+
+    # ---- the activation quantiser: assigning a_scale or a_zero updates everything derived from them ----
+    a_scale = property(lambda self: self._a_scale, lambda self, v: self._set_quantizer(v, self._a_zero))
+    a_zero = property(lambda self: self._a_zero, lambda self, v: self._set_quantizer(self._a_scale, v))
+
+    def _set_quantizer(self, scale, zero):
+        self._a_scale = scale.reshape(-1).contiguous().float()
+        self._a_zero = zero.reshape(-1).contiguous().float()
+        self._neg_a_zero = (-self._a_zero).contiguous()
+        s, z = tuple(self._a_scale.tolist()), tuple(self._a_zero.tolist())
+        self.q_key = (s, z, self.a_qmin, self.a_qmax, self.a_bits, self.a_signed)      # two layers share codes when equal
+        # round(max(y, 0) / s - 0).clamp(0, qmax) == round(y / s).clamp(0, qmax): the producer's ReLU folds into the clamp
+        self.folds_relu = (not self.a_signed) and self.a_qmin == 0.0 and all(v == 0.0 for v in z) and all(v > 0.0 for v in s)
 
     def to(self, device):
         for k, v in list(vars(self).items()):
             if torch.is_tensor(v):
                 setattr(self, k, v.to(device))
         return self
+
+    # ---- operands of the C ABI.  The sign convention is decided here and nowhere else: the packed x packed quantlinear
+    # takes the module's (q + zero); the convs and the float-input operators take (q - zero) -> the negated zeros ----
+    def wq(self, linear=None):
+        """The packed weights as a capi.qparam for this layer's own op, or for the packed x packed quantlinear
+        (linear=True: a conv run as the GEMM it is)."""
+        zero = self.w_zero if (self.LINEAR if linear is None else linear) else self._neg_w_zero
+        return capi.qparam(self.weight, self.w_bits, self.w_signed, self.w_scale.reshape(-1), zero.reshape(-1))
+
+    def xq(self, codes, n_bits=None, signed=None, linear=None):
+        """A code stream of this layer's activation quantiser (or of n_bits / signed codes at its scale) as a capi.qparam."""
+        zero = self._a_zero if (self.LINEAR if linear is None else linear) else self._neg_a_zero
+        return capi.qparam(codes, self.a_bits if n_bits is None else n_bits, self.a_signed if signed is None else signed,
+                           self._a_scale, zero)
+
+    def requant(self):
+        """This layer's activation quantiser as a capi.requant, for the epilogue of the layer that feeds it."""
+        return capi.requant(self._a_scale, self._a_zero, self.a_qmin, self.a_qmax, self.a_bits, self.a_signed)
+
+    def quantize_codes(self, x, status):
+        """quantize() through the C ABI with no host synchronisation: the range flag accumulates in `status`.  Returns
+        (packed, des) with des on the host; x is (N, C, ...) with a per-channel quantiser's channels in dimension 1."""
+        inner = 1
+        for v in x.shape[2:]:
+            inner *= v
+        codes = capi.quantize_pack(x, self._a_scale, self._a_zero, self.a_qmin, self.a_qmax, self.a_bits, self.a_signed,
+                                   inner=inner, status=status)[0]
+        return codes, (self.a_bits, int(self.a_signed), *x.shape)
 
     def quantize(self, x, channel_dim=1):
         """Quantizer.simulate in packed mode (quantizer.py:215,226) fused with tpack: (packed, des)."""
@@ -80,10 +138,31 @@ class PackedConv2d(_PackedBase):
     def __init__(self, *, stride=1, padding=0, **state):
         super().__init__(**state)
         self.stride, self.padding = _first(stride), _first(padding)
+        self.OC, self.IC, self.KH, self.KW = self.w_shape
+        self._prep = {}
 
     @classmethod
     def from_state_dict(cls, state_dict, prefix="", stride=1, padding=0):
         return cls(stride=stride, padding=padding, **cls._state(state_dict, prefix))
+
+    def to(self, device):
+        self._prep = {}
+        return super().to(device)
+
+    def out_hw(self, H, W):
+        return ((H + 2 * self.padding - self.KH) // self.stride + 1, (W + 2 * self.padding - self.KW) // self.stride + 1)
+
+    def shape(self, N, H, W):
+        return capi.conv_shape(N, self.IC, H, W, self.OC, self.KH, self.KW, self.stride, self.padding)
+
+    def operands(self, codes, N, H, W, n_bits=None, signed=None):
+        """(qe_conv_shape, activation operand, weight operand, prepared weight tables) of this conv on `codes` of an
+        N x IC x H x W input.  The tables are prepared once per table layout (batch size does not enter)."""
+        sh, xq, wq = self.shape(N, H, W), self.xq(codes, n_bits, signed), self.wq()
+        key = (xq.n_bits, capi.conv_prepared_layout(sh, xq.n_bits, self.w_bits))
+        if key not in self._prep:
+            self._prep[key] = capi.conv_prepare(wq, self.bias, sh, xq.n_bits)
+        return sh, xq, wq, self._prep[key]
 
     def __call__(self, x, route="packed"):
         w = (self.weight, self.w_des, self.w_scale, self._neg_w_zero)
@@ -95,40 +174,38 @@ class PackedConv2d(_PackedBase):
             return quantconv2d_forward(self.fake_quant(x), w, self.bias, self.stride, self.padding, 1, 1)
         raise ValueError("route must be 'packed' or 'float'")
 
-
     # ---- packed in, packed out: the conv-epilogue form of f-2 ----
-    def call_packed(self, xq, x_des, consumer=None):
-        """Activations as (packed stream, des) -- what quantize() or an earlier call_packed() returned.
+    def call_packed(self, xq, x_des, consumer=None, status=None):
+        """Activations as (packed stream, des) -- what quantize(), quantize_codes() or an earlier call_packed() returned.
         consumer=None: the fp32 output.  consumer = the Packed* layer that reads this layer's output directly: returns the
         (packed, des) pair of ITS activation quantiser, written by this layer's conv kernel itself
         (qe_quantconv2d_requant_prepared): no fp32 tensor between the two layers.  Bit-identical to
         consumer.quantize(self.call_packed(xq, x_des)).  (A ReLU in between folds into the clamp when the consumer's codes
-        are unsigned with zero point 0: round(max(y, 0) / s).clamp(0, qmax) == round(y / s).clamp(0, qmax).)"""
-        from . import capi
-        d = [int(v) for v in x_des.tolist()]
-        n_bits, sign, (N, IC, H, W) = d[0], d[1], d[2:6]
-        wd = [int(v) for v in self.w_des.tolist()]
-        sh = capi.conv_shape(N, IC, H, W, wd[2], wd[4], wd[5], self.stride, self.padding)
-        x = capi.qparam(xq, n_bits, sign, self.a_scale, self._neg_a_zero)
-        w = capi.qparam(self.weight, wd[0], wd[1], self.w_scale.reshape(-1), self._neg_w_zero.reshape(-1))
-        key = (n_bits, capi.conv_prepared_layout(sh, n_bits, wd[0]))
-        if getattr(self, "_prep_key", None) != key:      # weights prepared once per table layout (batch size does not enter)
-            self._prepared, self._prep_key = capi.conv_prepare(w, self.bias, sh, n_bits), key
+        are unsigned with zero point 0: round(max(y, 0) / s).clamp(0, qmax) == round(y / s).clamp(0, qmax).)
+        status: a device int32 the range flag accumulates in; nothing is read back or copied, des comes back as host
+        integers.  None: raise when the codes are out of range."""
+        n_bits, sign, N, IC, H, W = _host_des(x_des)
+        if IC != self.IC:
+            raise ValueError("codes of %d channels for a conv of %d" % (IC, self.IC))
+        sh, x, w, prepared = self.operands(xq, N, H, W, n_bits, sign)
         if consumer is None:
-            return capi.quantconv2d_prepared(x, w, self.bias, sh, self._prepared)
-        rq = capi.requant(consumer.a_scale, consumer.a_zero, consumer.a_qmin, consumer.a_qmax, consumer.a_bits, consumer.a_signed)
-        out, status = capi.quantconv2d_requant_prepared(x, w, self.bias, sh, self._prepared, rq)
-        if int(status.item()) != 0:
-            raise RuntimeError("The input tensor is out of range.")     # tpack.cu:14, as engine.tpack raises it
-        OH, OW = capi.out_hw(sh)
-        des = torch.tensor([consumer.a_bits, 1 if consumer.a_signed else 0, N, sh.OC, OH, OW], dtype=torch.int32, device=xq.device)
-        return out, des
+            return capi.quantconv2d_prepared(x, w, self.bias, sh, prepared)
+        out, flag = capi.quantconv2d_requant_prepared(x, w, self.bias, sh, prepared, consumer.requant(), status=status)
+        if status is None and int(flag.item()) != 0:
+            raise RuntimeError(OUT_OF_RANGE)
+        des = (consumer.a_bits, int(consumer.a_signed), N, self.OC, *self.out_hw(H, W))
+        return out, (des if status is not None else torch.tensor(des, dtype=torch.int32, device=xq.device))
 
 
 class PackedLinear(_PackedBase):
     """A packed QuantLinear's forward on the engine (quantlinear.py:150-161).  The packed x packed kernel of the
     reference indexes the activation scale by batch ROW (quantlinear.cu:96), so a per-tensor scale is what the modules'
     'layer' granularity provides; inputs with leading dimensions are flattened to (rows, in_features)."""
+    LINEAR = True
+
+    def __init__(self, **state):
+        super().__init__(**state)
+        self.O, self.K = self.w_shape[0], self.w_shape[-1]
 
     @classmethod
     def from_state_dict(cls, state_dict, prefix=""):
@@ -150,26 +227,22 @@ class PackedLinear(_PackedBase):
         return y.reshape(*lead, y.shape[-1])
 
     # ---- packed in, packed out: the linear-epilogue forms ----
-    def call_packed(self, xq, x_des, consumer=None, act=None, residual=None):
-        """Activations as (packed stream, des [n_bits, sign, rows, in_features]) -- what quantize() or an earlier
-        call_packed() returned.  consumer=None: the fp32 (rows, out_features) output, plus `residual` when given
+    def call_packed(self, xq, x_des, consumer=None, act=None, residual=None, status=None):
+        """Activations as (packed stream, des [n_bits, sign, rows, in_features]) -- what quantize(), quantize_codes() or an
+        earlier call_packed() returned.  consumer=None: the fp32 (rows, out_features) output, plus `residual` when given
         (qe_quantlinear_residual: the add in the kernel's epilogue; bit-identical to self.call_packed(xq, x_des) + residual).
         consumer = the Packed* layer that reads this layer's output: returns the (packed, des) pair of ITS activation quantiser
         of act(y) (act None or "gelu"), written by this layer's kernel itself where it can (qe_quantlinear_requant):
-        bit-identical to consumer.quantize(act(self.call_packed(xq, x_des))) with act applied in fp32 as F.gelu does."""
-        from . import capi
-        d = [int(v) for v in x_des.tolist()]
-        n_bits, sign = d[0], d[1]
-        K = d[-1]
-        B = 1
-        for v in d[2:-1]:
+        bit-identical to consumer.quantize(act(self.call_packed(xq, x_des))) with act applied in fp32 as F.gelu does.
+        status: a device int32 the range flag accumulates in; nothing is read back or copied, des comes back as host
+        integers.  None: raise when the codes are out of range."""
+        n_bits, sign, *lead, K = _host_des(x_des)
+        B, O = 1, self.O
+        for v in lead:
             B *= v
-        wd = [int(v) for v in self.w_des.tolist()]
-        O = wd[2]
         if self.a_scale.numel() != 1:
             raise ValueError("quantlinear takes a per-tensor or per-row activation scale")
-        x = capi.qparam(xq, n_bits, sign, self.a_scale, self.a_zero)            # quantlinear: (q + zero)
-        w = capi.qparam(self.weight, wd[0], wd[1], self.w_scale.reshape(-1), self.w_zero.reshape(-1))
+        x, w = self.xq(xq, n_bits, sign), self.wq()
         if consumer is None:
             if act is not None:
                 raise ValueError("act applies to the consumer's codes; the fp32 output is y itself")
@@ -178,12 +251,11 @@ class PackedLinear(_PackedBase):
             return capi.quantlinear_residual(x, w, self.bias, B, K, O, residual.contiguous().reshape(B, O))
         if residual is not None:
             raise ValueError("residual and consumer are exclusive")
-        rq = capi.requant(consumer.a_scale, consumer.a_zero, consumer.a_qmin, consumer.a_qmax, consumer.a_bits, consumer.a_signed)
-        codes, status = capi.quantlinear_requant(x, w, self.bias, B, K, O, rq, act=act)
-        if int(status.item()) != 0:
-            raise RuntimeError("The input tensor is out of range.")     # tpack.cu:14, as engine.tpack raises it
-        des = torch.tensor([consumer.a_bits, 1 if consumer.a_signed else 0, B, O], dtype=torch.int32, device=xq.device)
-        return codes, des
+        codes, flag = capi.quantlinear_requant(x, w, self.bias, B, K, O, consumer.requant(), act=act, status=status)
+        if status is None and int(flag.item()) != 0:
+            raise RuntimeError(OUT_OF_RANGE)
+        des = (consumer.a_bits, int(consumer.a_signed), B, O)
+        return codes, (des if status is not None else torch.tensor(des, dtype=torch.int32, device=xq.device))
 
 
 class PackedMultiheadAttention:
@@ -203,6 +275,15 @@ class PackedMultiheadAttention:
         self._neg_out_zero = (-out_zero).reshape(-1).contiguous()          # kernel convention of the float-input operator
         self.num_heads = int(num_heads)
 
+    @functools.cached_property
+    def _out_bits_sign(self):
+        """out_des's n_bits and sign as host integers: read once, by from_state_dict or else on first use."""
+        return tuple(int(v) for v in self.out_des.tolist()[:2])
+
+    def out_wq(self):
+        """out_proj's packed weights as a capi.qparam for the float-input quantlinear: (q - zero)."""
+        return capi.qparam(self.out_weight, *self._out_bits_sign, self.out_scale, self._neg_out_zero)
+
     @classmethod
     def from_state_dict(cls, sd, prefix="", num_heads=1):
         embed = int(sd[prefix + "q_proj_des"][2])
@@ -210,14 +291,16 @@ class PackedMultiheadAttention:
 
         def proj(name, i):
             qmin, qmax = float(sd[prefix + name + "_quantizer.qmin"]), float(sd[prefix + name + "_quantizer.qmax"])
-            a_bits = max(1, (int(round(qmax - qmin))).bit_length())
+            a_bits, a_signed = quantizer_bits(qmin, qmax)
             return PackedLinear(weight=sd[prefix + name + "_proj_weight"], w_des=sd[prefix + name + "_proj_des"],
                                 w_scale=sd[prefix + name + "_proj_scale"], w_zero=sd[prefix + name + "_proj_zero"],
                                 bias=None if bias is None else bias[i * embed:(i + 1) * embed].contiguous(),
                                 a_scale=sd[prefix + name + "_quantizer.scale"], a_zero=sd[prefix + name + "_quantizer.zero"],
-                                a_qmin=qmin, a_qmax=qmax, a_bits=a_bits, a_signed=qmin < 0)
-        return cls(proj("q", 0), proj("k", 1), proj("v", 2), sd[prefix + "out_proj.weight"], sd[prefix + "out_proj_des"],
-                   sd[prefix + "out_proj_scale"], sd[prefix + "out_proj_zero"], sd.get(prefix + "out_proj.bias"), num_heads)
+                                a_qmin=qmin, a_qmax=qmax, a_bits=a_bits, a_signed=a_signed, name=prefix + name)
+        mha = cls(proj("q", 0), proj("k", 1), proj("v", 2), sd[prefix + "out_proj.weight"], sd[prefix + "out_proj_des"],
+                  sd[prefix + "out_proj_scale"], sd[prefix + "out_proj_zero"], sd.get(prefix + "out_proj.bias"), num_heads)
+        mha._out_bits_sign       # parsed here, where the state_dict tensors normally still live on the host
+        return mha
 
     def to(self, device):
         for p in (self.q, self.k, self.v):
@@ -271,7 +354,6 @@ class PackedMultiheadAttention:
         if attention == "engine":
             if need_weights:
                 raise ValueError("attention='engine' materialises no attention weights: pass need_weights=False")
-            from . import capi
             Q, K, V = (p(x, route).reshape(-1, E).contiguous() for p, x in ((self.q, query), (self.k, key), (self.v, value)))
             if masked:
                 ctx = capi.attention(Q, K, V, N, L, H, S=S, layout="seq", mask=attn_mask, key_bias=key_padding_mask,

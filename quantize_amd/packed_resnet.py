@@ -29,56 +29,7 @@ import torch
 import torch.nn.functional as F
 
 from . import capi
-from .packed import PackedConv2d, PackedLinear
-
-OUT_OF_RANGE = "The input tensor is out of range."    # tpack.cu:14
-
-
-class _Conv:
-    """A PackedConv2d plus what the fused route needs on the host: its weight description and quantiser as host values,
-    and its prepared weight tables (kept per table layout, as PackedConv2d.call_packed does)."""
-
-    def __init__(self, layer, name):
-        self.m, self.name = layer, name
-        wd = [int(v) for v in layer.w_des.tolist()]
-        self.w_bits, self.w_sign, self.OC, self.IC, self.KH, self.KW = wd
-        self.stride, self.padding = layer.stride, layer.padding
-        self._prep = {}
-        self.refresh()
-
-    def refresh(self):
-        """Re-read the host copy of the activation quantiser (after calibration changes it)."""
-        m = self.m
-        self.q_key = (tuple(m.a_scale.tolist()), tuple(m.a_zero.tolist()), m.a_qmin, m.a_qmax, m.a_bits, m.a_signed)
-        # round(max(y, 0) / s - 0).clamp(0, qmax) == round(y / s).clamp(0, qmax): the producer's ReLU folds into the clamp
-        self.folds_relu = (not m.a_signed) and m.a_qmin == 0.0 and all(z == 0.0 for z in self.q_key[1]) and \
-            all(s > 0.0 for s in self.q_key[0])
-
-    def out_hw(self, H, W):
-        return ((H + 2 * self.padding - self.KH) // self.stride + 1, (W + 2 * self.padding - self.KW) // self.stride + 1)
-
-    def shape(self, N, H, W):
-        return capi.conv_shape(N, self.IC, H, W, self.OC, self.KH, self.KW, self.stride, self.padding)
-
-    def operands(self, codes, N, H, W):
-        m = self.m
-        sh = self.shape(N, H, W)
-        xq = capi.qparam(codes, m.a_bits, m.a_signed, m.a_scale, m._neg_a_zero)
-        wq = capi.qparam(m.weight, self.w_bits, self.w_sign, m.w_scale.reshape(-1), m._neg_w_zero.reshape(-1))
-        key = capi.conv_prepared_layout(sh, m.a_bits, self.w_bits)
-        if key not in self._prep:
-            self._prep[key] = capi.conv_prepare(wq, m.bias, sh, m.a_bits)
-        return sh, xq, wq, self._prep[key]
-
-    def requant(self):
-        m = self.m
-        return capi.requant(m.a_scale, m.a_zero, m.a_qmin, m.a_qmax, m.a_bits, m.a_signed)
-
-    def quantize(self, x, status):
-        """This layer's codes of an fp32 NCHW tensor (capi: no host synchronisation)."""
-        m = self.m
-        return capi.quantize_pack(x, m.a_scale, m.a_zero, m.a_qmin, m.a_qmax, m.a_bits, m.a_signed,
-                                  inner=x.shape[2] * x.shape[3], status=status)[0]
+from .packed import OUT_OF_RANGE, PackedConv2d, PackedLinear
 
 
 class _Block:
@@ -100,7 +51,11 @@ class PackedResNet:
 
     def __init__(self, stem, stages, fc, kind):
         self.stem, self.stages, self.fc, self.kind = stem, stages, fc, kind
-        self.fc_des = [int(v) for v in fc.w_des.tolist()]       # n_bits, sign, out_features, in_features
+
+    @property
+    def fc_des(self):
+        """The fc's weight description [n_bits, sign, out_features, in_features], from the layer's host values."""
+        return [self.fc.w_bits, int(self.fc.w_signed), self.fc.O, self.fc.K]
 
     @classmethod
     def from_state_dict(cls, sd, prefix=""):
@@ -110,10 +65,9 @@ class PackedResNet:
 
         def conv(name, stride, padding):
             try:
-                layer = PackedConv2d.from_state_dict(sd, name + ".", stride=stride, padding=padding)
+                c = PackedConv2d.from_state_dict(sd, name + ".", stride=stride, padding=padding)
             except KeyError as e:
                 raise KeyError("packed ResNet state_dict: missing %s%s" % (prefix, e.args[0])) from None
-            c = _Conv(layer, name)
             if c.KH != 2 * padding + 1 or c.KW != c.KH:
                 raise ValueError("%s: a %dx%d kernel where torchvision's ResNet has %dx%d" % (name, c.KH, c.KW, 2 * padding + 1,
                                                                                            2 * padding + 1))
@@ -182,24 +136,15 @@ class PackedResNet:
         res = []
         for i, (b, sh) in enumerate(self.block_end_shapes(N, H, W)):
             c = b.convs[-1]
-            m = c.m
-            codes = torch.empty(64, dtype=torch.uint8, device=m.weight.device)      # the plan reads only its alignment
-            xq = capi.qparam(codes, m.a_bits, m.a_signed, m.a_scale, m._neg_a_zero)
-            wq = capi.qparam(m.weight, c.w_bits, c.w_sign, m.w_scale.reshape(-1), m._neg_w_zero.reshape(-1))
+            codes = torch.empty(64, dtype=torch.uint8, device=c.weight.device)      # the plan reads only its alignment
             rq = blocks[i + 1].convs[0].requant() if i + 1 < len(blocks) else None
-            res.append(capi.residual_path(sh, xq, wq, rq))
+            res.append(capi.residual_path(sh, c.xq(codes), c.wq(), rq))
         return res
 
     def to(self, device):
-        for c in self.convs():
-            c.m.to(device)
-            c._prep = {}
-        self.fc.to(device)
+        for layer in self.convs() + [self.fc]:
+            layer.to(device)
         return self
-
-    def refresh(self):
-        for c in self.convs():
-            c.refresh()
 
     # ---- the two routes ----
     def __call__(self, images, route="fused", check=True):
@@ -222,13 +167,7 @@ class PackedResNet:
         if route == "layers":
             logits = self.fc(pooled, route="packed")
         else:
-            fc = self.fc
-            codes = capi.quantize_pack(pooled, fc.a_scale, fc.a_zero, fc.a_qmin, fc.a_qmax, fc.a_bits, fc.a_signed,
-                                       inner=1, status=status)[0]
-            wd = self.fc_des
-            xq = capi.qparam(codes, fc.a_bits, fc.a_signed, fc.a_scale, fc.a_zero)       # quantlinear: (q + zero)
-            wq = capi.qparam(fc.weight, wd[0], wd[1], fc.w_scale.reshape(-1), fc.w_zero.reshape(-1))
-            logits = capi.quantlinear(xq, wq, fc.bias, pooled.shape[0], wd[3], wd[2])
+            logits = self.fc.call_packed(*self.fc.quantize_codes(pooled, status), status=status)
             if check and int(status.item()) != 0:
                 raise RuntimeError(OUT_OF_RANGE)
         return logits, feat
@@ -238,7 +177,7 @@ class PackedResNet:
         def run(c, t):
             if observe is not None:
                 observe(c, t)
-            return c.m(t, route="packed")
+            return c(t, route="packed")
         y = F.max_pool2d(torch.relu(run(self.stem, x)), 3, 2, 1)
         for b in self.blocks():
             identity = run(b.downsample, y) if b.downsample is not None else y
@@ -252,9 +191,9 @@ class PackedResNet:
         """c's output as consumer's codes: fused into c's epilogue where the ReLU folds, else fp32 + relu + quantize_pack."""
         sh, xq, wq, prep = c.operands(codes, N, H, W)
         if consumer.folds_relu:
-            return capi.quantconv2d_requant_prepared(xq, wq, c.m.bias, sh, prep, consumer.requant(), status=status)[0]
-        y = torch.relu(capi.quantconv2d_prepared(xq, wq, c.m.bias, sh, prep))
-        return consumer.quantize(y, status)
+            return capi.quantconv2d_requant_prepared(xq, wq, c.bias, sh, prep, consumer.requant(), status=status)[0]
+        y = torch.relu(capi.quantconv2d_prepared(xq, wq, c.bias, sh, prep))
+        return consumer.quantize_codes(y, status)[0]
 
     def _fused(self, images, status):
         N, _, H, W = images.shape
@@ -262,27 +201,27 @@ class PackedResNet:
         first = blocks[0]
         c1 = first.convs[0]
         stem = self.stem
-        codes = stem.quantize(images, status)
+        codes = stem.quantize_codes(images, status)[0]
         Hs, Ws = stem.out_hw(H, W)
         Hp, Wp = (Hs + 2 - 3) // 2 + 1, (Ws + 2 - 3) // 2 + 1
         xin = None
-        if c1.folds_relu and c1.m.a_bits == 8 and first.downsample is not None and first.downsample.q_key == c1.q_key:
+        if c1.folds_relu and c1.a_bits == 8 and first.downsample is not None and first.downsample.q_key == c1.q_key:
             # stem -> layer1.0.conv1's codes (ReLU folded), then the maxpool on the codes: nothing else reads the fp32
             s_codes = self._conv_codes(stem, codes, N, H, W, c1, status)
             xcodes = capi.maxpool2d_codes(s_codes, 8, N, stem.OC, Hs, Ws, 3, 2, 1)
         else:
             sh, xq, wq, prep = stem.operands(codes, N, H, W)
-            xin = F.max_pool2d(torch.relu(capi.quantconv2d_prepared(xq, wq, stem.m.bias, sh, prep)), 3, 2, 1)
-            xcodes = c1.quantize(xin, status)
+            xin = F.max_pool2d(torch.relu(capi.quantconv2d_prepared(xq, wq, stem.bias, sh, prep)), 3, 2, 1)
+            xcodes = c1.quantize_codes(xin, status)[0]
         H, W = Hp, Wp
         for i, b in enumerate(blocks):
             nxt = blocks[i + 1] if i + 1 < len(blocks) else None
             # the identity: the downsample's fp32 output (its codes shared with conv1, or quantised from the fp32 input)
             if b.downsample is not None:
                 ds = b.downsample
-                dcodes = xcodes if ds.q_key == b.convs[0].q_key else ds.quantize(xin, status)
+                dcodes = xcodes if ds.q_key == b.convs[0].q_key else ds.quantize_codes(xin, status)[0]
                 sh, xq, wq, prep = ds.operands(dcodes, N, H, W)
-                identity = capi.quantconv2d_prepared(xq, wq, ds.m.bias, sh, prep)
+                identity = capi.quantconv2d_prepared(xq, wq, ds.bias, sh, prep)
             else:
                 identity = xin
             o, Ho, Wo = xcodes, H, W
@@ -296,7 +235,7 @@ class PackedResNet:
             sh, xq, wq, prep = last.operands(o, N, Ho, Wo)
             rq = nxt.convs[0].requant() if nxt is not None else None
             out = identity if need_f32 else None       # in place: nothing else reads the identity after this conv
-            xin, xcodes, _ = capi.quantconv2d_residual_prepared(xq, wq, last.m.bias, sh, prep, identity, rq=rq, out=out,
+            xin, xcodes, _ = capi.quantconv2d_residual_prepared(xq, wq, last.bias, sh, prep, identity, rq=rq, out=out,
                                                                 status=status)
             H, W = last.out_hw(Ho, Wo)
         return xin
@@ -306,23 +245,20 @@ class PackedResNet:
         """Set every activation quantiser's scale from the max of what reaches it in one `layers` pass (by max, as the
         existing bottleneck test does): unsigned quantisers take max / qmax, signed ones max|x| / qmax."""
         def observe(c, t):
-            m = c.m
-            if m.a_signed:
-                s = t.abs().max() / m.a_qmax
+            if c.a_signed:
+                s = t.abs().max() / c.a_qmax
             else:
-                s = t.clamp(min=0).max() / m.a_qmax
-            m.a_scale = torch.clamp(s, min=1e-8).reshape(1).float().contiguous()
+                s = t.clamp(min=0).max() / c.a_qmax
+            c.a_scale = torch.clamp(s, min=1e-8).reshape(1)
         with torch.no_grad():
             feat = self._layers(images, observe)
             pooled = capi.global_avgpool(feat)
-            fc = self.fc
-            fc.a_scale = torch.clamp(pooled.clamp(min=0).max() / fc.a_qmax, min=1e-8).reshape(1).float().contiguous()
-        self.refresh()
+            self.fc.a_scale = torch.clamp(pooled.clamp(min=0).max() / self.fc.a_qmax, min=1e-8).reshape(1)
         return self
 
     def state_dict_scales(self):
         """{key: tensor} of every activation scale, in the state_dict's key layout."""
-        out = {c.name + ".a_quantizer.scale": c.m.a_scale for c in self.convs()}
+        out = {c.name + ".a_quantizer.scale": c.a_scale for c in self.convs()}
         out["fc.a_quantizer.scale"] = self.fc.a_scale
         return out
 

@@ -29,10 +29,8 @@ import torch
 import torch.nn.functional as F
 
 from . import capi
-from .packed import PackedConv2d, PackedLinear, PackedMultiheadAttention
+from .packed import OUT_OF_RANGE, PackedConv2d, PackedLinear, PackedMultiheadAttention, quantizer_bits
 from .packed_resnet import pack_codes
-
-OUT_OF_RANGE = "The input tensor is out of range."    # tpack.cu:14
 
 
 ATTENTION = ("torch", "engine")
@@ -54,37 +52,17 @@ def _attention(Q, K, V, N, L, H, attention="torch"):
     return ctx.transpose(1, 2).reshape(N * L, E).contiguous()
 
 
-class _Lin:
-    """A PackedLinear plus its host-side operand descriptions."""
-
-    def __init__(self, m, name):
-        self.m, self.name = m, name
-        wd = [int(v) for v in m.w_des.tolist()]
-        self.w_bits, self.w_sign, self.O, self.K = wd[0], wd[1], wd[2], wd[-1]
-        if m.a_scale.numel() != 1:
-            raise ValueError("%s: a per-channel activation quantiser (%d scales) on a linear: the packed x packed kernel scales "
-                             "by batch row, so only a per-tensor quantiser is supported" % (name, m.a_scale.numel()))
-
-    def xq(self, codes):
-        m = self.m
-        return capi.qparam(codes, m.a_bits, m.a_signed, m.a_scale, m.a_zero)         # quantlinear: (q + zero)
-
-    def wq(self):
-        m = self.m
-        return capi.qparam(m.weight, self.w_bits, self.w_sign, m.w_scale.reshape(-1), m.w_zero.reshape(-1))
-
-    def requant(self):
-        m = self.m
-        return capi.requant(m.a_scale, m.a_zero, m.a_qmin, m.a_qmax, m.a_bits, m.a_signed)
+def _run(layer, t, observe):
+    """layer(t) on the `layers` route; observe(layer, its fp32 input) is called in front of it (calibration)."""
+    if observe is not None:
+        observe(layer, t)
+    return layer(t, route="packed")
 
 
 class _Block:
     def __init__(self, name, ln1, attn, ln2, fc1, fc2):
-        self.name, self.ln1, self.attn, self.ln2 = name, ln1, attn, ln2
-        self.q, self.k, self.v = (_Lin(p, name + ".self_attention." + n) for p, n in ((attn.q, "q"), (attn.k, "k"), (attn.v, "v")))
-        self.fc1, self.fc2 = _Lin(fc1, name + ".mlp.0"), _Lin(fc2, name + ".mlp.3")
-        od = [int(v) for v in attn.out_des.tolist()]
-        self.out_bits, self.out_sign = od[0], od[1]
+        self.name, self.ln1, self.attn, self.ln2, self.fc1, self.fc2 = name, ln1, attn, ln2, fc1, fc2
+        self.q, self.k, self.v = attn.q, attn.k, attn.v
 
 
 class PackedViT:
@@ -93,12 +71,13 @@ class PackedViT:
     def __init__(self, conv, class_token, pos, blocks, ln, head, num_heads, eps):
         self.conv, self.class_token, self.pos, self.blocks = conv, class_token, pos, blocks
         self.ln, self.head, self.num_heads, self.eps = ln, head, int(num_heads), float(eps)
-        wd = [int(v) for v in conv.w_des.tolist()]
-        self._conv_wd = wd
-        self.E, self.C, self.patch = wd[2], wd[3], wd[4]
-        if wd[4] != wd[5]:
-            raise ValueError("conv_proj: a %dx%d kernel; a ViT's patch embedding is square" % (wd[4], wd[5]))
-        self.head_lin = _Lin(head, "heads.head")
+        self.E, self.C, self.patch = conv.OC, conv.IC, conv.KH
+        if conv.KH != conv.KW:
+            raise ValueError("conv_proj: a %dx%d kernel; a ViT's patch embedding is square" % (conv.KH, conv.KW))
+        for lin in self.linears():
+            if lin.a_scale.numel() != 1:
+                raise ValueError("%s: a per-channel activation quantiser (%d scales) on a linear: the packed x packed kernel "
+                                 "scales by batch row, so only a per-tensor quantiser is supported" % (lin.name, lin.a_scale.numel()))
         if conv.a_scale.numel() != 1:
             raise ValueError("conv_proj: a per-channel image quantiser (%d scales): the patch embedding runs as a GEMM whose "
                              "activations are scaled by row, so only a per-tensor image quantiser is supported" % conv.a_scale.numel())
@@ -135,6 +114,8 @@ class PackedViT:
         return cls(conv, need("class_token"), need("encoder.pos_embedding"), blocks, ln, head, num_heads, eps)
 
     # ---- introspection ----
+    head_lin = property(lambda self: self.head)       # the head under its earlier name
+
     @property
     def depth(self):
         return len(self.blocks)
@@ -147,7 +128,7 @@ class PackedViT:
         out = []
         for b in self.blocks:
             out += [b.q, b.k, b.v, b.fc1, b.fc2]
-        return out + [self.head_lin]
+        return out + [self.head]
 
     # ---- the two routes ----
     def __call__(self, images, route="fused", check=True, attention="torch"):
@@ -174,15 +155,13 @@ class PackedViT:
         if route == "layers":
             logits = self.head(y, route="packed")
         else:
-            h = self.head_lin
-            codes = capi.quantize_pack(y, h.m.a_scale, h.m.a_zero, h.m.a_qmin, h.m.a_qmax, h.m.a_bits, h.m.a_signed, status=status)[0]
-            logits = capi.quantlinear(h.xq(codes), h.wq(), h.m.bias, N, h.K, h.O)
+            logits = self.head.call_packed(*self.head.quantize_codes(y, status), status=status)
             if check and int(status.item()) != 0:
                 raise RuntimeError(OUT_OF_RANGE)
         return logits, outs
 
-    def embed(self, images, route, status):
-        """Patch embedding + class token + position embedding: (N L, E) fp32 rows."""
+    def embed(self, images, route, status, observe=None):
+        """Patch embedding + class token + position embedding: (N L, E) fp32 rows.  observe: see _run (`layers` route)."""
         N, C, H, W = images.shape
         p = self.patch
         c = self.conv
@@ -190,47 +169,45 @@ class PackedViT:
         if route == "layers":
             # the Quantizer on the unfolded image, then the conv as the GEMM it is (the engine's direct convolution has
             # no kernel for a 16 x 16 filter of 768 taps)
+            if observe is not None:
+                observe(c, images)
             u = images.reshape(N, C, H // p, p, W // p, p).permute(0, 2, 4, 1, 3, 5).reshape(rows, C * p * p).contiguous()
             codes = capi.quantize_pack(u, c.a_scale, c.a_zero, c.a_qmin, c.a_qmax, c.a_bits, c.a_signed)[0]
         else:
             codes = capi.quantize_patchify(images, p, c.a_scale, c.a_zero, c.a_qmin, c.a_qmax, c.a_bits, c.a_signed,
                                            status=status)[0]
         # quantlinear's convention: (q + zero) with the module's zero -- the conv's (q - zero') with zero' = -zero
-        xq = capi.qparam(codes, c.a_bits, c.a_signed, c.a_scale, c.a_zero)
-        wq = capi.qparam(c.weight, self._conv_wd[0], self._conv_wd[1], c.w_scale.reshape(-1), c.w_zero.reshape(-1))
+        xq, wq = c.xq(codes, linear=True), c.wq(linear=True)
         t = capi.quantlinear(xq, wq, c.bias, rows, C * p * p, self.E).reshape(N, -1, self.E)
         x = torch.cat([self.class_token.expand(N, -1, -1), t], dim=1) + self.pos
         return x.reshape(-1, self.E).contiguous()
 
-    def block(self, b, x, N, route, status=None, attention="torch"):
-        """One encoder block on (N L, E) fp32 rows -> (N L, E).  The fused route updates x in place."""
+    def block(self, b, x, N, route, status=None, attention="torch", observe=None):
+        """One encoder block on (N L, E) fp32 rows -> (N L, E).  The fused route updates x in place.  observe: see _run
+        (`layers` route)."""
         _check_attention(attention)
         E, H = self.E, self.num_heads
         L = x.shape[0] // N
         if route == "layers":
             y = F.layer_norm(x, (E,), b.ln1[0], b.ln1[1], self.eps)
-            Q, K, V = (lin.m(y, route="packed") for lin in (b.q, b.k, b.v))
+            Q, K, V = (_run(lin, y, observe) for lin in (b.q, b.k, b.v))
             ctx = _attention(Q, K, V, N, L, H, attention)
-            a = b.attn
-            oq = capi.qparam(a.out_weight, b.out_bits, b.out_sign, a.out_scale, a._neg_out_zero)
-            x = x + capi.quantlinear_float_input(ctx, oq, a.out_bias, E)
+            x = x + capi.quantlinear_float_input(ctx, b.attn.out_wq(), b.attn.out_bias, E)
             y = F.layer_norm(x, (E,), b.ln2[0], b.ln2[1], self.eps)
-            h = F.gelu(b.fc1.m(y, route="packed"))
-            return x + b.fc2.m(h, route="packed")
+            h = F.gelu(_run(b.fc1, y, observe))
+            return x + _run(b.fc2, h, observe)
         if status is None:
             status = torch.zeros(1, dtype=torch.int32, device=x.device)
         rows = x.shape[0]
         codes = capi.layernorm_quantize_pack(x, b.ln1[0], b.ln1[1], self.eps, [b.q.requant(), b.k.requant(), b.v.requant()],
                                              status=status)[0]
-        Q, K, V = (capi.quantlinear(lin.xq(c), lin.wq(), lin.m.bias, rows, lin.K, lin.O) for lin, c in zip((b.q, b.k, b.v), codes))
+        Q, K, V = (capi.quantlinear(lin.xq(c), lin.wq(), lin.bias, rows, lin.K, lin.O) for lin, c in zip((b.q, b.k, b.v), codes))
         ctx = _attention(Q, K, V, N, L, H, attention)
-        a = b.attn
-        oq = capi.qparam(a.out_weight, b.out_bits, b.out_sign, a.out_scale, a._neg_out_zero)
-        x = capi.quantlinear_float_input_residual(ctx, oq, a.out_bias, E, x, out=x)
+        x = capi.quantlinear_float_input_residual(ctx, b.attn.out_wq(), b.attn.out_bias, E, x, out=x)
         c1 = capi.layernorm_quantize_pack(x, b.ln2[0], b.ln2[1], self.eps, [b.fc1.requant()], status=status)[0][0]
-        c2 = capi.quantlinear_requant(b.fc1.xq(c1), b.fc1.wq(), b.fc1.m.bias, rows, b.fc1.K, b.fc1.O, b.fc2.requant(), act="gelu",
+        c2 = capi.quantlinear_requant(b.fc1.xq(c1), b.fc1.wq(), b.fc1.bias, rows, b.fc1.K, b.fc1.O, b.fc2.requant(), act="gelu",
                                       status=status)[0]
-        return capi.quantlinear_residual(b.fc2.xq(c2), b.fc2.wq(), b.fc2.m.bias, rows, b.fc2.K, b.fc2.O, x, out=x)
+        return capi.quantlinear_residual(b.fc2.xq(c2), b.fc2.wq(), b.fc2.bias, rows, b.fc2.K, b.fc2.O, x, out=x)
 
     # ---- calibration (synthetic models, tests, tools) ----
     def calibrate(self, images):
@@ -238,33 +215,18 @@ class PackedViT:
         unsigned ones (fc2's, after the GELU) asymmetric over [min, max] with zero = round(min / scale)."""
         def set_q(m, t):
             if m.a_signed:
-                m.a_scale = torch.clamp(t.abs().max() / m.a_qmax, min=1e-8).reshape(1).float().contiguous()
+                m.a_scale = torch.clamp(t.abs().max() / m.a_qmax, min=1e-8).reshape(1)
             else:
                 lo, hi = t.min(), t.max()
                 s = torch.clamp((hi - lo) / (m.a_qmax - m.a_qmin), min=1e-8)
-                m.a_scale = s.reshape(1).float().contiguous()
-                m.a_zero = torch.round(lo / s).reshape(1).float().contiguous()
-            m._neg_a_zero = (-m.a_zero).contiguous()
+                m.a_scale = s.reshape(1)
+                m.a_zero = torch.round(lo / s).reshape(1)
         with torch.no_grad():
             N = images.shape[0]
-            set_q(self.conv, images)
-            x = self.embed(images, "layers", None)
+            x = self.embed(images, "layers", None, observe=set_q)
             for b in self.blocks:
-                y = F.layer_norm(x, (self.E,), b.ln1[0], b.ln1[1], self.eps)
-                for lin in (b.q, b.k, b.v):
-                    set_q(lin.m, y)
-                L = x.shape[0] // N
-                ctx = _attention(*(lin.m(y, route="packed") for lin in (b.q, b.k, b.v)), N, L, self.num_heads)
-                a = b.attn
-                oq = capi.qparam(a.out_weight, b.out_bits, b.out_sign, a.out_scale, a._neg_out_zero)
-                x = x + capi.quantlinear_float_input(ctx, oq, a.out_bias, self.E)
-                y = F.layer_norm(x, (self.E,), b.ln2[0], b.ln2[1], self.eps)
-                set_q(b.fc1.m, y)
-                h = F.gelu(b.fc1.m(y, route="packed"))
-                set_q(b.fc2.m, h)
-                x = x + b.fc2.m(h, route="packed")
-            y = F.layer_norm(x.reshape(N, -1, self.E)[:, 0], (self.E,), self.ln[0], self.ln[1], self.eps)
-            set_q(self.head, y)
+                x = self.block(b, x, N, "layers", observe=set_q)
+            set_q(self.head, F.layer_norm(x.reshape(N, -1, self.E)[:, 0], (self.E,), self.ln[0], self.ln[1], self.eps))
         return self
 
     def state_dict_quantizers(self):
@@ -276,9 +238,9 @@ class PackedViT:
         put("conv_proj.a_quantizer.", self.conv)
         for b in self.blocks:
             for n, lin in (("q", b.q), ("k", b.k), ("v", b.v)):
-                put(b.name + ".self_attention.%s_quantizer." % n, lin.m)
-            put(b.name + ".mlp.0.a_quantizer.", b.fc1.m)
-            put(b.name + ".mlp.3.a_quantizer.", b.fc2.m)
+                put(b.name + ".self_attention.%s_quantizer." % n, lin)
+            put(b.name + ".mlp.0.a_quantizer.", b.fc1)
+            put(b.name + ".mlp.3.a_quantizer.", b.fc2)
         put("heads.head.a_quantizer.", self.head)
         return out
 
@@ -286,15 +248,10 @@ class PackedViT:
 # ---------------------------------------------------------------------------------------------
 # From a calibrated reference ViT to this engine
 # ---------------------------------------------------------------------------------------------
-def _qbits(qmin, qmax):
-    qmin, qmax = float(qmin), float(qmax)
-    return max(1, int(round(qmax - qmin)).bit_length()), qmin < 0
-
-
 def _pack_weight(w, scale, zero, qmin, qmax, static_scale=None):
     """Quantizer.pack() of a weight (quantizer.py:228-250) + tpack: round(w / scale - zero).clamp(qmin, qmax) in fp32, the
     stored b-bit stream, des [n_bits, sign, *shape], and (scale * static_scale, zero)."""
-    n_bits, signed = _qbits(qmin, qmax)
+    n_bits, signed = quantizer_bits(qmin, qmax)
     w = w.detach().float().cpu()
     scale, zero = scale.detach().float().cpu(), zero.detach().float().cpu()
     q = (w / scale - zero).round().clamp(float(qmin), float(qmax))

@@ -103,6 +103,17 @@ def test_packed_layers_chain_without_fp32_in_between():
     torch.cuda.synchronize()
     assert torch.equal(out, ref)
     assert tuple(out.shape) == (4, 256, 14, 14)
+    # the same chain with a caller's status tensor: the same codes, nothing read back, no host synchronisation
+    flag = torch.zeros(1, dtype=torch.int32, device=DEV)
+    xq2, xd2 = a.quantize_codes(x, flag)
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        qb2, db2 = a.call_packed(xq2, xd2, consumer=b, status=flag)
+        qc2, dc2 = b.call_packed(qb2, db2, consumer=c, status=flag)
+        out2 = c.call_packed(qc2, dc2, status=flag)
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    assert torch.equal(qb2, qb) and list(db2) == db.tolist() and torch.equal(out2, out) and int(flag.item()) == 0
 
 
 def test_resnet_bottleneck_chained_through_call_packed():

@@ -25,7 +25,7 @@ def test_resnet50_layout_discovered():
                 assert (b.downsample.stride, b.downsample.padding, b.downsample.OC) == (s, 0, b.convs[-1].OC)
     assert m.fc_des == [8, 1, 1000, 2048]
     # quantisers: the image's signed, every post-ReLU one unsigned with zero point 0 (the ReLU folds into its clamp)
-    assert m.stem.m.a_signed and not m.stem.folds_relu
+    assert m.stem.a_signed and not m.stem.folds_relu
     assert all(c.folds_relu for c in m.convs()[1:])
     ends = [(sh.IC, sh.OC, sh.H) for _, sh in m.block_end_shapes(256)]
     assert ends == [(64, 256, 56)] * 3 + [(128, 512, 28)] * 4 + [(256, 1024, 14)] * 6 + [(512, 2048, 7)] * 3
@@ -53,8 +53,25 @@ def test_signed_consumer_does_not_fold():
     sd["layer3.1.conv2.a_quantizer.qmax"] = torch.tensor(127.0)
     m = PackedResNet.from_state_dict(sd)
     assert not m.stages[1][1].convs[1].folds_relu
-    assert not m.stages[2][1].convs[1].folds_relu and m.stages[2][1].convs[1].m.a_signed
+    assert not m.stages[2][1].convs[1].folds_relu and m.stages[2][1].convs[1].a_signed
     assert m.stages[3][1].convs[1].folds_relu
+
+
+def test_assigning_a_quantiser_updates_what_is_derived_from_it():
+    """folds_relu, q_key and the negated zero follow an assignment to a_scale / a_zero with no further call."""
+    m = PackedResNet.from_state_dict(synthetic_state_dict("resnet18"))
+    c, twin = m.stages[1][0].convs[0], m.stages[1][0].downsample
+    assert c.folds_relu and c.q_key == twin.q_key
+    c.a_scale = torch.tensor([0.5])
+    assert c.folds_relu and c.q_key != twin.q_key and c.q_key[0] == (0.5,)
+    c.a_zero = torch.tensor([3.0])
+    assert not c.folds_relu and c.q_key[1] == (3.0,) and c._neg_a_zero.tolist() == [-3.0]
+    c.a_zero = torch.tensor([0.0])
+    assert c.folds_relu
+    c.a_scale = torch.tensor([0.0])               # a non-positive scale never folds
+    assert not c.folds_relu
+    c.a_scale, twin.a_scale = torch.tensor([0.25]), torch.tensor([0.25])
+    assert c.folds_relu and c.q_key == twin.q_key
 
 
 @pytest.mark.parametrize("key", ["layer3.2.conv2.w_scale", "layer2.0.downsample.0.w_des", "fc.weight", "conv1.a_quantizer.qmax"])
@@ -80,9 +97,9 @@ def test_block_end_paths_at_batch_256():
     assert m.residual_paths(256) == [1] * 16
     # without codes, and with per-channel or 4-bit codes (two passes)
     b, sh = m.block_end_shapes(256)[4]
-    c = b.convs[-1].m
-    xq = capi.qparam(torch.empty(64, dtype=torch.uint8), 8, False, c.a_scale, c._neg_a_zero)
-    wq = capi.qparam(c.weight, 8, True, c.w_scale.reshape(-1), c._neg_w_zero.reshape(-1))
+    c = b.convs[-1]
+    assert (c.a_bits, c.a_signed, c.w_bits, c.w_signed) == (8, False, 8, True)
+    xq, wq = c.xq(torch.empty(64, dtype=torch.uint8)), c.wq()
     assert capi.residual_path(sh, xq, wq, None) == 1
     pc = torch.ones(sh.OC)
     assert capi.residual_path(sh, xq, wq, capi.requant(pc, pc * 0, 0, 255, 8, False)) == 0

@@ -96,7 +96,7 @@ def test_engine_context_on_model_projections(models, arch):
     worst = 0.0
     for b in m.blocks:
         codes = capi.layernorm_quantize_pack(x, b.ln1[0], b.ln1[1], m.eps, [b.q.requant(), b.k.requant(), b.v.requant()])[0]
-        Q, K, V = (capi.quantlinear(lin.xq(c), lin.wq(), lin.m.bias, x.shape[0], lin.K, lin.O)
+        Q, K, V = (capi.quantlinear(lin.xq(c), lin.wq(), lin.bias, x.shape[0], lin.K, lin.O)
                    for lin, c in zip((b.q, b.k, b.v), codes))
         ce = _attention(Q, K, V, N, L, m.num_heads, "engine")
         ct = _attention(Q, K, V, N, L, m.num_heads, "torch")

@@ -82,7 +82,7 @@ def test_block_fused_vs_layers(models, arch, N):
         # LayerNorm codes: the kernel's vs torch's LayerNorm through quantize_pack
         codes = capi.layernorm_quantize_pack(x, b.ln1[0], b.ln1[1], m.eps, [b.q.requant()])[0][0]
         y = F.layer_norm(x, (m.E,), b.ln1[0], b.ln1[1], m.eps)
-        ref = b.q.m.quantize(y, channel_dim=1)[0]
+        ref = b.q.quantize(y, channel_dim=1)[0]
         d = (codes.to(torch.int16) - ref.to(torch.int16)).abs()
         assert int(d.max()) <= 1 and float((d > 0).float().mean()) <= 1e-3
         fused = m.block(b, x.clone(), N, "fused")

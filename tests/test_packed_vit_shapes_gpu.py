@@ -35,8 +35,7 @@ def test_layer_kernels_at_64_images(vit_b):
     rows = N * 197
     c = m.conv
     p = m.patch
-    patch_x = capi.qparam(codes, c.a_bits, c.a_signed, c.a_scale, c.a_zero)
-    patch_w = capi.qparam(c.weight, m._conv_wd[0], m._conv_wd[1], c.w_scale.reshape(-1), c.w_zero.reshape(-1))
+    patch_x, patch_w = c.xq(codes, linear=True), c.wq(linear=True)
     assert capi.linear_form(patch_x, patch_w, N * 196, 3 * p * p, m.E) == 4
     for b in m.blocks:
         for lin in (b.q, b.k, b.v, b.fc1):

@@ -115,8 +115,8 @@ def test_resnet50_fallbacks():
     model = _engine(sd)
     assert [c.name for c in model.convs() if not c.folds_relu] == ["conv1", "layer1.0.conv1", "layer2.1.conv2",
                                                                    "layer3.1.conv3"]
-    assert model.stages[2][3].convs[0].m.a_scale.numel() == 1024 and model.stages[1][2].convs[1].m.a_scale.numel() == 128
-    assert len(set(model.stages[1][2].convs[1].m.a_scale.tolist())) > 1      # the channels' scales differ
+    assert model.stages[2][3].convs[0].a_scale.numel() == 1024 and model.stages[1][2].convs[1].a_scale.numel() == 128
+    assert len(set(model.stages[1][2].convs[1].a_scale.tolist())) > 1      # the channels' scales differ
     ds = model.stages[2][0]
     assert ds.downsample.q_key != ds.convs[0].q_key
     assert model.fc.a_zero.tolist() == [-3.0]
