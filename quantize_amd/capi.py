@@ -4,6 +4,7 @@ Tensors are only used here as device-memory handles (data_ptr) and for the curre
 stream; every compute call goes straight into libqe_hip.so.  Used by bench.py and by the
 `-m gpu` parity tests, which must exercise the C ABI itself and not only the torch module.
 """
+import contextlib
 import ctypes
 import os
 
@@ -243,6 +244,27 @@ def reload_env():
     """Re-read the QE_* tuning knobs: the library snapshots them once per process (qe_common.h env_get); call this after
     changing one inside a live process (tests, A/B tools).  Not part of the public C ABI."""
     lib().qe_debug_reload_env()
+
+
+@contextlib.contextmanager
+def knobs(**env):
+    """Set QE_* knobs (value None: unset), re-read them; on exit, also on an exception, put the environment back and
+    re-read again.  The one way to flip a knob in a live process: `with capi.knobs(QE_PWR="0"): ...`."""
+    old = {k: os.environ.get(k) for k in env}
+
+    def put(kv):
+        for k, v in kv.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = str(v)
+        reload_env()
+
+    try:
+        put(env)
+        yield
+    finally:
+        put(old)
 
 
 def conv_prepared_layout(sh, x_bits, w_bits):

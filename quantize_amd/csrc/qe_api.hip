@@ -68,12 +68,6 @@ int launch_conv_generic(bool packed_in, const void *x, const qe_qparam *xq, cons
 int launch_residual_relu_quant(const float *y, const float *identity, float *out, int64_t n, int64_t inner, const qe_requant *rq,
                                uint8_t *codes, int32_t *status, hipStream_t s);
 
-// qe_conv_f32.hip
-bool f32_conv_eligible(const qe_conv_shape *sh, const qe_qparam *w);
-size_t f32_conv_prepared_bytes(const qe_conv_shape *sh);
-int launch_conv_f32(const float *x, const qe_qparam *w, const float *bias, const qe_conv_shape *sh, float *out,
-                    void *prepared, size_t prepared_bytes, hipStream_t s, int mode);
-
 static int check_shape(const qe_conv_shape *sh)
 {
     if (sh == nullptr) return QE_ERR_ARG;
@@ -357,72 +351,71 @@ extern "C" int qe_quantconv2d_residual_prepared(const qe_qparam *x, const qe_qpa
     return launch_residual_relu_quant(y, identity, out, n, (int64_t)p.OH * p.OW, rq, codes, status, s);
 }
 
+// ---- float-input convolutions: every entry point that can take the MFMA kernels plans once (plan_conv_f32) ----
+static int check_float_input(const qe_conv_shape *shape, const qe_qparam *w, bool operands)
+{
+    int rc = qe::check_shape(shape);
+    if (rc != QE_OK) return rc;
+    if ((rc = qe::check_qparam(w)) != QE_OK) return rc;
+    if ((rc = qe::check_nparam(nullptr, w, shape)) != QE_OK) return rc;
+    return operands ? QE_OK : QE_ERR_ARG;
+}
+
+// no workspace, so no prepared tables: always the VALU kernel
 extern "C" int qe_quantconv2d_float_input(const float *x, const qe_qparam *w, const float *bias,
                                           const qe_conv_shape *shape, float *out, qe_stream_t stream)
 {
-    using namespace qe;
-    int rc = check_shape(shape);
+    const int rc = check_float_input(shape, w, x != nullptr && out != nullptr);
     if (rc != QE_OK) return rc;
-    if ((rc = check_qparam(w)) != QE_OK) return rc;
-    if ((rc = check_nparam(nullptr, w, shape)) != QE_OK) return rc;
-    if (x == nullptr || out == nullptr) return QE_ERR_ARG;
-    return launch_conv_generic(false, x, nullptr, w, bias, shape, out, static_cast<hipStream_t>(stream));
+    return qe::launch_conv_generic(false, x, nullptr, w, bias, shape, out, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int qe_quantconv2d_float_input_path(const qe_conv_shape *shape, const qe_qparam *w)
 {
     if (qe::check_shape(shape) != QE_OK || w == nullptr) return 0;
-    return qe::f32_conv_eligible(shape, w) ? 1 : 0;
+    return qe::plan_conv_f32(shape).ok ? 1 : 0;
 }
 
 extern "C" size_t qe_quantconv2d_float_input_workspace_bytes(const qe_conv_shape *shape, int w_bits)
 {
     (void)w_bits;
     if (qe::check_shape(shape) != QE_OK) return 0;
-    return qe::f32_conv_prepared_bytes(shape);
+    return qe::plan_conv_f32(shape).total;
 }
 
 extern "C" int qe_quantconv2d_float_input_ws(const float *x, const qe_qparam *w, const float *bias,
                                              const qe_conv_shape *shape, float *out, void *workspace,
                                              size_t workspace_bytes, qe_stream_t stream)
 {
-    using namespace qe;
-    int rc = check_shape(shape);
+    int rc = check_float_input(shape, w, x != nullptr && out != nullptr);
     if (rc != QE_OK) return rc;
-    if ((rc = check_qparam(w)) != QE_OK) return rc;
-    if ((rc = check_nparam(nullptr, w, shape)) != QE_OK) return rc;
-    if (x == nullptr || out == nullptr) return QE_ERR_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (f32_conv_eligible(shape, w)) return launch_conv_f32(x, w, bias, shape, out, workspace, workspace_bytes, s, 0);
-    return launch_conv_generic(false, x, nullptr, w, bias, shape, out, s);
+    const qe::F32Plan p = qe::plan_conv_f32(shape);
+    if (!p.ok) return qe::launch_conv_generic(false, x, nullptr, w, bias, shape, out, s);
+    if ((rc = qe::prepare_conv_f32(p, w, bias, shape, workspace, workspace_bytes, s)) != QE_OK) return rc;
+    return qe::launch_conv_f32(p, x, shape, workspace, workspace_bytes, out, s);
 }
 
 extern "C" int qe_conv_f32_prepare(const qe_qparam *w, const float *bias, const qe_conv_shape *shape,
                                    void *prepared, size_t prepared_bytes, qe_stream_t stream)
 {
-    using namespace qe;
-    int rc = check_shape(shape);
+    const int rc = check_float_input(shape, w, true);
     if (rc != QE_OK) return rc;
-    if ((rc = check_qparam(w)) != QE_OK) return rc;
-    if ((rc = check_nparam(nullptr, w, shape)) != QE_OK) return rc;
-    if (!f32_conv_eligible(shape, w)) return QE_OK;          // nothing to prepare: the VALU kernel reads the packed weights
-    return launch_conv_f32(nullptr, w, bias, shape, nullptr, prepared, prepared_bytes, static_cast<hipStream_t>(stream), 1);
+    const qe::F32Plan p = qe::plan_conv_f32(shape);
+    if (!p.ok) return QE_OK;          // nothing to prepare: the VALU kernel reads the packed weights
+    return qe::prepare_conv_f32(p, w, bias, shape, prepared, prepared_bytes, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int qe_quantconv2d_float_input_prepared(const float *x, const qe_qparam *w, const float *bias,
                                                    const qe_conv_shape *shape, const void *prepared,
                                                    size_t prepared_bytes, float *out, qe_stream_t stream)
 {
-    using namespace qe;
-    int rc = check_shape(shape);
+    const int rc = check_float_input(shape, w, x != nullptr && out != nullptr);
     if (rc != QE_OK) return rc;
-    if ((rc = check_qparam(w)) != QE_OK) return rc;
-    if ((rc = check_nparam(nullptr, w, shape)) != QE_OK) return rc;
-    if (x == nullptr || out == nullptr) return QE_ERR_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (f32_conv_eligible(shape, w))
-        return launch_conv_f32(x, w, bias, shape, out, const_cast<void *>(prepared), prepared_bytes, s, 2);
-    return launch_conv_generic(false, x, nullptr, w, bias, shape, out, s);
+    const qe::F32Plan p = qe::plan_conv_f32(shape);
+    if (!p.ok) return qe::launch_conv_generic(false, x, nullptr, w, bias, shape, out, s);
+    return qe::launch_conv_f32(p, x, shape, prepared, prepared_bytes, out, s);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -24,8 +24,9 @@ inline int hip_fail(hipError_t e) {
 #define QE_LAUNCH_CHECK() QE_HIP_TRY(hipGetLastError())
 
 // Tuning knobs (QE_* environment variables) are read ONCE per process into a snapshot (a conv call used to make 18 getenv
-// calls); env_get() answers from it.  qe_debug_reload_env() (not part of the public ABI; quantize_amd.capi.reload_env)
-// re-reads the environment -- the test-suite and the A/B tools use it after changing a knob inside a live process.
+// calls); env_get() answers from it.  qe_debug_reload_env() (not part of the public ABI) re-reads the environment: a test
+// or an A/B tool that flips a knob inside a live process does it with quantize_amd.capi.knobs, which re-reads after setting
+// the knob and again after putting the environment back.
 const char *env_get(const char *name);
 
 constexpr int kWave = 64;          // CDNA wavefront

@@ -25,6 +25,7 @@
 // 8 coalesced 16-byte loads (one per channel), the splits and the channel-major -> pixel-major turn in registers,
 // 12 ds_write_b128.  Weight fragments (bf16, prepared once per call or kept by the caller) go L2 -> VGPR one tap ahead.
 #include "qe_common.h"
+#include "qe_conv_plan.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -636,65 +637,65 @@ __global__ __launch_bounds__(F32_THREADS, 2) void conv_f32_stem_kernel(const F32
 }
 
 // ---------------------------------------------------------------------------------------------
-// host side
+// host side: plan_conv_f32 decides, prepare_conv_f32 / launch_conv_f32 read the plan (qe_conv_plan.hpp)
 // ---------------------------------------------------------------------------------------------
-struct F32Plan {
-    bool ok = false;
-    int cfg = 0;               // 0: 4x1 waves x 7 column tiles (MT 128), 1: 2x2 x 4 (MT 64)
-    int MT = 0, OCP = 0, NG = 0, KK = 0, OH = 0, OW = 0;
-    int TH = 0, GI = 1, IHT = 0, IWP = 0, ROWMUL = 1, COLMUL = 1, NS = 1;
-    bool stem = false;         // IC <= 4: K = kh x [kw 0..7][ic 0..3] (conv_f32_stem_kernel)
-    int niw = 0;
-    size_t lds = 0, wt_bytes = 0, ep_off = 0, total = 0;
-};
-
 static size_t f32_align(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-static F32Plan f32_plan(const qe_conv_shape *sh)
+// the table layout [weights | per-channel constants] and the XCD-aware block map of a plan whose tile is chosen
+static void f32_finish(F32Plan &p, const qe_conv_shape *sh, int MT, size_t wt_bytes)
+{
+    p.ep_off = f32_align(wt_bytes, 256);
+    p.total = f32_align(p.ep_off + (size_t)3 * p.OCP * sizeof(float), 256);
+    p.tiles_h = (p.OH + p.TH - 1) / p.TH;
+    p.n_pix_tiles = ((sh->N + p.GI - 1) / p.GI) * p.tiles_h;
+    p.n_oc_tiles = p.OCP / MT;
+    p.chunk = (int)std::max<int64_t>(1, ((int64_t)p.n_pix_tiles + 7) / 8);
+    const int64_t runs = ((int64_t)p.n_pix_tiles + p.chunk - 1) / p.chunk;
+    p.blocks = (runs + 7) / 8 * p.chunk * 8 * p.n_oc_tiles;
+    p.ok = true;
+}
+
+F32Plan plan_conv_f32(const qe_conv_shape *sh)
 {
     F32Plan p;
-    if (env_get("QE_F32_MFMA") && atoi(env_get("QE_F32_MFMA")) == 0) return p;
+    const char *knob = env_get("QE_F32_MFMA");
+    if (knob != nullptr && atoi(knob) == 0) return p;
     p.OH = (sh->H + 2 * sh->padding - sh->KH) / sh->stride + 1;
     p.OW = (sh->W + 2 * sh->padding - sh->KW) / sh->stride + 1;
     p.KK = sh->KH * sh->KW;
     if (p.OH <= 0 || p.OW <= 0 || sh->N <= 0 || sh->OC <= 0) return p;
     if (sh->W < 4 || p.KK > 64) return p;
-    if (sh->IC <= 4 && sh->KH <= 8 && sh->KW <= 8 && !(env_get("QE_F32_STEM") && atoi(env_get("QE_F32_STEM")) == 0)) {
+    const bool wide = sh->OC > 64;      // 4x1 waves x 7 column tiles (MT 128); otherwise 2x2 (MT 64)
+    if (sh->IC <= 4 && sh->KH <= 8 && sh->KW <= 8) {
         // the stem: K = kh x [kw][ic]; tile = whole output rows, as many as 448 / 224 pixel slots and 64 KB of LDS hold
         if ((int64_t)sh->IC * sh->H * sh->W >= (1ll << 29) || (int64_t)sh->OC * p.OH * p.OW >= (1ll << 29)) return p;
-        p.stem = true;
-        p.cfg = sh->OC > 64 ? 0 : 1;
-        p.MT = p.cfg == 0 ? 128 : 64;
-        p.OCP = (sh->OC + p.MT - 1) / p.MT * p.MT;
+        const int MT = wide ? 128 : 64;
+        p.OCP = (sh->OC + MT - 1) / MT * MT;
         p.NG = 1;
-        const int max_tiles = p.cfg == 0 ? 7 : 14;
-        if (p.OW > 32 * max_tiles) { p.stem = false; return p; }
+        const int max_tiles = wide ? 7 : 14;
+        if (p.OW > 32 * max_tiles) return p;
         for (int TH = std::min(p.OH, 32 * max_tiles / p.OW); TH >= 1; --TH) {
             const int IHT = (TH - 1) * sh->stride + sh->KH, IWP = (p.OW - 1) * sh->stride + 8;
             const size_t gsz = (size_t)IHT * IWP;
             const size_t lds = (3 * gsz + F32_TRASH) * 8 + gsz * 4;
             if (lds <= (size_t)F32_MAX_LDS) { p.TH = TH; p.IHT = IHT; p.IWP = IWP; p.lds = lds; break; }
         }
-        if (p.TH == 0) { p.stem = false; return p; }
+        if (p.TH == 0) return p;
+        p.stem = true;
         const int ni = (p.TH * p.OW + 31) / 32;
-        p.niw = p.cfg == 0 ? 7 : (ni <= 8 ? 4 : 7);          // 2 x 2 waves: 8 or 14 column slots
-        p.wt_bytes = (size_t)sh->KH * 2 * p.OCP * 16 * sizeof(uint16_t);
-        p.ep_off = f32_align(p.wt_bytes, 256);
-        p.total = f32_align(p.ep_off + (size_t)3 * p.OCP * sizeof(float), 256);
-        p.ok = true;
+        p.kernel = wide ? F32Kernel::Stem4x1x7 : (ni <= 8 ? F32Kernel::Stem2x2x4 : F32Kernel::Stem2x2x7);   // 2 x 2 waves: 8 or 14 column slots
+        f32_finish(p, sh, MT, (size_t)sh->KH * 2 * p.OCP * 16 * sizeof(uint16_t));
         return p;
     }
     if (sh->IC < 8) return p;                                               // 5..7 channels stay on the VALU kernel
     if ((int64_t)sh->IC * sh->H * sh->W * 8 >= (1ll << 31)) return p;       // 32-bit element offsets inside a tile's (<= 8) images
     if ((int64_t)sh->OC * p.OH * p.OW >= (1ll << 29)) return p;
-    p.cfg = sh->OC > 64 ? 0 : 1;
     // 3x3 on 7x7 maps: 64-channel workgroups (0.310 -> 0.247 ms on 512->512; every other layer is faster with 128)
-    if (sh->OC > 64 && p.KK == 9 && sh->stride == 1 && p.OH * p.OW <= 64) p.cfg = 1;
-    if (env_get("QE_F32_CFG")) p.cfg = atoi(env_get("QE_F32_CFG")) ? 1 : 0;        // tuning
-    p.MT = p.cfg == 0 ? 128 : 64;
-    const int max_tiles = p.cfg == 0 ? 7 : 8;
+    const bool w128 = wide && !(p.KK == 9 && sh->stride == 1 && p.OH * p.OW <= 64);
+    const int MT = w128 ? 128 : 64;
+    const int max_tiles = w128 ? 7 : 8;
     if (p.OW > 32 * max_tiles) return p;
-    p.OCP = (sh->OC + p.MT - 1) / p.MT * p.MT;
+    p.OCP = (sh->OC + MT - 1) / MT * MT;
     p.NG = (sh->IC + 15) / 16;
     p.ROWMUL = (sh->KH == 1) ? sh->stride : 1;
     p.COLMUL = (sh->KW == 1) ? sh->stride : 1;
@@ -722,86 +723,78 @@ static F32Plan f32_plan(const qe_conv_shape *sh)
             p.lds = (6 * gsz + F32_TRASH) * 16 + 2 * gsz * 4;
         }
     }
+    bool ns2 = false;
     {   // two groups per stage where threads and LDS allow and the K loop is long enough to matter
         const int units = p.GI * p.IHT * NQ;
         const size_t gsz = (size_t)p.GI * p.IHT * p.IWP;
         const size_t lds2 = (12 * gsz + F32_TRASH) * 16 + 4 * gsz * 4;
-        const bool ns2_env = !(env_get("QE_F32_NS") && atoi(env_get("QE_F32_NS")) == 1);
-        if (ns2_env && 4 * units <= F32_THREADS && lds2 <= (size_t)F32_MAX_LDS && p.NG >= 4) { p.NS = 2; p.lds = lds2; p.NG = (p.NG + 1) / 2 * 2; }
+        if (4 * units <= F32_THREADS && lds2 <= (size_t)F32_MAX_LDS && p.NG >= 4) { ns2 = true; p.lds = lds2; p.NG = (p.NG + 1) / 2 * 2; }
     }
-    p.wt_bytes = (size_t)p.KK * p.NG * p.OCP * 16 * sizeof(uint16_t);
-    if ((int64_t)p.wt_bytes >= (1ll << 31)) return p;
-    p.ep_off = f32_align(p.wt_bytes, 256);
-    p.total = f32_align(p.ep_off + (size_t)3 * p.OCP * sizeof(float), 256);
-    p.ok = true;
+    const size_t wt_bytes = (size_t)p.KK * p.NG * p.OCP * 16 * sizeof(uint16_t);
+    if ((int64_t)wt_bytes >= (1ll << 31)) return p;
+    const bool few = (p.GI * p.TH * p.OW + 31) / 32 <= 4;        // column tiles the tile really has
+    p.kernel = w128 ? (few ? (ns2 ? F32Kernel::M4x1x4S2 : F32Kernel::M4x1x4) : (ns2 ? F32Kernel::M4x1x7S2 : F32Kernel::M4x1x7))
+                    : (few ? (ns2 ? F32Kernel::M2x2x2S2 : F32Kernel::M2x2x2) : (ns2 ? F32Kernel::M2x2x4S2 : F32Kernel::M2x2x4));
+    f32_finish(p, sh, MT, wt_bytes);
     return p;
 }
 
-bool f32_conv_eligible(const qe_conv_shape *sh, const qe_qparam *w)
+static int f32_check_tables(const F32Plan &p, const void *prepared, size_t prepared_bytes)
 {
-    (void)w;
-    return f32_plan(sh).ok;
-}
-
-size_t f32_conv_prepared_bytes(const qe_conv_shape *sh)
-{
-    const F32Plan p = f32_plan(sh);
-    return p.ok ? p.total : 0;
-}
-
-// mode 0: prepare into `prepared` and run; 1: prepare only; 2: run on tables prepared earlier
-int launch_conv_f32(const float *x, const qe_qparam *w, const float *bias, const qe_conv_shape *sh, float *out,
-                    void *prepared, size_t prepared_bytes, hipStream_t s, int mode)
-{
-    const F32Plan p = f32_plan(sh);
     if (!p.ok) return QE_ERR_UNSUPPORTED;
     if (prepared == nullptr || prepared_bytes < p.total) return QE_ERR_WORKSPACE;
     if ((reinterpret_cast<uintptr_t>(prepared) & 15) != 0) return QE_ERR_ARG;
+    return QE_OK;
+}
+
+int prepare_conv_f32(const F32Plan &p, const qe_qparam *w, const float *bias, const qe_conv_shape *sh, void *prepared,
+                     size_t prepared_bytes, hipStream_t s)
+{
+    const int rc = f32_check_tables(p, prepared, prepared_bytes);
+    if (rc != QE_OK) return rc;
     uint8_t *wsp = static_cast<uint8_t *>(prepared);
-    if (mode != 2) {
-        F32PrepArgs pa;
-        pa.w = w->data; pa.w_scale = w->scale; pa.w_zero = w->zero; pa.bias = bias;
-        pa.w_bits = w->n_bits; pa.w_sign = w->sign; pa.w_per_tensor = (w->n_param == 1);
-        pa.OC = sh->OC; pa.IC = sh->IC; pa.KK = p.KK; pa.OCP = p.OCP; pa.NG = p.NG;
-        pa.wt = reinterpret_cast<uint16_t *>(wsp);
-        pa.ep = reinterpret_cast<float *>(wsp + p.ep_off);
-        if (p.stem) hipLaunchKernelGGL(conv_f32_prep_stem_kernel, dim3(p.OCP), dim3(64), 0, s, pa, (int)sh->KH, (int)sh->KW);
-        else hipLaunchKernelGGL(conv_f32_prep_kernel, dim3(p.OCP), dim3(256), 0, s, pa);
-        QE_LAUNCH_CHECK();
-        if (mode == 1) return QE_OK;
-    }
+    F32PrepArgs pa;
+    pa.w = w->data; pa.w_scale = w->scale; pa.w_zero = w->zero; pa.bias = bias;
+    pa.w_bits = w->n_bits; pa.w_sign = w->sign; pa.w_per_tensor = (w->n_param == 1);
+    pa.OC = sh->OC; pa.IC = sh->IC; pa.KK = p.KK; pa.OCP = p.OCP; pa.NG = p.NG;
+    pa.wt = reinterpret_cast<uint16_t *>(wsp);
+    pa.ep = reinterpret_cast<float *>(wsp + p.ep_off);
+    if (p.stem) hipLaunchKernelGGL(conv_f32_prep_stem_kernel, dim3(p.OCP), dim3(64), 0, s, pa, (int)sh->KH, (int)sh->KW);
+    else hipLaunchKernelGGL(conv_f32_prep_kernel, dim3(p.OCP), dim3(256), 0, s, pa);
+    QE_LAUNCH_CHECK();
+    return QE_OK;
+}
+
+int launch_conv_f32(const F32Plan &p, const float *x, const qe_conv_shape *sh, const void *prepared, size_t prepared_bytes,
+                    float *out, hipStream_t s)
+{
+    const int rc = f32_check_tables(p, prepared, prepared_bytes);
+    if (rc != QE_OK) return rc;
+    if (p.blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
+    const uint8_t *wsp = static_cast<const uint8_t *>(prepared);
     F32Args a;
     a.x = x; a.wt = reinterpret_cast<const uint16_t *>(wsp); a.ep = reinterpret_cast<const float *>(wsp + p.ep_off); a.out = out;
     a.N = sh->N; a.IC = sh->IC; a.H = sh->H; a.W = sh->W; a.OC = sh->OC; a.KH = sh->KH; a.KW = sh->KW;
     a.stride = sh->stride; a.pad = sh->padding; a.OH = p.OH; a.OW = p.OW;
-    a.OCP = p.OCP; a.NG = p.NG; a.TH = p.TH; a.tiles_h = (p.OH + p.TH - 1) / p.TH; a.GI = p.GI;
+    a.OCP = p.OCP; a.NG = p.NG; a.TH = p.TH; a.tiles_h = p.tiles_h; a.GI = p.GI;
     a.IHT = p.IHT; a.IWP = p.IWP; a.ROWMUL = p.ROWMUL; a.COLMUL = p.COLMUL;
-    a.n_pix_tiles = ((sh->N + p.GI - 1) / p.GI) * a.tiles_h;
-    a.n_oc_tiles = p.OCP / p.MT;
-    const int64_t per_xcd = ((int64_t)a.n_pix_tiles + 7) / 8;
-    a.chunk = (int)std::max<int64_t>(1, per_xcd);
-    const int64_t runs = ((int64_t)a.n_pix_tiles + a.chunk - 1) / a.chunk;
-    const int64_t blocks = (runs + 7) / 8 * a.chunk * 8 * a.n_oc_tiles;
-    if (blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
-    if (p.stem) {
-        if (p.cfg == 0) hipLaunchKernelGGL((conv_f32_stem_kernel<4, 1, 7>), dim3((unsigned)blocks), dim3(F32_THREADS), p.lds, s, a);
-        else if (p.niw == 4) hipLaunchKernelGGL((conv_f32_stem_kernel<2, 2, 4>), dim3((unsigned)blocks), dim3(F32_THREADS), p.lds, s, a);
-        else hipLaunchKernelGGL((conv_f32_stem_kernel<2, 2, 7>), dim3((unsigned)blocks), dim3(F32_THREADS), p.lds, s, a);
-        QE_LAUNCH_CHECK();
-        return QE_OK;
+    a.n_pix_tiles = p.n_pix_tiles; a.n_oc_tiles = p.n_oc_tiles; a.chunk = p.chunk;
+#define QE_F32_CASE(K, ...)                                                                                             \
+    case F32Kernel::K: hipLaunchKernelGGL((__VA_ARGS__), dim3((unsigned)p.blocks), dim3(F32_THREADS), p.lds, s, a); break
+    switch (p.kernel) {
+        QE_F32_CASE(Stem4x1x7, conv_f32_stem_kernel<4, 1, 7>);
+        QE_F32_CASE(Stem2x2x4, conv_f32_stem_kernel<2, 2, 4>);
+        QE_F32_CASE(Stem2x2x7, conv_f32_stem_kernel<2, 2, 7>);
+        QE_F32_CASE(M4x1x4, conv_f32_mfma_kernel<4, 1, 4, 1>);
+        QE_F32_CASE(M4x1x4S2, conv_f32_mfma_kernel<4, 1, 4, 2>);
+        QE_F32_CASE(M4x1x7, conv_f32_mfma_kernel<4, 1, 7, 1>);
+        QE_F32_CASE(M4x1x7S2, conv_f32_mfma_kernel<4, 1, 7, 2>);
+        QE_F32_CASE(M2x2x2, conv_f32_mfma_kernel<2, 2, 2, 1>);
+        QE_F32_CASE(M2x2x2S2, conv_f32_mfma_kernel<2, 2, 2, 2>);
+        QE_F32_CASE(M2x2x4, conv_f32_mfma_kernel<2, 2, 4, 1>);
+        QE_F32_CASE(M2x2x4S2, conv_f32_mfma_kernel<2, 2, 4, 2>);
     }
-    const int ni = (p.GI * p.TH * p.OW + 31) / 32;           // column tiles the tile really has
-#define QE_F32_LAUNCH(WM, WN, NIW)                                                                                              \
-    do {                                                                                                                        \
-        if (p.NS == 2) hipLaunchKernelGGL((conv_f32_mfma_kernel<WM, WN, NIW, 2>), dim3((unsigned)blocks), dim3(F32_THREADS), p.lds, s, a); \
-        else hipLaunchKernelGGL((conv_f32_mfma_kernel<WM, WN, NIW, 1>), dim3((unsigned)blocks), dim3(F32_THREADS), p.lds, s, a);           \
-    } while (0)
-    if (p.cfg == 0) {
-        if (ni <= 4) QE_F32_LAUNCH(4, 1, 4); else QE_F32_LAUNCH(4, 1, 7);
-    } else {
-        if (ni <= 4) QE_F32_LAUNCH(2, 2, 2); else QE_F32_LAUNCH(2, 2, 4);
-    }
-#undef QE_F32_LAUNCH
+#undef QE_F32_CASE
     QE_LAUNCH_CHECK();
     return QE_OK;
 }

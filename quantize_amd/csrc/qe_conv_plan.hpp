@@ -98,4 +98,31 @@ int launch_pwr(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, const 
 int launch_flatd(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, float *out, hipStream_t s,
                  const RequantHost *rq);
 
+// ---- float-input convolution (fp32 activations x packed weights, qe_conv_f32.hip) -------------------------------------
+// plan_conv_f32 is the only reader of QE_F32_MFMA (0: every shape stays on the VALU kernel) and decides the rest by shape.
+// !ok: the generic VALU kernel runs and nothing is prepared.
+enum class F32Kernel {         // <WM x WN waves x NIW column tiles per wave>, S2: two 16-channel groups per stage
+    Stem4x1x7, Stem2x2x4, Stem2x2x7,
+    M4x1x4, M4x1x4S2, M4x1x7, M4x1x7S2, M2x2x2, M2x2x2S2, M2x2x4, M2x2x4S2
+};
+
+struct F32Plan {
+    bool ok = false;
+    F32Kernel kernel = F32Kernel::M4x1x7;
+    bool stem = false;         // IC <= 4: K = kh x [kw 0..7][ic 0..3] (conv_f32_stem_kernel and its own table layout)
+    int OCP = 0, NG = 0, KK = 0, OH = 0, OW = 0;
+    int TH = 0, GI = 1, IHT = 0, IWP = 0, ROWMUL = 1, COLMUL = 1;
+    // XCD-aware block map, as ConvPlan's
+    int64_t blocks = 0;
+    int chunk = 1, n_pix_tiles = 0, n_oc_tiles = 0, tiles_h = 0;
+    size_t lds = 0;
+    size_t ep_off = 0, total = 0;      // prepared tables: [bf16 weights in fragment order | sw, zw, bias per padded channel]
+};
+
+F32Plan plan_conv_f32(const qe_conv_shape *sh);
+int prepare_conv_f32(const F32Plan &p, const qe_qparam *w, const float *bias, const qe_conv_shape *sh, void *prepared,
+                     size_t prepared_bytes, hipStream_t s);
+int launch_conv_f32(const F32Plan &p, const float *x, const qe_conv_shape *sh, const void *prepared, size_t prepared_bytes,
+                    float *out, hipStream_t s);
+
 }  // namespace qe

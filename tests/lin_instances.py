@@ -15,9 +15,6 @@ The first rows are real ViT layer shapes (S/16, B/16, L/16, H/14 at 1, 16, 64 an
 196 or 256 patches) that the planner places without knobs; the forced rows after them take each kernel to its edges.
 XQ[i % 3] is the activation quantiser of row i (the GPU tests draw the operands with it)."""
 
-import contextlib
-import os
-
 F32, CODES, CODES_GELU, RES = "F32", "CODES", "CODES_GELU", "RES"
 EPIS = (F32, CODES, CODES_GELU, RES)
 KERNEL = {0: "linear_generic_kernel<false>", 1: "linear_mfma_kernel<2>", 2: "linear_mfma_kernel<4>",
@@ -117,21 +114,3 @@ def every_instance():
     out = {(KERNEL[f], e) for f in (1, 2, 3, 4) for e in EPIS}
     out |= {(KERNEL[0], F32), (F_KERNEL[0], F32), (F_KERNEL[1], F32), (F_KERNEL[1], RES)}
     return out
-
-
-@contextlib.contextmanager
-def knobs(env, reload):
-    """Set a row's env (None: no knobs) around a block; `reload` re-reads the library's snapshot (capi.reload_env)."""
-    env = env or {}
-    old = {k: os.environ.get(k) for k in env}
-    try:
-        os.environ.update(env)
-        reload()
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-        reload()

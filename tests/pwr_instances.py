@@ -10,9 +10,6 @@ instance() restates only the launcher's dispatch (launch_pwr / launch_pwr7): whi
 once the planner has put it on the resident-tile route.  Whether the planner does is checked on the GPU (the tests assert
 the fused paths; a kernel trace names the instances)."""
 
-import contextlib
-import os
-
 PWR, PWR7 = "conv_pwr_kernel", "conv_pwr7_kernel"
 
 # (N, IC, H, W, OC, K, stride, pad)
@@ -114,22 +111,3 @@ def covered():
 
 def res_rows():
     return [r for r in ROWS if has_res(r[1])]
-
-
-@contextlib.contextmanager
-def knobs(env):
-    """QE_* knobs for the body (None: none); the library re-reads them on entry and again after they are restored."""
-    from quantize_amd import capi
-    env = env or {}
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    capi.reload_env()
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-        capi.reload_env()

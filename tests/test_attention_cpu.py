@@ -1,7 +1,6 @@
 """CPU: the attention core's C entry points are exported and declared, the kernel choice is a host-only answer, and
 qe_attention's argument checks answer before any device work (no GPU here: a device call would fail)."""
 import ctypes
-import os
 
 import pytest
 
@@ -30,18 +29,9 @@ def test_attention_path_unsupported(L, S, H, d):
 
 
 def test_attention_knob_forces_the_valu_kernel():
-    old = os.environ.get("QE_ATTN")
-    os.environ["QE_ATTN"] = "0"
-    capi.reload_env()
-    try:
+    with capi.knobs(QE_ATTN="0"):
         assert capi.attention_path(197, 197, 12, 64) == 0
         assert capi.attention_path(17, 17, 4, 20) == 0
-    finally:
-        if old is None:
-            os.environ.pop("QE_ATTN", None)
-        else:
-            os.environ["QE_ATTN"] = old
-        capi.reload_env()
     assert capi.attention_path(197, 197, 12, 64) == 1
 
 

@@ -5,9 +5,6 @@ Tolerance, per case: e_q = max |engine - ref64| and e_t = max |torch fp32 SDPA -
 e_q <= max(4 e_t, 1e-6 max|V|) and e_q <= 1e-5 max|V|.  Two score regimes: moderate (|scores| <~ 5) and peaky (|scores| up to
 ~60, each row's maximum in the last, ragged key tile: a missing online-softmax rescale or an exp overflow shows there).
 The output is pre-filled with NaN, so every element the kernel leaves unwritten fails the finiteness check."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -22,24 +19,6 @@ DEV = "cuda:0"
 # at d = 128, and VALU-only head sizes (d = 20, d = 136)
 CASES = [(2, 197, 197, 12, 64), (1, 50, 50, 12, 64), (2, 257, 257, 16, 80), (3, 17, 17, 4, 16), (2, 1, 1, 2, 64),
          (2, 33, 65, 3, 32), (1, 197, 197, 1, 128), (2, 37, 45, 3, 20), (1, 40, 70, 2, 136)]
-
-
-@contextlib.contextmanager
-def _knob(value):
-    old = os.environ.get("QE_ATTN")
-    if value is None:
-        os.environ.pop("QE_ATTN", None)
-    else:
-        os.environ["QE_ATTN"] = value
-    capi.reload_env()
-    try:
-        yield
-    finally:
-        if old is None:
-            os.environ.pop("QE_ATTN", None)
-        else:
-            os.environ["QE_ATTN"] = old
-        capi.reload_env()
 
 
 def _inputs(N, L, S, H, d, regime, seed):
@@ -120,7 +99,7 @@ def test_attention_vs_float64(case, regime):
     e_t = float(np.abs(_torch_sdpa(q, k, v) - ref).max())
     vmax = float(np.abs(v).max())
     for kern in _kernels(L, S, H, d):
-        with _knob(None if kern == "mfma" else "0"):
+        with capi.knobs(QE_ATTN=None if kern == "mfma" else "0"):
             assert capi.attention_path(L, S, H, d) == (1 if kern == "mfma" else 0)
             for layout in ("token", "seq"):
                 got = _run(q, k, v, layout)
@@ -140,7 +119,7 @@ def test_nan_locality(case):
     kn = k.copy()
     kn[0, 3, 1, 4] = np.nan
     for kern in _kernels(L, S, H, d):
-        with _knob(None if kern == "mfma" else "0"):
+        with capi.knobs(QE_ATTN=None if kern == "mfma" else "0"):
             for layout in ("token", "seq"):
                 got = _run(qn, k, v, layout)
                 bad = ~np.isfinite(got)

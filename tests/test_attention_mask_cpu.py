@@ -3,7 +3,6 @@ argument error of qe_attention_masked answers before any device work, the float6
 (tests/attention_ref.py) agrees with torch's own masked attention on the CPU -- which pins the bool polarity and the
 top-left causal alignment before any GPU is involved -- and PackedMultiheadAttention validates its mask arguments."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
@@ -43,19 +42,10 @@ def test_masked_path_unsupported(L, S, H, d):
 
 
 def test_masked_path_never_mfma_under_the_knob():
-    old = os.environ.get("QE_ATTN")
-    os.environ["QE_ATTN"] = "0"
-    capi.reload_env()
-    try:
+    with capi.knobs(QE_ATTN="0"):
         for shape in ((197, 197, 12, 64), (77, 77, 8, 64), (17, 17, 4, 20)):
             for m, b, c in OPERANDS:
                 assert capi.attention_masked_path(*shape, m, b, c) == 0, (shape, m, b, c)
-    finally:
-        if old is None:
-            os.environ.pop("QE_ATTN", None)
-        else:
-            os.environ["QE_ATTN"] = old
-        capi.reload_env()
     assert capi.attention_masked_path(197, 197, 12, 64, 1, 1, 1) == 1
 
 

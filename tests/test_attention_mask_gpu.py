@@ -69,7 +69,7 @@ def _torch_sdpa(q, k, v, m):
 
 def _each_kernel(L, S, H, d):
     for kern in base._kernels(L, S, H, d):
-        with base._knob(None if kern == "mfma" else "0"):
+        with capi.knobs(QE_ATTN=None if kern == "mfma" else "0"):
             assert capi.attention_masked_path(L, S, H, d, 1, 1, 1) == (1 if kern == "mfma" else 0)
             for layout in ("token", "seq"):
                 yield kern, layout

@@ -2,8 +2,6 @@
 x integer weight codes) vs the oracle.  Bar: |out - exact64| <= max(1e-5, |reference fp32 chain - exact64|) (the
 reference's own sequential chain, as written and contracted), and plain 1e-5 on the ResNet-50 layer shapes at the
 headline weight scales.  The order-preserving VALU kernel stays bit-identical to the contracted chain."""
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -100,17 +98,10 @@ def test_prepared_and_valu_forms():
 
 def test_env_switch_keeps_valu_kernel(engine):
     rng = np.random.RandomState(13)
-    old = os.environ.get("QE_F32_MFMA")
-    os.environ["QE_F32_MFMA"] = "0"
-    try:
+    with capi.knobs(QE_F32_MFMA="0"):
         case = _random_case(rng, 2, 64, 14, 14, 48, 3, 1, 1, 8, 1, 0, 0, w_pc=True, a_pc=False, zeros=True, bias=True)
         y, o32, o64 = _run_case(engine, case, via_capi=False)
         assert case["path"] == 0 and np.array_equal(y, case["fma"])
-    finally:
-        if old is None:
-            os.environ.pop("QE_F32_MFMA", None)
-        else:
-            os.environ["QE_F32_MFMA"] = old
 
 
 def test_non_finite_activations_declared_behaviour(engine):
@@ -126,6 +117,7 @@ def test_non_finite_activations_declared_behaviour(engine):
         wp, wd = engine.tpack(qw, 8, True)
         sw = (torch.rand(OC, generator=g, device="cuda") * 5e-4 + 2.5e-4).reshape(OC, 1, 1, 1)
         zw = torch.zeros(OC, 1, 1, 1, device="cuda")
+        assert capi.float_input_path(capi.conv_shape(N, IC, H, H, OC, K, K, s, p), capi.qparam(wp, 8, 1, sw, zw)) == 1, (IC, K)
         bad = [(0, 3, 5, 6, float("inf")), (1, 10, 0, 13, float("-inf")), (1, 20, 9, 2, float("nan"))]
         xb, xc = x.clone(), x.clone()
         for (n, c, h, w, v) in bad:

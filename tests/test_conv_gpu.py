@@ -120,7 +120,6 @@ def _random_case(rng, N, IC, H, W, OC, K, stride, pad, wb, wsgn, ab, asgn, w_pc,
 
 
 def _run_case(engine, case, via_capi=False):
-    capi.reload_env()      # the library snapshots the QE_* knobs once per process; tests flip them between cases
     wp, wd, sw, zw = case["w"]
     w = (_t(wp), _t(wd), _t(sw).reshape(-1, 1, 1, 1), _t(zw).reshape(-1, 1, 1, 1))  # (C,1,1,1) as QuantConv2d stores it
     bias = None if case["bias"] is None else _t(case["bias"])
@@ -287,11 +286,8 @@ def test_conv_error_messages(engine):
 def test_kernel_variants_forced_by_env(engine, env):
     """The tuning knobs select other kernel variants (two-strip / warp-specialised / single-role 3x3, flat tile widths,
     block maps); every variant must meet the same parity bar."""
-    import os
     rng = np.random.RandomState(17)
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
+    with capi.knobs(**env):
         for shp in [(2, 256, 14, 14, 256, 3, 1, 1), (3, 128, 28, 28, 128, 3, 1, 1), (4, 160, 7, 7, 130, 3, 1, 1),
                     (2, 128, 14, 14, 192, 3, 2, 1), (2, 256, 28, 28, 160, 1, 1, 0), (5, 64, 7, 7, 48, 3, 1, 1),
                     (9, 96, 30, 30, 130, 3, 2, 1), (2, 128, 56, 56, 160, 1, 2, 0), (3, 256, 14, 14, 140, 1, 2, 0),
@@ -300,13 +296,6 @@ def test_kernel_variants_forced_by_env(engine, env):
                 case = _random_case(rng, *shp, 8, 1, 8, 0 if zeros else 1, w_pc=True, a_pc=False, zeros=zeros, bias=True)
                 y, o32, o64 = _run_case(engine, case, via_capi=True)
                 _assert_conv_close(y, o64, o32, "%s %s zeros=%s" % (env, shp, zeros), case["fma"])
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-        capi.reload_env()
 
 
 @pytest.mark.parametrize("x4", ["1", "0"])
@@ -314,11 +303,8 @@ def test_sub8_activation_paths(engine, x4):
     """b < 8 activations are expanded once to 8-bit codes in the workspace and run on the 8-bit kernels, or -- 4-bit
     activations on stride-1 1x1 layers -- are unpacked by the flat kernel's own staging (QE_X4, default on; QE_X4=0:
     the expansion pass there too); both meet the parity bar, incl. asymmetric zero points."""
-    import os
     rng = np.random.RandomState(23)
-    oldx = os.environ.get("QE_X4")
-    os.environ["QE_X4"] = x4
-    try:
+    with capi.knobs(QE_X4=x4):
         for shp in [(2, 64, 28, 28, 160, 1, 1, 0), (2, 128, 14, 14, 130, 3, 1, 1), (3, 64, 56, 56, 64, 3, 1, 1),
                     (2, 3, 37, 41, 24, 7, 2, 3), (2, 96, 28, 28, 130, 1, 2, 0), (5, 96, 7, 7, 64, 1, 1, 0),
                     (2, 256, 56, 56, 130, 1, 1, 0), (3, 160, 14, 14, 200, 1, 1, 0), (2, 48, 10, 18, 136, 1, 1, 0)]:
@@ -328,13 +314,6 @@ def test_sub8_activation_paths(engine, x4):
                     y, o32, o64 = _run_case(engine, case, via_capi=True)
                     assert case["path"] == 1
                     _assert_conv_close(y, o64, o32, "x4=%s %s %s zeros=%s" % (x4, shp, (wb, wsgn, ab, asgn), zeros), case["fma"])
-    finally:
-        for k, v in (("QE_X4", oldx),):
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-        capi.reload_env()
 
 
 def test_4bit_weights_on_flat_kernels(engine):
@@ -459,11 +438,8 @@ def test_4bit_activations_on_strided_1x1(engine, sub_x4):
     """4-bit activations of a stride-2 1x1 layer: one pass picks the even nibbles of the even rows and writes dense 8-bit
     codes (QE_SUB_X4, default on) instead of expanding the whole tensor first; signed and unsigned codes, row lengths that
     are not a multiple of 8 output pixels, planes from 56x56 down to 14x14, with the pass disabled as well."""
-    import os
     rng = np.random.RandomState(77)
-    old = os.environ.get("QE_SUB_X4")
-    os.environ["QE_SUB_X4"] = sub_x4
-    try:
+    with capi.knobs(QE_SUB_X4=sub_x4):
         for shp in [(2, 128, 56, 56, 160, 1, 2, 0), (3, 256, 14, 14, 140, 1, 2, 0), (2, 64, 28, 28, 130, 1, 2, 0),
                     (2, 64, 30, 26, 40, 1, 2, 0), (3, 96, 12, 6, 72, 1, 2, 0)]:
             for (wb, wsgn, asgn) in [(8, 1, 1), (4, 1, 0)]:
@@ -472,12 +448,6 @@ def test_4bit_activations_on_strided_1x1(engine, sub_x4):
                     y, o32, o64 = _run_case(engine, case, via_capi=True)
                     assert case["path"] == 1
                     _assert_conv_close(y, o64, o32, "sub_x4=%s %s %s zeros=%s" % (sub_x4, shp, (wb, wsgn, asgn), zeros), case["fma"])
-    finally:
-        if old is None:
-            os.environ.pop("QE_SUB_X4", None)
-        else:
-            os.environ["QE_SUB_X4"] = old
-        capi.reload_env()
 
 
 def test_resnet50_shapes_w4a4(engine):
@@ -542,7 +512,6 @@ def test_unaligned_fp32_out_falls_back(engine):
     """A 7x7 layer whose fp32 `out` starts 4 bytes past a 16-byte boundary (default knobs): the resident-tile kernel that
     takes the aligned call stores 16-byte pieces, so the plan picks another kernel instead of failing, and the result meets
     the oracle."""
-    capi.reload_env()
     rng = np.random.RandomState(405)
     case = _random_case(rng, 4, 512, 7, 7, 2048, 1, 1, 0, 8, 1, 8, 1, w_pc=True, a_pc=False, zeros=False, bias=True)
     wp, wd, sw, zw = case["w"]

@@ -2,8 +2,6 @@
 images with byte-aligned planes, the patched last bytes of the tensor, ragged output-channel tiles and image groups, 2..32
 stages, symmetric and asymmetric operands (S_x / S_w terms), each also with the kernel disabled (QE_FLATD=0).  The larger
 planes of SHAPES take the kernels the planner picks for them (resident-tile, register-staged flat) in both runs."""
-import os
-
 import numpy as np
 import pytest
 
@@ -35,9 +33,7 @@ SHAPES = [
 def test_flatd_vs_oracle(engine, flatd):
     """flatd = QE_FLATD (1 = the DMA ring kernel on 7x7 planes, the default; 0 = register-staged kernels only)."""
     rng = np.random.RandomState(2024)
-    old = os.environ.get("QE_FLATD")
-    os.environ["QE_FLATD"] = flatd
-    try:
+    with capi.knobs(QE_FLATD=flatd):
         for shp in SHAPES:
             for (asgn, zeros) in [(1, False), (0, True), (1, True)]:
                 case = _random_case(rng, *shp, 8, 1 if asgn else 0, 8, asgn, w_pc=True, a_pc=False, zeros=zeros, bias=True)
@@ -46,10 +42,3 @@ def test_flatd_vs_oracle(engine, flatd):
                 _assert_conv_close(y, o64, o32, "flatd=%s %s asgn=%d zeros=%s" % (flatd, shp, asgn, zeros), case["fma"])
                 if not zeros:
                     assert np.abs(y.astype(np.float64) - o64).max() <= 1e-5
-    finally:
-        for k, v in (("QE_FLATD", old),):
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-        capi.reload_env()

@@ -16,7 +16,7 @@ def _q():
 
 def test_rows_name_their_planned_kernel():
     for B, K, O, env, form, note in li.ROWS:
-        with li.knobs(env, capi.reload_env):
+        with capi.knobs(**(env or {})):
             got = capi.linear_form(_q(), _q(), B, K, O)
         assert got == form, "%s (%s, env %s): the planner picks %s, the row says %s" % (
             (B, K, O), note, env, capi.LINEAR_FORMS[got], capi.LINEAR_FORMS[form])
@@ -25,7 +25,7 @@ def test_rows_name_their_planned_kernel():
 def test_float_input_rows_name_their_kernel():
     L = capi.lib()
     for B, K, O, env, form, note in li.F_ROWS:
-        with li.knobs(env, capi.reload_env):
+        with capi.knobs(**(env or {})):
             got = int(L.qe_quantlinear_float_input_path(ALIGNED, ctypes.byref(_q()), B, K, O))
         assert got == form, ((B, K, O), note, env, got)
 
@@ -63,9 +63,9 @@ def test_rows_reach_the_edges():
 
 def test_query_follows_the_knobs():
     q = _q()
-    with li.knobs({"QE_LIN_NJ": "2", "QE_LIN8": "1"}, capi.reload_env):
+    with capi.knobs(QE_LIN_NJ="2", QE_LIN8="1"):
         assert capi.linear_form(q, q, 12608, 3072, 768) == 1        # QE_LIN_NJ rules out the big tiles
-    with li.knobs({"QE_LIN8": "0"}, capi.reload_env):
+    with capi.knobs(QE_LIN8="0"):
         assert capi.linear_form(q, q, 12608, 3072, 768) == 2
     assert capi.linear_form(q, q, 12608, 3072, 768, dst_aligned=False) == 2   # big tiles store whole 16-byte pieces
     assert capi.linear_form(q, q, 12608, 3000, 768) == 0                       # K % 64 != 0
@@ -82,7 +82,7 @@ def test_queries_answer_from_one_plan():
     rq_path = lambda B, K, O, r, codes=ALIGNED: int(L.qe_quantlinear_requant_path(q, q, B, K, O, r, codes))
     for B, K, O, env, form, note in li.ROWS:
         row = ((B, K, O), note, env)
-        with li.knobs(env, capi.reload_env):
+        with capi.knobs(**(env or {})):
             fused = int(form != 0)
             assert capi.linear_path(q, q, B, K, O) == fused, row
             assert rq_path(B, K, O, rq(8, 1)) == fused, row
@@ -95,14 +95,14 @@ def test_queries_answer_from_one_plan():
             assert rq_path(B, K, O, rq(4, 1)) == 0, row
             assert rq_path(B, K, O, rq(8, 1), ALIGNED + 4) == 0, row
             assert int(L.qe_quantlinear_requant_workspace_bytes(q, q, B, K, O, rq(4, 1), ALIGNED)) == B * O * 4, row
-        with li.knobs(dict(env or {}, QE_LIN_EPI="0"), capi.reload_env):
+        with capi.knobs(**dict(env or {}, QE_LIN_EPI="0")):
             assert rq_path(B, K, O, rq(8, 1)) == 0 and capi.linear_residual_path(q, q, B, K, O) == 0, row
             assert int(L.qe_quantlinear_residual_workspace_bytes(q, q, B, K, O)) == B * O * 4, row
     for B, K, O, env, form, note in li.F_ROWS:
         row = ((B, K, O), note, env)
-        with li.knobs(env, capi.reload_env):
+        with capi.knobs(**(env or {})):
             assert int(L.qe_quantlinear_float_input_residual_path(ALIGNED, q, B, K, O)) == form, row
             ws = int(L.qe_quantlinear_float_input_residual_workspace_bytes(ALIGNED, q, B, K, O))
             assert ws == (0 if form else B * O * 4), row
-        with li.knobs(dict(env or {}, QE_LIN_EPI="0"), capi.reload_env):
+        with capi.knobs(**dict(env or {}, QE_LIN_EPI="0")):
             assert int(L.qe_quantlinear_float_input_residual_path(ALIGNED, q, B, K, O)) == 0, row

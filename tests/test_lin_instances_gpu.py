@@ -115,7 +115,7 @@ def test_linear_row_every_epilogue(i):
     xq, wq, bias = op["xq"], op["wq"], op["bias"]
     rows = _sample_rows(B)
     idx = torch.from_numpy(rows).to(DEV)
-    with li.knobs(env, capi.reload_env):
+    with capi.knobs(**(env or {})):
         assert capi.linear_form(xq, wq, B, K, O) == form, note
         assert capi.linear_path(xq, wq, B, K, O) == (form != 0)
         # F32
@@ -168,7 +168,7 @@ def test_float_input_row_every_epilogue(i):
     wq = capi.qparam(wu, 8, True, ws, wz)
     rows = _sample_rows(B)
     idx = torch.from_numpy(rows).to(DEV)
-    with li.knobs(env, capi.reload_env):
+    with capi.knobs(**(env or {})):
         assert capi.linear_float_input_path(x, wq, B, K, O) == form, note
         y = capi.quantlinear_float_input(x, wq, bias, O)
         torch.cuda.synchronize()

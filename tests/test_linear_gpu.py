@@ -178,7 +178,7 @@ def test_random_sweep_vs_oracle(engine, via_capi):
     assert len(seen_f32_mfma) >= 6      # quantlinear_float_input ran on the matrix cores for the 8-bit-weight, K % 32 == 0 shapes
 
 
-def test_float_input_mfma_vit_shapes(engine, monkeypatch):
+def test_float_input_mfma_vit_shapes(engine):
     """quantlinear_float_input on the bf16 x 3 MFMA kernel at ViT-B/16 shapes (the 'float route' of a packed Linear): absolute
     1e-5 against the float64-exact value at the headline scales, ragged rows / columns, asymmetric weights; and the same
     problem on the fp32 chain kernel (QE_LIN_F32_MFMA=0) stays bit-identical to the oracle's fused chain."""
@@ -202,12 +202,9 @@ def test_float_input_mfma_vit_shapes(engine, monkeypatch):
         assert capi.linear_float_input_residual_path(xt, wq, B, K, O) == 1
         out = capi.quantlinear_float_input_residual(xt, wq, _t(cz["bias"]), O, res)
         assert torch.equal(out, y + res)
-    monkeypatch.setenv("QE_LIN_F32_MFMA", "0")
-    capi.reload_env()
-    y0, path0 = _run(engine, c, True)
+    with capi.knobs(QE_LIN_F32_MFMA="0"):
+        y0, path0 = _run(engine, c, True)
     assert path0 == 0 and np.array_equal(y0.cpu().numpy(), c["fma"])
-    monkeypatch.delenv("QE_LIN_F32_MFMA")
-    capi.reload_env()
 
 
 def test_vit_shapes_and_row_independence(engine):
@@ -281,28 +278,23 @@ def test_deep_reductions_leave_the_int32_kernel():
     assert capi.linear_path(xq, wq, 4, 1 << 17, 4) == 0
 
 
-def test_big_tile_kernel_forced(engine, monkeypatch):
+def test_big_tile_kernel_forced(engine):
     """linear_mfma8_kernel (320 x 256 tiles, 8 waves) forced onto the sweep shapes it is eligible for (ragged row and column
     counts, per-row activation scales, asymmetric operands, 1 to 48 stages): against the oracle and, bit for bit, against
     the 128 x 256 kernel (same integer sums, same epilogue operation order)."""
-    from quantize_amd import capi as _capi
     rng = np.random.RandomState(11)
     k = 0
     for shp in [(330, 768, 256), (129, 3072, 256), (200, 1024, 512), (700, 128, 512), (321, 256, 256), (640, 3072, 256), (64, 768, 130), (1, 128, 4)]:
         for (wsgn, asgn) in [(1, 1), (0, 0), (1, 0)]:
             k += 1
             c = _random_case(rng, *shp, 8, wsgn, 8, asgn, w_pc=k % 2 == 0, a_pr=k % 3 != 0, zeros=k % 4 != 0, bias=k % 5 != 0)
-            monkeypatch.setenv("QE_LIN8", "0")
-            _capi.reload_env()
-            y4, _ = _run(engine, c, True)
-            torch.cuda.synchronize()
-            for form in ("1", "2"):                  # 8 waves / 320-row tiles; 4 waves / 160-row tiles, one stage buffer
-                monkeypatch.setenv("QE_LIN8", form)
-                _capi.reload_env()
-                y8, path = _run(engine, c, True)
+            with capi.knobs(QE_LIN8="0"):
+                y4, _ = _run(engine, c, True)
                 torch.cuda.synchronize()
+            for form in ("1", "2"):                  # 8 waves / 320-row tiles; 4 waves / 160-row tiles, one stage buffer
+                with capi.knobs(QE_LIN8=form):
+                    y8, path = _run(engine, c, True)
+                    torch.cuda.synchronize()
                 assert path == 1
                 _close(y8.cpu().numpy(), c["o64"], c["o32"], "big tile %s form %s" % (shp, form), c["fma"])
                 assert torch.equal(y8, y4), (shp, form)
-    monkeypatch.delenv("QE_LIN8")
-    _capi.reload_env()

@@ -3,8 +3,6 @@ adds in the linears' epilogues, the patch embedding as a GEMM) gives bit for bit
 fused epilogues as with their two-pass forms (QE_LIN_EPI=0), follows the layers route (the reference's dataflow with the
 engine plugged in) up to LayerNorm / GELU rounding, never synchronises with the host under check=False, and raises on a
 NaN image."""
-import os
-
 import pytest
 import torch
 import torch.nn.functional as F
@@ -40,26 +38,15 @@ def _images(N, arch, seed):
     return torch.randn(N, 3, s, s, generator=g).to(DEV)
 
 
-def _epi(on):
-    if on:
-        os.environ.pop("QE_LIN_EPI", None)
-    else:
-        os.environ["QE_LIN_EPI"] = "0"
-    capi.reload_env()
-
-
 @pytest.mark.parametrize("arch,N", [("vit_tiny_test", 2), ("vit_tiny_test", 5), ("vit_b_16", 1), ("vit_b_16", 2), ("vit_b_16", 3),
                                     ("vit_s16_shape", 3), ("vit_h14_shape", 2)])
 def test_fused_epilogues_equal_two_pass(models, arch, N):
     m = models[arch]
     x = _images(N, arch, N)
-    try:
-        _epi(True)
+    with capi.knobs(QE_LIN_EPI=None):
         l1, b1 = m.forward(x, "fused", keep_blocks=True)
-        _epi(False)
+    with capi.knobs(QE_LIN_EPI="0"):
         l0, b0 = m.forward(x, "fused", keep_blocks=True)
-    finally:
-        _epi(True)
     assert torch.isfinite(l1).all() and l1.std() > 0
     assert torch.equal(l1, l0)
     for a, b in zip(b1, b0):

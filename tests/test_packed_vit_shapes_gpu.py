@@ -2,8 +2,6 @@
 fc1 and the patch GEMM on the 4-wave 160 x 256 kernel and fc2 on the 8-wave 320 x 256 kernel: the layers' kernels are asserted
 (a planner change fails here instead of quietly testing something else), and the fused route with its fused epilogues gives
 bit for bit the logits and block outputs of their two-pass forms (QE_LIN_EPI=0)."""
-import os
-
 import pytest
 import torch
 
@@ -19,14 +17,6 @@ N = 64
 def vit_b():
     sd = calibrated_state_dict("vit_b_16", device=DEV, seed=0)
     return PackedViT.from_state_dict(sd, CONFIGS["vit_b_16"]["heads"])
-
-
-def _epi(on):
-    if on:
-        os.environ.pop("QE_LIN_EPI", None)
-    else:
-        os.environ["QE_LIN_EPI"] = "0"
-    capi.reload_env()
 
 
 def test_layer_kernels_at_64_images(vit_b):
@@ -48,13 +38,10 @@ def test_layer_kernels_at_64_images(vit_b):
 def test_fused_epilogues_equal_two_pass_at_64_images(vit_b):
     g = torch.Generator(device="cpu").manual_seed(64)
     x = torch.randn(N, 3, 224, 224, generator=g).to(DEV)
-    try:
-        _epi(True)
+    with capi.knobs(QE_LIN_EPI=None):
         l1, b1 = vit_b.forward(x, "fused", keep_blocks=True)
-        _epi(False)
+    with capi.knobs(QE_LIN_EPI="0"):
         l0, b0 = vit_b.forward(x, "fused", keep_blocks=True)
-    finally:
-        _epi(True)
     assert torch.isfinite(l1).all() and l1.std() > 0
     assert torch.equal(l1, l0)
     assert len(b1) == len(b0) == 12

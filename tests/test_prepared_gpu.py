@@ -135,13 +135,8 @@ def test_prepared_tables_serve_every_batch_size():
     (no tables) and the halo kernel at N = 3 (reads them): prepared once at N = 4 into a buffer of 0xFF bytes, both
     batch sizes meet the oracle."""
     import ctypes
-    import os
     from conftest import conv_tolerance
-    knobs = {"QE_FLATG": "0", "QE_FLATD": "0"}
-    old = {k: os.environ.get(k) for k in knobs}
-    os.environ.update(knobs)
-    capi.reload_env()
-    try:
+    with capi.knobs(QE_FLATG="0", QE_FLATD="0"):
         rng = np.random.RandomState(404)
         case = _random_case(rng, 4, 512, 7, 7, 2048, 1, 1, 0, 8, 1, 8, 1, w_pc=True, a_pc=False, zeros=False, bias=True)
         wp, wd, sw, zw = case["w"]
@@ -164,10 +159,3 @@ def test_prepared_tables_serve_every_batch_size():
             _, o64 = oracle.quantconv2d(xpn, xdn, sx, zx, wp, wd, sw, zw, case["bias"], 1, 0, mode="f64", return_f64=True)
             err, allowed = conv_tolerance(y, o64, *chains)
             assert (err <= allowed).all(), "N=%d: worst err %.3g (allowed %.3g)" % (n, float(np.nanmax(err)), allowed)   # NaN fails
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-        capi.reload_env()

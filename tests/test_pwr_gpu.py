@@ -3,8 +3,6 @@ are one tile (14x14: the 4-byte patched tail of the tensor), several tiles (28x2
 4-byte aligned, one to sixteen strips per wave, channel groups (QE_PWR_GROUPS), more tiles than XCDs, symmetric and asymmetric operands
 (S_x / S_w terms), per-tensor weight scales, no bias -- each also with the kernel disabled (QE_PWR=0), and a batch-256
 launch checked by batch independence."""
-import os
-
 import numpy as np
 import pytest
 
@@ -41,29 +39,13 @@ SHAPES = [
 ]
 
 
-def _with_env(env, fn):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    capi.reload_env()
-    try:
-        return fn()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-        capi.reload_env()      # the library snapshots the QE_* knobs: no stale value may reach a later test
-
-
 @pytest.mark.parametrize("pwr", ["1", "0"])
 def test_pwr_vs_oracle(engine, pwr):
     """pwr = 1: every eligible layer on the resident-tile kernel (one tile per workgroup; the patched
     tail of the tensor in a late tile); 0: kernel disabled."""
     rng = np.random.RandomState(4242)
     env = {"QE_PWR": "0" if pwr == "0" else "2"}      # 2: every eligible layer (default 1 = whole-plane tiles only)
-
-    def run():
+    with capi.knobs(**env):
         for shp in SHAPES:
             for (asgn, zeros, w_pc, bias) in [(1, False, True, True), (0, True, True, True), (1, True, False, False)]:
                 case = _random_case(rng, *shp, 8, 1 if asgn else 0, 8, asgn, w_pc=w_pc, a_pc=False, zeros=zeros, bias=bias)
@@ -72,7 +54,6 @@ def test_pwr_vs_oracle(engine, pwr):
                 _assert_conv_close(y, o64, o32, "pwr=%s %s asgn=%d zeros=%s w_pc=%s" % (pwr, shp, asgn, zeros, w_pc), case["fma"])
                 if not zeros:
                     assert np.abs(y.astype(np.float64) - o64).max() <= 1e-5
-    _with_env(env, run)
 
 
 def test_pwr_every_instance_vs_oracle(engine):
@@ -82,7 +63,7 @@ def test_pwr_every_instance_vs_oracle(engine):
     variants = [(1, False, True, True), (0, True, True, True), (1, True, False, False)]
     for i, (shp, base, note, env) in enumerate(pwr_instances.ROWS):
         asgn, zeros, w_pc, bias = variants[i % len(variants)]
-        with pwr_instances.knobs(env):
+        with capi.knobs(**(env or {})):
             case = _random_case(rng, *shp, 8, 1 if asgn else 0, 8, asgn, w_pc=w_pc, a_pc=False, zeros=zeros, bias=bias)
             y, o32, o64 = _run_case(engine, case, via_capi=True)
         assert case["path"] == 1
@@ -106,7 +87,7 @@ def test_pwr_unaligned_fp32_out(engine, shape):
     chains = [oracle.quantconv2d(xp, xd, sx, zx, wp, wd, sw, zw, case["bias"], 1, 0, mode=m) for m in ("fp32", "fp32_fma")]
     _, o64 = oracle.quantconv2d(xp, xd, sx, zx, wp, wd, sw, zw, case["bias"], 1, 0, mode="f64", return_f64=True)
     n = N * OC * H * W
-    with pwr_instances.knobs({"QE_PWR": "2"}):
+    with capi.knobs(QE_PWR="2"):
         assert capi.conv_path(sh, xq, wq) == 1
         for off in (1, 2, 3):
             buf = torch.full((n + 8,), -7.5, dtype=torch.float32, device=DEV)
@@ -123,18 +104,17 @@ def test_pwr_unaligned_fp32_out(engine, shape):
 @pytest.mark.parametrize("groups", ["2", "4"])
 def test_pwr_channel_groups(engine, groups):
     rng = np.random.RandomState(77)
-
-    def run():
+    with capi.knobs(QE_PWR="2", QE_PWR_GROUPS=groups):
         for shp in [(2, 256, 14, 14, 1024, 1, 1, 0), (1, 128, 28, 28, 512, 1, 1, 0), (1, 64, 56, 56, 256, 1, 1, 0)]:
             case = _random_case(rng, *shp, 8, 0, 8, 1, w_pc=True, a_pc=False, zeros=True, bias=True)
             y, o32, o64 = _run_case(engine, case, via_capi=True)
             _assert_conv_close(y, o64, o32, "groups=%s %s" % (groups, shp), case["fma"])
-    _with_env({"QE_PWR": "2", "QE_PWR_GROUPS": groups}, run)
 
 
 def test_pwr_batch256_independence(engine):
     """The batch-256 launch geometry (256 / 1024 / 3584 workgroups): image i of the batched call == the same image alone."""
-    _with_env({"QE_PWR": "2"}, lambda: _batch256_independence(engine))
+    with capi.knobs(QE_PWR="2"):
+        _batch256_independence(engine)
 
 
 def _batch256_independence(engine):

@@ -56,48 +56,38 @@ def _case_tensors(case):
     return sh, xq, wq, bias
 
 
-@pytest.fixture
-def fresh_env():
-    """The library reads QE_* once per process: re-read after the test's monkeypatch is undone."""
-    yield
-    import os
-    os.environ.pop("QE_PWR_RQ", None)
-    capi.reload_env()
-
-
 @pytest.mark.parametrize("sign,pwr_rq", [(True, "1"), (False, "1"), (True, "0")])
-def test_requant_equals_conv_then_quantize_pack(engine, sign, pwr_rq, monkeypatch, fresh_env):
+def test_requant_equals_conv_then_quantize_pack(engine, sign, pwr_rq):
     """pwr_rq = 0: the resident-tile kernel's re-quantising instances off -- the flat kernels' fused epilogue against the
     fp32 output of the resident-tile kernel (two kernels, one arithmetic)."""
-    monkeypatch.setenv("QE_PWR_RQ", pwr_rq)
-    capi.reload_env()
     rng = np.random.RandomState(77 + sign)
-    for shp in SHAPES:
-        for zeros in (False, True):
-            case = _random_case(rng, *shp, 8, 1, 8, 0 if zeros else 1, w_pc=True, a_pc=False, zeros=zeros, bias=True)
-            sh, xq, wq, bias = _case_tensors(case)
-            prepared = capi.conv_prepare(wq, bias, sh, 8)
-            y = capi.quantconv2d_prepared(xq, wq, bias, sh, prepared)
-            torch.cuda.synchronize()
-            amax = float(y.abs().max())
-            qmin, qmax = (-128.0, 127.0) if sign else (0.0, 255.0)
-            s = torch.tensor([amax / 100.0], device="cuda")          # clips a few percent of the values
-            z = torch.tensor([0.37 if sign else -117.25], device="cuda")
-            rq = capi.requant(s, z, qmin, qmax, 8, sign)
-            assert capi.requant_path(sh, xq, wq, rq) == 1, shp
-            got, status = capi.quantconv2d_requant_prepared(xq, wq, bias, sh, prepared, rq)
-            ref, st2 = capi.quantize_pack(y, s, z, qmin, qmax, 8, sign)
-            torch.cuda.synchronize()
-            assert int(status.item()) == 0 and int(st2.item()) == 0
-            g, r = got.cpu().numpy(), ref.cpu().numpy()
-            assert g.shape == r.shape
-            bad = np.nonzero(g != r)[0]
-            assert bad.size == 0, "%s zeros=%s: %d of %d codes differ, first at %d (%d vs %d)" % (
-                shp, zeros, bad.size, g.size, bad[0], g[bad[0]], r[bad[0]])
-            # the same codes from the host arithmetic of the oracle on the engine's fp32 output
-            yq = np.clip(np.rint(y.cpu().numpy() / np.float32(s.item()) - np.float32(z.item())), qmin, qmax)
-            op, _ = oracle.tpack(yq.astype(np.int64), 8, sign)
-            assert np.array_equal(g, op), shp
+    with capi.knobs(QE_PWR_RQ=pwr_rq):
+        for shp in SHAPES:
+            for zeros in (False, True):
+                case = _random_case(rng, *shp, 8, 1, 8, 0 if zeros else 1, w_pc=True, a_pc=False, zeros=zeros, bias=True)
+                sh, xq, wq, bias = _case_tensors(case)
+                prepared = capi.conv_prepare(wq, bias, sh, 8)
+                y = capi.quantconv2d_prepared(xq, wq, bias, sh, prepared)
+                torch.cuda.synchronize()
+                amax = float(y.abs().max())
+                qmin, qmax = (-128.0, 127.0) if sign else (0.0, 255.0)
+                s = torch.tensor([amax / 100.0], device="cuda")          # clips a few percent of the values
+                z = torch.tensor([0.37 if sign else -117.25], device="cuda")
+                rq = capi.requant(s, z, qmin, qmax, 8, sign)
+                assert capi.requant_path(sh, xq, wq, rq) == 1, shp
+                got, status = capi.quantconv2d_requant_prepared(xq, wq, bias, sh, prepared, rq)
+                ref, st2 = capi.quantize_pack(y, s, z, qmin, qmax, 8, sign)
+                torch.cuda.synchronize()
+                assert int(status.item()) == 0 and int(st2.item()) == 0
+                g, r = got.cpu().numpy(), ref.cpu().numpy()
+                assert g.shape == r.shape
+                bad = np.nonzero(g != r)[0]
+                assert bad.size == 0, "%s zeros=%s: %d of %d codes differ, first at %d (%d vs %d)" % (
+                    shp, zeros, bad.size, g.size, bad[0], g[bad[0]], r[bad[0]])
+                # the same codes from the host arithmetic of the oracle on the engine's fp32 output
+                yq = np.clip(np.rint(y.cpu().numpy() / np.float32(s.item()) - np.float32(z.item())), qmin, qmax)
+                op, _ = oracle.tpack(yq.astype(np.int64), 8, sign)
+                assert np.array_equal(g, op), shp
 
 
 def _oracle_chains(case):
@@ -119,7 +109,7 @@ def test_requant_every_pwr_instance(engine):
         what = "%s %s (%s)" % (pwr_instances.kernel_name(base + (True, False)), shp, note)
         case = _random_case(rng, *shp, 8, 1, 8, 0 if zeros else 1, w_pc=True, a_pc=False, zeros=zeros, bias=has_bias)
         sh, xq, wq, bias = _case_tensors(case)
-        with pwr_instances.knobs(env):
+        with capi.knobs(**(env or {})):
             prepared = capi.conv_prepare(wq, bias, sh, 8)
             y = capi.quantconv2d_prepared(xq, wq, bias, sh, prepared)
             torch.cuda.synchronize()

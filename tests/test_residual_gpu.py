@@ -16,12 +16,6 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-@pytest.fixture
-def fresh_env():
-    yield
-    capi.reload_env()
-
-
 def _t(a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
@@ -123,7 +117,7 @@ def test_block_end_every_instance(k):
     shp, base, note, env = RES_ROWS[k]
     x_signed, asym, bias = [(False, False, True), (True, True, True), (False, True, False)][k % 3]
     host = {}
-    with pwr_instances.knobs(env):
+    with capi.knobs(**(env or {})):
         c = _case(*shp[:5], x_signed=x_signed, asym=asym, bias=bias, seed=100 + k, host=host)
         ref = torch.relu(c[5] + c[6])
         _check(*c, rq=_rq(ref), expect_path=1)                          # fp32 + unsigned codes
@@ -169,12 +163,11 @@ def test_block_end_fallbacks(shape):
     _check(*c, rq=None, expect_path=0)
 
 
-def test_pwr_disabled_takes_two_passes(fresh_env, monkeypatch):   # fresh_env first: torn down after the env is restored
-    monkeypatch.setenv("QE_PWR", "0")
-    capi.reload_env()
-    c = _case(2, 128, 28, 28, 512, seed=3)
-    ref = torch.relu(c[5] + c[6])
-    _check(*c, rq=_rq(ref), expect_path=0)
+def test_pwr_disabled_takes_two_passes():
+    with capi.knobs(QE_PWR="0"):
+        c = _case(2, 128, 28, 28, 512, seed=3)
+        ref = torch.relu(c[5] + c[6])
+        _check(*c, rq=_rq(ref), expect_path=0)
 
 
 def test_two_pass_route_basic_block_per_channel_4bit():

@@ -25,12 +25,6 @@ FALLBACKS = {"layer1.0.conv1": {"signed": True}, "layer2.1.conv2": {"signed": Tr
              "layer3.0.downsample.0": {"scale_mult": 2.0}, "fc": {"zero": -3}}
 
 
-@pytest.fixture
-def fresh_env():
-    yield
-    capi.reload_env()
-
-
 @pytest.fixture(scope="module")
 def r50():
     sd = exact_state_dict("resnet50", seed=0)
@@ -101,13 +95,12 @@ def test_resnet50_w8a8_batch1(r50):
     _check(_engine(sd), f64, _images(1, 13), "c: ResNet-50 W8A8 N=1")
 
 
-def test_resnet50_pwr_disabled(r50, fresh_env, monkeypatch):   # fresh_env first: torn down after the env is restored
-    monkeypatch.setenv("QE_PWR", "0")
-    capi.reload_env()
+def test_resnet50_pwr_disabled(r50):
     sd, f64 = r50
-    model = _engine(sd)
-    assert model.residual_paths(2) == [0] * 16                 # every block end on the two-pass route
-    _check(model, f64, _images(2, 14), "d: ResNet-50 W8A8 QE_PWR=0")
+    with capi.knobs(QE_PWR="0"):
+        model = _engine(sd)
+        assert model.residual_paths(2) == [0] * 16                 # every block end on the two-pass route
+        _check(model, f64, _images(2, 14), "d: ResNet-50 W8A8 QE_PWR=0")
 
 
 def test_resnet50_fallbacks():

@@ -109,9 +109,7 @@ def test_call_packed(B, K, O):
 
 @pytest.mark.parametrize("lin8,nj", [(0, 2), (0, 4)])
 def test_ragged_epilogue_branches(lin8, nj):
-    os.environ["QE_LIN8"], os.environ["QE_LIN_NJ"] = str(lin8), str(nj)
-    capi.reload_env()
-    try:
+    with capi.knobs(QE_LIN8=lin8, QE_LIN_NJ=nj):
         rng = np.random.RandomState(nj)
         for B, K, O in ((257, 128, 200), (100, 64, 1000)):
             qx, qw = rng.randint(-128, 128, size=(B, K)), rng.randint(-128, 128, size=(O, K))
@@ -136,7 +134,3 @@ def test_ragged_epilogue_branches(lin8, nj):
             assert torch.equal(capi.quantlinear_residual(xq, wq, bias, B, K, O, res), ref)
             capi.quantlinear_residual(xq, wq, bias, B, K, O, res, out=res)        # in place, unaligned
             assert torch.equal(res, ref)
-    finally:
-        os.environ.pop("QE_LIN8", None)
-        os.environ.pop("QE_LIN_NJ", None)
-        capi.reload_env()

@@ -6,9 +6,7 @@
   * qe_quantize_pack_act's GELU is as close to float64 as torch's F.gelu (1 ulp slack);
   * qe_layernorm_quantize_pack: fp32 error at most 2x torch F.layer_norm's, codes == qe_quantize_pack of its own output;
   * qe_quantize_patchify == qe_quantize_pack of the unfolded images, and the patch GEMM computes conv_proj."""
-import contextlib
 import ctypes
-import os
 
 import numpy as np
 import pytest
@@ -21,26 +19,6 @@ from quantize_amd.packed_resnet import pack_codes
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-@contextlib.contextmanager
-def knobs(**kv):
-    old = {k: os.environ.get(k) for k in kv}
-    try:
-        for k, v in kv.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = str(v)
-        capi.reload_env()
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-        capi.reload_env()
 
 
 def _t(a):
@@ -85,7 +63,7 @@ FORMS = [(0, 2, 333, 256, 320), (0, 4, 333, 256, 320), (0, 4, 130, 192, 96), (1,
 @pytest.mark.parametrize("lin8,nj,B,K,O", FORMS)
 @pytest.mark.parametrize("act", [None, "gelu"])
 def test_requant_every_form(lin8, nj, B, K, O, act):
-    with knobs(QE_LIN8=lin8, QE_LIN_NJ=nj):
+    with capi.knobs(QE_LIN8=lin8, QE_LIN_NJ=nj):
         codes = _requant_case(B, K, O, act, _rq(0.004, 3.0, 8, False) if act == "gelu" else _rq(0.01, -1.0), seed=B + O)
         _requant_case(B, K, O, act, _rq(0.04, 0.0), seed=B + O + 1, x_sign=False, per_row=False, asym=False)
     # the clamp is exercised at both ends: stored codes 0 and 255 (qmin and qmax of either quantiser) both occur
@@ -94,7 +72,7 @@ def test_requant_every_form(lin8, nj, B, K, O, act):
 
 @pytest.mark.parametrize("act", [None, "gelu"])
 def test_requant_two_pass_forms(act):
-    with knobs(QE_LIN_EPI=0):
+    with capi.knobs(QE_LIN_EPI=0):
         _requant_case(333, 256, 320, act, _rq(0.05, 1.0), seed=5, expect_path=0)
     _requant_case(333, 256, 320, act, _rq(0.3, 0.0, 4, True), seed=6, expect_path=0)            # 4-bit consumer
     _requant_case(333, 256, 320, act, _rq(0.05, 2.0, 8, True, per=320), seed=7, expect_path=0)  # per-feature consumer
@@ -104,7 +82,7 @@ def test_requant_two_pass_forms(act):
 def test_requant_nan_sets_status():
     rng = np.random.RandomState(9)
     for lin8, nj, B, K, O in FORMS:
-        with knobs(QE_LIN8=lin8, QE_LIN_NJ=nj):
+        with capi.knobs(QE_LIN8=lin8, QE_LIN_NJ=nj):
             xq, wq, bias = _operands(rng, B, K, O)
             bias[O // 3] = float("nan")
             rq = _rq(0.05, 0.0)
@@ -119,7 +97,7 @@ def test_requant_nan_sets_status():
 @pytest.mark.parametrize("lin8,nj,B,K,O", FORMS)
 def test_residual_every_form(lin8, nj, B, K, O):
     rng = np.random.RandomState(B * 7 + O)
-    with knobs(QE_LIN8=lin8, QE_LIN_NJ=nj):
+    with capi.knobs(QE_LIN8=lin8, QE_LIN_NJ=nj):
         xq, wq, bias = _operands(rng, B, K, O)
         assert capi.linear_residual_path(xq, wq, B, K, O) == 1
         res = _t(rng.normal(0, 1, size=(B, O)).astype(np.float32))
@@ -129,7 +107,7 @@ def test_residual_every_form(lin8, nj, B, K, O):
         inplace = res.clone()
         capi.quantlinear_residual(xq, wq, bias, B, K, O, inplace, out=inplace)
         assert torch.equal(inplace, ref)
-    with knobs(QE_LIN_EPI=0):
+    with capi.knobs(QE_LIN_EPI=0):
         assert capi.linear_residual_path(xq, wq, B, K, O) == 0
         inplace = res.clone()
         capi.quantlinear_residual(xq, wq, bias, B, K, O, inplace, out=inplace)
@@ -150,7 +128,7 @@ def test_float_input_residual(B, K, O):
     out = capi.quantlinear_float_input_residual(x, wq, bias, O, res)
     inplace = res.clone()
     capi.quantlinear_float_input_residual(x, wq, bias, O, inplace, out=inplace)
-    with knobs(QE_LIN_EPI=0):
+    with capi.knobs(QE_LIN_EPI=0):
         assert capi.linear_float_input_residual_path(x, wq, B, K, O) == 0
         two = capi.quantlinear_float_input_residual(x, wq, bias, O, res)
     assert torch.equal(out, ref) and torch.equal(inplace, ref) and torch.equal(two, ref)

@@ -17,14 +17,14 @@ for (B, K, O) in [(50432, 768, 768), (50432, 768, 3072), (50432, 3072, 768)]:
     out = torch.empty(B, O, device=dev)
     row = {}
     for mode in ("1", "0"):
-        os.environ["QE_LIN_F32_MFMA"] = mode; capi.reload_env()
-        path = capi.linear_float_input_path(x, wq, B, K, O)
-        capi.quantlinear_float_input(x, wq, None, O, out=out); torch.cuda.synchronize()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        n = 5 if mode == "1" else 2
-        a.record()
-        for _ in range(n): capi.quantlinear_float_input(x, wq, None, O, out=out)
-        b.record(); torch.cuda.synchronize()
+        with capi.knobs(QE_LIN_F32_MFMA=mode):
+            path = capi.linear_float_input_path(x, wq, B, K, O)
+            capi.quantlinear_float_input(x, wq, None, O, out=out); torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            n = 5 if mode == "1" else 2
+            a.record()
+            for _ in range(n): capi.quantlinear_float_input(x, wq, None, O, out=out)
+            b.record(); torch.cuda.synchronize()
         ms = a.elapsed_time(b) / n
         row["mfma" if path == 1 else "fp32_chain"] = {"ms": round(ms, 4), "TFLOPs_fp32_equiv": round(2.0 * B * K * O / ms / 1e9, 1),
                                                       "GBs": round((4 * B * K + O * K + 4 * B * O) / ms / 1e6, 1)}
