@@ -17,23 +17,6 @@ QE_ERR_UNSUPPORTED = 7
 DTYPES = {"uint8": 0, "int8": 1, "int16": 2, "int32": 3, "int64": 4,
           "float16": 5, "float32": 6, "float64": 7}
 
-# every symbol include/quant_engine.h declares
-SYMBOLS = ["qe_error_string", "qe_last_hip_error", "qe_version", "qe_target_arch", "qe_packed_nbytes",
-           "qe_tpack", "qe_tunpack", "qe_quantconv2d_workspace_bytes", "qe_quantconv2d",
-           "qe_quantconv2d_float_input", "qe_quantconv2d_path", "qe_quantlinear", "qe_quantlinear_float_input",
-           "qe_quantlinear_path", "qe_quantlinear_form", "qe_quantlinear_float_input_path", "qe_global_avgpool", "qe_conv_prepared_bytes", "qe_quantconv2d_prepared_workspace_bytes",
-           "qe_conv_prepare", "qe_quantconv2d_prepared", "qe_quantize_pack", "qe_quantconv2d_float_input_workspace_bytes",
-           "qe_quantconv2d_float_input_ws", "qe_conv_f32_prepare", "qe_quantconv2d_float_input_prepared",
-           "qe_quantconv2d_float_input_path", "qe_quantconv2d_requant_path", "qe_quantconv2d_requant_workspace_bytes",
-           "qe_quantconv2d_requant_prepared", "qe_conv_prepared_layout", "qe_quantconv2d_residual_path",
-           "qe_quantconv2d_residual_workspace_bytes", "qe_quantconv2d_residual_prepared", "qe_maxpool2d_codes",
-           "qe_quantize_pack_act", "qe_quantlinear_requant_path", "qe_quantlinear_requant_workspace_bytes", "qe_quantlinear_requant",
-           "qe_quantlinear_residual_path", "qe_quantlinear_residual_workspace_bytes", "qe_quantlinear_residual",
-           "qe_quantlinear_float_input_residual_path", "qe_quantlinear_float_input_residual_workspace_bytes",
-           "qe_quantlinear_float_input_residual", "qe_layernorm_quantize_pack_path", "qe_layernorm_quantize_pack_workspace_bytes",
-           "qe_layernorm_quantize_pack", "qe_quantize_patchify", "qe_attention_path", "qe_attention",
-           "qe_attention_masked_path", "qe_attention_masked"]
-
 ACTS = {None: 0, "none": 0, "gelu": 1}
 
 
@@ -55,6 +38,78 @@ class QeError(RuntimeError):
     pass
 
 
+_vp, _i32, _i64, _sz, _f32, _str = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float,
+                                    ctypes.c_char_p)
+_pq, _ps, _pr, _ppc = ctypes.POINTER(QeQParam), ctypes.POINTER(QeConvShape), ctypes.POINTER(QeRequant), ctypes.POINTER(_vp)
+_attn = [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _f32]
+
+# every symbol include/quant_engine.h declares: name -> (restype, argtypes); lib() applies the table
+PROTOTYPES = {
+    "qe_error_string": (_str, [_i32]),
+    "qe_last_hip_error": (_i32, []),
+    "qe_version": (_str, []),
+    "qe_target_arch": (_str, []),
+    "qe_packed_nbytes": (_i64, [_i64, _i32]),
+    "qe_tpack": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "qe_tunpack": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp]),
+    "qe_quantize_pack": (_i32, [_vp, _i64, _vp, _vp, _i32, _i64, _f32, _f32, _i32, _i32, _vp, _vp, _vp]),
+    "qe_quantize_pack_act": (_i32, [_vp, _i64, _i32, _vp, _vp, _i32, _i64, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "qe_quantize_patchify": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _f32, _f32, _i32, _i32, _vp, _vp, _vp]),
+    "qe_global_avgpool": (_i32, [_vp, _i64, _i32, _vp, _vp]),
+    "qe_maxpool2d_codes": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    # packed-activation convolutions
+    "qe_quantconv2d_path": (_i32, [_ps, _pq, _pq]),
+    "qe_quantconv2d_workspace_bytes": (_sz, [_ps, _i32, _i32]),
+    "qe_quantconv2d": (_i32, [_pq, _pq, _vp, _ps, _vp, _vp, _sz, _vp]),
+    "qe_conv_prepared_bytes": (_sz, [_ps, _i32, _i32]),
+    "qe_conv_prepared_layout": (ctypes.c_uint64, [_ps, _i32, _i32]),
+    "qe_conv_prepare": (_i32, [_pq, _vp, _ps, _i32, _vp, _sz, _vp]),
+    "qe_quantconv2d_prepared_workspace_bytes": (_sz, [_ps, _i32, _i32]),
+    "qe_quantconv2d_prepared": (_i32, [_pq, _pq, _vp, _ps, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "qe_quantconv2d_requant_path": (_i32, [_ps, _pq, _pq, _pr]),
+    "qe_quantconv2d_requant_workspace_bytes": (_sz, [_ps, _pq, _pq, _pr]),
+    "qe_quantconv2d_requant_prepared": (_i32, [_pq, _pq, _vp, _ps, _vp, _sz, _pr, _vp, _vp, _vp, _sz, _vp]),
+    "qe_quantconv2d_residual_path": (_i32, [_ps, _pq, _pq, _pr]),
+    "qe_quantconv2d_residual_workspace_bytes": (_sz, [_ps, _pq, _pq, _pr]),
+    "qe_quantconv2d_residual_prepared": (_i32, [_pq, _pq, _vp, _ps, _vp, _sz, _vp, _vp, _pr, _vp, _vp, _vp, _sz, _vp]),
+    # float-input convolutions
+    "qe_quantconv2d_float_input": (_i32, [_vp, _pq, _vp, _ps, _vp, _vp]),
+    "qe_quantconv2d_float_input_path": (_i32, [_ps, _pq]),
+    "qe_quantconv2d_float_input_workspace_bytes": (_sz, [_ps, _i32]),
+    "qe_quantconv2d_float_input_ws": (_i32, [_vp, _pq, _vp, _ps, _vp, _vp, _sz, _vp]),
+    "qe_conv_f32_prepare": (_i32, [_pq, _vp, _ps, _vp, _sz, _vp]),
+    "qe_quantconv2d_float_input_prepared": (_i32, [_vp, _pq, _vp, _ps, _vp, _sz, _vp, _vp]),
+    # linears and their fused ViT forms
+    "qe_quantlinear": (_i32, [_pq, _pq, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "qe_quantlinear_path": (_i32, [_pq, _pq, _i64, _i32, _i32]),
+    "qe_quantlinear_form": (_i32, [_pq, _pq, _i64, _i32, _i32, _i32]),
+    "qe_quantlinear_float_input": (_i32, [_vp, _pq, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "qe_quantlinear_float_input_path": (_i32, [_vp, _pq, _i64, _i32, _i32]),
+    "qe_quantlinear_requant_path": (_i32, [_pq, _pq, _i64, _i32, _i32, _pr, _vp]),
+    "qe_quantlinear_requant_workspace_bytes": (_sz, [_pq, _pq, _i64, _i32, _i32, _pr, _vp]),
+    "qe_quantlinear_requant": (_i32, [_pq, _pq, _vp, _i64, _i32, _i32, _i32, _pr, _vp, _vp, _vp, _sz, _vp]),
+    "qe_quantlinear_residual_path": (_i32, [_pq, _pq, _i64, _i32, _i32]),
+    "qe_quantlinear_residual_workspace_bytes": (_sz, [_pq, _pq, _i64, _i32, _i32]),
+    "qe_quantlinear_residual": (_i32, [_pq, _pq, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "qe_quantlinear_float_input_residual_path": (_i32, [_vp, _pq, _i64, _i32, _i32]),
+    "qe_quantlinear_float_input_residual_workspace_bytes": (_sz, [_vp, _pq, _i64, _i32, _i32]),
+    "qe_quantlinear_float_input_residual": (_i32, [_vp, _pq, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "qe_layernorm_quantize_pack_path": (_i32, [_i64, _i32, _i32, _pr, _ppc]),
+    "qe_layernorm_quantize_pack_workspace_bytes": (_sz, [_i64, _i32, _i32, _pr, _ppc, _vp]),
+    "qe_layernorm_quantize_pack": (_i32, [_vp, _i64, _i32, _vp, _vp, _f32, _i32, _pr, _ppc, _vp, _vp, _vp, _sz, _vp]),
+    "qe_attention_path": (_i32, [_i32, _i32, _i32, _i32]),
+    "qe_attention": (_i32, _attn + [_vp]),
+    "qe_attention_masked_path": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "qe_attention_masked": (_i32, _attn + [_vp, _i64, _i64, _vp, _i32, _vp]),
+}
+SYMBOLS = sorted(PROTOTYPES)
+# exported by the library but absent from the header (not part of the public ABI): kept out of SYMBOLS
+DEBUG_PROTOTYPES = {
+    "qe_debug_reload_env": (None, []),
+    "qe_debug_set_stamp_buffer": (None, [_vp]),
+}
+
+
 def lib():
     """dlopen libqe_hip.so (no GPU needed to load it) and declare the prototypes."""
     global _lib
@@ -64,114 +119,10 @@ def lib():
     if not os.path.exists(path):
         raise ImportError("libqe_hip.so not built: run `python -m quantize_amd.build`. No fallback exists.")
     L = ctypes.CDLL(path)
-    vp, i32, i64, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t
-    L.qe_error_string.restype = ctypes.c_char_p
-    L.qe_error_string.argtypes = [i32]
-    L.qe_last_hip_error.restype = i32
-    L.qe_version.restype = ctypes.c_char_p
-    L.qe_target_arch.restype = ctypes.c_char_p
-    L.qe_packed_nbytes.restype = i64
-    L.qe_packed_nbytes.argtypes = [i64, i32]
-    L.qe_tpack.restype = i32
-    L.qe_tpack.argtypes = [vp, i32, i64, i32, i32, vp, vp, vp]
-    L.qe_tunpack.restype = i32
-    L.qe_tunpack.argtypes = [vp, i64, i32, i32, vp, vp]
-    L.qe_quantconv2d_workspace_bytes.restype = sz
-    L.qe_quantconv2d_workspace_bytes.argtypes = [ctypes.POINTER(QeConvShape), i32, i32]
-    L.qe_quantconv2d.restype = i32
-    L.qe_quantconv2d.argtypes = [ctypes.POINTER(QeQParam), ctypes.POINTER(QeQParam), vp,
-                                 ctypes.POINTER(QeConvShape), vp, vp, sz, vp]
-    L.qe_quantconv2d_float_input.restype = i32
-    L.qe_quantconv2d_float_input.argtypes = [vp, ctypes.POINTER(QeQParam), vp, ctypes.POINTER(QeConvShape), vp, vp]
-    L.qe_quantconv2d_path.restype = i32
-    L.qe_quantconv2d_path.argtypes = [ctypes.POINTER(QeConvShape), ctypes.POINTER(QeQParam), ctypes.POINTER(QeQParam)]
-    L.qe_quantlinear.restype = i32
-    L.qe_quantlinear.argtypes = [ctypes.POINTER(QeQParam), ctypes.POINTER(QeQParam), vp, i64, i32, i32, vp, vp]
-    L.qe_quantlinear_float_input.restype = i32
-    L.qe_quantlinear_float_input.argtypes = [vp, ctypes.POINTER(QeQParam), vp, i64, i32, i32, vp, vp]
-    L.qe_quantlinear_path.restype = i32
-    L.qe_quantlinear_path.argtypes = [ctypes.POINTER(QeQParam), ctypes.POINTER(QeQParam), i64, i32, i32]
-    L.qe_quantlinear_form.restype = i32
-    L.qe_quantlinear_form.argtypes = [ctypes.POINTER(QeQParam), ctypes.POINTER(QeQParam), i64, i32, i32, i32]
-    L.qe_quantlinear_float_input_path.restype = i32
-    L.qe_quantlinear_float_input_path.argtypes = [vp, ctypes.POINTER(QeQParam), i64, i32, i32]
-    L.qe_global_avgpool.restype = i32
-    L.qe_global_avgpool.argtypes = [vp, i64, i32, vp, vp]
-    L.qe_conv_prepared_bytes.restype = sz
-    L.qe_conv_prepared_bytes.argtypes = [ctypes.POINTER(QeConvShape), i32, i32]
-    L.qe_quantconv2d_prepared_workspace_bytes.restype = sz
-    L.qe_quantconv2d_prepared_workspace_bytes.argtypes = [ctypes.POINTER(QeConvShape), i32, i32]
-    L.qe_conv_prepare.restype = i32
-    L.qe_conv_prepare.argtypes = [ctypes.POINTER(QeQParam), vp, ctypes.POINTER(QeConvShape), i32, vp, sz, vp]
-    L.qe_quantconv2d_prepared.restype = i32
-    L.qe_quantconv2d_prepared.argtypes = [ctypes.POINTER(QeQParam), ctypes.POINTER(QeQParam), vp, ctypes.POINTER(QeConvShape),
-                                          vp, sz, vp, vp, sz, vp]
-    L.qe_quantconv2d_float_input_workspace_bytes.restype = sz
-    L.qe_quantconv2d_float_input_workspace_bytes.argtypes = [ctypes.POINTER(QeConvShape), i32]
-    L.qe_quantconv2d_float_input_ws.restype = i32
-    L.qe_quantconv2d_float_input_ws.argtypes = [vp, ctypes.POINTER(QeQParam), vp, ctypes.POINTER(QeConvShape), vp, vp, sz, vp]
-    L.qe_conv_f32_prepare.restype = i32
-    L.qe_conv_f32_prepare.argtypes = [ctypes.POINTER(QeQParam), vp, ctypes.POINTER(QeConvShape), vp, sz, vp]
-    L.qe_quantconv2d_float_input_prepared.restype = i32
-    L.qe_quantconv2d_float_input_prepared.argtypes = [vp, ctypes.POINTER(QeQParam), vp, ctypes.POINTER(QeConvShape), vp, sz, vp, vp]
-    L.qe_quantconv2d_float_input_path.restype = i32
-    L.qe_quantconv2d_float_input_path.argtypes = [ctypes.POINTER(QeConvShape), ctypes.POINTER(QeQParam)]
-    L.qe_quantize_pack.restype = i32
-    L.qe_quantize_pack.argtypes = [vp, i64, vp, vp, i32, i64, ctypes.c_float, ctypes.c_float, i32, i32, vp, vp, vp]
-    pq, ps, pr = ctypes.POINTER(QeQParam), ctypes.POINTER(QeConvShape), ctypes.POINTER(QeRequant)
-    L.qe_quantconv2d_requant_path.restype = i32
-    L.qe_quantconv2d_requant_path.argtypes = [ps, pq, pq, pr]
-    L.qe_quantconv2d_requant_workspace_bytes.restype = sz
-    L.qe_quantconv2d_requant_workspace_bytes.argtypes = [ps, pq, pq, pr]
-    L.qe_quantconv2d_requant_prepared.restype = i32
-    L.qe_quantconv2d_requant_prepared.argtypes = [pq, pq, vp, ps, vp, sz, pr, vp, vp, vp, sz, vp]
-    L.qe_quantconv2d_residual_path.restype = i32
-    L.qe_quantconv2d_residual_path.argtypes = [ps, pq, pq, pr]
-    L.qe_quantconv2d_residual_workspace_bytes.restype = sz
-    L.qe_quantconv2d_residual_workspace_bytes.argtypes = [ps, pq, pq, pr]
-    L.qe_quantconv2d_residual_prepared.restype = i32
-    L.qe_quantconv2d_residual_prepared.argtypes = [pq, pq, vp, ps, vp, sz, vp, vp, pr, vp, vp, vp, sz, vp]
-    L.qe_maxpool2d_codes.restype = i32
-    L.qe_maxpool2d_codes.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]
-    f32 = ctypes.c_float
-    L.qe_quantize_pack_act.restype = i32
-    L.qe_quantize_pack_act.argtypes = [vp, i64, i32, vp, vp, i32, i64, f32, f32, i32, i32, vp, vp, vp, vp]
-    L.qe_quantlinear_requant_path.restype = i32
-    L.qe_quantlinear_requant_path.argtypes = [pq, pq, i64, i32, i32, pr, vp]
-    L.qe_quantlinear_requant_workspace_bytes.restype = sz
-    L.qe_quantlinear_requant_workspace_bytes.argtypes = [pq, pq, i64, i32, i32, pr, vp]
-    L.qe_quantlinear_requant.restype = i32
-    L.qe_quantlinear_requant.argtypes = [pq, pq, vp, i64, i32, i32, i32, pr, vp, vp, vp, sz, vp]
-    L.qe_quantlinear_residual_path.restype = i32
-    L.qe_quantlinear_residual_path.argtypes = [pq, pq, i64, i32, i32]
-    L.qe_quantlinear_residual_workspace_bytes.restype = sz
-    L.qe_quantlinear_residual_workspace_bytes.argtypes = [pq, pq, i64, i32, i32]
-    L.qe_quantlinear_residual.restype = i32
-    L.qe_quantlinear_residual.argtypes = [pq, pq, vp, i64, i32, i32, vp, vp, vp, sz, vp]
-    L.qe_quantlinear_float_input_residual_path.restype = i32
-    L.qe_quantlinear_float_input_residual_path.argtypes = [vp, pq, i64, i32, i32]
-    L.qe_quantlinear_float_input_residual_workspace_bytes.restype = sz
-    L.qe_quantlinear_float_input_residual_workspace_bytes.argtypes = [vp, pq, i64, i32, i32]
-    L.qe_quantlinear_float_input_residual.restype = i32
-    L.qe_quantlinear_float_input_residual.argtypes = [vp, pq, vp, i64, i32, i32, vp, vp, vp, sz, vp]
-    ppc = ctypes.POINTER(ctypes.c_void_p)
-    L.qe_layernorm_quantize_pack_path.restype = i32
-    L.qe_layernorm_quantize_pack_path.argtypes = [i64, i32, i32, pr, ppc]
-    L.qe_layernorm_quantize_pack_workspace_bytes.restype = sz
-    L.qe_layernorm_quantize_pack_workspace_bytes.argtypes = [i64, i32, i32, pr, ppc, vp]
-    L.qe_layernorm_quantize_pack.restype = i32
-    L.qe_layernorm_quantize_pack.argtypes = [vp, i64, i32, vp, vp, f32, i32, pr, ppc, vp, vp, vp, sz, vp]
-    L.qe_quantize_patchify.restype = i32
-    L.qe_quantize_patchify.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, f32, f32, i32, i32, vp, vp, vp]
-    L.qe_attention_path.restype = i32
-    L.qe_attention_path.argtypes = [i32, i32, i32, i32]
-    L.qe_attention.restype = i32
-    L.qe_attention.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, i64, i64, f32, vp]
-    L.qe_attention_masked_path.restype = i32
-    L.qe_attention_masked_path.argtypes = [i32, i32, i32, i32, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    L.qe_attention_masked.restype = i32
-    L.qe_attention_masked.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, i64, i64, f32,
-                                      vp, i64, i64, vp, ctypes.c_int, vp]
+    for table in (PROTOTYPES, DEBUG_PROTOTYPES):
+        for name, (restype, argtypes) in table.items():
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -191,6 +142,25 @@ def _stream(stream=None):
     return ctypes.c_void_p(s.cuda_stream)
 
 
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _ws(need, dev):
+    import torch
+    return torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+
+
+def _status(status, dev):
+    import torch
+    return torch.zeros(1, dtype=torch.int32, device=dev) if status is None else status
+
+
+def _prep(t):
+    """(pointer, bytes) of a prepared-table or workspace tensor; (None, 0) when there is none or it is empty."""
+    return (t.data_ptr(), t.numel()) if t is not None and t.numel() else (None, 0)
+
+
 def packed_nbytes(n, n_bits):
     return int(lib().qe_packed_nbytes(int(n), int(n_bits)))
 
@@ -202,8 +172,7 @@ def tpack(x, n_bits, sign, out=None, status=None, stream=None):
     n = x.numel()
     if out is None:
         out = torch.empty(packed_nbytes(n, n_bits), dtype=torch.uint8, device=x.device)
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=x.device)
+    status = _status(status, x.device)
     check(lib().qe_tpack(x.data_ptr(), DTYPES[str(x.dtype).replace("torch.", "")], n, int(n_bits),
                          1 if sign else 0, out.data_ptr(), status.data_ptr(), _stream(stream)))
     return out, status
@@ -268,9 +237,7 @@ def knobs(**env):
 
 
 def conv_prepared_layout(sh, x_bits, w_bits):
-    f = lib().qe_conv_prepared_layout
-    f.restype = ctypes.c_uint64
-    return int(f(ctypes.byref(sh), int(x_bits), int(w_bits)))
+    return int(lib().qe_conv_prepared_layout(ctypes.byref(sh), int(x_bits), int(w_bits)))
 
 
 def conv_path(sh, xq, wq):
@@ -283,13 +250,10 @@ def quantconv2d(xq, wq, bias, sh, out=None, workspace=None, stream=None):
     OH, OW = out_hw(sh)
     if out is None:
         out = torch.empty((sh.N, sh.OC, OH, OW), dtype=torch.float32, device=dev)
-    need = workspace_bytes(sh, xq.n_bits, wq.n_bits)
-    if workspace is None and need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    check(lib().qe_quantconv2d(ctypes.byref(xq), ctypes.byref(wq),
-                               None if bias is None else bias.data_ptr(), ctypes.byref(sh), out.data_ptr(),
-                               None if workspace is None else workspace.data_ptr(),
-                               0 if workspace is None else workspace.numel(), _stream(stream)))
+    if workspace is None:
+        workspace = _ws(workspace_bytes(sh, xq.n_bits, wq.n_bits), dev)
+    check(lib().qe_quantconv2d(ctypes.byref(xq), ctypes.byref(wq), _ptr(bias), ctypes.byref(sh), out.data_ptr(),
+                               *_prep(workspace), _stream(stream)))
     return out
 
 
@@ -299,8 +263,7 @@ def conv_prepare(wq, bias, sh, x_bits, stream=None):
     dev = wq._keep[0].device
     need = int(lib().qe_conv_prepared_bytes(ctypes.byref(sh), int(x_bits), wq.n_bits))
     prepared = torch.empty(max(need, 0), dtype=torch.uint8, device=dev)
-    check(lib().qe_conv_prepare(ctypes.byref(wq), None if bias is None else bias.data_ptr(), ctypes.byref(sh), int(x_bits),
-                                prepared.data_ptr() if need else None, need, _stream(stream)))
+    check(lib().qe_conv_prepare(ctypes.byref(wq), _ptr(bias), ctypes.byref(sh), int(x_bits), *_prep(prepared), _stream(stream)))
     return prepared
 
 
@@ -310,13 +273,10 @@ def quantconv2d_prepared(xq, wq, bias, sh, prepared, out=None, workspace=None, s
     OH, OW = out_hw(sh)
     if out is None:
         out = torch.empty((sh.N, sh.OC, OH, OW), dtype=torch.float32, device=dev)
-    need = int(lib().qe_quantconv2d_prepared_workspace_bytes(ctypes.byref(sh), xq.n_bits, wq.n_bits))
-    if workspace is None and need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    check(lib().qe_quantconv2d_prepared(ctypes.byref(xq), ctypes.byref(wq), None if bias is None else bias.data_ptr(),
-                                        ctypes.byref(sh), prepared.data_ptr() if prepared.numel() else None, prepared.numel(),
-                                        out.data_ptr(), None if workspace is None else workspace.data_ptr(),
-                                        0 if workspace is None else workspace.numel(), _stream(stream)))
+    if workspace is None:
+        workspace = _ws(int(lib().qe_quantconv2d_prepared_workspace_bytes(ctypes.byref(sh), xq.n_bits, wq.n_bits)), dev)
+    check(lib().qe_quantconv2d_prepared(ctypes.byref(xq), ctypes.byref(wq), _ptr(bias), ctypes.byref(sh), *_prep(prepared),
+                                        out.data_ptr(), *_prep(workspace), _stream(stream)))
     return out
 
 
@@ -338,16 +298,13 @@ def quantconv2d_requant_prepared(xq, wq, bias, sh, prepared, rq, out=None, statu
     OH, OW = out_hw(sh)
     if out is None:
         out = torch.empty(packed_nbytes(sh.N * sh.OC * OH * OW, rq.n_bits), dtype=torch.uint8, device=dev)
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-    need = int(lib().qe_quantconv2d_requant_workspace_bytes(ctypes.byref(sh), ctypes.byref(xq), ctypes.byref(wq), ctypes.byref(rq)))
-    if workspace is None and need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    check(lib().qe_quantconv2d_requant_prepared(ctypes.byref(xq), ctypes.byref(wq), None if bias is None else bias.data_ptr(),
-                                                ctypes.byref(sh), prepared.data_ptr() if prepared.numel() else None, prepared.numel(),
-                                                ctypes.byref(rq), out.data_ptr(), status.data_ptr(),
-                                                None if workspace is None else workspace.data_ptr(),
-                                                0 if workspace is None else workspace.numel(), _stream(stream)))
+    status = _status(status, dev)
+    if workspace is None:
+        workspace = _ws(int(lib().qe_quantconv2d_requant_workspace_bytes(ctypes.byref(sh), ctypes.byref(xq), ctypes.byref(wq),
+                                                                         ctypes.byref(rq))), dev)
+    check(lib().qe_quantconv2d_requant_prepared(ctypes.byref(xq), ctypes.byref(wq), _ptr(bias), ctypes.byref(sh), *_prep(prepared),
+                                                ctypes.byref(rq), out.data_ptr(), status.data_ptr(), *_prep(workspace),
+                                                _stream(stream)))
     return out, status
 
 
@@ -375,17 +332,12 @@ def quantconv2d_residual_prepared(xq, wq, bias, sh, prepared, identity, rq=None,
         out = torch.empty((sh.N, sh.OC, OH, OW), dtype=torch.float32, device=dev)
     if rq is not None and codes is None:
         codes = torch.empty(packed_nbytes(sh.N * sh.OC * OH * OW, rq.n_bits), dtype=torch.uint8, device=dev)
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-    need = residual_workspace_bytes(sh, xq, wq, rq)
-    if workspace is None and need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    status = _status(status, dev)
+    if workspace is None:
+        workspace = _ws(residual_workspace_bytes(sh, xq, wq, rq), dev)
     check(lib().qe_quantconv2d_residual_prepared(
-        ctypes.byref(xq), ctypes.byref(wq), None if bias is None else bias.data_ptr(), ctypes.byref(sh),
-        prepared.data_ptr() if prepared.numel() else None, prepared.numel(), identity.data_ptr(),
-        None if out is None else out.data_ptr(), None if rq is None else ctypes.byref(rq),
-        None if codes is None else codes.data_ptr(), status.data_ptr(), None if workspace is None else workspace.data_ptr(),
-        0 if workspace is None else workspace.numel(), _stream(stream)))
+        ctypes.byref(xq), ctypes.byref(wq), _ptr(bias), ctypes.byref(sh), *_prep(prepared), identity.data_ptr(), _ptr(out),
+        None if rq is None else ctypes.byref(rq), _ptr(codes), status.data_ptr(), *_prep(workspace), _stream(stream)))
     return out, codes, status
 
 
@@ -411,8 +363,7 @@ def quantize_pack(x, scale, zero, qmin, qmax, n_bits, sign, inner=1, out=None, s
     n = x.numel()
     if out is None:
         out = torch.empty(packed_nbytes(n, n_bits), dtype=torch.uint8, device=x.device)
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=x.device)
+    status = _status(status, x.device)
     check(lib().qe_quantize_pack(x.data_ptr(), n, scale.data_ptr(), zero.data_ptr(), int(scale.numel()), int(inner),
                                  float(qmin), float(qmax), int(n_bits), 1 if sign else 0, out.data_ptr(), status.data_ptr(),
                                  _stream(stream)))
@@ -426,7 +377,7 @@ def quantconv2d_float_input(x, wq, bias, sh, out=None, stream=None, mfma=True):
     OH, OW = out_hw(sh)
     if out is None:
         out = torch.empty((sh.N, sh.OC, OH, OW), dtype=torch.float32, device=x.device)
-    bp = None if bias is None else bias.data_ptr()
+    bp = _ptr(bias)
     if mfma:
         need = int(lib().qe_quantconv2d_float_input_workspace_bytes(ctypes.byref(sh), wq.n_bits))
         ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
@@ -445,8 +396,7 @@ def conv_f32_prepare(wq, bias, sh, stream=None):
     import torch
     need = int(lib().qe_quantconv2d_float_input_workspace_bytes(ctypes.byref(sh), wq.n_bits))
     prepared = torch.empty(need, dtype=torch.uint8, device=wq._keep[0].device)
-    check(lib().qe_conv_f32_prepare(ctypes.byref(wq), None if bias is None else bias.data_ptr(), ctypes.byref(sh),
-                                    prepared.data_ptr() if need else None, need, _stream(stream)))
+    check(lib().qe_conv_f32_prepare(ctypes.byref(wq), _ptr(bias), ctypes.byref(sh), *_prep(prepared), _stream(stream)))
     return prepared
 
 
@@ -455,9 +405,8 @@ def quantconv2d_float_input_prepared(x, wq, bias, sh, prepared, out=None, stream
     OH, OW = out_hw(sh)
     if out is None:
         out = torch.empty((sh.N, sh.OC, OH, OW), dtype=torch.float32, device=x.device)
-    check(lib().qe_quantconv2d_float_input_prepared(x.data_ptr(), ctypes.byref(wq), None if bias is None else bias.data_ptr(),
-                                                    ctypes.byref(sh), prepared.data_ptr() if prepared.numel() else None,
-                                                    prepared.numel(), out.data_ptr(), _stream(stream)))
+    check(lib().qe_quantconv2d_float_input_prepared(x.data_ptr(), ctypes.byref(wq), _ptr(bias), ctypes.byref(sh), *_prep(prepared),
+                                                    out.data_ptr(), _stream(stream)))
     return out
 
 
@@ -480,8 +429,8 @@ def quantlinear(xq, wq, bias, B, K, O, out=None, stream=None):
     import torch
     if out is None:
         out = torch.empty((B, O), dtype=torch.float32, device=wq._keep[0].device)
-    check(lib().qe_quantlinear(ctypes.byref(xq), ctypes.byref(wq), None if bias is None else bias.data_ptr(),
-                               int(B), int(K), int(O), out.data_ptr(), _stream(stream)))
+    check(lib().qe_quantlinear(ctypes.byref(xq), ctypes.byref(wq), _ptr(bias), int(B), int(K), int(O), out.data_ptr(),
+                               _stream(stream)))
     return out
 
 
@@ -495,8 +444,8 @@ def quantlinear_float_input(x, wq, bias, O, out=None, stream=None):
     B, K = x.shape
     if out is None:
         out = torch.empty((B, O), dtype=torch.float32, device=x.device)
-    check(lib().qe_quantlinear_float_input(x.data_ptr(), ctypes.byref(wq), None if bias is None else bias.data_ptr(),
-                                           int(B), int(K), int(O), out.data_ptr(), _stream(stream)))
+    check(lib().qe_quantlinear_float_input(x.data_ptr(), ctypes.byref(wq), _ptr(bias), int(B), int(K), int(O), out.data_ptr(),
+                                           _stream(stream)))
     return out
 
 
@@ -512,20 +461,6 @@ def global_avgpool(x, out=None, stream=None):
 
 
 # ---- fused ViT forms ----------------------------------------------------------------------------------------------
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _ws(need, dev):
-    import torch
-    return torch.empty(need, dtype=torch.uint8, device=dev) if need else None
-
-
-def _status(status, dev):
-    import torch
-    return torch.zeros(1, dtype=torch.int32, device=dev) if status is None else status
-
-
 def quantize_pack_act(x, scale, zero, qmin, qmax, n_bits, sign, act=None, inner=1, out=None, y=None, status=None, stream=None):
     """qe_quantize_pack_act: codes of act(x) (act None | "gelu"); y: optional fp32 output of act(x) (a tensor, or "new").
     Returns (codes, y or None, status)."""
@@ -708,6 +643,6 @@ def attention(q, k, v, N, L, H, S=None, layout="token", scale=None, out=None, st
                 and key_bias.dtype == torch.float32 and tuple(key_bias.shape) == (N, S)):
             raise ValueError("key_bias must be a contiguous fp32 CUDA tensor of shape (N, S)")
     check(lib().qe_attention_masked(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), N, L, S, H, d, q_rn, q_rt, kv_rn,
-                                    kv_rt, q_rn, q_rt, scale, None if mask is None else mask.data_ptr(), mask_sn, mask_sh,
-                                    None if key_bias is None else key_bias.data_ptr(), 1 if causal else 0, _stream(stream)))
+                                    kv_rt, q_rn, q_rt, scale, _ptr(mask), mask_sn, mask_sh, _ptr(key_bias), 1 if causal else 0,
+                                    _stream(stream)))
     return out

@@ -15,15 +15,6 @@ extern char **environ;
 
 namespace qe {
 
-struct RequantHost {   // qe_conv_mfma_kernel.hpp
-    uint8_t *out;
-    const float *scale, *zero;
-    int n_param;
-    float qmin, qmax;
-    int n_bits, sign;
-    int32_t *status;
-};
-
 thread_local int g_last_hip_error = 0;
 
 namespace {
@@ -94,6 +85,17 @@ static int check_qparam(const qe_qparam *q)
     return QE_OK;
 }
 
+// what every packed-conv entry point checks first, in this order: the shape, the input operand, the weight operand, the
+// scale counts
+static int check_packed_conv(const qe_conv_shape *sh, const qe_qparam *x, const qe_qparam *w)
+{
+    int rc = check_shape(sh);
+    if (rc != QE_OK) return rc;
+    if ((rc = check_qparam(x)) != QE_OK) return rc;
+    if ((rc = check_qparam(w)) != QE_OK) return rc;
+    return check_nparam(x, w, sh);
+}
+
 }  // namespace qe
 
 extern "C" const char *qe_error_string(int status)
@@ -154,11 +156,8 @@ extern "C" int qe_quantconv2d(const qe_qparam *x, const qe_qparam *w, const floa
                               void *workspace, size_t workspace_bytes, qe_stream_t stream)
 {
     using namespace qe;
-    int rc = check_shape(shape);
+    const int rc = check_packed_conv(shape, x, w);
     if (rc != QE_OK) return rc;
-    if ((rc = check_qparam(x)) != QE_OK) return rc;
-    if ((rc = check_qparam(w)) != QE_OK) return rc;
-    if ((rc = check_nparam(x, w, shape)) != QE_OK) return rc;
     if (out == nullptr) return QE_ERR_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const ConvPlan p = plan_conv({shape, x, w, reinterpret_cast<uintptr_t>(out)});
@@ -203,11 +202,8 @@ extern "C" int qe_quantconv2d_prepared(const qe_qparam *x, const qe_qparam *w, c
                                        float *out, void *workspace, size_t workspace_bytes, qe_stream_t stream)
 {
     using namespace qe;
-    int rc = check_shape(shape);
+    const int rc = check_packed_conv(shape, x, w);
     if (rc != QE_OK) return rc;
-    if ((rc = check_qparam(x)) != QE_OK) return rc;
-    if ((rc = check_qparam(w)) != QE_OK) return rc;
-    if ((rc = check_nparam(x, w, shape)) != QE_OK) return rc;
     if (out == nullptr) return QE_ERR_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const ConvPlan p = plan_conv({shape, x, w, reinterpret_cast<uintptr_t>(out)});
@@ -256,11 +252,8 @@ extern "C" int qe_quantconv2d_requant_prepared(const qe_qparam *x, const qe_qpar
                                                void *workspace, size_t workspace_bytes, qe_stream_t stream)
 {
     using namespace qe;
-    int rc = check_shape(shape);
+    int rc = check_packed_conv(shape, x, w);
     if (rc != QE_OK) return rc;
-    if ((rc = check_qparam(x)) != QE_OK) return rc;
-    if ((rc = check_qparam(w)) != QE_OK) return rc;
-    if ((rc = check_nparam(x, w, shape)) != QE_OK) return rc;
     if ((rc = check_requant(rq)) != QE_OK) return rc;
     if (out == nullptr) return QE_ERR_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -314,11 +307,8 @@ extern "C" int qe_quantconv2d_residual_prepared(const qe_qparam *x, const qe_qpa
                                                 int32_t *status, void *workspace, size_t workspace_bytes, qe_stream_t stream)
 {
     using namespace qe;
-    int rc = check_shape(shape);
+    int rc = check_packed_conv(shape, x, w);
     if (rc != QE_OK) return rc;
-    if ((rc = check_qparam(x)) != QE_OK) return rc;
-    if ((rc = check_qparam(w)) != QE_OK) return rc;
-    if ((rc = check_nparam(x, w, shape)) != QE_OK) return rc;
     if (rq != nullptr && (rc = check_requant(rq)) != QE_OK) return rc;
     if (rq != nullptr && !(rq->n_param == 1 || rq->n_param >= shape->OC)) return QE_ERR_ARG;
     if (identity == nullptr || (rq != nullptr && codes == nullptr) || (out == nullptr && rq == nullptr)) return QE_ERR_ARG;

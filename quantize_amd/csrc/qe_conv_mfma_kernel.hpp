@@ -136,16 +136,6 @@ __device__ __forceinline__ void rq_report(const Args &a, bool bad)
     if (__builtin_amdgcn_ballot_w64(bad) != 0 && (threadIdx.x & 63) == 0 && a.rq_status != nullptr) atomicOr(a.rq_status, 1);
 }
 
-// host-side description of a fused output quantiser (qe_requant of the C ABI + destination)
-struct RequantHost {
-    uint8_t *out;
-    const float *scale, *zero;
-    int n_param;
-    float qmin, qmax;
-    int n_bits, sign;
-    int32_t *status;
-};
-
 // stored code u -> MFMA operand a = q - d = u - c, c = off (signed) | 128 (unsigned 8-bit) | 0
 __host__ __device__ __forceinline__ int code_bias(int n_bits, int sign)
 {

@@ -13,7 +13,15 @@
 
 namespace qe {
 
-struct RequantHost;
+// host-side description of a fused output quantiser (qe_requant of the C ABI + destination)
+struct RequantHost {
+    uint8_t *out;
+    const float *scale, *zero;
+    int n_param;
+    float qmin, qmax;
+    int n_bits, sign;
+    int32_t *status;
+};
 
 constexpr int FD_CK = 64;   // flatd: input channels per stage
 

@@ -1,12 +1,14 @@
 // torch_binding.cpp -- the `quant_engine` Python module for PyTorch-ROCm.
 //
 // Drop-in for the reference's pybind module of the same name
-// (engine/kernels/pybind.cpp:7-17): same 8 exports, positional-only signatures,
-// same return types/dtypes, and the reference's TORCH_CHECK messages (-> Python
+// (engine/kernels/pybind.cpp:7-17): its 8 exports (plus 4 of this engine's own), positional-only
+// signatures, same return types/dtypes, and the reference's TORCH_CHECK messages (-> Python
 // RuntimeError).  All device work goes through the C ABI in include/quant_engine.h;
-// this file only checks arguments, allocates outputs from torch's caching
-// allocator and picks up torch's current device and stream (the reference launches
-// on the legacy default stream with no device guard).
+// this file only checks arguments (the operand, bias and conv-geometry checks once each, shared by
+// the four quantised operators), allocates outputs from torch's caching allocator, keeps the parsed
+// descriptions and ONE cache of prepared weight tables for both conv operators, and picks up torch's
+// current device and stream (the reference launches on the legacy default stream with no device
+// guard).
 //
 // tpack/tunpack dispatch on the tensor's device exactly like the reference (tpack.cu:241-251, :458-468):
 // device tensors go to the HIP kernels, CPU-resident tensors (a model packed or reloaded before it was
@@ -85,9 +87,9 @@ struct Des {
 // Host-side caches.  A packed layer hands the SAME des / weight / scale tensors to the
 // operator on every forward pass (buffers registered by pack(), quantconv2d.py:187-192), so what the host derives from
 // them is kept between calls: the parsed description (saves the blocking device->host copy the reference pays ten
-// times per call, quantconv2d.cu:191-207) and the prepared weight tables of qe_conv_prepare (saves the re-layout
-// launch).  An entry is keyed on the tensor object (TensorImpl), its version counter, data pointer and size, and is
-// dropped once the tensor object is gone.  `tensor.data = other` swaps storage without bumping the version: the data
+// times per call, quantconv2d.cu:191-207) and the prepared weight tables (prepared_tables() below; saves the re-layout
+// launch).  A tensor is recognised by its object (TensorImpl), version counter, data pointer and size, and its entry is
+// dropped once the object is gone.  `tensor.data = other` swaps storage without bumping the version: the data
 // pointer in the key catches that unless the allocator hands the new storage the old address -- after such surgery on
 // a packed module call quant_engine.clear_cache() (or run with QE_NO_CACHE=1, which disables both caches).
 // ------------------------------------------------------------------------------------------
@@ -161,6 +163,21 @@ Des read_des_uncached(const torch::Tensor &des)
 // read-modify-write per half; here the elements go through a 64-bit shift register that is flushed a byte
 // at a time (no RMW, output need not be pre-zeroed).  The range check (tpack.cu:211-215) runs in the same pass.
 // ------------------------------------------------------------------------------------------
+// des = [n_bits, sign, *shape], int32 (tpack.cu:228-238), built on the host
+torch::Tensor make_des(int n_bits, bool sign, c10::IntArrayRef sizes)
+{
+    std::vector<int32_t> d{n_bits, sign ? 1 : 0};
+    for (auto s : sizes) d.push_back((int32_t)s);
+    return torch::tensor(d, torch::dtype(torch::kInt));
+}
+
+// the b-bit stream of x's elements (uninitialised) and the zeroed range flag of the pass that fills it, on x's device
+std::pair<torch::Tensor, torch::Tensor> packed_and_status(const torch::Tensor &x, int n_bits)
+{
+    return {torch::empty({qe_packed_nbytes(x.numel(), n_bits)}, torch::dtype(torch::kByte).device(x.device())),
+            torch::zeros({1}, torch::dtype(torch::kInt).device(x.device()))};
+}
+
 std::vector<torch::Tensor> tpack_host(const torch::Tensor &x, int n_bits, bool sign)
 {
     (void)to_qe_dtype(x, "tpack_cpu");                     // same dtype set as the device path
@@ -187,12 +204,7 @@ std::vector<torch::Tensor> tpack_host(const torch::Tensor &x, int n_bits, bool s
         while (fill >= 8) { dst[o++] = (uint8_t)reg; reg >>= 8; fill -= 8; }
     }
     if (fill > 0) dst[o++] = (uint8_t)reg;
-
-    std::vector<int32_t> d;
-    d.push_back(n_bits);
-    d.push_back(sign ? 1 : 0);
-    for (auto s : x.sizes()) d.push_back((int32_t)s);
-    return {x_out, torch::tensor(d, torch::dtype(torch::kInt))};
+    return {x_out, make_des(n_bits, sign, x.sizes())};
 }
 
 torch::Tensor tunpack_host(const torch::Tensor &x, const Des &d)
@@ -231,23 +243,15 @@ static std::vector<torch::Tensor> tpack_impl(torch::Tensor x, int n_bits, bool s
     const int dtype = to_qe_dtype(x, "tpack_cuda");
 
     c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
-    const int64_t n = x.numel();
-    auto x_out = torch::empty({qe_packed_nbytes(n, n_bits)}, torch::dtype(torch::kByte).device(x.device()));
-    auto status = torch::zeros({1}, torch::dtype(torch::kInt).device(x.device()));
-
-    check_status(qe_tpack(x.data_ptr(), dtype, n, n_bits, sign ? 1 : 0, x_out.data_ptr<uint8_t>(),
+    auto [x_out, status] = packed_and_status(x, n_bits);
+    check_status(qe_tpack(x.data_ptr(), dtype, x.numel(), n_bits, sign ? 1 : 0, x_out.data_ptr<uint8_t>(),
                           status.data_ptr<int32_t>(), current_stream(x)),
                  "tpack");
     // CHECK_RANGE (tpack.cu:14,211-215), fused into the pack pass: one 4-byte read-back
     // instead of two full reductions + two syncs.
     if (check_now) TORCH_CHECK(status.item<int>() == 0, "The input tensor is out of range.");
 
-    // des = [n_bits, sign, *shape], int32, on x.device (tpack.cu:228-238)
-    std::vector<int32_t> d;
-    d.push_back(n_bits);
-    d.push_back(sign ? 1 : 0);
-    for (auto s : x.sizes()) d.push_back((int32_t)s);
-    auto des = torch::tensor(d, torch::dtype(torch::kInt)).to(x.device());
+    auto des = make_des(n_bits, sign, x.sizes()).to(x.device());
     if (check_now) return {x_out, des};
     return {x_out, des, status};
 }
@@ -284,29 +288,153 @@ torch::Tensor tunpack(torch::Tensor x, torch::Tensor des)
     return x_out.reshape(d.shape);
 }
 
-qe_qparam make_qparam(const torch::Tensor &data, const Des &d, const torch::Tensor &scale, const torch::Tensor &zero)
+// ------------------------------------------------------------------------------------------
+// Argument checks shared by the four quantised operators.  The messages and the order in which the checks fire are the
+// reference's and part of the contract: every operator runs them in the order it always has.
+// ------------------------------------------------------------------------------------------
+struct Operand {                     // one packed operand
+    const char *name;                // "input" | "weight", as the messages spell it
+    const torch::Tensor &data, &scale, &zero;
+    const Des &des;
+    int64_t numel;                   // elements the bit stream must hold
+    int64_t channels;                // scale / zero hold 1 element or one per channel ...
+    const char *channels_name;       // ... "input_channel" / "output_channel" (conv), "batch_size" / "output_size" (linear)
+    bool exact;                      // linear: exactly `channels` (indexed by row / column); conv: at least
+    qe_qparam qparam() const
+    {
+        return {data.data_ptr<uint8_t>(), des.n_bits, des.sign, scale.data_ptr<float>(), zero.data_ptr<float>(), (int32_t)scale.numel()};
+    }
+};
+
+// data_ptr<unsigned char>() / data_ptr<float>() of the reference (quantconv2d.cu:235-247) throw on a dtype mismatch; check
+// up front, plus the buffer lengths the kernel will index.  x == nullptr: float input.  Each check runs over the input,
+// then the weight, before the next check starts.
+void check_operands(const Operand *x, const Operand &w)
 {
-    qe_qparam q;
-    q.data = data.data_ptr<uint8_t>();
-    q.n_bits = d.n_bits;
-    q.sign = d.sign;
-    q.scale = scale.data_ptr<float>();
-    q.zero = zero.data_ptr<float>();
-    q.n_param = (int32_t)scale.numel();
-    return q;
+    auto each = [&](auto check) { if (x) check(*x); check(w); };
+    auto is = [](const torch::Tensor &t, torch::ScalarType want) {
+        TORCH_CHECK(t.scalar_type() == want, "expected scalar type ", toString(want), " but found ", toString(t.scalar_type()));
+    };
+    each([&](const Operand &o) { is(o.data, torch::kByte); });
+    each([&](const Operand &o) { is(o.scale, torch::kFloat); is(o.zero, torch::kFloat); });
+    each([](const Operand &o) {
+        TORCH_CHECK(o.data.numel() >= qe_packed_nbytes(o.numel, o.des.n_bits), "The packed ", o.name, " is shorter than its description requires.");
+    });
+    // The reference expands 0-dim scales (quantlinear.cu:276-290) and indexes anything else by channel; a 1-element tensor
+    // is accepted as a broadcast too, anything else has to cover every channel.
+    each([](const Operand &o) {
+        const int64_t n = o.scale.numel();
+        TORCH_CHECK(n == o.zero.numel() && (n == 1 || (o.exact ? n == o.channels : n >= o.channels)), o.name, "_scale/", o.name,
+                    "_zero must hold 1 or ", o.channels_name, " elements");
+    });
 }
 
+// The optional fp32 bias of n output channels; returns its pointer.  reference_linear: quantlinear's own form, which
+// looks at device and strides only here and checks the length like the reference (quantlinear.cu:267).
+const float *check_bias(const c10::optional<torch::Tensor> &bias, int64_t n, const char *channels_name, bool reference_linear)
+{
+    if (!bias.has_value()) return nullptr;
+    if (reference_linear) { CHECK_INPUT(bias.value()); }
+    TORCH_CHECK(bias.value().scalar_type() == torch::kFloat, "expected scalar type Float but found ", toString(bias.value().scalar_type()));
+    if (reference_linear) {
+        TORCH_CHECK(n == bias.value().size(0), "Weight and bias do not match");
+    } else {
+        TORCH_CHECK(bias.value().numel() >= n, "bias must hold ", channels_name, " elements");
+    }
+    return bias.value().data_ptr<float>();
+}
+
+// The conv problem of an (N, IC, H, W) input and a weight description (quantconv2d.cu:199-211,
+// quantconv2d_float_input.cu:168-178; weight_shape[1] is never read)
+struct ConvGeometry {
+    qe_conv_shape sh;
+    int64_t OH, OW;
+    int64_t weight_numel() const { return (int64_t)sh.OC * sh.IC * sh.KH * sh.KW; }
+};
+ConvGeometry conv_geometry(int64_t N, int64_t IC, int64_t H, int64_t W, const Des &wd, int stride, int padding)
+{
+    TORCH_CHECK(stride > 0 && padding >= 0, "stride must be positive and padding non-negative");
+    ConvGeometry g;
+    g.sh = {(int32_t)N, (int32_t)IC, (int32_t)H, (int32_t)W, (int32_t)wd.shape[0], (int32_t)wd.shape[2], (int32_t)wd.shape[3], stride, padding};
+    g.OH = (g.sh.H + 2 * padding - g.sh.KH) / stride + 1;
+    g.OW = (g.sh.W + 2 * padding - g.sh.KW) / stride + 1;
+    TORCH_CHECK(g.OH > 0 && g.OW > 0, "Calculated output size is too small: (", g.OH, " x ", g.OW, ")");
+    return g;
+}
+
+// ------------------------------------------------------------------------------------------
+// The prepared-table cache of both conv operators: the x-independent tables of qe_conv_prepare / qe_conv_f32_prepare are
+// built once per (weight, scale, zero, bias) tensor set and kept while those tensors live unchanged; later calls run only
+// the convolution.  Results are bit-identical.  One entry per weight tensor.
+// Stream rule, the same for both operators (the float-input operator used to rebuild its tables when another stream
+// called): the tables are filled in stream order and never rewritten, so an entry remembers the stream that filled it, and
+// a hit from another stream synchronises that stream once and takes the entry over.
+// ------------------------------------------------------------------------------------------
+struct PrepKey {               // what the tables depend on besides the tensors; a field an operator does not use stays zero
+    int x_bits;                // 32: float input
+    int w_bits, w_sign;
+    uint64_t layout;           // packed input: qe_conv_prepared_layout, what the tables look like -- NOT the batch or image
+                               // size, so alternating batch sizes of one layer share the entry
+    qe_conv_shape sh;          // float input: the problem with N = 0 (the tables do not depend on the batch size)
+    size_t bytes;
+    bool operator==(const PrepKey &o) const
+    {
+        return x_bits == o.x_bits && w_bits == o.w_bits && w_sign == o.w_sign && layout == o.layout &&
+               std::memcmp(&sh, &o.sh, sizeof(sh)) == 0 && bytes == o.bytes;
+    }
+};
 struct PrepEntry {
     TensorKey w, s, z, b;
     bool has_bias = false;
-    int x_bits = 0, w_bits = 0, w_sign = 0;
-    qe_conv_shape sh{};        // float-input entries: the problem with N = 0 (the tables do not depend on the batch size)
-    uint64_t layout = 0;       // qe_conv_prepared_layout: what the tables look like -- NOT the batch or image size, so
-                               // alternating batch sizes of one layer share the entry
+    PrepKey key{};
     torch::Tensor prepared;
     qe_stream_t stream = nullptr;
 };
 std::unordered_map<const void *, PrepEntry> g_prep_cache;
+
+bool cacheable(const Operand &w, const c10::optional<torch::Tensor> &bias)
+{
+    return cacheable(w.data) && cacheable(w.scale) && cacheable(w.zero) && (!bias.has_value() || cacheable(bias.value()));
+}
+
+// fill(void *tables) runs the operator's prepare function on `stream`
+template <class Fill>
+torch::Tensor fresh_tables(size_t bytes, const torch::Device &device, Fill fill)
+{
+    auto prepared = torch::empty({(int64_t)bytes}, torch::dtype(torch::kByte).device(device));
+    fill(prepared.data_ptr());
+    return prepared;
+}
+
+// The tables of a cacheable weight set, valid for work queued on `stream`
+template <class Fill>
+torch::Tensor prepared_tables(const Operand &w, const c10::optional<torch::Tensor> &bias, const PrepKey &key, qe_stream_t stream,
+                              const torch::Device &device, Fill fill)
+{
+    {
+        std::lock_guard<std::mutex> lock(g_cache_mutex);
+        auto it = g_prep_cache.find(w.data.unsafeGetTensorImpl());
+        if (it != g_prep_cache.end()) {
+            PrepEntry &e = it->second;
+            if (e.w.matches(w.data) && e.s.matches(w.scale) && e.z.matches(w.zero) && e.has_bias == bias.has_value() &&
+                (!e.has_bias || e.b.matches(bias.value())) && e.key == key) {
+                ++g_prep_hits;
+                if (e.stream != stream) {
+                    TORCH_CHECK(hipStreamSynchronize(static_cast<hipStream_t>(e.stream)) == hipSuccess, "hipStreamSynchronize failed");
+                    e.stream = stream;
+                }
+                return e.prepared;
+            }
+        }
+    }
+    PrepEntry e{TensorKey::of(w.data), TensorKey::of(w.scale), TensorKey::of(w.zero), bias.has_value() ? TensorKey::of(bias.value()) : TensorKey{},
+                bias.has_value(), key, fresh_tables(key.bytes, device, fill), stream};
+    std::lock_guard<std::mutex> lock(g_cache_mutex);
+    ++g_prep_misses;
+    if (g_prep_cache.size() > 4096) g_prep_cache.clear();
+    g_prep_cache[w.data.unsafeGetTensorImpl()] = e;
+    return e.prepared;
+}
 
 void clear_cache()
 {
@@ -341,10 +469,6 @@ std::vector<torch::Tensor> quantize_pack(torch::Tensor x, torch::Tensor scale, t
                     "per-channel scale must hold x.size(channel_dim) elements");
         for (int64_t d = channel_dim + 1; d < x.dim(); ++d) inner *= x.size(d);
     }
-    std::vector<int32_t> dv;
-    dv.push_back(n_bits);
-    dv.push_back(sign ? 1 : 0);
-    for (auto sz : x.sizes()) dv.push_back((int32_t)sz);
     if (!x.device().is_cuda()) {   // host tensors: the module's own arithmetic, then the host packer
         std::vector<int64_t> bshape(x.dim(), 1);
         if (scale.numel() > 1) bshape[channel_dim] = scale.numel();
@@ -356,15 +480,13 @@ std::vector<torch::Tensor> quantize_pack(torch::Tensor x, torch::Tensor scale, t
     CHECK_CONTIGUOUS(scale);
     CHECK_CONTIGUOUS(zero);
     c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
-    const int64_t n = x.numel();
-    auto x_out = torch::empty({qe_packed_nbytes(n, n_bits)}, torch::dtype(torch::kByte).device(x.device()));
-    auto status = torch::zeros({1}, torch::dtype(torch::kInt).device(x.device()));
-    check_status(qe_quantize_pack(x.data_ptr<float>(), n, scale.data_ptr<float>(), zero.data_ptr<float>(), (int32_t)scale.numel(),
+    auto [x_out, status] = packed_and_status(x, n_bits);
+    check_status(qe_quantize_pack(x.data_ptr<float>(), x.numel(), scale.data_ptr<float>(), zero.data_ptr<float>(), (int32_t)scale.numel(),
                                   inner, (float)qmin, (float)qmax, n_bits, sign ? 1 : 0, x_out.data_ptr<uint8_t>(),
                                   status.data_ptr<int32_t>(), current_stream(x)),
                  "quantize_pack");
     TORCH_CHECK(status.item<int>() == 0, "The input tensor is out of range.");
-    return {x_out, torch::tensor(dv, torch::dtype(torch::kInt)).to(x.device())};
+    return {x_out, make_des(n_bits, sign, x.sizes()).to(x.device())};
 }
 
 // ------------------------------------------------------------------------------------------
@@ -392,101 +514,37 @@ torch::Tensor quantconv2d(const torch::Tensor &input, const torch::Tensor &input
     const Des wd = read_des(weight_des);  // quantconv2d.cu:194-196
     CHECK_NBITS(xd.n_bits);
     CHECK_NBITS(wd.n_bits);
-    TORCH_CHECK(stride > 0 && padding >= 0, "stride must be positive and padding non-negative");
-
-    qe_conv_shape sh;
-    sh.N = (int32_t)xd.shape[0]; sh.IC = (int32_t)xd.shape[1];      // quantconv2d.cu:199-202
-    sh.H = (int32_t)xd.shape[2]; sh.W = (int32_t)xd.shape[3];
-    sh.OC = (int32_t)wd.shape[0];                                   // :205 (weight_shape[1] is never read)
-    sh.KH = (int32_t)wd.shape[2]; sh.KW = (int32_t)wd.shape[3];     // :206-207
-    sh.stride = stride; sh.padding = padding;
-    const int64_t OH = (sh.H + 2 * padding - sh.KH) / stride + 1;   // :210
-    const int64_t OW = (sh.W + 2 * padding - sh.KW) / stride + 1;   // :211
-    TORCH_CHECK(OH > 0 && OW > 0, "Calculated output size is too small: (", OH, " x ", OW, ")");
-
-    // data_ptr<unsigned char>() / data_ptr<float>() of the reference (:235-247) throw on a
-    // dtype mismatch; check up front, plus the buffer lengths the kernel will index.
-    TORCH_CHECK(input.scalar_type() == torch::kByte, "expected scalar type Byte but found ", toString(input.scalar_type()));
-    TORCH_CHECK(weight.scalar_type() == torch::kByte, "expected scalar type Byte but found ", toString(weight.scalar_type()));
-    for (const torch::Tensor *t : {&input_scale, &input_zero, &weight_scale, &weight_zero})
-        TORCH_CHECK(t->scalar_type() == torch::kFloat, "expected scalar type Float but found ", toString(t->scalar_type()));
-    TORCH_CHECK(input.numel() >= qe_packed_nbytes((int64_t)sh.N * sh.IC * sh.H * sh.W, xd.n_bits),
-                "The packed input is shorter than its description requires.");
-    TORCH_CHECK(weight.numel() >= qe_packed_nbytes((int64_t)sh.OC * sh.IC * sh.KH * sh.KW, wd.n_bits),
-                "The packed weight is shorter than its description requires.");
-    TORCH_CHECK(input_scale.numel() == input_zero.numel() && (input_scale.numel() == 1 || input_scale.numel() >= sh.IC),
-                "input_scale/input_zero must hold 1 or input_channel elements");
-    TORCH_CHECK(weight_scale.numel() == weight_zero.numel() && (weight_scale.numel() == 1 || weight_scale.numel() >= sh.OC),
-                "weight_scale/weight_zero must hold 1 or output_channel elements");
-    const float *bias_ptr = nullptr;
-    if (bias.has_value()) {
-        TORCH_CHECK(bias.value().scalar_type() == torch::kFloat, "expected scalar type Float but found ",
-                    toString(bias.value().scalar_type()));
-        TORCH_CHECK(bias.value().numel() >= sh.OC, "bias must hold output_channel elements");
-        bias_ptr = bias.value().data_ptr<float>();
-    }
+    const ConvGeometry g = conv_geometry(xd.shape[0], xd.shape[1], xd.shape[2], xd.shape[3], wd, stride, padding);
+    const qe_conv_shape &sh = g.sh;
+    const Operand x{"input", input, input_scale, input_zero, xd, (int64_t)sh.N * sh.IC * sh.H * sh.W, sh.IC, "input_channel", false};
+    const Operand w{"weight", weight, weight_scale, weight_zero, wd, g.weight_numel(), sh.OC, "output_channel", false};
+    check_operands(&x, w);
+    const float *bias_ptr = check_bias(bias, sh.OC, "output_channel", false);
 
     c10::hip::HIPGuardMasqueradingAsCUDA guard(input.device());
-    auto output = torch::empty({sh.N, sh.OC, OH, OW}, torch::dtype(torch::kFloat32).device(input.device()));
-    const qe_qparam xq = make_qparam(input, xd, input_scale, input_zero);
-    const qe_qparam wq = make_qparam(weight, wd, weight_scale, weight_zero);
+    auto output = torch::empty({sh.N, sh.OC, g.OH, g.OW}, torch::dtype(torch::kFloat32).device(input.device()));
+    const qe_qparam xq = x.qparam(), wq = w.qparam();
+    const qe_stream_t stream = current_stream(input);
+    auto bytes = [&](size_t n) { return torch::empty({(int64_t)n}, torch::dtype(torch::kByte).device(input.device())); };
 
-    // Prepared weight tables: built once per (weight, scale, zero, bias) tensor set and kept while those tensors live
-    // unchanged; later calls run only the convolution (qe_quantconv2d_prepared).  Results are bit-identical.
     const size_t prep_bytes = qe_conv_prepared_bytes(&sh, xd.n_bits, wd.n_bits);
-    const uint64_t prep_layout = qe_conv_prepared_layout(&sh, xd.n_bits, wd.n_bits);
-    const bool use_cache = prep_bytes > 0 && qe_quantconv2d_path(&sh, &xq, &wq) == 1 && cacheable(weight) &&
-                           cacheable(weight_scale) && cacheable(weight_zero) && (!bias.has_value() || cacheable(bias.value()));
-    if (use_cache) {
-        torch::Tensor prepared;
-        {
-            std::lock_guard<std::mutex> lock(g_cache_mutex);
-            auto it = g_prep_cache.find(weight.unsafeGetTensorImpl());
-            if (it != g_prep_cache.end()) {
-                const PrepEntry &e = it->second;
-                const bool hit = e.w.matches(weight) && e.s.matches(weight_scale) && e.z.matches(weight_zero) &&
-                                 e.has_bias == bias.has_value() && (!e.has_bias || e.b.matches(bias.value())) &&
-                                 e.x_bits == xd.n_bits && e.w_bits == wd.n_bits && e.w_sign == wd.sign &&
-                                 e.layout == prep_layout && (size_t)e.prepared.numel() == prep_bytes;
-                if (hit) { prepared = e.prepared; ++g_prep_hits; }
-            }
-        }
-        if (!prepared.defined()) {
-            prepared = torch::empty({(int64_t)prep_bytes}, torch::dtype(torch::kByte).device(input.device()));
-            check_status(qe_conv_prepare(&wq, bias_ptr, &sh, xd.n_bits, prepared.data_ptr(), prep_bytes, current_stream(input)),
-                         "quantconv2d (prepare)");
-            // the tables are filled in stream order; other streams using the entry later would need an event --
-            // the entry therefore remembers its stream and is only reused on it
-            PrepEntry e;
-            e.w = TensorKey::of(weight); e.s = TensorKey::of(weight_scale); e.z = TensorKey::of(weight_zero);
-            e.has_bias = bias.has_value();
-            if (e.has_bias) e.b = TensorKey::of(bias.value());
-            e.x_bits = xd.n_bits; e.w_bits = wd.n_bits; e.w_sign = wd.sign; e.layout = prep_layout; e.prepared = prepared;
-            e.stream = current_stream(input);
-            std::lock_guard<std::mutex> lock(g_cache_mutex);
-            ++g_prep_misses;
-            if (g_prep_cache.size() > 4096) g_prep_cache.clear();
-            g_prep_cache[weight.unsafeGetTensorImpl()] = e;
-        } else {
-            std::lock_guard<std::mutex> lock(g_cache_mutex);
-            auto it = g_prep_cache.find(weight.unsafeGetTensorImpl());
-            if (it != g_prep_cache.end() && it->second.stream != current_stream(input)) {
-                // another stream: order it behind the stream that filled the tables (they are never rewritten)
-                TORCH_CHECK(hipStreamSynchronize(static_cast<hipStream_t>(it->second.stream)) == hipSuccess, "hipStreamSynchronize failed");
-                it->second.stream = current_stream(input);
-            }
-        }
+    const PrepKey key{xd.n_bits, wd.n_bits, wd.sign, qe_conv_prepared_layout(&sh, xd.n_bits, wd.n_bits), qe_conv_shape{}, prep_bytes};
+    if (prep_bytes > 0 && qe_quantconv2d_path(&sh, &xq, &wq) == 1 && cacheable(w, bias)) {
+        const torch::Tensor prepared = prepared_tables(w, bias, key, stream, input.device(), [&](void *tables) {
+            check_status(qe_conv_prepare(&wq, bias_ptr, &sh, xd.n_bits, tables, prep_bytes, stream), "quantconv2d (prepare)");
+        });
         const size_t sc_bytes = qe_quantconv2d_prepared_workspace_bytes(&sh, xd.n_bits, wd.n_bits);
-        auto scratch = torch::empty({(int64_t)sc_bytes}, torch::dtype(torch::kByte).device(input.device()));
+        auto scratch = bytes(sc_bytes);
         check_status(qe_quantconv2d_prepared(&xq, &wq, bias_ptr, &sh, prepared.data_ptr(), prep_bytes, output.data_ptr<float>(),
-                                             sc_bytes ? scratch.data_ptr() : nullptr, sc_bytes, current_stream(input)),
+                                             sc_bytes ? scratch.data_ptr() : nullptr, sc_bytes, stream),
                      "quantconv2d");
         return output;
     }
+    // nothing to keep, or tensors that cannot be recognised again: the per-call route prepares inside the call
     const size_t ws_bytes = qe_quantconv2d_workspace_bytes(&sh, xd.n_bits, wd.n_bits);
-    auto workspace = torch::empty({(int64_t)ws_bytes}, torch::dtype(torch::kByte).device(input.device()));
+    auto workspace = bytes(ws_bytes);
     check_status(qe_quantconv2d(&xq, &wq, bias_ptr, &sh, output.data_ptr<float>(),
-                                ws_bytes ? workspace.data_ptr() : nullptr, ws_bytes, current_stream(input)),
+                                ws_bytes ? workspace.data_ptr() : nullptr, ws_bytes, stream),
                  "quantconv2d");
     return output;
 }
@@ -511,81 +569,35 @@ torch::Tensor quantconv2d_float_input(const torch::Tensor &input, const torch::T
     TORCH_CHECK(weight_des.numel() >= 6, "The description is too short, which should be at least 6.");
     const Des wd = read_des(weight_des);  // quantconv2d_float_input.cu:163-165
     CHECK_NBITS(wd.n_bits);
-    TORCH_CHECK(stride > 0 && padding >= 0, "stride must be positive and padding non-negative");
-
-    qe_conv_shape sh;
-    sh.N = (int32_t)input.size(0); sh.IC = (int32_t)input.size(1);  // :168-171
-    sh.H = (int32_t)input.size(2); sh.W = (int32_t)input.size(3);
-    sh.OC = (int32_t)wd.shape[0]; sh.KH = (int32_t)wd.shape[2]; sh.KW = (int32_t)wd.shape[3];  // :174-176
-    sh.stride = stride; sh.padding = padding;
-    const int64_t OH = (sh.H + 2 * padding - sh.KH) / stride + 1;  // :177
-    const int64_t OW = (sh.W + 2 * padding - sh.KW) / stride + 1;  // :178
-    TORCH_CHECK(OH > 0 && OW > 0, "Calculated output size is too small: (", OH, " x ", OW, ")");
-
-    TORCH_CHECK(weight.scalar_type() == torch::kByte, "expected scalar type Byte but found ", toString(weight.scalar_type()));
-    for (const torch::Tensor *t : {&weight_scale, &weight_zero})
-        TORCH_CHECK(t->scalar_type() == torch::kFloat, "expected scalar type Float but found ", toString(t->scalar_type()));
-    TORCH_CHECK(weight.numel() >= qe_packed_nbytes((int64_t)sh.OC * sh.IC * sh.KH * sh.KW, wd.n_bits),
-                "The packed weight is shorter than its description requires.");
-    TORCH_CHECK(weight_scale.numel() == weight_zero.numel() && (weight_scale.numel() == 1 || weight_scale.numel() >= sh.OC),
-                "weight_scale/weight_zero must hold 1 or output_channel elements");
-    const float *bias_ptr = nullptr;
-    if (bias.has_value()) {
-        TORCH_CHECK(bias.value().scalar_type() == torch::kFloat, "expected scalar type Float but found ",
-                    toString(bias.value().scalar_type()));
-        TORCH_CHECK(bias.value().numel() >= sh.OC, "bias must hold output_channel elements");
-        bias_ptr = bias.value().data_ptr<float>();
-    }
+    const ConvGeometry g = conv_geometry(input.size(0), input.size(1), input.size(2), input.size(3), wd, stride, padding);
+    const qe_conv_shape &sh = g.sh;
+    const Operand w{"weight", weight, weight_scale, weight_zero, wd, g.weight_numel(), sh.OC, "output_channel", false};
+    check_operands(nullptr, w);
+    const float *bias_ptr = check_bias(bias, sh.OC, "output_channel", false);
 
     c10::hip::HIPGuardMasqueradingAsCUDA guard(input.device());
-    auto output = torch::empty({sh.N, sh.OC, OH, OW}, input.options());
-    const qe_qparam wq = make_qparam(weight, wd, weight_scale, weight_zero);
+    auto output = torch::empty({sh.N, sh.OC, g.OH, g.OW}, input.options());
+    const qe_qparam wq = w.qparam();
+    const qe_stream_t stream = current_stream(input);
     // bf16 MFMA kernel where the problem is eligible (its weight tables are x-independent: cached like the packed
     // operator's), the order-preserving VALU kernel otherwise
     const size_t prep_bytes = qe_quantconv2d_float_input_path(&sh, &wq) == 1 ? qe_quantconv2d_float_input_workspace_bytes(&sh, wd.n_bits) : 0;
-    qe_conv_shape sh_key = sh;
-    sh_key.N = 0;              // the weight tables do not depend on the batch size: alternating batch sizes share the entry
     if (prep_bytes > 0) {
-        const bool use_cache = cacheable(weight) && cacheable(weight_scale) && cacheable(weight_zero) &&
-                               (!bias.has_value() || cacheable(bias.value()));
-        torch::Tensor prepared;
-        if (use_cache) {
-            std::lock_guard<std::mutex> lock(g_cache_mutex);
-            auto it = g_prep_cache.find(weight.unsafeGetTensorImpl());
-            if (it != g_prep_cache.end()) {
-                const PrepEntry &e = it->second;
-                const bool hit = e.w.matches(weight) && e.s.matches(weight_scale) && e.z.matches(weight_zero) &&
-                                 e.has_bias == bias.has_value() && (!e.has_bias || e.b.matches(bias.value())) &&
-                                 e.x_bits == 32 && e.w_bits == wd.n_bits && e.w_sign == wd.sign &&
-                                 std::memcmp(&e.sh, &sh_key, sizeof(sh_key)) == 0 && (size_t)e.prepared.numel() == prep_bytes &&
-                                 e.stream == current_stream(input);
-                if (hit) { prepared = e.prepared; ++g_prep_hits; }
-            }
-        }
-        if (!prepared.defined()) {
-            prepared = torch::empty({(int64_t)prep_bytes}, torch::dtype(torch::kByte).device(input.device()));
-            check_status(qe_conv_f32_prepare(&wq, bias_ptr, &sh, prepared.data_ptr(), prep_bytes, current_stream(input)),
-                         "quantconv2d_float_input (prepare)");
-            if (use_cache) {
-                PrepEntry e;
-                e.w = TensorKey::of(weight); e.s = TensorKey::of(weight_scale); e.z = TensorKey::of(weight_zero);
-                e.has_bias = bias.has_value();
-                if (e.has_bias) e.b = TensorKey::of(bias.value());
-                e.x_bits = 32; e.w_bits = wd.n_bits; e.w_sign = wd.sign; e.sh = sh_key; e.prepared = prepared;
-                e.stream = current_stream(input);
-                std::lock_guard<std::mutex> lock(g_cache_mutex);
-                ++g_prep_misses;
-                if (g_prep_cache.size() > 4096) g_prep_cache.clear();
-                g_prep_cache[weight.unsafeGetTensorImpl()] = e;
-            }
-        }
+        qe_conv_shape sh_key = sh;
+        sh_key.N = 0;
+        const PrepKey key{32, wd.n_bits, wd.sign, 0, sh_key, prep_bytes};
+        auto fill = [&](void *tables) {
+            check_status(qe_conv_f32_prepare(&wq, bias_ptr, &sh, tables, prep_bytes, stream), "quantconv2d_float_input (prepare)");
+        };
+        // tensors that cannot be recognised again: the kernel still needs its tables, in a buffer of this call
+        const torch::Tensor prepared = cacheable(w, bias) ? prepared_tables(w, bias, key, stream, input.device(), fill)
+                                                          : fresh_tables(prep_bytes, input.device(), fill);
         check_status(qe_quantconv2d_float_input_prepared(input.data_ptr<float>(), &wq, bias_ptr, &sh, prepared.data_ptr(), prep_bytes,
-                                                         output.data_ptr<float>(), current_stream(input)),
+                                                         output.data_ptr<float>(), stream),
                      "quantconv2d_float_input");
         return output;
     }
-    check_status(qe_quantconv2d_float_input(input.data_ptr<float>(), &wq, bias_ptr, &sh, output.data_ptr<float>(),
-                                            current_stream(input)),
+    check_status(qe_quantconv2d_float_input(input.data_ptr<float>(), &wq, bias_ptr, &sh, output.data_ptr<float>(), stream),
                  "quantconv2d_float_input");
     return output;
 }
@@ -640,31 +652,14 @@ torch::Tensor quantlinear(const torch::Tensor &input, const torch::Tensor &input
     const int64_t B = xd.shape[0], K = xd.shape[1], O = wd.shape[0];   // :272-274
     TORCH_CHECK(K == wd.shape[1], "Input and weight do not match");    // :261
     TORCH_CHECK(B >= 0 && K >= 0 && O >= 0 && K < (1ll << 31) && O < (1ll << 31), "invalid linear shape");
-    const float *bias_ptr = nullptr;
-    if (bias.has_value()) {
-        CHECK_INPUT(bias.value());
-        TORCH_CHECK(bias.value().scalar_type() == torch::kFloat, "expected scalar type Float but found ",
-                    toString(bias.value().scalar_type()));
-        TORCH_CHECK(O == bias.value().size(0), "Weight and bias do not match");   // :267
-        bias_ptr = bias.value().data_ptr<float>();
-    }
-    TORCH_CHECK(input.scalar_type() == torch::kByte, "expected scalar type Byte but found ", toString(input.scalar_type()));
-    TORCH_CHECK(weight.scalar_type() == torch::kByte, "expected scalar type Byte but found ", toString(weight.scalar_type()));
-    for (const torch::Tensor *t : {&input_scale, &input_zero, &weight_scale, &weight_zero})
-        TORCH_CHECK(t->scalar_type() == torch::kFloat, "expected scalar type Float but found ", toString(t->scalar_type()));
-    TORCH_CHECK(input.numel() >= qe_packed_nbytes(B * K, xd.n_bits), "The packed input is shorter than its description requires.");
-    TORCH_CHECK(weight.numel() >= qe_packed_nbytes(O * K, wd.n_bits), "The packed weight is shorter than its description requires.");
-    // The reference expands 0-dim scales (:276-290) and indexes anything else by row / column; a 1-element tensor
-    // is accepted as a broadcast too, anything else has to cover every row / column.
-    TORCH_CHECK(input_scale.numel() == input_zero.numel() && (input_scale.numel() == 1 || input_scale.numel() == B),
-                "input_scale/input_zero must hold 1 or batch_size elements");
-    TORCH_CHECK(weight_scale.numel() == weight_zero.numel() && (weight_scale.numel() == 1 || weight_scale.numel() == O),
-                "weight_scale/weight_zero must hold 1 or output_size elements");
+    const float *bias_ptr = check_bias(bias, O, "output_size", true);   // :267: before the operands, as in the reference
+    const Operand x{"input", input, input_scale, input_zero, xd, B * K, B, "batch_size", true};
+    const Operand w{"weight", weight, weight_scale, weight_zero, wd, O * K, O, "output_size", true};
+    check_operands(&x, w);
 
     c10::hip::HIPGuardMasqueradingAsCUDA guard(input.device());
     auto output = torch::empty({B, O}, torch::dtype(torch::kFloat32).device(input.device()));   // :166
-    const qe_qparam xq = make_qparam(input, xd, input_scale, input_zero);
-    const qe_qparam wq = make_qparam(weight, wd, weight_scale, weight_zero);
+    const qe_qparam xq = x.qparam(), wq = w.qparam();
     check_status(qe_quantlinear(&xq, &wq, bias_ptr, B, (int32_t)K, (int32_t)O, output.data_ptr<float>(),
                                 current_stream(input)), "quantlinear");
     return output;
@@ -691,22 +686,12 @@ torch::Tensor quantlinear_float_input(const torch::Tensor &input, const torch::T
     const int64_t B = input.size(0), K = input.size(1), O = wd.shape[0];   // :146-150
     TORCH_CHECK(K == wd.shape[1], "Input and weight do not match");        // (the reference never compares them)
     TORCH_CHECK(K < (1ll << 31) && O >= 0 && O < (1ll << 31), "invalid linear shape");
-    TORCH_CHECK(weight.scalar_type() == torch::kByte, "expected scalar type Byte but found ", toString(weight.scalar_type()));
-    for (const torch::Tensor *t : {&weight_scale, &weight_zero})
-        TORCH_CHECK(t->scalar_type() == torch::kFloat, "expected scalar type Float but found ", toString(t->scalar_type()));
-    TORCH_CHECK(weight.numel() >= qe_packed_nbytes(O * K, wd.n_bits), "The packed weight is shorter than its description requires.");
-    TORCH_CHECK(weight_scale.numel() == weight_zero.numel() && (weight_scale.numel() == 1 || weight_scale.numel() == O),
-                "weight_scale/weight_zero must hold 1 or output_size elements");
-    const float *bias_ptr = nullptr;
-    if (bias.has_value()) {
-        TORCH_CHECK(bias.value().scalar_type() == torch::kFloat, "expected scalar type Float but found ",
-                    toString(bias.value().scalar_type()));
-        TORCH_CHECK(bias.value().numel() >= O, "bias must hold output_size elements");
-        bias_ptr = bias.value().data_ptr<float>();
-    }
+    const Operand w{"weight", weight, weight_scale, weight_zero, wd, O * K, O, "output_size", true};
+    check_operands(nullptr, w);
+    const float *bias_ptr = check_bias(bias, O, "output_size", false);
     c10::hip::HIPGuardMasqueradingAsCUDA guard(input.device());
     auto output = torch::empty({B, O}, input.options());   // :153
-    const qe_qparam wq = make_qparam(weight, wd, weight_scale, weight_zero);
+    const qe_qparam wq = w.qparam();
     check_status(qe_quantlinear_float_input(input.data_ptr<float>(), &wq, bias_ptr, B, (int32_t)K, (int32_t)O,
                                             output.data_ptr<float>(), current_stream(input)), "quantlinear_float_input");
     return output;

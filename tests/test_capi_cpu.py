@@ -65,3 +65,22 @@ def test_host_side_argument_checks_need_no_gpu():
     bad = capi.QeQParam(16, 9, 1, 16, 16, 1)
     assert L.qe_quantconv2d(ctypes.byref(bad), ctypes.byref(q), None, ctypes.byref(sh), ctypes.c_void_p(16),
                             None, 0, None) == 1
+
+
+def test_every_symbol_has_a_prototype():
+    """capi.lib() declares restype and argtypes of every header symbol from one table (an undeclared 64-bit result would
+    come back as a truncated C int), and the library's debug hooks stay out of SYMBOLS."""
+    text = open(os.path.join(REPO, "include", "quant_engine.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    params = {name: " ".join(p.split()) for name, p in re.findall(r"\b(qe_[a-z0-9_]+)\s*\(([^)]*)\)", text)}
+    assert sorted(params) == sorted(capi.SYMBOLS)
+    L = capi.lib()
+    for name in capi.SYMBOLS:
+        argtypes = getattr(L, name).argtypes
+        if params[name] == "void":
+            assert not argtypes, name
+        else:
+            assert argtypes is not None and len(argtypes) == params[name].count(",") + 1, name
+    assert L.qe_conv_prepared_layout.restype is ctypes.c_uint64
+    assert not [s for s in capi.SYMBOLS if s.startswith("qe_debug_")]
+    assert all(hasattr(L, s) and s not in capi.SYMBOLS for s in capi.DEBUG_PROTOTYPES)

@@ -159,3 +159,91 @@ def test_prepared_tables_serve_every_batch_size():
             _, o64 = oracle.quantconv2d(xpn, xdn, sx, zx, wp, wd, sw, zw, case["bias"], 1, 0, mode="f64", return_f64=True)
             err, allowed = conv_tolerance(y, o64, *chains)
             assert (err <= allowed).all(), "N=%d: worst err %.3g (allowed %.3g)" % (n, float(np.nanmax(err)), allowed)   # NaN fails
+
+
+# ---- the float-input operator shares the prepared-table cache: fp32 x, IC=64, 14x14, OC=96, 3x3 on the bf16 MFMA kernel ----
+from test_conv_gpu import _assert_conv_close  # noqa: E402
+
+
+def _float_input_layer(rng, N):
+    case = _random_case(rng, N, 64, 14, 14, 96, 3, 1, 1, 8, 1, 0, 0, w_pc=True, a_pc=False, zeros=True, bias=True)
+    wp, wd, sw, zw = case["w"]
+    t = dict(wp=_t(wp), wd=_t(wd), sw=_t(sw).reshape(-1, 1, 1, 1), zw=_t(zw).reshape(-1, 1, 1, 1), b=_t(case["bias"]))
+    # the tests below must not pass on the VALU kernel, which prepares nothing
+    assert capi.float_input_path(capi.conv_shape(N, 64, 14, 14, 96, 3, 3, 1, 1), capi.qparam(t["wp"], 8, 1, t["sw"], t["zw"])) == 1
+    return case, t
+
+
+def _float_input_close(y, xf, w, bias, what):
+    chains = [oracle.quantconv2d_float_input(xf, *w, bias, 1, 1, mode=m) for m in ("fp32", "fp32_fma")]
+    _, o64 = oracle.quantconv2d_float_input(xf, *w, bias, 1, 1, mode="f64", return_f64=True)
+    _assert_conv_close(y.cpu().numpy(), o64, chains[0], what, chains[1])
+
+
+def test_float_input_module_cache_hits_and_invalidates(engine):
+    import quant_engine
+    quant_engine.clear_cache()
+    case, t = _float_input_layer(np.random.RandomState(6), 2)
+    wp, wd, sw, zw = case["w"]
+    x = _t(case["xf"])
+    call = lambda: engine.quantconv2d_float_input(x, t["wp"], t["wd"], t["sw"], t["zw"], t["b"], 1, 1)
+    sb = quant_engine.cache_stats()
+    y0 = call()
+    s0 = quant_engine.cache_stats()
+    assert s0[1] - sb[1] == 1 and s0[3] - sb[3] == 1 and s0[2] == sb[2] and s0[4:] == [1, 1]   # one description, one weight set
+    y1 = call()
+    s1 = quant_engine.cache_stats()
+    assert s1[0] == s0[0] + 1 and s1[2] == s0[2] + 1 and s1[1] == s0[1] and s1[3] == s0[3]      # all hits, no new misses
+    assert torch.equal(y0, y1)
+    _float_input_close(y1, case["xf"], (wp, wd, sw, zw), case["bias"], "cached float-input conv")
+    # in-place change of the packed weights: version bump -> re-prepared, result follows the new weights
+    t["wp"].copy_(torch.flip(t["wp"], dims=[0]))
+    y2 = call()
+    s2 = quant_engine.cache_stats()
+    assert s2[3] == s1[3] + 1 and s2[2] == s1[2]
+    _float_input_close(y2, case["xf"], (np.ascontiguousarray(wp[::-1]), wd, sw, zw), case["bias"], "after the weight change")
+    quant_engine.clear_cache()
+    assert quant_engine.cache_stats()[4:] == [0, 0]
+
+
+def test_float_input_entry_is_shared_across_batch_sizes(engine):
+    """The float-input tables do not depend on the batch size either: batch sizes 5, 2, 5, 2 of one layer prepare once."""
+    import quant_engine
+    quant_engine.clear_cache()
+    case, t = _float_input_layer(np.random.RandomState(92), 5)
+    stats0 = quant_engine.cache_stats()
+    ys = [engine.quantconv2d_float_input(_t(case["xf"][:n]), t["wp"], t["wd"], t["sw"], t["zw"], t["b"], 1, 1) for n in (5, 2, 5, 2)]
+    stats = quant_engine.cache_stats()
+    assert stats[3] == stats0[3] + 1 and stats[2] == stats0[2] + 3     # prepared once, hit three times
+    _float_input_close(ys[0], case["xf"], case["w"], case["bias"], "batch 5")
+    _float_input_close(ys[1], case["xf"][:2], case["w"], case["bias"], "batch 2")
+    assert torch.equal(ys[2], ys[0]) and torch.equal(ys[3], ys[1])
+
+
+@pytest.mark.parametrize("op", ["quantconv2d", "quantconv2d_float_input"])
+def test_prepared_entry_follows_the_calling_stream(engine, op):
+    """An entry remembers the stream that filled it; a call from another stream waits for that stream once and takes the
+    entry over: current stream, a second stream, the first again -> one miss, two hits, three equal results."""
+    import quant_engine
+    quant_engine.clear_cache()
+    rng = np.random.RandomState(93)
+    if op == "quantconv2d":
+        case = _random_case(rng, 2, 64, 14, 14, 96, 3, 1, 1, 8, 1, 8, 1, w_pc=True, a_pc=False, zeros=False, bias=True)
+        wp, wd, sw, zw = case["w"]
+        x = tuple(_t(a) for a in case["x"])
+        t = dict(wp=_t(wp), wd=_t(wd), sw=_t(sw).reshape(-1, 1, 1, 1), zw=_t(zw).reshape(-1, 1, 1, 1), b=_t(case["bias"]))
+        assert capi.conv_prepared_layout(capi.conv_shape(2, 64, 14, 14, 96, 3, 3, 1, 1), 8, 8) != 0
+    else:
+        case, t = _float_input_layer(rng, 2)
+        x = (_t(case["xf"]),)
+    call = lambda: getattr(engine, op)(*x, t["wp"], t["wd"], t["sw"], t["zw"], t["b"], 1, 1)
+    torch.cuda.synchronize()
+    s0 = quant_engine.cache_stats()
+    y0 = call()
+    with torch.cuda.stream(torch.cuda.Stream()):
+        y1 = call()
+    y2 = call()
+    torch.cuda.synchronize()
+    s1 = quant_engine.cache_stats()
+    assert (s1[3] - s0[3], s1[2] - s0[2]) == (1, 2), "prepared (misses, hits) over the three calls: %s" % ((s1[3] - s0[3], s1[2] - s0[2]),)
+    assert torch.equal(y0, y1) and torch.equal(y0, y2)
