@@ -26,13 +26,15 @@
 // row poisons that row of that head only, a NaN in a key or value row that (image, head) only.
 //
 // Masked form (qe_attention_masked): the score becomes scale q.k + mask[n, h, t, s] + key_bias[n, s], restricted to
-// s <= t under `causal`.  Which operands exist is the template parameter MODE of both kernels (kMask | kBias | kCausal,
-// plus kVec4 where every mask / bias run of four keys is 16-byte aligned), never a branch in the tile loop: MODE 0 is the
-// unmasked kernel, instruction for instruction.  In the MFMA kernel a lane's 16 scores are four runs of four consecutive
-// keys of ONE query row, so the mask adds lane-locally; its loads are issued with the K prefetch, a tile ahead.  Causal
-// waves stop at the diagonal tile (the tiles above it are never loaded) and mask that tile by index.  While a row's
-// running max is still -inf (every key so far masked) the rescale factor is 1 and p is 0, so a later visible key starts
-// the row cleanly; a row with no visible key at all ends as 0 / 0 = NaN, that row of that head only.
+// s <= t under `causal`.  Both kernels add mask and key_bias to each other first, in fp32, then their sum to the score: a
+// call with both returns the bits of a call with the mask alone that holds that sum.  Which operands exist is the template
+// parameter MODE of both kernels (kMask | kBias | kCausal, plus kVec4 where every mask / bias run of four keys is 16-byte
+// aligned), never a branch in the tile loop: MODE 0 is the unmasked kernel, instruction for instruction.  In the MFMA
+// kernel a lane's 16 scores are four runs of four consecutive keys of ONE query row, so the mask adds lane-locally; its
+// loads are issued with the K prefetch, a tile ahead.  Causal waves stop at the diagonal tile (the tiles above it are never
+// loaded) and mask that tile by index.  While a row's running max is still -inf (every key so far masked) the rescale
+// factor is 1 and p is 0, so a later visible key starts the row cleanly; a row with no visible key at all ends as
+// 0 / 0 = NaN, that row of that head only.
 #include "qe_common.h"
 
 #include <algorithm>
@@ -286,8 +288,9 @@ __global__ __launch_bounds__(256) void attn_valu_kernel(const AttnArgs a)
             const float *kr = kbase + key * kv_step;
             s = 0.0f;
             for (int c = 0; c < a.d; ++c) s = fmaf(qs[wave][c], kr[c], s);
-            if constexpr (MASK) s += mrow[key];
-            if constexpr (BIAS) s += brow[key];
+            if constexpr (MASK && BIAS) s += mrow[key] + brow[key];      // summed first, as the MFMA kernel does
+            else if constexpr (MASK) s += mrow[key];
+            else if constexpr (BIAS) s += brow[key];
         }
         const float mn = fmaxf(m, wave_max(s));
         float alpha = exp2f((m - mn) * kLog2e);

@@ -18,7 +18,9 @@ def test_attention_symbols_exported_and_declared():
 
 @pytest.mark.parametrize("L,S,H,d,want", [(197, 197, 12, 64, 1), (257, 257, 16, 80, 1), (17, 17, 4, 16, 1),
                                           (50, 50, 12, 64, 1), (33, 65, 3, 32, 1), (197, 197, 1, 128, 1),
-                                          (17, 17, 4, 20, 0), (9, 9, 2, 136, 0), (9, 9, 2, 7, 0), (9, 9, 2, 256, 0)])
+                                          (17, 17, 4, 20, 0), (9, 9, 2, 136, 0), (9, 9, 2, 7, 0), (9, 9, 2, 256, 0),
+                                          (40, 45, 2, 48, 1), (40, 45, 2, 96, 1), (40, 45, 2, 112, 1), (40, 45, 2, 192, 0),
+                                          (40, 45, 2, 193, 0), (300, 300, 2, 64, 1)])
 def test_attention_path(L, S, H, d, want):
     assert capi.attention_path(L, S, H, d) == want
 
