@@ -33,6 +33,19 @@ constexpr int kWave = 64;          // CDNA wavefront
 constexpr int kNumCU = 256;        // MI355X
 constexpr int kNumXCD = 8;
 
+// One kernel instance: more than 64 KB of dynamic LDS needs the attribute, raised once per instance (to `lds_attr`; 0: the
+// instance stays inside the default limit), then the launch
+template <auto KERNEL, class Args>
+inline void launch_instance(unsigned blocks, unsigned threads, size_t lds, size_t lds_attr, hipStream_t s, const Args &a)
+{
+    if (lds_attr > 0) {
+        static const bool raised = hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                       (int)lds_attr) == hipSuccess;
+        (void)raised;
+    }
+    hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(threads), lds, s, a);
+}
+
 __host__ __device__ inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 

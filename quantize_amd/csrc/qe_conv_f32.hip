@@ -24,7 +24,7 @@
 // the image holds per halo pixel 3 splits x 2 k-halves x 8 bf16; a staging thread owns (k-half, halo row, 4 columns):
 // 8 coalesced 16-byte loads (one per channel), the splits and the channel-major -> pixel-major turn in registers,
 // 12 ds_write_b128.  Weight fragments (bf16, prepared once per call or kept by the caller) go L2 -> VGPR one tap ahead.
-#include "qe_common.h"
+#include "qe_conv_common.hpp"
 #include "qe_conv_plan.hpp"
 
 #include <algorithm>
@@ -649,9 +649,7 @@ static void f32_finish(F32Plan &p, const qe_conv_shape *sh, int MT, size_t wt_by
     p.tiles_h = (p.OH + p.TH - 1) / p.TH;
     p.n_pix_tiles = ((sh->N + p.GI - 1) / p.GI) * p.tiles_h;
     p.n_oc_tiles = p.OCP / MT;
-    p.chunk = (int)std::max<int64_t>(1, ((int64_t)p.n_pix_tiles + 7) / 8);
-    const int64_t runs = ((int64_t)p.n_pix_tiles + p.chunk - 1) / p.chunk;
-    p.blocks = (runs + 7) / 8 * p.chunk * 8 * p.n_oc_tiles;
+    p.blocks = tile_grid(p.n_pix_tiles, p.tiles_h, p.n_oc_tiles, false, p.chunk);   // QE_CHUNK_IMAGES is the packed convs' knob
     p.ok = true;
 }
 

@@ -24,7 +24,7 @@
 // The only bytes such slots could read past the tensor are those behind the LAST plane of the LAST image when the plane
 // size is not a multiple of 16: pure-garbage slots fetch the tensor's last 16 bytes instead, and the one slot that is
 // partly valid is left out of the DMA (lane masked off) and written by its thread from a register.
-#include "qe_conv_mfma_kernel.hpp"
+#include "qe_conv_common.hpp"
 #include "qe_conv_plan.hpp"
 
 #include <utility>
@@ -40,12 +40,7 @@ struct FlatdArgs {
     int N, IC, OC, P;
     int tiles_per_image;       // unused (a tile is 4 whole images)
     int n_pix_tiles, n_oc_tiles, chunk;
-    // fused re-quantisation (7x7 planes, RQ instances): the 8-bit code of the consumer's quantiser instead of fp32, fields as in MfmaArgs
-    uint8_t *rq_out;
-    const float *rq_scale, *rq_zero;
-    float rq_qmin, rq_qmax, rq_lo, rq_hi;
-    unsigned rq_offset;
-    int32_t *rq_status;
+    RqArgs rq;                 // fused re-quantisation (7x7 planes, RQ instances): the 8-bit code of the consumer's quantiser instead of fp32
 };
 
 constexpr int FD_RING_DEFAULT = 3;      // slots of the ring (RING - 1 stages in flight); 6 = one workgroup per CU with 5 in flight
@@ -326,7 +321,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_flatd_kernel(const FlatdAr
         // fp32 value is computed exactly as below, then quantised as quantize_pack would (rq_value / rq_fast2).
         uint8_t *bp = smem + wave * (32 * 49 * 4);
         const int oc0 = ot * FD_MT + wave * 32;
-        RqConst rqc = rq_setup(a);
+        RqConst rqc = rq_setup(a.rq);
         rqc.slow = __builtin_amdgcn_readfirstlane(rqc.slow);
         rqc.chk = __builtin_amdgcn_readfirstlane(rqc.chk);
         bool bad = false;
@@ -360,7 +355,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_flatd_kernel(const FlatdAr
                 }
             }
             if (img && oc0 + 32 <= a.OC) {
-                uint8_t *dst = a.rq_out + ((int64_t)(n0 + gi) * a.OC + oc0) * P;
+                uint8_t *dst = a.rq.out + ((int64_t)(n0 + gi) * a.OC + oc0) * P;
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
                     const uint4 d4 = *reinterpret_cast<const uint4 *>(bp + 16 * (64 * k + lane));
@@ -368,7 +363,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_flatd_kernel(const FlatdAr
                 }
             }
         }
-        rq_report(a, bad);
+        rq_report(a.rq, bad);
     } else {
         // a wave's 32 channels x P pixels of one image are ONE contiguous, 16-byte aligned run of the output
         // ((n OC + oc0) P floats, oc0 % 32 == 0, OC % 4 == 0): the patch is laid out exactly like it and copied flat.
@@ -405,20 +400,19 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_flatd_kernel(const FlatdAr
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
+template <int WV, bool RQ>
+static void launch_fd(const FlatdArgs &a, int64_t blocks, hipStream_t s)
+{
+    launch_instance<&conv_flatd_kernel<3, WV, RQ>>((unsigned)blocks, 64 * WV, FdGeom<3, WV>::LDS, FdGeom<3, WV>::LDS, s, a);
+}
+
 // p.route == Flatd: 8-wave workgroups when p.fd_w8; rq != nullptr: the re-quantising instances
 int launch_flatd(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, float *out, hipStream_t s,
                  const RequantHost *rq)
 {
     const qe_conv_shape *sh = &p.run;
     FlatdArgs a;
-    a.rq_out = nullptr; a.rq_scale = nullptr; a.rq_zero = nullptr; a.rq_status = nullptr;
-    a.rq_qmin = a.rq_qmax = a.rq_lo = a.rq_hi = 0.0f; a.rq_offset = 0;
-    if (rq != nullptr) {
-        a.rq_out = rq->out; a.rq_scale = rq->scale; a.rq_zero = rq->zero;
-        a.rq_qmin = rq->qmin; a.rq_qmax = rq->qmax; a.rq_status = rq->status;
-        a.rq_offset = rq->sign ? 128u : 0u;                       // tpack.cu:108-111
-        a.rq_lo = rq->sign ? -128.0f : 0.0f; a.rq_hi = rq->sign ? 127.0f : 255.0f;
-    }
+    a.rq = make_rq_args(rq);
     a.x = static_cast<const uint8_t *>(x->data); a.w = static_cast<const uint8_t *>(w->data);
     a.x_scale = x->scale; a.x_zero = x->zero; a.w_scale = w->scale; a.w_zero = w->zero; a.bias = bias;
     a.x_sign = x->sign; a.w_sign = w->sign; a.w_per_tensor = (w->n_param == 1);
@@ -430,20 +424,11 @@ int launch_flatd(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, cons
     const int64_t blocks = p.blocks;
     // ring depth 3 = two stages in flight, two workgroups per CU.  A 6-slot ring (one workgroup per CU, five stages in flight)
     // was 25-60 % slower on every layer (profiles/r02i_flatd_ring.txt): the K loop is not bound by prefetch depth.
-#define QE_FD_LAUNCH(WV, RQ)                                                                                                \
-    do {                                                                                                                    \
-        static const bool ok_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_flatd_kernel<3, WV, RQ>),          \
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, FdGeom<3, WV>::LDS) == hipSuccess; \
-        (void)ok_;                                                                                                          \
-        constexpr size_t lds_ = FdGeom<3, WV>::LDS;                                                                         \
-        hipLaunchKernelGGL((conv_flatd_kernel<3, WV, RQ>), dim3((unsigned)blocks), dim3(64 * WV), lds_, s, a);              \
-    } while (0)
     if (rq != nullptr) {
-        if (p.fd_w8) QE_FD_LAUNCH(8, true); else QE_FD_LAUNCH(4, true);
+        if (p.fd_w8) launch_fd<8, true>(a, blocks, s); else launch_fd<4, true>(a, blocks, s);
     } else {
-        if (p.fd_w8) QE_FD_LAUNCH(8, false); else QE_FD_LAUNCH(4, false);
+        if (p.fd_w8) launch_fd<8, false>(a, blocks, s); else launch_fd<4, false>(a, blocks, s);
     }
-#undef QE_FD_LAUNCH
     QE_LAUNCH_CHECK();
     return QE_OK;
 }

@@ -347,7 +347,7 @@ static PrepArgs prep_args(const MfmaPlan &p, const qe_qparam *w, const float *bi
 
 static void launch_prep(const MfmaPlan &p, const PrepArgs &pa, hipStream_t s)
 {
-    if (p.smallic)
+    if (p.family == MfmaFamily::Stem)
         hipLaunchKernelGGL(conv_mfma_prep_smallic_kernel, dim3(p.OCP), dim3(64), 0, s, pa, pa.KH, pa.KW);
     else
         hipLaunchKernelGGL(conv_mfma_prep_kernel, dim3(p.OCP), dim3(256), 0, s, pa);
@@ -365,6 +365,34 @@ int prepare_conv_tables(const MfmaPlan &p, const qe_qparam *w, const float *bias
     return QE_OK;
 }
 
+// The instance a plan selects: the one switch over the families.  Each family's unit names its instances (case by case,
+// null for a parameter combination it does not compile), so a plan value outside the instantiated set cannot run a
+// kernel compiled for another tile.
+MfmaLaunch mfma_instance(const MfmaPlan &m, int KW, int split, bool rq, bool patch)
+{
+    switch (m.family) {
+        case MfmaFamily::None: return nullptr;
+        case MfmaFamily::Halo: {
+            const int kkt = m.KK == 1 ? 1 : ((m.KK == 9 && KW == 3) ? 9 : 0);
+            switch (m.cfg) {
+                case 0: return mfma_halo_cfg0(m.niw, kkt, m.NS, rq, patch);
+                case 1: return mfma_halo_cfg1(m.niw, kkt, m.NS, rq, patch);
+                case 2: return mfma_halo_cfg2(m.niw, kkt, m.NS, rq, patch);
+            }
+            return nullptr;
+        }
+        case MfmaFamily::Ws: return (m.cfg == 0 && !patch) ? mfma_ws(m.niw, split, rq) : nullptr;
+        case MfmaFamily::Sm2: return m.cfg <= 1 ? mfma_sm2(m.cfg == 0 ? 2 : 1, split, rq, patch) : nullptr;
+        case MfmaFamily::Stem: return mfma_stem(m.cfg, m.niw, rq, patch);
+        // the flat kernels test rq.out themselves (one instance for both epilogues, no PATCH form)
+        case MfmaFamily::Flat: return patch ? nullptr : mfma_flat(m.cfg, m.niw, m.NS, m.wraw, false);
+        case MfmaFamily::FlatS2: return patch ? nullptr : mfma_flat(m.cfg, m.niw, m.NS, m.wraw, true);
+        case MfmaFamily::FlatX4: return (m.cfg == 0 && !m.wraw && !patch) ? mfma_flat_x4(m.niw, m.NS) : nullptr;
+        case MfmaFamily::Flatg: return (m.cfg == 0 && !patch) ? mfma_flatg(m.niw, m.NS, m.wraw) : nullptr;
+    }
+    return nullptr;
+}
+
 // use_prepared = false: workspace = [prepared part | scratch], the tables are rebuilt on every call; true: the tables are
 // in `prepared` (qe_conv_prepare) and the workspace holds the scratch only.  rq != nullptr: the plan's fused
 // re-quantisation (codes into rq->out instead of fp32 into `out`); res != nullptr: its fused residual block end.
@@ -373,8 +401,9 @@ int launch_conv_mfma(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, 
                      bool use_prepared, hipStream_t s, const RequantHost *rq, const float *res)
 {
     const MfmaPlan &m = p.m;
-    uint8_t *wsp = static_cast<uint8_t *>(workspace);       // base the plan's offsets are relative to
+    uint8_t *wsp = static_cast<uint8_t *>(workspace);
     uint8_t *tables = wsp;
+    size_t sub_off = m.sub_off, xe_off = m.xe_off;          // the plan's offsets count from [prepared part | scratch]
     if (!use_prepared) {
         if (m.total > 0) {
             if (workspace == nullptr || workspace_bytes < m.total) return QE_ERR_WORKSPACE;
@@ -389,7 +418,8 @@ int launch_conv_mfma(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, 
         if (m.total > m.prep_total) {
             if (workspace == nullptr || workspace_bytes < m.total - m.prep_total) return QE_ERR_WORKSPACE;
             if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return QE_ERR_ARG;
-            wsp = static_cast<uint8_t *>(workspace) - m.prep_total;   // scratch offsets start behind the prepared part
+            if (m.sub) sub_off -= m.prep_total;                 // the workspace holds the scratch only
+            if (m.expand) xe_off -= m.prep_total;
         }
     }
     const qe_conv_shape *rs = &p.run;
@@ -398,19 +428,19 @@ int launch_conv_mfma(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, 
     qe_qparam xr = *x;
     const uint8_t *xsrc = static_cast<const uint8_t *>(x->data);
     if (p.pre == PrePass::SubX4) {
-        hipLaunchKernelGGL(subsample_x4_kernel, dim3((unsigned)p.pre_blocks), dim3(256), 0, s, xsrc, wsp + m.sub_off,
+        hipLaunchKernelGGL(subsample_x4_kernel, dim3((unsigned)p.pre_blocks), dim3(256), 0, s, xsrc, wsp + sub_off,
                            (int64_t)sh->N * sh->IC * rs->H, (int)sh->H, (int)sh->W, (int)rs->H, (int)rs->W, (int)x->sign);
         QE_LAUNCH_CHECK();
     } else {
         if (m.expand) {
-            const int rc = expand_codes_s8(xsrc, (int64_t)sh->N * sh->IC * sh->H * sh->W, x->n_bits, x->sign, wsp + m.xe_off, s);
+            const int rc = expand_codes_s8(xsrc, (int64_t)sh->N * sh->IC * sh->H * sh->W, x->n_bits, x->sign, wsp + xe_off, s);
             if (rc != QE_OK) return rc;
-            xsrc = wsp + m.xe_off;
+            xsrc = wsp + xe_off;
             xr.data = xsrc;
         }
         const int64_t n_planes = (int64_t)sh->N * sh->IC;
         const dim3 grid((unsigned)p.pre_blocks);
-        uint8_t *dst = wsp + m.sub_off;
+        uint8_t *dst = wsp + sub_off;
 #define QE_SUB2(L) hipLaunchKernelGGL(subsample2_kernel<L>, grid, dim3(256), 0, s, xsrc, dst, n_planes, (int)sh->H, (int)sh->W, \
                                       (int)rs->H, (int)rs->W, p.sub2_log_nq)
         switch (p.pre) {
@@ -433,7 +463,7 @@ int launch_conv_mfma(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, 
 #undef QE_SUB2
         if (p.pre != PrePass::None) QE_LAUNCH_CHECK();
     }
-    if (m.sub) xr.data = wsp + m.sub_off;
+    if (m.sub) xr.data = wsp + sub_off;
     if (m.sub_x4 || m.expand) { xr.n_bits = 8; xr.sign = 1; }
 
     if (p.route == ConvRoute::Pwr || p.route == ConvRoute::Pwr7) return launch_pwr(p, &xr, w, bias, out, s, rq, res);
@@ -464,25 +494,11 @@ int launch_conv_mfma(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, 
     a.dbg = g_mfma_dbg;
     a.w_raw = w->data; a.w_scale = w->scale; a.w_zero = w->zero; a.x_scale = xr.scale; a.bias = bias;
     a.w_bits = w->n_bits; a.w_sign = w->sign; a.w_per_tensor = (w->n_param == 1);
-    a.rq_out = nullptr; a.rq_scale = nullptr; a.rq_zero = nullptr; a.rq_status = nullptr;
-    a.rq_qmin = a.rq_qmax = a.rq_lo = a.rq_hi = 0.0f; a.rq_offset = 0;
+    a.rq = make_rq_args(rq);
     a.rq_patch = p.rq_patch ? 1 : 0;
-    if (rq != nullptr) {
-        a.rq_out = rq->out; a.rq_scale = rq->scale; a.rq_zero = rq->zero;
-        a.rq_qmin = rq->qmin; a.rq_qmax = rq->qmax; a.rq_status = rq->status;
-        a.rq_offset = rq->sign ? 128u : 0u;                       // tpack.cu:108-111
-        a.rq_lo = rq->sign ? -128.0f : 0.0f; a.rq_hi = rq->sign ? 127.0f : 255.0f;
-    }
-    const unsigned blocks = (unsigned)p.blocks;
-    if (m.flatg) launch_mfma_flatg(a, m.NS, m.wraw, blocks, p.lds, s);
-    else if (m.flat && m.x4) launch_mfma_flat_x4(a, m.niw, m.NS, blocks, p.lds, s);
-    else if (m.flat) launch_mfma_flat(a, m.cfg, m.niw, m.NS, m.wraw, m.s2, blocks, p.lds, s);
-    else if (m.sm2) launch_mfma_sm2(a, m.cfg == 0 ? 2 : 1, p.split, blocks, p.lds, s);
-    else if (m.ws) launch_mfma_ws(a, m.niw, p.split, blocks, p.lds, s);
-    else if (m.smallic) launch_mfma_smallic(a, m.cfg, blocks, p.lds, s);
-    else if (m.cfg == 0) launch_mfma_cfg0(a, m.niw, m.NS, m.KK, blocks, p.lds, s);
-    else if (m.cfg == 1) launch_mfma_cfg1(a, m.niw, m.NS, m.KK, blocks, p.lds, s);
-    else launch_mfma_cfg2(a, m.niw, m.NS, m.KK, blocks, p.lds, s);
+    const MfmaLaunch launch = mfma_instance(m, rs->KW, p.split, rq != nullptr, p.rq_patch);
+    if (launch == nullptr) return QE_ERR_UNSUPPORTED;       // never for a plan of plan_conv
+    launch(a, (unsigned)p.blocks, p.lds, s);
     QE_LAUNCH_CHECK();
     return QE_OK;
 }

@@ -3,13 +3,14 @@
 
 namespace qe {
 
-void launch_mfma_cfg0(const MfmaArgs &a, int niw, int ns, int KK, unsigned blocks, size_t lds, hipStream_t s)
+MfmaLaunch mfma_halo_cfg0(int niw, int kkt, int ns, bool rq, bool patch)
 {
     switch (niw) {
-        case 7: QE_MFMA_LAUNCH(4, 1, 7); break;
-        case 4: QE_MFMA_LAUNCH(4, 1, 4); break;
-        default: QE_MFMA_LAUNCH(4, 1, 2); break;
+        case 7: return mfma_halo<4, 1, 7>(kkt, ns, rq, patch);
+        case 4: return mfma_halo<4, 1, 4>(kkt, ns, rq, patch);
+        case 2: return mfma_halo<4, 1, 2>(kkt, ns, rq, patch);
     }
+    return nullptr;
 }
 
 }  // namespace qe

@@ -3,13 +3,14 @@
 
 namespace qe {
 
-void launch_mfma_cfg1(const MfmaArgs &a, int niw, int ns, int KK, unsigned blocks, size_t lds, hipStream_t s)
+MfmaLaunch mfma_halo_cfg1(int niw, int kkt, int ns, bool rq, bool patch)
 {
     switch (niw) {
-        case 4: QE_MFMA_LAUNCH(2, 2, 4); break;
-        case 2: QE_MFMA_LAUNCH(2, 2, 2); break;
-        default: QE_MFMA_LAUNCH(2, 2, 1); break;
+        case 4: return mfma_halo<2, 2, 4>(kkt, ns, rq, patch);
+        case 2: return mfma_halo<2, 2, 2>(kkt, ns, rq, patch);
+        case 1: return mfma_halo<2, 2, 1>(kkt, ns, rq, patch);
     }
+    return nullptr;
 }
 
 }  // namespace qe

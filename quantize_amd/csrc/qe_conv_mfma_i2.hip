@@ -3,12 +3,13 @@
 
 namespace qe {
 
-void launch_mfma_cfg2(const MfmaArgs &a, int niw, int ns, int KK, unsigned blocks, size_t lds, hipStream_t s)
+MfmaLaunch mfma_halo_cfg2(int niw, int kkt, int ns, bool rq, bool patch)
 {
     switch (niw) {
-        case 2: QE_MFMA_LAUNCH(1, 4, 2); break;
-        default: QE_MFMA_LAUNCH(1, 4, 1); break;
+        case 2: return mfma_halo<1, 4, 2>(kkt, ns, rq, patch);
+        case 1: return mfma_halo<1, 4, 1>(kkt, ns, rq, patch);
     }
+    return nullptr;
 }
 
 }  // namespace qe

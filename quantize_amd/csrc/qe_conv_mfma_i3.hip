@@ -3,24 +3,24 @@
 
 namespace qe {
 
-#define QE_SMALLIC(WM, WN, NIW)                                                                                          \
-    do {                                                                                                                \
-        constexpr bool patch_ = mfma_has_patch(MfKind::Stem, WM, NIW, 0, 1);                                             \
-        if (a.rq_out != nullptr && a.rq_patch)                                                                          \
-            hipLaunchKernelGGL((conv_mfma_smallic_kernel<WM, WN, NIW, true, patch_>), dim3(blocks), dim3(MF_THREADS), lds, s, a);  \
-        else if (a.rq_out != nullptr)                                                                                   \
-            hipLaunchKernelGGL((conv_mfma_smallic_kernel<WM, WN, NIW, true>), dim3(blocks), dim3(MF_THREADS), lds, s, a);  \
-        else                                                                                                            \
-            hipLaunchKernelGGL((conv_mfma_smallic_kernel<WM, WN, NIW, false>), dim3(blocks), dim3(MF_THREADS), lds, s, a); \
-    } while (0)
+// PATCH form: the instances with 7 column tiles per wave
+template <int WM, int WN, int NIW>
+static MfmaLaunch stem_rq(bool rq, bool patch)
+{
+    if (!rq) return patch ? nullptr : &mfma_launch<&conv_mfma_smallic_kernel<WM, WN, NIW, false>>;
+    if (!patch) return &mfma_launch<&conv_mfma_smallic_kernel<WM, WN, NIW, true>>;
+    if constexpr (NIW == 7) return &mfma_launch<&conv_mfma_smallic_kernel<WM, WN, NIW, true, true>>;
+    return nullptr;
+}
 
-void launch_mfma_smallic(const MfmaArgs &a, int cfg, unsigned blocks, size_t lds, hipStream_t s)
+MfmaLaunch mfma_stem(int cfg, int niw, bool rq, bool patch)
 {
     switch (cfg) {
-        case 0: QE_SMALLIC(4, 1, 7); break;
-        case 1: QE_SMALLIC(2, 2, 7); break;   // 64 output channels, 448-pixel tiles (4 rows of the 112-wide stem output)
-        default: QE_SMALLIC(1, 4, 2); break;
+        case 0: return niw == 7 ? stem_rq<4, 1, 7>(rq, patch) : nullptr;
+        case 1: return niw == 7 ? stem_rq<2, 2, 7>(rq, patch) : nullptr;   // 64 output channels, 448-pixel tiles (4 rows of the 112-wide stem output)
+        case 2: return niw == 2 ? stem_rq<1, 4, 2>(rq, patch) : nullptr;
     }
+    return nullptr;
 }
 
 }  // namespace qe

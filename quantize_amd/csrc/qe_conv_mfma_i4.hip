@@ -3,36 +3,40 @@
 
 namespace qe {
 
-#define QE_FLAT(WM, WN, NIW, NS, WRAW) \
-    hipLaunchKernelGGL((conv_mfma_flat_kernel<WM, WN, NIW, NS, WRAW, false>), dim3(blocks), dim3(MF_THREADS), lds, s, a)
+template <int WM, int WN, int NIW, bool WRAW>
+static MfmaLaunch flat_ns(int ns)
+{
+    switch (ns) {
+        case 4: return &mfma_launch<&conv_mfma_flat_kernel<WM, WN, NIW, 4, WRAW, false>>;
+        case 2: return &mfma_launch<&conv_mfma_flat_kernel<WM, WN, NIW, 2, WRAW, false>>;
+        case 1: return &mfma_launch<&conv_mfma_flat_kernel<WM, WN, NIW, 1, WRAW, false>>;
+    }
+    return nullptr;
+}
+template <int WM, int WN, int NIW>
+static MfmaLaunch flat_w(int ns, bool wraw)
+{
+    return wraw ? flat_ns<WM, WN, NIW, true>(ns) : flat_ns<WM, WN, NIW, false>(ns);
+}
 
-#define QE_FLAT_NS(WM, WN, NIW)                                     \
-    do {                                                            \
-        if (wraw) {                                                 \
-            if (ns == 4) QE_FLAT(WM, WN, NIW, 4, true);             \
-            else if (ns == 2) QE_FLAT(WM, WN, NIW, 2, true);        \
-            else QE_FLAT(WM, WN, NIW, 1, true);                     \
-        } else {                                                    \
-            if (ns == 4) QE_FLAT(WM, WN, NIW, 4, false);            \
-            else if (ns == 2) QE_FLAT(WM, WN, NIW, 2, false);       \
-            else QE_FLAT(WM, WN, NIW, 1, false);                    \
-        }                                                           \
-    } while (0)
-
-void launch_mfma_flat(const MfmaArgs &a, int cfg, int niw, int ns, bool wraw, bool s2, unsigned blocks, size_t lds, hipStream_t s)
+MfmaLaunch mfma_flat(int cfg, int niw, int ns, bool wraw, bool s2)
 {
     if (s2) {   // stride-2 1x1: 224-pixel tiles, 64-channel stages, 128-channel workgroups only
-        if (wraw) hipLaunchKernelGGL((conv_mfma_flat_kernel<4, 1, 7, 2, true, true>), dim3(blocks), dim3(MF_THREADS), lds, s, a);
-        else      hipLaunchKernelGGL((conv_mfma_flat_kernel<4, 1, 7, 2, false, true>), dim3(blocks), dim3(MF_THREADS), lds, s, a);
-        return;
+        if (cfg != 0 || niw != 7 || ns != 2) return nullptr;
+        return wraw ? &mfma_launch<&conv_mfma_flat_kernel<4, 1, 7, 2, true, true>> : &mfma_launch<&conv_mfma_flat_kernel<4, 1, 7, 2, false, true>>;
     }
     switch (cfg) {
         case 0:
-            if (niw == 4) QE_FLAT_NS(4, 1, 4); else if (niw == 5) QE_FLAT_NS(4, 1, 5); else QE_FLAT_NS(4, 1, 7);
-            break;
-        case 1: QE_FLAT_NS(2, 2, 4); break;
-        default: QE_FLAT_NS(1, 4, 2); break;
+            switch (niw) {
+                case 4: return flat_w<4, 1, 4>(ns, wraw);
+                case 5: return flat_w<4, 1, 5>(ns, wraw);
+                case 7: return flat_w<4, 1, 7>(ns, wraw);
+            }
+            return nullptr;
+        case 1: return niw == 4 ? flat_w<2, 2, 4>(ns, wraw) : nullptr;
+        case 2: return niw == 2 ? flat_w<1, 4, 2>(ns, wraw) : nullptr;
     }
+    return nullptr;
 }
 
 }  // namespace qe

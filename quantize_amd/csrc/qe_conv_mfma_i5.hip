@@ -3,20 +3,31 @@
 
 namespace qe {
 
-#define QE_WS_K(NIW, SPLIT, RQ) \
-    hipLaunchKernelGGL((conv_mfma_ws_kernel<NIW, 9, SPLIT, RQ>), dim3(blocks), dim3(2 * MF_THREADS), lds, s, a)
-#define QE_WS(NIW, SPLIT) \
-    do { if (a.rq_out != nullptr) QE_WS_K(NIW, SPLIT, true); else QE_WS_K(NIW, SPLIT, false); } while (0)
-#define QE_WS_SPLIT(NIW) \
-    do { if (split == 4) QE_WS(NIW, 4); else if (split == 2) QE_WS(NIW, 2); else QE_WS(NIW, 1); } while (0)
+template <int NIW, int SPLIT>
+static MfmaLaunch ws_rq(bool rq)
+{
+    return rq ? &mfma_launch<&conv_mfma_ws_kernel<NIW, 9, SPLIT, true>, 2 * MF_THREADS>
+              : &mfma_launch<&conv_mfma_ws_kernel<NIW, 9, SPLIT, false>, 2 * MF_THREADS>;
+}
+template <int NIW>
+static MfmaLaunch ws_split(int split, bool rq)
+{
+    switch (split) {
+        case 4: return ws_rq<NIW, 4>(rq);
+        case 2: return ws_rq<NIW, 2>(rq);
+        case 1: return ws_rq<NIW, 1>(rq);
+    }
+    return nullptr;
+}
 
-void launch_mfma_ws(const MfmaArgs &a, int niw, int split, unsigned blocks, size_t lds, hipStream_t s)
+MfmaLaunch mfma_ws(int niw, int split, bool rq)
 {
     switch (niw) {
-        case 7: QE_WS_SPLIT(7); break;
-        case 4: QE_WS_SPLIT(4); break;
-        default: QE_WS_SPLIT(2); break;
+        case 7: return ws_split<7>(split, rq);
+        case 4: return ws_split<4>(split, rq);
+        case 2: return ws_split<2>(split, rq);
     }
+    return nullptr;
 }
 
 }  // namespace qe

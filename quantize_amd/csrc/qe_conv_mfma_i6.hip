@@ -3,34 +3,32 @@
 
 namespace qe {
 
-template <int WMS, int SPLIT, bool RQ, bool PATCH = false>
-static void launch_rq(const MfmaArgs &a, unsigned blocks, size_t lds, hipStream_t s)
-{
-    // more than 64 KB of dynamic LDS needs the attribute once per kernel
-    static const bool raised = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_mfma_sm2_kernel<WMS, 9, SPLIT, RQ, PATCH>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, MF_MAX_LDS_SM2) == hipSuccess;
-    (void)raised;
-    hipLaunchKernelGGL((conv_mfma_sm2_kernel<WMS, 9, SPLIT, RQ, PATCH>), dim3(blocks), dim3(MF_THREADS), lds, s, a);
-}
+// every re-quantising instance has its PATCH form; up to 80 KB of dynamic LDS
 template <int WMS, int SPLIT>
-static void launch_one(const MfmaArgs &a, unsigned blocks, size_t lds, hipStream_t s)
+static MfmaLaunch sm2_rq(bool rq, bool patch)
 {
-    if (a.rq_out != nullptr && a.rq_patch) launch_rq<WMS, SPLIT, true, mfma_has_patch(MfKind::Sm2, 2 * WMS, 4, 9, 1)>(a, blocks, lds, s);
-    else if (a.rq_out != nullptr) launch_rq<WMS, SPLIT, true>(a, blocks, lds, s);
-    else launch_rq<WMS, SPLIT, false>(a, blocks, lds, s);
+    if (!rq) return patch ? nullptr : &mfma_launch<&conv_mfma_sm2_kernel<WMS, 9, SPLIT, false, false>, MF_THREADS, MF_MAX_LDS_SM2>;
+    if (!patch) return &mfma_launch<&conv_mfma_sm2_kernel<WMS, 9, SPLIT, true, false>, MF_THREADS, MF_MAX_LDS_SM2>;
+    return &mfma_launch<&conv_mfma_sm2_kernel<WMS, 9, SPLIT, true, true>, MF_THREADS, MF_MAX_LDS_SM2>;
+}
+template <int WMS>
+static MfmaLaunch sm2_split(int split, bool rq, bool patch)
+{
+    switch (split) {
+        case 4: return sm2_rq<WMS, 4>(rq, patch);
+        case 2: return sm2_rq<WMS, 2>(rq, patch);
+        case 1: return sm2_rq<WMS, 1>(rq, patch);
+    }
+    return nullptr;
 }
 
-void launch_mfma_sm2(const MfmaArgs &a, int wms, int split, unsigned blocks, size_t lds, hipStream_t s)
+MfmaLaunch mfma_sm2(int wms, int split, bool rq, bool patch)
 {
-    if (wms == 2) {
-        if (split == 4) launch_one<2, 4>(a, blocks, lds, s);
-        else if (split == 2) launch_one<2, 2>(a, blocks, lds, s);
-        else launch_one<2, 1>(a, blocks, lds, s);
-    } else {
-        if (split == 4) launch_one<1, 4>(a, blocks, lds, s);
-        else if (split == 2) launch_one<1, 2>(a, blocks, lds, s);
-        else launch_one<1, 1>(a, blocks, lds, s);
+    switch (wms) {
+        case 2: return sm2_split<2>(split, rq, patch);
+        case 1: return sm2_split<1>(split, rq, patch);
     }
+    return nullptr;
 }
 
 }  // namespace qe

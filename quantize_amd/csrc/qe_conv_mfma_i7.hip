@@ -3,15 +3,20 @@
 
 namespace qe {
 
-void launch_mfma_flatg(const MfmaArgs &a, int ns, bool wraw, unsigned blocks, size_t lds, hipStream_t s)
+template <int NS>
+static MfmaLaunch flatg_w(bool wraw)   // 49-pixel planes
 {
-#define QE_FG(NS, WRAW) hipLaunchKernelGGL((conv_mfma_flatg_kernel<7, NS, WRAW, 7>), dim3(blocks), dim3(MF_THREADS), lds, s, a)   // 49-pixel planes
-    if (wraw) {
-        if (ns == 4) QE_FG(4, true); else QE_FG(2, true);
-    } else {
-        if (ns == 4) QE_FG(4, false); else QE_FG(2, false);
+    return wraw ? &mfma_launch<&conv_mfma_flatg_kernel<7, NS, true, 7>> : &mfma_launch<&conv_mfma_flatg_kernel<7, NS, false, 7>>;
+}
+
+MfmaLaunch mfma_flatg(int niw, int ns, bool wraw)
+{
+    if (niw != 7) return nullptr;
+    switch (ns) {
+        case 4: return flatg_w<4>(wraw);
+        case 2: return flatg_w<2>(wraw);
     }
-#undef QE_FG
+    return nullptr;
 }
 
 }  // namespace qe

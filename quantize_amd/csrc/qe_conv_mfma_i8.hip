@@ -4,14 +4,25 @@
 
 namespace qe {
 
-#define QE_FLAT4(NIW, NS) \
-    hipLaunchKernelGGL((conv_mfma_flat_kernel<4, 1, NIW, NS, false, false, true>), dim3(blocks), dim3(MF_THREADS), lds, s, a)
-#define QE_FLAT4_NS(NIW) \
-    do { if (ns == 4) QE_FLAT4(NIW, 4); else if (ns == 2) QE_FLAT4(NIW, 2); else QE_FLAT4(NIW, 1); } while (0)
-
-void launch_mfma_flat_x4(const MfmaArgs &a, int niw, int ns, unsigned blocks, size_t lds, hipStream_t s)
+template <int NIW>
+static MfmaLaunch flat4_ns(int ns)
 {
-    if (niw == 4) QE_FLAT4_NS(4); else if (niw == 5) QE_FLAT4_NS(5); else QE_FLAT4_NS(7);
+    switch (ns) {
+        case 4: return &mfma_launch<&conv_mfma_flat_kernel<4, 1, NIW, 4, false, false, true>>;
+        case 2: return &mfma_launch<&conv_mfma_flat_kernel<4, 1, NIW, 2, false, false, true>>;
+        case 1: return &mfma_launch<&conv_mfma_flat_kernel<4, 1, NIW, 1, false, false, true>>;
+    }
+    return nullptr;
+}
+
+MfmaLaunch mfma_flat_x4(int niw, int ns)
+{
+    switch (niw) {
+        case 4: return flat4_ns<4>(ns);
+        case 5: return flat4_ns<5>(ns);
+        case 7: return flat4_ns<7>(ns);
+    }
+    return nullptr;
 }
 
 }  // namespace qe

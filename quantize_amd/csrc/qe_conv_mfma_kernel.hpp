@@ -3,20 +3,11 @@
 // unconditional (clamped address + mask) because hipcc waits vmcnt(0) after every load it has to
 // branch around, which serialises the whole activation fetch into one HBM round trip per dword.
 #pragma once
-#include "qe_common.h"
+#include "qe_conv_common.hpp"
 
 #include <type_traits>
 
 namespace qe {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
-
-constexpr int MF_THREADS = 256;
-constexpr int MF_UNITS = 2;        // staging units (16 ch x 4 px) per thread per chunk
-constexpr int MF_TRASH = 64;       // per-lane LDS slots that swallow masked-off staging writes
-constexpr int MF_MAX_LDS = 64 * 1024;
-constexpr int MF_MAX_LDS_SM2 = 80 * 1024;   // sm2 kernel: 2 workgroups per CU x 80 KB = the CU's 160 KB
 
 struct MfmaArgs {
     const uint8_t *x;
@@ -42,125 +33,10 @@ struct MfmaArgs {
     const uint8_t *w_raw;      // packed OIHW weights as the caller passed them
     const float *w_scale, *w_zero, *x_scale, *bias;
     int w_bits, w_sign, w_per_tensor;
-    // fused re-quantisation of the output (qe_quantconv2d_requant): rq_out != nullptr -> the epilogue stores the 8-bit
-    // code of round(y / scale - zero).clamp(qmin, qmax) (1 byte per element, NCHW) instead of the fp32 y into `out`
-    uint8_t *rq_out;
-    const float *rq_scale, *rq_zero;   // per tensor (the consumer's activation quantiser; its conv wants one scale anyway)
-    float rq_qmin, rq_qmax, rq_lo, rq_hi;   // clamp of the quantiser; representable range of the code (tpack's range test)
-    unsigned rq_offset;                     // stored code = (q + offset) & 0xff (tpack.cu:108-111)
-    int32_t *rq_status;                     // bit 0 set when a value fails the range test (NaN, or qmin/qmax outside the code range)
+    RqArgs rq;                 // fused re-quantisation of the output: rq.out != nullptr -> codes into rq.out instead of fp32 into `out`
     int rq_patch;                           // lane = pixel kernels (halo, sm2, stem), one image per tile: the tile's codes go through a
                                             // workgroup byte patch [MT][32 NIW WN] at the start of the dynamic LDS and leave as 16-byte row pieces
 };
-
-// y -> stored 8-bit code with the arithmetic of the fused quantise+pack kernel (qe_tpack.hip tp_quantize + tp_code):
-//   r = rint(y / scale - zero) ; clamp to [qmin, qmax] ; code = (int(r) + offset) & 0xff ; flag when r is NaN or outside the
-// code range.  An IEEE division per output element (~10 VALU instructions) made the fused epilogue SLOWER than storing fp32
-// (4.84 vs 4.17 ms per step), so the quotient comes from Markstein's sequence on a reciprocal taken once per thread:
-//   q0 = y * rcp ; e = fma(-scale, q0, y) ; q = fma(e, rcp, q0)
-// which IS the correctly rounded y / scale whenever rcp = RN(1 / scale), the significand of scale is not all ones and
-// nothing over- or underflows (Markstein 1990; Cornea et al., "Scientific computing on Itanium", thm. 8.3).  y is first
-// clamped to +-B with B / |scale| beyond the clamp bounds, which changes no code and keeps infinities out of the fma;
-// tiny quotients (where the sequence could round differently) cannot reach a rounding boundary of q - zero.  Scales
-// outside those conditions take the division (`slow`, uniform).  When the status flag comes back set the codes are
-// unspecified (the reference raises "out of range" there).
-struct RqConst {
-    float sc, rcp, nsc, zr, qmin, qmax, offf, B, lo, hi;
-    bool slow, chk;
-};
-template <class Args>                                      // MfmaArgs, PwrArgs: the same rq_* fields
-__device__ __forceinline__ RqConst rq_setup(const Args &a)
-{
-    RqConst c;
-    c.sc = a.rq_scale[0];
-    c.zr = a.rq_zero[0];
-    c.rcp = 1.0f / c.sc;
-    c.nsc = -c.sc;
-    c.qmin = a.rq_qmin; c.qmax = a.rq_qmax; c.lo = a.rq_lo; c.hi = a.rq_hi;
-    c.offf = (float)a.rq_offset;
-    const float asc = fabsf(c.sc);
-    const float span = fmaxf(fabsf(c.qmin), fabsf(c.qmax)) + fabsf(c.zr) + 2.0f;
-    c.B = asc * span * 2.0f;
-    c.slow = !(asc >= 0x1p-60f && asc <= 0x1p60f) || (__float_as_uint(c.sc) & 0x7fffffu) == 0x7fffffu || !(span <= 0x1p30f) ||
-             !(c.qmin <= c.qmax);
-    c.chk = !(c.qmin >= c.lo && c.qmax <= c.hi);          // clamp bounds inside the code range: only NaN can fail the range test
-    return c;
-}
-// returns r + offset as a float (0 .. 255 whenever the range test passes)
-__device__ __forceinline__ float rq_value(const RqConst &c, float v, bool &bad)
-{
-    float r;
-    if (c.slow) {
-        r = rintf(v / c.sc - c.zr);
-        r = (r != r) ? r : fminf(fmaxf(r, c.qmin), c.qmax);
-        bad |= !(r >= c.lo && r <= c.hi);
-    } else {
-        bad |= (v != v);
-        const float vc = __builtin_amdgcn_fmed3f(v, -c.B, c.B);
-        const float q0 = vc * c.rcp;
-        const float e = fmaf(c.nsc, q0, vc);
-        const float q = fmaf(e, c.rcp, q0);
-        r = __builtin_amdgcn_fmed3f(rintf(q - c.zr), c.qmin, c.qmax);
-        if (c.chk) bad |= !(r >= c.lo && r <= c.hi);
-    }
-    return r + c.offf;
-}
-// Two values per instruction where the ISA has packed fp32 (v_pk_mul_f32, v_pk_fma_f32, v_pk_add_f32: 7.5 instead of 13 VALU
-// instructions per output element; the fused epilogue is VALU-bound: 2.8 G elements per batch-256 ResNet-50 step).  Valid
-// when rq_fast_ok(c) and the caller has bounded its own constants so that y is finite and |y| <= 2^52 (rq_bounded): then
-// no NaN and no overflow can occur anywhere in the sequence, the +-B clamp of rq_value is the identity wherever it matters
-// (beyond B the code is the clamp bound either way) and no range flag can be raised -- the same codes as rq_value.
-typedef float v2f __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ bool rq_fast_ok(const RqConst &c) { return !c.slow && !c.chk; }
-// |alpha| <= 2^10, |cst| <= 2^40, |bias| <= 2^50, |zw'| <= 2^20: y = fma(alpha, acc + cst - zw' S_x, bias) stays below 2^52
-__device__ __forceinline__ bool rq_bounded(float alpha, float cst, float bias, float zwp)
-{
-    return fabsf(alpha) <= 0x1p10f && fabsf(cst) <= 0x1p40f && fabsf(bias) <= 0x1p50f && fabsf(zwp) <= 0x1p20f;
-}
-__device__ __forceinline__ v2f rq_fast2(const RqConst &c, v2f y)
-{
-#pragma clang fp contract(off)
-    const v2f rcp = {c.rcp, c.rcp}, nsc = {c.nsc, c.nsc}, zr = {c.zr, c.zr}, off = {c.offf, c.offf};
-    const v2f q0 = y * rcp;
-    const v2f e = __builtin_elementwise_fma(nsc, q0, y);
-    const v2f q = __builtin_elementwise_fma(e, rcp, q0);
-    const v2f d = q - zr;
-    v2f r;
-    r.x = __builtin_amdgcn_fmed3f(rintf(d.x), c.qmin, c.qmax);
-    r.y = __builtin_amdgcn_fmed3f(rintf(d.y), c.qmin, c.qmax);
-    return r + off;
-}
-template <class Args>
-__device__ __forceinline__ void rq_report(const Args &a, bool bad)
-{
-    if (__builtin_amdgcn_ballot_w64(bad) != 0 && (threadIdx.x & 63) == 0 && a.rq_status != nullptr) atomicOr(a.rq_status, 1);
-}
-
-// stored code u -> MFMA operand a = q - d = u - c, c = off (signed) | 128 (unsigned 8-bit) | 0
-__host__ __device__ __forceinline__ int code_bias(int n_bits, int sign)
-{
-    return sign ? (1 << (n_bits - 1)) : (n_bits == 8 ? 128 : 0);
-}
-// d: what was subtracted from q on top of the sign offset (added back through the zero point)
-__host__ __device__ __forceinline__ float zero_shift(int n_bits, int sign)
-{
-    return (!sign && n_bits == 8) ? 128.0f : 0.0f;
-}
-
-#ifdef QE_STAMP
-// In-kernel stamps (guide section 7): one asm statement, fenced, lgkmcnt(0) inside.  Diagnostic build only.
-__device__ __forceinline__ unsigned long long qe_stamp()
-{
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define QE_ST(i) do { const unsigned long long _t = qe_stamp(); st[i] += _t - tprev; tprev = _t; } while (0)
-#else
-#define QE_ST(i) do { } while (0)
-#endif
 
 // 4x4 byte transpose: in d0..d3 (one channel each, 4 pixels), out o0..o3 (one pixel each, 4 channels)
 __device__ __forceinline__ void transpose4x4(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t d3,
@@ -212,10 +88,10 @@ __device__ __forceinline__ void mfma_epilogue_impl(const MfmaArgs &a, v16i (&acc
     const int64_t out_base = ((int64_t)g.n0 * a.OC + ot * MT + wm * 32) * OHW + (int64_t)g.oh0 * a.OW;
     float *out_w = a.out + (RQ ? 0 : out_base);
     // RQ: one byte per element (lanes 0-31 = 32 consecutive bytes of row dr, lanes 32-63 of row dr + 4)
-    uint8_t *out_q = RQ ? a.rq_out + out_base : nullptr;
+    uint8_t *out_q = RQ ? a.rq.out + out_base : nullptr;
     bool bad = false;
     RqConst rqc;
-    if constexpr (RQ) rqc = rq_setup(a);   // per tensor: wave-uniform constants, no registers per row
+    if constexpr (RQ) rqc = rq_setup(a.rq);   // per tensor: wave-uniform constants, no registers per row
     // per-lane element offset of column q: image gi of the tile, pixel rq inside it, rows 4h apart
     uint32_t voff[NIW];
     bool valid[NIW];
@@ -356,7 +232,7 @@ __device__ __forceinline__ void mfma_epilogue_impl(const MfmaArgs &a, v16i (&acc
                     }
                 }
                 }
-            if constexpr (RQ) rq_report(a, bad);
+            if constexpr (RQ) rq_report(a.rq, bad);
             return;
         }
         float zw[16];
@@ -404,7 +280,7 @@ __device__ __forceinline__ void mfma_epilogue_impl(const MfmaArgs &a, v16i (&acc
             }
         }
     }
-    if constexpr (RQ) rq_report(a, bad);
+    if constexpr (RQ) rq_report(a.rq, bad);
 }
 
 // The patch of the PATCH form -> global memory: [MT][PSTR] codes, row = output channel ot MT + row, slot = pixel of the tile
@@ -423,7 +299,7 @@ __device__ __forceinline__ void rq_patch_copy_out(const MfmaArgs &a, const TileG
         const int oc = ot * MT + row;
         if (oc < a.OC && px < NT) {
             const uint4 d4 = *reinterpret_cast<const uint4 *>(qe_ep_smem + row * PSTR + px);
-            uint8_t *dst = a.rq_out + ((int64_t)g.n0 * a.OC + oc) * OHW + (int64_t)g.oh0 * a.OW + px;
+            uint8_t *dst = a.rq.out + ((int64_t)g.n0 * a.OC + oc) * OHW + (int64_t)g.oh0 * a.OW + px;
             if (px + 16 <= NT) {
                 __builtin_memcpy(dst, &d4, 16);
             } else {                                                       // NT % 4 == 0: whole dwords
@@ -497,15 +373,10 @@ __device__ __forceinline__ const float *stage_ctab(const MfmaArgs &a, uint8_t *s
     return t;
 }
 
-// tile decode shared by both kernels.  XCD-aware block map: blocks b and b+8 share an XCD (and its
-// L2); the oc-tiles of one pixel tile get ids that differ by multiples of 8 so they read the same
-// activations from one L2.
+// tile decode shared by the kernels: the device half of the XCD-aware block map (tile_grid, qe_conv_common.hpp, is the
+// host half and explains the map; the two must agree)
 __device__ __forceinline__ void block_to_tile(const MfmaArgs &a, int &pt, int &ot)
 {
-    // XCD x = bid & 7 takes runs of `chunk` consecutive pixel tiles (all their oc tiles), run r of the XCD
-    // being global run 8*r + x.  chunk = 1 interleaves neighbouring tiles over the XCDs; a chunk of one or
-    // more whole images keeps the lines an L2 has in flight contiguous in memory, which the write-bound
-    // layers need (tools/probe_store_pattern2.hip: 4.2 -> 4.9 TB/s store-only at 28x28, 5.5 -> 5.8 at 56x56).
     const int bid = blockIdx.x;
     const int idx = bid >> 3;
     const int j = idx / a.n_oc_tiles;
@@ -1501,7 +1372,6 @@ __global__ __launch_bounds__(MF_THREADS, 2) void conv_mfma_smallic_kernel(const 
 // Template: WM x WN waves (oc strips x pixel tiles), NIW pixel tiles per wave, NS 32-channel chunks
 // per stage, WRAW = weights read from the packed tensor (else from the prep'd Wt).
 // ---------------------------------------------------------------------------------------------
-typedef int v2i __attribute__((ext_vector_type(2)));
 
 // X4: 4-bit activations consumed straight from the packed stream (a piece = 16 pixels = 8 bytes, nibbles spread to bytes
 // in the staging registers) instead of being expanded to 8-bit codes by a pass of their own first.
@@ -1767,12 +1637,12 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_mfma_flat_kernel(const M
     // stores of full lines).  Each wave therefore turns its 32 oc x 32 px tile through a private LDS
     // patch (row stride 36 floats: conflict-free b128 writes) and reads it back with 8 lanes per
     // channel row: one global_store_dwordx4 then writes 8 rows x 128 contiguous bytes.
-    if (a.rq_out != nullptr) {
+    if (a.rq.out != nullptr) {
         // Fused re-quantisation: 8-bit codes instead of fp32.  The workgroup's MT x NTP tile of codes goes through ONE byte
         // patch in LDS (behind the staging image and the channel sums: a.ptab_off), then every thread stores 16-byte
         // pieces of rows: NTP contiguous bytes per output channel instead of 4 x NTP.
         uint8_t *bp = smem + a.ptab_off;                                       // [MT][NTP]
-        RqConst rqc = rq_setup(a);
+        RqConst rqc = rq_setup(a.rq);
         rqc.slow = __builtin_amdgcn_readfirstlane(rqc.slow);                   // the same in every lane: a branch, not a select
         rqc.chk = __builtin_amdgcn_readfirstlane(rqc.chk);
         bool bad = false;
@@ -1822,7 +1692,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_mfma_flat_kernel(const M
             const int oc_r = ot * MT + row;
             if (oc_r < a.OC && px < NT) {
                 const uint4 d4 = *reinterpret_cast<const uint4 *>(bp + row * NTP + px);
-                uint8_t *dst = a.rq_out + ((int64_t)n * a.OC + oc_r) * P + p0 + px;
+                uint8_t *dst = a.rq.out + ((int64_t)n * a.OC + oc_r) * P + p0 + px;
                 if (px + 16 <= NT) {
                     __builtin_memcpy(dst, &d4, 16);                            // dword aligned (P % 4 == 0)
                 } else {                                                       // NT % 4 == 0: whole dwords
@@ -1833,7 +1703,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_mfma_flat_kernel(const M
                 }
             }
         }
-        rq_report(a, bad);
+        rq_report(a.rq, bad);
         return;
     }
     float *out_w = a.out + ((int64_t)n * a.OC + ot * MT + wm * 32) * P + p0;   // wave-uniform
@@ -2056,12 +1926,12 @@ __global__ __launch_bounds__(MF_THREADS, 2) void conv_mfma_flatg_kernel(const Mf
     // ---- epilogue: lane = output channel, 4 consecutive registers = 4 consecutive slots; per-wave LDS patch ----
     const int sw_sum = swacc + __shfl_xor(swacc, 32);
     const float cst = fmaf((float)a.IC * zxp, zwp, -zxp * (float)sw_sum);
-    if (a.rq_out != nullptr) {
+    if (a.rq.out != nullptr) {
         // Fused re-quantisation (see conv_mfma_flat_kernel).  Byte patch in OUTPUT order [image gi][oc row][P]: the MT planes
         // of one image are one contiguous run of MT * P bytes of the output tensor, stored as 16-byte pieces at byte alignment
         // (49-byte planes; unaligned global_store_dwordx4: tools/probe_unaligned.hip).
         uint8_t *bp = smem + a.ptab_off;
-        const RqConst rqc = rq_setup(a);
+        const RqConst rqc = rq_setup(a.rq);
         bool bad = false;
 #pragma unroll
         for (int t = 0; t < NIW; ++t) {
@@ -2088,7 +1958,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void conv_mfma_flatg_kernel(const Mf
             const int gi = e / ppi, b = 16 * (e - gi * ppi);
             if (n0 + gi >= a.N) continue;
             const uint8_t *src = bp + gi * MT * P + b;
-            uint8_t *dst = a.rq_out + ((int64_t)(n0 + gi) * a.OC + ot * MT) * P + b;
+            uint8_t *dst = a.rq.out + ((int64_t)(n0 + gi) * a.OC + ot * MT) * P + b;
             if (b + 16 <= run) {
                 const uint4 d4 = *reinterpret_cast<const uint4 *>(src);   // LDS side is 16-byte aligned (MT * P % 16 == 0)
                 __builtin_memcpy(dst, &d4, 16);
@@ -2096,7 +1966,7 @@ __global__ __launch_bounds__(MF_THREADS, 2) void conv_mfma_flatg_kernel(const Mf
                 for (int k = 0; b + k < run; ++k) dst[k] = src[k];
             }
         }
-        rq_report(a, bad);
+        rq_report(a.rq, bad);
         return;
     }
     float *patch = reinterpret_cast<float *>(smem) + wave * (32 * 36);
@@ -2141,49 +2011,54 @@ __global__ __launch_bounds__(MF_THREADS, 2) void conv_mfma_flatg_kernel(const Mf
     }
 }
 
-// Which re-quantising lane = pixel kernels have a PATCH instance (codes through the workgroup's LDS byte patch): the halo
-// kernel <WM 4, NIW 7, KK 9, NS 1>, the stem kernels with NIW 7 and every sm2 kernel.  The planner sets rq_patch only
-// where this holds; the launchers instantiate PATCH from it.
-enum class MfKind { Halo, Stem, Sm2 };
-constexpr bool mfma_has_patch(MfKind k, int wm, int niw, int kkt, int ns)
+// ---- instances ----------------------------------------------------------------------------------------------------
+// Each family's translation unit (qe_conv_mfma_i*.hip, one per family or wave layout) answers with the launch function
+// of the instance its parameters name, or null when that instance is not compiled.  mfma_instance (qe_conv_mfma.hip) is the
+// one switch over them.  rq: the re-quantising instance; patch: its PATCH form
+// (codes through the workgroup's LDS byte patch), which only some lane = pixel instances have -- what each selector
+// instantiates is the whole rule, the planner asks and the launcher calls the same answer.
+MfmaLaunch mfma_halo_cfg0(int niw, int kkt, int ns, bool rq, bool patch);   // kkt: 1 | 9 (3x3) | 0 (any other kernel size)
+MfmaLaunch mfma_halo_cfg1(int niw, int kkt, int ns, bool rq, bool patch);
+MfmaLaunch mfma_halo_cfg2(int niw, int kkt, int ns, bool rq, bool patch);
+MfmaLaunch mfma_stem(int cfg, int niw, bool rq, bool patch);
+MfmaLaunch mfma_ws(int niw, int split, bool rq);
+MfmaLaunch mfma_sm2(int wms, int split, bool rq, bool patch);
+MfmaLaunch mfma_flatg(int niw, int ns, bool wraw);
+MfmaLaunch mfma_flat(int cfg, int niw, int ns, bool wraw, bool s2);
+MfmaLaunch mfma_flat_x4(int niw, int ns);
+
+// LDS_ATTR > 0: the instance may ask for more than 64 KB of dynamic LDS
+template <auto KERNEL, int THREADS = MF_THREADS, int LDS_ATTR = 0>
+void mfma_launch(const MfmaArgs &a, unsigned blocks, size_t lds, hipStream_t s)
 {
-    return k == MfKind::Sm2 || (k == MfKind::Stem && niw == 7) || (k == MfKind::Halo && wm == 4 && niw == 7 && kkt == 9 && ns == 1);
+    launch_instance<KERNEL>(blocks, THREADS, lds, LDS_ATTR, s, a);
 }
 
-// launchers, one translation unit per wave layout (qe_conv_mfma_i*.hip)
-void launch_mfma_cfg0(const MfmaArgs &a, int niw, int ns, int KK, unsigned blocks, size_t lds, hipStream_t s);
-void launch_mfma_cfg1(const MfmaArgs &a, int niw, int ns, int KK, unsigned blocks, size_t lds, hipStream_t s);
-void launch_mfma_cfg2(const MfmaArgs &a, int niw, int ns, int KK, unsigned blocks, size_t lds, hipStream_t s);
-void launch_mfma_smallic(const MfmaArgs &a, int cfg, unsigned blocks, size_t lds, hipStream_t s);
-void launch_mfma_ws(const MfmaArgs &a, int niw, int split, unsigned blocks, size_t lds, hipStream_t s);
-void launch_mfma_sm2(const MfmaArgs &a, int wms, int split, unsigned blocks, size_t lds, hipStream_t s);
-void launch_mfma_flatg(const MfmaArgs &a, int ns, bool wraw, unsigned blocks, size_t lds, hipStream_t s);
-void launch_mfma_flat(const MfmaArgs &a, int cfg, int niw, int ns, bool wraw, bool s2, unsigned blocks, size_t lds, hipStream_t s);
-void launch_mfma_flat_x4(const MfmaArgs &a, int niw, int ns, unsigned blocks, size_t lds, hipStream_t s);
-
-#define QE_MFMA_K(WM, WN, NIW, KKT, NS)                                                                                         \
-    do {                                                                                                                        \
-        constexpr bool patch_ = mfma_has_patch(MfKind::Halo, WM, NIW, KKT, NS);                                                 \
-        if (a.rq_out != nullptr && a.rq_patch)                                                                                  \
-            hipLaunchKernelGGL((conv_mfma_kernel<WM, WN, NIW, KKT, NS, true, patch_>), dim3(blocks), dim3(MF_THREADS), lds, s, a); \
-        else if (a.rq_out != nullptr)                                                                                           \
-            hipLaunchKernelGGL((conv_mfma_kernel<WM, WN, NIW, KKT, NS, true>), dim3(blocks), dim3(MF_THREADS), lds, s, a);      \
-        else                                                                                                                    \
-            hipLaunchKernelGGL((conv_mfma_kernel<WM, WN, NIW, KKT, NS, false>), dim3(blocks), dim3(MF_THREADS), lds, s, a);     \
-    } while (0)
-
+// the halo kernel of one wave layout and column-tile count.  PATCH form: <WM 4, NIW 7, KK 9, NS 1> only
+template <int WM, int WN, int NIW, int KKT, int NS>
+MfmaLaunch mfma_halo_rq(bool rq, bool patch)
+{
+    if (!rq) return patch ? nullptr : &mfma_launch<&conv_mfma_kernel<WM, WN, NIW, KKT, NS, false>>;
+    if (!patch) return &mfma_launch<&conv_mfma_kernel<WM, WN, NIW, KKT, NS, true>>;
+    if constexpr (WM == 4 && NIW == 7 && KKT == 9 && NS == 1) return &mfma_launch<&conv_mfma_kernel<WM, WN, NIW, KKT, NS, true, true>>;
+    return nullptr;
+}
 // 1x1 convolutions get the multi-chunk stages (ns = 1, 2, 4)
-#define QE_MFMA_LAUNCH(WM, WN, NIW)                                                   \
-    do {                                                                              \
-        if (KK == 1) {                                                                \
-            if (ns == 4)       QE_MFMA_K(WM, WN, NIW, 1, 4);                          \
-            else if (ns == 2)  QE_MFMA_K(WM, WN, NIW, 1, 2);                          \
-            else               QE_MFMA_K(WM, WN, NIW, 1, 1);                          \
-        } else if (KK == 9 && a.KW == 3) {                                            \
-            QE_MFMA_K(WM, WN, NIW, 9, 1);                                             \
-        } else {                                                                      \
-            QE_MFMA_K(WM, WN, NIW, 0, 1);                                             \
-        }                                                                             \
-    } while (0)
+template <int WM, int WN, int NIW>
+MfmaLaunch mfma_halo(int kkt, int ns, bool rq, bool patch)
+{
+    switch (kkt) {
+        case 1:
+            switch (ns) {
+                case 4: return mfma_halo_rq<WM, WN, NIW, 1, 4>(rq, patch);
+                case 2: return mfma_halo_rq<WM, WN, NIW, 1, 2>(rq, patch);
+                case 1: return mfma_halo_rq<WM, WN, NIW, 1, 1>(rq, patch);
+            }
+            return nullptr;
+        case 9: return ns == 1 ? mfma_halo_rq<WM, WN, NIW, 9, 1>(rq, patch) : nullptr;
+        case 0: return ns == 1 ? mfma_halo_rq<WM, WN, NIW, 0, 1>(rq, patch) : nullptr;
+    }
+    return nullptr;
+}
 
 }  // namespace qe

@@ -9,35 +9,37 @@
 // The prepared part (re-laid-out weights, per-channel constants, tap-sum tables) comes from plan_prepared: shape without
 // the batch size, and bits.  It never depends on a pointer, on N or on the route a run takes.
 #pragma once
-#include "qe_common.h"
+#include "qe_conv_common.hpp"
 
 namespace qe {
 
-// host-side description of a fused output quantiser (qe_requant of the C ABI + destination)
-struct RequantHost {
-    uint8_t *out;
-    const float *scale, *zero;
-    int n_param;
-    float qmin, qmax;
-    int n_bits, sign;
-    int32_t *status;
+constexpr int FD_CK = 64;   // flatd: input channels per stage
+
+// which MFMA kernel runs (None: no family fits, the generic VALU kernel runs)
+enum class MfmaFamily {
+    None,
+    Halo,      // conv_mfma_kernel: halo tile in LDS, any kernel size
+    Ws,        // conv_mfma_ws_kernel: 3x3, warp-specialised producer / consumer waves
+    Sm2,       // conv_mfma_sm2_kernel: 3x3, two strips per wave, weights through LDS
+    Stem,      // conv_mfma_smallic_kernel: IC <= 4
+    Flat,      // conv_mfma_flat_kernel: 1x1 / stride 1 / no padding over the flat pixel index
+    FlatS2,    // ... stride 2 (the downsample branches)
+    FlatX4,    // ... 4-bit activations read from the packed stream by the kernel itself
+    Flatg      // conv_mfma_flatg_kernel: 1x1 on small planes (several whole images per tile)
 };
 
-constexpr int FD_CK = 64;   // flatd: input channels per stage
+inline bool mfma_is_flat(MfmaFamily f) { return f == MfmaFamily::Flat || f == MfmaFamily::FlatS2 || f == MfmaFamily::FlatX4; }
 
 // MFMA family, pre-pass and workspace [prepared tables | scratch] of one problem
 struct MfmaPlan {
-    bool ok = false;
+    MfmaFamily family = MfmaFamily::None;
     int cfg = 0;       // 0: 4x1 waves (MT 128), 1: 2x2 (MT 64), 2: 1x4 (MT 32)
     int MT = 0, OCP = 0, NCH = 0, NG = 0, KK = 0, OH = 0, OW = 0;
     int TH = 0, ni = 0, niw = 0, IHT = 0, IWP = 0, ROWMUL = 1, COLMUL = 1;
-    bool smallic = false;
     int GI = 1, NS = 1;
-    bool flat = false, wraw = false, ws = false, s2 = false, sm2 = false;
+    bool wraw = false;         // the flat kernels read the packed 8-bit weights themselves: no tables
     bool expand = false;       // sub-8-bit activations are expanded to 8-bit codes in the workspace first
-    bool x4 = false;           // 4-bit activations read from the packed stream by the flat kernel itself
     size_t xe_off = 0;
-    bool flatg = false;        // flat 1x1 kernel for small planes (several whole images per tile)
     bool sub = false;          // strided 1x1: the sampled pixels are gathered into a dense tensor first
     bool sub_x4 = false;       // ... straight from the 4-bit stream (subsample_x4_kernel), no expansion pass
     size_t sub_off = 0;
@@ -94,6 +96,11 @@ struct ConvPlan {
 ConvPlan plan_conv(const ConvRequest &rq);
 MfmaPlan plan_prepared(const qe_conv_shape *sh, int x_bits, int w_bits);
 uint64_t prepared_layout(const MfmaPlan &p, const qe_conv_shape *sh);
+
+// The launch function of the MFMA-family instance a plan selects (split: ConvPlan::split; rq: the re-quantising instance;
+// patch: its LDS byte patch form), or null when no such instance is compiled.  The planner asks it whether a PATCH form
+// exists, launch_conv_mfma calls what it returns: the two cannot disagree about the instance set (qe_conv_mfma.hip).
+MfmaLaunch mfma_instance(const MfmaPlan &m, int KW, int split, bool rq, bool patch);
 
 // launchers of the routes (the plan was made for these operands)
 int launch_conv_mfma(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *sh,

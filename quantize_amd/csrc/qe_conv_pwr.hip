@@ -25,7 +25,7 @@
 //     of 896-byte row runs -- or, when the tile is a whole plane (14x14), as ONE contiguous, line-aligned 6272-byte run
 //     (8 rows x 784 B = 49 lines), which the 8-rows-x-128-B pieces of the flat kernels cannot give on 784-byte rows
 //     (store-only probes: 3.6 TB/s against 5.1-5.6, profiles/r02c_probe_store_occ.txt).
-#include "qe_conv_mfma_kernel.hpp"
+#include "qe_conv_common.hpp"
 #include "qe_conv_plan.hpp"
 
 #include <utility>
@@ -44,12 +44,7 @@ struct PwrArgs {
     int strips_per_group;      // 32-channel strips of one group
     unsigned long long *dbg;   // diagnostic builds (-DQE_STAMP) only: per-wave phase cycle sums
     int W_in, PIN, OW;         // stride-2 form: input row length, input plane size, output row length (P = output plane)
-    // fused re-quantisation (RQ instances): the 8-bit code of the consumer's quantiser instead of fp32, fields as in MfmaArgs
-    uint8_t *rq_out;
-    const float *rq_scale, *rq_zero;
-    float rq_qmin, rq_qmax, rq_lo, rq_hi;
-    unsigned rq_offset;
-    int32_t *rq_status;
+    RqArgs rq;                 // fused re-quantisation (RQ instances): the 8-bit code of the consumer's quantiser instead of fp32
     // residual block end (RES instances): out = max(y + res, 0) with res shaped like out; out may be NULL when RQ
     const float *res;
 };
@@ -83,7 +78,7 @@ __device__ __forceinline__ void res_flush(const PwrArgs &a, const ResBlock<RQ, N
     }
     if constexpr (RQ) {
 #pragma unroll
-        for (int k = 0; k < NB; ++k) *reinterpret_cast<uint32_t *>(a.rq_out + b.e + off[k]) = b.pk[k];
+        for (int k = 0; k < NB; ++k) *reinterpret_cast<uint32_t *>(a.rq.out + b.e + off[k]) = b.pk[k];
     }
 }
 template <bool RQ>
@@ -325,7 +320,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_pwr_kernel(const PwrArgs a
     RqConst rqc;
     bool bad = false, rq_fast_u = false;
     if constexpr (RQ) {
-        rqc = rq_setup(a);
+        rqc = rq_setup(a.rq);
         rqc.slow = __builtin_amdgcn_readfirstlane(rqc.slow);      // the same in every lane: say so (or every use becomes a select)
         rqc.chk = __builtin_amdgcn_readfirstlane(rqc.chk);
         rq_fast_u = rq_fast_ok(rqc);
@@ -458,7 +453,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_pwr_kernel(const PwrArgs a
             };
             if (fast) { if (need_sx) body(std::true_type{}, std::true_type{}); else body(std::true_type{}, std::false_type{}); }
             else body(std::false_type{}, std::false_type{});
-            uint8_t *out_q = a.rq_out + ((int64_t)n0 * a.OC + oc0) * P + p0;   // wave-uniform
+            uint8_t *out_q = a.rq.out + ((int64_t)n0 * a.OC + oc0) * P + p0;   // wave-uniform
 #pragma unroll
             for (int k = 0; k < G::NRQ; ++k) {
                 uint4 d4;
@@ -555,7 +550,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_pwr_kernel(const PwrArgs a
         QE_ST(3);
     }
     epilogue(strip0 + (n_my - 1) * WAVES, c_sw, c_zw, c_bi, sx_cur);
-    if constexpr (RQ) rq_report(a, bad);
+    if constexpr (RQ) rq_report(a.rq, bad);
 #ifdef QE_STAMP
     QE_ST(4);
     __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): stores acknowledged
@@ -750,7 +745,7 @@ __global__ __launch_bounds__(512, 2) void conv_pwr7_kernel(const PwrArgs a)
     RqConst rqc;
     bool bad = false, rq_fast_u = false;
     if constexpr (RQ) {
-        rqc = rq_setup(a);
+        rqc = rq_setup(a.rq);
         rqc.slow = __builtin_amdgcn_readfirstlane(rqc.slow);
         rqc.chk = __builtin_amdgcn_readfirstlane(rqc.chk);
         rq_fast_u = rq_fast_ok(rqc);
@@ -828,7 +823,7 @@ __global__ __launch_bounds__(512, 2) void conv_pwr7_kernel(const PwrArgs a)
                     }
                 }
                 // the run of image n0 + gi: 32 x 49 codes = 98 16-byte pieces, copied flat
-                uint8_t *dst = a.rq_out + ((int64_t)(n0 + gi) * a.OC + oc0) * P;
+                uint8_t *dst = a.rq.out + ((int64_t)(n0 + gi) * a.OC + oc0) * P;
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
                     const uint4 d4 = *reinterpret_cast<const uint4 *>(bp + 16 * (64 * k + lane));
@@ -898,25 +893,43 @@ __global__ __launch_bounds__(512, 2) void conv_pwr7_kernel(const PwrArgs a)
         if (sx_cur) mma_strip(std::true_type{}); else mma_strip(std::false_type{});
     }
     epilogue(strip0 + (n_my - 1) * WAVES, c_sw, c_zw, c_bi, sx_cur);
-    if constexpr (RQ) rq_report(a, bad);
+    if constexpr (RQ) rq_report(a.rq, bad);
 #undef QE_PWR7_WAIT
 }
 
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-extern unsigned long long *g_mfma_dbg;   // qe_conv_mfma.hip (diagnostic builds)
-
-static void rq_args(PwrArgs &a, const RequantHost *rq)
+// the instances; each one's tile geometry sizes its dynamic LDS
+template <int KSV, int GIV, bool RQV, bool RESV>
+static void launch_pwr7_k(const PwrArgs &a, int64_t blocks, hipStream_t s)
 {
-    a.rq_out = nullptr; a.rq_scale = nullptr; a.rq_zero = nullptr; a.rq_status = nullptr;
-    a.rq_qmin = a.rq_qmax = a.rq_lo = a.rq_hi = 0.0f; a.rq_offset = 0;
-    if (rq != nullptr) {
-        a.rq_out = rq->out; a.rq_scale = rq->scale; a.rq_zero = rq->zero;
-        a.rq_qmin = rq->qmin; a.rq_qmax = rq->qmax; a.rq_status = rq->status;
-        a.rq_offset = rq->sign ? 128u : 0u;                       // tpack.cu:108-111
-        a.rq_lo = rq->sign ? -128.0f : 0.0f; a.rq_hi = rq->sign ? 127.0f : 255.0f;
-    }
+    constexpr size_t lds = Pwr7Geom<KSV, GIV>::LDS;
+    launch_instance<&conv_pwr7_kernel<KSV, GIV, RQV, RESV>>((unsigned)blocks, 512, lds, lds, s, a);
+}
+template <int KSV, int GIV, bool RESV>
+static void launch_pwr7_rq(const PwrArgs &a, bool rq, int64_t blocks, hipStream_t s)
+{
+    if (rq) launch_pwr7_k<KSV, GIV, true, RESV>(a, blocks, s); else launch_pwr7_k<KSV, GIV, false, RESV>(a, blocks, s);
+}
+template <int WV, int KSV, int TWV, bool S2V, bool RQV>
+static void launch_pwr_k(const PwrArgs &a, int64_t blocks, hipStream_t s)
+{
+    constexpr size_t lds = PwrGeom<7, WV, KSV, TWV>::LDS;
+    launch_instance<&conv_pwr_kernel<7, WV, KSV, TWV, S2V, RQV>>((unsigned)blocks, 64 * WV, lds, lds, s, a);
+}
+template <int WV, int KSV, int TWV, bool RQV>
+static void launch_pwr_res(const PwrArgs &a, int64_t blocks, hipStream_t s)
+{
+    constexpr size_t lds = PwrGeom<7, WV, KSV, TWV>::LDS;
+    launch_instance<&conv_pwr_kernel<7, WV, KSV, TWV, false, RQV, true>>((unsigned)blocks, 64 * WV, lds, lds, s, a);
+}
+template <int WV, int KSV, int TWV>
+static void launch_pwr_tile(const PwrArgs &a, bool s2, bool rq, bool res, int64_t blocks, hipStream_t s)
+{
+    if (res) { if (rq) launch_pwr_res<WV, KSV, TWV, true>(a, blocks, s); else launch_pwr_res<WV, KSV, TWV, false>(a, blocks, s); }
+    else if (s2) { if (rq) launch_pwr_k<WV, KSV, TWV, true, true>(a, blocks, s); else launch_pwr_k<WV, KSV, TWV, true, false>(a, blocks, s); }
+    else { if (rq) launch_pwr_k<WV, KSV, TWV, false, true>(a, blocks, s); else launch_pwr_k<WV, KSV, TWV, false, false>(a, blocks, s); }
 }
 
 // p.route == Pwr7: 7x7 planes, p.pwr7_gi images per tile (the residual block end: the 512-channel form only)
@@ -926,7 +939,7 @@ static void launch_pwr7(const ConvPlan &p, const qe_qparam *x, const qe_qparam *
     const qe_conv_shape *sh = &p.run;
     PwrArgs a;
     a.res = res;
-    rq_args(a, rq);
+    a.rq = make_rq_args(rq);
     a.W_in = 7; a.PIN = 49; a.OW = 7;
     a.x = static_cast<const uint8_t *>(x->data); a.w = static_cast<const uint8_t *>(w->data);
     a.x_scale = x->scale; a.x_zero = x->zero; a.w_scale = w->scale; a.w_zero = w->zero; a.bias = bias;
@@ -939,22 +952,10 @@ static void launch_pwr7(const ConvPlan &p, const qe_qparam *x, const qe_qparam *
     a.dbg = g_mfma_dbg;
     a.chunk = p.chunk;
     const int64_t blocks = p.blocks;
-#define QE_PWR7_LAUNCH3(KSV, GIV, RQV, RESV)                                                                                \
-    do {                                                                                                                    \
-        static const bool ok_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_pwr7_kernel<KSV, GIV, RQV, RESV>), \
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, Pwr7Geom<KSV, GIV>::LDS) == hipSuccess; \
-        (void)ok_;                                                                                                          \
-        constexpr size_t lds_ = Pwr7Geom<KSV, GIV>::LDS;                                                                    \
-        hipLaunchKernelGGL((conv_pwr7_kernel<KSV, GIV, RQV, RESV>), dim3((unsigned)blocks), dim3(512), lds_, s, a);         \
-    } while (0)
-#define QE_PWR7_LAUNCH2(KSV, GIV, RQV) QE_PWR7_LAUNCH3(KSV, GIV, RQV, false)
-#define QE_PWR7_LAUNCH(KSV, GIV) do { if (rq != nullptr) QE_PWR7_LAUNCH2(KSV, GIV, true); else QE_PWR7_LAUNCH2(KSV, GIV, false); } while (0)
-    if (res != nullptr) {
-        if (rq != nullptr) QE_PWR7_LAUNCH3(16, 2, true, true); else QE_PWR7_LAUNCH3(16, 2, false, true);
-    } else if (sh->IC == 512) QE_PWR7_LAUNCH(16, 2); else if (sh->IC == 256) QE_PWR7_LAUNCH(8, 4); else QE_PWR7_LAUNCH(4, 4);
-#undef QE_PWR7_LAUNCH
-#undef QE_PWR7_LAUNCH2
-#undef QE_PWR7_LAUNCH3
+    if (res != nullptr) launch_pwr7_rq<16, 2, true>(a, rq != nullptr, blocks, s);
+    else if (sh->IC == 512) launch_pwr7_rq<16, 2, false>(a, rq != nullptr, blocks, s);
+    else if (sh->IC == 256) launch_pwr7_rq<8, 4, false>(a, rq != nullptr, blocks, s);
+    else launch_pwr7_rq<4, 4, false>(a, rq != nullptr, blocks, s);
 }
 
 // res != nullptr: the residual block end (RES instances, stride 1 only): out (may be NULL when rq) = relu(y + res)
@@ -969,7 +970,7 @@ int launch_pwr(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, const 
     const qe_conv_shape *sh = &p.run;
     PwrArgs a;
     a.res = res;
-    rq_args(a, rq);
+    a.rq = make_rq_args(rq);
     a.x = static_cast<const uint8_t *>(x->data); a.w = static_cast<const uint8_t *>(w->data);
     a.x_scale = x->scale; a.x_zero = x->zero; a.w_scale = w->scale; a.w_zero = w->zero; a.bias = bias;
     a.x_sign = x->sign; a.w_sign = w->sign; a.w_per_tensor = (w->n_param == 1);
@@ -984,37 +985,16 @@ int launch_pwr(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, const 
     a.dbg = g_mfma_dbg;
     a.chunk = p.chunk;
     const int64_t blocks = p.blocks;
-#define QE_PWR_LAUNCH2(WV, KSV, TWV, S2V, RQV)                                                                             \
-    do {                                                                                                                    \
-        static const bool ok_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_pwr_kernel<7, WV, KSV, TWV, S2V, RQV>), \
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, PwrGeom<7, WV, KSV, TWV>::LDS) == hipSuccess; \
-        (void)ok_;                                                                                                          \
-        constexpr size_t lds_ = PwrGeom<7, WV, KSV, TWV>::LDS;                                                              \
-        hipLaunchKernelGGL((conv_pwr_kernel<7, WV, KSV, TWV, S2V, RQV>), dim3((unsigned)blocks), dim3(64 * WV), lds_, s, a); \
-    } while (0)
-#define QE_PWR_LAUNCH1(WV, KSV, TWV, S2V) do { if (rq != nullptr) QE_PWR_LAUNCH2(WV, KSV, TWV, S2V, true); else QE_PWR_LAUNCH2(WV, KSV, TWV, S2V, false); } while (0)
-#define QE_PWR_LAUNCHR(WV, KSV, TWV, RQV)                                                                                   \
-    do {                                                                                                                    \
-        static const bool ok_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_pwr_kernel<7, WV, KSV, TWV, false, RQV, true>), \
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, PwrGeom<7, WV, KSV, TWV>::LDS) == hipSuccess; \
-        (void)ok_;                                                                                                          \
-        constexpr size_t lds_ = PwrGeom<7, WV, KSV, TWV>::LDS;                                                              \
-        hipLaunchKernelGGL((conv_pwr_kernel<7, WV, KSV, TWV, false, RQV, true>), dim3((unsigned)blocks), dim3(64 * WV), lds_, s, a); \
-    } while (0)
-#define QE_PWR_LAUNCH(WV, KSV, TWV)                                                                                         \
-    do {                                                                                                                    \
-        if (res != nullptr) { if (rq != nullptr) QE_PWR_LAUNCHR(WV, KSV, TWV, true); else QE_PWR_LAUNCHR(WV, KSV, TWV, false); } \
-        else if (p.pwr_s2) QE_PWR_LAUNCH1(WV, KSV, TWV, true); else QE_PWR_LAUNCH1(WV, KSV, TWV, false);                      \
-    } while (0)
+    const bool rqv = rq != nullptr, resv = res != nullptr;
     if (p.pwr_tw == 224) {
-        if (p.pwr_ks == 2) QE_PWR_LAUNCH(4, 2, 224); else if (p.pwr_ks == 4) QE_PWR_LAUNCH(4, 4, 224); else QE_PWR_LAUNCH(8, 8, 224);
+        if (p.pwr_ks == 2) launch_pwr_tile<4, 2, 224>(a, p.pwr_s2, rqv, resv, blocks, s);
+        else if (p.pwr_ks == 4) launch_pwr_tile<4, 4, 224>(a, p.pwr_s2, rqv, resv, blocks, s);
+        else launch_pwr_tile<8, 8, 224>(a, p.pwr_s2, rqv, resv, blocks, s);
     } else {
-        if (p.pwr_ks == 2) QE_PWR_LAUNCH(4, 2, 196); else if (p.pwr_ks == 4) QE_PWR_LAUNCH(4, 4, 196); else QE_PWR_LAUNCH(8, 8, 196);
+        if (p.pwr_ks == 2) launch_pwr_tile<4, 2, 196>(a, p.pwr_s2, rqv, resv, blocks, s);
+        else if (p.pwr_ks == 4) launch_pwr_tile<4, 4, 196>(a, p.pwr_s2, rqv, resv, blocks, s);
+        else launch_pwr_tile<8, 8, 196>(a, p.pwr_s2, rqv, resv, blocks, s);
     }
-#undef QE_PWR_LAUNCH1
-#undef QE_PWR_LAUNCH2
-#undef QE_PWR_LAUNCHR
-#undef QE_PWR_LAUNCH
     QE_LAUNCH_CHECK();
     return QE_OK;
 }

@@ -1115,33 +1115,28 @@ static LinArgs lin_args(const LinRequest &r, float *out)
     return a;
 }
 
-// One template instance; more than 64 KB of dynamic LDS needs the attribute, raised once per instance
+// One template instance of the plan (launch_instance raises the dynamic-LDS attribute once per instance)
 template <auto KERNEL>
-static void launch_instance(const LinPlan &p, const LinArgs &a, hipStream_t s)
+static void launch_lin(const LinPlan &p, const LinArgs &a, hipStream_t s)
 {
-    if (p.lds > 0) {
-        static const bool raised = hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       (int)p.lds) == hipSuccess;
-        (void)raised;
-    }
-    hipLaunchKernelGGL(KERNEL, dim3((unsigned)p.blocks), dim3(p.threads), p.lds, s, a);
+    launch_instance<KERNEL>((unsigned)p.blocks, p.threads, p.lds, p.lds, s, a);
 }
 
 template <int EPI>
 static void launch_epi(const LinPlan &p, const LinArgs &a, hipStream_t s)
 {
     switch (p.form) {
-    case LIN_FORM_NJ2: return launch_instance<&linear_mfma_kernel<2, EPI>>(p, a, s);
-    case LIN_FORM_NJ4: return launch_instance<&linear_mfma_kernel<4, EPI>>(p, a, s);
-    case LIN_FORM_W8: return launch_instance<&linear_mfma8_kernel<2, EPI>>(p, a, s);
-    case LIN_FORM_W4: return launch_instance<&linear_mfma8_kernel<1, EPI>>(p, a, s);
+    case LIN_FORM_NJ2: return launch_lin<&linear_mfma_kernel<2, EPI>>(p, a, s);
+    case LIN_FORM_NJ4: return launch_lin<&linear_mfma_kernel<4, EPI>>(p, a, s);
+    case LIN_FORM_W8: return launch_lin<&linear_mfma8_kernel<2, EPI>>(p, a, s);
+    case LIN_FORM_W4: return launch_lin<&linear_mfma8_kernel<1, EPI>>(p, a, s);
     }
     // the bf16 kernel has F32 and RES instances, the order-preserving kernels F32 only (the plan sends the rest to two passes)
     if constexpr (EPI == LIN_F32 || EPI == LIN_RES)
-        if (p.form == LIN_FORM_BF16) return launch_instance<&linear_f32_mfma_kernel<EPI>>(p, a, s);
+        if (p.form == LIN_FORM_BF16) return launch_lin<&linear_f32_mfma_kernel<EPI>>(p, a, s);
     if constexpr (EPI == LIN_F32) {
-        if (p.form == LIN_FORM_CHAIN) return launch_instance<&linear_generic_kernel<false>>(p, a, s);
-        if (p.form == LIN_FORM_CHAIN_F) return launch_instance<&linear_generic_kernel<true>>(p, a, s);
+        if (p.form == LIN_FORM_CHAIN) return launch_lin<&linear_generic_kernel<false>>(p, a, s);
+        if (p.form == LIN_FORM_CHAIN_F) return launch_lin<&linear_generic_kernel<true>>(p, a, s);
     }
 }
 
