@@ -261,6 +261,41 @@ int qe_quantconv2d_float_input_path(const qe_conv_shape *shape, const qe_qparam 
  * and profiles): 0 = generic fp32 direct convolution, 1 = int8 MFMA implicit GEMM. */
 int qe_quantconv2d_path(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w);
 
+/* The whole host-side plan of a packed-activation convolution request (for tests, bench and profiles): which kernel
+ * instance the call launches, with which pre-pass, epilogue, LDS size and grid.  Copied from the one plan every query and
+ * launcher reads (the QE_* knobs of the last snapshot included); the call decides nothing and does no device work.
+ *   route        0 generic VALU kernel, 1 resident-tile pwr, 2 pwr7, 3 LDS-DMA ring flatd, 4 one of the MFMA families
+ *   fused        the requested re-quantisation runs inside the conv kernel
+ *   family       0 none, 1 halo, 2 warp-specialised, 3 two-strip, 4 stem, 5 flat, 6 flat stride 2, 7 flat 4-bit
+ *                activations, 8 flatg (set whenever an MFMA family fits, also when another route takes the problem)
+ *   cfg niw kkt ns split wraw rq patch
+ *                the template instance of the family (route 4): wave layout (0: 4x1, 1: 2x2, 2: 1x4), column tiles per
+ *                wave, tap form (1: 1x1, 9: 3x3, 0: any other kernel size), chunks per stage, channel slices of the
+ *                staging threads, raw 8-bit weights, and whether the re-quantising / LDS byte patch instance is launched
+ *   has_instance the library compiles that instance (route 4; a plan without one would fail with QE_ERR_UNSUPPORTED)
+ *   pre          strided gather in front of the kernel: 0 none, 1 subsample_x4, 2 subsample2<sub2_log_up>,
+ *                3 subsample<wide>, 4 subsample<narrow>; expand: the sub-8-bit expansion pass runs first
+ *   lds          dynamic LDS bytes of the MFMA-family launch; blocks: its grid
+ *   total / prep_total / y_bytes   workspace [prepared part | scratch], its prepared part, the rounded fp32 output */
+typedef struct qe_conv_plan_info {
+    int32_t route, fused;
+    int32_t family, cfg, niw, kkt, ns, split, wraw, rq, patch, has_instance;
+    int32_t ctab, gi, th, ni, mt, nch, oh, ow, rowmul, colmul;
+    int32_t pre, sub2_log_up, expand, sub_x4;
+    int32_t fd_w8;
+    int32_t pwr_tw, pwr_ks, pwr_groups, pwr7_gi, pwr_s2;
+    int64_t lds, blocks, total, prep_total, y_bytes;
+} qe_conv_plan_info;
+/* rq: the consumer's quantiser of a qe_quantconv2d_requant_prepared call, or NULL for the fp32 call; out / codes: the
+ * destination addresses (only their alignment counts; NULL reads as aligned).  QE_ERR_ARG for a bad shape or a NULL
+ * operand. */
+int qe_quantconv2d_plan_info(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq,
+                             const float *out, const uint8_t *codes, qe_conv_plan_info *info);
+/* 1 when the library compiles the MFMA-family instance these parameters name (as in qe_conv_plan_info), else 0: what the
+ * planner's PATCH question and the launcher ask, answered for any parameter set.  Host-only. */
+int qe_conv_mfma_has_instance(int32_t family, int32_t cfg, int32_t niw, int32_t kkt, int32_t ns, int32_t split,
+                              int32_t wraw, int32_t rq, int32_t patch);
+
 /* ---- quantlinear ------------------------------------------------------------
  * Replaces quantlinear / quantlinear_cuda (functions/quantlinear.cu:233-297, :153-214):
  *   out[b, o] = bias[o] + sum_k (q_x[b,k] + zx[b]) * (q_w[o,k] + zw[o]) * (sx[b] * sw[o])

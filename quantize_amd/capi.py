@@ -34,6 +34,14 @@ class QeRequant(ctypes.Structure):
                 ("qmin", ctypes.c_float), ("qmax", ctypes.c_float), ("n_bits", ctypes.c_int32), ("sign", ctypes.c_int32)]
 
 
+class QeConvPlanInfo(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_int32) for n in (
+        "route", "fused", "family", "cfg", "niw", "kkt", "ns", "split", "wraw", "rq", "patch", "has_instance",
+        "ctab", "gi", "th", "ni", "mt", "nch", "oh", "ow", "rowmul", "colmul", "pre", "sub2_log_up", "expand", "sub_x4",
+        "fd_w8", "pwr_tw", "pwr_ks", "pwr_groups", "pwr7_gi", "pwr_s2")] +
+                [(n, ctypes.c_int64) for n in ("lds", "blocks", "total", "prep_total", "y_bytes")])
+
+
 class QeError(RuntimeError):
     pass
 
@@ -41,6 +49,7 @@ class QeError(RuntimeError):
 _vp, _i32, _i64, _sz, _f32, _str = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float,
                                     ctypes.c_char_p)
 _pq, _ps, _pr, _ppc = ctypes.POINTER(QeQParam), ctypes.POINTER(QeConvShape), ctypes.POINTER(QeRequant), ctypes.POINTER(_vp)
+_pi = ctypes.POINTER(QeConvPlanInfo)
 _attn = [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _f32]
 
 # every symbol include/quant_engine.h declares: name -> (restype, argtypes); lib() applies the table
@@ -59,6 +68,8 @@ PROTOTYPES = {
     "qe_maxpool2d_codes": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     # packed-activation convolutions
     "qe_quantconv2d_path": (_i32, [_ps, _pq, _pq]),
+    "qe_quantconv2d_plan_info": (_i32, [_ps, _pq, _pq, _pr, _vp, _vp, _pi]),
+    "qe_conv_mfma_has_instance": (_i32, [_i32] * 9),
     "qe_quantconv2d_workspace_bytes": (_sz, [_ps, _i32, _i32]),
     "qe_quantconv2d": (_i32, [_pq, _pq, _vp, _ps, _vp, _vp, _sz, _vp]),
     "qe_conv_prepared_bytes": (_sz, [_ps, _i32, _i32]),
@@ -242,6 +253,28 @@ def conv_prepared_layout(sh, x_bits, w_bits):
 
 def conv_path(sh, xq, wq):
     return int(lib().qe_quantconv2d_path(ctypes.byref(sh), ctypes.byref(xq), ctypes.byref(wq)))
+
+
+# qe_conv_plan_info: route, MFMA family and pre-pass by number
+CONV_ROUTES = {0: "generic", 1: "pwr", 2: "pwr7", 3: "flatd", 4: "mfma"}
+CONV_FAMILIES = {0: "none", 1: "halo", 2: "ws", 3: "sm2", 4: "stem", 5: "flat", 6: "flat_s2", 7: "flat_x4", 8: "flatg"}
+CONV_PREPASSES = {0: "none", 1: "sub_x4", 2: "sub2", 3: "sub_wide", 4: "sub_narrow"}
+
+
+def conv_plan_info(sh, xq, wq, rq=None, out=0, codes=0):
+    """qe_quantconv2d_plan_info (host-only): the plan of the request as a QeConvPlanInfo, with the QE_* knobs of the last
+    reload_env().  rq: a capi.requant for the re-quantising call; out / codes: destination addresses (0: aligned)."""
+    info = QeConvPlanInfo()
+    check(lib().qe_quantconv2d_plan_info(ctypes.byref(sh), ctypes.byref(xq), ctypes.byref(wq),
+                                         None if rq is None else ctypes.byref(rq), int(out) or None, int(codes) or None,
+                                         ctypes.byref(info)))
+    return info
+
+
+def conv_mfma_has_instance(family, cfg, niw, kkt, ns, split, wraw, rq, patch):
+    """qe_conv_mfma_has_instance (host-only): the library compiles this MFMA-family instance (fields as QeConvPlanInfo)."""
+    return bool(lib().qe_conv_mfma_has_instance(int(family), int(cfg), int(niw), int(kkt), int(ns), int(split), int(wraw),
+                                                int(rq), int(patch)))
 
 
 def quantconv2d(xq, wq, bias, sh, out=None, workspace=None, stream=None):

@@ -151,6 +151,47 @@ extern "C" int qe_quantconv2d_path(const qe_conv_shape *shape, const qe_qparam *
     return qe::plan_conv({shape, x, w}).route != qe::ConvRoute::Generic ? 1 : 0;
 }
 
+// the plan of a request, field by field (tests, bench, profiles): decides nothing, reads no knob of its own
+extern "C" int qe_quantconv2d_plan_info(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq,
+                                        const float *out, const uint8_t *codes, qe_conv_plan_info *info)
+{
+    using namespace qe;
+    if (check_shape(shape) != QE_OK || x == nullptr || w == nullptr || info == nullptr) return QE_ERR_ARG;
+    ConvRequest r{shape, x, w, reinterpret_cast<uintptr_t>(out), reinterpret_cast<uintptr_t>(codes)};
+    if (rq != nullptr) { r.rq_bits = rq->n_bits; r.rq_n_param = rq->n_param; }
+    const ConvPlan p = plan_conv(r);
+    const MfmaPlan &m = p.m;
+    const bool mfma = p.route == ConvRoute::Mfma;
+    qe_conv_plan_info i{};
+    i.route = (int)p.route; i.fused = p.fused;
+    i.family = (int)m.family; i.cfg = m.cfg; i.niw = m.niw; i.kkt = mfma_kkt(m.KK, p.run.KW); i.ns = m.NS; i.split = p.split;
+    i.wraw = m.wraw;
+    i.rq = mfma && p.fused; i.patch = p.rq_patch;          // what the re-quantising entry point hands launch_conv_mfma
+    i.has_instance = mfma && mfma_instance(m, p.run.KW, p.split, i.rq != 0, p.rq_patch) != nullptr;
+    i.ctab = p.ctab; i.gi = m.GI; i.th = m.TH; i.ni = m.ni; i.mt = m.MT; i.nch = m.NCH; i.oh = m.OH; i.ow = m.OW;
+    i.rowmul = m.ROWMUL; i.colmul = m.COLMUL;
+    i.pre = (int)p.pre; i.sub2_log_up = p.sub2_log_up; i.expand = m.expand; i.sub_x4 = m.sub_x4;
+    i.fd_w8 = p.fd_w8;
+    i.pwr_tw = p.pwr_tw; i.pwr_ks = p.pwr_ks; i.pwr_groups = p.pwr_groups; i.pwr7_gi = p.pwr7_gi; i.pwr_s2 = p.pwr_s2;
+    i.lds = (int64_t)p.lds; i.blocks = p.blocks; i.total = (int64_t)m.total; i.prep_total = (int64_t)m.prep_total;
+    i.y_bytes = (int64_t)p.y_bytes;
+    *info = i;
+    return QE_OK;
+}
+
+extern "C" int qe_conv_mfma_has_instance(int32_t family, int32_t cfg, int32_t niw, int32_t kkt, int32_t ns, int32_t split,
+                                         int32_t wraw, int32_t rq, int32_t patch)
+{
+    using namespace qe;
+    if (family <= (int)MfmaFamily::None || family > (int)MfmaFamily::Flatg) return 0;
+    if (kkt != 1 && kkt != 9 && kkt != 0) return 0;
+    MfmaPlan m;
+    m.family = (MfmaFamily)family; m.cfg = cfg; m.niw = niw; m.NS = ns; m.wraw = wraw != 0;
+    const int KW = kkt == 1 ? 1 : (kkt == 9 ? 3 : 5);      // a kernel size with that tap form
+    m.KK = KW * KW;
+    return mfma_instance(m, KW, split, rq != 0, patch != 0) != nullptr ? 1 : 0;
+}
+
 extern "C" int qe_quantconv2d(const qe_qparam *x, const qe_qparam *w, const float *bias,
                               const qe_conv_shape *shape, float *out,
                               void *workspace, size_t workspace_bytes, qe_stream_t stream)

@@ -373,7 +373,7 @@ MfmaLaunch mfma_instance(const MfmaPlan &m, int KW, int split, bool rq, bool pat
     switch (m.family) {
         case MfmaFamily::None: return nullptr;
         case MfmaFamily::Halo: {
-            const int kkt = m.KK == 1 ? 1 : ((m.KK == 9 && KW == 3) ? 9 : 0);
+            const int kkt = mfma_kkt(m.KK, KW);
             switch (m.cfg) {
                 case 0: return mfma_halo_cfg0(m.niw, kkt, m.NS, rq, patch);
                 case 1: return mfma_halo_cfg1(m.niw, kkt, m.NS, rq, patch);

@@ -101,6 +101,8 @@ uint64_t prepared_layout(const MfmaPlan &p, const qe_conv_shape *sh);
 // patch: its LDS byte patch form), or null when no such instance is compiled.  The planner asks it whether a PATCH form
 // exists, launch_conv_mfma calls what it returns: the two cannot disagree about the instance set (qe_conv_mfma.hip).
 MfmaLaunch mfma_instance(const MfmaPlan &m, int KW, int split, bool rq, bool patch);
+// tap form of an instance: 1 (1x1), 9 (3x3) or 0 (any other kernel size); only the halo family branches on it
+inline int mfma_kkt(int KK, int KW) { return KK == 1 ? 1 : ((KK == 9 && KW == 3) ? 9 : 0); }
 
 // launchers of the routes (the plan was made for these operands)
 int launch_conv_mfma(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *sh,

@@ -280,18 +280,21 @@ def test_conv_error_messages(engine):
 
 
 # ids keep the numbering the sets have always had (env1, the unpadded-row warp-specialised kernel, was removed with it)
-@pytest.mark.parametrize("env", [{"QE_SM2": "0", "QE_WS": "1"}, {"QE_SM2": "0", "QE_WS": "0"}, {"QE_SM2": "1"}, {"QE_FLAT_NIW": "4"}, {"QE_FLAT_NIW": "5"},
-                                 {"QE_FLAT_NIW": "7"}, {"QE_CHUNK_IMAGES": "0"}, {"QE_CHUNK_IMAGES": "1"}, {"QE_SUBSAMPLE": "0"}, {"QE_SUBSAMPLE": "1"}, {"QE_FLATG": "0"}, {"QE_CTAB": "0"}],
-                         ids=["env0"] + ["env%d" % i for i in range(2, 13)])
+VARIANT_ENVS = [{"QE_SM2": "0", "QE_WS": "1"}, {"QE_SM2": "0", "QE_WS": "0"}, {"QE_SM2": "1"}, {"QE_FLAT_NIW": "4"}, {"QE_FLAT_NIW": "5"},
+                {"QE_FLAT_NIW": "7"}, {"QE_CHUNK_IMAGES": "0"}, {"QE_CHUNK_IMAGES": "1"}, {"QE_SUBSAMPLE": "0"}, {"QE_SUBSAMPLE": "1"}, {"QE_FLATG": "0"}, {"QE_CTAB": "0"}]
+VARIANT_SHAPES = [(2, 256, 14, 14, 256, 3, 1, 1), (3, 128, 28, 28, 128, 3, 1, 1), (4, 160, 7, 7, 130, 3, 1, 1),
+                  (2, 128, 14, 14, 192, 3, 2, 1), (2, 256, 28, 28, 160, 1, 1, 0), (5, 64, 7, 7, 48, 3, 1, 1),
+                  (9, 96, 30, 30, 130, 3, 2, 1), (2, 128, 56, 56, 160, 1, 2, 0), (3, 256, 14, 14, 140, 1, 2, 0),
+                  (2, 64, 15, 13, 40, 1, 3, 0), (9, 512, 7, 7, 256, 1, 1, 0), (5, 2048, 7, 7, 130, 1, 1, 0)]
+
+
+@pytest.mark.parametrize("env", VARIANT_ENVS, ids=["env0"] + ["env%d" % i for i in range(2, 13)])
 def test_kernel_variants_forced_by_env(engine, env):
     """The tuning knobs select other kernel variants (two-strip / warp-specialised / single-role 3x3, flat tile widths,
     block maps); every variant must meet the same parity bar."""
     rng = np.random.RandomState(17)
     with capi.knobs(**env):
-        for shp in [(2, 256, 14, 14, 256, 3, 1, 1), (3, 128, 28, 28, 128, 3, 1, 1), (4, 160, 7, 7, 130, 3, 1, 1),
-                    (2, 128, 14, 14, 192, 3, 2, 1), (2, 256, 28, 28, 160, 1, 1, 0), (5, 64, 7, 7, 48, 3, 1, 1),
-                    (9, 96, 30, 30, 130, 3, 2, 1), (2, 128, 56, 56, 160, 1, 2, 0), (3, 256, 14, 14, 140, 1, 2, 0),
-                    (2, 64, 15, 13, 40, 1, 3, 0), (9, 512, 7, 7, 256, 1, 1, 0), (5, 2048, 7, 7, 130, 1, 1, 0)]:
+        for shp in VARIANT_SHAPES:
             for zeros in (False, True):
                 case = _random_case(rng, *shp, 8, 1, 8, 0 if zeros else 1, w_pc=True, a_pc=False, zeros=zeros, bias=True)
                 y, o32, o64 = _run_case(engine, case, via_capi=True)
