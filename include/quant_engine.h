@@ -257,6 +257,29 @@ int qe_quantconv2d_float_input_prepared(const float *x, const qe_qparam *w, cons
 /* 0 = order-preserving VALU kernel, 1 = bf16 MFMA kernel */
 int qe_quantconv2d_float_input_path(const qe_conv_shape *shape, const qe_qparam *w);
 
+/* The whole host-side plan of a float-input convolution (for tests, bench and profiles), copied field by field from the one
+ * plan that qe_quantconv2d_float_input_path / _workspace_bytes / _ws / _prepared and qe_conv_f32_prepare read (the
+ * QE_F32_MFMA knob of the last snapshot included).  The call decides nothing and does no device work.
+ *   ok           1: a bf16 MFMA kernel runs; 0: the order-preserving VALU kernel (the other fields then say nothing)
+ *   kernel       the instance: 0..2 conv_f32_stem_kernel<4,1,7>, <2,2,4>, <2,2,7> (IC <= 4), 3..10 conv_f32_mfma_kernel
+ *                <4,1,4,1>, <4,1,4,2>, <4,1,7,1>, <4,1,7,2>, <2,2,2,1>, <2,2,2,2>, <2,2,4,1>, <2,2,4,2>
+ *                (<WM, WN waves, column tiles per wave, 16-channel groups per stage>)
+ *   stem         the stem kernel and its table layout
+ *   OCP NG KK    padded output channels, 16-channel groups (padded to even on the two-group instances), KH * KW
+ *   OH OW TH GI  output plane, output rows and images of a tile (GI > 1: whole images)
+ *   IHT IWP ROWMUL COLMUL   rows and columns of the halo image in LDS; a 1-wide kernel side keeps sampled rows / columns only
+ *   chunk n_pix_tiles n_oc_tiles tiles_h blocks   the block map and the grid
+ *   lds          dynamic LDS bytes of the launch
+ *   ep_off total the prepared tables [bf16 weights | sw, zw, bias per padded channel]: offset of the constants, size */
+typedef struct qe_conv_f32_plan {
+    int32_t ok, kernel, stem;
+    int32_t OCP, NG, KK, OH, OW, TH, GI, IHT, IWP, ROWMUL, COLMUL;
+    int32_t chunk, n_pix_tiles, n_oc_tiles, tiles_h;
+    int64_t blocks, lds, ep_off, total;
+} qe_conv_f32_plan;
+/* QE_ERR_ARG for a bad shape or a NULL argument. */
+int qe_conv_f32_plan_info(const qe_conv_shape *shape, qe_conv_f32_plan *info);
+
 /* Which kernel family qe_quantconv2d will pick for a problem (for tests, bench
  * and profiles): 0 = generic fp32 direct convolution, 1 = int8 MFMA implicit GEMM. */
 int qe_quantconv2d_path(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w);

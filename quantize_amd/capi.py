@@ -42,6 +42,13 @@ class QeConvPlanInfo(ctypes.Structure):
                 [(n, ctypes.c_int64) for n in ("lds", "blocks", "total", "prep_total", "y_bytes")])
 
 
+class QeConvF32Plan(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_int32) for n in (
+        "ok", "kernel", "stem", "OCP", "NG", "KK", "OH", "OW", "TH", "GI", "IHT", "IWP", "ROWMUL", "COLMUL",
+        "chunk", "n_pix_tiles", "n_oc_tiles", "tiles_h")] +
+                [(n, ctypes.c_int64) for n in ("blocks", "lds", "ep_off", "total")])
+
+
 class QeError(RuntimeError):
     pass
 
@@ -50,6 +57,7 @@ _vp, _i32, _i64, _sz, _f32, _str = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int6
                                     ctypes.c_char_p)
 _pq, _ps, _pr, _ppc = ctypes.POINTER(QeQParam), ctypes.POINTER(QeConvShape), ctypes.POINTER(QeRequant), ctypes.POINTER(_vp)
 _pi = ctypes.POINTER(QeConvPlanInfo)
+_pf = ctypes.POINTER(QeConvF32Plan)
 _attn = [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _f32]
 
 # every symbol include/quant_engine.h declares: name -> (restype, argtypes); lib() applies the table
@@ -86,6 +94,7 @@ PROTOTYPES = {
     # float-input convolutions
     "qe_quantconv2d_float_input": (_i32, [_vp, _pq, _vp, _ps, _vp, _vp]),
     "qe_quantconv2d_float_input_path": (_i32, [_ps, _pq]),
+    "qe_conv_f32_plan_info": (_i32, [_ps, _pf]),
     "qe_quantconv2d_float_input_workspace_bytes": (_sz, [_ps, _i32]),
     "qe_quantconv2d_float_input_ws": (_i32, [_vp, _pq, _vp, _ps, _vp, _vp, _sz, _vp]),
     "qe_conv_f32_prepare": (_i32, [_pq, _vp, _ps, _vp, _sz, _vp]),
@@ -423,6 +432,19 @@ def quantconv2d_float_input(x, wq, bias, sh, out=None, stream=None, mfma=True):
 
 def float_input_path(sh, wq):
     return int(lib().qe_quantconv2d_float_input_path(ctypes.byref(sh), ctypes.byref(wq)))
+
+
+# qe_conv_f32_plan_info: the kernel instance by number (F32Kernel, qe_conv_plan.hpp)
+F32_KERNELS = ("Stem4x1x7", "Stem2x2x4", "Stem2x2x7", "M4x1x4", "M4x1x4S2", "M4x1x7", "M4x1x7S2", "M2x2x2", "M2x2x2S2",
+               "M2x2x4", "M2x2x4S2")
+
+
+def conv_f32_plan_info(sh):
+    """qe_conv_f32_plan_info (host-only): the plan of a float-input convolution as a QeConvF32Plan, with the QE_F32_MFMA
+    knob of the last reload_env().  ok == 0: the VALU kernel runs and the other fields say nothing."""
+    info = QeConvF32Plan()
+    check(lib().qe_conv_f32_plan_info(ctypes.byref(sh), ctypes.byref(info)))
+    return info
 
 
 def conv_f32_prepare(wq, bias, sh, stream=None):

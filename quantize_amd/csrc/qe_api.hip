@@ -407,6 +407,21 @@ extern "C" int qe_quantconv2d_float_input_path(const qe_conv_shape *shape, const
     return qe::plan_conv_f32(shape).ok ? 1 : 0;
 }
 
+// the plan of a float-input request, field by field (tests, bench, profiles): decides nothing
+extern "C" int qe_conv_f32_plan_info(const qe_conv_shape *shape, qe_conv_f32_plan *info)
+{
+    if (qe::check_shape(shape) != QE_OK || info == nullptr) return QE_ERR_ARG;
+    const qe::F32Plan p = qe::plan_conv_f32(shape);
+    qe_conv_f32_plan i{};
+    i.ok = p.ok; i.kernel = (int)p.kernel; i.stem = p.stem;
+    i.OCP = p.OCP; i.NG = p.NG; i.KK = p.KK; i.OH = p.OH; i.OW = p.OW; i.TH = p.TH; i.GI = p.GI;
+    i.IHT = p.IHT; i.IWP = p.IWP; i.ROWMUL = p.ROWMUL; i.COLMUL = p.COLMUL;
+    i.chunk = p.chunk; i.n_pix_tiles = p.n_pix_tiles; i.n_oc_tiles = p.n_oc_tiles; i.tiles_h = p.tiles_h;
+    i.blocks = p.blocks; i.lds = (int64_t)p.lds; i.ep_off = (int64_t)p.ep_off; i.total = (int64_t)p.total;
+    *info = i;
+    return QE_OK;
+}
+
 extern "C" size_t qe_quantconv2d_float_input_workspace_bytes(const qe_conv_shape *shape, int w_bits)
 {
     (void)w_bits;

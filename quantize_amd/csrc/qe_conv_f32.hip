@@ -552,6 +552,9 @@ __global__ __launch_bounds__(F32_THREADS, 2) void conv_f32_stem_kernel(const F32
     for (int t = 0; t < NIW; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
+    // kernel columns kw >= KW have zero weights, but the halo pixel there is a real one (it belongs to the next outputs'
+    // windows) and 0 x inf = 0 x NaN = NaN: such a pixel is kept out of the MFMA.  live[j][kwl]: column 4 j + 2 h + kwl < KW.
+    const bool live[2][2] = {{2 * h < a.KW, 2 * h + 1 < a.KW}, {4 + 2 * h < a.KW, 5 + 2 * h < a.KW}};
 #pragma unroll
     for (int kh = 0; kh < 8; ++kh) {
         if (kh < a.KH) {
@@ -564,7 +567,8 @@ __global__ __launch_bounds__(F32_THREADS, 2) void conv_f32_stem_kernel(const F32
 #pragma unroll
                     for (int sp = 2; sp >= 0; --sp) {                            // smallest parts first
                         const uint2 b0 = bp[sp * GSZ], b1 = bp[sp * GSZ + 1];
-                        const v4i b = {(int)b0.x, (int)b0.y, (int)b1.x, (int)b1.y};
+                        const v4i b = {live[j][0] ? (int)b0.x : 0, live[j][0] ? (int)b0.y : 0,
+                                       live[j][1] ? (int)b1.x : 0, live[j][1] ? (int)b1.y : 0};
                         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf, __builtin_bit_cast(v8bf, b), acc[t], 0, 0, 0);
                     }
                 }
@@ -686,7 +690,7 @@ F32Plan plan_conv_f32(const qe_conv_shape *sh)
         return p;
     }
     if (sh->IC < 8) return p;                                               // 5..7 channels stay on the VALU kernel
-    if ((int64_t)sh->IC * sh->H * sh->W * 8 >= (1ll << 31)) return p;       // 32-bit element offsets inside a tile's (<= 8) images
+    if ((int64_t)sh->IC * sh->H * sh->W * 8 >= (1ll << 31)) return p;       // 32-bit element offsets inside a tile of up to 8 images
     if ((int64_t)sh->OC * p.OH * p.OW >= (1ll << 29)) return p;
     // 3x3 on 7x7 maps: 64-channel workgroups (0.310 -> 0.247 ms on 512->512; every other layer is faster with 128)
     const bool w128 = wide && !(p.KK == 9 && sh->stride == 1 && p.OH * p.OW <= 64);
@@ -711,6 +715,9 @@ F32Plan plan_conv_f32(const qe_conv_shape *sh)
         if (p.GI > 1) { --p.GI; continue; }
         if (--TH < 1) return p;
     }
+    // ... and of more: the kernel forms gi * IC * H * W (u_off) in int and (gi * OC + oc) * OH * OW + pixel (voff) in uint32_t
+    // with gi < GI, and tiny planes take up to 128 images.  Such a shape stays on the VALU kernel.
+    if ((int64_t)p.GI * sh->IC * sh->H * sh->W >= (1ll << 31) || (int64_t)p.GI * sh->OC * p.OH * p.OW >= (1ll << 32)) return p;
     if (p.GI == 1 && p.TH >= 1) {                       // balanced row tiles
         const int nt = (p.OH + p.TH - 1) / p.TH;
         const int th2 = (p.OH + nt - 1) / nt;

@@ -84,3 +84,18 @@ def test_every_symbol_has_a_prototype():
     assert L.qe_conv_prepared_layout.restype is ctypes.c_uint64
     assert not [s for s in capi.SYMBOLS if s.startswith("qe_debug_")]
     assert all(hasattr(L, s) and s not in capi.SYMBOLS for s in capi.DEBUG_PROTOTYPES)
+
+
+def test_plan_structs_match_the_header():
+    """The ctypes views of the two plan structs list the header's fields in the header's order and types (a field added on
+    one side only would shift every later one)."""
+    text = open(os.path.join(REPO, "include", "quant_engine.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    ctype = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64}
+    for name, view in (("qe_conv_plan_info", capi.QeConvPlanInfo), ("qe_conv_f32_plan", capi.QeConvF32Plan)):
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, flags=re.S).group(1)
+        fields = [(f.strip(), ctype[ty]) for ty, names in re.findall(r"(int32_t|int64_t)\s+([^;]+);", body)
+                  for f in names.split(",")]
+        assert fields == list(view._fields_), name
+        assert ctypes.sizeof(view) == sum(ctypes.sizeof(t) for _, t in fields), name       # no padding on either side
+    assert "qe_conv_f32_plan_info" in capi.SYMBOLS and len(capi.F32_KERNELS) == 11
