@@ -489,6 +489,30 @@ int qe_attention_masked(const float *q, const float *k, const float *v, float *o
                         float scale, const float *mask, int64_t mask_sn, int64_t mask_sh, const float *key_bias,
                         int causal, qe_stream_t stream);
 
+/* qe_attention_bf16 -- qe_attention_masked with both products on the bf16 matrix cores (v_mfma_f32_32x32x16_bf16): an
+ * opt-in trade of the core's fp32 exactness for matrix-core rate.  Same parameters, same layouts, same operands and the
+ * same argument checks (QE_ERR_ARG before any device work); mask == NULL && key_bias == NULL && !causal is the unmasked
+ * instance.  q, k, v and out stay fp32 in memory and are read in place: no workspace, no host synchronisation.
+ * Numerics contract:
+ *  - q^ = bf16(fp32(q * scale)), k^ = bf16(k), v^ = bf16(v), each rounded to nearest even;
+ *  - scores are fp32 sums of exact bf16 products, plus the fp32 mask / key_bias (summed with each other first);
+ *  - the online softmax is qe_attention's, in fp32; p is rounded to bf16 only as the operand of P.V;
+ *  - the row sum l is the fp32 sum of the unrounded p; O is accumulated in fp32, one fp32 division by l at the end.
+ * Hence, against exact attention on q^, k^, v^ (scale 1), |out - ref| <= 2^-8 max|v^| (the rounding of p) plus qe_attention's
+ * own 1e-5 max|v|.  The distance to attention on the unrounded inputs grows with the scores: a score of size s moves by up
+ * to ~2^-8 s through the rounding of q and k.
+ * NaN and all-masked rows: as qe_attention_masked declares (a row with no visible key is NaN in that row of that head).
+ * Shapes: d % 16 == 0 and d <= 128 only.  Every other d returns QE_ERR_UNSUPPORTED: this entry point never runs the fp32
+ * kernels instead, and QE_ATTN does not affect it.
+ * qe_attention_bf16_path (host only): 2 = the bf16 MFMA kernel, -1 = no kernel (d % 16 != 0, d > 128 or a non-positive
+ * size), whatever the operands.                                                                                       */
+int qe_attention_bf16_path(int32_t L, int32_t S, int32_t H, int32_t d, int has_mask, int has_key_bias, int causal);
+int qe_attention_bf16(const float *q, const float *k, const float *v, float *out,
+                      int32_t N, int32_t L, int32_t S, int32_t H, int32_t d,
+                      int64_t q_rn, int64_t q_rt, int64_t kv_rn, int64_t kv_rt, int64_t o_rn, int64_t o_rt,
+                      float scale, const float *mask, int64_t mask_sn, int64_t mask_sh, const float *key_bias,
+                      int causal, qe_stream_t stream);
+
 /* ---- auxiliary (no counterpart in the reference's extension) ---------------------------------
  * Global average pool of an fp32 NCHW tensor: out[plane] = mean(x[plane][0..P)) for n_planes = N*C planes of P
  * contiguous floats.  The reference's models do this in PyTorch (torchvision ResNet: AdaptiveAvgPool2d); bench.py's

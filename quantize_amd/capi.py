@@ -121,6 +121,8 @@ PROTOTYPES = {
     "qe_attention": (_i32, _attn + [_vp]),
     "qe_attention_masked_path": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
     "qe_attention_masked": (_i32, _attn + [_vp, _i64, _i64, _vp, _i32, _vp]),
+    "qe_attention_bf16_path": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "qe_attention_bf16": (_i32, _attn + [_vp, _i64, _i64, _vp, _i32, _vp]),
 }
 SYMBOLS = sorted(PROTOTYPES)
 # exported by the library but absent from the header (not part of the public ABI): kept out of SYMBOLS
@@ -649,15 +651,28 @@ def attention_masked_path(L, S, H, d, has_mask=False, has_key_bias=False, causal
                                               int(bool(causal))))
 
 
+def attention_bf16_path(L, S, H, d, has_mask=False, has_key_bias=False, causal=False):
+    """qe_attention_bf16_path: 2 = the bf16 MFMA kernel, -1 = no kernel (d % 16 != 0, d > 128, a non-positive size)."""
+    return int(lib().qe_attention_bf16_path(int(L), int(S), int(H), int(d), int(bool(has_mask)), int(bool(has_key_bias)),
+                                            int(bool(causal))))
+
+
+PRECISIONS = ("fp32", "bf16")
+
+
 def attention(q, k, v, N, L, H, S=None, layout="token", scale=None, out=None, stream=None, mask=None, key_bias=None,
-              causal=False):
+              causal=False, precision="fp32"):
     """qe_attention: softmax(scale q k^T) v per (image, head) on fp32 rows of E = H d floats, read in place.
     layout "token": q / out are (N L, E) and k / v (N S, E) rows (a ViT's projections); "seq": (L N, E) and (S N, E)
     (nn.MultiheadAttention with batch_first=False).  S defaults to L, scale to d ** -0.5.  Returns out, shaped like q
     (a new tensor when out is None).  No host synchronisation.
     mask / key_bias / causal (qe_attention_masked): the score becomes scale q.k + mask + key_bias, keys s <= t only under
     causal (top-left aligned).  mask: contiguous fp32, additive (finite or -inf), of shape (L, S), (N, L, S), (N, H, L, S) or
-    (N*H, L, S); key_bias: contiguous fp32 (N, S).  A row with no visible key comes out NaN."""
+    (N*H, L, S); key_bias: contiguous fp32 (N, S).  A row with no visible key comes out NaN.
+    precision "bf16" (qe_attention_bf16): both products on the bf16 matrix cores, fp32 softmax and accumulation, the same
+    operands; d % 16 == 0 and d <= 128 only -- any other d raises QeError (unsupported), never the fp32 kernels instead."""
+    if precision not in PRECISIONS:
+        raise ValueError("precision must be 'fp32' or 'bf16'")
     import torch
     S = L if S is None else int(S)
     N, L, H = int(N), int(L), int(H)
@@ -676,7 +691,7 @@ def attention(q, k, v, N, L, H, S=None, layout="token", scale=None, out=None, st
         out = torch.empty_like(q)
     assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == q.numel()
     scale = float(d ** -0.5 if scale is None else scale)
-    if mask is None and key_bias is None and not causal:
+    if mask is None and key_bias is None and not causal and precision == "fp32":
         check(lib().qe_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), N, L, S, H, d, q_rn, q_rt, kv_rn,
                                  kv_rt, q_rn, q_rt, scale, _stream(stream)))
         return out
@@ -697,7 +712,7 @@ def attention(q, k, v, N, L, H, S=None, layout="token", scale=None, out=None, st
         if not (torch.is_tensor(key_bias) and key_bias.is_cuda and key_bias.is_contiguous()
                 and key_bias.dtype == torch.float32 and tuple(key_bias.shape) == (N, S)):
             raise ValueError("key_bias must be a contiguous fp32 CUDA tensor of shape (N, S)")
-    check(lib().qe_attention_masked(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), N, L, S, H, d, q_rn, q_rt, kv_rn,
-                                    kv_rt, q_rn, q_rt, scale, _ptr(mask), mask_sn, mask_sh, _ptr(key_bias), 1 if causal else 0,
-                                    _stream(stream)))
+    run = lib().qe_attention_bf16 if precision == "bf16" else lib().qe_attention_masked
+    check(run(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), N, L, S, H, d, q_rn, q_rt, kv_rn, kv_rt, q_rn, q_rt, scale,
+              _ptr(mask), mask_sn, mask_sh, _ptr(key_bias), 1 if causal else 0, _stream(stream)))
     return out

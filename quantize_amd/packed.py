@@ -338,28 +338,32 @@ class PackedMultiheadAttention:
                  key_padding_mask=None, is_causal=False):
         """attention="torch": the core as torch bmm / softmax / bmm (the reference's own arithmetic).  "engine": the fp32
         qe_attention kernel reads the three projections in their (L N, E) / (S N, E) layout and writes the context in
-        place for out_proj -- no score matrix, so need_weights must be False.
+        place for out_proj -- no score matrix, so need_weights must be False.  "engine_bf16": the same through
+        qe_attention_bf16 (both products on the bf16 matrix cores; head sizes d % 16 == 0, d <= 128 only, no fallback).
         attn_mask ((L, S) or (N*H, L, S)) and key_padding_mask ((N, S)) follow nn.MultiheadAttention: bool (True = not
         allowed / ignored key) or float (added to the scores).  is_causal=True without attn_mask is the top-left aligned
         tril mask.  The engine core takes attn_mask with its broadcast strides and key_padding_mask as a key bias row:
         no merged (N, H, L, S) tensor.  A row with no visible key is NaN in both cores."""
-        if attention not in ("torch", "engine"):
-            raise ValueError("attention must be 'torch' or 'engine'")
+        if attention not in ("torch", "engine", "engine_bf16"):
+            raise ValueError("attention must be 'torch', 'engine' or 'engine_bf16'")
         L, N, E = query.shape
         S = key.shape[0]
         H, d = self.num_heads, E // self.num_heads
         masked = attn_mask is not None or key_padding_mask is not None or is_causal
         if masked:
             attn_mask, key_padding_mask = self._additive_masks(attn_mask, key_padding_mask, N, H, L, S)
-        if attention == "engine":
+        if attention != "torch":
             if need_weights:
-                raise ValueError("attention='engine' materialises no attention weights: pass need_weights=False")
+                raise ValueError("attention='%s' materialises no attention weights: pass need_weights=False" % attention)
+            precision = "bf16" if attention == "engine_bf16" else "fp32"
+            if precision == "bf16" and capi.attention_bf16_path(L, S, H, d) < 0:
+                raise ValueError("attention='engine_bf16' takes head sizes d %% 16 == 0, d <= 128; got d = %d" % d)
             Q, K, V = (p(x, route).reshape(-1, E).contiguous() for p, x in ((self.q, query), (self.k, key), (self.v, value)))
             if masked:
                 ctx = capi.attention(Q, K, V, N, L, H, S=S, layout="seq", mask=attn_mask, key_bias=key_padding_mask,
-                                     causal=bool(is_causal) and attn_mask is None)
+                                     causal=bool(is_causal) and attn_mask is None, precision=precision)
             else:
-                ctx = capi.attention(Q, K, V, N, L, H, S=S, layout="seq")
+                ctx = capi.attention(Q, K, V, N, L, H, S=S, layout="seq", precision=precision)
             out = quantlinear_forward(ctx, (self.out_weight, self.out_des, self.out_scale, self._neg_out_zero), self.out_bias)
             return out.reshape(L, N, E), None
         Q = self.q(query, route).reshape(L, N * H, d).transpose(0, 1)      # (N H, L, d), as F.multi_head_attention_forward splits heads

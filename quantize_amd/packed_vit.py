@@ -17,7 +17,8 @@ PackedViT takes the state_dict of such a model after pack() and runs it two ways
 
 Both routes call the same attention core, _attention: by default fp32 F.scaled_dot_product_attention on (N, H, L, d) --
 what F.multi_head_attention_forward runs for need_weights=False; with attention="engine" the fp32 qe_attention kernel,
-which reads the three projections in their (N L, E) buffers and writes the context straight into out_proj's input.
+which reads the three projections in their (N L, E) buffers and writes the context straight into out_proj's input; with
+attention="engine_bf16" the same, its two products on the bf16 matrix cores (qe_attention_bf16: not fp32-exact).
 The C entry points take their two-pass form wherever the fused form is not eligible (sub-8-bit or per-channel consumer codes, non-MFMA shapes, QE_LIN_EPI=0), so every step of
 the fused route exists for every model the layers route runs.  With check=False the fused route makes no device -> host
 copy or synchronisation: every range flag accumulates in one device int32, read once at the end when check=True.
@@ -33,18 +34,20 @@ from .packed import OUT_OF_RANGE, PackedConv2d, PackedLinear, PackedMultiheadAtt
 from .packed_resnet import pack_codes
 
 
-ATTENTION = ("torch", "engine")
+ATTENTION = ("torch", "engine", "engine_bf16")
 
 
 def _check_attention(attention):
     if attention not in ATTENTION:
-        raise ValueError("attention must be 'torch' or 'engine'")
+        raise ValueError("attention must be 'torch', 'engine' or 'engine_bf16'")
 
 
 def _attention(Q, K, V, N, L, H, attention="torch"):
     """(N L, E) fp32 projections -> (N L, E) context: softmax(Q K^T / sqrt(d)) V per head, fp32."""
     if attention == "engine":
         return capi.attention(Q, K, V, N, L, H)
+    if attention == "engine_bf16":
+        return capi.attention(Q, K, V, N, L, H, precision="bf16")
     E = Q.shape[-1]
     d = E // H
     q, k, v = (t.reshape(N, L, H, d).transpose(1, 2) for t in (Q, K, V))
@@ -136,7 +139,7 @@ class PackedViT:
 
     def forward(self, images, route="fused", check=True, keep_blocks=False, attention="torch"):
         """(logits, [block outputs (N, L, E)] if keep_blocks else None).  attention: "torch" (F.scaled_dot_product_attention)
-        or "engine" (the qe_attention kernel), in either route."""
+        "engine" (the fp32 qe_attention kernel) or "engine_bf16" (qe_attention_bf16), in either route."""
         if route not in ("fused", "layers"):
             raise ValueError("route must be 'fused' or 'layers'")
         _check_attention(attention)

@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
-"""The fp32 attention core alone: qe_attention (the engine) against torch's F.scaled_dot_product_attention on the same
-(N L, E) projection buffers -- the engine reads them in place, torch gets the (N, H, L, d) views the ViT's _attention
-passes it.  The two alternate step by step, timed with device events after a warm-up; medians are reported.
+"""The attention core alone: qe_attention (the fp32 engine kernel) and qe_attention_bf16 (its bf16 matrix-core form,
+precision="bf16") against torch's F.scaled_dot_product_attention on the same (N L, E) fp32 projection buffers -- the engine
+reads them in place, torch gets the (N, H, L, d) views the ViT's _attention passes it.  They alternate step by step, timed
+with device events after a warm-up; medians are reported.  For orientation a fourth column times torch's own bf16 SDPA on
+inputs cast to bf16 beforehand (`torch_bf16_precast`): it reads half the bytes the other three read and writes bf16.
 Useful TFLOP/s counts 4 N H L S d (QK^T and PV, padding not counted); `of_peak` is the share of the 157.3 TFLOP/s fp32
-matrix-pipe peak.  Prints one JSON line.
+matrix-pipe peak, given for the two fp32 columns only.  Prints one JSON line (`metric` keeps its name, attention_core_fp32:
+the buffers are fp32 in every column but the pre-cast one).
 --mask gives both the same mask: `causal` (the engine's flag, torch's is_causal), `causal-additive` (the -inf tril as an
 (L, L) float mask), `additive2d` (a finite (L, L) float mask), `padding` (ragged key padding: the engine reads an (N, L) key
 bias, torch the merged (N, 1, 1, L) mask it would build itself).  The FLOP count stays the unmasked one, so a causal row's
@@ -35,17 +38,19 @@ def main():
     from quantize_amd import capi
 
     dev = "cuda:0"
-    res = {"metric": "attention_core_fp32", "unit": "ms", "peak_tflops": PEAK_TF, "mask": args.mask, "path": {},
+    res = {"metric": "attention_core_fp32", "unit": "ms", "peak_tflops": PEAK_TF, "mask": args.mask, "path": {}, "bf16_path": {},
            "shapes": {}}
     for name in args.shapes:
         L, H, d = SHAPES[name]
         res["path"][name] = capi.attention_path(L, L, H, d)
+        res["bf16_path"][name] = capi.attention_bf16_path(L, L, H, d)
         for N in args.batches:
             E = H * d
             g = torch.Generator(device="cpu").manual_seed(N + L)
             q, k, v = (torch.randn(N * L, E, generator=g).to(dev) for _ in range(3))
             out = torch.empty_like(q)
             views = [t.view(N, L, H, d).transpose(1, 2) for t in (q, k, v)]
+            views16 = [t.to(torch.bfloat16) for t in views]             # cast once, outside the timed region
             ekw, tkw = {}, {}
             if args.mask == "causal":
                 ekw, tkw = dict(causal=True), dict(is_causal=True)
@@ -59,14 +64,20 @@ def main():
                 lengths = torch.randint(L // 2, L + 1, (N,), generator=g)
                 kb = torch.zeros(N, L).masked_fill_(torch.arange(L)[None, :] >= lengths[:, None], float("-inf")).to(dev)
                 ekw, tkw = dict(key_bias=kb), dict(attn_mask=kb.view(N, 1, 1, L))
-            times = {"engine": [], "torch": []}
+            out16 = torch.empty_like(q)
+            tkw16 = {n: (m.to(torch.bfloat16) if torch.is_tensor(m) else m) for n, m in tkw.items()}
+            times = {"engine": [], "bf16": [], "torch": [], "torch_bf16_precast": []}
             with torch.no_grad():
                 for i in range(args.warmup + args.steps):
-                    for who in ("engine", "torch"):
+                    for who in times:
                         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                         a.record()
                         if who == "engine":
                             capi.attention(q, k, v, N, L, H, out=out, **ekw)
+                        elif who == "bf16":
+                            capi.attention(q, k, v, N, L, H, out=out16, precision="bf16", **ekw)
+                        elif who == "torch_bf16_precast":
+                            F.scaled_dot_product_attention(*views16, **tkw16)
                         else:
                             ref = F.scaled_dot_product_attention(*views, **tkw)
                         b.record()
@@ -75,15 +86,18 @@ def main():
                             times[who].append(a.elapsed_time(b))
                 diff = float((out.view(N, L, H, d).transpose(1, 2) - ref).abs().max())
             flop = 4.0 * N * H * L * L * d
-            row = {"N": N, "L": L, "H": H, "d": d, "max_abs_engine_minus_torch": diff}
+            row = {"N": N, "L": L, "H": H, "d": d, "max_abs_engine_minus_torch": diff,
+                   "max_abs_bf16_minus_torch": float((out16.view(N, L, H, d).transpose(1, 2) - ref).abs().max())}
             for who, t in times.items():
                 ms = sorted(t)[len(t) // 2]
                 row[who + "_ms"] = ms
                 row[who + "_tflops"] = flop / (ms * 1e-3) / 1e12
-                row[who + "_of_peak"] = row[who + "_tflops"] / PEAK_TF
+                if who in ("engine", "torch"):              # the fp32 matrix-pipe peak is no yardstick for the bf16 columns
+                    row[who + "_of_peak"] = row[who + "_tflops"] / PEAK_TF
             row["speedup"] = row["torch_ms"] / row["engine_ms"]
+            row["bf16_speedup_over_engine"] = row["engine_ms"] / row["bf16_ms"]
             res["shapes"]["%s_N%d" % (name, N)] = row
-            del q, k, v, out, views, ref
+            del q, k, v, out, out16, views, views16, ref
             torch.cuda.empty_cache()
     print(json.dumps(res))
 

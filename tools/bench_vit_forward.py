@@ -7,9 +7,10 @@ alternating, with device events, at each batch size; print one JSON line.
                   the patch embedding as a GEMM on the matrix cores, no host synchronisation (check=False).
 
 The HBM bytes reported are ALGORITHMIC (the byte model below, per token row outside the attention core and the GEMM
-operands both routes share), not counters.  --attention torch engine also times both routes with the engine's attention
-core (keys fused_engine_ms, layers_engine_ms, ...); the default, torch, keeps the output as it was.
-usage: python tools/bench_vit_forward.py [--batches 64 256] [--steps 10] [--warmup 2] [--attention torch [engine]]"""
+operands both routes share), not counters.  --attention torch engine engine_bf16 also times both routes with the engine's
+fp32 and bf16 attention cores (keys fused_engine_ms, layers_engine_bf16_ms, ...); the default, torch, keeps the output as
+it was.
+usage: python tools/bench_vit_forward.py [--batches 64 256] [--steps 10] [--warmup 2] [--attention torch [engine] [engine_bf16]]"""
 import argparse
 import json
 import os
@@ -35,7 +36,7 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[64, 256])
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--attention", nargs="+", choices=["torch", "engine"], default=["torch"])
+    ap.add_argument("--attention", nargs="+", choices=["torch", "engine", "engine_bf16"], default=["torch"])
     args = ap.parse_args()
     import torch
     from quantize_amd.packed_vit import CONFIGS, PackedViT, calibrated_state_dict
