@@ -19,32 +19,16 @@
 // scores are fp32 sums of exact bf16 products plus the fp32 mask / bias (summed first); p in fp32, rounded to bf16 only as
 // the operand of P.V; l the fp32 sum of the unrounded p; O accumulated in fp32, one fp32 division at the end.
 //
-// The argument struct, the mode bits and the argument checks restate qe_attention.hip's: that translation unit stays as it
-// is (its 144 instances compile to the same code), so nothing is shared through a header.
-#include "qe_common.h"
-
-#include <algorithm>
+// The argument struct, the MODE bits, the argument checks, the mode and head-size switches and the launch geometry are
+// qe_attention_common.hpp's, shared with the fp32 core.  The kernel's prologue, K-row load, accumulator zeroing, online
+// softmax and store are attn_mfma_kernel's text, written out here as well (marked below): a device helper for any of them
+// changed some instance's code in one of the two units.
+#include "qe_attention_common.hpp"
 
 namespace qe {
 
-struct AttnBf16Args {
-    const float *q, *k, *v;
-    float *out;
-    int64_t q_rn, q_rt, kv_rn, kv_rt, o_rn, o_rt;    // in rows of H*d floats
-    int N, L, S, H, d;
-    int qgroups;                                     // workgroups per (image, head)
-    float scale;
-    const float *mask, *key_bias;                    // masked instances only (MODE != 0)
-    int64_t mask_sn, mask_sh;                        // element strides of the (L, S) mask block per image / head
-};
-
 namespace {
 
-enum : int { kMask = 1, kBias = 2, kCausal = 4, kVec4 = 8 };    // as qe_attention.hip
-
-constexpr float kLog2e = 1.4426950408889634f;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // eight fp32 -> one MFMA fragment, round to nearest even (v_cvt_pk_bf16_f32)
@@ -59,14 +43,15 @@ __device__ __forceinline__ bf16x8 pack8(float x0, float x1, float x2, float x3, 
 }  // namespace
 
 template <int D, int MODE = 0>
-__global__ __launch_bounds__(D <= 64 ? 512 : 256) void attn_bf16_kernel(const AttnBf16Args a)
+__global__ __launch_bounds__(64 * attn_wpb(D)) void attn_bf16_kernel(const AttnArgs a)
 {
     constexpr bool MASK = (MODE & kMask) != 0, BIAS = (MODE & kBias) != 0, CAUSAL = (MODE & kCausal) != 0;
     constexpr bool VEC4 = (MODE & kVec4) != 0;
     constexpr int HALF = D / 2;                 // dims [h*HALF, h*HALF + HALF) on lane half h
     constexpr int KS = D / 16;                  // k-steps of S^T: step s takes elements 8s .. 8s+7 of the lane's run
     constexpr int NB = (D + 31) / 32;           // 32-column blocks of O^T
-    constexpr int WPB = D <= 64 ? 8 : 4;
+    constexpr int WPB = attn_wpb(D);
+    // this block / wave / lane decode is also attn_mfma_kernel's
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int lo = lane & 31, hi = lane >> 5;
@@ -141,7 +126,7 @@ __global__ __launch_bounds__(D <= 64 ? 512 : 256) void attn_bf16_kernel(const At
     float kr[HALF];
     auto load_k = [&](int k0) {
         if constexpr (MASK || BIAS) load_add(k0);
-        const int key = k0 + lo;
+        const int key = k0 + lo;                    // this K-row load is also attn_mfma_kernel's
         if (key < a.S) {
             const float4 *src = reinterpret_cast<const float4 *>(kbase + key * kv_step + hi * HALF);
 #pragma unroll
@@ -155,7 +140,7 @@ __global__ __launch_bounds__(D <= 64 ? 512 : 256) void attn_bf16_kernel(const At
         }
     };
 
-    f32x16 o[NB];
+    f32x16 o[NB];                               // zeroed as in attn_mfma_kernel
 #pragma unroll
     for (int b = 0; b < NB; ++b)
 #pragma unroll
@@ -194,7 +179,7 @@ __global__ __launch_bounds__(D <= 64 ? 512 : 256) void attn_bf16_kernel(const At
         }
         if (k0 + 32 < kend) load_k(k0 + 32);
 
-        // online softmax over this tile's 32 keys of query q0 + lo
+        // online softmax over this tile's 32 keys of query q0 + lo; also attn_mfma_kernel's
         float tmax = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -240,7 +225,7 @@ __global__ __launch_bounds__(D <= 64 ? 512 : 256) void attn_bf16_kernel(const At
     const int t = q0 + lo;
     const float l = lsum + __shfl_xor(lsum, 32);
     if (t >= a.L) return;
-    float *dst = a.out + (n * a.o_rn + t * a.o_rt) * E + col;
+    float *dst = a.out + (n * a.o_rn + t * a.o_rt) * E + col;      // from the row-sum exchange on, also attn_mfma_kernel's
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
 #pragma unroll
@@ -261,107 +246,22 @@ static int attn_bf16_path(int L, int S, int H, int d)
     return 2;
 }
 
-template <int D, int MODE>
-static void launch_bf16(const AttnBf16Args &a, hipStream_t s)
-{
-    constexpr int WPB = D <= 64 ? 8 : 4;
-    AttnBf16Args b = a;
-    const int tiles = ceil_div(a.L, 32);
-    const int wpb = std::min(WPB, tiles);        // a short sequence launches only the waves it has rows for
-    b.qgroups = ceil_div(tiles, WPB);
-    const int64_t blocks = (int64_t)b.qgroups * a.H * a.N;
-    hipLaunchKernelGGL((attn_bf16_kernel<D, MODE>), dim3((unsigned)blocks), dim3(64 * (b.qgroups == 1 ? wpb : WPB)), 0, s, b);
-}
+struct AttnBf16 {
+    template <int D, int MODE> static constexpr auto kernel = &attn_bf16_kernel<D, MODE>;
+};
 
-template <int MODE>
-static void launch_bf16_mode(const AttnBf16Args &a, hipStream_t s)
-{
-    switch (a.d) {
-    case 16: launch_bf16<16, MODE>(a, s); break;
-    case 32: launch_bf16<32, MODE>(a, s); break;
-    case 48: launch_bf16<48, MODE>(a, s); break;
-    case 64: launch_bf16<64, MODE>(a, s); break;
-    case 80: launch_bf16<80, MODE>(a, s); break;
-    case 96: launch_bf16<96, MODE>(a, s); break;
-    case 112: launch_bf16<112, MODE>(a, s); break;
-    default: launch_bf16<128, MODE>(a, s); break;
-    }
-}
-
-// [lo, hi) byte range the rows of (n < N, t < T) span
-static void row_span(const float *p, int N, int T, int64_t rn, int64_t rt, int64_t E, uintptr_t &lo, uintptr_t &hi)
-{
-    const int64_t last = (int64_t)(N - 1) * rn + (int64_t)(T - 1) * rt;
-    lo = reinterpret_cast<uintptr_t>(p);
-    hi = lo + (uintptr_t)((last + 1) * E) * sizeof(float);
-}
-
-// qe_attention_masked's checks, in its order (attn_run of qe_attention.hip), then the bf16 kernel's instance
 static int attn_bf16_run(const float *q, const float *k, const float *v, float *out, int32_t N, int32_t L, int32_t S, int32_t H,
                          int32_t d, int64_t q_rn, int64_t q_rt, int64_t kv_rn, int64_t kv_rt, int64_t o_rn, int64_t o_rt,
                          float scale, const float *mask, int64_t mask_sn, int64_t mask_sh, const float *key_bias, int causal,
                          qe_stream_t stream)
 {
-    if (N <= 0 || L <= 0 || S <= 0 || H <= 0 || d <= 0) return QE_ERR_ARG;
-    if (q_rn < 0 || q_rt < 0 || kv_rn < 0 || kv_rt < 0 || o_rn < 0 || o_rt < 0) return QE_ERR_ARG;
-    if (q == nullptr || k == nullptr || v == nullptr || out == nullptr) return QE_ERR_ARG;
-    if (((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) |
-          reinterpret_cast<uintptr_t>(out)) & 15) != 0)
-        return QE_ERR_ARG;
-    if (mask_sn < 0 || mask_sh < 0) return QE_ERR_ARG;
-    if (mask == nullptr && (mask_sn != 0 || mask_sh != 0)) return QE_ERR_ARG;
-    if (((reinterpret_cast<uintptr_t>(mask) | reinterpret_cast<uintptr_t>(key_bias)) & 15) != 0) return QE_ERR_ARG;
-    if (attn_bf16_path(L, S, H, d) < 0) return QE_ERR_UNSUPPORTED;      // never the fp32 kernels instead
-    const int64_t E = (int64_t)H * d;
-    uintptr_t olo, ohi;
-    row_span(out, N, L, o_rn, o_rt, E, olo, ohi);
-    const float *ins[3] = {q, k, v};
-    const int64_t rn[3] = {q_rn, kv_rn, kv_rn}, rt[3] = {q_rt, kv_rt, kv_rt};
-    const int len[3] = {L, S, S};
-    for (int i = 0; i < 3; ++i) {
-        uintptr_t lo, hi;
-        row_span(ins[i], N, len[i], rn[i], rt[i], E, lo, hi);
-        if (lo < ohi && olo < hi) return QE_ERR_ARG;
-    }
-    if (mask != nullptr) {                       // the (L, S) blocks of (n < N, h < H) span up to this many floats
-        const uintptr_t lo = reinterpret_cast<uintptr_t>(mask);
-        const uintptr_t hi = lo + (uintptr_t)((N - 1) * mask_sn + (H - 1) * mask_sh + (int64_t)L * S) * sizeof(float);
-        if (lo < ohi && olo < hi) return QE_ERR_ARG;
-    }
-    if (key_bias != nullptr) {
-        const uintptr_t lo = reinterpret_cast<uintptr_t>(key_bias);
-        const uintptr_t hi = lo + (uintptr_t)((int64_t)N * S) * sizeof(float);
-        if (lo < ohi && olo < hi) return QE_ERR_ARG;
-    }
-    // the second limit is the fp32 VALU kernel's grid: kept so that both entry points answer every argument list alike
-    // (tests/test_attention_bf16_cpu.py compares them)
-    if ((int64_t)N * H * ceil_div(L, 32) > 0x7fffffffLL || ceil_div64((int64_t)N * H * L, 4) > 0x7fffffffLL)
-        return QE_ERR_UNSUPPORTED;
-    AttnBf16Args a = {};
-    a.q = q; a.k = k; a.v = v; a.out = out;
-    a.q_rn = q_rn; a.q_rt = q_rt; a.kv_rn = kv_rn; a.kv_rt = kv_rt; a.o_rn = o_rn; a.o_rt = o_rt;
-    a.N = N; a.L = L; a.S = S; a.H = H; a.d = d; a.scale = scale;
-    a.mask = mask; a.key_bias = key_bias; a.mask_sn = mask_sn; a.mask_sh = mask_sh;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int mode = (mask != nullptr ? kMask : 0) | (key_bias != nullptr ? kBias : 0) | (causal ? kCausal : 0);
-    // every run of four keys a lane reads starts at a multiple of four floats from a 16-byte aligned base
-    if ((mode & (kMask | kBias)) != 0 && S % 4 == 0 && mask_sn % 4 == 0 && mask_sh % 4 == 0) mode |= kVec4;
-    switch (mode) {
-    case 0: launch_bf16_mode<0>(a, s); break;
-    case kMask: launch_bf16_mode<kMask>(a, s); break;
-    case kBias: launch_bf16_mode<kBias>(a, s); break;
-    case kMask | kBias: launch_bf16_mode<kMask | kBias>(a, s); break;
-    case kCausal: launch_bf16_mode<kCausal>(a, s); break;
-    case kCausal | kMask: launch_bf16_mode<kCausal | kMask>(a, s); break;
-    case kCausal | kBias: launch_bf16_mode<kCausal | kBias>(a, s); break;
-    case kCausal | kMask | kBias: launch_bf16_mode<kCausal | kMask | kBias>(a, s); break;
-    case kVec4 | kMask: launch_bf16_mode<kVec4 | kMask>(a, s); break;
-    case kVec4 | kBias: launch_bf16_mode<kVec4 | kBias>(a, s); break;
-    case kVec4 | kMask | kBias: launch_bf16_mode<kVec4 | kMask | kBias>(a, s); break;
-    case kVec4 | kCausal | kMask: launch_bf16_mode<kVec4 | kCausal | kMask>(a, s); break;
-    case kVec4 | kCausal | kBias: launch_bf16_mode<kVec4 | kCausal | kBias>(a, s); break;
-    default: launch_bf16_mode<kVec4 | kCausal | kMask | kBias>(a, s); break;
-    }
+    AttnArgs a;
+    int mode;
+    // a head size without a bf16 instance is refused here: never the fp32 kernels instead
+    if (const int e = attn_prepare(q, k, v, out, N, L, S, H, d, q_rn, q_rt, kv_rn, kv_rt, o_rn, o_rt, scale, mask, mask_sn,
+                                   mask_sh, key_bias, causal, attn_bf16_path(L, S, H, d), a, mode))
+        return e;
+    attn_dispatch_mode(mode, [&](auto m) { attn_launch_rows32<AttnBf16, decltype(m)::value>(a, static_cast<hipStream_t>(stream)); });
     QE_LAUNCH_CHECK();
     return QE_OK;
 }

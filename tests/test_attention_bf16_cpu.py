@@ -148,9 +148,9 @@ def test_exact_cases_are_exact_in_the_emulation(d, bias):
 
 
 def test_bad_arguments_get_the_fp32_entry_points_answer():
-    """qe_attention_bf16 restates qe_attention_masked's argument checks (its translation unit is not shared): for every
-    argument list that is refused before any device work, both return the same code.  Pointers are plain integers here;
-    nothing is launched, so no GPU is needed."""
+    """qe_attention_bf16 and qe_attention_masked make their argument checks in one function (attn_prepare of
+    qe_attention_common.hpp), each with its own path function's answer: for every argument list that is refused before any
+    device work, both return the same code.  Pointers are plain integers here; nothing is launched, so no GPU is needed."""
     L_ = capi.lib()
     A, FAR = 1 << 20, 1 << 44                 # 16-byte aligned, far enough apart for any span below
     ARG, UNSUPPORTED = 4, capi.QE_ERR_UNSUPPORTED

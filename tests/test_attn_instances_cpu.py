@@ -53,11 +53,19 @@ def test_instance_restates_the_dispatch():
 
 
 def test_kernel_names_match_the_source():
-    src = open(os.path.join(REPO, "quantize_amd", "csrc", "qe_attention.hip")).read()
-    assert re.search(r"attn_mfma_kernel<D, MODE>", src) and re.search(r"attn_valu_kernel<NO, MODE>", src)
-    assert re.search(r"enum : int \{ kMask = 1, kBias = 2, kCausal = 4, kVec4 = 8 \}", src)
+    """The mode bits and the head sizes of the Python table have their counterpart in the one place the source keeps each:
+    the enum and the head-size switch of qe_attention_common.hpp, which both units launch their 32-row kernel through."""
+    read = lambda name: open(os.path.join(REPO, "quantize_amd", "csrc", name)).read()
+    common, fp32, bf16 = read("qe_attention_common.hpp"), read("qe_attention.hip"), read("qe_attention_bf16.hip")
+    assert re.search(r"enum : int \{ kMask = 1, kBias = 2, kCausal = 4, kVec4 = 8 \}", common)
     for D in ai.MFMA_D:
-        assert "launch_mfma<%d, MODE>" % D in src
+        assert "attn_launch_d<CORE, %d, MODE>" % D in common
+    assert "launch_instance<CORE::template kernel<D, MODE>>" in common
+    assert re.search(r"kernel = &attn_mfma_kernel<D, MODE>", fp32) and re.search(r"attn_valu_kernel<NO, MODE>", fp32)
+    assert re.search(r"kernel = &attn_bf16_kernel<D, MODE>", bf16)
+    for src, core in ((fp32, "AttnMfma"), (bf16, "AttnBf16")):
+        assert '#include "qe_attention_common.hpp"' in src and "attn_launch_rows32<%s, " % core in src
+        assert "attn_dispatch_mode(mode" in src and "enum" not in src      # no mode bits or mode switch of its own
     assert ai.kernel_name((ai.MFMA, 112, 13)) == "attn_mfma_kernel<112, 13>"
     assert ai.kernel_name((ai.VALU, 4, 0)) == "attn_valu_kernel<4, 0>"
 
