@@ -402,6 +402,23 @@ int qe_quantlinear_float_input_residual(const float *x, const qe_qparam *w, cons
                                         const float *residual, float *out, void *workspace, size_t workspace_bytes,
                                         qe_stream_t stream);
 
+/* qe_quantlinear_bf16 -- qe_quantlinear with a bf16 result, for a consumer that would round it anyway (the q / k / v
+ * projections in front of qe_attention_bf16_stored):
+ *   out[b, o] = bf16( y[b, o] * post_scale ),   y = qe_quantlinear(x, w, bias, B, K, O)      (B x O row-major bf16 bit patterns)
+ * y is the fp32 value qe_quantlinear computes for the same problem, bit for bit; the product is one fp32 multiply and the
+ * rounding is to nearest even (a NaN stays a NaN, an overflow becomes inf), so post_scale == 1.0f is the plain rounding of
+ * y and out equals (qe_quantlinear(...) * post_scale) rounded elementwise.  x, w, bias, B, K, O and their checks as
+ * qe_quantlinear_residual; out NULL or not 2-byte aligned is QE_ERR_ARG.
+ * _path: 1 = the int8 MFMA kernel rounds and stores the bf16 rows itself (qe_quantlinear_path == 1, O % 8 == 0, out 16-byte
+ *        aligned -- so every O % 64 == 0 with an aligned out -- and QE_LIN_EPI not 0); 0 = qe_quantlinear into the
+ *        workspace, then one elementwise pass with the same multiply and rounding.  `out` (NULL reads as aligned) is only
+ *        looked at for its alignment.  workspace: _workspace_bytes() bytes (0 on path 1), 16-byte aligned.            */
+int qe_quantlinear_bf16_path(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O, const uint16_t *out);
+size_t qe_quantlinear_bf16_workspace_bytes(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O,
+                                           const uint16_t *out);
+int qe_quantlinear_bf16(const qe_qparam *x, const qe_qparam *w, const float *bias, int64_t B, int32_t K, int32_t O,
+                        float post_scale, uint16_t *out, void *workspace, size_t workspace_bytes, qe_stream_t stream);
+
 /* qe_layernorm_quantize_pack -- torch's F.layer_norm over the last dimension of fp32 rows (rows x E, contiguous) and the
  * codes of up to 3 consumer quantisers of the result (q / k / v projections: each its own), reading each row once.
  *   ln = (x - mean) * rstd * gamma + beta, mean = sum(x) / E, var = sum((x - mean)^2) / E (centred: not E[x^2] - mean^2),
@@ -512,6 +529,24 @@ int qe_attention_bf16(const float *q, const float *k, const float *v, float *out
                       int64_t q_rn, int64_t q_rt, int64_t kv_rn, int64_t kv_rt, int64_t o_rn, int64_t o_rt,
                       float scale, const float *mask, int64_t mask_sn, int64_t mask_sh, const float *key_bias,
                       int causal, qe_stream_t stream);
+
+/* qe_attention_bf16_stored -- qe_attention_bf16 on q, k, v that are bf16 in memory: rows of H*d bf16 elements (bit
+ * patterns, 2 bytes each) with the same row strides q_rn, q_rt, kv_rn, kv_rt (in rows), read in place.  out, mask and
+ * key_bias stay fp32, every other parameter and every operand is qe_attention_bf16's; the argument checks are the same ones
+ * in the same order, the alignment (16 bytes) and the overlap of q / k / v with out taken on 2-byte elements.
+ * Numerics contract: q^ = bf16(fp32(q) * scale) (one fp32 multiply, round to nearest even; scale == 1.0f uses the stored q
+ * as it is), k^ = k, v^ = v; everything after that is qe_attention_bf16's contract word for word.  On q, k, v that hold
+ * bf16 values, qe_attention_bf16 on them as fp32 and this entry point on them as bf16 give the same bits.
+ * K rows reach the matrix cores as loaded (16-byte loads), V elements as 2-byte loads: half the bytes of the fp32 rows and
+ * no conversion in the key loop.
+ * Shapes: d % 16 == 0 and d <= 128 only; every other d returns QE_ERR_UNSUPPORTED and nothing else runs instead.
+ * qe_attention_bf16_stored_path (host only): 2 = the bf16 MFMA kernel, -1 = no kernel, as qe_attention_bf16_path.   */
+int qe_attention_bf16_stored_path(int32_t L, int32_t S, int32_t H, int32_t d, int has_mask, int has_key_bias, int causal);
+int qe_attention_bf16_stored(const uint16_t *q, const uint16_t *k, const uint16_t *v, float *out,
+                             int32_t N, int32_t L, int32_t S, int32_t H, int32_t d,
+                             int64_t q_rn, int64_t q_rt, int64_t kv_rn, int64_t kv_rt, int64_t o_rn, int64_t o_rt,
+                             float scale, const float *mask, int64_t mask_sn, int64_t mask_sh, const float *key_bias,
+                             int causal, qe_stream_t stream);
 
 /* ---- auxiliary (no counterpart in the reference's extension) ---------------------------------
  * Global average pool of an fp32 NCHW tensor: out[plane] = mean(x[plane][0..P)) for n_planes = N*C planes of P

@@ -114,6 +114,9 @@ PROTOTYPES = {
     "qe_quantlinear_float_input_residual_path": (_i32, [_vp, _pq, _i64, _i32, _i32]),
     "qe_quantlinear_float_input_residual_workspace_bytes": (_sz, [_vp, _pq, _i64, _i32, _i32]),
     "qe_quantlinear_float_input_residual": (_i32, [_vp, _pq, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "qe_quantlinear_bf16_path": (_i32, [_pq, _pq, _i64, _i32, _i32, _vp]),
+    "qe_quantlinear_bf16_workspace_bytes": (_sz, [_pq, _pq, _i64, _i32, _i32, _vp]),
+    "qe_quantlinear_bf16": (_i32, [_pq, _pq, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _sz, _vp]),
     "qe_layernorm_quantize_pack_path": (_i32, [_i64, _i32, _i32, _pr, _ppc]),
     "qe_layernorm_quantize_pack_workspace_bytes": (_sz, [_i64, _i32, _i32, _pr, _ppc, _vp]),
     "qe_layernorm_quantize_pack": (_i32, [_vp, _i64, _i32, _vp, _vp, _f32, _i32, _pr, _ppc, _vp, _vp, _vp, _sz, _vp]),
@@ -123,6 +126,8 @@ PROTOTYPES = {
     "qe_attention_masked": (_i32, _attn + [_vp, _i64, _i64, _vp, _i32, _vp]),
     "qe_attention_bf16_path": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
     "qe_attention_bf16": (_i32, _attn + [_vp, _i64, _i64, _vp, _i32, _vp]),
+    "qe_attention_bf16_stored_path": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "qe_attention_bf16_stored": (_i32, _attn + [_vp, _i64, _i64, _vp, _i32, _vp]),
 }
 SYMBOLS = sorted(PROTOTYPES)
 # exported by the library but absent from the header (not part of the public ABI): kept out of SYMBOLS
@@ -574,6 +579,27 @@ def quantlinear_residual(xq, wq, bias, B, K, O, residual, out=None, stream=None)
     return out
 
 
+def quantlinear_bf16_path(xq, wq, B, K, O, out=None):
+    """qe_quantlinear_bf16_path: 1 = the MFMA kernel rounds and stores the bf16 rows itself, 0 = two passes inside the call.
+    out=None asks for a 16-byte aligned buffer (torch allocations are)."""
+    return int(lib().qe_quantlinear_bf16_path(ctypes.byref(xq), ctypes.byref(wq), int(B), int(K), int(O), _ptr(out)))
+
+
+def quantlinear_bf16(xq, wq, bias, B, K, O, post_scale=1.0, out=None, stream=None):
+    """qe_quantlinear_bf16: bf16(quantlinear(...) * post_scale) as a torch.bfloat16 tensor (B, O) -- one fp32 multiply, round
+    to nearest even: equal to (quantlinear(...) * post_scale).to(torch.bfloat16) element for element."""
+    import torch
+    dev = wq._keep[0].device
+    if out is None:
+        out = torch.empty((B, O), dtype=torch.bfloat16, device=dev)
+    assert out.is_contiguous() and out.dtype == torch.bfloat16 and out.numel() == B * O
+    need = int(lib().qe_quantlinear_bf16_workspace_bytes(ctypes.byref(xq), ctypes.byref(wq), int(B), int(K), int(O), out.data_ptr()))
+    ws = _ws(need, dev)
+    check(lib().qe_quantlinear_bf16(ctypes.byref(xq), ctypes.byref(wq), _ptr(bias), int(B), int(K), int(O), float(post_scale),
+                                    out.data_ptr(), _ptr(ws), need, _stream(stream)))
+    return out
+
+
 def linear_float_input_residual_path(x, wq, B, K, O):
     return int(lib().qe_quantlinear_float_input_residual_path(x.data_ptr(), ctypes.byref(wq), int(B), int(K), int(O)))
 
@@ -657,6 +683,12 @@ def attention_bf16_path(L, S, H, d, has_mask=False, has_key_bias=False, causal=F
                                             int(bool(causal))))
 
 
+def attention_bf16_stored_path(L, S, H, d, has_mask=False, has_key_bias=False, causal=False):
+    """qe_attention_bf16_stored_path: 2 = the bf16 MFMA kernel on bf16 rows, -1 = no kernel, as attention_bf16_path."""
+    return int(lib().qe_attention_bf16_stored_path(int(L), int(S), int(H), int(d), int(bool(has_mask)), int(bool(has_key_bias)),
+                                                   int(bool(causal))))
+
+
 PRECISIONS = ("fp32", "bf16")
 
 
@@ -670,14 +702,22 @@ def attention(q, k, v, N, L, H, S=None, layout="token", scale=None, out=None, st
     causal (top-left aligned).  mask: contiguous fp32, additive (finite or -inf), of shape (L, S), (N, L, S), (N, H, L, S) or
     (N*H, L, S); key_bias: contiguous fp32 (N, S).  A row with no visible key comes out NaN.
     precision "bf16" (qe_attention_bf16): both products on the bf16 matrix cores, fp32 softmax and accumulation, the same
-    operands; d % 16 == 0 and d <= 128 only -- any other d raises QeError (unsupported), never the fp32 kernels instead."""
+    operands; d % 16 == 0 and d <= 128 only -- any other d raises QeError (unsupported), never the fp32 kernels instead.
+    With precision "bf16", q, k and v may be torch.bfloat16 tensors, all three (qe_attention_bf16_stored: the rows are read
+    as bf16, q^ = bf16(fp32(q) scale), k and v as stored; out stays fp32).  Mixed dtypes, or bf16 tensors with precision
+    "fp32", raise ValueError."""
     if precision not in PRECISIONS:
         raise ValueError("precision must be 'fp32' or 'bf16'")
     import torch
     S = L if S is None else int(S)
     N, L, H = int(N), int(L), int(H)
+    stored = q.dtype == torch.bfloat16
+    if not (q.dtype == k.dtype == v.dtype) or q.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("q, k and v must all be torch.float32 or all torch.bfloat16; got %s, %s, %s" % (q.dtype, k.dtype, v.dtype))
+    if stored and precision != "bf16":
+        raise ValueError("torch.bfloat16 q / k / v need precision='bf16'")
     for t, rows in ((q, N * L), (k, N * S), (v, N * S)):
-        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() % rows == 0
+        assert t.is_cuda and t.is_contiguous() and t.numel() % rows == 0
     E = q.numel() // (N * L)
     assert k.numel() == N * S * E and v.numel() == N * S * E and E % H == 0
     d = E // H
@@ -688,7 +728,7 @@ def attention(q, k, v, N, L, H, S=None, layout="token", scale=None, out=None, st
     else:
         raise ValueError("layout must be 'token' or 'seq'")
     if out is None:
-        out = torch.empty_like(q)
+        out = torch.empty_like(q, dtype=torch.float32)
     assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == q.numel()
     scale = float(d ** -0.5 if scale is None else scale)
     if mask is None and key_bias is None and not causal and precision == "fp32":
@@ -712,7 +752,7 @@ def attention(q, k, v, N, L, H, S=None, layout="token", scale=None, out=None, st
         if not (torch.is_tensor(key_bias) and key_bias.is_cuda and key_bias.is_contiguous()
                 and key_bias.dtype == torch.float32 and tuple(key_bias.shape) == (N, S)):
             raise ValueError("key_bias must be a contiguous fp32 CUDA tensor of shape (N, S)")
-    run = lib().qe_attention_bf16 if precision == "bf16" else lib().qe_attention_masked
+    run = lib().qe_attention_bf16_stored if stored else lib().qe_attention_bf16 if precision == "bf16" else lib().qe_attention_masked
     check(run(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), N, L, S, H, d, q_rn, q_rt, kv_rn, kv_rt, q_rn, q_rt, scale,
               _ptr(mask), mask_sn, mask_sh, _ptr(key_bias), 1 if causal else 0, _stream(stream)))
     return out

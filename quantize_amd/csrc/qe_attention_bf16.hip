@@ -238,14 +238,6 @@ __global__ __launch_bounds__(64 * attn_wpb(D)) void attn_bf16_kernel(const AttnA
     }
 }
 
-// 2 = the bf16 MFMA kernel, -1 = no kernel.  QE_ATTN is not read: it chooses between the two fp32 kernels only.
-static int attn_bf16_path(int L, int S, int H, int d)
-{
-    if (L <= 0 || S <= 0 || H <= 0 || d <= 0) return -1;
-    if (d % 16 != 0 || d > 128) return -1;
-    return 2;
-}
-
 struct AttnBf16 {
     template <int D, int MODE> static constexpr auto kernel = &attn_bf16_kernel<D, MODE>;
 };
@@ -258,7 +250,7 @@ static int attn_bf16_run(const float *q, const float *k, const float *v, float *
     AttnArgs a;
     int mode;
     // a head size without a bf16 instance is refused here: never the fp32 kernels instead
-    if (const int e = attn_prepare(q, k, v, out, N, L, S, H, d, q_rn, q_rt, kv_rn, kv_rt, o_rn, o_rt, scale, mask, mask_sn,
+    if (const int e = attn_prepare(q, k, v, sizeof(float), out, N, L, S, H, d, q_rn, q_rt, kv_rn, kv_rt, o_rn, o_rt, scale, mask, mask_sn,
                                    mask_sh, key_bias, causal, attn_bf16_path(L, S, H, d), a, mode))
         return e;
     attn_dispatch_mode(mode, [&](auto m) { attn_launch_rows32<AttnBf16, decltype(m)::value>(a, static_cast<hipStream_t>(stream)); });

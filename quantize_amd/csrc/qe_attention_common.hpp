@@ -1,4 +1,5 @@
-// qe_attention_common.hpp -- what the attention cores (qe_attention.hip: fp32, qe_attention_bf16.hip: bf16 MFMA) share: the
+// qe_attention_common.hpp -- what the attention cores (qe_attention.hip: fp32, qe_attention_bf16.hip: bf16 MFMA on fp32
+// rows, qe_attention_bf16_stored.hip: the same on bf16 rows) share: the
 // argument struct and the MODE bits, every check an entry point makes before it launches (attn_prepare), and the two
 // switches that turn the runtime mode and head size into a kernel instance (attn_dispatch_mode, attn_launch_rows32), with
 // the launch geometry of the kernels that give a wave 32 query rows.  No device code: attn_mfma_kernel and attn_bf16_kernel
@@ -13,9 +14,9 @@
 namespace qe {
 
 struct AttnArgs {
-    const float *q, *k, *v;
+    const float *q, *k, *v;                          // attn_bf16_stored_kernel: rows of bf16 behind the same three pointers
     float *out;
-    int64_t q_rn, q_rt, kv_rn, kv_rt, o_rn, o_rt;    // in rows of H*d floats
+    int64_t q_rn, q_rt, kv_rn, kv_rt, o_rn, o_rt;    // in rows of H*d elements
     int N, L, S, H, d;
     int qgroups;                                     // workgroups per (image, head)
     float scale;
@@ -29,7 +30,7 @@ constexpr float kLog2e = 1.4426950408889634f;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// ---- the kernels with 32 query rows per wave (attn_mfma_kernel, attn_bf16_kernel) ----
+// ---- the kernels with 32 query rows per wave (attn_mfma_kernel, attn_bf16_kernel, attn_bf16_stored_kernel) ----
 
 // waves of one (image, head) per workgroup (they share the K / V rows they stream in the CU's L1): the kernels' block size
 // and query decode, and the grid below
@@ -88,19 +89,29 @@ inline void attn_dispatch_mode(int mode, F &&f)
     }
 }
 
-// [lo, hi) byte range the rows of (n < N, t < T) span
-inline void row_span(const float *p, int N, int T, int64_t rn, int64_t rt, int64_t E, uintptr_t &lo, uintptr_t &hi)
+// 2 = a bf16 matrix-core kernel (either storage), -1 = no kernel.  QE_ATTN is not read: it chooses between the two fp32
+// kernels only.
+inline int attn_bf16_path(int L, int S, int H, int d)
+{
+    if (L <= 0 || S <= 0 || H <= 0 || d <= 0) return -1;
+    if (d % 16 != 0 || d > 128) return -1;
+    return 2;
+}
+
+// [lo, hi) byte range the rows of (n < N, t < T) span; elem = bytes per element
+inline void row_span(const void *p, int N, int T, int64_t rn, int64_t rt, int64_t E, size_t elem, uintptr_t &lo, uintptr_t &hi)
 {
     const int64_t last = (int64_t)(N - 1) * rn + (int64_t)(T - 1) * rt;
     lo = reinterpret_cast<uintptr_t>(p);
-    hi = lo + (uintptr_t)((last + 1) * E) * sizeof(float);
+    hi = lo + (uintptr_t)((last + 1) * E) * elem;
 }
 
-// Everything qe_attention, qe_attention_masked and qe_attention_bf16 check before a launch, in one order, so that an
-// argument list that breaks two rules gets one answer from all of them.  `path` is the entry point's own path function's
+// Everything qe_attention, qe_attention_masked, qe_attention_bf16 and qe_attention_bf16_stored check before a launch, in one
+// order, so that an argument list that breaks two rules gets one answer from all of them.  in_elem = bytes per element of
+// q, k and v (4: fp32 rows, 2: bf16 rows; out, mask and key_bias are fp32 for every entry point).  `path` is the entry point's own path function's
 // answer for (L, S, H, d), < 0: no kernel.  On QE_OK `a` is filled (but for qgroups) and `mode` is the instance's MODE.
 // Both grid limits hold for every entry point: the second is the fp32 VALU kernel's.
-inline int attn_prepare(const float *q, const float *k, const float *v, float *out, int32_t N, int32_t L, int32_t S, int32_t H,
+inline int attn_prepare(const void *q, const void *k, const void *v, size_t in_elem, float *out, int32_t N, int32_t L, int32_t S, int32_t H,
                         int32_t d, int64_t q_rn, int64_t q_rt, int64_t kv_rn, int64_t kv_rt, int64_t o_rn, int64_t o_rt,
                         float scale, const float *mask, int64_t mask_sn, int64_t mask_sh, const float *key_bias, int causal,
                         int path, AttnArgs &a, int &mode)
@@ -117,13 +128,13 @@ inline int attn_prepare(const float *q, const float *k, const float *v, float *o
     if (path < 0) return QE_ERR_UNSUPPORTED;
     const int64_t E = (int64_t)H * d;
     uintptr_t olo, ohi;
-    row_span(out, N, L, o_rn, o_rt, E, olo, ohi);
-    const float *ins[3] = {q, k, v};
+    row_span(out, N, L, o_rn, o_rt, E, sizeof(float), olo, ohi);
+    const void *ins[3] = {q, k, v};
     const int64_t rn[3] = {q_rn, kv_rn, kv_rn}, rt[3] = {q_rt, kv_rt, kv_rt};
     const int len[3] = {L, S, S};
     for (int i = 0; i < 3; ++i) {
         uintptr_t lo, hi;
-        row_span(ins[i], N, len[i], rn[i], rt[i], E, lo, hi);
+        row_span(ins[i], N, len[i], rn[i], rt[i], E, in_elem, lo, hi);
         if (lo < ohi && olo < hi) return QE_ERR_ARG;
     }
     if (mask != nullptr) {                       // the (L, S) blocks of (n < N, h < H) span up to this many floats
@@ -139,7 +150,7 @@ inline int attn_prepare(const float *q, const float *k, const float *v, float *o
     const int64_t rows = (int64_t)N * H * L;
     if ((int64_t)N * H * ceil_div(L, 32) > 0x7fffffffLL || ceil_div64(rows, 4) > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
     a = {};
-    a.q = q; a.k = k; a.v = v; a.out = out;
+    a.q = static_cast<const float *>(q); a.k = static_cast<const float *>(k); a.v = static_cast<const float *>(v); a.out = out;
     a.q_rn = q_rn; a.q_rt = q_rt; a.kv_rn = kv_rn; a.kv_rt = kv_rt; a.o_rn = o_rn; a.o_rt = o_rt;
     a.N = N; a.L = L; a.S = S; a.H = H; a.d = d; a.scale = scale;
     a.mask = mask; a.key_bias = key_bias; a.mask_sn = mask_sn; a.mask_sh = mask_sh;

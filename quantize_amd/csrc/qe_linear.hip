@@ -40,6 +40,7 @@ __device__ __forceinline__ unsigned long long lin_stamp()
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
+typedef __bf16 v8bf_l __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ int lin_unpack(const uint8_t *__restrict__ p, int64_t ele_idx, int n_bits, int sign)
 {
@@ -67,15 +68,27 @@ struct LinArgs {
     uint8_t *codes;         // LIN_CODES*: B x O stored 8-bit codes of a per-tensor consumer quantiser
     int32_t *status;        // LIN_CODES*: bit 0 set when a code fails the range test (NaN included)
     QeRq rq;
+    uint16_t *out16;        // LIN_BF16: B x O bf16 values of y * post_scale
+    float post_scale;
 };
 
 // Epilogue of an MFMA linear kernel, a template parameter and never a runtime branch: what leaves
-// the kernel is y (LIN_F32), y + res in fp32 (LIN_RES), or the consumer's 8-bit codes of y / gelu(y) (LIN_CODES,
+// the kernel is y (LIN_F32), y + res in fp32 (LIN_RES), the consumer's 8-bit codes of y / gelu(y) (LIN_CODES,
 // LIN_CODES_GELU), computed with qe_elementwise.hpp's functions -- the ones qe_quantize_pack_act runs -- so each fused form
-// is bit-identical to its two-pass form.  Codes go through the wave's LDS patch and leave as 16-byte row pieces.
-enum { LIN_F32 = 0, LIN_CODES = 1, LIN_CODES_GELU = 2, LIN_RES = 3 };
+// is bit-identical to its two-pass form, or bf16(y * post_scale) (LIN_BF16: one fp32 multiply, round to nearest even, a NaN
+// stays a NaN; lin_bf16x8 below, which the two-pass form's round_bf16_kernel runs as well).  Codes and bf16 values go through
+// the wave's LDS patch and leave as 16-byte row pieces.
+enum { LIN_F32 = 0, LIN_CODES = 1, LIN_CODES_GELU = 2, LIN_RES = 3, LIN_BF16 = 4 };
 template <int EPI> constexpr bool lin_codes() { return EPI == LIN_CODES || EPI == LIN_CODES_GELU; }
 template <int EPI> constexpr int lin_act() { return EPI == LIN_CODES_GELU ? QE_ACT_GELU : QE_ACT_NONE; }
+// 8 consecutive fp32 outputs -> 8 bf16 of x * ps: one 16-byte piece (v_cvt_pk_bf16_f32 rounds to nearest even)
+__device__ __forceinline__ uint4 lin_bf16x8(const float4 x, const float4 y, float ps)
+{
+    v8bf_l f;
+    f[0] = (__bf16)(x.x * ps); f[1] = (__bf16)(x.y * ps); f[2] = (__bf16)(x.z * ps); f[3] = (__bf16)(x.w * ps);
+    f[4] = (__bf16)(y.x * ps); f[5] = (__bf16)(y.y * ps); f[6] = (__bf16)(y.z * ps); f[7] = (__bf16)(y.w * ps);
+    return __builtin_bit_cast(uint4, f);
+}
 // 16 consecutive outputs in LDS (p[0..15]) -> their 16 stored codes.  Plain codes: four float4 reads, unrolled.  GELU: a loop
 // that is NOT unrolled, one value per trip -- unrolled, the erf bodies (each with its own branch and exp) of every tile
 // spilled the live accumulators to scratch -- the codes shifted in from the top of the 16-byte piece.
@@ -336,6 +349,7 @@ __global__ __launch_bounds__(256, 2) void linear_mfma_kernel(const LinArgs a)
     if constexpr (lin_codes<EPI>()) vec4 = (a.O & 15) == 0 && (reinterpret_cast<uintptr_t>(a.codes) & 15) == 0;
     else if constexpr (EPI == LIN_RES)
         vec4 = (a.O & 3) == 0 && ((reinterpret_cast<uintptr_t>(a.out) | reinterpret_cast<uintptr_t>(a.res)) & 15) == 0;
+    else if constexpr (EPI == LIN_BF16) vec4 = true;      // O % 8 == 0 and out16 16-byte aligned (host)
     else vec4 = (a.O & 3) == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0;
     float *patch = reinterpret_cast<float *>(lsm) + wave * (32 * 36);
     const int rrow = lane >> 3, rq = lane & 7;
@@ -383,6 +397,23 @@ __global__ __launch_bounds__(256, 2) void linear_mfma_kernel(const LinArgs a)
                             const uint32_t ww[4] = {c16.x, c16.y, c16.z, c16.w};
                             for (int b = 0; b < 16 && cb + b < a.O; ++b) dst[b] = (uint8_t)(ww[b >> 2] >> ((b & 3) * 8));
                         }
+                    }
+                } else if constexpr (EPI == LIN_BF16) {
+                    // y through the fp32 patch; lane (row 16 k + (lane >> 2), piece lane & 3) rounds 8 consecutive values of its
+                    // row and stores them as one piece.  O % 8 == 0 (host): a piece lies wholly below O or wholly beyond it
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) patch[((r & 3) + 8 * (r >> 2) + 4 * h) * 36 + col] = v[r];
+                    const int c8 = n0 + wn * 32 * NJ + j * 32 + 8 * (lane & 3);
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) {
+                        const int rt = 16 * k + (lane >> 2);
+                        const float *src = patch + rt * 36 + 8 * (lane & 3);
+                        const uint4 o8 = lin_bf16x8(*reinterpret_cast<const float4 *>(src), *reinterpret_cast<const float4 *>(src + 4),
+                                                    a.post_scale);
+                        const int64_t row = row0 + rt;
+                        uint16_t *dst = a.out16 + row * a.O + c8;
+                        if constexpr (FULL) *reinterpret_cast<uint4 *>(dst) = o8;
+                        else if (row < a.B && c8 < a.O) *reinterpret_cast<uint4 *>(dst) = o8;
                     }
                 } else if constexpr (FULL) {
 #pragma unroll
@@ -713,6 +744,8 @@ __global__ __launch_bounds__(256 * WMW, WMW == 2 ? 1 : 2) void linear_mfma8_kern
     float *patch0 = reinterpret_cast<float *>(lsm) + wave * (32 * 64);
     const int r4 = lane >> 4, q16 = lane & 15;
     const uint32_t voff = (uint32_t)r4 * (uint32_t)a.O + 4u * (uint32_t)q16;   // elements; r4 O + 64 < 2^31 (O < 2^29)
+    const int r8 = lane >> 3, q8 = lane & 7;                                   // LIN_BF16: 8 lanes per row
+    const uint32_t voff8 = (uint32_t)r8 * (uint32_t)a.O + 8u * (uint32_t)q8;   // elements; 7 O + 64 < 2^31 (O < 2^28)
     bool bad = false;                                     // LIN_CODES*: range flag of this lane's codes
     float rsc = 0.0f, rzr = 0.0f;
     if constexpr (lin_codes<EPI>()) { rsc = a.rq.scale[0]; rzr = a.rq.zero[0]; }
@@ -749,6 +782,19 @@ __global__ __launch_bounds__(256 * WMW, WMW == 2 ? 1 : 2) void linear_mfma8_kern
                 for (int r = 0; r < 16; ++r) patch0[((r & 3) + 8 * (r >> 2) + 4 * h) * 64 + j * 32 + col] = v[r];
             }
             const int64_t row0 = m0 + wm * 160 + i * 32;
+            if constexpr (EPI == LIN_BF16) {
+                // read back as 8 rows x 128 contiguous bytes of bf16 per store instruction (8 lanes per row, 8 values per lane)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float *src = patch0 + (8 * k + r8) * 64 + 8 * q8;
+                    const uint4 o8 = lin_bf16x8(*reinterpret_cast<const float4 *>(src), *reinterpret_cast<const float4 *>(src + 4),
+                                                a.post_scale);
+                    uint16_t *base = a.out16 + (row0 + 8 * k) * (int64_t)a.O + (n0 + wn * 64);
+                    if constexpr (decltype(full_tag)::value) *reinterpret_cast<uint4 *>(base + voff8) = o8;
+                    else if (row0 + 8 * k + r8 < a.B) *reinterpret_cast<uint4 *>(base + voff8) = o8;
+                }
+                continue;
+            }
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const float4 o4 = *reinterpret_cast<const float4 *>(patch0 + (4 * k + r4) * 64 + 4 * q16);
@@ -798,7 +844,6 @@ __global__ __launch_bounds__(256 * WMW, WMW == 2 ? 1 : 2) void linear_mfma8_kern
 // fetched 4 consecutive k of a row splits them and writes 3 x 8 bytes; weights: 16 codes -> 16 bf16 per thread.
 // LDS images [row][32 k] bf16 (64-byte rows), 16-byte pieces XOR-swizzled as in linear_mfma_kernel.
 // ---------------------------------------------------------------------------------------------
-typedef __bf16 v8bf_l __attribute__((ext_vector_type(8)));
 typedef float v16f_l __attribute__((ext_vector_type(16)));
 constexpr int LF_T = 128, LF_K = 32;
 constexpr int LF_PLANE = LF_T * LF_K * 2;                 // bytes of one [128][32] bf16 image (8 KB)
@@ -981,10 +1026,12 @@ struct LinRequest {
     const float *xf = nullptr;
     int64_t B = 0;
     int K = 0, O = 0;
-    int epi = LIN_F32;                  // LIN_CODES*: the consumer's quantiser rq, codes and status; LIN_RES: out = y + res
+    int epi = LIN_F32;                  // LIN_CODES*: the consumer's quantiser rq, codes and status; LIN_RES: out = y + res;
+                                        // LIN_BF16: out16 = bf16(y * post_scale)
     const qe_requant *rq = nullptr;
     const float *bias = nullptr, *res = nullptr;
     float *out = nullptr; uint8_t *codes = nullptr; int32_t *status = nullptr;
+    uint16_t *out16 = nullptr; float post_scale = 1.0f;
 };
 
 struct LinPlan {
@@ -1037,14 +1084,18 @@ static LinPlan plan_linear(const LinRequest &r)
                    // kernel, as the reference's fp32 sum does)
         mfma = mfma && r.x != nullptr && r.x->n_bits == 8 && (K % LK) == 0 && K >= LK && K < (1 << 17) && al16(ad(r.x->data));
 
-    // Fused epilogues run in the MFMA kernels: the residual add, or 8-bit per-tensor codes at a 16-byte aligned address.
+    // Fused epilogues run in the MFMA kernels: the residual add, 8-bit per-tensor codes at a 16-byte aligned address, or
+    // bf16 values at a 16-byte aligned address with O % 8 == 0 (a row piece of 8 values is then one aligned 16-byte store
+    // that lies wholly inside a row: every O % 64 == 0 fuses, and a narrower multiple of 8 as well).
     // Anything else, and every call under QE_LIN_EPI=0, takes two passes: the linear into the workspace, then the
     // elementwise pass whose arithmetic the epilogue shares.
     LinPlan p;
     const qe_requant *rq = r.rq;
     const bool rq_ok = rq != nullptr && rq->n_bits == 8 && rq->n_param == 1 && rq->scale != nullptr && rq->zero != nullptr &&
                        al16(ad(r.codes));
-    p.two_pass = r.epi != LIN_F32 && !(mfma && !((e = env_get("QE_LIN_EPI")) && atoi(e) == 0) && (r.epi == LIN_RES || rq_ok));
+    const bool bf16_ok = O % 8 == 0 && al16(ad(r.out16));
+    const bool epi_ok = r.epi == LIN_RES || (r.epi == LIN_BF16 ? bf16_ok : rq_ok);
+    p.two_pass = r.epi != LIN_F32 && !(mfma && !((e = env_get("QE_LIN_EPI")) && atoi(e) == 0) && epi_ok);
     p.epi = p.two_pass ? LIN_F32 : r.epi;
     p.ws = p.two_pass && B > 0 && O > 0 ? (size_t)B * (size_t)O * sizeof(float) : 0;
 
@@ -1052,8 +1103,10 @@ static LinPlan plan_linear(const LinRequest &r)
         p.form = mfma ? LIN_FORM_BF16 : LIN_FORM_CHAIN_F;
     } else if (mfma) {
         // The epilogue's destination: y in the 16-byte aligned workspace, out, or out and res.  The codes count as aligned,
-        // as qe_quantlinear_requant has always passed them (its fused form requires aligned codes in any case).
-        const bool dst_aligned = p.two_pass || r.epi == LIN_CODES || r.epi == LIN_CODES_GELU || al16(ad(r.out) | ad(r.res));
+        // as qe_quantlinear_requant has always passed them (its fused form requires aligned codes in any case), and so do
+        // fused bf16 values (bf16_ok).
+        const bool dst_aligned = p.two_pass || r.epi == LIN_CODES || r.epi == LIN_CODES_GELU || r.epi == LIN_BF16 ||
+                                 al16(ad(r.out) | ad(r.res));
         // tile width: 256 columns unless that leaves the chip under-filled (the ViT head: 8 workgroups): twice as many,
         // half as wide (17.8 -> 11.5 us)
         p.form = ((B + LM - 1) / LM) * ((O + 255) / 256) < kNumCU ? LIN_FORM_NJ2 : LIN_FORM_NJ4;
@@ -1110,7 +1163,7 @@ static LinArgs lin_args(const LinRequest &r, float *out)
     a.w = static_cast<const uint8_t *>(r.w->data); a.w_scale = r.w->scale; a.w_zero = r.w->zero; a.bias = r.bias;
     a.w_bits = r.w->n_bits; a.w_sign = r.w->sign; a.w_per_tensor = r.w->n_param == 1;
     a.B = r.B; a.K = r.K; a.O = r.O; a.out = out; a.dbg = g_mfma_dbg;
-    a.res = r.res; a.codes = r.codes; a.status = r.status;
+    a.res = r.res; a.codes = r.codes; a.status = r.status; a.out16 = r.out16; a.post_scale = r.post_scale;
     if (r.rq != nullptr) a.rq = make_rq(r.rq);
     return a;
 }
@@ -1138,6 +1191,29 @@ static void launch_epi(const LinPlan &p, const LinArgs &a, hipStream_t s)
         if (p.form == LIN_FORM_CHAIN) return launch_lin<&linear_generic_kernel<false>>(p, a, s);
         if (p.form == LIN_FORM_CHAIN_F) return launch_lin<&linear_generic_kernel<true>>(p, a, s);
     }
+}
+
+// out = bf16(y * ps): lin_bf16x8, the LIN_BF16 epilogue's own arithmetic (path 0 of qe_quantlinear_bf16)
+__global__ __launch_bounds__(256) void round_bf16_kernel(const float *y, uint16_t *out, int64_t n, float ps, int vec)
+{
+    const int64_t n8 = vec ? n / 8 : 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256)
+        reinterpret_cast<uint4 *>(out)[i] = lin_bf16x8(reinterpret_cast<const float4 *>(y)[2 * i], reinterpret_cast<const float4 *>(y)[2 * i + 1], ps);
+    for (int64_t i = 8 * n8 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const __bf16 b = (__bf16)(y[i] * ps);
+        out[i] = __builtin_bit_cast(uint16_t, b);
+    }
+}
+
+static int launch_round_bf16(const float *y, uint16_t *out, int64_t n, float ps, hipStream_t s)
+{
+    if (n <= 0) return QE_OK;
+    const int vec = ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+    const int64_t want = ((vec ? n / 8 : n) + 255) / 256;
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, kNumCU * 16));
+    hipLaunchKernelGGL(round_bf16_kernel, dim3(blocks), dim3(256), 0, s, y, out, n, ps, vec);
+    QE_LAUNCH_CHECK();
+    return QE_OK;
 }
 
 // out = y + res, one fp32 add per element (path 0 of the residual forms); out may be res
@@ -1175,11 +1251,13 @@ static int run_linear(const LinRequest &r, void *workspace, size_t workspace_byt
     if (p.epi == LIN_CODES) launch_epi<LIN_CODES>(p, a, s);
     else if (p.epi == LIN_CODES_GELU) launch_epi<LIN_CODES_GELU>(p, a, s);
     else if (p.epi == LIN_RES) launch_epi<LIN_RES>(p, a, s);
+    else if (p.epi == LIN_BF16) launch_epi<LIN_BF16>(p, a, s);
     else launch_epi<LIN_F32>(p, a, s);
     QE_LAUNCH_CHECK();
     if (!p.two_pass) return QE_OK;
     const int64_t n = r.B * (int64_t)r.O;
     if (r.epi == LIN_RES) return launch_add_residual(y, r.res, r.out, n, s);
+    if (r.epi == LIN_BF16) return launch_round_bf16(y, r.out16, n, r.post_scale, s);
     // per-channel rq: channel = output feature o, element (b, o) -> (i / 1) % O
     const qe_requant *rq = r.rq;
     return qe_quantize_pack_act(y, n, r.epi == LIN_CODES_GELU ? QE_ACT_GELU : QE_ACT_NONE, rq->scale, rq->zero, rq->n_param, 1,
@@ -1283,6 +1361,36 @@ extern "C" int qe_quantlinear_residual(const qe_qparam *x, const qe_qparam *w, c
     if (int rc = check_lin(r)) return rc;
     if (B == 0 || O == 0) return QE_OK;
     if (residual == nullptr || out == nullptr || !res_overlap_ok(residual, out, B * (int64_t)O)) return QE_ERR_ARG;
+    return run_linear(r, workspace, workspace_bytes, stream);
+}
+
+// bf16 rows for a consumer that rounds them anyway (qe_attention_bf16_stored): path 1 is an MFMA kernel with the LIN_BF16
+// epilogue, path 0 the linear into the workspace and round_bf16_kernel.  The queries take `out` for its alignment (NULL
+// reads as aligned).
+extern "C" int qe_quantlinear_bf16_path(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O, const uint16_t *out)
+{
+    qe::LinRequest r = qe::lin_req(x, w, B, K, O, qe::LIN_BF16);
+    r.out16 = const_cast<uint16_t *>(out);
+    return !qe::plan_linear(r).two_pass;
+}
+
+extern "C" size_t qe_quantlinear_bf16_workspace_bytes(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O,
+                                                      const uint16_t *out)
+{
+    qe::LinRequest r = qe::lin_req(x, w, B, K, O, qe::LIN_BF16);
+    r.out16 = const_cast<uint16_t *>(out);
+    return qe::plan_linear(r).ws;
+}
+
+extern "C" int qe_quantlinear_bf16(const qe_qparam *x, const qe_qparam *w, const float *bias, int64_t B, int32_t K, int32_t O,
+                                   float post_scale, uint16_t *out, void *workspace, size_t workspace_bytes, qe_stream_t stream)
+{
+    using namespace qe;
+    LinRequest r = lin_req(x, w, B, K, O, LIN_BF16);
+    r.bias = bias; r.out16 = out; r.post_scale = post_scale;
+    if (int rc = check_lin(r)) return rc;
+    if (B == 0 || O == 0) return QE_OK;
+    if (out == nullptr || (reinterpret_cast<uintptr_t>(out) & 1) != 0) return QE_ERR_ARG;
     return run_linear(r, workspace, workspace_bytes, stream);
 }
 

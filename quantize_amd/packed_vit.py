@@ -19,6 +19,9 @@ Both routes call the same attention core, _attention: by default fp32 F.scaled_d
 what F.multi_head_attention_forward runs for need_weights=False; with attention="engine" the fp32 qe_attention kernel,
 which reads the three projections in their (N L, E) buffers and writes the context straight into out_proj's input; with
 attention="engine_bf16" the same, its two products on the bf16 matrix cores (qe_attention_bf16: not fp32-exact).
+qkv="bf16" (fused route with attention="engine_bf16" only) has the three projections write bf16 rows (qe_quantlinear_bf16,
+q already multiplied by d ** -0.5) that the attention kernel reads as stored (qe_attention_bf16_stored, scale 1): the values
+the bf16 kernel would have rounded to anyway, so logits and block outputs are bit-identical to qkv="fp32".
 The C entry points take their two-pass form wherever the fused form is not eligible (sub-8-bit or per-channel consumer codes, non-MFMA shapes, QE_LIN_EPI=0), so every step of
 the fused route exists for every model the layers route runs.  With check=False the fused route makes no device -> host
 copy or synchronisation: every range flag accumulates in one device int32, read once at the end when check=True.
@@ -35,6 +38,7 @@ from .packed_resnet import pack_codes
 
 
 ATTENTION = ("torch", "engine", "engine_bf16")
+QKV = ("fp32", "bf16")
 
 
 def _check_attention(attention):
@@ -42,8 +46,18 @@ def _check_attention(attention):
         raise ValueError("attention must be 'torch', 'engine' or 'engine_bf16'")
 
 
+def _check_qkv(qkv, route, attention):
+    if qkv not in QKV:
+        raise ValueError("qkv must be 'fp32' or 'bf16'")
+    if qkv == "bf16" and (route != "fused" or attention != "engine_bf16"):
+        raise ValueError("qkv='bf16' needs route='fused' and attention='engine_bf16' (the bf16 attention core reads the rows)")
+
+
 def _attention(Q, K, V, N, L, H, attention="torch"):
-    """(N L, E) fp32 projections -> (N L, E) context: softmax(Q K^T / sqrt(d)) V per head, fp32."""
+    """(N L, E) fp32 projections -> (N L, E) context: softmax(Q K^T / sqrt(d)) V per head, fp32.  bf16 projections (Q
+    already scaled; "engine_bf16" only) are read as stored, with scale 1."""
+    if Q.dtype == torch.bfloat16:
+        return capi.attention(Q, K, V, N, L, H, scale=1.0, precision="bf16")
     if attention == "engine":
         return capi.attention(Q, K, V, N, L, H)
     if attention == "engine_bf16":
@@ -134,16 +148,21 @@ class PackedViT:
         return out + [self.head]
 
     # ---- the two routes ----
-    def __call__(self, images, route="fused", check=True, attention="torch"):
-        return self.forward(images, route, check, attention=attention)[0]
+    def __call__(self, images, route="fused", check=True, attention="torch", qkv="fp32"):
+        return self.forward(images, route, check, attention=attention, qkv=qkv)[0]
 
-    def forward(self, images, route="fused", check=True, keep_blocks=False, attention="torch"):
+    def forward(self, images, route="fused", check=True, keep_blocks=False, attention="torch", qkv="fp32"):
         """(logits, [block outputs (N, L, E)] if keep_blocks else None).  attention: "torch" (F.scaled_dot_product_attention)
-        "engine" (the fp32 qe_attention kernel) or "engine_bf16" (qe_attention_bf16), in either route."""
+        "engine" (the fp32 qe_attention kernel) or "engine_bf16" (qe_attention_bf16), in either route.  qkv: "fp32", or
+        "bf16" (route "fused" with attention "engine_bf16" only; ValueError otherwise, before any launch): the q / k / v
+        projections as bf16 rows, bit-identical results."""
         if route not in ("fused", "layers"):
             raise ValueError("route must be 'fused' or 'layers'")
         _check_attention(attention)
+        _check_qkv(qkv, route, attention)
         kw = {} if attention == "torch" else {"attention": attention}    # the default keeps block()'s five-argument call
+        if qkv != "fp32":
+            kw["qkv"] = qkv
         images = images.contiguous()
         N = images.shape[0]
         status = torch.zeros(1, dtype=torch.int32, device=images.device)
@@ -185,10 +204,11 @@ class PackedViT:
         x = torch.cat([self.class_token.expand(N, -1, -1), t], dim=1) + self.pos
         return x.reshape(-1, self.E).contiguous()
 
-    def block(self, b, x, N, route, status=None, attention="torch", observe=None):
+    def block(self, b, x, N, route, status=None, attention="torch", observe=None, qkv="fp32"):
         """One encoder block on (N L, E) fp32 rows -> (N L, E).  The fused route updates x in place.  observe: see _run
-        (`layers` route)."""
+        (`layers` route).  qkv: see forward."""
         _check_attention(attention)
+        _check_qkv(qkv, route, attention)
         E, H = self.E, self.num_heads
         L = x.shape[0] // N
         if route == "layers":
@@ -204,7 +224,12 @@ class PackedViT:
         rows = x.shape[0]
         codes = capi.layernorm_quantize_pack(x, b.ln1[0], b.ln1[1], self.eps, [b.q.requant(), b.k.requant(), b.v.requant()],
                                              status=status)[0]
-        Q, K, V = (capi.quantlinear(lin.xq(c), lin.wq(), lin.bias, rows, lin.K, lin.O) for lin, c in zip((b.q, b.k, b.v), codes))
+        if qkv == "bf16":       # q carries the score scale, the fp32 value capi.attention would pass: the kernel's own q^
+            post = ((E // H) ** -0.5, 1.0, 1.0)
+            Q, K, V = (capi.quantlinear_bf16(lin.xq(c), lin.wq(), lin.bias, rows, lin.K, lin.O, post_scale=s)
+                       for lin, c, s in zip((b.q, b.k, b.v), codes, post))
+        else:
+            Q, K, V = (capi.quantlinear(lin.xq(c), lin.wq(), lin.bias, rows, lin.K, lin.O) for lin, c in zip((b.q, b.k, b.v), codes))
         ctx = _attention(Q, K, V, N, L, H, attention)
         x = capi.quantlinear_float_input_residual(ctx, b.attn.out_wq(), b.attn.out_bias, E, x, out=x)
         c1 = capi.layernorm_quantize_pack(x, b.ln2[0], b.ln2[1], self.eps, [b.fc1.requant()], status=status)[0][0]

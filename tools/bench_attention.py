@@ -3,7 +3,9 @@
 precision="bf16") against torch's F.scaled_dot_product_attention on the same (N L, E) fp32 projection buffers -- the engine
 reads them in place, torch gets the (N, H, L, d) views the ViT's _attention passes it.  They alternate step by step, timed
 with device events after a warm-up; medians are reported.  For orientation a fourth column times torch's own bf16 SDPA on
-inputs cast to bf16 beforehand (`torch_bf16_precast`): it reads half the bytes the other three read and writes bf16.
+inputs cast to bf16 beforehand (`torch_bf16_precast`): it reads half the bytes the other three read and writes bf16; and next
+to it `bf16_stored`, the engine's bf16 kernel on q / k / v cast to bf16 beforehand (qe_attention_bf16_stored: bf16 rows in,
+fp32 out -- what the ViT runs with qkv="bf16").
 Useful TFLOP/s counts 4 N H L S d (QK^T and PV, padding not counted); `of_peak` is the share of the 157.3 TFLOP/s fp32
 matrix-pipe peak, given for the two fp32 columns only.  Prints one JSON line (`metric` keeps its name, attention_core_fp32:
 the buffers are fp32 in every column but the pre-cast one).
@@ -65,8 +67,10 @@ def main():
                 kb = torch.zeros(N, L).masked_fill_(torch.arange(L)[None, :] >= lengths[:, None], float("-inf")).to(dev)
                 ekw, tkw = dict(key_bias=kb), dict(attn_mask=kb.view(N, 1, 1, L))
             out16 = torch.empty_like(q)
+            q16, k16, v16 = (t.to(torch.bfloat16) for t in (q, k, v))      # (N L, E) bf16 rows, cast outside the timed region
+            out_st = torch.empty_like(q)
             tkw16 = {n: (m.to(torch.bfloat16) if torch.is_tensor(m) else m) for n, m in tkw.items()}
-            times = {"engine": [], "bf16": [], "torch": [], "torch_bf16_precast": []}
+            times = {"engine": [], "bf16": [], "bf16_stored": [], "torch": [], "torch_bf16_precast": []}
             with torch.no_grad():
                 for i in range(args.warmup + args.steps):
                     for who in times:
@@ -76,6 +80,8 @@ def main():
                             capi.attention(q, k, v, N, L, H, out=out, **ekw)
                         elif who == "bf16":
                             capi.attention(q, k, v, N, L, H, out=out16, precision="bf16", **ekw)
+                        elif who == "bf16_stored":
+                            capi.attention(q16, k16, v16, N, L, H, out=out_st, precision="bf16", **ekw)
                         elif who == "torch_bf16_precast":
                             F.scaled_dot_product_attention(*views16, **tkw16)
                         else:
@@ -87,7 +93,8 @@ def main():
                 diff = float((out.view(N, L, H, d).transpose(1, 2) - ref).abs().max())
             flop = 4.0 * N * H * L * L * d
             row = {"N": N, "L": L, "H": H, "d": d, "max_abs_engine_minus_torch": diff,
-                   "max_abs_bf16_minus_torch": float((out16.view(N, L, H, d).transpose(1, 2) - ref).abs().max())}
+                   "max_abs_bf16_minus_torch": float((out16.view(N, L, H, d).transpose(1, 2) - ref).abs().max()),
+                   "max_abs_bf16_stored_minus_torch": float((out_st.view(N, L, H, d).transpose(1, 2) - ref).abs().max())}
             for who, t in times.items():
                 ms = sorted(t)[len(t) // 2]
                 row[who + "_ms"] = ms
@@ -96,8 +103,9 @@ def main():
                     row[who + "_of_peak"] = row[who + "_tflops"] / PEAK_TF
             row["speedup"] = row["torch_ms"] / row["engine_ms"]
             row["bf16_speedup_over_engine"] = row["engine_ms"] / row["bf16_ms"]
+            row["bf16_stored_speedup_over_bf16"] = row["bf16_ms"] / row["bf16_stored_ms"]
             res["shapes"]["%s_N%d" % (name, N)] = row
-            del q, k, v, out, out16, views, views16, ref
+            del q, k, v, out, out16, views, views16, ref, q16, k16, v16, out_st
             torch.cuda.empty_cache()
     print(json.dumps(res))
 
