@@ -419,6 +419,28 @@ size_t qe_quantlinear_bf16_workspace_bytes(const qe_qparam *x, const qe_qparam *
 int qe_quantlinear_bf16(const qe_qparam *x, const qe_qparam *w, const float *bias, int64_t B, int32_t K, int32_t O,
                         float post_scale, uint16_t *out, void *workspace, size_t workspace_bytes, qe_stream_t stream);
 
+/* qe_quantlinear_bf16_input -- qe_quantlinear_float_input(_residual) on activations that are bf16 in memory (the context
+ * qe_attention_bf16_ctx wrote, in front of out_proj):
+ *   out = qe_quantlinear_float_input(fp32(x), w, bias, B, K, O)  [+ residual]
+ * x  B x K row-major bf16 bit patterns; fp32(x) are the values they denote (exact).  residual NULL: none; given, one fp32 add
+ * of residual follows, so the with-residual result is the no-residual result plus residual, bit for bit.  out == residual
+ * (in place) is allowed; any other overlap of out with residual or x returns QE_ERR_ARG, as do a NULL x or out, an odd x and
+ * an out or residual that is not 4-byte aligned.  w, bias, B, K, O and their checks as qe_quantlinear_float_input_residual.
+ * _path: 1 = the bf16-input MFMA kernel (8-bit weights, K % 32 == 0, x 16-byte aligned, QE_LIN_F32_MFMA not 0; the entry
+ *        point also wants out 16-byte aligned, which a query cannot see): a row of x is the matrix cores' operand as stored --
+ *        one v_mfma_f32_32x32x16_bf16 per product where the float-input kernel's exact three-way split issues three; each
+ *        product bf16 x centred integer code is exact in fp32, the fp32 accumulation and the fp32 row sum round, so the
+ *        result meets the float-input kernels' parity rule against float64 and is NOT bit-identical to them.  A NaN or inf
+ *        in a row of x makes that row's outputs non-finite (NaN where the reference's chain keeps inf) and no other row's.
+ *        0 = one elementwise pass widens x to fp32 at the front of the workspace, then the float-input plan runs on the
+ *        copy: bit-identical to qe_quantlinear_float_input(_residual) on the widened rows.
+ * workspace: _workspace_bytes() bytes, 16-byte aligned: 0 on path 1; on path 0 B * K * 4 (rounded up to 16) plus
+ *        qe_quantlinear_float_input_residual_workspace_bytes of the widened problem.                                   */
+int qe_quantlinear_bf16_input_path(const uint16_t *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O);
+size_t qe_quantlinear_bf16_input_workspace_bytes(const uint16_t *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O);
+int qe_quantlinear_bf16_input(const uint16_t *x, const qe_qparam *w, const float *bias, int64_t B, int32_t K, int32_t O,
+                              const float *residual, float *out, void *workspace, size_t workspace_bytes, qe_stream_t stream);
+
 /* qe_layernorm_quantize_pack -- torch's F.layer_norm over the last dimension of fp32 rows (rows x E, contiguous) and the
  * codes of up to 3 consumer quantisers of the result (q / k / v projections: each its own), reading each row once.
  *   ln = (x - mean) * rstd * gamma + beta, mean = sum(x) / E, var = sum((x - mean)^2) / E (centred: not E[x^2] - mean^2),
@@ -547,6 +569,20 @@ int qe_attention_bf16_stored(const uint16_t *q, const uint16_t *k, const uint16_
                              int64_t q_rn, int64_t q_rt, int64_t kv_rn, int64_t kv_rt, int64_t o_rn, int64_t o_rt,
                              float scale, const float *mask, int64_t mask_sn, int64_t mask_sh, const float *key_bias,
                              int causal, qe_stream_t stream);
+
+/* qe_attention_bf16_ctx -- qe_attention_bf16_stored with a bf16 context: out holds rows of H*d bf16 elements (bit patterns)
+ * with the row strides o_rn, o_rt, and each element is qe_attention_bf16_stored's fp32 element rounded once to bf16, to
+ * nearest even (a NaN stays a NaN) -- for every head size, operand mode and layout.  Every other parameter, operand and the
+ * numerics contract are qe_attention_bf16_stored's word for word; the argument checks are the same ones in the same order,
+ * the alignment (16 bytes) and the overlap of q / k / v, mask and key_bias with out taken on 2-byte output elements.
+ * For a consumer that reads bf16 rows: qe_quantlinear_bf16_input (out_proj).
+ * qe_attention_bf16_ctx_path (host only): 2 = the bf16 MFMA kernel, -1 = no kernel, as qe_attention_bf16_path.       */
+int qe_attention_bf16_ctx_path(int32_t L, int32_t S, int32_t H, int32_t d, int has_mask, int has_key_bias, int causal);
+int qe_attention_bf16_ctx(const uint16_t *q, const uint16_t *k, const uint16_t *v, uint16_t *out,
+                          int32_t N, int32_t L, int32_t S, int32_t H, int32_t d,
+                          int64_t q_rn, int64_t q_rt, int64_t kv_rn, int64_t kv_rt, int64_t o_rn, int64_t o_rt,
+                          float scale, const float *mask, int64_t mask_sn, int64_t mask_sh, const float *key_bias,
+                          int causal, qe_stream_t stream);
 
 /* ---- auxiliary (no counterpart in the reference's extension) ---------------------------------
  * Global average pool of an fp32 NCHW tensor: out[plane] = mean(x[plane][0..P)) for n_planes = N*C planes of P

@@ -117,6 +117,9 @@ PROTOTYPES = {
     "qe_quantlinear_bf16_path": (_i32, [_pq, _pq, _i64, _i32, _i32, _vp]),
     "qe_quantlinear_bf16_workspace_bytes": (_sz, [_pq, _pq, _i64, _i32, _i32, _vp]),
     "qe_quantlinear_bf16": (_i32, [_pq, _pq, _vp, _i64, _i32, _i32, _f32, _vp, _vp, _sz, _vp]),
+    "qe_quantlinear_bf16_input_path": (_i32, [_vp, _pq, _i64, _i32, _i32]),
+    "qe_quantlinear_bf16_input_workspace_bytes": (_sz, [_vp, _pq, _i64, _i32, _i32]),
+    "qe_quantlinear_bf16_input": (_i32, [_vp, _pq, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "qe_layernorm_quantize_pack_path": (_i32, [_i64, _i32, _i32, _pr, _ppc]),
     "qe_layernorm_quantize_pack_workspace_bytes": (_sz, [_i64, _i32, _i32, _pr, _ppc, _vp]),
     "qe_layernorm_quantize_pack": (_i32, [_vp, _i64, _i32, _vp, _vp, _f32, _i32, _pr, _ppc, _vp, _vp, _vp, _sz, _vp]),
@@ -128,6 +131,8 @@ PROTOTYPES = {
     "qe_attention_bf16": (_i32, _attn + [_vp, _i64, _i64, _vp, _i32, _vp]),
     "qe_attention_bf16_stored_path": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
     "qe_attention_bf16_stored": (_i32, _attn + [_vp, _i64, _i64, _vp, _i32, _vp]),
+    "qe_attention_bf16_ctx_path": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "qe_attention_bf16_ctx": (_i32, _attn + [_vp, _i64, _i64, _vp, _i32, _vp]),
 }
 SYMBOLS = sorted(PROTOTYPES)
 # exported by the library but absent from the header (not part of the public ABI): kept out of SYMBOLS
@@ -619,6 +624,38 @@ def quantlinear_float_input_residual(x, wq, bias, O, residual, out=None, stream=
     return out
 
 
+def _check_bf16_rows(x):
+    import torch
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 2 and x.is_contiguous()):
+        raise ValueError("x must be a contiguous torch.bfloat16 CUDA tensor of shape (B, K)")
+
+
+def quantlinear_bf16_input_path(x, wq, B, K, O):
+    """qe_quantlinear_bf16_input_path: 1 = the bf16-input MFMA kernel reads the rows of x as they are stored, 0 = one pass
+    widens them to fp32 and the float-input plan runs on the copy."""
+    return int(lib().qe_quantlinear_bf16_input_path(_ptr(x), ctypes.byref(wq), int(B), int(K), int(O)))
+
+
+def quantlinear_bf16_input(x, wq, bias, O, residual=None, out=None, stream=None):
+    """qe_quantlinear_bf16_input: quantlinear_float_input on a contiguous torch.bfloat16 (B, K) tensor, read in place
+    (+ residual when given: one fp32 add; out=residual: in place).  Anything else as x raises ValueError."""
+    import torch
+    _check_bf16_rows(x)
+    B, K = x.shape
+    if residual is not None:
+        assert residual.is_contiguous() and residual.dtype == torch.float32 and residual.numel() == B * O
+    if out is None:
+        out = torch.empty((B, O), dtype=torch.float32, device=x.device)
+    assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == B * O
+    # the query cannot see `out`: an `out` that is not 16-byte aligned takes path 0 whatever it answers
+    need = int(lib().qe_quantlinear_bf16_input_workspace_bytes(x.data_ptr() if out.data_ptr() % 16 == 0 else 2, ctypes.byref(wq),
+                                                               int(B), int(K), int(O)))
+    ws = _ws(need, x.device)
+    check(lib().qe_quantlinear_bf16_input(x.data_ptr(), ctypes.byref(wq), _ptr(bias), int(B), int(K), int(O), _ptr(residual),
+                                          out.data_ptr(), _ptr(ws), need, _stream(stream)))
+    return out
+
+
 def _rq_array(rqs):
     arr = (QeRequant * max(1, len(rqs)))(*rqs) if rqs else None
     return arr
@@ -689,11 +726,17 @@ def attention_bf16_stored_path(L, S, H, d, has_mask=False, has_key_bias=False, c
                                                    int(bool(causal))))
 
 
+def attention_bf16_ctx_path(L, S, H, d, has_mask=False, has_key_bias=False, causal=False):
+    """qe_attention_bf16_ctx_path: 2 = the bf16 MFMA kernel on bf16 rows with a bf16 context, -1 = no kernel."""
+    return int(lib().qe_attention_bf16_ctx_path(int(L), int(S), int(H), int(d), int(bool(has_mask)), int(bool(has_key_bias)),
+                                                int(bool(causal))))
+
+
 PRECISIONS = ("fp32", "bf16")
 
 
 def attention(q, k, v, N, L, H, S=None, layout="token", scale=None, out=None, stream=None, mask=None, key_bias=None,
-              causal=False, precision="fp32"):
+              causal=False, precision="fp32", out_dtype=None):
     """qe_attention: softmax(scale q k^T) v per (image, head) on fp32 rows of E = H d floats, read in place.
     layout "token": q / out are (N L, E) and k / v (N S, E) rows (a ViT's projections); "seq": (L N, E) and (S N, E)
     (nn.MultiheadAttention with batch_first=False).  S defaults to L, scale to d ** -0.5.  Returns out, shaped like q
@@ -705,10 +748,19 @@ def attention(q, k, v, N, L, H, S=None, layout="token", scale=None, out=None, st
     operands; d % 16 == 0 and d <= 128 only -- any other d raises QeError (unsupported), never the fp32 kernels instead.
     With precision "bf16", q, k and v may be torch.bfloat16 tensors, all three (qe_attention_bf16_stored: the rows are read
     as bf16, q^ = bf16(fp32(q) scale), k and v as stored; out stays fp32).  Mixed dtypes, or bf16 tensors with precision
-    "fp32", raise ValueError."""
+    "fp32", raise ValueError.
+    out_dtype=torch.bfloat16 (qe_attention_bf16_ctx; torch.bfloat16 q / k / v only, ValueError otherwise): the context as a
+    bf16 tensor, each element the fp32 context's rounded to nearest even -- out, when given, is that bf16 tensor.  None (or
+    torch.float32): the fp32 context."""
     if precision not in PRECISIONS:
         raise ValueError("precision must be 'fp32' or 'bf16'")
     import torch
+    if out_dtype not in (None, torch.float32, torch.bfloat16):
+        raise ValueError("out_dtype must be None, torch.float32 or torch.bfloat16")
+    ctx16 = out_dtype == torch.bfloat16
+    if ctx16 and not (q.dtype == k.dtype == v.dtype == torch.bfloat16):
+        raise ValueError("out_dtype=torch.bfloat16 is allowed only with torch.bfloat16 q / k / v (precision='bf16'); got %s, %s, %s"
+                         % (q.dtype, k.dtype, v.dtype))
     S = L if S is None else int(S)
     N, L, H = int(N), int(L), int(H)
     stored = q.dtype == torch.bfloat16
@@ -728,8 +780,8 @@ def attention(q, k, v, N, L, H, S=None, layout="token", scale=None, out=None, st
     else:
         raise ValueError("layout must be 'token' or 'seq'")
     if out is None:
-        out = torch.empty_like(q, dtype=torch.float32)
-    assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == q.numel()
+        out = torch.empty_like(q, dtype=torch.bfloat16 if ctx16 else torch.float32)
+    assert out.is_contiguous() and out.dtype == (torch.bfloat16 if ctx16 else torch.float32) and out.numel() == q.numel()
     scale = float(d ** -0.5 if scale is None else scale)
     if mask is None and key_bias is None and not causal and precision == "fp32":
         check(lib().qe_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), N, L, S, H, d, q_rn, q_rt, kv_rn,
@@ -752,7 +804,7 @@ def attention(q, k, v, N, L, H, S=None, layout="token", scale=None, out=None, st
         if not (torch.is_tensor(key_bias) and key_bias.is_cuda and key_bias.is_contiguous()
                 and key_bias.dtype == torch.float32 and tuple(key_bias.shape) == (N, S)):
             raise ValueError("key_bias must be a contiguous fp32 CUDA tensor of shape (N, S)")
-    run = lib().qe_attention_bf16_stored if stored else lib().qe_attention_bf16 if precision == "bf16" else lib().qe_attention_masked
+    run = lib().qe_attention_bf16_ctx if ctx16 else lib().qe_attention_bf16_stored if stored else lib().qe_attention_bf16 if precision == "bf16" else lib().qe_attention_masked
     check(run(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), N, L, S, H, d, q_rn, q_rt, kv_rn, kv_rt, q_rn, q_rt, scale,
               _ptr(mask), mask_sn, mask_sh, _ptr(key_bias), 1 if causal else 0, _stream(stream)))
     return out

@@ -350,7 +350,7 @@ static int attn_run(const float *q, const float *k, const float *v, float *out, 
     const int path = attn_path(L, S, H, d);
     AttnArgs a;
     int mode;
-    if (const int e = attn_prepare(q, k, v, sizeof(float), out, N, L, S, H, d, q_rn, q_rt, kv_rn, kv_rt, o_rn, o_rt, scale, mask, mask_sn,
+    if (const int e = attn_prepare(q, k, v, sizeof(float), out, sizeof(float), N, L, S, H, d, q_rn, q_rt, kv_rn, kv_rt, o_rn, o_rt, scale, mask, mask_sn,
                                    mask_sh, key_bias, causal, path, a, mode))
         return e;
     attn_dispatch_mode(mode, [&](auto m) { launch_mode<decltype(m)::value>(a, path, static_cast<hipStream_t>(stream)); });

@@ -250,7 +250,7 @@ static int attn_bf16_run(const float *q, const float *k, const float *v, float *
     AttnArgs a;
     int mode;
     // a head size without a bf16 instance is refused here: never the fp32 kernels instead
-    if (const int e = attn_prepare(q, k, v, sizeof(float), out, N, L, S, H, d, q_rn, q_rt, kv_rn, kv_rt, o_rn, o_rt, scale, mask, mask_sn,
+    if (const int e = attn_prepare(q, k, v, sizeof(float), out, sizeof(float), N, L, S, H, d, q_rn, q_rt, kv_rn, kv_rt, o_rn, o_rt, scale, mask, mask_sn,
                                    mask_sh, key_bias, causal, attn_bf16_path(L, S, H, d), a, mode))
         return e;
     attn_dispatch_mode(mode, [&](auto m) { attn_launch_rows32<AttnBf16, decltype(m)::value>(a, static_cast<hipStream_t>(stream)); });

@@ -1,5 +1,5 @@
 // qe_attention_common.hpp -- what the attention cores (qe_attention.hip: fp32, qe_attention_bf16.hip: bf16 MFMA on fp32
-// rows, qe_attention_bf16_stored.hip: the same on bf16 rows) share: the
+// rows, qe_attention_bf16_stored.hip: the same on bf16 rows, qe_attention_bf16_ctx.hip: that one with a bf16 context) share: the
 // argument struct and the MODE bits, every check an entry point makes before it launches (attn_prepare), and the two
 // switches that turn the runtime mode and head size into a kernel instance (attn_dispatch_mode, attn_launch_rows32), with
 // the launch geometry of the kernels that give a wave 32 query rows.  No device code: attn_mfma_kernel and attn_bf16_kernel
@@ -15,7 +15,7 @@ namespace qe {
 
 struct AttnArgs {
     const float *q, *k, *v;                          // attn_bf16_stored_kernel: rows of bf16 behind the same three pointers
-    float *out;
+    float *out;                                      // attn_bf16_ctx_kernel: rows of bf16 behind this pointer
     int64_t q_rn, q_rt, kv_rn, kv_rt, o_rn, o_rt;    // in rows of H*d elements
     int N, L, S, H, d;
     int qgroups;                                     // workgroups per (image, head)
@@ -106,12 +106,14 @@ inline void row_span(const void *p, int N, int T, int64_t rn, int64_t rt, int64_
     hi = lo + (uintptr_t)((last + 1) * E) * elem;
 }
 
-// Everything qe_attention, qe_attention_masked, qe_attention_bf16 and qe_attention_bf16_stored check before a launch, in one
+// Everything qe_attention, qe_attention_masked, qe_attention_bf16, qe_attention_bf16_stored and qe_attention_bf16_ctx check
+// before a launch, in one
 // order, so that an argument list that breaks two rules gets one answer from all of them.  in_elem = bytes per element of
-// q, k and v (4: fp32 rows, 2: bf16 rows; out, mask and key_bias are fp32 for every entry point).  `path` is the entry point's own path function's
+// q, k and v (4: fp32 rows, 2: bf16 rows), out_elem = bytes per element of out (4, or 2: qe_attention_bf16_ctx's bf16 rows);
+// mask and key_bias are fp32 for every entry point.  `path` is the entry point's own path function's
 // answer for (L, S, H, d), < 0: no kernel.  On QE_OK `a` is filled (but for qgroups) and `mode` is the instance's MODE.
 // Both grid limits hold for every entry point: the second is the fp32 VALU kernel's.
-inline int attn_prepare(const void *q, const void *k, const void *v, size_t in_elem, float *out, int32_t N, int32_t L, int32_t S, int32_t H,
+inline int attn_prepare(const void *q, const void *k, const void *v, size_t in_elem, void *out, size_t out_elem, int32_t N, int32_t L, int32_t S, int32_t H,
                         int32_t d, int64_t q_rn, int64_t q_rt, int64_t kv_rn, int64_t kv_rt, int64_t o_rn, int64_t o_rt,
                         float scale, const float *mask, int64_t mask_sn, int64_t mask_sh, const float *key_bias, int causal,
                         int path, AttnArgs &a, int &mode)
@@ -128,7 +130,7 @@ inline int attn_prepare(const void *q, const void *k, const void *v, size_t in_e
     if (path < 0) return QE_ERR_UNSUPPORTED;
     const int64_t E = (int64_t)H * d;
     uintptr_t olo, ohi;
-    row_span(out, N, L, o_rn, o_rt, E, sizeof(float), olo, ohi);
+    row_span(out, N, L, o_rn, o_rt, E, out_elem, olo, ohi);
     const void *ins[3] = {q, k, v};
     const int64_t rn[3] = {q_rn, kv_rn, kv_rn}, rt[3] = {q_rt, kv_rt, kv_rt};
     const int len[3] = {L, S, S};
@@ -150,7 +152,7 @@ inline int attn_prepare(const void *q, const void *k, const void *v, size_t in_e
     const int64_t rows = (int64_t)N * H * L;
     if ((int64_t)N * H * ceil_div(L, 32) > 0x7fffffffLL || ceil_div64(rows, 4) > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
     a = {};
-    a.q = static_cast<const float *>(q); a.k = static_cast<const float *>(k); a.v = static_cast<const float *>(v); a.out = out;
+    a.q = static_cast<const float *>(q); a.k = static_cast<const float *>(k); a.v = static_cast<const float *>(v); a.out = static_cast<float *>(out);
     a.q_rn = q_rn; a.q_rt = q_rt; a.kv_rn = kv_rn; a.kv_rt = kv_rt; a.o_rn = o_rn; a.o_rt = o_rt;
     a.N = N; a.L = L; a.S = S; a.H = H; a.d = d; a.scale = scale;
     a.mask = mask; a.key_bias = key_bias; a.mask_sn = mask_sn; a.mask_sh = mask_sh;

@@ -15,6 +15,7 @@
 // (with fused multiply-add, as nvcc contracts it).
 #include "qe_common.h"
 #include "qe_elementwise.hpp"
+#include "qe_linear_bf16in.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -849,15 +850,7 @@ constexpr int LF_T = 128, LF_K = 32;
 constexpr int LF_PLANE = LF_T * LF_K * 2;                 // bytes of one [128][32] bf16 image (8 KB)
 constexpr size_t linf_lds_bytes() { return (size_t)4 * LF_PLANE + LF_T * sizeof(float) + 2 * LF_T * sizeof(float4); }
 
-// The integer c a column's weight codes are centred on before the bf16 conversion: rint(zw), clamped to the code range so
-// that |q - c| <= 255 stays exact in bf16.  The MFMAs then sum x (q - c), and the epilogue subtracts only (zw - c) S_x: with
-// zw itself there (zw ~ 128 for unsigned codes, asymmetric weights) the two fp32 terms sw (S_xq - zw S_x) are large and
-// cancel, and their rounding error was many times the reference chain's on non-zero-mean activations.
-__device__ __forceinline__ float linf_centre(float zw, int w_sign)
-{
-    const float c = rintf(zw);
-    return w_sign ? fminf(fmaxf(c, -128.0f), 127.0f) : fminf(fmaxf(c, 0.0f), 255.0f);
-}
+// (linf_centre, the integer c a column's weight codes are centred on: qe_linear_bf16in.hpp, shared with the bf16-input kernel)
 
 template <int EPI = LIN_F32>   // LIN_F32 | LIN_RES
 __global__ __launch_bounds__(256, 2) void linear_f32_mfma_kernel(const LinArgs a)
@@ -1016,7 +1009,8 @@ __global__ __launch_bounds__(256, 2) void linear_f32_mfma_kernel(const LinArgs a
 // The kernel of a plan.  0..4 are qe_quantlinear_form's numbers (0: the order-preserving fp32 kernel, 1..4: the int8 MFMA
 // kernels, one choice for every epilogue); the fp32-activation problems run one of the last two.
 enum { LIN_FORM_CHAIN = 0, LIN_FORM_NJ2 = 1, LIN_FORM_NJ4 = 2, LIN_FORM_W8 = 3, LIN_FORM_W4 = 4,
-       LIN_FORM_CHAIN_F = 5, LIN_FORM_BF16 = 6 };   // linear_generic_kernel<true>, linear_f32_mfma_kernel
+       LIN_FORM_CHAIN_F = 5, LIN_FORM_BF16 = 6,     // linear_generic_kernel<true>, linear_f32_mfma_kernel
+       LIN_FORM_BF16IN = 7 };                       // bf16 activations: linear_bf16in_kernel (qe_linear_bf16in.hip)
 
 // What is asked.  The plan reads the operands' alignment only; a query leaves the pointers it does not know null, which
 // reads as aligned.
@@ -1024,6 +1018,8 @@ struct LinRequest {
     bool f32_x = false;                 // fp32 activations at xf, else the packed activations x
     const qe_qparam *x = nullptr, *w = nullptr;
     const float *xf = nullptr;
+    bool bf16_x = false;                // bf16 activations at x16 (qe_quantlinear_bf16_input; epi LIN_F32 | LIN_RES)
+    const uint16_t *x16 = nullptr;
     int64_t B = 0;
     int K = 0, O = 0;
     int epi = LIN_F32;                  // LIN_CODES*: the consumer's quantiser rq, codes and status; LIN_RES: out = y + res;
@@ -1039,7 +1035,9 @@ struct LinPlan {
     bool two_pass = false;   // the kernel writes y into the workspace, then the elementwise pass applies the epilogue
     int epi = LIN_F32;       // the epilogue compiled into the kernel that runs
     int64_t blocks = 0; int threads = 256; size_t lds = 0;   // grid, block, dynamic LDS
-    size_t ws = 0;           // workspace bytes: y of a two-pass form
+    size_t ws = 0;           // workspace bytes: y of a two-pass form (behind the widened rows of a bf16-input request)
+    size_t widen = 0;        // bf16 activations that linear_bf16in_kernel does not take: bytes of their fp32 copy at the
+                             // front of the workspace; the rest of the plan is the float-input plan on that copy
 };
 
 static LinRequest lin_req(const qe_qparam *x, const qe_qparam *w, int64_t B, int K, int O, int epi = LIN_F32,
@@ -1057,6 +1055,22 @@ static LinRequest linf_req(const float *x, const qe_qparam *w, int64_t B, int K,
     return r;
 }
 
+static LinRequest linb_req(const uint16_t *x, const qe_qparam *w, int64_t B, int K, int O, int epi = LIN_F32)
+{
+    LinRequest r = lin_req(nullptr, w, B, K, O, epi);
+    r.bf16_x = true; r.x16 = x;
+    return r;
+}
+
+// The float-input request a bf16-input request becomes once its rows are widened to fp32 at `xf` (a query: NULL, the
+// 16-byte aligned front of the workspace)
+static LinRequest linb_widened(const LinRequest &r, const float *xf)
+{
+    LinRequest f = r;
+    f.bf16_x = false; f.x16 = nullptr; f.f32_x = true; f.xf = xf;
+    return f;
+}
+
 // The checks every entry point starts with, in this order
 static int check_lin(const LinRequest &r)
 {
@@ -1066,7 +1080,7 @@ static int check_lin(const LinRequest &r)
         return q->n_param != 1 && q->n_param != n_expected ? QE_ERR_ARG : QE_OK;
     };
     if (r.B < 0 || r.K < 0 || r.O < 0) return QE_ERR_ARG;
-    if (int rc = r.f32_x ? QE_OK : check_q(r.x, r.B)) return rc;
+    if (int rc = r.f32_x || r.bf16_x ? QE_OK : check_q(r.x, r.B)) return rc;
     return check_q(r.w, r.O);
 }
 
@@ -1078,6 +1092,23 @@ static LinPlan plan_linear(const LinRequest &r)
     const int K = r.K, O = r.O;
     const char *e;
     bool mfma = r.w != nullptr && r.w->n_bits == 8 && B > 0 && O > 0 && al16(ad(r.w->data));
+    if (r.bf16_x) {
+        // bf16 rows are the MFMA operand as stored: whole 32-deep stages, 16-byte loads of x, `out` written in 16-byte pieces.
+        // Under QE_LIN_F32_MFMA=0, and for everything else, one pass widens the rows and the float-input plan runs on them.
+        if (mfma && (K % LB_K) == 0 && K >= LB_K && al16(ad(r.x16)) && al16(ad(r.out)) &&
+            !((e = env_get("QE_LIN_F32_MFMA")) && atoi(e) == 0)) {
+            LinPlan p;
+            p.form = LIN_FORM_BF16IN;
+            p.epi = r.epi;                               // LIN_F32 | LIN_RES: both are instances of the kernel
+            p.blocks = ((B + LB_T - 1) / LB_T) * ((O + LB_T - 1) / LB_T);
+            p.lds = linb_lds_bytes();
+            return p;
+        }
+        LinPlan p = plan_linear(linb_widened(r, nullptr));
+        p.widen = B > 0 && K > 0 ? (((size_t)B * (size_t)K * sizeof(float) + 15) & ~(size_t)15) : 0;
+        p.ws += p.widen;
+        return p;
+    }
     if (r.f32_x)   // bf16 MFMA on the split activations, whole 32-deep stages; QE_LIN_F32_MFMA=0: the fp32 chain kernel only
         mfma = mfma && (K % LF_K) == 0 && K >= LF_K && al16(ad(r.xf)) && !((e = env_get("QE_LIN_F32_MFMA")) && atoi(e) == 0);
     else           // K < 2^17: int32 accumulation of products up to 2^14 cannot overflow (deeper reductions take the fp32
@@ -1264,6 +1295,28 @@ static int run_linear(const LinRequest &r, void *workspace, size_t workspace_byt
                                 rq->qmin, rq->qmax, rq->n_bits, rq->sign, r.codes, nullptr, r.status, stream);
 }
 
+// A validated, non-empty bf16-input request: linear_bf16in_kernel, or the widening pass and the float-input plan behind it
+static int run_linear_bf16in(const LinRequest &r, void *workspace, size_t workspace_bytes, qe_stream_t stream)
+{
+    const LinPlan p = plan_linear(r);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (p.form == LIN_FORM_BF16IN) {
+        if (p.blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
+        LinBf16Args a = {};
+        a.x = r.x16; a.w = static_cast<const uint8_t *>(r.w->data); a.w_scale = r.w->scale; a.w_zero = r.w->zero; a.bias = r.bias;
+        a.res = r.res; a.out = r.out; a.w_sign = r.w->sign; a.w_per_tensor = r.w->n_param == 1; a.B = r.B; a.K = r.K; a.O = r.O;
+        launch_linear_bf16in(a, p.epi == LIN_RES, p.blocks, s);
+        QE_LAUNCH_CHECK();
+        return QE_OK;
+    }
+    if (p.ws > 0 && (workspace == nullptr || workspace_bytes < p.ws || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0))
+        return QE_ERR_WORKSPACE;
+    float *xf = static_cast<float *>(workspace);
+    launch_widen_bf16(r.x16, xf, r.B * (int64_t)r.K, s);
+    QE_LAUNCH_CHECK();
+    return run_linear(linb_widened(r, xf), static_cast<uint8_t *>(workspace) + p.widen, workspace_bytes - p.widen, stream);
+}
+
 // residual and out: the same buffer or disjoint
 static bool res_overlap_ok(const float *res, const float *out, int64_t n)
 {
@@ -1416,4 +1469,36 @@ extern "C" int qe_quantlinear_float_input_residual(const float *x, const qe_qpar
     if (B == 0 || O == 0) return QE_OK;
     if (x == nullptr || residual == nullptr || out == nullptr || !res_overlap_ok(residual, out, B * (int64_t)O)) return QE_ERR_ARG;
     return run_linear(r, workspace, workspace_bytes, stream);
+}
+
+// bf16 activations (include/quant_engine.h): path 1 is linear_bf16in_kernel, which reads the rows as its MFMA operand; path 0
+// widens them into the workspace and runs the float-input plan on the copy.
+extern "C" int qe_quantlinear_bf16_input_path(const uint16_t *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O)
+{
+    return qe::plan_linear(qe::linb_req(x, w, B, K, O, qe::LIN_RES)).form == qe::LIN_FORM_BF16IN;
+}
+
+extern "C" size_t qe_quantlinear_bf16_input_workspace_bytes(const uint16_t *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O)
+{
+    return qe::plan_linear(qe::linb_req(x, w, B, K, O, qe::LIN_RES)).ws;
+}
+
+extern "C" int qe_quantlinear_bf16_input(const uint16_t *x, const qe_qparam *w, const float *bias, int64_t B, int32_t K, int32_t O,
+                                         const float *residual, float *out, void *workspace, size_t workspace_bytes,
+                                         qe_stream_t stream)
+{
+    using namespace qe;
+    LinRequest r = linb_req(x, w, B, K, O, residual != nullptr ? LIN_RES : LIN_F32);
+    r.bias = bias; r.res = residual; r.out = out;
+    if (int rc = check_lin(r)) return rc;
+    if (B == 0 || O == 0) return QE_OK;
+    if ((x == nullptr && K > 0) || out == nullptr) return QE_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(x) & 1) != 0 || (reinterpret_cast<uintptr_t>(out) & 3) != 0 ||
+        (reinterpret_cast<uintptr_t>(residual) & 3) != 0)
+        return QE_ERR_ARG;
+    const uintptr_t xlo = reinterpret_cast<uintptr_t>(x), xhi = xlo + (uintptr_t)B * (uintptr_t)K * sizeof(uint16_t);
+    const uintptr_t olo = reinterpret_cast<uintptr_t>(out), ohi = olo + (uintptr_t)B * (uintptr_t)O * sizeof(float);
+    if (xlo < ohi && olo < xhi) return QE_ERR_ARG;
+    if (residual != nullptr && !res_overlap_ok(residual, out, B * (int64_t)O)) return QE_ERR_ARG;
+    return run_linear_bf16in(r, workspace, workspace_bytes, stream);
 }

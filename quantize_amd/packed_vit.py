@@ -22,6 +22,9 @@ attention="engine_bf16" the same, its two products on the bf16 matrix cores (qe_
 qkv="bf16" (fused route with attention="engine_bf16" only) has the three projections write bf16 rows (qe_quantlinear_bf16,
 q already multiplied by d ** -0.5) that the attention kernel reads as stored (qe_attention_bf16_stored, scale 1): the values
 the bf16 kernel would have rounded to anyway, so logits and block outputs are bit-identical to qkv="fp32".
+ctx="bf16" (on top of qkv="bf16") has the attention kernel write its context as bf16 rows as well (qe_attention_bf16_ctx: the
+fp32 context rounded once) and out_proj read them as stored (qe_quantlinear_bf16_input, residual add in its epilogue): one
+rounding of the context to 8 significant bits, so NOT bit-identical to ctx="fp32".
 The C entry points take their two-pass form wherever the fused form is not eligible (sub-8-bit or per-channel consumer codes, non-MFMA shapes, QE_LIN_EPI=0), so every step of
 the fused route exists for every model the layers route runs.  With check=False the fused route makes no device -> host
 copy or synchronisation: every range flag accumulates in one device int32, read once at the end when check=True.
@@ -39,6 +42,7 @@ from .packed_resnet import pack_codes
 
 ATTENTION = ("torch", "engine", "engine_bf16")
 QKV = ("fp32", "bf16")
+CTX = ("fp32", "bf16")
 
 
 def _check_attention(attention):
@@ -53,11 +57,19 @@ def _check_qkv(qkv, route, attention):
         raise ValueError("qkv='bf16' needs route='fused' and attention='engine_bf16' (the bf16 attention core reads the rows)")
 
 
-def _attention(Q, K, V, N, L, H, attention="torch"):
+def _check_ctx(ctx, route, attention, qkv):
+    if ctx not in CTX:
+        raise ValueError("ctx must be 'fp32' or 'bf16'")
+    if ctx == "bf16" and (route != "fused" or attention != "engine_bf16" or qkv != "bf16"):
+        raise ValueError("ctx='bf16' needs route='fused', attention='engine_bf16' and qkv='bf16' (the bf16 attention core on "
+                         "bf16 rows writes the context)")
+
+
+def _attention(Q, K, V, N, L, H, attention="torch", ctx="fp32"):
     """(N L, E) fp32 projections -> (N L, E) context: softmax(Q K^T / sqrt(d)) V per head, fp32.  bf16 projections (Q
-    already scaled; "engine_bf16" only) are read as stored, with scale 1."""
+    already scaled; "engine_bf16" only) are read as stored, with scale 1; with ctx "bf16" their context is bf16 rows too."""
     if Q.dtype == torch.bfloat16:
-        return capi.attention(Q, K, V, N, L, H, scale=1.0, precision="bf16")
+        return capi.attention(Q, K, V, N, L, H, scale=1.0, precision="bf16", out_dtype=torch.bfloat16 if ctx == "bf16" else None)
     if attention == "engine":
         return capi.attention(Q, K, V, N, L, H)
     if attention == "engine_bf16":
@@ -148,21 +160,25 @@ class PackedViT:
         return out + [self.head]
 
     # ---- the two routes ----
-    def __call__(self, images, route="fused", check=True, attention="torch", qkv="fp32"):
-        return self.forward(images, route, check, attention=attention, qkv=qkv)[0]
+    def __call__(self, images, route="fused", check=True, attention="torch", qkv="fp32", ctx="fp32"):
+        return self.forward(images, route, check, attention=attention, qkv=qkv, ctx=ctx)[0]
 
-    def forward(self, images, route="fused", check=True, keep_blocks=False, attention="torch", qkv="fp32"):
+    def forward(self, images, route="fused", check=True, keep_blocks=False, attention="torch", qkv="fp32", ctx="fp32"):
         """(logits, [block outputs (N, L, E)] if keep_blocks else None).  attention: "torch" (F.scaled_dot_product_attention)
         "engine" (the fp32 qe_attention kernel) or "engine_bf16" (qe_attention_bf16), in either route.  qkv: "fp32", or
         "bf16" (route "fused" with attention "engine_bf16" only; ValueError otherwise, before any launch): the q / k / v
-        projections as bf16 rows, bit-identical results."""
+        projections as bf16 rows, bit-identical results.  ctx: "fp32", or "bf16" (with qkv "bf16" only; ValueError otherwise,
+        before any launch): the attention context as bf16 rows that out_proj reads in place -- the context rounded once."""
         if route not in ("fused", "layers"):
             raise ValueError("route must be 'fused' or 'layers'")
         _check_attention(attention)
         _check_qkv(qkv, route, attention)
+        _check_ctx(ctx, route, attention, qkv)
         kw = {} if attention == "torch" else {"attention": attention}    # the default keeps block()'s five-argument call
         if qkv != "fp32":
             kw["qkv"] = qkv
+        if ctx != "fp32":
+            kw["ctx"] = ctx
         images = images.contiguous()
         N = images.shape[0]
         status = torch.zeros(1, dtype=torch.int32, device=images.device)
@@ -204,18 +220,19 @@ class PackedViT:
         x = torch.cat([self.class_token.expand(N, -1, -1), t], dim=1) + self.pos
         return x.reshape(-1, self.E).contiguous()
 
-    def block(self, b, x, N, route, status=None, attention="torch", observe=None, qkv="fp32"):
+    def block(self, b, x, N, route, status=None, attention="torch", observe=None, qkv="fp32", ctx="fp32"):
         """One encoder block on (N L, E) fp32 rows -> (N L, E).  The fused route updates x in place.  observe: see _run
-        (`layers` route).  qkv: see forward."""
+        (`layers` route).  qkv, ctx: see forward."""
         _check_attention(attention)
         _check_qkv(qkv, route, attention)
+        _check_ctx(ctx, route, attention, qkv)
         E, H = self.E, self.num_heads
         L = x.shape[0] // N
         if route == "layers":
             y = F.layer_norm(x, (E,), b.ln1[0], b.ln1[1], self.eps)
             Q, K, V = (_run(lin, y, observe) for lin in (b.q, b.k, b.v))
-            ctx = _attention(Q, K, V, N, L, H, attention)
-            x = x + capi.quantlinear_float_input(ctx, b.attn.out_wq(), b.attn.out_bias, E)
+            c = _attention(Q, K, V, N, L, H, attention)
+            x = x + capi.quantlinear_float_input(c, b.attn.out_wq(), b.attn.out_bias, E)
             y = F.layer_norm(x, (E,), b.ln2[0], b.ln2[1], self.eps)
             h = F.gelu(_run(b.fc1, y, observe))
             return x + _run(b.fc2, h, observe)
@@ -230,8 +247,11 @@ class PackedViT:
                        for lin, c, s in zip((b.q, b.k, b.v), codes, post))
         else:
             Q, K, V = (capi.quantlinear(lin.xq(c), lin.wq(), lin.bias, rows, lin.K, lin.O) for lin, c in zip((b.q, b.k, b.v), codes))
-        ctx = _attention(Q, K, V, N, L, H, attention)
-        x = capi.quantlinear_float_input_residual(ctx, b.attn.out_wq(), b.attn.out_bias, E, x, out=x)
+        c = _attention(Q, K, V, N, L, H, attention, ctx)
+        if ctx == "bf16":
+            x = capi.quantlinear_bf16_input(c, b.attn.out_wq(), b.attn.out_bias, E, residual=x, out=x)
+        else:
+            x = capi.quantlinear_float_input_residual(c, b.attn.out_wq(), b.attn.out_bias, E, x, out=x)
         c1 = capi.layernorm_quantize_pack(x, b.ln2[0], b.ln2[1], self.eps, [b.fc1.requant()], status=status)[0][0]
         c2 = capi.quantlinear_requant(b.fc1.xq(c1), b.fc1.wq(), b.fc1.bias, rows, b.fc1.K, b.fc1.O, b.fc2.requant(), act="gelu",
                                       status=status)[0]

@@ -5,7 +5,8 @@ reads them in place, torch gets the (N, H, L, d) views the ViT's _attention pass
 with device events after a warm-up; medians are reported.  For orientation a fourth column times torch's own bf16 SDPA on
 inputs cast to bf16 beforehand (`torch_bf16_precast`): it reads half the bytes the other three read and writes bf16; and next
 to it `bf16_stored`, the engine's bf16 kernel on q / k / v cast to bf16 beforehand (qe_attention_bf16_stored: bf16 rows in,
-fp32 out -- what the ViT runs with qkv="bf16").
+fp32 out -- what the ViT runs with qkv="bf16"), and `bf16_ctx`, the same kernel with a bf16 context (qe_attention_bf16_ctx: bf16
+rows in, bf16 rows out -- ctx="bf16").
 Useful TFLOP/s counts 4 N H L S d (QK^T and PV, padding not counted); `of_peak` is the share of the 157.3 TFLOP/s fp32
 matrix-pipe peak, given for the two fp32 columns only.  Prints one JSON line (`metric` keeps its name, attention_core_fp32:
 the buffers are fp32 in every column but the pre-cast one).
@@ -69,8 +70,9 @@ def main():
             out16 = torch.empty_like(q)
             q16, k16, v16 = (t.to(torch.bfloat16) for t in (q, k, v))      # (N L, E) bf16 rows, cast outside the timed region
             out_st = torch.empty_like(q)
+            out_ctx = torch.empty_like(q16)
             tkw16 = {n: (m.to(torch.bfloat16) if torch.is_tensor(m) else m) for n, m in tkw.items()}
-            times = {"engine": [], "bf16": [], "bf16_stored": [], "torch": [], "torch_bf16_precast": []}
+            times = {"engine": [], "bf16": [], "bf16_stored": [], "bf16_ctx": [], "torch": [], "torch_bf16_precast": []}
             with torch.no_grad():
                 for i in range(args.warmup + args.steps):
                     for who in times:
@@ -82,6 +84,8 @@ def main():
                             capi.attention(q, k, v, N, L, H, out=out16, precision="bf16", **ekw)
                         elif who == "bf16_stored":
                             capi.attention(q16, k16, v16, N, L, H, out=out_st, precision="bf16", **ekw)
+                        elif who == "bf16_ctx":
+                            capi.attention(q16, k16, v16, N, L, H, out=out_ctx, precision="bf16", out_dtype=torch.bfloat16, **ekw)
                         elif who == "torch_bf16_precast":
                             F.scaled_dot_product_attention(*views16, **tkw16)
                         else:
@@ -104,8 +108,10 @@ def main():
             row["speedup"] = row["torch_ms"] / row["engine_ms"]
             row["bf16_speedup_over_engine"] = row["engine_ms"] / row["bf16_ms"]
             row["bf16_stored_speedup_over_bf16"] = row["bf16_ms"] / row["bf16_stored_ms"]
+            row["bf16_ctx_speedup_over_bf16_stored"] = row["bf16_stored_ms"] / row["bf16_ctx_ms"]
+            row["bf16_ctx_is_bf16_stored_rounded"] = bool(torch.equal(out_ctx.view(torch.int16), out_st.to(torch.bfloat16).view(torch.int16)))
             res["shapes"]["%s_N%d" % (name, N)] = row
-            del q, k, v, out, out16, views, views16, ref, q16, k16, v16, out_st
+            del q, k, v, out, out16, views, views16, ref, q16, k16, v16, out_st, out_ctx
             torch.cuda.empty_cache()
     print(json.dumps(res))
 

@@ -11,8 +11,10 @@ operands both routes share), not counters.  --attention torch engine engine_bf16
 fp32 and bf16 attention cores (keys fused_engine_ms, layers_engine_bf16_ms, ...); the default, torch, keeps the output as
 it was.  --qkv fp32 bf16 adds, for the fused route with engine_bf16 only (the one combination that takes it), the forward with
 the q / k / v projections stored as bf16 rows (key fused_engine_bf16_qkv_bf16_ms); it alternates with the others step by step.
+--ctx fp32 bf16 adds, on top of --qkv bf16 (the one combination that takes it), the forward whose attention context is bf16
+rows that out_proj reads in place (key fused_engine_bf16_qkv_bf16_ctx_bf16_ms), alternating in the same way.
 usage: python tools/bench_vit_forward.py [--batches 64 256] [--steps 10] [--warmup 2] [--attention torch [engine] [engine_bf16]]
-                                         [--qkv fp32 [bf16]]"""
+                                         [--qkv fp32 [bf16]] [--ctx fp32 [bf16]]"""
 import argparse
 import json
 import os
@@ -40,6 +42,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--attention", nargs="+", choices=["torch", "engine", "engine_bf16"], default=["torch"])
     ap.add_argument("--qkv", nargs="+", choices=["fp32", "bf16"], default=["fp32"])
+    ap.add_argument("--ctx", nargs="+", choices=["fp32", "bf16"], default=["fp32"])
     args = ap.parse_args()
     import torch
     from quantize_amd.packed_vit import CONFIGS, PackedViT, calibrated_state_dict
@@ -51,25 +54,28 @@ def main():
     for N in args.batches:
         g = torch.Generator(device="cpu").manual_seed(N)
         x = torch.randn(N, 3, 224, 224, generator=g).to(dev)
-        runs = [(route, att, qkv) for att in args.attention for route in ("fused", "layers")
-                for qkv in args.qkv if qkv == "fp32" or (route, att) == ("fused", "engine_bf16")]
+        runs = [(route, att, qkv, ctx) for att in args.attention for route in ("fused", "layers")
+                for qkv in args.qkv if qkv == "fp32" or (route, att) == ("fused", "engine_bf16")
+                for ctx in args.ctx if ctx == "fp32" or (route, att, qkv) == ("fused", "engine_bf16", "bf16")]
         times = {r: [] for r in runs}
         with torch.no_grad():
             for i in range(args.warmup + args.steps):
-                for route, att, qkv in runs:
+                for route, att, qkv, ctx in runs:
                     kw = {} if qkv == "fp32" else {"qkv": qkv}
+                    if ctx != "fp32":
+                        kw["ctx"] = ctx
                     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     a.record()
                     model(x, route, check=False, attention=att, **kw) if route == "fused" else model(x, route, attention=att)
                     b.record()
                     torch.cuda.synchronize()
                     if i >= args.warmup:
-                        times[(route, att, qkv)].append(a.elapsed_time(b))
+                        times[(route, att, qkv, ctx)].append(a.elapsed_time(b))
         lay, fus = byte_model(N)
         out = {}
-        for (route, att, qkv), t in times.items():
+        for (route, att, qkv, ctx), t in times.items():
             med = sorted(t)[len(t) // 2]
-            sfx = ("" if att == "torch" else "_" + att) + ("" if qkv == "fp32" else "_qkv_" + qkv)
+            sfx = ("" if att == "torch" else "_" + att) + ("" if qkv == "fp32" else "_qkv_" + qkv) + ("" if ctx == "fp32" else "_ctx_" + ctx)
             out["%s%s_ms" % (route, sfx)] = med
             out["%s%s_img_s" % (route, sfx)] = N / med * 1e3
         out.update({"byte_model_layers_GB": lay / 1e9, "byte_model_fused_GB": fus / 1e9})

@@ -2,7 +2,7 @@
 # VGPRs / scratch / LDS of every kernel of the library: metadata notes of the gfx950 code object in each translation
 # unit's object file (quantize_amd/_ext/obj/*.o).   usage: tools/kernel_resources.sh [obj dir] [name filter]
 # The filter keeps the kernels whose mangled name contains it: `tools/kernel_resources.sh "" attn_bf16_kernel` lists the 112
-# instances of the bf16 attention core, `... attn_mfma_kernel` the fp32 ones, `... attn_bf16_stored` the 112 of the bf16 core on
+# instances of the bf16 attention core, `... attn_mfma_kernel` the fp32 ones, `... attn_bf16_ctx` / `... linear_bf16in` those of the bf16 context route, `... attn_bf16_stored` the 112 of the bf16 core on
 # bf16 rows, `... ELi4EEEvNS_7LinArgs` the four LIN_BF16 instances of the int8 linears; the last line counts what was listed.
 DIR=${1:-quantize_amd/_ext/obj}
 FILTER=${2:-}
