@@ -416,22 +416,8 @@ __global__ __launch_bounds__(256, 2) void linear_mfma_kernel(const LinArgs a)
                         if constexpr (FULL) *reinterpret_cast<uint4 *>(dst) = o8;
                         else if (row < a.B && c8 < a.O) *reinterpret_cast<uint4 *>(dst) = o8;
                     }
-                } else if constexpr (FULL) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) patch[((r & 3) + 8 * (r >> 2) + 4 * h) * 36 + col] = v[r];
-                    const int c4 = n0 + wn * 32 * NJ + j * 32 + 4 * rq;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int rt = 8 * k + rrow;
-                        float4 o4 = *reinterpret_cast<const float4 *>(patch + rt * 36 + 4 * rq);
-                        if constexpr (EPI == LIN_RES) {
-                            const float4 r4 = *reinterpret_cast<const float4 *>(a.res + (row0 + rt) * a.O + c4);
-                            o4.x += r4.x; o4.y += r4.y; o4.z += r4.z; o4.w += r4.w;
-                        }
-                        *reinterpret_cast<float4 *>(a.out + (row0 + rt) * a.O + c4) = o4;
-                        if constexpr (EPI == LIN_RES) __builtin_amdgcn_sched_barrier(0);   // one residual piece in flight (else scratch)
-                    }
-                } else if (vec4) {
+                } else if (FULL || vec4) {
+                    // (the patch write stays a loop in each branch: as a local lambda it changed all ten instances)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) patch[((r & 3) + 8 * (r >> 2) + 4 * h) * 36 + col] = v[r];
                     const int c4 = n0 + wn * 32 * NJ + j * 32 + 4 * rq;
@@ -440,14 +426,14 @@ __global__ __launch_bounds__(256, 2) void linear_mfma_kernel(const LinArgs a)
                         const int rt = 8 * k + rrow;
                         float4 o4 = *reinterpret_cast<const float4 *>(patch + rt * 36 + 4 * rq);
                         const int64_t row = row0 + rt;
-                        if (row < a.B && c4 < a.O) {
+                        if (FULL || (row < a.B && c4 < a.O)) {
                             if constexpr (EPI == LIN_RES) {
                                 const float4 r4 = *reinterpret_cast<const float4 *>(a.res + row * a.O + c4);
                                 o4.x += r4.x; o4.y += r4.y; o4.z += r4.z; o4.w += r4.w;
                             }
                             *reinterpret_cast<float4 *>(a.out + row * a.O + c4) = o4;
                         }
-                        if constexpr (EPI == LIN_RES) __builtin_amdgcn_sched_barrier(0);
+                        if constexpr (EPI == LIN_RES) __builtin_amdgcn_sched_barrier(0);   // one residual piece in flight (else scratch)
                     }
                 } else {
 #pragma unroll
@@ -1000,17 +986,23 @@ __global__ __launch_bounds__(256, 2) void linear_f32_mfma_kernel(const LinArgs a
 }
 
 // ---------------------------------------------------------------------------------------------
-// Host side.  plan_linear decides everything about one linear problem once: the kernel, whether the requested epilogue
+// Host side.  One table (kLinForms) says which kernels exist, their tile and which epilogues each has an instance of.
+// plan_linear decides everything about one linear problem once, from that table: the kernel, whether the requested epilogue
 // runs inside it or as a second pass over the workspace, the grid, block, dynamic LDS and workspace.  It is the only reader
-// of the QE_LIN_* knobs and makes no HIP call (the CPU suite asks the queries on a machine without a GPU).  The C-ABI
-// queries answer from the plan; every entry point validates its arguments, plans and runs the plan.
+// of the QE_LIN_* knobs and makes no HIP call (the CPU suite asks the queries on a machine without a GPU).  run_linear runs
+// the plan of any request, launching what the table names.  Every entry family has one request builder that its queries and
+// its call share; every entry point validates its arguments, builds the request and runs it.
 // ---------------------------------------------------------------------------------------------
 
-// The kernel of a plan.  0..4 are qe_quantlinear_form's numbers (0: the order-preserving fp32 kernel, 1..4: the int8 MFMA
-// kernels, one choice for every epilogue); the fp32-activation problems run one of the last two.
+// The kernel of a plan, named after what it runs.  0..4 are qe_quantlinear_form's numbers (0: the order-preserving fp32
+// kernel, 1..4: the int8 MFMA kernels, one choice for every epilogue); fp32 activations run 5 or 6, bf16 activations 7 or,
+// widened to fp32 first, 5 or 6.
 enum { LIN_FORM_CHAIN = 0, LIN_FORM_NJ2 = 1, LIN_FORM_NJ4 = 2, LIN_FORM_W8 = 3, LIN_FORM_W4 = 4,
-       LIN_FORM_CHAIN_F = 5, LIN_FORM_BF16 = 6,     // linear_generic_kernel<true>, linear_f32_mfma_kernel
-       LIN_FORM_BF16IN = 7 };                       // bf16 activations: linear_bf16in_kernel (qe_linear_bf16in.hip)
+       LIN_FORM_CHAIN_F32 = 5,      // linear_generic_kernel<true>
+       LIN_FORM_F32_SPLIT = 6,      // linear_f32_mfma_kernel: fp32 rows split into three bf16 parts
+       LIN_FORM_BF16_ROWS = 7,      // linear_bf16in_kernel (qe_linear_bf16in.hip): bf16 rows as stored
+       LIN_N_FORMS = 8 };
+constexpr int LIN_N_EPIS = 5;       // LIN_F32 .. LIN_BF16
 
 // What is asked.  The plan reads the operands' alignment only; a query leaves the pointers it does not know null, which
 // reads as aligned.
@@ -1035,40 +1027,188 @@ struct LinPlan {
     bool two_pass = false;   // the kernel writes y into the workspace, then the elementwise pass applies the epilogue
     int epi = LIN_F32;       // the epilogue compiled into the kernel that runs
     int64_t blocks = 0; int threads = 256; size_t lds = 0;   // grid, block, dynamic LDS
-    size_t ws = 0;           // workspace bytes: y of a two-pass form (behind the widened rows of a bf16-input request)
     size_t widen = 0;        // bf16 activations that linear_bf16in_kernel does not take: bytes of their fp32 copy at the
-                             // front of the workspace; the rest of the plan is the float-input plan on that copy
+                             // front of the workspace, which the float-input kernel of the plan reads
+    size_t ws = 0;           // workspace bytes: the widened rows, then y of a two-pass form
 };
 
-static LinRequest lin_req(const qe_qparam *x, const qe_qparam *w, int64_t B, int K, int O, int epi = LIN_F32,
-                          const qe_requant *rq = nullptr, const uint8_t *codes = nullptr)
+// One template instance of the plan (launch_instance raises the dynamic-LDS attribute once per instance)
+using LinLaunch = void (*)(const LinPlan &, const LinArgs &, hipStream_t);
+template <auto KERNEL>
+static void launch_lin(const LinPlan &p, const LinArgs &a, hipStream_t s)
+{
+    launch_instance<KERNEL>((unsigned)p.blocks, p.threads, p.lds, p.lds, s, a);
+}
+template <int NJ, int EPI> constexpr LinLaunch lin64 = &launch_lin<&linear_mfma_kernel<NJ, EPI>>;
+template <int WMW, int EPI> constexpr LinLaunch lin128 = &launch_lin<&linear_mfma8_kernel<WMW, EPI>>;
+
+// linear_bf16in_kernel takes its own, smaller argument block: the bf16 rows travel in LinArgs::x
+template <bool RES>
+static void launch_bf16_rows(const LinPlan &p, const LinArgs &a, hipStream_t s)
+{
+    LinBf16Args b = {};
+    b.x = reinterpret_cast<const uint16_t *>(a.x); b.w = a.w; b.w_scale = a.w_scale; b.w_zero = a.w_zero; b.bias = a.bias;
+    b.res = a.res; b.out = a.out; b.w_sign = a.w_sign; b.w_per_tensor = a.w_per_tensor; b.B = a.B; b.K = a.K; b.O = a.O;
+    launch_linear_bf16in(b, RES, p.blocks, s);
+}
+
+// Every kernel, by form: rows x columns of a workgroup's tile, threads, dynamic LDS (the 128-deep kernels only run whole
+// column tiles) and, per epilogue, the launcher of that template instance -- null where there is none: the plan then runs
+// the epilogue as a second pass, and nothing else can select an instance.
+struct LinForm { int tm, tn, threads; size_t lds; LinLaunch launch[LIN_N_EPIS]; };   // launch[LIN_F32 .. LIN_BF16]
+static constexpr LinForm kLinForms[] = {
+    {32, 32, 256, 0, {&launch_lin<&linear_generic_kernel<false>>, nullptr, nullptr, nullptr, nullptr}},   // CHAIN
+    {LM, 128, 256, lin_lds_bytes<2>(),                                                                    // NJ2
+     {lin64<2, LIN_F32>, lin64<2, LIN_CODES>, lin64<2, LIN_CODES_GELU>, lin64<2, LIN_RES>, lin64<2, LIN_BF16>}},
+    {LM, 256, 256, lin_lds_bytes<4>(),                                                                    // NJ4
+     {lin64<4, LIN_F32>, lin64<4, LIN_CODES>, lin64<4, LIN_CODES_GELU>, lin64<4, LIN_RES>, lin64<4, LIN_BF16>}},
+    {320, L8_TN, 512, L8Geom<2>::LDS,                                                                     // W8
+     {lin128<2, LIN_F32>, lin128<2, LIN_CODES>, lin128<2, LIN_CODES_GELU>, lin128<2, LIN_RES>, lin128<2, LIN_BF16>}},
+    {160, L8_TN, 256, L8Geom<1>::LDS,                                                                     // W4
+     {lin128<1, LIN_F32>, lin128<1, LIN_CODES>, lin128<1, LIN_CODES_GELU>, lin128<1, LIN_RES>, lin128<1, LIN_BF16>}},
+    {32, 32, 256, 0, {&launch_lin<&linear_generic_kernel<true>>, nullptr, nullptr, nullptr, nullptr}},    // CHAIN_F32
+    {LF_T, LF_T, 256, linf_lds_bytes(),                                                                   // F32_SPLIT
+     {&launch_lin<&linear_f32_mfma_kernel<LIN_F32>>, nullptr, nullptr, &launch_lin<&linear_f32_mfma_kernel<LIN_RES>>, nullptr}},
+    {LB_T, LB_T, 256, linb_lds_bytes(), {&launch_bf16_rows<false>, nullptr, nullptr, &launch_bf16_rows<true>, nullptr}},   // BF16_ROWS
+};
+static_assert(sizeof(kLinForms) / sizeof(kLinForms[0]) == LIN_N_FORMS, "one row per form");
+static_assert(LB_K == LF_K, "the plan tests K once for both float-input MFMA kernels");
+
+static LinPlan plan_linear(const LinRequest &r)
+{
+    const auto ad = [](const void *p) { return reinterpret_cast<uintptr_t>(p); };
+    const auto al16 = [](uintptr_t a) { return (a & 15) == 0; };
+    const auto knob = [](const char *name, int unset) { const char *e = env_get(name); return e != nullptr ? atoi(e) : unset; };
+    const int64_t B = r.B;
+    const int K = r.K, O = r.O;
+    LinPlan p;
+    const bool w8 = r.w != nullptr && r.w->n_bits == 8 && B > 0 && O > 0 && al16(ad(r.w->data));
+    bool int8 = false;
+    if (r.f32_x || r.bf16_x) {
+        // bf16 MFMA on whole 32-deep stages; QE_LIN_F32_MFMA=0: the fp32 chain kernel only.  bf16 rows are the MFMA operand
+        // as stored where x is 16-byte aligned and `out` is written in 16-byte pieces; otherwise one pass widens them into the
+        // (aligned) front of the workspace and the float-input kernel runs on the copy.
+        const bool stages = w8 && (K % LF_K) == 0 && K >= LF_K && knob("QE_LIN_F32_MFMA", 1) != 0;
+        if (r.bf16_x && stages && al16(ad(r.x16)) && al16(ad(r.out))) p.form = LIN_FORM_BF16_ROWS;
+        else p.form = stages && (r.bf16_x || al16(ad(r.xf))) ? LIN_FORM_F32_SPLIT : LIN_FORM_CHAIN_F32;
+        if (r.bf16_x && p.form != LIN_FORM_BF16_ROWS && B > 0 && K > 0)
+            p.widen = ((size_t)B * (size_t)K * sizeof(float) + 15) & ~(size_t)15;
+    } else {
+        // K < 2^17: int32 accumulation of products up to 2^14 cannot overflow (deeper reductions take the fp32 kernel, as the
+        // reference's fp32 sum does).  Tile width: 256 columns unless that leaves the chip under-filled (the ViT head: 8
+        // workgroups): twice as many, half as wide (17.8 -> 11.5 us)
+        int8 = w8 && r.x != nullptr && r.x->n_bits == 8 && (K % LK) == 0 && K >= LK && K < (1 << 17) && al16(ad(r.x->data));
+        if (int8) p.form = ((B + LM - 1) / LM) * ((O + 255) / 256) < kNumCU ? LIN_FORM_NJ2 : LIN_FORM_NJ4;
+    }
+
+    // A fused epilogue is an instance of the chosen kernel: the residual add, 8-bit per-tensor codes at a 16-byte aligned
+    // address, or bf16 values at a 16-byte aligned address with O % 8 == 0 (a row piece of 8 values is then one aligned
+    // 16-byte store that lies wholly inside a row: every O % 64 == 0 fuses, and a narrower multiple of 8 as well).
+    // Anything else, and every call under QE_LIN_EPI=0, takes two passes: the linear into the workspace, then the
+    // elementwise pass whose arithmetic the epilogue shares.  (The knob is the A/B switch of the kernels that have a
+    // two-pass twin in the same plan; linear_bf16in_kernel's residual instance does not read it.)
+    const qe_requant *rq = r.rq;
+    const bool rq_ok = rq != nullptr && rq->n_bits == 8 && rq->n_param == 1 && rq->scale != nullptr && rq->zero != nullptr &&
+                       al16(ad(r.codes));
+    const bool bf16_ok = O % 8 == 0 && al16(ad(r.out16));
+    const bool epi_ok = r.epi == LIN_RES || (r.epi == LIN_BF16 ? bf16_ok : rq_ok);
+    p.two_pass = r.epi != LIN_F32 && !(kLinForms[p.form].launch[r.epi] != nullptr && epi_ok &&
+                                       (p.form == LIN_FORM_BF16_ROWS || knob("QE_LIN_EPI", 1) != 0));
+    p.epi = p.two_pass ? LIN_F32 : r.epi;
+    p.ws = p.widen + (p.two_pass && B > 0 && O > 0 ? (size_t)B * (size_t)O * sizeof(float) : 0);
+
+    if (int8) {
+        // The epilogue's destination: y in the 16-byte aligned workspace, out, or out and res.  The codes count as aligned,
+        // as qe_quantlinear_requant has always passed them (its fused form requires aligned codes in any case), and so do
+        // fused bf16 values (bf16_ok).
+        const bool dst_aligned = p.two_pass || r.epi == LIN_CODES || r.epi == LIN_CODES_GELU || r.epi == LIN_BF16 ||
+                                 al16(ad(r.out) | ad(r.res));
+        // 128-deep stages: 320 x 256 tiles (one 8-wave workgroup per CU) when the reduction is deep, 160 x 256 tiles (two 4-wave
+        // workgroups per CU) when the layer is bound by its stores (K <= 1024) -- either when the problem fills the chip with
+        // them (O % 256 == 0: whole column tiles).  QE_LIN8=0: never, 1: the 8-wave form, 2: the 4-wave form.  Every int8
+        // MFMA form has every epilogue, so the choice between them leaves two_pass as decided above.
+        if ((K % L8_K) == 0 && (O % L8_TN) == 0 && dst_aligned && B * (int64_t)K < (1ll << 32) &&
+            (int64_t)O * K < (1ll << 32) && O < (1 << 28)) {
+            // thresholds from tools/bench_linear.py at 256 / 64 / 16 images (profiles/r03zz_lin_small_batches.txt): the big
+            // tiles still win at 12,608 rows (120 / 237 tiles), the 64-deep kernel's smaller tiles at 3,152 rows unless O is wide
+            int big = 0;
+            if (K > 1024 && (B / 320) * (O / L8_TN) >= kNumCU / 3) big = 1;
+            else if (K <= 1024 && (B / 160) * (O / L8_TN) >= kNumCU / 2) big = 2;
+            big = knob("QE_LIN8", big);
+            if (big == 1) p.form = LIN_FORM_W8;
+            if (big == 2) p.form = LIN_FORM_W4;
+        }
+        // QE_LIN_NJ=2|4 overrides (tuning), big tiles included
+        if (const char *e = env_get("QE_LIN_NJ")) p.form = atoi(e) == 2 ? LIN_FORM_NJ2 : LIN_FORM_NJ4;
+    }
+
+    const LinForm &g = kLinForms[p.form];
+    p.blocks = ((B + g.tm - 1) / g.tm) * ((O + g.tn - 1) / g.tn);
+    p.threads = g.threads;
+    p.lds = g.lds;
+    return p;
+}
+
+// Request builders, one per entry family: its path query, its workspace query and its call all plan what this returns.  A
+// query passes what its signature has and leaves the rest at the defaults.
+static LinRequest lin_req(const qe_qparam *x, const qe_qparam *w, int64_t B, int K, int O, const float *bias = nullptr,
+                          float *out = nullptr)
 {
     LinRequest r;
-    r.x = x; r.w = w; r.B = B; r.K = K; r.O = O; r.epi = epi; r.rq = rq; r.codes = const_cast<uint8_t *>(codes);
+    r.x = x; r.w = w; r.B = B; r.K = K; r.O = O; r.bias = bias; r.out = out;
     return r;
 }
 
-static LinRequest linf_req(const float *x, const qe_qparam *w, int64_t B, int K, int O, int epi = LIN_F32)
+static LinRequest linf_req(const float *x, const qe_qparam *w, int64_t B, int K, int O, const float *bias = nullptr,
+                           float *out = nullptr)
 {
-    LinRequest r = lin_req(nullptr, w, B, K, O, epi);
+    LinRequest r = lin_req(nullptr, w, B, K, O, bias, out);
     r.f32_x = true; r.xf = x;
     return r;
 }
 
-static LinRequest linb_req(const uint16_t *x, const qe_qparam *w, int64_t B, int K, int O, int epi = LIN_F32)
+// (the queries have no `act`: plain and GELU codes are instances of the same kernels and plan alike)
+static LinRequest requant_req(const qe_qparam *x, const qe_qparam *w, int64_t B, int K, int O, const qe_requant *rq,
+                              const uint8_t *codes, int act = QE_ACT_NONE, const float *bias = nullptr, int32_t *status = nullptr)
 {
-    LinRequest r = lin_req(nullptr, w, B, K, O, epi);
-    r.bf16_x = true; r.x16 = x;
+    LinRequest r = lin_req(x, w, B, K, O, bias);
+    r.epi = act == QE_ACT_GELU ? LIN_CODES_GELU : LIN_CODES;
+    r.rq = rq; r.codes = const_cast<uint8_t *>(codes); r.status = status;
     return r;
 }
 
-// The float-input request a bf16-input request becomes once its rows are widened to fp32 at `xf` (a query: NULL, the
-// 16-byte aligned front of the workspace)
-static LinRequest linb_widened(const LinRequest &r, const float *xf)
+static LinRequest residual_req(const qe_qparam *x, const qe_qparam *w, int64_t B, int K, int O, const float *bias = nullptr,
+                               const float *res = nullptr, float *out = nullptr)
 {
-    LinRequest f = r;
-    f.bf16_x = false; f.x16 = nullptr; f.f32_x = true; f.xf = xf;
-    return f;
+    LinRequest r = lin_req(x, w, B, K, O, bias, out);
+    r.epi = LIN_RES; r.res = res;
+    return r;
+}
+
+static LinRequest bf16_req(const qe_qparam *x, const qe_qparam *w, int64_t B, int K, int O, const uint16_t *out,
+                           const float *bias = nullptr, float post_scale = 1.0f)
+{
+    LinRequest r = lin_req(x, w, B, K, O, bias);
+    r.epi = LIN_BF16; r.out16 = const_cast<uint16_t *>(out); r.post_scale = post_scale;
+    return r;
+}
+
+static LinRequest linf_residual_req(const float *x, const qe_qparam *w, int64_t B, int K, int O, const float *bias = nullptr,
+                                    const float *res = nullptr, float *out = nullptr)
+{
+    LinRequest r = linf_req(x, w, B, K, O, bias, out);
+    r.epi = LIN_RES; r.res = res;
+    return r;
+}
+
+// The queries of this family see neither the residual nor `out` (the C ABI): they describe the call with a residual, whose
+// workspace is the larger one, on an aligned `out`.
+static LinRequest bf16_input_req(const uint16_t *x, const qe_qparam *w, int64_t B, int K, int O, bool with_res = true,
+                                 const float *bias = nullptr, const float *res = nullptr, float *out = nullptr)
+{
+    LinRequest r = lin_req(nullptr, w, B, K, O, bias, out);
+    r.bf16_x = true; r.x16 = x; r.epi = with_res ? LIN_RES : LIN_F32; r.res = res;
+    return r;
 }
 
 // The checks every entry point starts with, in this order
@@ -1084,92 +1224,6 @@ static int check_lin(const LinRequest &r)
     return check_q(r.w, r.O);
 }
 
-static LinPlan plan_linear(const LinRequest &r)
-{
-    const auto ad = [](const void *p) { return reinterpret_cast<uintptr_t>(p); };
-    const auto al16 = [](uintptr_t a) { return (a & 15) == 0; };
-    const int64_t B = r.B;
-    const int K = r.K, O = r.O;
-    const char *e;
-    bool mfma = r.w != nullptr && r.w->n_bits == 8 && B > 0 && O > 0 && al16(ad(r.w->data));
-    if (r.bf16_x) {
-        // bf16 rows are the MFMA operand as stored: whole 32-deep stages, 16-byte loads of x, `out` written in 16-byte pieces.
-        // Under QE_LIN_F32_MFMA=0, and for everything else, one pass widens the rows and the float-input plan runs on them.
-        if (mfma && (K % LB_K) == 0 && K >= LB_K && al16(ad(r.x16)) && al16(ad(r.out)) &&
-            !((e = env_get("QE_LIN_F32_MFMA")) && atoi(e) == 0)) {
-            LinPlan p;
-            p.form = LIN_FORM_BF16IN;
-            p.epi = r.epi;                               // LIN_F32 | LIN_RES: both are instances of the kernel
-            p.blocks = ((B + LB_T - 1) / LB_T) * ((O + LB_T - 1) / LB_T);
-            p.lds = linb_lds_bytes();
-            return p;
-        }
-        LinPlan p = plan_linear(linb_widened(r, nullptr));
-        p.widen = B > 0 && K > 0 ? (((size_t)B * (size_t)K * sizeof(float) + 15) & ~(size_t)15) : 0;
-        p.ws += p.widen;
-        return p;
-    }
-    if (r.f32_x)   // bf16 MFMA on the split activations, whole 32-deep stages; QE_LIN_F32_MFMA=0: the fp32 chain kernel only
-        mfma = mfma && (K % LF_K) == 0 && K >= LF_K && al16(ad(r.xf)) && !((e = env_get("QE_LIN_F32_MFMA")) && atoi(e) == 0);
-    else           // K < 2^17: int32 accumulation of products up to 2^14 cannot overflow (deeper reductions take the fp32
-                   // kernel, as the reference's fp32 sum does)
-        mfma = mfma && r.x != nullptr && r.x->n_bits == 8 && (K % LK) == 0 && K >= LK && K < (1 << 17) && al16(ad(r.x->data));
-
-    // Fused epilogues run in the MFMA kernels: the residual add, 8-bit per-tensor codes at a 16-byte aligned address, or
-    // bf16 values at a 16-byte aligned address with O % 8 == 0 (a row piece of 8 values is then one aligned 16-byte store
-    // that lies wholly inside a row: every O % 64 == 0 fuses, and a narrower multiple of 8 as well).
-    // Anything else, and every call under QE_LIN_EPI=0, takes two passes: the linear into the workspace, then the
-    // elementwise pass whose arithmetic the epilogue shares.
-    LinPlan p;
-    const qe_requant *rq = r.rq;
-    const bool rq_ok = rq != nullptr && rq->n_bits == 8 && rq->n_param == 1 && rq->scale != nullptr && rq->zero != nullptr &&
-                       al16(ad(r.codes));
-    const bool bf16_ok = O % 8 == 0 && al16(ad(r.out16));
-    const bool epi_ok = r.epi == LIN_RES || (r.epi == LIN_BF16 ? bf16_ok : rq_ok);
-    p.two_pass = r.epi != LIN_F32 && !(mfma && !((e = env_get("QE_LIN_EPI")) && atoi(e) == 0) && epi_ok);
-    p.epi = p.two_pass ? LIN_F32 : r.epi;
-    p.ws = p.two_pass && B > 0 && O > 0 ? (size_t)B * (size_t)O * sizeof(float) : 0;
-
-    if (r.f32_x) {
-        p.form = mfma ? LIN_FORM_BF16 : LIN_FORM_CHAIN_F;
-    } else if (mfma) {
-        // The epilogue's destination: y in the 16-byte aligned workspace, out, or out and res.  The codes count as aligned,
-        // as qe_quantlinear_requant has always passed them (its fused form requires aligned codes in any case), and so do
-        // fused bf16 values (bf16_ok).
-        const bool dst_aligned = p.two_pass || r.epi == LIN_CODES || r.epi == LIN_CODES_GELU || r.epi == LIN_BF16 ||
-                                 al16(ad(r.out) | ad(r.res));
-        // tile width: 256 columns unless that leaves the chip under-filled (the ViT head: 8 workgroups): twice as many,
-        // half as wide (17.8 -> 11.5 us)
-        p.form = ((B + LM - 1) / LM) * ((O + 255) / 256) < kNumCU ? LIN_FORM_NJ2 : LIN_FORM_NJ4;
-        // 128-deep stages: 320 x 256 tiles (one 8-wave workgroup per CU) when the reduction is deep, 160 x 256 tiles (two 4-wave
-        // workgroups per CU) when the layer is bound by its stores (K <= 1024) -- either when the problem fills the chip with
-        // them (O % 256 == 0: whole column tiles).  QE_LIN8=0: never, 1: the 8-wave form, 2: the 4-wave form
-        int big = 0;
-        if ((K % L8_K) == 0 && (O % L8_TN) == 0 && dst_aligned && B * (int64_t)K < (1ll << 32) &&
-            (int64_t)O * K < (1ll << 32) && O < (1 << 28)) {
-            // thresholds from tools/bench_linear.py at 256 / 64 / 16 images (profiles/r03zz_lin_small_batches.txt): the big
-            // tiles still win at 12,608 rows (120 / 237 tiles), the 64-deep kernel's smaller tiles at 3,152 rows unless O is wide
-            if (K > 1024 && (B / 320) * (O / L8_TN) >= kNumCU / 3) big = 1;
-            else if (K <= 1024 && (B / 160) * (O / L8_TN) >= kNumCU / 2) big = 2;
-            if ((e = env_get("QE_LIN8"))) big = atoi(e);
-            if (big == 1) p.form = LIN_FORM_W8;
-            if (big == 2) p.form = LIN_FORM_W4;
-        }
-        // QE_LIN_NJ=2|4 overrides (tuning), big tiles included
-        if ((e = env_get("QE_LIN_NJ"))) p.form = atoi(e) == 2 ? LIN_FORM_NJ2 : LIN_FORM_NJ4;
-    }
-
-    // rows x columns of a workgroup's tile, threads and dynamic LDS of each kernel (the 128-deep ones only run whole column tiles)
-    static constexpr struct { int tm, tn, threads; size_t lds; } geom[] = {
-        {32, 32, 256, 0}, {LM, 128, 256, lin_lds_bytes<2>()}, {LM, 256, 256, lin_lds_bytes<4>()}, {320, L8_TN, 512, L8Geom<2>::LDS},
-        {160, L8_TN, 256, L8Geom<1>::LDS}, {32, 32, 256, 0}, {LF_T, LF_T, 256, linf_lds_bytes()}};
-    const auto &g = geom[p.form];
-    p.blocks = ((B + g.tm - 1) / g.tm) * ((O + g.tn - 1) / g.tn);
-    p.threads = g.threads;
-    p.lds = g.lds;
-    return p;
-}
-
 static QeRq make_rq(const qe_requant *rq)
 {
     QeRq q;
@@ -1181,12 +1235,13 @@ static QeRq make_rq(const qe_requant *rq)
     return q;
 }
 
-// The kernel arguments of a request whose linear writes `out` (r.out, or y in the workspace)
-static LinArgs lin_args(const LinRequest &r, float *out)
+// The kernel arguments of a request whose kernel reads fp32 activations at `xf` (r.xf, or the widened rows in the
+// workspace; unused for packed activations) and writes `out` (r.out, or y in the workspace).  bf16 rows travel in `x`.
+static LinArgs lin_args(const LinRequest &r, const float *xf, float *out)
 {
     LinArgs a = {};
-    if (r.f32_x) {
-        a.xf = r.xf; a.x_per_tensor = 1;
+    if (r.f32_x || r.bf16_x) {
+        a.x = reinterpret_cast<const uint8_t *>(r.x16); a.xf = xf; a.x_per_tensor = 1;
     } else {
         a.x = static_cast<const uint8_t *>(r.x->data); a.x_scale = r.x->scale; a.x_zero = r.x->zero;
         a.x_bits = r.x->n_bits; a.x_sign = r.x->sign; a.x_per_tensor = r.x->n_param == 1;
@@ -1197,31 +1252,6 @@ static LinArgs lin_args(const LinRequest &r, float *out)
     a.res = r.res; a.codes = r.codes; a.status = r.status; a.out16 = r.out16; a.post_scale = r.post_scale;
     if (r.rq != nullptr) a.rq = make_rq(r.rq);
     return a;
-}
-
-// One template instance of the plan (launch_instance raises the dynamic-LDS attribute once per instance)
-template <auto KERNEL>
-static void launch_lin(const LinPlan &p, const LinArgs &a, hipStream_t s)
-{
-    launch_instance<KERNEL>((unsigned)p.blocks, p.threads, p.lds, p.lds, s, a);
-}
-
-template <int EPI>
-static void launch_epi(const LinPlan &p, const LinArgs &a, hipStream_t s)
-{
-    switch (p.form) {
-    case LIN_FORM_NJ2: return launch_lin<&linear_mfma_kernel<2, EPI>>(p, a, s);
-    case LIN_FORM_NJ4: return launch_lin<&linear_mfma_kernel<4, EPI>>(p, a, s);
-    case LIN_FORM_W8: return launch_lin<&linear_mfma8_kernel<2, EPI>>(p, a, s);
-    case LIN_FORM_W4: return launch_lin<&linear_mfma8_kernel<1, EPI>>(p, a, s);
-    }
-    // the bf16 kernel has F32 and RES instances, the order-preserving kernels F32 only (the plan sends the rest to two passes)
-    if constexpr (EPI == LIN_F32 || EPI == LIN_RES)
-        if (p.form == LIN_FORM_BF16) return launch_lin<&linear_f32_mfma_kernel<EPI>>(p, a, s);
-    if constexpr (EPI == LIN_F32) {
-        if (p.form == LIN_FORM_CHAIN) return launch_lin<&linear_generic_kernel<false>>(p, a, s);
-        if (p.form == LIN_FORM_CHAIN_F) return launch_lin<&linear_generic_kernel<true>>(p, a, s);
-    }
 }
 
 // out = bf16(y * ps): lin_bf16x8, the LIN_BF16 epilogue's own arithmetic (path 0 of qe_quantlinear_bf16)
@@ -1239,10 +1269,8 @@ __global__ __launch_bounds__(256) void round_bf16_kernel(const float *y, uint16_
 static int launch_round_bf16(const float *y, uint16_t *out, int64_t n, float ps, hipStream_t s)
 {
     if (n <= 0) return QE_OK;
-    const int vec = ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-    const int64_t want = ((vec ? n / 8 : n) + 255) / 256;
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, kNumCU * 16));
-    hipLaunchKernelGGL(round_bf16_kernel, dim3(blocks), dim3(256), 0, s, y, out, n, ps, vec);
+    const ElementwiseGrid g = elementwise_grid(n, 8, reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(out));
+    hipLaunchKernelGGL(round_bf16_kernel, dim3(g.blocks), dim3(256), 0, s, y, out, n, ps, g.vec);
     QE_LAUNCH_CHECK();
     return QE_OK;
 }
@@ -1261,29 +1289,31 @@ __global__ __launch_bounds__(256) void add_residual_kernel(const float *y, const
 static int launch_add_residual(const float *y, const float *res, float *out, int64_t n, hipStream_t s)
 {
     if (n <= 0) return QE_OK;
-    const int vec = ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(res) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-    const int64_t want = ((vec ? n / 4 : n) + 255) / 256;
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, kNumCU * 16));
-    hipLaunchKernelGGL(add_residual_kernel, dim3(blocks), dim3(256), 0, s, y, res, out, n, vec);
+    const ElementwiseGrid g = elementwise_grid(n, 4, reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(res) |
+                                                         reinterpret_cast<uintptr_t>(out));
+    hipLaunchKernelGGL(add_residual_kernel, dim3(g.blocks), dim3(256), 0, s, y, res, out, n, g.vec);
     QE_LAUNCH_CHECK();
     return QE_OK;
 }
 
-// Plan a validated, non-empty request and run it: one launch, or the linear into the workspace and then the elementwise pass
+// Plan a validated, non-empty request and run it: the widening pass of bf16 rows the kernel does not take, the kernel (the
+// table's launcher of the plan's form and epilogue), and for a two-pass plan the elementwise pass over y in the workspace.
 static int run_linear(const LinRequest &r, void *workspace, size_t workspace_bytes, qe_stream_t stream)
 {
     const LinPlan p = plan_linear(r);
+    const LinLaunch launch = kLinForms[p.form].launch[p.epi];
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (p.two_pass && (workspace == nullptr || workspace_bytes < p.ws || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0))
+    if (p.ws > 0 && (workspace == nullptr || workspace_bytes < p.ws || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0))
         return QE_ERR_WORKSPACE;
-    if (p.blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
-    float *y = p.two_pass ? static_cast<float *>(workspace) : r.out;
-    const LinArgs a = lin_args(r, y);
-    if (p.epi == LIN_CODES) launch_epi<LIN_CODES>(p, a, s);
-    else if (p.epi == LIN_CODES_GELU) launch_epi<LIN_CODES_GELU>(p, a, s);
-    else if (p.epi == LIN_RES) launch_epi<LIN_RES>(p, a, s);
-    else if (p.epi == LIN_BF16) launch_epi<LIN_BF16>(p, a, s);
-    else launch_epi<LIN_F32>(p, a, s);
+    if (p.blocks > 0x7fffffffLL || launch == nullptr) return QE_ERR_UNSUPPORTED;   // (null: the plan named no instance)
+    // the workspace: the widened rows (p.widen bytes, a multiple of 16), then y of a two-pass plan
+    float *xw = static_cast<float *>(workspace);
+    float *y = p.two_pass ? reinterpret_cast<float *>(static_cast<uint8_t *>(workspace) + p.widen) : r.out;
+    if (p.widen > 0) {
+        launch_widen_bf16(r.x16, xw, r.B * (int64_t)r.K, s);
+        QE_LAUNCH_CHECK();
+    }
+    launch(p, lin_args(r, r.bf16_x ? xw : r.xf, y), s);
     QE_LAUNCH_CHECK();
     if (!p.two_pass) return QE_OK;
     const int64_t n = r.B * (int64_t)r.O;
@@ -1293,28 +1323,6 @@ static int run_linear(const LinRequest &r, void *workspace, size_t workspace_byt
     const qe_requant *rq = r.rq;
     return qe_quantize_pack_act(y, n, r.epi == LIN_CODES_GELU ? QE_ACT_GELU : QE_ACT_NONE, rq->scale, rq->zero, rq->n_param, 1,
                                 rq->qmin, rq->qmax, rq->n_bits, rq->sign, r.codes, nullptr, r.status, stream);
-}
-
-// A validated, non-empty bf16-input request: linear_bf16in_kernel, or the widening pass and the float-input plan behind it
-static int run_linear_bf16in(const LinRequest &r, void *workspace, size_t workspace_bytes, qe_stream_t stream)
-{
-    const LinPlan p = plan_linear(r);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (p.form == LIN_FORM_BF16IN) {
-        if (p.blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
-        LinBf16Args a = {};
-        a.x = r.x16; a.w = static_cast<const uint8_t *>(r.w->data); a.w_scale = r.w->scale; a.w_zero = r.w->zero; a.bias = r.bias;
-        a.res = r.res; a.out = r.out; a.w_sign = r.w->sign; a.w_per_tensor = r.w->n_param == 1; a.B = r.B; a.K = r.K; a.O = r.O;
-        launch_linear_bf16in(a, p.epi == LIN_RES, p.blocks, s);
-        QE_LAUNCH_CHECK();
-        return QE_OK;
-    }
-    if (p.ws > 0 && (workspace == nullptr || workspace_bytes < p.ws || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0))
-        return QE_ERR_WORKSPACE;
-    float *xf = static_cast<float *>(workspace);
-    launch_widen_bf16(r.x16, xf, r.B * (int64_t)r.K, s);
-    QE_LAUNCH_CHECK();
-    return run_linear(linb_widened(r, xf), static_cast<uint8_t *>(workspace) + p.widen, workspace_bytes - p.widen, stream);
 }
 
 // residual and out: the same buffer or disjoint
@@ -1331,17 +1339,15 @@ extern "C" int qe_quantlinear_path(const qe_qparam *x, const qe_qparam *w, int64
 
 extern "C" int qe_quantlinear_form(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O, int32_t dst_aligned)
 {
-    qe::LinRequest r = qe::lin_req(x, w, B, K, O);
-    r.out = reinterpret_cast<float *>(dst_aligned != 0 ? 0 : 4);   // a stand-in address of that alignment
-    return qe::plan_linear(r).form;
+    // a stand-in `out` of that alignment
+    return qe::plan_linear(qe::lin_req(x, w, B, K, O, nullptr, reinterpret_cast<float *>(dst_aligned != 0 ? 0 : 4))).form;
 }
 
 extern "C" int qe_quantlinear(const qe_qparam *x, const qe_qparam *w, const float *bias,
                               int64_t B, int32_t K, int32_t O, float *out, qe_stream_t stream)
 {
     using namespace qe;
-    LinRequest r = lin_req(x, w, B, K, O);
-    r.bias = bias; r.out = out;
+    const LinRequest r = lin_req(x, w, B, K, O, bias, out);
     if (int rc = check_lin(r)) return rc;
     if (out == nullptr && B * O > 0) return QE_ERR_ARG;
     if (B == 0 || O == 0) return QE_OK;
@@ -1352,8 +1358,7 @@ extern "C" int qe_quantlinear_float_input(const float *x, const qe_qparam *w, co
                                           int64_t B, int32_t K, int32_t O, float *out, qe_stream_t stream)
 {
     using namespace qe;
-    LinRequest r = linf_req(x, w, B, K, O);
-    r.bias = bias; r.out = out;
+    const LinRequest r = linf_req(x, w, B, K, O, bias, out);
     if (int rc = check_lin(r)) return rc;
     if ((x == nullptr && B * K > 0) || (out == nullptr && B * O > 0)) return QE_ERR_ARG;
     if (B == 0 || O == 0) return QE_OK;
@@ -1362,7 +1367,7 @@ extern "C" int qe_quantlinear_float_input(const float *x, const qe_qparam *w, co
 
 extern "C" int qe_quantlinear_float_input_path(const float *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O)
 {
-    return qe::plan_linear(qe::linf_req(x, w, B, K, O)).form == qe::LIN_FORM_BF16;
+    return qe::plan_linear(qe::linf_req(x, w, B, K, O)).form == qe::LIN_FORM_F32_SPLIT;
 }
 
 // Fused ViT forms (include/quant_engine.h): the consumer's codes of y / gelu(y), and y + residual.  Path 1 is an MFMA kernel
@@ -1370,13 +1375,13 @@ extern "C" int qe_quantlinear_float_input_path(const float *x, const qe_qparam *
 extern "C" int qe_quantlinear_requant_path(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O,
                                            const qe_requant *rq, const uint8_t *codes)
 {
-    return !qe::plan_linear(qe::lin_req(x, w, B, K, O, qe::LIN_CODES, rq, codes)).two_pass;
+    return !qe::plan_linear(qe::requant_req(x, w, B, K, O, rq, codes)).two_pass;
 }
 
 extern "C" size_t qe_quantlinear_requant_workspace_bytes(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O,
                                                          const qe_requant *rq, const uint8_t *codes)
 {
-    return qe::plan_linear(qe::lin_req(x, w, B, K, O, qe::LIN_CODES, rq, codes)).ws;
+    return qe::plan_linear(qe::requant_req(x, w, B, K, O, rq, codes)).ws;
 }
 
 extern "C" int qe_quantlinear_requant(const qe_qparam *x, const qe_qparam *w, const float *bias, int64_t B, int32_t K, int32_t O,
@@ -1387,8 +1392,7 @@ extern "C" int qe_quantlinear_requant(const qe_qparam *x, const qe_qparam *w, co
     if (B < 0 || K < 0 || O < 0 || rq == nullptr || (act != QE_ACT_NONE && act != QE_ACT_GELU)) return QE_ERR_ARG;
     if (!(rq->n_bits > 0 && rq->n_bits <= 8)) return QE_ERR_NBITS;
     if (rq->n_param != 1 && rq->n_param != O) return QE_ERR_ARG;
-    LinRequest r = lin_req(x, w, B, K, O, act == QE_ACT_GELU ? LIN_CODES_GELU : LIN_CODES, rq, codes);
-    r.bias = bias; r.status = status;
+    const LinRequest r = requant_req(x, w, B, K, O, rq, codes, act, bias, status);
     if (int rc = check_lin(r)) return rc;
     if (B == 0 || O == 0) return QE_OK;
     if (codes == nullptr) return QE_ERR_ARG;
@@ -1397,20 +1401,19 @@ extern "C" int qe_quantlinear_requant(const qe_qparam *x, const qe_qparam *w, co
 
 extern "C" int qe_quantlinear_residual_path(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O)
 {
-    return !qe::plan_linear(qe::lin_req(x, w, B, K, O, qe::LIN_RES)).two_pass;
+    return !qe::plan_linear(qe::residual_req(x, w, B, K, O)).two_pass;
 }
 
 extern "C" size_t qe_quantlinear_residual_workspace_bytes(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O)
 {
-    return qe::plan_linear(qe::lin_req(x, w, B, K, O, qe::LIN_RES)).ws;
+    return qe::plan_linear(qe::residual_req(x, w, B, K, O)).ws;
 }
 
 extern "C" int qe_quantlinear_residual(const qe_qparam *x, const qe_qparam *w, const float *bias, int64_t B, int32_t K, int32_t O,
                                        const float *residual, float *out, void *workspace, size_t workspace_bytes, qe_stream_t stream)
 {
     using namespace qe;
-    LinRequest r = lin_req(x, w, B, K, O, LIN_RES);
-    r.bias = bias; r.res = residual; r.out = out;
+    const LinRequest r = residual_req(x, w, B, K, O, bias, residual, out);
     if (int rc = check_lin(r)) return rc;
     if (B == 0 || O == 0) return QE_OK;
     if (residual == nullptr || out == nullptr || !res_overlap_ok(residual, out, B * (int64_t)O)) return QE_ERR_ARG;
@@ -1422,25 +1425,20 @@ extern "C" int qe_quantlinear_residual(const qe_qparam *x, const qe_qparam *w, c
 // reads as aligned).
 extern "C" int qe_quantlinear_bf16_path(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O, const uint16_t *out)
 {
-    qe::LinRequest r = qe::lin_req(x, w, B, K, O, qe::LIN_BF16);
-    r.out16 = const_cast<uint16_t *>(out);
-    return !qe::plan_linear(r).two_pass;
+    return !qe::plan_linear(qe::bf16_req(x, w, B, K, O, out)).two_pass;
 }
 
 extern "C" size_t qe_quantlinear_bf16_workspace_bytes(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O,
                                                       const uint16_t *out)
 {
-    qe::LinRequest r = qe::lin_req(x, w, B, K, O, qe::LIN_BF16);
-    r.out16 = const_cast<uint16_t *>(out);
-    return qe::plan_linear(r).ws;
+    return qe::plan_linear(qe::bf16_req(x, w, B, K, O, out)).ws;
 }
 
 extern "C" int qe_quantlinear_bf16(const qe_qparam *x, const qe_qparam *w, const float *bias, int64_t B, int32_t K, int32_t O,
                                    float post_scale, uint16_t *out, void *workspace, size_t workspace_bytes, qe_stream_t stream)
 {
     using namespace qe;
-    LinRequest r = lin_req(x, w, B, K, O, LIN_BF16);
-    r.bias = bias; r.out16 = out; r.post_scale = post_scale;
+    const LinRequest r = bf16_req(x, w, B, K, O, out, bias, post_scale);
     if (int rc = check_lin(r)) return rc;
     if (B == 0 || O == 0) return QE_OK;
     if (out == nullptr || (reinterpret_cast<uintptr_t>(out) & 1) != 0) return QE_ERR_ARG;
@@ -1449,13 +1447,13 @@ extern "C" int qe_quantlinear_bf16(const qe_qparam *x, const qe_qparam *w, const
 
 extern "C" int qe_quantlinear_float_input_residual_path(const float *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O)
 {
-    return !qe::plan_linear(qe::linf_req(x, w, B, K, O, qe::LIN_RES)).two_pass;
+    return !qe::plan_linear(qe::linf_residual_req(x, w, B, K, O)).two_pass;
 }
 
 extern "C" size_t qe_quantlinear_float_input_residual_workspace_bytes(const float *x, const qe_qparam *w, int64_t B, int32_t K,
                                                                      int32_t O)
 {
-    return qe::plan_linear(qe::linf_req(x, w, B, K, O, qe::LIN_RES)).ws;
+    return qe::plan_linear(qe::linf_residual_req(x, w, B, K, O)).ws;
 }
 
 extern "C" int qe_quantlinear_float_input_residual(const float *x, const qe_qparam *w, const float *bias, int64_t B, int32_t K,
@@ -1463,8 +1461,7 @@ extern "C" int qe_quantlinear_float_input_residual(const float *x, const qe_qpar
                                                    size_t workspace_bytes, qe_stream_t stream)
 {
     using namespace qe;
-    LinRequest r = linf_req(x, w, B, K, O, LIN_RES);
-    r.bias = bias; r.res = residual; r.out = out;
+    const LinRequest r = linf_residual_req(x, w, B, K, O, bias, residual, out);
     if (int rc = check_lin(r)) return rc;
     if (B == 0 || O == 0) return QE_OK;
     if (x == nullptr || residual == nullptr || out == nullptr || !res_overlap_ok(residual, out, B * (int64_t)O)) return QE_ERR_ARG;
@@ -1472,15 +1469,15 @@ extern "C" int qe_quantlinear_float_input_residual(const float *x, const qe_qpar
 }
 
 // bf16 activations (include/quant_engine.h): path 1 is linear_bf16in_kernel, which reads the rows as its MFMA operand; path 0
-// widens them into the workspace and runs the float-input plan on the copy.
+// widens them into the workspace and runs the float-input kernel on the copy.
 extern "C" int qe_quantlinear_bf16_input_path(const uint16_t *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O)
 {
-    return qe::plan_linear(qe::linb_req(x, w, B, K, O, qe::LIN_RES)).form == qe::LIN_FORM_BF16IN;
+    return qe::plan_linear(qe::bf16_input_req(x, w, B, K, O)).form == qe::LIN_FORM_BF16_ROWS;
 }
 
 extern "C" size_t qe_quantlinear_bf16_input_workspace_bytes(const uint16_t *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O)
 {
-    return qe::plan_linear(qe::linb_req(x, w, B, K, O, qe::LIN_RES)).ws;
+    return qe::plan_linear(qe::bf16_input_req(x, w, B, K, O)).ws;
 }
 
 extern "C" int qe_quantlinear_bf16_input(const uint16_t *x, const qe_qparam *w, const float *bias, int64_t B, int32_t K, int32_t O,
@@ -1488,8 +1485,7 @@ extern "C" int qe_quantlinear_bf16_input(const uint16_t *x, const qe_qparam *w, 
                                          qe_stream_t stream)
 {
     using namespace qe;
-    LinRequest r = linb_req(x, w, B, K, O, residual != nullptr ? LIN_RES : LIN_F32);
-    r.bias = bias; r.res = residual; r.out = out;
+    const LinRequest r = bf16_input_req(x, w, B, K, O, residual != nullptr, bias, residual, out);
     if (int rc = check_lin(r)) return rc;
     if (B == 0 || O == 0) return QE_OK;
     if ((x == nullptr && K > 0) || out == nullptr) return QE_ERR_ARG;
@@ -1500,5 +1496,6 @@ extern "C" int qe_quantlinear_bf16_input(const uint16_t *x, const qe_qparam *w, 
     const uintptr_t olo = reinterpret_cast<uintptr_t>(out), ohi = olo + (uintptr_t)B * (uintptr_t)O * sizeof(float);
     if (xlo < ohi && olo < xhi) return QE_ERR_ARG;
     if (residual != nullptr && !res_overlap_ok(residual, out, B * (int64_t)O)) return QE_ERR_ARG;
-    return run_linear_bf16in(r, workspace, workspace_bytes, stream);
+    return run_linear(r, workspace, workspace_bytes, stream);
 }
+

@@ -221,10 +221,8 @@ __global__ __launch_bounds__(256) void widen_bf16_kernel(const uint16_t *x, floa
 void launch_widen_bf16(const uint16_t *x, float *out, int64_t n, hipStream_t s)
 {
     if (n <= 0) return;
-    const int vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-    const int64_t want = ((vec ? n / 8 : n) + 255) / 256;
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(want, kNumCU * 16));
-    hipLaunchKernelGGL(widen_bf16_kernel, dim3(blocks), dim3(256), 0, s, x, out, n, vec);
+    const ElementwiseGrid g = elementwise_grid(n, 8, reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out));
+    hipLaunchKernelGGL(widen_bf16_kernel, dim3(g.blocks), dim3(256), 0, s, x, out, n, g.vec);
 }
 
 }  // namespace qe

@@ -33,6 +33,17 @@ struct LinBf16Args {
     int K, O;
 };
 
+// Grid of a linear's elementwise pass (widen_bf16_kernel, round_bf16_kernel, add_residual_kernel: 256-thread blocks, grid
+// stride) over n > 0 elements: `width` elements per thread and trip where every address is 16-byte aligned (`addrs`: their
+// bitwise OR), one otherwise; at most 16 blocks per CU.
+struct ElementwiseGrid { int vec, blocks; };
+inline ElementwiseGrid elementwise_grid(int64_t n, int width, uintptr_t addrs)
+{
+    const int vec = (addrs & 15) == 0;
+    const int64_t want = ((vec ? n / width : n) + 255) / 256;
+    return {vec, (int)(want < 1 ? 1 : want > kNumCU * 16 ? kNumCU * 16 : want)};
+}
+
 // blocks = ceil(B / 128) ceil(O / 128); residual chooses the template instance
 void launch_linear_bf16in(const LinBf16Args &a, bool residual, int64_t blocks, hipStream_t s);
 // out[i] = fp32 of the bf16 bit pattern x[i] (exact): path 0 of qe_quantlinear_bf16_input

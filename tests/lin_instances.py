@@ -1,25 +1,35 @@
-"""One problem per instance of the linear kernels (qe_linear.hip), shared by the CPU coverage test and the GPU tests of every
-epilogue.
+"""One problem per instance of the linear kernels (qe_linear.hip, qe_linear_bf16in.hip), shared by the CPU coverage test and
+the GPU tests of every epilogue.
 
 ROWS: int8 x int8 problems, (B, K, O, env, form, note).  `form` is what qe_quantlinear_form must name with `env` applied:
-0 = linear_generic_kernel<false> (the order-preserving fp32 kernel), 1 = linear_mfma_kernel<2> (64-deep, 128 x 128 tiles),
-2 = linear_mfma_kernel<4> (64-deep, 128 x 256), 3 = linear_mfma8_kernel<2> (8 waves, 320 x 256), 4 = linear_mfma8_kernel<1>
-(4 waves, 160 x 256).  The MFMA forms run every epilogue on the same kernel -- F32 (qe_quantlinear), CODES / CODES_GELU
-(qe_quantlinear_requant) and RES (qe_quantlinear_residual) -- so a row reaches four template instances; form 0 has only
-the F32 one (the fused entries run it in two passes).
+0 = linear_generic_kernel<false> (the order-preserving fp32 kernel, LIN_FORM_CHAIN), 1 = linear_mfma_kernel<2> (64-deep,
+128 x 128 tiles, LIN_FORM_NJ2), 2 = linear_mfma_kernel<4> (64-deep, 128 x 256, LIN_FORM_NJ4), 3 = linear_mfma8_kernel<2>
+(8 waves, 320 x 256, LIN_FORM_W8), 4 = linear_mfma8_kernel<1> (4 waves, 160 x 256, LIN_FORM_W4).  The MFMA forms run every
+epilogue on the same kernel -- F32 (qe_quantlinear), CODES / CODES_GELU (qe_quantlinear_requant), RES
+(qe_quantlinear_residual) and BF16 (qe_quantlinear_bf16) -- so a row reaches five template instances; tests/
+test_linear_bf16_gpu.py runs the BF16 one on the rows with B <= 3152 (BF16_MAX_B).  Form 0 has only the F32 instance (the
+fused entries run it in two passes).
 
-F_ROWS: fp32-activation problems (qe_quantlinear_float_input), same layout; form 1 = linear_f32_mfma_kernel (F32 and, through
-qe_quantlinear_float_input_residual, RES), 0 = linear_generic_kernel<true>.
+F_ROWS: fp32-activation problems (qe_quantlinear_float_input), same layout; form 1 = linear_f32_mfma_kernel (the fp32 rows
+split into three bf16 parts, LIN_FORM_F32_SPLIT: F32 and, through qe_quantlinear_float_input_residual, RES),
+0 = linear_generic_kernel<true> (LIN_FORM_CHAIN_F32).
+
+bf16-activation problems (qe_quantlinear_bf16_input) are the rows of tests/lin_bf16in_instances.py: path 1 =
+linear_bf16in_kernel (bf16 rows as stored, LIN_FORM_BF16_ROWS: F32 and, with a residual, RES -- tests/
+test_linear_bf16_input_gpu.py runs both on every row), path 0 = the widening pass and a float-input kernel.
 
 The first rows are real ViT layer shapes (S/16, B/16, L/16, H/14 at 1, 16, 64 and 256 images: 197 or 257 tokens per image,
 196 or 256 patches) that the planner places without knobs; the forced rows after them take each kernel to its edges.
 XQ[i % 3] is the activation quantiser of row i (the GPU tests draw the operands with it)."""
+import lin_bf16in_instances as bi
 
-F32, CODES, CODES_GELU, RES = "F32", "CODES", "CODES_GELU", "RES"
-EPIS = (F32, CODES, CODES_GELU, RES)
+F32, CODES, CODES_GELU, RES, BF16 = "F32", "CODES", "CODES_GELU", "RES", "BF16"
+EPIS = (F32, CODES, CODES_GELU, RES, BF16)
 KERNEL = {0: "linear_generic_kernel<false>", 1: "linear_mfma_kernel<2>", 2: "linear_mfma_kernel<4>",
           3: "linear_mfma8_kernel<2>", 4: "linear_mfma8_kernel<1>"}
 F_KERNEL = {0: "linear_generic_kernel<true>", 1: "linear_f32_mfma_kernel"}
+B_KERNEL = "linear_bf16in_kernel"
+BF16_MAX_B = 3152        # tests/test_linear_bf16_gpu.py runs the rows up to this many batch rows
 
 N4 = {"QE_LIN_NJ": "4"}
 W8, W4 = {"QE_LIN8": "1"}, {"QE_LIN8": "2"}
@@ -83,9 +93,11 @@ F_ROWS = [
 XQ = [(True, False, False), (True, True, True), (False, True, True)]
 
 
-def epilogues(form):
-    """The epilogues whose template instance a row of this form runs."""
-    return EPIS if form != 0 else (F32,)
+def epilogues(row):
+    """The epilogues whose template instance a row runs: all of an MFMA form (BF16 on the rows test_linear_bf16_gpu.py runs)."""
+    if row[4] == 0:
+        return (F32,)
+    return tuple(e for e in EPIS if e != BF16 or row[0] <= BF16_MAX_B)
 
 
 def f_epilogues(form):
@@ -93,11 +105,17 @@ def f_epilogues(form):
 
 
 def instances(row):
-    return {(KERNEL[row[4]], e) for e in epilogues(row[4])}
+    return {(KERNEL[row[4]], e) for e in epilogues(row)}
 
 
 def f_instances(row):
     return {(F_KERNEL[row[4]], e) for e in f_epilogues(row[4])}
+
+
+def b_instances(row):
+    """A bf16-input row: both instances of linear_bf16in_kernel on path 1; on path 0 the float-input kernels, which F_ROWS
+    count."""
+    return {(B_KERNEL, F32), (B_KERNEL, RES)} if row[5] == 1 else set()
 
 
 def covered():
@@ -106,11 +124,13 @@ def covered():
         out |= instances(r)
     for r in F_ROWS:
         out |= f_instances(r)
+    for r in bi.ROWS:
+        out |= b_instances(r)
     return out
 
 
 def every_instance():
-    """The 20 instances the linear launchers can select."""
+    """The 26 instances the linear launchers can select (the non-null launchers of kLinForms in qe_linear.hip)."""
     out = {(KERNEL[f], e) for f in (1, 2, 3, 4) for e in EPIS}
-    out |= {(KERNEL[0], F32), (F_KERNEL[0], F32), (F_KERNEL[1], F32), (F_KERNEL[1], RES)}
+    out |= {(KERNEL[0], F32), (F_KERNEL[0], F32), (F_KERNEL[1], F32), (F_KERNEL[1], RES), (B_KERNEL, F32), (B_KERNEL, RES)}
     return out

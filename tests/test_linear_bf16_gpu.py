@@ -15,7 +15,7 @@ from quantize_amd import capi
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
-ROWS = [(i, r) for i, r in enumerate(li.ROWS) if r[0] <= 3152]
+ROWS = [(i, r) for i, r in enumerate(li.ROWS) if r[0] <= li.BF16_MAX_B]
 SCALES = (1.0, 0.125, float(np.float32(48 ** -0.5)))
 
 
