@@ -183,6 +183,11 @@ def _ws(need, dev):
     return torch.empty(need, dtype=torch.uint8, device=dev) if need else None
 
 
+def _given_ws(workspace, need, dev):
+    """The caller's workspace as it is (the library refuses one that is too small), or a new one of `need` bytes."""
+    return _ws(need, dev) if workspace is None else workspace
+
+
 def _status(status, dev):
     import torch
     return torch.zeros(1, dtype=torch.int32, device=dev) if status is None else status
@@ -551,7 +556,7 @@ def linear_requant_path(xq, wq, B, K, O, rq, codes=None):
                                                  codes.data_ptr() if codes is not None else 256))
 
 
-def quantlinear_requant(xq, wq, bias, B, K, O, rq, act=None, codes=None, status=None, stream=None):
+def quantlinear_requant(xq, wq, bias, B, K, O, rq, act=None, codes=None, status=None, workspace=None, stream=None):
     """qe_quantlinear_requant: the consumer's codes of act(quantlinear(...)) (B x O elements).  Returns (codes, status)."""
     import torch
     dev = wq._keep[0].device
@@ -560,9 +565,9 @@ def quantlinear_requant(xq, wq, bias, B, K, O, rq, act=None, codes=None, status=
     status = _status(status, dev)
     need = int(lib().qe_quantlinear_requant_workspace_bytes(ctypes.byref(xq), ctypes.byref(wq), int(B), int(K), int(O),
                                                             ctypes.byref(rq), codes.data_ptr()))
-    ws = _ws(need, dev)
+    ws = _given_ws(workspace, need, dev)
     check(lib().qe_quantlinear_requant(ctypes.byref(xq), ctypes.byref(wq), _ptr(bias), int(B), int(K), int(O), ACTS[act],
-                                       ctypes.byref(rq), codes.data_ptr(), status.data_ptr(), _ptr(ws), need, _stream(stream)))
+                                       ctypes.byref(rq), codes.data_ptr(), status.data_ptr(), *_prep(ws), _stream(stream)))
     return codes, status
 
 
@@ -570,7 +575,7 @@ def linear_residual_path(xq, wq, B, K, O):
     return int(lib().qe_quantlinear_residual_path(ctypes.byref(xq), ctypes.byref(wq), int(B), int(K), int(O)))
 
 
-def quantlinear_residual(xq, wq, bias, B, K, O, residual, out=None, stream=None):
+def quantlinear_residual(xq, wq, bias, B, K, O, residual, out=None, workspace=None, stream=None):
     """qe_quantlinear_residual: out = quantlinear(...) + residual (out=None: a new tensor; out=residual: in place)."""
     import torch
     assert residual.is_contiguous() and residual.dtype == torch.float32 and residual.numel() == B * O
@@ -578,9 +583,9 @@ def quantlinear_residual(xq, wq, bias, B, K, O, residual, out=None, stream=None)
     if out is None:
         out = torch.empty((B, O), dtype=torch.float32, device=dev)
     need = int(lib().qe_quantlinear_residual_workspace_bytes(ctypes.byref(xq), ctypes.byref(wq), int(B), int(K), int(O)))
-    ws = _ws(need, dev)
+    ws = _given_ws(workspace, need, dev)
     check(lib().qe_quantlinear_residual(ctypes.byref(xq), ctypes.byref(wq), _ptr(bias), int(B), int(K), int(O), residual.data_ptr(),
-                                        out.data_ptr(), _ptr(ws), need, _stream(stream)))
+                                        out.data_ptr(), *_prep(ws), _stream(stream)))
     return out
 
 
@@ -590,7 +595,7 @@ def quantlinear_bf16_path(xq, wq, B, K, O, out=None):
     return int(lib().qe_quantlinear_bf16_path(ctypes.byref(xq), ctypes.byref(wq), int(B), int(K), int(O), _ptr(out)))
 
 
-def quantlinear_bf16(xq, wq, bias, B, K, O, post_scale=1.0, out=None, stream=None):
+def quantlinear_bf16(xq, wq, bias, B, K, O, post_scale=1.0, out=None, workspace=None, stream=None):
     """qe_quantlinear_bf16: bf16(quantlinear(...) * post_scale) as a torch.bfloat16 tensor (B, O) -- one fp32 multiply, round
     to nearest even: equal to (quantlinear(...) * post_scale).to(torch.bfloat16) element for element."""
     import torch
@@ -599,9 +604,9 @@ def quantlinear_bf16(xq, wq, bias, B, K, O, post_scale=1.0, out=None, stream=Non
         out = torch.empty((B, O), dtype=torch.bfloat16, device=dev)
     assert out.is_contiguous() and out.dtype == torch.bfloat16 and out.numel() == B * O
     need = int(lib().qe_quantlinear_bf16_workspace_bytes(ctypes.byref(xq), ctypes.byref(wq), int(B), int(K), int(O), out.data_ptr()))
-    ws = _ws(need, dev)
+    ws = _given_ws(workspace, need, dev)
     check(lib().qe_quantlinear_bf16(ctypes.byref(xq), ctypes.byref(wq), _ptr(bias), int(B), int(K), int(O), float(post_scale),
-                                    out.data_ptr(), _ptr(ws), need, _stream(stream)))
+                                    out.data_ptr(), *_prep(ws), _stream(stream)))
     return out
 
 
@@ -609,7 +614,7 @@ def linear_float_input_residual_path(x, wq, B, K, O):
     return int(lib().qe_quantlinear_float_input_residual_path(x.data_ptr(), ctypes.byref(wq), int(B), int(K), int(O)))
 
 
-def quantlinear_float_input_residual(x, wq, bias, O, residual, out=None, stream=None):
+def quantlinear_float_input_residual(x, wq, bias, O, residual, out=None, workspace=None, stream=None):
     """qe_quantlinear_float_input_residual: out = quantlinear_float_input(x, ...) + residual."""
     import torch
     assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and x.dim() == 2
@@ -618,9 +623,9 @@ def quantlinear_float_input_residual(x, wq, bias, O, residual, out=None, stream=
     if out is None:
         out = torch.empty((B, O), dtype=torch.float32, device=x.device)
     need = int(lib().qe_quantlinear_float_input_residual_workspace_bytes(x.data_ptr(), ctypes.byref(wq), int(B), int(K), int(O)))
-    ws = _ws(need, x.device)
+    ws = _given_ws(workspace, need, x.device)
     check(lib().qe_quantlinear_float_input_residual(x.data_ptr(), ctypes.byref(wq), _ptr(bias), int(B), int(K), int(O),
-                                                    residual.data_ptr(), out.data_ptr(), _ptr(ws), need, _stream(stream)))
+                                                    residual.data_ptr(), out.data_ptr(), *_prep(ws), _stream(stream)))
     return out
 
 
@@ -636,7 +641,7 @@ def quantlinear_bf16_input_path(x, wq, B, K, O):
     return int(lib().qe_quantlinear_bf16_input_path(_ptr(x), ctypes.byref(wq), int(B), int(K), int(O)))
 
 
-def quantlinear_bf16_input(x, wq, bias, O, residual=None, out=None, stream=None):
+def quantlinear_bf16_input(x, wq, bias, O, residual=None, out=None, workspace=None, stream=None):
     """qe_quantlinear_bf16_input: quantlinear_float_input on a contiguous torch.bfloat16 (B, K) tensor, read in place
     (+ residual when given: one fp32 add; out=residual: in place).  Anything else as x raises ValueError."""
     import torch
@@ -650,9 +655,9 @@ def quantlinear_bf16_input(x, wq, bias, O, residual=None, out=None, stream=None)
     # the query cannot see `out`: an `out` that is not 16-byte aligned takes path 0 whatever it answers
     need = int(lib().qe_quantlinear_bf16_input_workspace_bytes(x.data_ptr() if out.data_ptr() % 16 == 0 else 2, ctypes.byref(wq),
                                                                int(B), int(K), int(O)))
-    ws = _ws(need, x.device)
+    ws = _given_ws(workspace, need, x.device)
     check(lib().qe_quantlinear_bf16_input(x.data_ptr(), ctypes.byref(wq), _ptr(bias), int(B), int(K), int(O), _ptr(residual),
-                                          out.data_ptr(), _ptr(ws), need, _stream(stream)))
+                                          out.data_ptr(), *_prep(ws), _stream(stream)))
     return out
 
 
@@ -667,7 +672,7 @@ def layernorm_path(rows, E, rqs, codes):
     return int(lib().qe_layernorm_quantize_pack_path(int(rows), int(E), len(rqs), arr, cp))
 
 
-def layernorm_quantize_pack(x, gamma, beta, eps, rqs=(), ln_out=None, codes=None, status=None, stream=None):
+def layernorm_quantize_pack(x, gamma, beta, eps, rqs=(), ln_out=None, codes=None, status=None, workspace=None, stream=None):
     """qe_layernorm_quantize_pack over the last dimension of x: the codes of every quantiser in rqs (a list of capi.requant),
     and the fp32 LayerNorm when ln_out is a tensor or "new".  Returns (list of codes, ln_out or None, status)."""
     import torch
@@ -683,9 +688,9 @@ def layernorm_quantize_pack(x, gamma, beta, eps, rqs=(), ln_out=None, codes=None
     arr = _rq_array(rqs)
     cp = (ctypes.c_void_p * max(1, len(codes)))(*[c.data_ptr() for c in codes])
     need = int(lib().qe_layernorm_quantize_pack_workspace_bytes(int(rows), int(E), len(rqs), arr, cp, _ptr(ln_out)))
-    ws = _ws(need, x.device)
+    ws = _given_ws(workspace, need, x.device)
     check(lib().qe_layernorm_quantize_pack(x.data_ptr(), int(rows), int(E), _ptr(gamma), _ptr(beta), float(eps), len(rqs), arr, cp,
-                                           _ptr(ln_out), status.data_ptr(), _ptr(ws), need, _stream(stream)))
+                                           _ptr(ln_out), status.data_ptr(), *_prep(ws), _stream(stream)))
     return codes, ln_out, status
 
 
