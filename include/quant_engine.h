@@ -319,6 +319,48 @@ int qe_quantconv2d_plan_info(const qe_conv_shape *shape, const qe_qparam *x, con
 int qe_conv_mfma_has_instance(int32_t family, int32_t cfg, int32_t niw, int32_t kkt, int32_t ns, int32_t split,
                               int32_t wraw, int32_t rq, int32_t patch);
 
+/* ---------------------------------------------------------------------------
+ * qe_quantconv2d_depthwise -- a depthwise convolution (groups == IC == OC == C) on packed codes, fp32 and / or codes out.
+ *   reference: the packed forward of modelzoo/modules/quantconv2d.py on a groups = C layer (F.conv2d(..., groups=C) on the
+ *   dequantised tensors; pack() leaves w_des [b, s, C, 1, KH, KW]), followed by ReLU and the consumer's Quantizer + tpack.
+ *   y[n,c,oh,ow] = bias[c] + sum over in-bounds taps (kh,kw) of ((qx - zx) * sx) * ((qw - zw) * sw);  relu != 0: max(y, 0),
+ *   NaN passing, as qe_quantconv2d_residual_prepared.  out (fp32, may be NULL with rq) receives y; codes (with rq) are
+ *   bit-identical to qe_quantize_pack(y, rq->scale, rq->zero, rq->n_param, OH*OW, ...).
+ * shape    IC == OC == C; a depth multiplier (OC != IC) returns QE_ERR_UNSUPPORTED.  KH, KW <= 7 (need not be equal), any
+ *          stride, 2 * padding <= min(KH, KW); anything else returns QE_ERR_UNSUPPORTED.
+ * x, w     packed operands: x N*C*H*W elements, w C*KH*KW elements; n_param 1 or C each (x by input channel = the plane).
+ * bias     fp32[C] or NULL.   rq   n_param 1 or C.   out 4-byte aligned; status as qe_tpack.
+ * QE_ERR_ARG before any device work: a NULL operand, an n_param that is neither 1 nor C, out and codes both NULL, codes
+ *          without rq or rq without codes, an output (out, codes, status) overlapping any operand or another output.
+ * Integer arithmetic on centred codes: the sums over the in-bounds taps are exact in int32, the zero points enter through their
+ * integer parts (exactly) and their remainders (fp32 terms of the size of the remainder), then one fma with sx * sw and bias.
+ * Sub-8-bit rq codes: two planes can share a byte of the stream, so the kernels do not pack them: with out != NULL the call
+ *          runs the kernel into out and then qe_quantize_pack on it (two_pass); with out == NULL it returns QE_ERR_UNSUPPORTED.
+ * No workspace and no prepared tables.  Asynchronous on stream; no host synchronisation, allocation or free.
+ * _path (host only): 1 = the fast kernel (3x3, padding 1, stride 1 or 2, 8-bit x 8-bit codes of any sign pair), 0 = the plain
+ *          kernel (one thread per output), -1 = none (QE_ERR_UNSUPPORTED or a bad argument).  rq may be NULL.
+ * qe_dwconv_plan: the one plan the launcher reads, copied field by field (the call decides nothing, no device work):
+ *   kernel     the instance: 0 plain; 1 + 3 * (stride - 1) + e the fast kernel, e = 0 fp32 out, 1 codes, 2 both
+ *   symmetric  both operands are signed, so a plane whose zero points are 0 has no zero-point term and the kernel skips them
+ *              (an unsigned operand is re-centred by 128 and always has one; the box sum is skipped whenever zw' == 0)
+ *   G TH       the fast kernel's span: G whole consecutive planes per workgroup, or (G == 1) bands of TH output rows
+ *   vec        consecutive outputs of a thread
+ *   store16 codes4  out is 16-byte / codes 4-byte aligned: every store of the body takes that form (otherwise the spans'
+ *              aligned chunks are shifted against the tensor and their edges are completed with narrower stores)
+ *   two_pass   sub-8-bit codes through out and qe_quantize_pack
+ *   OH OW bands     output plane; bands per plane (1: whole planes)
+ *   blocks lds the 1-D grid and the dynamic LDS bytes                                                                    */
+typedef struct qe_dwconv_plan {
+    int32_t kernel, symmetric, G, TH, vec, store16, codes4, two_pass, OH, OW, bands;
+    int64_t blocks, lds;
+} qe_dwconv_plan;
+int qe_quantconv2d_depthwise_path(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq);
+int qe_quantconv2d_depthwise_plan_info(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq,
+                                       const float *out, const uint8_t *codes, qe_dwconv_plan *info);
+int qe_quantconv2d_depthwise(const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *shape,
+                             int32_t relu, float *out, const qe_requant *rq, uint8_t *codes, int32_t *status,
+                             qe_stream_t stream);
+
 /* ---- quantlinear ------------------------------------------------------------
  * Replaces quantlinear / quantlinear_cuda (functions/quantlinear.cu:233-297, :153-214):
  *   out[b, o] = bias[o] + sum_k (q_x[b,k] + zx[b]) * (q_w[o,k] + zw[o]) * (sx[b] * sw[o])

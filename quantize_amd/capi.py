@@ -49,6 +49,12 @@ class QeConvF32Plan(ctypes.Structure):
                 [(n, ctypes.c_int64) for n in ("blocks", "lds", "ep_off", "total")])
 
 
+class QeDwConvPlan(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_int32) for n in (
+        "kernel", "symmetric", "G", "TH", "vec", "store16", "codes4", "two_pass", "OH", "OW", "bands")] +
+                [(n, ctypes.c_int64) for n in ("blocks", "lds")])
+
+
 class QeError(RuntimeError):
     pass
 
@@ -58,6 +64,7 @@ _vp, _i32, _i64, _sz, _f32, _str = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int6
 _pq, _ps, _pr, _ppc = ctypes.POINTER(QeQParam), ctypes.POINTER(QeConvShape), ctypes.POINTER(QeRequant), ctypes.POINTER(_vp)
 _pi = ctypes.POINTER(QeConvPlanInfo)
 _pf = ctypes.POINTER(QeConvF32Plan)
+_pd = ctypes.POINTER(QeDwConvPlan)
 _attn = [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _f32]
 
 # every symbol include/quant_engine.h declares: name -> (restype, argtypes); lib() applies the table
@@ -91,6 +98,10 @@ PROTOTYPES = {
     "qe_quantconv2d_residual_path": (_i32, [_ps, _pq, _pq, _pr]),
     "qe_quantconv2d_residual_workspace_bytes": (_sz, [_ps, _pq, _pq, _pr]),
     "qe_quantconv2d_residual_prepared": (_i32, [_pq, _pq, _vp, _ps, _vp, _sz, _vp, _vp, _pr, _vp, _vp, _vp, _sz, _vp]),
+    # depthwise packed convolutions
+    "qe_quantconv2d_depthwise_path": (_i32, [_ps, _pq, _pq, _pr]),
+    "qe_quantconv2d_depthwise_plan_info": (_i32, [_ps, _pq, _pq, _pr, _vp, _vp, _pd]),
+    "qe_quantconv2d_depthwise": (_i32, [_pq, _pq, _vp, _ps, _i32, _vp, _pr, _vp, _vp, _vp]),
     # float-input convolutions
     "qe_quantconv2d_float_input": (_i32, [_vp, _pq, _vp, _ps, _vp, _vp]),
     "qe_quantconv2d_float_input_path": (_i32, [_ps, _pq]),
@@ -397,6 +408,44 @@ def quantconv2d_residual_prepared(xq, wq, bias, sh, prepared, identity, rq=None,
     check(lib().qe_quantconv2d_residual_prepared(
         ctypes.byref(xq), ctypes.byref(wq), _ptr(bias), ctypes.byref(sh), *_prep(prepared), identity.data_ptr(), _ptr(out),
         None if rq is None else ctypes.byref(rq), _ptr(codes), status.data_ptr(), *_prep(workspace), _stream(stream)))
+    return out, codes, status
+
+
+# qe_dwconv_plan: the kernel instance by number
+DW_KERNELS = ("plain", "fast_s1_out", "fast_s1_codes", "fast_s1_both", "fast_s2_out", "fast_s2_codes", "fast_s2_both")
+
+
+def depthwise_path(sh, xq, wq, rq=None):
+    """qe_quantconv2d_depthwise_path (host-only): 1 = the fast depthwise kernel, 0 = the plain one, -1 = none."""
+    return int(lib().qe_quantconv2d_depthwise_path(ctypes.byref(sh), ctypes.byref(xq), ctypes.byref(wq),
+                                                   None if rq is None else ctypes.byref(rq)))
+
+
+def depthwise_plan_info(sh, xq, wq, rq=None, out=0, codes=0):
+    """qe_quantconv2d_depthwise_plan_info (host-only): the plan of the request as a QeDwConvPlan.  out / codes: destination
+    addresses; with rq, out == 0 asks for the codes-only call (pass any aligned non-zero address for both), codes == 0 reads
+    as aligned."""
+    info = QeDwConvPlan()
+    check(lib().qe_quantconv2d_depthwise_plan_info(ctypes.byref(sh), ctypes.byref(xq), ctypes.byref(wq),
+                                                   None if rq is None else ctypes.byref(rq), int(out) or None, int(codes) or None,
+                                                   ctypes.byref(info)))
+    return info
+
+
+def quantconv2d_depthwise(xq, wq, bias, sh, relu=False, rq=None, out="new", codes=None, status=None, stream=None):
+    """qe_quantconv2d_depthwise: y = [relu](depthwise conv + bias) as fp32 `out` and / or, with rq, the consumer's codes of y.
+    out="new" allocates it, None skips it (rq required), or pass a tensor.  Returns (out or None, codes or None, status)."""
+    import torch
+    dev = wq._keep[0].device
+    OH, OW = out_hw(sh)
+    if isinstance(out, str):
+        out = torch.empty((sh.N, sh.OC, OH, OW), dtype=torch.float32, device=dev)
+    if rq is not None and codes is None:
+        codes = torch.empty(packed_nbytes(sh.N * sh.OC * OH * OW, rq.n_bits), dtype=torch.uint8, device=dev)
+    status = _status(status, dev)
+    check(lib().qe_quantconv2d_depthwise(ctypes.byref(xq), ctypes.byref(wq), _ptr(bias), ctypes.byref(sh), 1 if relu else 0,
+                                         _ptr(out), None if rq is None else ctypes.byref(rq), _ptr(codes), status.data_ptr(),
+                                         _stream(stream)))
     return out, codes, status
 
 

@@ -2,6 +2,7 @@
 // error strings, version, and the conv dispatch (generic fp32 vs int8 MFMA).
 #include "qe_common.h"
 #include "qe_conv_plan.hpp"
+#include "qe_conv_dw.hpp"
 
 #include <atomic>
 #include <cstring>
@@ -577,4 +578,97 @@ extern "C" int qe_maxpool2d_codes(const uint8_t *x, int32_t N, int32_t C, int32_
                        (int)H, (int)W, OH, OW, (int)kernel, (int)stride, (int)padding, (reinterpret_cast<uintptr_t>(out) & 15) == 0 ? 1 : 0);
     QE_LAUNCH_CHECK();
     return QE_OK;
+}
+
+// ---- depthwise packed convolutions (qe_conv_dw.hip): every query and the launch read one plan (plan_dw) ----
+namespace qe {
+static DwRequest dw_request(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq, const float *out,
+                            const uint8_t *codes, bool has_out)
+{
+    return DwRequest{shape, x->n_bits, x->sign, w->n_bits, w->sign, rq ? rq->n_bits : 0, has_out, reinterpret_cast<uintptr_t>(out),
+                     reinterpret_cast<uintptr_t>(codes)};
+}
+
+// shape, operand formats and scale counts of a depthwise request (pointers are not looked at)
+static int check_dw_request(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq)
+{
+    int rc = check_shape(shape);
+    if (rc != QE_OK) return rc;
+    if (x == nullptr || w == nullptr) return QE_ERR_ARG;
+    if (!(x->n_bits > 0 && x->n_bits <= 8) || !(w->n_bits > 0 && w->n_bits <= 8)) return QE_ERR_NBITS;
+    if (rq != nullptr && !(rq->n_bits > 0 && rq->n_bits <= 8)) return QE_ERR_NBITS;
+    if (shape->OC != shape->IC) return QE_ERR_UNSUPPORTED;
+    const int C = shape->IC;
+    if (!(x->n_param == 1 || x->n_param == C) || !(w->n_param == 1 || w->n_param == C)) return QE_ERR_ARG;
+    if (rq != nullptr && !(rq->n_param == 1 || rq->n_param == C)) return QE_ERR_ARG;
+    return QE_OK;
+}
+
+struct Span { uintptr_t lo, hi; };
+static Span span_of(const void *p, int64_t bytes) { return Span{reinterpret_cast<uintptr_t>(p), reinterpret_cast<uintptr_t>(p) + (uintptr_t)bytes}; }
+static bool overlaps(const Span &a, const Span &b) { return a.lo != 0 && b.lo != 0 && a.lo < b.hi && b.lo < a.hi; }
+}  // namespace qe
+
+extern "C" int qe_quantconv2d_depthwise_path(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq)
+{
+    using namespace qe;
+    if (check_dw_request(shape, x, w, rq) != QE_OK) return -1;
+    const DwPlan p = plan_dw(dw_request(shape, x, w, rq, nullptr, nullptr, true));
+    return p.kernel == DW_NONE ? -1 : p.kernel == DW_PLAIN ? 0 : 1;
+}
+
+extern "C" int qe_quantconv2d_depthwise_plan_info(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq,
+                                                  const float *out, const uint8_t *codes, qe_dwconv_plan *info)
+{
+    using namespace qe;
+    if (info == nullptr) return QE_ERR_ARG;
+    int rc = check_dw_request(shape, x, w, rq);
+    if (rc != QE_OK) return rc;
+    const bool sub8 = rq != nullptr && rq->n_bits < 8;
+    const DwPlan p = plan_dw(dw_request(shape, x, w, rq, out, codes, out != nullptr || rq == nullptr || sub8));
+    if (p.kernel == DW_NONE) return QE_ERR_UNSUPPORTED;
+    *info = qe_dwconv_plan{p.kernel, p.symmetric, p.G, p.TH, p.vec, p.store16, p.codes4, p.two_pass, p.OH, p.OW, p.bands, p.blocks, p.lds};
+    return QE_OK;
+}
+
+extern "C" int qe_quantconv2d_depthwise(const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *shape,
+                                        int32_t relu, float *out, const qe_requant *rq, uint8_t *codes, int32_t *status,
+                                        qe_stream_t stream)
+{
+    using namespace qe;
+    int rc = check_shape(shape);
+    if (rc != QE_OK) return rc;
+    if ((rc = check_qparam(x)) != QE_OK) return rc;
+    if ((rc = check_qparam(w)) != QE_OK) return rc;
+    if (rq != nullptr && (rc = check_requant(rq)) != QE_OK) return rc;
+    if ((rc = check_dw_request(shape, x, w, rq)) != QE_OK) return rc;
+    if ((out == nullptr && codes == nullptr) || (codes != nullptr) != (rq != nullptr)) return QE_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(out) & 3) != 0 || (reinterpret_cast<uintptr_t>(status) & 3) != 0) return QE_ERR_ARG;
+    const DwPlan p = plan_dw(dw_request(shape, x, w, rq, out, codes, out != nullptr));
+    if (p.kernel == DW_NONE) return QE_ERR_UNSUPPORTED;
+    if (p.two_pass && out == nullptr) return QE_ERR_UNSUPPORTED;
+    const int C = shape->IC;
+    const int64_t n_in = (int64_t)shape->N * C * shape->H * shape->W, n = (int64_t)shape->N * C * p.OH * p.OW;
+    // an output may overlap neither an operand nor another output
+    const Span outs[3] = {span_of(out, n * 4), span_of(codes, rq ? qe_packed_nbytes(n, rq->n_bits) : 0), span_of(status, 4)};
+    const Span ins[9] = {span_of(x->data, qe_packed_nbytes(n_in, x->n_bits)),
+                         span_of(w->data, qe_packed_nbytes((int64_t)C * shape->KH * shape->KW, w->n_bits)),
+                         span_of(x->scale, 4 * (int64_t)x->n_param), span_of(x->zero, 4 * (int64_t)x->n_param),
+                         span_of(w->scale, 4 * (int64_t)w->n_param), span_of(w->zero, 4 * (int64_t)w->n_param),
+                         span_of(bias, 4 * (int64_t)C), span_of(rq ? rq->scale : nullptr, rq ? 4 * (int64_t)rq->n_param : 0),
+                         span_of(rq ? rq->zero : nullptr, rq ? 4 * (int64_t)rq->n_param : 0)};
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 9; ++j)
+            if (overlaps(outs[i], ins[j])) return QE_ERR_ARG;
+        for (int j = i + 1; j < 3; ++j)
+            if (overlaps(outs[i], outs[j])) return QE_ERR_ARG;
+    }
+    if (n == 0) return QE_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (p.two_pass) {
+        if ((rc = launch_dw(p, x, w, bias, shape, relu, out, nullptr, nullptr, nullptr, s)) != QE_OK) return rc;
+        return qe_quantize_pack(out, n, rq->scale, rq->zero, rq->n_param, (int64_t)p.OH * p.OW, rq->qmin, rq->qmax, rq->n_bits,
+                                rq->sign, codes, status, stream);
+    }
+    return launch_dw(p, x, w, bias, shape, relu, out, rq, codes, status, s);
 }

@@ -46,6 +46,20 @@ inline void launch_instance(unsigned blocks, unsigned threads, size_t lds, size_
     hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(threads), lds, s, a);
 }
 
+// Element `ele_idx` of a packed n_bits stream as the integer it denotes (quantconv2d.cu:103-112 / :118-127 with 64-bit
+// indices): what the order-preserving kernels (qe_conv_generic.hip, the plain depthwise kernel of qe_conv_dw.hip) read with.
+__device__ __forceinline__ int unpack_elem(const uint8_t *__restrict__ p, int64_t ele_idx, int n_bits, int sign)
+{
+    const int64_t bit = ele_idx * n_bits;
+    const int64_t byte_idx = bit >> 3;
+    const int bit_idx = (int)(bit & 7);
+    unsigned v = ((unsigned)p[byte_idx] >> bit_idx) & ((1u << n_bits) - 1u);
+    if (bit_idx + n_bits > 8) v |= ((unsigned)p[byte_idx + 1] << (8 - bit_idx)) & ((1u << n_bits) - 1u);
+    const unsigned offset = sign ? (1u << (n_bits - 1)) : 0u;
+    v = (v - offset) & 0xffu;
+    return sign ? (int)(int8_t)v : (int)v;
+}
+
 __host__ __device__ inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 

@@ -45,19 +45,6 @@ struct GenericConvArgs {
     int oc_blocks;
 };
 
-// quantconv2d.cu:103-112 / :118-127 with 64-bit indices.
-__device__ __forceinline__ int unpack_elem(const uint8_t *__restrict__ p, int64_t ele_idx, int n_bits, int sign)
-{
-    const int64_t bit = ele_idx * n_bits;
-    const int64_t byte_idx = bit >> 3;
-    const int bit_idx = (int)(bit & 7);
-    unsigned v = ((unsigned)p[byte_idx] >> bit_idx) & ((1u << n_bits) - 1u);
-    if (bit_idx + n_bits > 8) v |= ((unsigned)p[byte_idx + 1] << (8 - bit_idx)) & ((1u << n_bits) - 1u);
-    const unsigned offset = sign ? (1u << (n_bits - 1)) : 0u;
-    v = (v - offset) & 0xffu;
-    return sign ? (int)(int8_t)v : (int)v;
-}
-
 constexpr int GC_THREADS = 256;
 constexpr int GC_OCT = 16;  // output channels per thread
 constexpr int GC_PXT = 4;   // consecutive output pixels per thread: a weight vector read from LDS feeds 4 x 16 FMAs

@@ -197,6 +197,57 @@ class PackedConv2d(_PackedBase):
         return out, (des if status is not None else torch.tensor(des, dtype=torch.int32, device=xq.device))
 
 
+class PackedDepthwiseConv2d(_PackedBase):
+    """A packed depthwise QuantConv2d (groups == in_channels == out_channels; pack() leaves w_des [b, s, C, 1, KH, KW]) on
+    qe_quantconv2d_depthwise: codes in, fp32 and / or the consumer's codes out.  The sign convention is the convs':
+    (q - zero), so the zeros are negated.  There is no float-input depthwise kernel and nothing runs in its place."""
+
+    def __init__(self, *, stride=1, padding=0, **state):
+        super().__init__(**state)
+        self.stride, self.padding = _first(stride), _first(padding)
+        self.C, per_group, self.KH, self.KW = self.w_shape
+        if per_group != 1:
+            raise ValueError("%s: w_des %s is not a depthwise layer's (its second shape entry, the input channels of a group, "
+                             "must be 1); use PackedConv2d" % (self.name or "layer", [self.w_bits, int(self.w_signed)] + self.w_shape))
+        self.IC = self.OC = self.C
+
+    @classmethod
+    def from_state_dict(cls, state_dict, prefix="", stride=1, padding=0):
+        return cls(stride=stride, padding=padding, **cls._state(state_dict, prefix))
+
+    def out_hw(self, H, W):
+        return ((H + 2 * self.padding - self.KH) // self.stride + 1, (W + 2 * self.padding - self.KW) // self.stride + 1)
+
+    def shape(self, N, H, W):
+        return capi.conv_shape(N, self.C, H, W, self.C, self.KH, self.KW, self.stride, self.padding)
+
+    def __call__(self, x, route="packed"):
+        if route == "float":
+            raise ValueError("route='float': there is no float-input depthwise kernel; use route='packed'")
+        if route != "packed":
+            raise ValueError("route must be 'packed'")
+        xq, x_des = self.quantize(x)
+        return self.call_packed(xq, x_des)
+
+    def call_packed(self, xq, x_des, consumer=None, relu=False, status=None):
+        """Activations as (packed stream, des), as PackedConv2d.call_packed.  consumer=None: the fp32 output (after the ReLU
+        when relu).  consumer = the Packed* layer that reads [relu of] this layer's output: the (packed, des) pair of ITS
+        activation quantiser from this layer's own epilogue, bit-identical to consumer.quantize([relu](fp32 output)).
+        Sub-8-bit consumers go through an fp32 tensor inside the call (two planes can share a byte of their stream)."""
+        n_bits, sign, N, C, H, W = _host_des(x_des)
+        if C != self.C:
+            raise ValueError("codes of %d channels for a depthwise conv of %d" % (C, self.C))
+        sh, x, w = self.shape(N, H, W), self.xq(xq, n_bits, sign), self.wq()
+        if consumer is None:
+            return capi.quantconv2d_depthwise(x, w, self.bias, sh, relu=relu)[0]
+        _, codes, flag = capi.quantconv2d_depthwise(x, w, self.bias, sh, relu=relu, rq=consumer.requant(),
+                                                    out="new" if consumer.a_bits < 8 else None, status=status)
+        if status is None and int(flag.item()) != 0:
+            raise RuntimeError(OUT_OF_RANGE)
+        des = (consumer.a_bits, int(consumer.a_signed), N, self.C, *self.out_hw(H, W))
+        return codes, (des if status is not None else torch.tensor(des, dtype=torch.int32, device=xq.device))
+
+
 class PackedLinear(_PackedBase):
     """A packed QuantLinear's forward on the engine (quantlinear.py:150-161).  The packed x packed kernel of the
     reference indexes the activation scale by batch ROW (quantlinear.cu:96), so a per-tensor scale is what the modules'
