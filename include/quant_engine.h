@@ -361,6 +361,55 @@ int qe_quantconv2d_depthwise(const qe_qparam *x, const qe_qparam *w, const float
                              int32_t relu, float *out, const qe_requant *rq, uint8_t *codes, int32_t *status,
                              qe_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * qe_quantconv2d_grouped -- a grouped convolution (1 < groups < channels) on packed codes, fp32 and / or codes out.
+ *   reference: the packed forward of modelzoo/modules/quantconv2d.py on a groups = g layer (F.conv2d(..., groups=g) on the
+ *   dequantised tensors; pack() leaves w_des [b, s, OC, IC/g, KH, KW]), followed by ReLU and the consumer's Quantizer + tpack.
+ *   y[n,oc,oh,ow] = bias[oc] + sum over the IC/g input channels ic of oc's group and the in-bounds taps (kh,kw) of
+ *   ((qx - zx) * sx) * ((qw - zw) * sw);  relu != 0: max(y, 0), NaN passing.  out (fp32, may be NULL with rq) receives y; codes
+ *   (with rq) are bit-identical to qe_quantize_pack(y, rq->scale, rq->zero, rq->n_param, OH*OW, ...).
+ * shape    IC and OC are the totals (qe_conv_shape has no groups); w is (OC, IC/groups, KH, KW).  KH, KW <= 7 (need not be
+ *          equal), any stride, 2 * padding <= min(KH, KW); anything else returns QE_ERR_UNSUPPORTED.
+ * groups   must divide IC and OC (else QE_ERR_ARG).  groups == 1 and groups == IC == OC return QE_ERR_UNSUPPORTED: the dense and
+ *          the depthwise entry points own them and nothing is forwarded.
+ * x, w     packed operands: x N*IC*H*W elements, w OC*(IC/groups)*KH*KW elements; x n_param 1 or IC, w n_param 1 or OC.
+ * bias     fp32[OC] or NULL.   rq   n_param 1 or OC.   out 4-byte aligned; status as qe_tpack.
+ * QE_ERR_ARG before any device work: a NULL operand, a bad n_param or groups, out and codes both NULL, codes without rq or rq
+ *          without codes, an output (out, codes, status) overlapping any operand or another output.
+ * Arithmetic, per-tensor x parameters: z = zi + dz (zi = rint(z), |dz| <= 1/2), a = qx - zxi, b = qw - zwi; over the in-bounds
+ *          taps and the group's input channels I = sum a b, A = sum a, B = sum b and the count n are exact in int32;
+ *          f = (float)I + fma((float)n dzx, dzw, -dzx (float)B); when dzw != 0: f = fma(-dzw, (float)A, f); y = fma(sx sw, f, bias).
+ *          (float)I is a rounding step once |I| >= 2^24 (288 products of up to 255 * 255).  Both kernels run this sequence.
+ *          Per-input-channel x parameters: f_c as above per channel c of the group, y = bias, then y = fma(sx[c] sw, f_c, y) in
+ *          channel order (plain kernel only).
+ * Sub-8-bit rq codes: two planes can share a byte of the stream, so the kernels do not pack them: with out != NULL the call
+ *          runs the kernel into out and then qe_quantize_pack on it (two_pass); with out == NULL it returns QE_ERR_UNSUPPORTED.
+ * No workspace and no prepared tables.  Asynchronous on stream; no host synchronisation, allocation or free.
+ * _path (host only): 1 = the fast family (3x3, padding 1, stride 1 or 2, 8-bit x 8-bit codes of any sign pair, per-tensor x
+ *          parameters, IC/groups == OC/groups in {4, 8, 16, 32}) on v_mfma_i32_32x32x32_i8, 0 = the plain kernel (one thread per
+ *          output), -1 = none (QE_ERR_UNSUPPORTED or a bad argument).  rq may be NULL.
+ * qe_grpconv_plan: the one plan the launcher reads, copied field by field (the call decides nothing, no device work):
+ *   kernel     the instance: 0 plain; 1 + 6 * log2(Cg / 4) + 3 * (stride - 1) + e the fast family, e = 0 fp32 out, 1 codes, 2 both
+ *   slab       consecutive channels of a workgroup (fast: 32, i.e. 32 / Cg whole groups; plain: 1)
+ *   TH TW      the workgroup's pixel tile in output rows and columns (fast: a band of TH whole rows, TW == OW; plain: 1 x 1)
+ *   tiles      tiles per plane
+ *   two_pass   sub-8-bit codes through out and qe_quantize_pack
+ *   out16 codes16   out / codes are 16-byte aligned (otherwise the per-channel aligned chunks are shifted against the tensor
+ *              and their edges are completed with narrower stores)
+ *   OH OW      output plane
+ *   blocks lds the 1-D grid and the dynamic LDS bytes                                                                    */
+typedef struct qe_grpconv_plan {
+    int32_t kernel, slab, TH, TW, tiles, two_pass, out16, codes16, OH, OW;
+    int64_t blocks, lds;
+} qe_grpconv_plan;
+int qe_quantconv2d_grouped_path(const qe_conv_shape *shape, int32_t groups, const qe_qparam *x, const qe_qparam *w,
+                                const qe_requant *rq);
+int qe_quantconv2d_grouped_plan_info(const qe_conv_shape *shape, int32_t groups, const qe_qparam *x, const qe_qparam *w,
+                                     const qe_requant *rq, const float *out, const uint8_t *codes, qe_grpconv_plan *info);
+int qe_quantconv2d_grouped(const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *shape,
+                           int32_t groups, int32_t relu, float *out, const qe_requant *rq, uint8_t *codes, int32_t *status,
+                           qe_stream_t stream);
+
 /* ---- quantlinear ------------------------------------------------------------
  * Replaces quantlinear / quantlinear_cuda (functions/quantlinear.cu:233-297, :153-214):
  *   out[b, o] = bias[o] + sum_k (q_x[b,k] + zx[b]) * (q_w[o,k] + zw[o]) * (sx[b] * sw[o])

@@ -55,6 +55,12 @@ class QeDwConvPlan(ctypes.Structure):
                 [(n, ctypes.c_int64) for n in ("blocks", "lds")])
 
 
+class QeGrpConvPlan(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_int32) for n in (
+        "kernel", "slab", "TH", "TW", "tiles", "two_pass", "out16", "codes16", "OH", "OW")] +
+                [(n, ctypes.c_int64) for n in ("blocks", "lds")])
+
+
 class QeError(RuntimeError):
     pass
 
@@ -65,6 +71,7 @@ _pq, _ps, _pr, _ppc = ctypes.POINTER(QeQParam), ctypes.POINTER(QeConvShape), cty
 _pi = ctypes.POINTER(QeConvPlanInfo)
 _pf = ctypes.POINTER(QeConvF32Plan)
 _pd = ctypes.POINTER(QeDwConvPlan)
+_pg = ctypes.POINTER(QeGrpConvPlan)
 _attn = [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _f32]
 
 # every symbol include/quant_engine.h declares: name -> (restype, argtypes); lib() applies the table
@@ -102,6 +109,10 @@ PROTOTYPES = {
     "qe_quantconv2d_depthwise_path": (_i32, [_ps, _pq, _pq, _pr]),
     "qe_quantconv2d_depthwise_plan_info": (_i32, [_ps, _pq, _pq, _pr, _vp, _vp, _pd]),
     "qe_quantconv2d_depthwise": (_i32, [_pq, _pq, _vp, _ps, _i32, _vp, _pr, _vp, _vp, _vp]),
+    # grouped packed convolutions
+    "qe_quantconv2d_grouped_path": (_i32, [_ps, _i32, _pq, _pq, _pr]),
+    "qe_quantconv2d_grouped_plan_info": (_i32, [_ps, _i32, _pq, _pq, _pr, _vp, _vp, _pg]),
+    "qe_quantconv2d_grouped": (_i32, [_pq, _pq, _vp, _ps, _i32, _i32, _vp, _pr, _vp, _vp, _vp]),
     # float-input convolutions
     "qe_quantconv2d_float_input": (_i32, [_vp, _pq, _vp, _ps, _vp, _vp]),
     "qe_quantconv2d_float_input_path": (_i32, [_ps, _pq]),
@@ -446,6 +457,45 @@ def quantconv2d_depthwise(xq, wq, bias, sh, relu=False, rq=None, out="new", code
     check(lib().qe_quantconv2d_depthwise(ctypes.byref(xq), ctypes.byref(wq), _ptr(bias), ctypes.byref(sh), 1 if relu else 0,
                                          _ptr(out), None if rq is None else ctypes.byref(rq), _ptr(codes), status.data_ptr(),
                                          _stream(stream)))
+    return out, codes, status
+
+
+# qe_grpconv_plan: the kernel instance by number
+GRP_KERNELS = ("plain",) + tuple("fast_cg%d_s%d_%s" % (cg, s, e) for cg in (4, 8, 16, 32) for s in (1, 2)
+                                 for e in ("out", "codes", "both"))
+
+
+def grouped_path(sh, groups, xq, wq, rq=None):
+    """qe_quantconv2d_grouped_path (host-only): 1 = the fast grouped family, 0 = the plain kernel, -1 = none."""
+    return int(lib().qe_quantconv2d_grouped_path(ctypes.byref(sh), int(groups), ctypes.byref(xq), ctypes.byref(wq),
+                                                 None if rq is None else ctypes.byref(rq)))
+
+
+def grouped_plan_info(sh, groups, xq, wq, rq=None, out=0, codes=0):
+    """qe_quantconv2d_grouped_plan_info (host-only): the plan of the request as a QeGrpConvPlan.  out / codes: destination
+    addresses; with rq, out == 0 asks for the codes-only call (pass any aligned non-zero address for both), codes == 0 reads
+    as aligned."""
+    info = QeGrpConvPlan()
+    check(lib().qe_quantconv2d_grouped_plan_info(ctypes.byref(sh), int(groups), ctypes.byref(xq), ctypes.byref(wq),
+                                                 None if rq is None else ctypes.byref(rq), int(out) or None, int(codes) or None,
+                                                 ctypes.byref(info)))
+    return info
+
+
+def quantconv2d_grouped(xq, wq, bias, sh, groups, relu=False, rq=None, out="new", codes=None, status=None, stream=None):
+    """qe_quantconv2d_grouped: y = [relu](grouped conv + bias) as fp32 `out` and / or, with rq, the consumer's codes of y.
+    out="new" allocates it, None skips it (rq required), or pass a tensor.  Returns (out or None, codes or None, status)."""
+    import torch
+    dev = wq._keep[0].device
+    OH, OW = out_hw(sh)
+    if isinstance(out, str):
+        out = torch.empty((sh.N, sh.OC, OH, OW), dtype=torch.float32, device=dev)
+    if rq is not None and codes is None:
+        codes = torch.empty(packed_nbytes(sh.N * sh.OC * OH * OW, rq.n_bits), dtype=torch.uint8, device=dev)
+    status = _status(status, dev)
+    check(lib().qe_quantconv2d_grouped(ctypes.byref(xq), ctypes.byref(wq), _ptr(bias), ctypes.byref(sh), int(groups),
+                                       1 if relu else 0, _ptr(out), None if rq is None else ctypes.byref(rq), _ptr(codes),
+                                       status.data_ptr(), _stream(stream)))
     return out, codes, status
 
 

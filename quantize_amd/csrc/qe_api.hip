@@ -3,6 +3,7 @@
 #include "qe_common.h"
 #include "qe_conv_plan.hpp"
 #include "qe_conv_dw.hpp"
+#include "qe_conv_grp.hpp"
 
 #include <atomic>
 #include <cstring>
@@ -671,4 +672,95 @@ extern "C" int qe_quantconv2d_depthwise(const qe_qparam *x, const qe_qparam *w, 
                                 rq->sign, codes, status, stream);
     }
     return launch_dw(p, x, w, bias, shape, relu, out, rq, codes, status, s);
+}
+
+// ---- grouped packed convolutions (qe_conv_grp.hip): every query and the launch read one plan (plan_grp) ----
+namespace qe {
+static GrpRequest grp_request(const qe_conv_shape *shape, int groups, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq,
+                              const float *out, const uint8_t *codes, bool has_out)
+{
+    return GrpRequest{shape, groups, x->n_bits, x->sign, x->n_param, w->n_bits, w->sign, rq ? rq->n_bits : 0, has_out,
+                      reinterpret_cast<uintptr_t>(out), reinterpret_cast<uintptr_t>(codes)};
+}
+
+// shape, groups, operand formats and scale counts of a grouped request (pointers are not looked at)
+static int check_grp_request(const qe_conv_shape *shape, int groups, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq)
+{
+    int rc = check_shape(shape);
+    if (rc != QE_OK) return rc;
+    if (x == nullptr || w == nullptr) return QE_ERR_ARG;
+    if (!(x->n_bits > 0 && x->n_bits <= 8) || !(w->n_bits > 0 && w->n_bits <= 8)) return QE_ERR_NBITS;
+    if (rq != nullptr && !(rq->n_bits > 0 && rq->n_bits <= 8)) return QE_ERR_NBITS;
+    if (groups < 1 || shape->OC < 1 || shape->IC % groups != 0 || shape->OC % groups != 0) return QE_ERR_ARG;
+    if (!(x->n_param == 1 || x->n_param == shape->IC) || !(w->n_param == 1 || w->n_param == shape->OC)) return QE_ERR_ARG;
+    if (rq != nullptr && !(rq->n_param == 1 || rq->n_param == shape->OC)) return QE_ERR_ARG;
+    // the dense and the depthwise entry points own these; they are not forwarded
+    if (groups == 1 || (groups == shape->IC && groups == shape->OC)) return QE_ERR_UNSUPPORTED;
+    return QE_OK;
+}
+}  // namespace qe
+
+extern "C" int qe_quantconv2d_grouped_path(const qe_conv_shape *shape, int32_t groups, const qe_qparam *x, const qe_qparam *w,
+                                           const qe_requant *rq)
+{
+    using namespace qe;
+    if (check_grp_request(shape, groups, x, w, rq) != QE_OK) return -1;
+    const GrpPlan p = plan_grp(grp_request(shape, groups, x, w, rq, nullptr, nullptr, true));
+    return p.kernel == GRP_NONE ? -1 : p.kernel == GRP_PLAIN ? 0 : 1;
+}
+
+extern "C" int qe_quantconv2d_grouped_plan_info(const qe_conv_shape *shape, int32_t groups, const qe_qparam *x, const qe_qparam *w,
+                                                const qe_requant *rq, const float *out, const uint8_t *codes, qe_grpconv_plan *info)
+{
+    using namespace qe;
+    if (info == nullptr) return QE_ERR_ARG;
+    int rc = check_grp_request(shape, groups, x, w, rq);
+    if (rc != QE_OK) return rc;
+    const bool sub8 = rq != nullptr && rq->n_bits < 8;
+    const GrpPlan p = plan_grp(grp_request(shape, groups, x, w, rq, out, codes, out != nullptr || rq == nullptr || sub8));
+    if (p.kernel == GRP_NONE) return QE_ERR_UNSUPPORTED;
+    *info = qe_grpconv_plan{p.kernel, p.slab, p.TH, p.TW, p.tiles, p.two_pass, p.out16, p.codes16, p.OH, p.OW, p.blocks, p.lds};
+    return QE_OK;
+}
+
+extern "C" int qe_quantconv2d_grouped(const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *shape,
+                                      int32_t groups, int32_t relu, float *out, const qe_requant *rq, uint8_t *codes,
+                                      int32_t *status, qe_stream_t stream)
+{
+    using namespace qe;
+    int rc = check_shape(shape);
+    if (rc != QE_OK) return rc;
+    if ((rc = check_qparam(x)) != QE_OK) return rc;
+    if ((rc = check_qparam(w)) != QE_OK) return rc;
+    if (rq != nullptr && (rc = check_requant(rq)) != QE_OK) return rc;
+    if ((rc = check_grp_request(shape, groups, x, w, rq)) != QE_OK) return rc;
+    if ((out == nullptr && codes == nullptr) || (codes != nullptr) != (rq != nullptr)) return QE_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(out) & 3) != 0 || (reinterpret_cast<uintptr_t>(status) & 3) != 0) return QE_ERR_ARG;
+    const GrpPlan p = plan_grp(grp_request(shape, groups, x, w, rq, out, codes, out != nullptr));
+    if (p.kernel == GRP_NONE) return QE_ERR_UNSUPPORTED;
+    if (p.two_pass && out == nullptr) return QE_ERR_UNSUPPORTED;
+    const int IC = shape->IC, OC = shape->OC;
+    const int64_t n_in = (int64_t)shape->N * IC * shape->H * shape->W, n = (int64_t)shape->N * OC * p.OH * p.OW;
+    // an output may overlap neither an operand nor another output
+    const Span outs[3] = {span_of(out, n * 4), span_of(codes, rq ? qe_packed_nbytes(n, rq->n_bits) : 0), span_of(status, 4)};
+    const Span ins[9] = {span_of(x->data, qe_packed_nbytes(n_in, x->n_bits)),
+                         span_of(w->data, qe_packed_nbytes((int64_t)OC * (IC / groups) * shape->KH * shape->KW, w->n_bits)),
+                         span_of(x->scale, 4 * (int64_t)x->n_param), span_of(x->zero, 4 * (int64_t)x->n_param),
+                         span_of(w->scale, 4 * (int64_t)w->n_param), span_of(w->zero, 4 * (int64_t)w->n_param),
+                         span_of(bias, 4 * (int64_t)OC), span_of(rq ? rq->scale : nullptr, rq ? 4 * (int64_t)rq->n_param : 0),
+                         span_of(rq ? rq->zero : nullptr, rq ? 4 * (int64_t)rq->n_param : 0)};
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 9; ++j)
+            if (overlaps(outs[i], ins[j])) return QE_ERR_ARG;
+        for (int j = i + 1; j < 3; ++j)
+            if (overlaps(outs[i], outs[j])) return QE_ERR_ARG;
+    }
+    if (n == 0) return QE_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (p.two_pass) {
+        if ((rc = launch_grp(p, x, w, bias, shape, groups, relu, out, nullptr, nullptr, nullptr, s)) != QE_OK) return rc;
+        return qe_quantize_pack(out, n, rq->scale, rq->zero, rq->n_param, (int64_t)p.OH * p.OW, rq->qmin, rq->qmax, rq->n_bits,
+                                rq->sign, codes, status, stream);
+    }
+    return launch_grp(p, x, w, bias, shape, groups, relu, out, rq, codes, status, s);
 }

@@ -248,6 +248,67 @@ class PackedDepthwiseConv2d(_PackedBase):
         return codes, (des if status is not None else torch.tensor(des, dtype=torch.int32, device=xq.device))
 
 
+class PackedGroupedConv2d(_PackedBase):
+    """A packed grouped QuantConv2d (1 < groups < channels; pack() leaves w_des [b, s, OC, IC / groups, KH, KW]) on
+    qe_quantconv2d_grouped: codes in, fp32 and / or the consumer's codes out.  w_des does not name the groups, so the layer's
+    input channels are given.  The sign convention is the convs': (q - zero), so the zeros are negated.  There is no
+    float-input grouped kernel and nothing runs in its place."""
+
+    def __init__(self, *, stride=1, padding=0, in_channels, **state):
+        super().__init__(**state)
+        self.stride, self.padding = _first(stride), _first(padding)
+        self.OC, self.ICg, self.KH, self.KW = self.w_shape
+        self.IC = int(in_channels)
+        who = self.name or "layer"
+        if self.ICg < 1 or self.IC % self.ICg != 0:
+            raise ValueError("%s: %d input channels are no multiple of the %d a group has in w_des" % (who, self.IC, self.ICg))
+        self.groups = self.IC // self.ICg
+        if self.groups == 1:
+            raise ValueError("%s: groups == 1 is a dense layer; use PackedConv2d" % who)
+        if self.OC % self.groups != 0:
+            raise ValueError("%s: %d output channels are no multiple of the %d groups" % (who, self.OC, self.groups))
+        if self.groups == self.IC and self.OC == self.IC:
+            raise ValueError("%s: groups == in_channels == out_channels is a depthwise layer; use PackedDepthwiseConv2d" % who)
+
+    @classmethod
+    def from_state_dict(cls, state_dict, prefix="", stride=1, padding=0, in_channels=None):
+        if in_channels is None:
+            raise ValueError("PackedGroupedConv2d.from_state_dict: in_channels is required (w_des does not name the groups)")
+        return cls(stride=stride, padding=padding, in_channels=in_channels, **cls._state(state_dict, prefix))
+
+    def out_hw(self, H, W):
+        return ((H + 2 * self.padding - self.KH) // self.stride + 1, (W + 2 * self.padding - self.KW) // self.stride + 1)
+
+    def shape(self, N, H, W):
+        return capi.conv_shape(N, self.IC, H, W, self.OC, self.KH, self.KW, self.stride, self.padding)
+
+    def __call__(self, x, route="packed"):
+        if route == "float":
+            raise ValueError("route='float': there is no float-input grouped kernel; use route='packed'")
+        if route != "packed":
+            raise ValueError("route must be 'packed'")
+        xq, x_des = self.quantize(x)
+        return self.call_packed(xq, x_des)
+
+    def call_packed(self, xq, x_des, consumer=None, relu=False, status=None):
+        """Activations as (packed stream, des), as PackedConv2d.call_packed.  consumer=None: the fp32 output (after the ReLU
+        when relu).  consumer = the Packed* layer that reads [relu of] this layer's output: the (packed, des) pair of ITS
+        activation quantiser from this layer's own epilogue, bit-identical to consumer.quantize([relu](fp32 output)).
+        Sub-8-bit consumers go through an fp32 tensor inside the call (two planes can share a byte of their stream)."""
+        n_bits, sign, N, C, H, W = _host_des(x_des)
+        if C != self.IC:
+            raise ValueError("codes of %d channels for a grouped conv of %d" % (C, self.IC))
+        sh, x, w = self.shape(N, H, W), self.xq(xq, n_bits, sign), self.wq()
+        if consumer is None:
+            return capi.quantconv2d_grouped(x, w, self.bias, sh, self.groups, relu=relu)[0]
+        _, codes, flag = capi.quantconv2d_grouped(x, w, self.bias, sh, self.groups, relu=relu, rq=consumer.requant(),
+                                                  out="new" if consumer.a_bits < 8 else None, status=status)
+        if status is None and int(flag.item()) != 0:
+            raise RuntimeError(OUT_OF_RANGE)
+        des = (consumer.a_bits, int(consumer.a_signed), N, self.OC, *self.out_hw(H, W))
+        return codes, (des if status is not None else torch.tensor(des, dtype=torch.int32, device=xq.device))
+
+
 class PackedLinear(_PackedBase):
     """A packed QuantLinear's forward on the engine (quantlinear.py:150-161).  The packed x packed kernel of the
     reference indexes the activation scale by batch ROW (quantlinear.cu:96), so a per-tensor scale is what the modules'

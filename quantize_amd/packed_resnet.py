@@ -29,7 +29,7 @@ import torch
 import torch.nn.functional as F
 
 from . import capi
-from .packed import OUT_OF_RANGE, PackedConv2d, PackedLinear
+from .packed import OUT_OF_RANGE, PackedConv2d, PackedGroupedConv2d, PackedLinear
 
 
 class _Block:
@@ -49,8 +49,8 @@ def _stage_keys(sd):
 class PackedResNet:
     """A packed torchvision ResNet (Bottleneck: ResNet-50 / 101 / 152, BasicBlock: ResNet-18 / 34) on the engine."""
 
-    def __init__(self, stem, stages, fc, kind):
-        self.stem, self.stages, self.fc, self.kind = stem, stages, fc, kind
+    def __init__(self, stem, stages, fc, kind, groups=1):
+        self.stem, self.stages, self.fc, self.kind, self.groups = stem, stages, fc, kind, groups
 
     @property
     def fc_des(self):
@@ -63,9 +63,13 @@ class PackedResNet:
         (the BasicBlock's conv1) and on the downsample; 3x3 convs pad 1, 1x1 convs pad 0."""
         sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
 
-        def conv(name, stride, padding):
+        def conv(name, stride, padding, in_channels=None):
+            """in_channels: what feeds the layer; a w_des that names fewer input channels is a grouped layer's (ResNeXt)."""
             try:
-                c = PackedConv2d.from_state_dict(sd, name + ".", stride=stride, padding=padding)
+                if in_channels is not None and (name + ".w_des") in sd and int(sd[name + ".w_des"][3]) < in_channels:
+                    c = PackedGroupedConv2d.from_state_dict(sd, name + ".", stride=stride, padding=padding, in_channels=in_channels)
+                else:
+                    c = PackedConv2d.from_state_dict(sd, name + ".", stride=stride, padding=padding)
             except KeyError as e:
                 raise KeyError("packed ResNet state_dict: missing %s%s" % (prefix, e.args[0])) from None
             if c.KH != 2 * padding + 1 or c.KW != c.KH:
@@ -84,7 +88,7 @@ class PackedResNet:
             kind = "basic"
         else:
             raise ValueError("packed ResNet state_dict: blocks with conv sets %s are neither Bottleneck nor BasicBlock" % sorted(kinds))
-        stages = []
+        stages, groups = [], set()
         for S in sorted(found):
             if sorted(found[S]) != list(range(len(found[S]))):
                 raise KeyError("packed ResNet state_dict: layer%d has blocks %s" % (S, sorted(found[S])))
@@ -93,9 +97,14 @@ class PackedResNet:
                 pre = "layer%d.%d." % (S, B)
                 s = (1 if S == 1 else 2) if B == 0 else 1
                 if kind == "bottleneck":
-                    convs = [conv(pre + "conv1", 1, 0), conv(pre + "conv2", s, 1), conv(pre + "conv3", 1, 0)]
+                    c1 = conv(pre + "conv1", 1, 0)
+                    convs = [c1, conv(pre + "conv2", s, 1, c1.OC), conv(pre + "conv3", 1, 0)]
+                    groups.add(getattr(convs[1], "groups", 1))
                 else:
                     convs = [conv(pre + "conv1", s, 1), conv(pre + "conv2", 1, 1)]
+                    if convs[1].IC != convs[0].OC:
+                        raise ValueError("%sconv2: a grouped conv in a BasicBlock is not supported (w_des names %d input channels, "
+                                         "conv1 has %d outputs)" % (pre, convs[1].IC, convs[0].OC))
                 ds = conv(pre + "downsample.0", s, 0) if (pre + "downsample.0.w_des") in sd else None
                 if B == 0 and ds is None and (s != 1 or convs[0].IC != convs[-1].OC):
                     raise KeyError("packed ResNet state_dict: missing %s%sdownsample.0.w_des" % (prefix, pre))
@@ -105,7 +114,9 @@ class PackedResNet:
             fc = PackedLinear.from_state_dict(sd, "fc.")
         except KeyError as e:
             raise KeyError("packed ResNet state_dict: missing %s%s" % (prefix, e.args[0])) from None
-        return cls(stem, stages, fc, kind)
+        if len(groups) > 1:
+            raise ValueError("packed ResNet state_dict: the Bottlenecks' conv2 layers have different groups %s" % sorted(groups))
+        return cls(stem, stages, fc, kind, groups.pop() if groups else 1)
 
     # ---- introspection ----
     def blocks(self):
@@ -188,7 +199,10 @@ class PackedResNet:
         return y
 
     def _conv_codes(self, c, codes, N, H, W, consumer, status):
-        """c's output as consumer's codes: fused into c's epilogue where the ReLU folds, else fp32 + relu + quantize_pack."""
+        """c's output as consumer's codes: fused into c's epilogue where the ReLU folds, else fp32 + relu + quantize_pack.
+        A grouped conv (ResNeXt's conv2) applies the ReLU in its own epilogue, whatever the consumer's quantiser."""
+        if isinstance(c, PackedGroupedConv2d):
+            return c.call_packed(codes, (c.a_bits, int(c.a_signed), N, c.IC, H, W), consumer, relu=True, status=status)[0]
         sh, xq, wq, prep = c.operands(codes, N, H, W)
         if consumer.folds_relu:
             return capi.quantconv2d_requant_prepared(xq, wq, c.bias, sh, prep, consumer.requant(), status=status)[0]
@@ -279,8 +293,9 @@ def pack_codes(q, n_bits, signed):
     return np.packbits(bits, bitorder="little")
 
 
-def _conv_entries(rng, IC, OC, K, w_bits, a_bits, a_signed, gain):
+def _conv_entries(rng, IC, OC, K, w_bits, a_bits, a_signed, gain, groups=1):
     lim = (1 << (w_bits - 1)) - 1
+    IC //= groups                  # the input channels a weight sees: pack() stores w_des [b, s, OC, IC / groups, KH, KW]
     q = rng.randint(-lim, lim + 1, size=(OC, IC, K, K))
     std_q = np.sqrt(((2 * lim + 1) ** 2 - 1) / 12.0)
     ws = gain * np.sqrt(2.0 / (IC * K * K)) / std_q * rng.uniform(0.8, 1.2, size=OC)     # He-scaled
@@ -295,10 +310,12 @@ def _conv_entries(rng, IC, OC, K, w_bits, a_bits, a_signed, gain):
             "a_quantizer.qmin": torch.tensor(float(qmin)), "a_quantizer.qmax": torch.tensor(float(qmax))}
 
 
-def synthetic_state_dict(arch="resnet50", num_classes=1000, w_bits=8, a_bits=8, seed=0, width=64):
+def synthetic_state_dict(arch="resnet50", num_classes=1000, w_bits=8, a_bits=8, seed=0, width=64, groups=1, width_per_group=64):
     """A packed ResNet state_dict in the key layout pack() leaves (host tensors, scales not calibrated: 1.0).  Random
     b-bit weights, He-scaled (block-end convs at gain 0.3 so activations stay O(1) through 16 blocks), folded biases;
-    post-ReLU activation quantisers unsigned, the image quantiser signed.  See calibrated_state_dict."""
+    post-ReLU activation quantisers unsigned, the image quantiser signed.  See calibrated_state_dict.
+    groups / width_per_group: torchvision's ResNeXt Bottleneck (resnext50_32x4d: arch="resnet50", groups=32,
+    width_per_group=4) -- conv1 and conv2 have planes * width_per_group / 64 * groups channels, conv2 is grouped."""
     kind, depth = ARCHS[arch]
     rng = np.random.RandomState(seed)
     sd = {}
@@ -314,9 +331,10 @@ def synthetic_state_dict(arch="resnet50", num_classes=1000, w_bits=8, a_bits=8, 
         for B in range(nb):
             pre = "layer%d.%d" % (S, B)
             if kind == "bottleneck":
-                put(pre + ".conv1", _conv_entries(rng, inplanes, planes, 1, w_bits, a_bits, False, 1.0))
-                put(pre + ".conv2", _conv_entries(rng, planes, planes, 3, w_bits, a_bits, False, 1.0))
-                put(pre + ".conv3", _conv_entries(rng, planes, planes * 4, 1, w_bits, a_bits, False, 0.3))
+                mid = planes * width_per_group // 64 * groups
+                put(pre + ".conv1", _conv_entries(rng, inplanes, mid, 1, w_bits, a_bits, False, 1.0))
+                put(pre + ".conv2", _conv_entries(rng, mid, mid, 3, w_bits, a_bits, False, 1.0, groups))
+                put(pre + ".conv3", _conv_entries(rng, mid, planes * 4, 1, w_bits, a_bits, False, 0.3))
             else:
                 put(pre + ".conv1", _conv_entries(rng, inplanes, planes, 3, w_bits, a_bits, False, 1.0))
                 put(pre + ".conv2", _conv_entries(rng, planes, planes, 3, w_bits, a_bits, False, 0.3))
