@@ -426,26 +426,19 @@ def quantconv2d_residual_prepared(xq, wq, bias, sh, prepared, identity, rq=None,
 DW_KERNELS = ("plain", "fast_s1_out", "fast_s1_codes", "fast_s1_both", "fast_s2_out", "fast_s2_codes", "fast_s2_both")
 
 
-def depthwise_path(sh, xq, wq, rq=None):
-    """qe_quantconv2d_depthwise_path (host-only): 1 = the fast depthwise kernel, 0 = the plain one, -1 = none."""
-    return int(lib().qe_quantconv2d_depthwise_path(ctypes.byref(sh), ctypes.byref(xq), ctypes.byref(wq),
-                                                   None if rq is None else ctypes.byref(rq)))
+# The depthwise and the grouped entry points differ in their names, in one `groups` argument (head: () | (groups,)) and in
+# their plan struct; one helper each stands behind the two path queries, the two plan queries and the two calls.
+def _span_path(fn, sh, head, xq, wq, rq):
+    return int(fn(ctypes.byref(sh), *head, ctypes.byref(xq), ctypes.byref(wq), None if rq is None else ctypes.byref(rq)))
 
 
-def depthwise_plan_info(sh, xq, wq, rq=None, out=0, codes=0):
-    """qe_quantconv2d_depthwise_plan_info (host-only): the plan of the request as a QeDwConvPlan.  out / codes: destination
-    addresses; with rq, out == 0 asks for the codes-only call (pass any aligned non-zero address for both), codes == 0 reads
-    as aligned."""
-    info = QeDwConvPlan()
-    check(lib().qe_quantconv2d_depthwise_plan_info(ctypes.byref(sh), ctypes.byref(xq), ctypes.byref(wq),
-                                                   None if rq is None else ctypes.byref(rq), int(out) or None, int(codes) or None,
-                                                   ctypes.byref(info)))
+def _span_plan_info(fn, info, sh, head, xq, wq, rq, out, codes):
+    check(fn(ctypes.byref(sh), *head, ctypes.byref(xq), ctypes.byref(wq), None if rq is None else ctypes.byref(rq),
+             int(out) or None, int(codes) or None, ctypes.byref(info)))
     return info
 
 
-def quantconv2d_depthwise(xq, wq, bias, sh, relu=False, rq=None, out="new", codes=None, status=None, stream=None):
-    """qe_quantconv2d_depthwise: y = [relu](depthwise conv + bias) as fp32 `out` and / or, with rq, the consumer's codes of y.
-    out="new" allocates it, None skips it (rq required), or pass a tensor.  Returns (out or None, codes or None, status)."""
+def _span_conv(fn, xq, wq, bias, sh, head, relu, rq, out, codes, status, stream):
     import torch
     dev = wq._keep[0].device
     OH, OW = out_hw(sh)
@@ -454,10 +447,27 @@ def quantconv2d_depthwise(xq, wq, bias, sh, relu=False, rq=None, out="new", code
     if rq is not None and codes is None:
         codes = torch.empty(packed_nbytes(sh.N * sh.OC * OH * OW, rq.n_bits), dtype=torch.uint8, device=dev)
     status = _status(status, dev)
-    check(lib().qe_quantconv2d_depthwise(ctypes.byref(xq), ctypes.byref(wq), _ptr(bias), ctypes.byref(sh), 1 if relu else 0,
-                                         _ptr(out), None if rq is None else ctypes.byref(rq), _ptr(codes), status.data_ptr(),
-                                         _stream(stream)))
+    check(fn(ctypes.byref(xq), ctypes.byref(wq), _ptr(bias), ctypes.byref(sh), *head, 1 if relu else 0, _ptr(out),
+             None if rq is None else ctypes.byref(rq), _ptr(codes), status.data_ptr(), _stream(stream)))
     return out, codes, status
+
+
+def depthwise_path(sh, xq, wq, rq=None):
+    """qe_quantconv2d_depthwise_path (host-only): 1 = the fast depthwise kernel, 0 = the plain one, -1 = none."""
+    return _span_path(lib().qe_quantconv2d_depthwise_path, sh, (), xq, wq, rq)
+
+
+def depthwise_plan_info(sh, xq, wq, rq=None, out=0, codes=0):
+    """qe_quantconv2d_depthwise_plan_info (host-only): the plan of the request as a QeDwConvPlan.  out / codes: destination
+    addresses; with rq, out == 0 asks for the codes-only call (pass any aligned non-zero address for both), codes == 0 reads
+    as aligned."""
+    return _span_plan_info(lib().qe_quantconv2d_depthwise_plan_info, QeDwConvPlan(), sh, (), xq, wq, rq, out, codes)
+
+
+def quantconv2d_depthwise(xq, wq, bias, sh, relu=False, rq=None, out="new", codes=None, status=None, stream=None):
+    """qe_quantconv2d_depthwise: y = [relu](depthwise conv + bias) as fp32 `out` and / or, with rq, the consumer's codes of y.
+    out="new" allocates it, None skips it (rq required), or pass a tensor.  Returns (out or None, codes or None, status)."""
+    return _span_conv(lib().qe_quantconv2d_depthwise, xq, wq, bias, sh, (), relu, rq, out, codes, status, stream)
 
 
 # qe_grpconv_plan: the kernel instance by number
@@ -467,36 +477,20 @@ GRP_KERNELS = ("plain",) + tuple("fast_cg%d_s%d_%s" % (cg, s, e) for cg in (4, 8
 
 def grouped_path(sh, groups, xq, wq, rq=None):
     """qe_quantconv2d_grouped_path (host-only): 1 = the fast grouped family, 0 = the plain kernel, -1 = none."""
-    return int(lib().qe_quantconv2d_grouped_path(ctypes.byref(sh), int(groups), ctypes.byref(xq), ctypes.byref(wq),
-                                                 None if rq is None else ctypes.byref(rq)))
+    return _span_path(lib().qe_quantconv2d_grouped_path, sh, (int(groups),), xq, wq, rq)
 
 
 def grouped_plan_info(sh, groups, xq, wq, rq=None, out=0, codes=0):
     """qe_quantconv2d_grouped_plan_info (host-only): the plan of the request as a QeGrpConvPlan.  out / codes: destination
     addresses; with rq, out == 0 asks for the codes-only call (pass any aligned non-zero address for both), codes == 0 reads
     as aligned."""
-    info = QeGrpConvPlan()
-    check(lib().qe_quantconv2d_grouped_plan_info(ctypes.byref(sh), int(groups), ctypes.byref(xq), ctypes.byref(wq),
-                                                 None if rq is None else ctypes.byref(rq), int(out) or None, int(codes) or None,
-                                                 ctypes.byref(info)))
-    return info
+    return _span_plan_info(lib().qe_quantconv2d_grouped_plan_info, QeGrpConvPlan(), sh, (int(groups),), xq, wq, rq, out, codes)
 
 
 def quantconv2d_grouped(xq, wq, bias, sh, groups, relu=False, rq=None, out="new", codes=None, status=None, stream=None):
     """qe_quantconv2d_grouped: y = [relu](grouped conv + bias) as fp32 `out` and / or, with rq, the consumer's codes of y.
     out="new" allocates it, None skips it (rq required), or pass a tensor.  Returns (out or None, codes or None, status)."""
-    import torch
-    dev = wq._keep[0].device
-    OH, OW = out_hw(sh)
-    if isinstance(out, str):
-        out = torch.empty((sh.N, sh.OC, OH, OW), dtype=torch.float32, device=dev)
-    if rq is not None and codes is None:
-        codes = torch.empty(packed_nbytes(sh.N * sh.OC * OH * OW, rq.n_bits), dtype=torch.uint8, device=dev)
-    status = _status(status, dev)
-    check(lib().qe_quantconv2d_grouped(ctypes.byref(xq), ctypes.byref(wq), _ptr(bias), ctypes.byref(sh), int(groups),
-                                       1 if relu else 0, _ptr(out), None if rq is None else ctypes.byref(rq), _ptr(codes),
-                                       status.data_ptr(), _stream(stream)))
-    return out, codes, status
+    return _span_conv(lib().qe_quantconv2d_grouped, xq, wq, bias, sh, (int(groups),), relu, rq, out, codes, status, stream)
 
 
 def maxpool2d_codes(x, n_bits, N, C, H, W, kernel=3, stride=2, padding=1, out=None, stream=None):

@@ -581,170 +581,106 @@ extern "C" int qe_maxpool2d_codes(const uint8_t *x, int32_t N, int32_t C, int32_
     return QE_OK;
 }
 
-// ---- depthwise packed convolutions (qe_conv_dw.hip): every query and the launch read one plan (plan_dw) ----
+// ---- depthwise and grouped packed convolutions (qe_conv_dw.hip, qe_conv_grp.hip) ----
+// A depthwise request is a grouped request with groups == IC == OC, so the two entry families share one request check and
+// one run path.  A family supplies what differs: its plan (every query and the launch read one plan: plan_dw / plan_grp),
+// its launcher and which of the two entries it is.  The depthwise entries carry no groups argument: groups == 0 stands for it.
 namespace qe {
-static DwRequest dw_request(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq, const float *out,
-                            const uint8_t *codes, bool has_out)
-{
-    return DwRequest{shape, x->n_bits, x->sign, w->n_bits, w->sign, rq ? rq->n_bits : 0, has_out, reinterpret_cast<uintptr_t>(out),
-                     reinterpret_cast<uintptr_t>(codes)};
-}
+struct DwFamily {
+    static constexpr bool depthwise = true;
+    static DwPlan plan(const qe_conv_shape *shape, int, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq, const float *out,
+                       const uint8_t *codes, bool has_out)
+    {
+        return plan_dw(DwRequest{shape, x->n_bits, x->sign, w->n_bits, w->sign, rq ? rq->n_bits : 0, has_out,
+                                 reinterpret_cast<uintptr_t>(out), reinterpret_cast<uintptr_t>(codes)});
+    }
+    static int launch(const DwPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *sh, int, int relu,
+                      float *out, const qe_requant *rq, uint8_t *codes, int32_t *status, hipStream_t s)
+    {
+        return launch_dw(p, x, w, bias, sh, relu, out, rq, codes, status, s);
+    }
+};
+struct GrpFamily {
+    static constexpr bool depthwise = false;
+    static GrpPlan plan(const qe_conv_shape *shape, int groups, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq,
+                        const float *out, const uint8_t *codes, bool has_out)
+    {
+        return plan_grp(GrpRequest{shape, groups, x->n_bits, x->sign, x->n_param, w->n_bits, w->sign, rq ? rq->n_bits : 0, has_out,
+                                   reinterpret_cast<uintptr_t>(out), reinterpret_cast<uintptr_t>(codes)});
+    }
+    static constexpr auto launch = &launch_grp;
+};
+static_assert((int)DW_NONE == (int)GRP_NONE && (int)DW_PLAIN == (int)GRP_PLAIN, "the queries read both plans' kernel numbers alike");
 
-// shape, operand formats and scale counts of a depthwise request (pointers are not looked at)
-static int check_dw_request(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq)
+// shape, groups, operand formats and scale counts of a request (pointers are not looked at).  The order decides which code
+// wins: on the depthwise entry OC != IC is refused before the scale counts are looked at; on the grouped entry the groups the
+// dense and the depthwise entry points own (they are not forwarded) are refused after them.
+static int check_span_request(bool depthwise, const qe_conv_shape *shape, int groups, const qe_qparam *x, const qe_qparam *w,
+                              const qe_requant *rq)
 {
     int rc = check_shape(shape);
     if (rc != QE_OK) return rc;
     if (x == nullptr || w == nullptr) return QE_ERR_ARG;
     if (!(x->n_bits > 0 && x->n_bits <= 8) || !(w->n_bits > 0 && w->n_bits <= 8)) return QE_ERR_NBITS;
     if (rq != nullptr && !(rq->n_bits > 0 && rq->n_bits <= 8)) return QE_ERR_NBITS;
-    if (shape->OC != shape->IC) return QE_ERR_UNSUPPORTED;
-    const int C = shape->IC;
-    if (!(x->n_param == 1 || x->n_param == C) || !(w->n_param == 1 || w->n_param == C)) return QE_ERR_ARG;
-    if (rq != nullptr && !(rq->n_param == 1 || rq->n_param == C)) return QE_ERR_ARG;
+    if (depthwise) {
+        if (shape->OC != shape->IC) return QE_ERR_UNSUPPORTED;
+    } else if (groups < 1 || shape->OC < 1 || shape->IC % groups != 0 || shape->OC % groups != 0) {
+        return QE_ERR_ARG;
+    }
+    if (!(x->n_param == 1 || x->n_param == shape->IC) || !(w->n_param == 1 || w->n_param == shape->OC)) return QE_ERR_ARG;
+    if (rq != nullptr && !(rq->n_param == 1 || rq->n_param == shape->OC)) return QE_ERR_ARG;
+    if (!depthwise && (groups == 1 || (groups == shape->IC && groups == shape->OC))) return QE_ERR_UNSUPPORTED;
     return QE_OK;
 }
 
 struct Span { uintptr_t lo, hi; };
 static Span span_of(const void *p, int64_t bytes) { return Span{reinterpret_cast<uintptr_t>(p), reinterpret_cast<uintptr_t>(p) + (uintptr_t)bytes}; }
 static bool overlaps(const Span &a, const Span &b) { return a.lo != 0 && b.lo != 0 && a.lo < b.hi && b.lo < a.hi; }
-}  // namespace qe
 
-extern "C" int qe_quantconv2d_depthwise_path(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq)
+// 1 = the family's fast kernels, 0 = its plain kernel, -1 = none
+template <class F>
+static int span_conv_path(const qe_conv_shape *shape, int groups, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq)
 {
-    using namespace qe;
-    if (check_dw_request(shape, x, w, rq) != QE_OK) return -1;
-    const DwPlan p = plan_dw(dw_request(shape, x, w, rq, nullptr, nullptr, true));
+    if (check_span_request(F::depthwise, shape, groups, x, w, rq) != QE_OK) return -1;
+    const auto p = F::plan(shape, groups, x, w, rq, nullptr, nullptr, true);
     return p.kernel == DW_NONE ? -1 : p.kernel == DW_PLAIN ? 0 : 1;
 }
 
-extern "C" int qe_quantconv2d_depthwise_plan_info(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq,
-                                                  const float *out, const uint8_t *codes, qe_dwconv_plan *info)
+// the plan of the request as the call with these destinations would read it, into p
+template <class F, class Plan>
+static int span_conv_plan(const qe_conv_shape *shape, int groups, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq,
+                          const float *out, const uint8_t *codes, const void *info, Plan &p)
 {
-    using namespace qe;
     if (info == nullptr) return QE_ERR_ARG;
-    int rc = check_dw_request(shape, x, w, rq);
+    const int rc = check_span_request(F::depthwise, shape, groups, x, w, rq);
     if (rc != QE_OK) return rc;
     const bool sub8 = rq != nullptr && rq->n_bits < 8;
-    const DwPlan p = plan_dw(dw_request(shape, x, w, rq, out, codes, out != nullptr || rq == nullptr || sub8));
-    if (p.kernel == DW_NONE) return QE_ERR_UNSUPPORTED;
-    *info = qe_dwconv_plan{p.kernel, p.symmetric, p.G, p.TH, p.vec, p.store16, p.codes4, p.two_pass, p.OH, p.OW, p.bands, p.blocks, p.lds};
-    return QE_OK;
+    p = F::plan(shape, groups, x, w, rq, out, codes, out != nullptr || rq == nullptr || sub8);
+    return p.kernel == DW_NONE ? QE_ERR_UNSUPPORTED : QE_OK;
 }
 
-extern "C" int qe_quantconv2d_depthwise(const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *shape,
-                                        int32_t relu, float *out, const qe_requant *rq, uint8_t *codes, int32_t *status,
-                                        qe_stream_t stream)
+template <class F>
+static int run_span_conv(const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *shape, int groups, int relu,
+                         float *out, const qe_requant *rq, uint8_t *codes, int32_t *status, qe_stream_t stream)
 {
-    using namespace qe;
     int rc = check_shape(shape);
     if (rc != QE_OK) return rc;
     if ((rc = check_qparam(x)) != QE_OK) return rc;
     if ((rc = check_qparam(w)) != QE_OK) return rc;
     if (rq != nullptr && (rc = check_requant(rq)) != QE_OK) return rc;
-    if ((rc = check_dw_request(shape, x, w, rq)) != QE_OK) return rc;
+    if ((rc = check_span_request(F::depthwise, shape, groups, x, w, rq)) != QE_OK) return rc;
     if ((out == nullptr && codes == nullptr) || (codes != nullptr) != (rq != nullptr)) return QE_ERR_ARG;
     if ((reinterpret_cast<uintptr_t>(out) & 3) != 0 || (reinterpret_cast<uintptr_t>(status) & 3) != 0) return QE_ERR_ARG;
-    const DwPlan p = plan_dw(dw_request(shape, x, w, rq, out, codes, out != nullptr));
+    const auto p = F::plan(shape, groups, x, w, rq, out, codes, out != nullptr);
     if (p.kernel == DW_NONE) return QE_ERR_UNSUPPORTED;
     if (p.two_pass && out == nullptr) return QE_ERR_UNSUPPORTED;
-    const int C = shape->IC;
-    const int64_t n_in = (int64_t)shape->N * C * shape->H * shape->W, n = (int64_t)shape->N * C * p.OH * p.OW;
-    // an output may overlap neither an operand nor another output
-    const Span outs[3] = {span_of(out, n * 4), span_of(codes, rq ? qe_packed_nbytes(n, rq->n_bits) : 0), span_of(status, 4)};
-    const Span ins[9] = {span_of(x->data, qe_packed_nbytes(n_in, x->n_bits)),
-                         span_of(w->data, qe_packed_nbytes((int64_t)C * shape->KH * shape->KW, w->n_bits)),
-                         span_of(x->scale, 4 * (int64_t)x->n_param), span_of(x->zero, 4 * (int64_t)x->n_param),
-                         span_of(w->scale, 4 * (int64_t)w->n_param), span_of(w->zero, 4 * (int64_t)w->n_param),
-                         span_of(bias, 4 * (int64_t)C), span_of(rq ? rq->scale : nullptr, rq ? 4 * (int64_t)rq->n_param : 0),
-                         span_of(rq ? rq->zero : nullptr, rq ? 4 * (int64_t)rq->n_param : 0)};
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 9; ++j)
-            if (overlaps(outs[i], ins[j])) return QE_ERR_ARG;
-        for (int j = i + 1; j < 3; ++j)
-            if (overlaps(outs[i], outs[j])) return QE_ERR_ARG;
-    }
-    if (n == 0) return QE_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (p.two_pass) {
-        if ((rc = launch_dw(p, x, w, bias, shape, relu, out, nullptr, nullptr, nullptr, s)) != QE_OK) return rc;
-        return qe_quantize_pack(out, n, rq->scale, rq->zero, rq->n_param, (int64_t)p.OH * p.OW, rq->qmin, rq->qmax, rq->n_bits,
-                                rq->sign, codes, status, stream);
-    }
-    return launch_dw(p, x, w, bias, shape, relu, out, rq, codes, status, s);
-}
-
-// ---- grouped packed convolutions (qe_conv_grp.hip): every query and the launch read one plan (plan_grp) ----
-namespace qe {
-static GrpRequest grp_request(const qe_conv_shape *shape, int groups, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq,
-                              const float *out, const uint8_t *codes, bool has_out)
-{
-    return GrpRequest{shape, groups, x->n_bits, x->sign, x->n_param, w->n_bits, w->sign, rq ? rq->n_bits : 0, has_out,
-                      reinterpret_cast<uintptr_t>(out), reinterpret_cast<uintptr_t>(codes)};
-}
-
-// shape, groups, operand formats and scale counts of a grouped request (pointers are not looked at)
-static int check_grp_request(const qe_conv_shape *shape, int groups, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq)
-{
-    int rc = check_shape(shape);
-    if (rc != QE_OK) return rc;
-    if (x == nullptr || w == nullptr) return QE_ERR_ARG;
-    if (!(x->n_bits > 0 && x->n_bits <= 8) || !(w->n_bits > 0 && w->n_bits <= 8)) return QE_ERR_NBITS;
-    if (rq != nullptr && !(rq->n_bits > 0 && rq->n_bits <= 8)) return QE_ERR_NBITS;
-    if (groups < 1 || shape->OC < 1 || shape->IC % groups != 0 || shape->OC % groups != 0) return QE_ERR_ARG;
-    if (!(x->n_param == 1 || x->n_param == shape->IC) || !(w->n_param == 1 || w->n_param == shape->OC)) return QE_ERR_ARG;
-    if (rq != nullptr && !(rq->n_param == 1 || rq->n_param == shape->OC)) return QE_ERR_ARG;
-    // the dense and the depthwise entry points own these; they are not forwarded
-    if (groups == 1 || (groups == shape->IC && groups == shape->OC)) return QE_ERR_UNSUPPORTED;
-    return QE_OK;
-}
-}  // namespace qe
-
-extern "C" int qe_quantconv2d_grouped_path(const qe_conv_shape *shape, int32_t groups, const qe_qparam *x, const qe_qparam *w,
-                                           const qe_requant *rq)
-{
-    using namespace qe;
-    if (check_grp_request(shape, groups, x, w, rq) != QE_OK) return -1;
-    const GrpPlan p = plan_grp(grp_request(shape, groups, x, w, rq, nullptr, nullptr, true));
-    return p.kernel == GRP_NONE ? -1 : p.kernel == GRP_PLAIN ? 0 : 1;
-}
-
-extern "C" int qe_quantconv2d_grouped_plan_info(const qe_conv_shape *shape, int32_t groups, const qe_qparam *x, const qe_qparam *w,
-                                                const qe_requant *rq, const float *out, const uint8_t *codes, qe_grpconv_plan *info)
-{
-    using namespace qe;
-    if (info == nullptr) return QE_ERR_ARG;
-    int rc = check_grp_request(shape, groups, x, w, rq);
-    if (rc != QE_OK) return rc;
-    const bool sub8 = rq != nullptr && rq->n_bits < 8;
-    const GrpPlan p = plan_grp(grp_request(shape, groups, x, w, rq, out, codes, out != nullptr || rq == nullptr || sub8));
-    if (p.kernel == GRP_NONE) return QE_ERR_UNSUPPORTED;
-    *info = qe_grpconv_plan{p.kernel, p.slab, p.TH, p.TW, p.tiles, p.two_pass, p.out16, p.codes16, p.OH, p.OW, p.blocks, p.lds};
-    return QE_OK;
-}
-
-extern "C" int qe_quantconv2d_grouped(const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *shape,
-                                      int32_t groups, int32_t relu, float *out, const qe_requant *rq, uint8_t *codes,
-                                      int32_t *status, qe_stream_t stream)
-{
-    using namespace qe;
-    int rc = check_shape(shape);
-    if (rc != QE_OK) return rc;
-    if ((rc = check_qparam(x)) != QE_OK) return rc;
-    if ((rc = check_qparam(w)) != QE_OK) return rc;
-    if (rq != nullptr && (rc = check_requant(rq)) != QE_OK) return rc;
-    if ((rc = check_grp_request(shape, groups, x, w, rq)) != QE_OK) return rc;
-    if ((out == nullptr && codes == nullptr) || (codes != nullptr) != (rq != nullptr)) return QE_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(out) & 3) != 0 || (reinterpret_cast<uintptr_t>(status) & 3) != 0) return QE_ERR_ARG;
-    const GrpPlan p = plan_grp(grp_request(shape, groups, x, w, rq, out, codes, out != nullptr));
-    if (p.kernel == GRP_NONE) return QE_ERR_UNSUPPORTED;
-    if (p.two_pass && out == nullptr) return QE_ERR_UNSUPPORTED;
-    const int IC = shape->IC, OC = shape->OC;
+    const int IC = shape->IC, OC = shape->OC, icg = F::depthwise ? 1 : IC / groups;
     const int64_t n_in = (int64_t)shape->N * IC * shape->H * shape->W, n = (int64_t)shape->N * OC * p.OH * p.OW;
     // an output may overlap neither an operand nor another output
     const Span outs[3] = {span_of(out, n * 4), span_of(codes, rq ? qe_packed_nbytes(n, rq->n_bits) : 0), span_of(status, 4)};
     const Span ins[9] = {span_of(x->data, qe_packed_nbytes(n_in, x->n_bits)),
-                         span_of(w->data, qe_packed_nbytes((int64_t)OC * (IC / groups) * shape->KH * shape->KW, w->n_bits)),
+                         span_of(w->data, qe_packed_nbytes((int64_t)OC * icg * shape->KH * shape->KW, w->n_bits)),
                          span_of(x->scale, 4 * (int64_t)x->n_param), span_of(x->zero, 4 * (int64_t)x->n_param),
                          span_of(w->scale, 4 * (int64_t)w->n_param), span_of(w->zero, 4 * (int64_t)w->n_param),
                          span_of(bias, 4 * (int64_t)OC), span_of(rq ? rq->scale : nullptr, rq ? 4 * (int64_t)rq->n_param : 0),
@@ -758,9 +694,55 @@ extern "C" int qe_quantconv2d_grouped(const qe_qparam *x, const qe_qparam *w, co
     if (n == 0) return QE_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (p.two_pass) {
-        if ((rc = launch_grp(p, x, w, bias, shape, groups, relu, out, nullptr, nullptr, nullptr, s)) != QE_OK) return rc;
+        if ((rc = F::launch(p, x, w, bias, shape, groups, relu, out, nullptr, nullptr, nullptr, s)) != QE_OK) return rc;
         return qe_quantize_pack(out, n, rq->scale, rq->zero, rq->n_param, (int64_t)p.OH * p.OW, rq->qmin, rq->qmax, rq->n_bits,
                                 rq->sign, codes, status, stream);
     }
-    return launch_grp(p, x, w, bias, shape, groups, relu, out, rq, codes, status, s);
+    return F::launch(p, x, w, bias, shape, groups, relu, out, rq, codes, status, s);
+}
+}  // namespace qe
+
+extern "C" int qe_quantconv2d_depthwise_path(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq)
+{
+    return qe::span_conv_path<qe::DwFamily>(shape, 0, x, w, rq);
+}
+
+extern "C" int qe_quantconv2d_depthwise_plan_info(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq,
+                                                  const float *out, const uint8_t *codes, qe_dwconv_plan *info)
+{
+    qe::DwPlan p;
+    const int rc = qe::span_conv_plan<qe::DwFamily>(shape, 0, x, w, rq, out, codes, info, p);
+    if (rc != QE_OK) return rc;
+    *info = qe_dwconv_plan{p.kernel, p.symmetric, p.G, p.TH, p.vec, p.store16, p.codes4, p.two_pass, p.OH, p.OW, p.bands, p.blocks, p.lds};
+    return QE_OK;
+}
+
+extern "C" int qe_quantconv2d_depthwise(const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *shape,
+                                        int32_t relu, float *out, const qe_requant *rq, uint8_t *codes, int32_t *status,
+                                        qe_stream_t stream)
+{
+    return qe::run_span_conv<qe::DwFamily>(x, w, bias, shape, 0, relu, out, rq, codes, status, stream);
+}
+
+extern "C" int qe_quantconv2d_grouped_path(const qe_conv_shape *shape, int32_t groups, const qe_qparam *x, const qe_qparam *w,
+                                           const qe_requant *rq)
+{
+    return qe::span_conv_path<qe::GrpFamily>(shape, groups, x, w, rq);
+}
+
+extern "C" int qe_quantconv2d_grouped_plan_info(const qe_conv_shape *shape, int32_t groups, const qe_qparam *x, const qe_qparam *w,
+                                                const qe_requant *rq, const float *out, const uint8_t *codes, qe_grpconv_plan *info)
+{
+    qe::GrpPlan p;
+    const int rc = qe::span_conv_plan<qe::GrpFamily>(shape, groups, x, w, rq, out, codes, info, p);
+    if (rc != QE_OK) return rc;
+    *info = qe_grpconv_plan{p.kernel, p.slab, p.TH, p.TW, p.tiles, p.two_pass, p.out16, p.codes16, p.OH, p.OW, p.blocks, p.lds};
+    return QE_OK;
+}
+
+extern "C" int qe_quantconv2d_grouped(const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *shape,
+                                      int32_t groups, int32_t relu, float *out, const qe_requant *rq, uint8_t *codes,
+                                      int32_t *status, qe_stream_t stream)
+{
+    return qe::run_span_conv<qe::GrpFamily>(x, w, bias, shape, groups, relu, out, rq, codes, status, stream);
 }

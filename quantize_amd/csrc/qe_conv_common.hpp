@@ -87,6 +87,14 @@ inline RqArgs make_rq_args(const RequantHost *rq)
     return a;
 }
 
+// the same from the C ABI's operand: the 8-bit codes of rq into `codes`; rq or codes NULL: no codes
+inline RqArgs make_rq_args(const qe_requant *rq, uint8_t *codes, int32_t *status)
+{
+    if (rq == nullptr || codes == nullptr) return make_rq_args(nullptr);
+    const RequantHost rh{codes, rq->scale, rq->zero, rq->n_param, rq->qmin, rq->qmax, rq->n_bits, rq->sign, status};
+    return make_rq_args(&rh);
+}
+
 // y -> stored 8-bit code with the arithmetic of the fused quantise+pack kernel (qe_tpack.hip tp_quantize + tp_code):
 //   r = rint(y / scale - zero) ; clamp to [qmin, qmax] ; code = (int(r) + offset) & 0xff ; flag when r is NaN or outside the
 // code range.  An IEEE division per output element (~10 VALU instructions) made the fused epilogue SLOWER than storing fp32

@@ -25,50 +25,20 @@
 // plane with zw == 0), and B, n and the constants from a 16-entry table per plane (top / bottom / left / right tap out of
 // bounds) that the workgroup computes in LDS: there are no prepared tables.  With integer zeros everything is exact integers,
 // and non-integer zeros only add terms of the size of |dz| * sum, so nothing cancels at the size of the uncentred sums.
+// The zero split, the float half, the border classes, the ReLU and the bodies of the 16-byte chunk copies are the grouped
+// kernels' too: qe_conv_span.hpp.
 #include "qe_conv_dw.hpp"
-#include "qe_conv_common.hpp"
+#include "qe_conv_span.hpp"
 
 namespace qe {
 
-struct DwArgs {
-    const uint8_t *x, *w;
-    const float *xs, *xz, *ws, *wz, *bias;
-    float *out;
-    RqArgs rq;                 // rq.out: the 8-bit codes (NULL: none)
-    int x_pt, w_pt, rq_pt;     // per tensor
-    int x_bits, x_sign, w_bits, w_sign;
-    int N, C, H, W, OH, OW, KH, KW, stride, pad, relu;
+struct DwArgs : SpanOperands {
+    int C, H, W, OH, OW, KH, KW, stride, pad, relu;
     int G, TH, bands, ncg;
     unsigned m_ncg, m_oh;
     int in_off, codes_off, out_off;
     int64_t NP;                // planes: N * C
 };
-
-// zero point -> integer part (less `shift`) and remainder; a zero that is NaN or beyond +-1024 keeps its value in the remainder
-__device__ __forceinline__ void dw_split_zero(float z, int shift, int &zi, float &dz)
-{
-    if (fabsf(z) <= 1024.0f) {
-        const float r = rintf(z);
-        zi = (int)r - shift;
-        dz = z - r;
-    } else {
-        zi = -shift;
-        dz = z;
-    }
-}
-
-__device__ __forceinline__ float dw_relu(float v) { return (v > 0.0f || v != v) ? v : 0.0f; }   // torch.relu: NaN passes
-
-__device__ __forceinline__ RqConst dw_rq_setup(const RqArgs &a, int idx)
-{
-    RqArgs t = a;
-    t.scale = a.scale + idx;
-    t.zero = a.zero + idx;
-    return rq_setup(t);
-}
-
-// the float half of the sum, shared by the two kernels: B = sum (qw - zwi), n taps
-__device__ __forceinline__ float dw_cf(int n, int B, float dzx, float dzw) { return fmaf((float)n * dzx, dzw, -dzx * (float)B); }
 
 struct DwPlaneTab {
     int w[3];            // weight rows as signed bytes (w0, w1, w2, 0)
@@ -126,24 +96,22 @@ __global__ __launch_bounds__(DW_THREADS) void dw_fast_kernel(const DwArgs a)
         }
         int zxi, zwi;
         float dzx, dzw;
-        dw_split_zero(a.xz[a.x_pt ? 0 : c], a.x_sign ? 0 : 128, zxi, dzx);
-        dw_split_zero(a.wz[a.w_pt ? 0 : c], a.w_sign ? 0 : 128, zwi, dzw);
+        span_split_zero(a.xz[a.x_pt ? 0 : c], a.x_sign ? 0 : 128, zxi, dzx);
+        span_split_zero(a.wz[a.w_pt ? 0 : c], a.w_sign ? 0 : 128, zwi, dzw);
         T.zxi = zxi; T.zwi = zwi; T.ndzw = -dzw;
         T.need_box = (zwi != 0 || dzw != 0.0f) ? 1 : 0;
         T.alpha = a.xs[a.x_pt ? 0 : c] * a.ws[a.w_pt ? 0 : c];
         T.bias = a.bias != nullptr ? a.bias[c] : 0.0f;
-        if constexpr (HAS_CODES) T.rq = dw_rq_setup(a.rq, a.rq_pt ? 0 : c);
+        if constexpr (HAS_CODES) T.rq = span_rq_setup(a.rq, a.rq_pt ? 0 : c);
         for (int cls = 0; cls < 16; ++cls) {
             int n = 0, sw = 0;
             for (int r = 0; r < 3; ++r)
-                for (int k = 0; k < 3; ++k) {
-                    const bool off = (r == 0 && (cls & 1)) || (r == 2 && (cls & 2)) || (k == 0 && (cls & 4)) || (k == 2 && (cls & 8));
-                    if (!off) { ++n; sw += wv[r][k]; }
-                }
+                for (int k = 0; k < 3; ++k)
+                    if (!span_tap_off(cls, r, k)) { ++n; sw += wv[r][k]; }
             const int B = sw - n * zwi;
             T.cI[cls] = -zxi * B;                  // sum a b = S - zwi Bx - zxi (Sw - n zwi)
             T.nzx[cls] = n * zxi;
-            T.cF[cls] = dw_cf(n, B, dzx, dzw);
+            T.cF[cls] = span_cf(n, B, dzx, dzw);
         }
     }
 
@@ -154,15 +122,7 @@ __global__ __launch_bounds__(DW_THREADS) void dw_fast_kernel(const DwArgs a)
         const int chunks = (lead + in_len + 15) >> 4;
         for (int i = tid; i < chunks; i += DW_THREADS) {
             const uint8_t *src = A0 + 16 * i;
-            uint4 v;
-            if (src >= x_lo && src + 16 <= x_hi) {
-                v = *reinterpret_cast<const uint4 *>(src);
-            } else {
-                unsigned d[4] = {0, 0, 0, 0};
-                for (int b = 0; b < 16; ++b)
-                    if (src + b >= x_lo && src + b < x_hi) d[b >> 2] |= (unsigned)src[b] << (8 * (b & 3));
-                v = make_uint4(d[0], d[1], d[2], d[3]);
-            }
+            uint4 v = span_load16(src, x_lo, x_hi);
             v.x ^= 0x80808080u; v.y ^= 0x80808080u; v.z ^= 0x80808080u; v.w ^= 0x80808080u;
             *reinterpret_cast<uint4 *>(dw_lds + a.in_off + 16 * i) = v;
         }
@@ -190,8 +150,8 @@ __global__ __launch_bounds__(DW_THREADS) void dw_fast_kernel(const DwArgs a)
         const DwPlaneTab &T = tab[gi];
         const int oh = oh0 + r, ow0 = cg * DW_VEC;
         const int ih0 = oh * S - 1, col0 = ow0 * S - 1;
-        const bool top = ih0 < 0, bot = ih0 + 2 >= a.H;
-        const int rb = (top ? 1 : 0) | (bot ? 2 : 0);
+        const int rb = span_row_cls(oh, S, a.H);
+        const bool top = rb & 1, bot = rb & 2;
         const int mid = in_base + gi * HW + (ih0 + 1 - ih_lo) * a.W + col0;
         // byte masks: column -1 (byte 0 of the first unit of a row) and column W (byte ir)
         const int ir = a.W - col0;
@@ -239,7 +199,7 @@ __global__ __launch_bounds__(DW_THREADS) void dw_fast_kernel(const DwArgs a)
         for (int j = 0; j < DW_VEC; ++j) {
             const int ow = ow0 + j;
             if (ow >= a.OW) break;
-            const int cls = rb | (ow == 0 ? 4 : 0) | (ow * S + 1 >= a.W ? 8 : 0);
+            const int cls = span_out_cls(rb, ow, S, a.W);
             float f;
             if (box) {
                 f = (float)(acc[j] - T.zwi * bx[j] + T.cI[cls]) + T.cF[cls];
@@ -248,7 +208,7 @@ __global__ __launch_bounds__(DW_THREADS) void dw_fast_kernel(const DwArgs a)
                 f = (float)(acc[j] + T.cI[cls]) + T.cF[cls];
             }
             float y = fmaf(T.alpha, f, T.bias);
-            if (a.relu) y = dw_relu(y);
+            if (a.relu) y = span_relu(y);
             if constexpr (HAS_OUT) *reinterpret_cast<float *>(lout + 4 * (orow + j)) = y;
             if constexpr (HAS_CODES) lcodes[orow + j] = (uint8_t)(unsigned)rq_value(T.rq, y, bad);
         }
@@ -264,20 +224,7 @@ __global__ __launch_bounds__(DW_THREADS) void dw_fast_kernel(const DwArgs a)
         for (int i = tid; i < chunks; i += DW_THREADS) {
             uint8_t *dst = A0 + 16 * i;
             const uint4 v = *reinterpret_cast<const uint4 *>(dw_lds + a.codes_off + 16 * i);
-            if (dst >= lo && dst + 16 <= hi) {
-                *reinterpret_cast<uint4 *>(dst) = v;
-            } else {
-                const unsigned d[4] = {v.x, v.y, v.z, v.w};
-                for (int q = 0; q < 4; ++q) {
-                    uint8_t *dq = dst + 4 * q;
-                    if (dq >= lo && dq + 4 <= hi) {
-                        *reinterpret_cast<unsigned *>(dq) = d[q];
-                    } else {
-                        for (int b = 0; b < 4; ++b)
-                            if (dq + b >= lo && dq + b < hi) dq[b] = (uint8_t)(d[q] >> (8 * b));
-                    }
-                }
-            }
+            span_store16_bytes(dst, v, lo, hi);
         }
     }
     if constexpr (HAS_OUT) {
@@ -287,13 +234,7 @@ __global__ __launch_bounds__(DW_THREADS) void dw_fast_kernel(const DwArgs a)
         for (int i = tid; i < chunks; i += DW_THREADS) {
             uint8_t *dst = A0 + 16 * i;
             const uint4 v = *reinterpret_cast<const uint4 *>(dw_lds + a.out_off + 16 * i);
-            if (dst >= lo && dst + 16 <= hi) {
-                *reinterpret_cast<uint4 *>(dst) = v;
-            } else {
-                const unsigned d[4] = {v.x, v.y, v.z, v.w};
-                for (int q = 0; q < 4; ++q)
-                    if (dst + 4 * q >= lo && dst + 4 * q + 4 <= hi) *reinterpret_cast<unsigned *>(dst + 4 * q) = d[q];
-            }
+            span_store16_words(dst, v, lo, hi);
         }
     }
 }
@@ -311,8 +252,8 @@ __global__ __launch_bounds__(DW_THREADS) void dw_plain_kernel(const DwArgs a)
         const int c = (int)(p % a.C);
         int zxi, zwi;
         float dzx, dzw;
-        dw_split_zero(a.xz[a.x_pt ? 0 : c], 0, zxi, dzx);
-        dw_split_zero(a.wz[a.w_pt ? 0 : c], 0, zwi, dzw);
+        span_split_zero(a.xz[a.x_pt ? 0 : c], 0, zxi, dzx);
+        span_split_zero(a.wz[a.w_pt ? 0 : c], 0, zwi, dzw);
         const int64_t xb = p * a.H * a.W, wb = (int64_t)c * a.KH * a.KW;
         int I = 0, A = 0, B = 0, n = 0;
         for (int kh = 0; kh < a.KH; ++kh) {
@@ -326,14 +267,14 @@ __global__ __launch_bounds__(DW_THREADS) void dw_plain_kernel(const DwArgs a)
                 I += qa * qb; A += qa; B += qb; ++n;
             }
         }
-        float f = (float)I + dw_cf(n, B, dzx, dzw);
+        float f = (float)I + span_cf(n, B, dzx, dzw);
         if (zwi != 0 || dzw != 0.0f) f = fmaf(-dzw, (float)A, f);
         const float alpha = a.xs[a.x_pt ? 0 : c] * a.ws[a.w_pt ? 0 : c];
         float y = fmaf(alpha, f, a.bias != nullptr ? a.bias[c] : 0.0f);
-        if (a.relu) y = dw_relu(y);
+        if (a.relu) y = span_relu(y);
         if (a.out != nullptr) a.out[idx] = y;
         if (a.rq.out != nullptr) {
-            const RqConst rc = dw_rq_setup(a.rq, a.rq_pt ? 0 : c);
+            const RqConst rc = span_rq_setup(a.rq, a.rq_pt ? 0 : c);
             a.rq.out[idx] = (uint8_t)(unsigned)rq_value(rc, y, bad);
         }
     }
@@ -341,7 +282,6 @@ __global__ __launch_bounds__(DW_THREADS) void dw_plain_kernel(const DwArgs a)
 }
 
 // ---- host: the plan ---------------------------------------------------------------------------------------------------
-static int round16(int v) { return (v + 15) & ~15; }
 static unsigned dw_magic(int d) { return (unsigned)((1ull << 31) / (unsigned)d) + 1u; }
 
 DwPlan plan_dw(const DwRequest &r)
@@ -406,38 +346,27 @@ DwPlan plan_dw(const DwRequest &r)
     return f;
 }
 
+// the instances by number: the plain kernel, then the fast kernel as plan_dw numbers it (stride, then out | codes | both)
+template <int S, bool HAS_OUT, bool HAS_CODES>
+constexpr SpanLaunch<DwArgs> dw_fast = &launch_instance<&dw_fast_kernel<S, HAS_OUT, HAS_CODES>, DwArgs>;
+static constexpr SpanLaunch<DwArgs> kDwInstances[] = {
+    &launch_instance<&dw_plain_kernel, DwArgs>,
+    dw_fast<1, true, false>, dw_fast<1, false, true>, dw_fast<1, true, true>,
+    dw_fast<2, true, false>, dw_fast<2, false, true>, dw_fast<2, true, true>};
+static_assert(sizeof(kDwInstances) / sizeof(kDwInstances[0]) == DW_KERNELS, "one launcher per instance number");
+
 int launch_dw(const DwPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *sh, int relu,
               float *out, const qe_requant *rq, uint8_t *codes, int32_t *status, hipStream_t s)
 {
+    if (p.kernel < 0 || p.kernel >= DW_KERNELS) return QE_ERR_UNSUPPORTED;
     DwArgs a;
-    a.x = x->data; a.w = w->data;
-    a.xs = x->scale; a.xz = x->zero; a.ws = w->scale; a.wz = w->zero; a.bias = bias;
-    a.out = out;
-    RequantHost rh{codes, nullptr, nullptr, 1, 0.0f, 0.0f, 8, 0, status};
-    if (rq != nullptr && codes != nullptr) {
-        rh.scale = rq->scale; rh.zero = rq->zero; rh.n_param = rq->n_param; rh.qmin = rq->qmin; rh.qmax = rq->qmax;
-        rh.n_bits = rq->n_bits; rh.sign = rq->sign;
-    }
-    a.rq = make_rq_args(rq != nullptr && codes != nullptr ? &rh : nullptr);
-    a.x_pt = x->n_param == 1; a.w_pt = w->n_param == 1; a.rq_pt = rq == nullptr || rq->n_param == 1;
-    a.x_bits = x->n_bits; a.x_sign = x->sign; a.w_bits = w->n_bits; a.w_sign = w->sign;
-    a.N = sh->N; a.C = sh->IC; a.H = sh->H; a.W = sh->W; a.OH = p.OH; a.OW = p.OW; a.KH = sh->KH; a.KW = sh->KW;
+    static_cast<SpanOperands &>(a) = span_operands(x, w, bias, sh->N, out, rq, codes, status);
+    a.C = sh->IC; a.H = sh->H; a.W = sh->W; a.OH = p.OH; a.OW = p.OW; a.KH = sh->KH; a.KW = sh->KW;
     a.stride = sh->stride; a.pad = sh->padding; a.relu = relu ? 1 : 0;
     a.G = p.G; a.TH = p.TH; a.bands = p.bands; a.ncg = p.ncg; a.m_ncg = p.m_ncg; a.m_oh = p.m_oh;
     a.in_off = p.in_off; a.codes_off = p.codes_off; a.out_off = p.out_off;
     a.NP = (int64_t)sh->N * sh->IC;
-    const dim3 grid((unsigned)p.blocks), block(DW_THREADS);
-    const size_t lds = (size_t)p.lds;
-    switch (p.kernel) {
-        case DW_PLAIN: hipLaunchKernelGGL(dw_plain_kernel, grid, block, 0, s, a); break;
-        case 1: hipLaunchKernelGGL((dw_fast_kernel<1, true, false>), grid, block, lds, s, a); break;
-        case 2: hipLaunchKernelGGL((dw_fast_kernel<1, false, true>), grid, block, lds, s, a); break;
-        case 3: hipLaunchKernelGGL((dw_fast_kernel<1, true, true>), grid, block, lds, s, a); break;
-        case 4: hipLaunchKernelGGL((dw_fast_kernel<2, true, false>), grid, block, lds, s, a); break;
-        case 5: hipLaunchKernelGGL((dw_fast_kernel<2, false, true>), grid, block, lds, s, a); break;
-        case 6: hipLaunchKernelGGL((dw_fast_kernel<2, true, true>), grid, block, lds, s, a); break;
-        default: return QE_ERR_UNSUPPORTED;
-    }
+    kDwInstances[p.kernel]((unsigned)p.blocks, DW_THREADS, (size_t)p.lds, 0, s, a);
     QE_LAUNCH_CHECK();
     return QE_OK;
 }

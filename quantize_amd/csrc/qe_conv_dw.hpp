@@ -14,7 +14,8 @@ struct DwRequest {
     uintptr_t out, codes;      // 0 reads as aligned
 };
 
-enum DwKernel { DW_NONE = -1, DW_PLAIN = 0, DW_FAST_FIRST = 1 };   // fast: 1 + 3 * (stride - 1) + (0 out, 1 codes, 2 out + codes)
+// fast: 1 + 3 * (stride - 1) + (0 out, 1 codes, 2 out + codes)
+enum DwKernel { DW_NONE = -1, DW_PLAIN = 0, DW_FAST_FIRST = 1, DW_KERNELS = 7 };
 
 struct DwPlan {
     int kernel = DW_NONE;

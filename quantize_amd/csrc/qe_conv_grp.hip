@@ -38,55 +38,22 @@
 // The fast kernel gets I and A from S = sum qx' qw' (MFMA) and the group's box sum Bx = sum qx' (MFMA against ones), and B, n
 // and the constants from a 16-entry table per output channel (top / bottom / left / right taps out of bounds) that the
 // workgroup computes from the weights in LDS.
+// The zero split, the float half, the border classes, the ReLU and the bodies of the 16-byte chunk copies are the depthwise
+// kernels' too: qe_conv_span.hpp.
 #include "qe_conv_grp.hpp"
-#include "qe_conv_common.hpp"
+#include "qe_conv_span.hpp"
 
 #include <algorithm>
 
 namespace qe {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
-
-struct GrpArgs {
-    const uint8_t *x, *w;
-    const float *xs, *xz, *ws, *wz, *bias;
-    float *out;
-    RqArgs rq;                 // rq.out: the 8-bit codes (NULL: none)
-    int x_pt, w_pt, rq_pt;     // per tensor
-    int x_bits, x_sign, w_bits, w_sign;
-    int N, IC, OC, H, W, OH, OW, KH, KW, stride, pad, relu;
+struct GrpArgs : SpanOperands {
+    int IC, OC, H, W, OH, OW, KH, KW, stride, pad, relu;
     int groups, icg, ocg;
     int TH, bands, nslabs, wps, ntiles;   // wps: workgroups of a slab; ntiles: N * bands, the tiles they share
     int in_rows, raw_stride, codes_stride, out_stride;
     int tile_off, stage_off, ostage_off;
 };
-
-// zero point -> integer part (less `shift`) and remainder; a zero that is NaN or beyond +-1024 keeps its value in the remainder
-__device__ __forceinline__ void grp_split_zero(float z, int shift, int &zi, float &dz)
-{
-    if (fabsf(z) <= 1024.0f) {
-        const float r = rintf(z);
-        zi = (int)r - shift;
-        dz = z - r;
-    } else {
-        zi = -shift;
-        dz = z;
-    }
-}
-
-__device__ __forceinline__ float grp_relu(float v) { return (v > 0.0f || v != v) ? v : 0.0f; }   // torch.relu: NaN passes
-
-__device__ __forceinline__ RqConst grp_rq_setup(const RqArgs &a, int idx)
-{
-    RqArgs t = a;
-    t.scale = a.scale + idx;
-    t.zero = a.zero + idx;
-    return rq_setup(t);
-}
-
-// the float half of the sum, shared by the two kernels: B = sum (qw - zwi), n products
-__device__ __forceinline__ float grp_cf(int n, int B, float dzx, float dzw) { return fmaf((float)n * dzx, dzw, -dzx * (float)B); }
 
 struct GrpCls { int cI; float cF; };
 struct GrpChanTab {
@@ -116,7 +83,7 @@ __global__ __launch_bounds__(GRP_THREADS) void grp_fast_kernel(const GrpArgs a)
 
     int zxi;
     float dzx;
-    grp_split_zero(a.xz[0], a.x_sign ? 0 : 128, zxi, dzx);
+    span_split_zero(a.xz[0], a.x_sign ? 0 : 128, zxi, dzx);
 
     // ---- the wave's weight fragments: lane (row r = output channel in slab, half h) holds K = 16 h + j of each tap ---------------
     v4i wf[9], ones;
@@ -155,24 +122,22 @@ __global__ __launch_bounds__(GRP_THREADS) void grp_fast_kernel(const GrpArgs a)
                 const int oc = c0 + r;
                 int zwi;
                 float dzw;
-                grp_split_zero(a.wz[a.w_pt ? 0 : oc], a.w_sign ? 0 : 128, zwi, dzw);
+                span_split_zero(a.wz[a.w_pt ? 0 : oc], a.w_sign ? 0 : 128, zwi, dzw);
                 T.zwi = zwi; T.ndzw = -dzw;
                 T.flags = ((zwi != 0 || dzw != 0.0f) ? 1 : 0) | (dzw != 0.0f ? 2 : 0);
                 T.alpha = a.xs[0] * a.ws[a.w_pt ? 0 : oc];
                 T.bias = a.bias != nullptr ? a.bias[oc] : 0.0f;
-                if constexpr (HAS_CODES) T.rq = grp_rq_setup(a.rq, a.rq_pt ? 0 : oc);
+                if constexpr (HAS_CODES) T.rq = span_rq_setup(a.rq, a.rq_pt ? 0 : oc);
                 for (int cls = 0; cls < 16; ++cls) {
                     int taps = 0, sw = 0;
 #pragma unroll
                     for (int t = 0; t < 9; ++t) {
-                        const int kh = t / 3, kw = t % 3;
-                        const bool off = (kh == 0 && (cls & 1)) || (kh == 2 && (cls & 2)) || (kw == 0 && (cls & 4)) || (kw == 2 && (cls & 8));
-                        if (!off) { ++taps; sw += swt[t]; }
+                        if (!span_tap_off(cls, t / 3, t % 3)) { ++taps; sw += swt[t]; }
                     }
                     const int nn = taps * CG;
                     const int B = sw - nn * zwi;
                     T.c[cls].cI = -zxi * B;                // sum a b = S - zwi Bx - zxi (Sw - n zwi)
-                    T.c[cls].cF = grp_cf(nn, B, dzx, dzw);
+                    T.c[cls].cF = span_cf(nn, B, dzx, dzw);
                     T.nzx[cls] = nn * zxi;
                 }
             } else {
@@ -232,16 +197,7 @@ __global__ __launch_bounds__(GRP_THREADS) void grp_fast_kernel(const GrpArgs a)
                 const int lead = (int)(reinterpret_cast<uintptr_t>(g) & 15);
                 if (i >= ((lead + in_len + 15) >> 4)) continue;
                 const uint8_t *src = g - lead + 16 * i;
-                uint4 v;
-                if (src >= x_lo && src + 16 <= x_hi) {
-                    v = *reinterpret_cast<const uint4 *>(src);
-                } else {
-                    unsigned d[4] = {0, 0, 0, 0};
-                    for (int b = 0; b < 16; ++b)
-                        if (src + b >= x_lo && src + b < x_hi) d[b >> 2] |= (unsigned)src[b] << (8 * (b & 3));
-                    v = make_uint4(d[0], d[1], d[2], d[3]);
-                }
-                *reinterpret_cast<uint4 *>(raw + ch * a.raw_stride + 16 * i) = v;
+                *reinterpret_cast<uint4 *>(raw + ch * a.raw_stride + 16 * i) = span_load16(src, x_lo, x_hi);
             }
         }
         __syncthreads();
@@ -289,7 +245,7 @@ __global__ __launch_bounds__(GRP_THREADS) void grp_fast_kernel(const GrpArgs a)
                 acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(wf[t], bf, acc, 0, 0, 0);
                 if (box) acc2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(ones, bf, acc2, 0, 0, 0);
             }
-            const int oh = oh0 + orow;
+            const int oh = oh0 + orow;                            // span_out_cls, written out: see section 4g-bis
             const int cls = (oh * S - 1 < 0 ? 1 : 0) | (oh * S + 1 >= a.H ? 2 : 0) | (ocol == 0 ? 4 : 0) | (ocol * S + 1 >= a.W ? 8 : 0);
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
@@ -317,7 +273,7 @@ __global__ __launch_bounds__(GRP_THREADS) void grp_fast_kernel(const GrpArgs a)
             uint8_t *cp = cstage + ech * a.codes_stride + (HAS_CODES ? (int)((gcodes_addr + (uintptr_t)ech * (uintptr_t)OHW) & 15) : 0);
             for (int px = esub; px < npx; px += 8) {
                 float y = fmaf(e_alpha, fp[px], e_bias);
-                if (a.relu) y = grp_relu(y);
+                if (a.relu) y = span_relu(y);
                 if constexpr (HAS_OUT) fp[px] = y;
                 if constexpr (HAS_CODES) cp[px] = (uint8_t)(unsigned)rq_value(e_rq, y, bad);
             }
@@ -336,7 +292,7 @@ __global__ __launch_bounds__(GRP_THREADS) void grp_fast_kernel(const GrpArgs a)
                 const uint8_t *lo = g, *hi = g + npx;
                 uint8_t *dst = g - lead + 16 * i;
                 const uint4 v = *reinterpret_cast<const uint4 *>(cstage + ch * a.codes_stride + 16 * i);
-                if (dst >= lo && dst + 16 <= hi) {
+                if (dst >= lo && dst + 16 <= hi) {             // span_store16_bytes, written out: see section 4g-bis
                     *reinterpret_cast<uint4 *>(dst) = v;
                 } else {
                     const unsigned d[4] = {v.x, v.y, v.z, v.w};
@@ -363,13 +319,7 @@ __global__ __launch_bounds__(GRP_THREADS) void grp_fast_kernel(const GrpArgs a)
                 const uint8_t *lo = g, *hi = g + 4 * (int64_t)npx;
                 uint8_t *dst = g - lead + 16 * i;
                 const uint4 v = *reinterpret_cast<const uint4 *>(fstage + ch * a.out_stride + 16 * i);
-                if (dst >= lo && dst + 16 <= hi) {
-                    *reinterpret_cast<uint4 *>(dst) = v;
-                } else {
-                    const unsigned d[4] = {v.x, v.y, v.z, v.w};
-                    for (int q = 0; q < 4; ++q)
-                        if (dst + 4 * q >= lo && dst + 4 * q + 4 <= hi) *reinterpret_cast<unsigned *>(dst + 4 * q) = d[q];
-                }
+                span_store16_words(dst, v, lo, hi);
             }
         }
         __syncthreads();                                          // the stage is the next tile's raw span
@@ -392,18 +342,18 @@ __global__ __launch_bounds__(GRP_THREADS) void grp_plain_kernel(const GrpArgs a)
         const int ic0 = (oc / a.ocg) * a.icg;
         int zwi;
         float dzw;
-        grp_split_zero(a.wz[a.w_pt ? 0 : oc], 0, zwi, dzw);
+        span_split_zero(a.wz[a.w_pt ? 0 : oc], 0, zwi, dzw);
         const float sw = a.ws[a.w_pt ? 0 : oc];
         const int64_t wb = (int64_t)oc * a.icg * a.KH * a.KW;
         int I = 0, A = 0, B = 0, nn = 0;
         int zxi = 0;
         float dzx = 0.0f;
-        if (a.x_pt) grp_split_zero(a.xz[0], 0, zxi, dzx);
+        if (a.x_pt) span_split_zero(a.xz[0], 0, zxi, dzx);
         float y = a.bias != nullptr ? a.bias[oc] : 0.0f;
         for (int ci = 0; ci < a.icg; ++ci) {
             const int ic = ic0 + ci;
             if (!a.x_pt) {
-                grp_split_zero(a.xz[ic], 0, zxi, dzx);
+                span_split_zero(a.xz[ic], 0, zxi, dzx);
                 I = A = B = nn = 0;
             }
             const int64_t xb = (n * a.IC + ic) * a.H * a.W;
@@ -419,20 +369,20 @@ __global__ __launch_bounds__(GRP_THREADS) void grp_plain_kernel(const GrpArgs a)
                 }
             }
             if (!a.x_pt) {
-                float f = (float)I + grp_cf(nn, B, dzx, dzw);
+                float f = (float)I + span_cf(nn, B, dzx, dzw);
                 if (dzw != 0.0f) f = fmaf(-dzw, (float)A, f);
                 y = fmaf(a.xs[ic] * sw, f, y);
             }
         }
         if (a.x_pt) {
-            float f = (float)I + grp_cf(nn, B, dzx, dzw);
+            float f = (float)I + span_cf(nn, B, dzx, dzw);
             if (dzw != 0.0f) f = fmaf(-dzw, (float)A, f);
             y = fmaf(a.xs[0] * sw, f, y);
         }
-        if (a.relu) y = grp_relu(y);
+        if (a.relu) y = span_relu(y);
         if (a.out != nullptr) a.out[idx] = y;
         if (a.rq.out != nullptr) {
-            const RqConst rc = grp_rq_setup(a.rq, a.rq_pt ? 0 : oc);
+            const RqConst rc = span_rq_setup(a.rq, a.rq_pt ? 0 : oc);
             a.rq.out[idx] = (uint8_t)(unsigned)rq_value(rc, y, bad);
         }
     }
@@ -440,7 +390,6 @@ __global__ __launch_bounds__(GRP_THREADS) void grp_plain_kernel(const GrpArgs a)
 }
 
 // ---- host: the plan ---------------------------------------------------------------------------------------------------
-static int grp_round16(int v) { return (v + 15) & ~15; }
 
 GrpPlan plan_grp(const GrpRequest &r)
 {
@@ -475,10 +424,10 @@ GrpPlan plan_grp(const GrpRequest &r)
         const int in_rows = (TH - 1) * S + 3;
         const int npx = TH * p.OW;
         q.in_rows = in_rows;
-        q.raw_stride = grp_round16(std::min(s.H, in_rows) * s.W + 30);
-        q.codes_stride = k_codes ? grp_round16(npx + 30) : 0;
-        q.out_stride = grp_round16(4 * npx + 27);             // the fp32 stage: always (the first pass leaves f there)
-        q.tile_off = grp_round16(GRP_SLAB * (int)sizeof(GrpChanTab));
+        q.raw_stride = round16(std::min(s.H, in_rows) * s.W + 30);
+        q.codes_stride = k_codes ? round16(npx + 30) : 0;
+        q.out_stride = round16(4 * npx + 27);             // the fp32 stage: always (the first pass leaves f there)
+        q.tile_off = round16(GRP_SLAB * (int)sizeof(GrpChanTab));
         q.stage_off = q.tile_off + in_rows * (s.W + 2) * 32;
         q.ostage_off = q.stage_off + GRP_SLAB * q.codes_stride;
         const int64_t stage = std::max<int64_t>((int64_t)GRP_SLAB * q.raw_stride, (int64_t)GRP_SLAB * (q.codes_stride + q.out_stride));
@@ -504,59 +453,29 @@ GrpPlan plan_grp(const GrpRequest &r)
     return f;
 }
 
-template <int CG>
-static bool launch_grp_fast(int e, const dim3 &grid, size_t lds, hipStream_t s, const GrpArgs &a)
-{
-    const dim3 block(GRP_THREADS);
-    switch (e) {
-        case 0: hipLaunchKernelGGL((grp_fast_kernel<CG, 1, true, false>), grid, block, lds, s, a); return true;
-        case 1: hipLaunchKernelGGL((grp_fast_kernel<CG, 1, false, true>), grid, block, lds, s, a); return true;
-        case 2: hipLaunchKernelGGL((grp_fast_kernel<CG, 1, true, true>), grid, block, lds, s, a); return true;
-        case 3: hipLaunchKernelGGL((grp_fast_kernel<CG, 2, true, false>), grid, block, lds, s, a); return true;
-        case 4: hipLaunchKernelGGL((grp_fast_kernel<CG, 2, false, true>), grid, block, lds, s, a); return true;
-        case 5: hipLaunchKernelGGL((grp_fast_kernel<CG, 2, true, true>), grid, block, lds, s, a); return true;
-        default: return false;
-    }
-}
+// the instances by number: the plain kernel, then the fast family as plan_grp numbers it (Cg, then stride, then out | codes | both)
+template <int CG, int S, bool HAS_OUT, bool HAS_CODES>
+constexpr SpanLaunch<GrpArgs> grp_fast = &launch_instance<&grp_fast_kernel<CG, S, HAS_OUT, HAS_CODES>, GrpArgs>;
+#define GRP_CG(CG) grp_fast<CG, 1, true, false>, grp_fast<CG, 1, false, true>, grp_fast<CG, 1, true, true>, \
+                   grp_fast<CG, 2, true, false>, grp_fast<CG, 2, false, true>, grp_fast<CG, 2, true, true>
+static constexpr SpanLaunch<GrpArgs> kGrpInstances[] = {&launch_instance<&grp_plain_kernel, GrpArgs>, GRP_CG(4), GRP_CG(8), GRP_CG(16),
+                                                        GRP_CG(32)};
+#undef GRP_CG
+static_assert(sizeof(kGrpInstances) / sizeof(kGrpInstances[0]) == GRP_KERNELS, "one launcher per instance number");
 
 int launch_grp(const GrpPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *sh, int groups,
                int relu, float *out, const qe_requant *rq, uint8_t *codes, int32_t *status, hipStream_t s)
 {
+    if (p.kernel < 0 || p.kernel >= GRP_KERNELS) return QE_ERR_UNSUPPORTED;
     GrpArgs a;
-    a.x = x->data; a.w = w->data;
-    a.xs = x->scale; a.xz = x->zero; a.ws = w->scale; a.wz = w->zero; a.bias = bias;
-    a.out = out;
-    RequantHost rh{codes, nullptr, nullptr, 1, 0.0f, 0.0f, 8, 0, status};
-    if (rq != nullptr && codes != nullptr) {
-        rh.scale = rq->scale; rh.zero = rq->zero; rh.n_param = rq->n_param; rh.qmin = rq->qmin; rh.qmax = rq->qmax;
-        rh.n_bits = rq->n_bits; rh.sign = rq->sign;
-    }
-    a.rq = make_rq_args(rq != nullptr && codes != nullptr ? &rh : nullptr);
-    a.x_pt = x->n_param == 1; a.w_pt = w->n_param == 1; a.rq_pt = rq == nullptr || rq->n_param == 1;
-    a.x_bits = x->n_bits; a.x_sign = x->sign; a.w_bits = w->n_bits; a.w_sign = w->sign;
-    a.N = sh->N; a.IC = sh->IC; a.OC = sh->OC; a.H = sh->H; a.W = sh->W; a.OH = p.OH; a.OW = p.OW; a.KH = sh->KH; a.KW = sh->KW;
+    static_cast<SpanOperands &>(a) = span_operands(x, w, bias, sh->N, out, rq, codes, status);
+    a.IC = sh->IC; a.OC = sh->OC; a.H = sh->H; a.W = sh->W; a.OH = p.OH; a.OW = p.OW; a.KH = sh->KH; a.KW = sh->KW;
     a.stride = sh->stride; a.pad = sh->padding; a.relu = relu ? 1 : 0;
     a.groups = groups; a.icg = sh->IC / groups; a.ocg = sh->OC / groups;
     a.TH = p.TH; a.bands = p.tiles; a.nslabs = p.nslabs; a.wps = p.wps; a.ntiles = sh->N * p.tiles;
     a.in_rows = p.in_rows; a.raw_stride = p.raw_stride; a.codes_stride = p.codes_stride; a.out_stride = p.out_stride;
     a.tile_off = p.tile_off; a.stage_off = p.stage_off; a.ostage_off = p.ostage_off;
-    const dim3 grid((unsigned)p.blocks);
-    const size_t lds = (size_t)p.lds;
-    if (p.kernel == GRP_PLAIN) {
-        hipLaunchKernelGGL(grp_plain_kernel, grid, dim3(GRP_THREADS), 0, s, a);
-    } else if (p.kernel >= GRP_FAST_FIRST && p.kernel < GRP_KERNELS) {
-        const int k = p.kernel - GRP_FAST_FIRST, e = k % 6;
-        bool ok = false;
-        switch (k / 6) {
-            case 0: ok = launch_grp_fast<4>(e, grid, lds, s, a); break;
-            case 1: ok = launch_grp_fast<8>(e, grid, lds, s, a); break;
-            case 2: ok = launch_grp_fast<16>(e, grid, lds, s, a); break;
-            case 3: ok = launch_grp_fast<32>(e, grid, lds, s, a); break;
-        }
-        if (!ok) return QE_ERR_UNSUPPORTED;
-    } else {
-        return QE_ERR_UNSUPPORTED;
-    }
+    kGrpInstances[p.kernel]((unsigned)p.blocks, GRP_THREADS, (size_t)p.lds, 0, s, a);
     QE_LAUNCH_CHECK();
     return QE_OK;
 }

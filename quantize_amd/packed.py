@@ -130,7 +130,17 @@ class _PackedBase:
         return ((q + z) * s).contiguous()
 
 
-class PackedConv2d(_PackedBase):
+class _PackedConvBase(_PackedBase):
+    """The geometry the three conv classes share; IC, OC, KH, KW, stride and padding are their constructors'."""
+
+    def out_hw(self, H, W):
+        return ((H + 2 * self.padding - self.KH) // self.stride + 1, (W + 2 * self.padding - self.KW) // self.stride + 1)
+
+    def shape(self, N, H, W):
+        return capi.conv_shape(N, self.IC, H, W, self.OC, self.KH, self.KW, self.stride, self.padding)
+
+
+class PackedConv2d(_PackedConvBase):
     """A packed QuantConv2d's forward on the engine: quantconv2d_forward(x, (weight, w_des, w_scale, w_zero), bias,
     stride, padding, dilation, groups) -- the commented call of quantconv2d.py:204-206 -- with the activation operand
     produced on the device."""
@@ -148,12 +158,6 @@ class PackedConv2d(_PackedBase):
     def to(self, device):
         self._prep = {}
         return super().to(device)
-
-    def out_hw(self, H, W):
-        return ((H + 2 * self.padding - self.KH) // self.stride + 1, (W + 2 * self.padding - self.KW) // self.stride + 1)
-
-    def shape(self, N, H, W):
-        return capi.conv_shape(N, self.IC, H, W, self.OC, self.KH, self.KW, self.stride, self.padding)
 
     def operands(self, codes, N, H, W, n_bits=None, signed=None):
         """(qe_conv_shape, activation operand, weight operand, prepared weight tables) of this conv on `codes` of an
@@ -197,10 +201,45 @@ class PackedConv2d(_PackedBase):
         return out, (des if status is not None else torch.tensor(des, dtype=torch.int32, device=xq.device))
 
 
-class PackedDepthwiseConv2d(_PackedBase):
+class _PackedSpanConv(_PackedConvBase):
+    """The calls the depthwise and the grouped class share.  KIND names the layer in messages; _conv is its entry point."""
+    KIND = None
+
+    def _conv(self, x, w, sh, **kw):
+        raise NotImplementedError
+
+    def __call__(self, x, route="packed"):
+        if route == "float":
+            raise ValueError("route='float': there is no float-input %s kernel; use route='packed'" % self.KIND)
+        if route != "packed":
+            raise ValueError("route must be 'packed'")
+        xq, x_des = self.quantize(x)
+        return self.call_packed(xq, x_des)
+
+    def call_packed(self, xq, x_des, consumer=None, relu=False, status=None):
+        """Activations as (packed stream, des), as PackedConv2d.call_packed.  consumer=None: the fp32 output (after the ReLU
+        when relu).  consumer = the Packed* layer that reads [relu of] this layer's output: the (packed, des) pair of ITS
+        activation quantiser from this layer's own epilogue, bit-identical to consumer.quantize([relu](fp32 output)).
+        Sub-8-bit consumers go through an fp32 tensor inside the call (two planes can share a byte of their stream)."""
+        n_bits, sign, N, C, H, W = _host_des(x_des)
+        if C != self.IC:
+            raise ValueError("codes of %d channels for a %s conv of %d" % (C, self.KIND, self.IC))
+        sh, x, w = self.shape(N, H, W), self.xq(xq, n_bits, sign), self.wq()
+        if consumer is None:
+            return self._conv(x, w, sh, relu=relu)[0]
+        _, codes, flag = self._conv(x, w, sh, relu=relu, rq=consumer.requant(), out="new" if consumer.a_bits < 8 else None,
+                                    status=status)
+        if status is None and int(flag.item()) != 0:
+            raise RuntimeError(OUT_OF_RANGE)
+        des = (consumer.a_bits, int(consumer.a_signed), N, self.OC, *self.out_hw(H, W))
+        return codes, (des if status is not None else torch.tensor(des, dtype=torch.int32, device=xq.device))
+
+
+class PackedDepthwiseConv2d(_PackedSpanConv):
     """A packed depthwise QuantConv2d (groups == in_channels == out_channels; pack() leaves w_des [b, s, C, 1, KH, KW]) on
     qe_quantconv2d_depthwise: codes in, fp32 and / or the consumer's codes out.  The sign convention is the convs':
     (q - zero), so the zeros are negated.  There is no float-input depthwise kernel and nothing runs in its place."""
+    KIND = "depthwise"
 
     def __init__(self, *, stride=1, padding=0, **state):
         super().__init__(**state)
@@ -215,44 +254,16 @@ class PackedDepthwiseConv2d(_PackedBase):
     def from_state_dict(cls, state_dict, prefix="", stride=1, padding=0):
         return cls(stride=stride, padding=padding, **cls._state(state_dict, prefix))
 
-    def out_hw(self, H, W):
-        return ((H + 2 * self.padding - self.KH) // self.stride + 1, (W + 2 * self.padding - self.KW) // self.stride + 1)
-
-    def shape(self, N, H, W):
-        return capi.conv_shape(N, self.C, H, W, self.C, self.KH, self.KW, self.stride, self.padding)
-
-    def __call__(self, x, route="packed"):
-        if route == "float":
-            raise ValueError("route='float': there is no float-input depthwise kernel; use route='packed'")
-        if route != "packed":
-            raise ValueError("route must be 'packed'")
-        xq, x_des = self.quantize(x)
-        return self.call_packed(xq, x_des)
-
-    def call_packed(self, xq, x_des, consumer=None, relu=False, status=None):
-        """Activations as (packed stream, des), as PackedConv2d.call_packed.  consumer=None: the fp32 output (after the ReLU
-        when relu).  consumer = the Packed* layer that reads [relu of] this layer's output: the (packed, des) pair of ITS
-        activation quantiser from this layer's own epilogue, bit-identical to consumer.quantize([relu](fp32 output)).
-        Sub-8-bit consumers go through an fp32 tensor inside the call (two planes can share a byte of their stream)."""
-        n_bits, sign, N, C, H, W = _host_des(x_des)
-        if C != self.C:
-            raise ValueError("codes of %d channels for a depthwise conv of %d" % (C, self.C))
-        sh, x, w = self.shape(N, H, W), self.xq(xq, n_bits, sign), self.wq()
-        if consumer is None:
-            return capi.quantconv2d_depthwise(x, w, self.bias, sh, relu=relu)[0]
-        _, codes, flag = capi.quantconv2d_depthwise(x, w, self.bias, sh, relu=relu, rq=consumer.requant(),
-                                                    out="new" if consumer.a_bits < 8 else None, status=status)
-        if status is None and int(flag.item()) != 0:
-            raise RuntimeError(OUT_OF_RANGE)
-        des = (consumer.a_bits, int(consumer.a_signed), N, self.C, *self.out_hw(H, W))
-        return codes, (des if status is not None else torch.tensor(des, dtype=torch.int32, device=xq.device))
+    def _conv(self, x, w, sh, **kw):
+        return capi.quantconv2d_depthwise(x, w, self.bias, sh, **kw)
 
 
-class PackedGroupedConv2d(_PackedBase):
+class PackedGroupedConv2d(_PackedSpanConv):
     """A packed grouped QuantConv2d (1 < groups < channels; pack() leaves w_des [b, s, OC, IC / groups, KH, KW]) on
     qe_quantconv2d_grouped: codes in, fp32 and / or the consumer's codes out.  w_des does not name the groups, so the layer's
     input channels are given.  The sign convention is the convs': (q - zero), so the zeros are negated.  There is no
     float-input grouped kernel and nothing runs in its place."""
+    KIND = "grouped"
 
     def __init__(self, *, stride=1, padding=0, in_channels, **state):
         super().__init__(**state)
@@ -276,37 +287,8 @@ class PackedGroupedConv2d(_PackedBase):
             raise ValueError("PackedGroupedConv2d.from_state_dict: in_channels is required (w_des does not name the groups)")
         return cls(stride=stride, padding=padding, in_channels=in_channels, **cls._state(state_dict, prefix))
 
-    def out_hw(self, H, W):
-        return ((H + 2 * self.padding - self.KH) // self.stride + 1, (W + 2 * self.padding - self.KW) // self.stride + 1)
-
-    def shape(self, N, H, W):
-        return capi.conv_shape(N, self.IC, H, W, self.OC, self.KH, self.KW, self.stride, self.padding)
-
-    def __call__(self, x, route="packed"):
-        if route == "float":
-            raise ValueError("route='float': there is no float-input grouped kernel; use route='packed'")
-        if route != "packed":
-            raise ValueError("route must be 'packed'")
-        xq, x_des = self.quantize(x)
-        return self.call_packed(xq, x_des)
-
-    def call_packed(self, xq, x_des, consumer=None, relu=False, status=None):
-        """Activations as (packed stream, des), as PackedConv2d.call_packed.  consumer=None: the fp32 output (after the ReLU
-        when relu).  consumer = the Packed* layer that reads [relu of] this layer's output: the (packed, des) pair of ITS
-        activation quantiser from this layer's own epilogue, bit-identical to consumer.quantize([relu](fp32 output)).
-        Sub-8-bit consumers go through an fp32 tensor inside the call (two planes can share a byte of their stream)."""
-        n_bits, sign, N, C, H, W = _host_des(x_des)
-        if C != self.IC:
-            raise ValueError("codes of %d channels for a grouped conv of %d" % (C, self.IC))
-        sh, x, w = self.shape(N, H, W), self.xq(xq, n_bits, sign), self.wq()
-        if consumer is None:
-            return capi.quantconv2d_grouped(x, w, self.bias, sh, self.groups, relu=relu)[0]
-        _, codes, flag = capi.quantconv2d_grouped(x, w, self.bias, sh, self.groups, relu=relu, rq=consumer.requant(),
-                                                  out="new" if consumer.a_bits < 8 else None, status=status)
-        if status is None and int(flag.item()) != 0:
-            raise RuntimeError(OUT_OF_RANGE)
-        des = (consumer.a_bits, int(consumer.a_signed), N, self.OC, *self.out_hw(H, W))
-        return codes, (des if status is not None else torch.tensor(des, dtype=torch.int32, device=xq.device))
+    def _conv(self, x, w, sh, **kw):
+        return capi.quantconv2d_grouped(x, w, self.bias, sh, self.groups, **kw)
 
 
 class PackedLinear(_PackedBase):
