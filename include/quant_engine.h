@@ -189,6 +189,9 @@ int qe_quantconv2d_prepared(const qe_qparam *x, const qe_qparam *w, const float 
  *      0 = two passes inside the call (fp32 y in the workspace, then the quantise+pack kernel).
  * workspace  qe_quantconv2d_requant_workspace_bytes(shape, x, w, rq) bytes, 16-byte aligned.
  * prepared   as qe_quantconv2d_prepared (qe_conv_prepare); status as qe_tpack.
+ *            The flag is a function of the N*OC*OH*OW values alone, whichever kernel runs and whatever form of the
+ *            quantiser it takes: an infinite y clamps to qmin / qmax like any other and raises it only where that clamp
+ *            bound lies outside the code range, a NaN always does, and lanes that compute on tile padding never do.
  * ------------------------------------------------------------------------- */
 typedef struct qe_requant {
     const float *scale;

@@ -1670,11 +1670,15 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv_mfma_flat_kernel(const M
                             pk = __builtin_amdgcn_cvt_pk_u8_f32(r.y, j + 1, pk);
                         }
                     } else {
+                        // NT % 4 == 0: the four slots are real or none is; slots past NT hold what the staging never wrote
+                        const bool real = q0 + 8 * gq + 4 * h < NT;
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
                             float f = (float)acc[t][4 * gq + j] + cst;
                             if (need_sx) f = fmaf(-zwp, (float)sxp[q0 + 8 * gq + 4 * h + j], f);
-                            pk = __builtin_amdgcn_cvt_pk_u8_f32(rq_value(rqc, fmaf(alpha, f, bia), bad), j, pk);
+                            bool b = false;
+                            pk = __builtin_amdgcn_cvt_pk_u8_f32(rq_value(rqc, fmaf(alpha, f, bia), b), j, pk);
+                            bad |= b && real;
                         }
                     }
                     *reinterpret_cast<uint32_t *>(bp + (wm * 32 + col) * NTP + q0 + 8 * gq + 4 * h) = pk;
