@@ -692,6 +692,73 @@ int qe_global_avgpool(const float *x, int64_t n_planes, int32_t P, float *out, q
 int qe_maxpool2d_codes(const uint8_t *x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t kernel, int32_t stride,
                        int32_t padding, uint8_t *out, qe_stream_t stream);
 
+/* ---- quantised ReLU and pooling layers: module forms ------------------------------------------------------------------
+ * The packed forwards of the reference's QuantReLU, QuantMaxPool2d and QuantAdaptiveAvgPool2d (modelzoo/modules/quantrelu.py:
+ * 81-86, quant_pooling.py:90-97, :159-165): `x, s, z = a_quantizer(x)` and then relu | max_pool2d | adaptive_avg_pool2d of
+ * (x + z) * s.  fp32 NCHW in, fp32 out, one pass, no workspace, asynchronous on stream.
+ * rq     the layer's activation quantiser in the MODULE's convention; n_bits and sign are ignored (nothing is packed).
+ *        n_param 1 (per tensor) or C (per channel; a plane is one channel).
+ * qdq(v) = (clamp(rint(v / scale - zero), qmin, qmax) + zero) * scale, each step one fp32 operation in this order: IEEE
+ *        division, subtraction, round half to even, clamp (a NaN passes the clamp; +-inf clamps to qmax / qmin), addition,
+ *        multiplication (quantizer.py:31,215, quant_pooling.py:95), element for element; no step is fused with another.
+ * x, out 4-byte aligned (any such alignment takes the same kernel); QE_ERR_ARG for a NULL operand, a negative size, an
+ *        n_param that is neither 1 nor the channel count, or out overlapping x, scale or zero (except x == out where stated).
+ *
+ * qe_quant_relu          out[i] = relu(qdq(x[i])) for i < n, relu(y) = y when y > 0 or y is NaN, else +0.  The channel of element
+ *        i is (i / inner) % n_param (NCHW: inner = H*W), as qe_quantize_pack; any n_param >= 1.  x == out (in place) is allowed,
+ *        as QuantReLU(inplace=True).
+ * qe_quant_maxpool2d     geometry as qe_maxpool2d_codes: square kernel / stride / padding, dilation 1, ceil_mode false,
+ *        2 * padding <= kernel, OH = (H + 2 * padding - kernel) / stride + 1, padding taps ignored.  out[n,c,oh,ow] = the maximum
+ *        of qdq(tap) over the in-bounds taps of the window; a window that holds a NaN tap gives NaN; +0 and -0 compare equal and
+ *        either may come back.  qdq is non-decreasing for scale > 0, so the kernel takes the maximum of the raw taps and applies
+ *        qdq once (the same bits); planes whose scale is not > 0 are done tap by tap.  The ABI has no dilation or return_indices
+ *        argument: the bindings answer those with QE_ERR_UNSUPPORTED.
+ * qe_quant_adaptive_avgpool2d   the window of output (oh, ow) is rows floor(oh * H / OH) .. ceil((oh + 1) * H / OH) - 1 and
+ *        columns floor(ow * W / OW) .. ceil((ow + 1) * W / OW) - 1 (torch's rule).  out = sum / (float)cnt, where sum starts at
+ *        +0 and adds qdq(tap) in fp32 tap by tap, rows outer, columns inner, both ascending; cnt is the tap count; one fp32
+ *        division.  THIS SEQUENCE IS THE CONTRACT: torch's CPU adaptive_avg_pool2d does not add in a fixed sequential order, so
+ *        the result is within (cnt + 1) * 2^-24 * max|qdq(tap)| of torch's and of the exact mean, not torch's bit pattern. */
+int qe_quant_relu(const float *x, int64_t n, int64_t inner, const qe_requant *rq, float *out, qe_stream_t stream);
+int qe_quant_maxpool2d(const float *x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t kernel, int32_t stride,
+                       int32_t padding, const qe_requant *rq, float *out, qe_stream_t stream);
+int qe_quant_adaptive_avgpool2d(const float *x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t OH, int32_t OW,
+                                const qe_requant *rq, float *out, qe_stream_t stream);
+
+/* ---- qe_avgpool2d_codes -- average pooling of 8-bit stored codes, fp32 and / or the consumer's codes out ---------------
+ * What stands between two quantised layers in CLIP's ModifiedResNet (AvgPool2d(2) after the stem, AvgPool2d(stride) in
+ * front of the strided convs) and at the end of wrn_40_2 (avg_pool2d(out, 8)); AdaptiveAvgPool2d too.
+ * x       N*C*H*W stored codes, one byte each (n_bits == 8; sub-8-bit streams return QE_ERR_UNSUPPORTED); q = byte - 128 when
+ *         sign, else byte; scale / zero' in the KERNEL convention (q - zero') * scale; n_param 1 or C.
+ * kernel  > 0: kernel x kernel windows at `stride`, no padding, floor mode (nn.AvgPool2d(kernel, stride)); OH and OW must equal
+ *         (H - kernel) / stride + 1 and (W - kernel) / stride + 1 (else QE_ERR_ARG).
+ *         == 0: adaptive windows to (OH, OW) by the rule of qe_quant_adaptive_avgpool2d (stride is ignored); (1, 1) is the
+ *         global pool.
+ * value   cnt = taps of the window, fc = (float)cnt.  All operations are single fp32 operations, none fused:
+ *         relu == 0:  S = the exact integer sum of q over the window;  y = (scale * ((float)S - fc * zero')) / fc.
+ *         relu != 0:  t = (float)q - zero';  r = t when t > 0 or t is NaN, else +0;  R = the fp32 sum of r over the window, from +0,
+ *                     tap by tap, rows outer, columns inner, both ascending;  y = (scale * R) / fc.
+ *                     (The producer's codes are pre-ReLU.  For an integer zero' with |zero'| <= 256 and cnt * 512 < 2^24 every
+ *                     partial sum is an exact integer, so R is the exact integer sum in any order; the kernels use that.)
+ *         A window with cnt * 255 >= 2^24 returns QE_ERR_UNSUPPORTED ((float)S would round).
+ * out     fp32[N*C*OH*OW], 4-byte aligned; may be NULL when rq != NULL.
+ * rq, codes  the consumer's quantiser (module convention; n_param 1 or C) and its packed stream: bit-identical to
+ *         qe_quantize_pack(y, rq->scale, rq->zero, rq->n_param, OH*OW, ...) for every n_bits.  codes without rq, rq without codes
+ *         and out == codes == NULL are QE_ERR_ARG, as is an output (out, codes, status) overlapping an operand or another output.
+ * status  as qe_tpack.     No workspace.  Asynchronous on stream; no host synchronisation, allocation or free.
+ * qe_avgpool2d_codes_path (host only): the instance the call with these arguments launches, from the one plan the launch reads:
+ *         1 pair   kernel == stride == 2 (rq NULL or 8-bit): a thread makes 16 adjacent outputs of a row from 2 x 32 input bytes
+ *                  (two 16-byte loads per row at any alignment, horizontal pair sums by byte dot products, 16-byte stores);
+ *         2 plane  the one window is the whole plane (adaptive (1, 1), or kernel == H == W; rq NULL or 8-bit): 2^k lanes per
+ *                  plane read it in aligned 16-byte pieces, several planes per workgroup, any plane size the value rule admits;
+ *         0 plain  one thread per output (8 consecutive outputs per thread for a sub-8-bit rq, whose bytes it then owns);
+ *        -1 none   (the call returns QE_ERR_ARG or QE_ERR_UNSUPPORTED).
+ *         out / codes are looked at for being NULL only: no instance depends on an alignment. */
+int qe_avgpool2d_codes_path(const qe_qparam *x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t kernel, int32_t stride,
+                            int32_t OH, int32_t OW, int32_t relu, const float *out, const qe_requant *rq, const uint8_t *codes);
+int qe_avgpool2d_codes(const qe_qparam *x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t kernel, int32_t stride,
+                       int32_t OH, int32_t OW, int32_t relu, float *out, const qe_requant *rq, uint8_t *codes, int32_t *status,
+                       qe_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -88,6 +88,12 @@ PROTOTYPES = {
     "qe_quantize_patchify": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _f32, _f32, _i32, _i32, _vp, _vp, _vp]),
     "qe_global_avgpool": (_i32, [_vp, _i64, _i32, _vp, _vp]),
     "qe_maxpool2d_codes": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    # quantised ReLU and pooling layers
+    "qe_quant_relu": (_i32, [_vp, _i64, _i64, _pr, _vp, _vp]),
+    "qe_quant_maxpool2d": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _pr, _vp, _vp]),
+    "qe_quant_adaptive_avgpool2d": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _pr, _vp, _vp]),
+    "qe_avgpool2d_codes_path": (_i32, [_pq] + [_i32] * 9 + [_vp, _pr, _vp]),
+    "qe_avgpool2d_codes": (_i32, [_pq] + [_i32] * 9 + [_vp, _pr, _vp, _vp, _vp]),
     # packed-activation convolutions
     "qe_quantconv2d_path": (_i32, [_ps, _pq, _pq]),
     "qe_quantconv2d_plan_info": (_i32, [_ps, _pq, _pq, _pr, _vp, _vp, _pi]),
@@ -505,6 +511,98 @@ def maxpool2d_codes(x, n_bits, N, C, H, W, kernel=3, stride=2, padding=1, out=No
     check(lib().qe_maxpool2d_codes(x.data_ptr(), int(N), int(C), int(H), int(W), int(kernel), int(stride), int(padding),
                                    out.data_ptr(), _stream(stream)))
     return out
+
+
+def _fp32_nchw(x):
+    import torch
+    assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and x.dim() == 4
+
+
+def quant_relu(x, rq, inner=None, out=None, stream=None):
+    """qe_quant_relu: relu(qdq(x)) of a contiguous fp32 tensor under the layer's quantiser rq (a capi.requant; per channel:
+    dimension 1, so inner defaults to the product of the later dimensions).  out=None: a new tensor; out=x: in place."""
+    import torch
+    assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32
+    if inner is None:
+        inner = 1
+        for v in x.shape[2:]:
+            inner *= v
+    if out is None:
+        out = torch.empty_like(x)
+    check(lib().qe_quant_relu(x.data_ptr(), x.numel(), int(inner), ctypes.byref(rq), out.data_ptr(), _stream(stream)))
+    return out
+
+
+def quant_maxpool2d(x, rq, kernel, stride=None, padding=0, dilation=1, return_indices=False, ceil_mode=False, out=None, stream=None):
+    """qe_quant_maxpool2d: max_pool2d(qdq(x)) of fp32 NCHW x.  Square geometry, dilation 1, no indices, floor mode: anything else
+    raises QeError(QE_ERR_UNSUPPORTED)."""
+    import torch
+    _fp32_nchw(x)
+    stride = kernel if stride is None else stride
+    if int(dilation) != 1 or return_indices or ceil_mode:
+        check(QE_ERR_UNSUPPORTED)
+    N, C, H, W = x.shape
+    OH, OW = (H + 2 * padding - kernel) // stride + 1, (W + 2 * padding - kernel) // stride + 1
+    if out is None:
+        out = torch.empty((N, C, max(OH, 0), max(OW, 0)), dtype=torch.float32, device=x.device)
+    check(lib().qe_quant_maxpool2d(x.data_ptr(), N, C, H, W, int(kernel), int(stride), int(padding), ctypes.byref(rq),
+                                   out.data_ptr(), _stream(stream)))
+    return out
+
+
+def quant_adaptive_avgpool2d(x, rq, output_size, out=None, stream=None):
+    """qe_quant_adaptive_avgpool2d: the mean of qdq(x) over torch's adaptive windows, summed in the header's fixed order."""
+    import torch
+    _fp32_nchw(x)
+    N, C, H, W = x.shape
+    OH, OW = (output_size, output_size) if isinstance(output_size, int) else output_size
+    OH, OW = (H if OH is None else int(OH)), (W if OW is None else int(OW))
+    if out is None:
+        out = torch.empty((N, C, OH, OW), dtype=torch.float32, device=x.device)
+    check(lib().qe_quant_adaptive_avgpool2d(x.data_ptr(), N, C, H, W, OH, OW, ctypes.byref(rq), out.data_ptr(), _stream(stream)))
+    return out
+
+
+# qe_avgpool2d_codes_path: the instance by number
+POOL_KERNELS = ("plain", "pair", "plane")
+
+
+def avgpool2d_out_hw(H, W, kernel, stride, output_size=None):
+    """(OH, OW) of a codes-domain average pool: fixed windows (kernel > 0, floor mode, no padding) or adaptive (kernel == 0)."""
+    if kernel:
+        return (H - kernel) // stride + 1, (W - kernel) // stride + 1
+    return (output_size, output_size) if isinstance(output_size, int) else tuple(output_size)
+
+
+def avgpool2d_codes_path(xq, N, C, H, W, kernel=0, stride=None, output_size=None, relu=False, rq=None, out=256, codes=256):
+    """qe_avgpool2d_codes_path (host-only): 1 pair, 2 plane, 0 plain, -1 none.  out / codes: destination addresses (out == 0 asks
+    for the codes-only call; codes is passed only with rq)."""
+    stride = (kernel or 1) if stride is None else stride
+    OH, OW = avgpool2d_out_hw(H, W, kernel, stride, output_size)
+    return int(lib().qe_avgpool2d_codes_path(ctypes.byref(xq), int(N), int(C), int(H), int(W), int(kernel), int(stride), int(OH),
+                                             int(OW), 1 if relu else 0, int(out) or None, None if rq is None else ctypes.byref(rq),
+                                             (int(codes) or None) if rq is not None else None))
+
+
+def avgpool2d_codes(xq, N, C, H, W, kernel=0, stride=None, output_size=None, relu=False, rq=None, out="new", codes=None,
+                    status=None, stream=None):
+    """qe_avgpool2d_codes: the window means of 8-bit stored codes (kernel > 0: nn.AvgPool2d(kernel, stride); kernel == 0: adaptive
+    to output_size) as fp32 `out` and / or, with rq, the consumer's codes.  relu: max(q - zero', 0) per tap first.
+    out="new" allocates it, None skips it (rq required), or pass a tensor.  Returns (out or None, codes or None, status)."""
+    import torch
+    dev = xq._keep[0].device
+    stride = (kernel or 1) if stride is None else stride
+    OH, OW = avgpool2d_out_hw(H, W, kernel, stride, output_size)
+    n = max(N * C * OH * OW, 0)
+    if isinstance(out, str):
+        out = torch.empty((N, C, max(OH, 0), max(OW, 0)), dtype=torch.float32, device=dev)
+    if rq is not None and codes is None:
+        codes = torch.empty(packed_nbytes(n, rq.n_bits), dtype=torch.uint8, device=dev)
+    status = _status(status, dev)
+    check(lib().qe_avgpool2d_codes(ctypes.byref(xq), int(N), int(C), int(H), int(W), int(kernel), int(stride), int(OH), int(OW),
+                                   1 if relu else 0, _ptr(out), None if rq is None else ctypes.byref(rq), _ptr(codes),
+                                   status.data_ptr(), _stream(stream)))
+    return out, codes, status
 
 
 def quantize_pack(x, scale, zero, qmin, qmax, n_bits, sign, inner=1, out=None, status=None, stream=None):

@@ -4,6 +4,7 @@
 #include "qe_conv_plan.hpp"
 #include "qe_conv_dw.hpp"
 #include "qe_conv_grp.hpp"
+#include "qe_pool.hpp"
 
 #include <atomic>
 #include <cstring>
@@ -745,4 +746,113 @@ extern "C" int qe_quantconv2d_grouped(const qe_qparam *x, const qe_qparam *w, co
                                       int32_t *status, qe_stream_t stream)
 {
     return qe::run_span_conv<qe::GrpFamily>(x, w, bias, shape, groups, relu, out, rq, codes, status, stream);
+}
+
+// ---- quantised ReLU and pooling layers (qe_pool.hip) ----
+// The module forms check their request here and hand it to one launcher each; the codes-domain average pool plans once
+// (plan_pool, qe_pool.hpp) and the path query and the call read that plan.
+namespace qe {
+// x, out and the layer's quantiser of a module form: n elements in, n_out out, `channels` planes' worth of scales (0: any count)
+static int check_module_form(const float *x, int64_t n_in, const qe_requant *rq, float *out, int64_t n_out, int channels, bool in_place_ok)
+{
+    if (rq == nullptr || rq->scale == nullptr || rq->zero == nullptr || rq->n_param < 1) return QE_ERR_ARG;
+    if (channels > 0 && !(rq->n_param == 1 || rq->n_param == channels)) return QE_ERR_ARG;
+    if (n_out == 0) return QE_OK;
+    if (x == nullptr || out == nullptr) return QE_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(x) & 3) != 0 || (reinterpret_cast<uintptr_t>(out) & 3) != 0) return QE_ERR_ARG;
+    const Span o = span_of(out, n_out * 4);
+    if (!(in_place_ok && x == out) && overlaps(o, span_of(x, n_in * 4))) return QE_ERR_ARG;
+    if (overlaps(o, span_of(rq->scale, 4 * (int64_t)rq->n_param)) || overlaps(o, span_of(rq->zero, 4 * (int64_t)rq->n_param)))
+        return QE_ERR_ARG;
+    return QE_OK;
+}
+
+static PoolPlan plan_pool_request(const qe_qparam *x, int N, int C, int H, int W, int kernel, int stride, int OH, int OW, const float *out,
+                                  const qe_requant *rq)
+{
+    return plan_pool(PoolRequest{N, C, H, W, kernel, stride, OH, OW, x->n_bits, rq != nullptr ? rq->n_bits : 0, out != nullptr});
+}
+
+// formats and counts of a codes-domain request (pointers are not looked at)
+static int check_pool_request(const qe_qparam *x, int C, const qe_requant *rq)
+{
+    if (x == nullptr) return QE_ERR_ARG;
+    if (!(x->n_bits > 0 && x->n_bits <= 8)) return QE_ERR_NBITS;
+    if (rq != nullptr && !(rq->n_bits > 0 && rq->n_bits <= 8)) return QE_ERR_NBITS;
+    if (!(x->n_param == 1 || x->n_param == C)) return QE_ERR_ARG;
+    if (rq != nullptr && !(rq->n_param == 1 || rq->n_param == C)) return QE_ERR_ARG;
+    return QE_OK;
+}
+}  // namespace qe
+
+extern "C" int qe_quant_relu(const float *x, int64_t n, int64_t inner, const qe_requant *rq, float *out, qe_stream_t stream)
+{
+    using namespace qe;
+    if (n < 0 || inner <= 0) return QE_ERR_ARG;
+    const int rc = check_module_form(x, n, rq, out, n, 0, true);
+    if (rc != QE_OK || n == 0) return rc;
+    return launch_quant_relu(x, n, inner, rq, out, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int qe_quant_maxpool2d(const float *x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t kernel, int32_t stride,
+                                  int32_t padding, const qe_requant *rq, float *out, qe_stream_t stream)
+{
+    using namespace qe;
+    if (N < 0 || C < 0 || H <= 0 || W <= 0 || kernel <= 0 || stride <= 0 || padding < 0 || 2 * padding > kernel) return QE_ERR_ARG;
+    const int OH = (H + 2 * padding - kernel) / stride + 1, OW = (W + 2 * padding - kernel) / stride + 1;
+    if (H + 2 * padding < kernel || W + 2 * padding < kernel || OH <= 0 || OW <= 0) return QE_ERR_ARG;
+    if ((int64_t)H * W > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
+    const int64_t n_in = (int64_t)N * C * H * W, n = (int64_t)N * C * OH * OW;
+    const int rc = check_module_form(x, n_in, rq, out, n, C, false);
+    if (rc != QE_OK || n == 0) return rc;
+    return launch_quant_maxpool2d(x, N, C, H, W, kernel, stride, padding, OH, OW, rq, out, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int qe_quant_adaptive_avgpool2d(const float *x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t OH, int32_t OW,
+                                           const qe_requant *rq, float *out, qe_stream_t stream)
+{
+    using namespace qe;
+    if (N < 0 || C < 0 || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return QE_ERR_ARG;
+    if ((int64_t)H * W > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
+    const int64_t n_in = (int64_t)N * C * H * W, n = (int64_t)N * C * OH * OW;
+    const int rc = check_module_form(x, n_in, rq, out, n, C, false);
+    if (rc != QE_OK || n == 0) return rc;
+    return launch_quant_adaptive_avgpool2d(x, N, C, H, W, OH, OW, rq, out, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int qe_avgpool2d_codes_path(const qe_qparam *x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t kernel, int32_t stride,
+                                       int32_t OH, int32_t OW, int32_t relu, const float *out, const qe_requant *rq, const uint8_t *codes)
+{
+    (void)relu;
+    if (qe::check_pool_request(x, C, rq) != QE_OK || (codes != nullptr) != (rq != nullptr)) return -1;
+    return qe::plan_pool_request(x, N, C, H, W, kernel, stride, OH, OW, out, rq).kernel;
+}
+
+extern "C" int qe_avgpool2d_codes(const qe_qparam *x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t kernel, int32_t stride,
+                                  int32_t OH, int32_t OW, int32_t relu, float *out, const qe_requant *rq, uint8_t *codes,
+                                  int32_t *status, qe_stream_t stream)
+{
+    using namespace qe;
+    int rc = check_qparam(x);
+    if (rc != QE_OK) return rc;
+    if (rq != nullptr && (rc = check_requant(rq)) != QE_OK) return rc;
+    if ((rc = check_pool_request(x, C, rq)) != QE_OK) return rc;
+    if ((out == nullptr && codes == nullptr) || (codes != nullptr) != (rq != nullptr)) return QE_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(out) & 3) != 0 || (reinterpret_cast<uintptr_t>(status) & 3) != 0) return QE_ERR_ARG;
+    const PoolPlan p = plan_pool_request(x, N, C, H, W, kernel, stride, OH, OW, out, rq);
+    if (p.kernel == POOL_NONE) return p.rc;
+    const int64_t n_in = (int64_t)N * C * H * W, n = (int64_t)N * C * OH * OW;
+    // an output may overlap neither an operand nor another output
+    const Span outs[3] = {span_of(out, n * 4), span_of(codes, rq ? qe_packed_nbytes(n, rq->n_bits) : 0), span_of(status, 4)};
+    const Span ins[5] = {span_of(x->data, n_in), span_of(x->scale, 4 * (int64_t)x->n_param), span_of(x->zero, 4 * (int64_t)x->n_param),
+                         span_of(rq ? rq->scale : nullptr, rq ? 4 * (int64_t)rq->n_param : 0),
+                         span_of(rq ? rq->zero : nullptr, rq ? 4 * (int64_t)rq->n_param : 0)};
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 5; ++j)
+            if (overlaps(outs[i], ins[j])) return QE_ERR_ARG;
+        for (int j = i + 1; j < 3; ++j)
+            if (overlaps(outs[i], outs[j])) return QE_ERR_ARG;
+    }
+    if (n == 0) return QE_OK;
+    return launch_pool_codes(p, x, N, C, H, W, kernel, stride, relu, out, rq, codes, status, static_cast<hipStream_t>(stream));
 }

@@ -480,15 +480,189 @@ class PackedMultiheadAttention:
         return out.reshape(L, N, E), (attn.reshape(N, H, L, S).mean(dim=1) if need_weights else None)
 
 
-def from_state_dict(state_dict, conv_geometry=None, num_heads=None):
+class _PackedQuantLayer:
+    """A packed layer that owns nothing but its activation quantiser (QuantReLU, the quantised pools): pack() leaves
+    a_quantizer.{scale, zero, qmin, qmax} in the state_dict and no weight.  The quantiser reaches the engine in the module's
+    convention (capi.requant) for the fp32 forwards and as the (q - zero') operand of a code stream for call_packed."""
+
+    def __init__(self, a_scale, a_zero, a_qmin, a_qmax, name=None):
+        self.name = name
+        self.a_qmin, self.a_qmax = float(a_qmin), float(a_qmax)
+        self.a_bits, self.a_signed = quantizer_bits(a_qmin, a_qmax)
+        self._a_scale = a_scale.reshape(-1).contiguous().float()
+        self._a_zero = a_zero.reshape(-1).contiguous().float()
+        self._neg_a_zero = (-self._a_zero).contiguous()
+
+    a_scale = property(lambda self: self._a_scale)
+    a_zero = property(lambda self: self._a_zero)
+
+    @classmethod
+    def _state(cls, sd, prefix):
+        g = lambda k: sd[prefix + "a_quantizer." + k]
+        return dict(a_scale=g("scale"), a_zero=g("zero"), a_qmin=float(g("qmin")), a_qmax=float(g("qmax")), name=prefix.rstrip("."))
+
+    def to(self, device):
+        for k, v in list(vars(self).items()):
+            if torch.is_tensor(v):
+                setattr(self, k, v.to(device))
+        return self
+
+    def requant(self):
+        """This layer's quantiser as a capi.requant: the operand of its own fp32 forward, or of a producer's epilogue."""
+        return capi.requant(self._a_scale, self._a_zero, self.a_qmin, self.a_qmax, self.a_bits, self.a_signed)
+
+    def _check(self, x):
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32):
+            raise ValueError("%s takes an fp32 CUDA tensor" % type(self).__name__)
+        if self._a_scale.numel() not in (1, x.shape[1]):
+            raise ValueError("%s: %d scales for %d channels" % (self.name or "layer", self._a_scale.numel(), x.shape[1]))
+        return x.contiguous()
+
+
+class PackedReLU(_PackedQuantLayer):
+    """A packed QuantReLU's forward (quantrelu.py:81-86) in one kernel: relu((q + zero) * scale), q the layer's codes of x."""
+
+    def __init__(self, *, inplace=False, **state):
+        super().__init__(**state)
+        self.inplace = bool(inplace)
+
+    @classmethod
+    def from_state_dict(cls, state_dict, prefix="", inplace=False):
+        return cls(inplace=inplace, **cls._state(state_dict, prefix))
+
+    def __call__(self, x):
+        xc = self._check(x)
+        return capi.quant_relu(xc, self.requant(), out=xc if self.inplace and xc is x else None)
+
+
+class PackedMaxPool2d(_PackedQuantLayer):
+    """A packed QuantMaxPool2d's forward (quant_pooling.py:90-97) in one kernel.  Square kernel / stride / padding, dilation 1,
+    floor mode, no indices: a layer with anything else is refused here (QeError, unsupported) and nothing runs in its place."""
+
+    def __init__(self, *, kernel_size, stride=None, padding=0, dilation=1, return_indices=False, ceil_mode=False, **state):
+        super().__init__(**state)
+        for v in (kernel_size, stride, padding, dilation):
+            if isinstance(v, (tuple, list)) and len(set(v)) != 1:
+                capi.check(capi.QE_ERR_UNSUPPORTED)
+        self.kernel = _first(kernel_size)
+        self.stride = self.kernel if stride is None else _first(stride)
+        self.padding = _first(padding)
+        if _first(dilation) != 1 or return_indices or ceil_mode:
+            capi.check(capi.QE_ERR_UNSUPPORTED)
+
+    @classmethod
+    def from_state_dict(cls, state_dict, prefix="", kernel_size=None, stride=None, padding=0, **kw):
+        if kernel_size is None:
+            raise ValueError("PackedMaxPool2d.from_state_dict: kernel_size is required (a state_dict holds no geometry)")
+        return cls(kernel_size=kernel_size, stride=stride, padding=padding, **kw, **cls._state(state_dict, prefix))
+
+    def __call__(self, x):
+        return capi.quant_maxpool2d(self._check(x), self.requant(), self.kernel, self.stride, self.padding)
+
+
+class _PackedAvgPoolBase(_PackedQuantLayer):
+    """call_packed of the two average pools: codes of this layer's quantiser in, through qe_avgpool2d_codes."""
+
+    def _window(self, H, W):
+        raise NotImplementedError          # (kernel, stride, output_size) of the codes-domain call
+
+    def call_packed(self, xq, x_des, consumer=None, relu=False, status=None):
+        """Activations as (packed stream, des) of THIS layer's quantiser -- what a producer's call_packed(consumer=this layer)
+        returned.  consumer=None: the fp32 window means (of max(q - zero', 0) per tap when relu: the producer's codes are
+        pre-ReLU).  consumer = the Packed* layer that reads them: the (packed, des) pair of ITS quantiser from this call's own
+        epilogue, bit-identical to consumer.quantize(fp32 output).  status as PackedDepthwiseConv2d.call_packed."""
+        n_bits, sign, N, C, H, W = _host_des(x_des)
+        if self._a_scale.numel() not in (1, C):
+            raise ValueError("%s: %d scales for codes of %d channels" % (self.name or "layer", self._a_scale.numel(), C))
+        kernel, stride, osize = self._window(H, W)
+        x = capi.qparam(xq, n_bits, sign, self._a_scale, self._neg_a_zero)
+        if consumer is None:
+            return capi.avgpool2d_codes(x, N, C, H, W, kernel, stride, osize, relu=relu)[0]
+        _, codes, flag = capi.avgpool2d_codes(x, N, C, H, W, kernel, stride, osize, relu=relu, rq=consumer.requant(), out=None,
+                                              status=status)
+        if status is None and int(flag.item()) != 0:
+            raise RuntimeError(OUT_OF_RANGE)
+        des = (consumer.a_bits, int(consumer.a_signed), N, C, *capi.avgpool2d_out_hw(H, W, kernel, stride, osize))
+        return codes, (des if status is not None else torch.tensor(des, dtype=torch.int32, device=xq.device))
+
+
+class PackedAdaptiveAvgPool2d(_PackedAvgPoolBase):
+    """A packed QuantAdaptiveAvgPool2d's forward (quant_pooling.py:159-165) in one kernel: the mean of (q + zero) * scale over
+    torch's adaptive windows, added up in the fixed order include/quant_engine.h states (not torch's bit pattern)."""
+
+    def __init__(self, *, output_size, **state):
+        super().__init__(**state)
+        self.output_size = (output_size, output_size) if isinstance(output_size, int) else tuple(output_size)
+
+    @classmethod
+    def from_state_dict(cls, state_dict, prefix="", output_size=None):
+        if output_size is None:
+            raise ValueError("PackedAdaptiveAvgPool2d.from_state_dict: output_size is required (a state_dict holds no geometry)")
+        return cls(output_size=output_size, **cls._state(state_dict, prefix))
+
+    def _size(self, H, W):
+        return (H if self.output_size[0] is None else int(self.output_size[0]), W if self.output_size[1] is None else int(self.output_size[1]))
+
+    def _window(self, H, W):
+        return 0, 1, self._size(H, W)
+
+    def __call__(self, x):
+        xc = self._check(x)
+        return capi.quant_adaptive_avgpool2d(xc, self.requant(), self._size(*xc.shape[2:]))
+
+
+class PackedAvgPool2d(_PackedAvgPoolBase):
+    """nn.AvgPool2d(kernel_size, stride) (no padding, floor mode) behind a quantiser: what stands between two quantised layers
+    of CLIP's ModifiedResNet and at the end of wrn_40_2.  call_packed runs any kernel / stride on codes.  The fp32 forward is the
+    adaptive module kernel, whose windows are these exactly when stride == kernel divides H and W; other geometries have no fp32
+    kernel and raise ValueError (nothing runs in its place)."""
+
+    def __init__(self, *, kernel_size, stride=None, **state):
+        super().__init__(**state)
+        self.kernel = _first(kernel_size)
+        self.stride = self.kernel if stride is None else _first(stride)
+
+    @classmethod
+    def from_state_dict(cls, state_dict, prefix="", kernel_size=None, stride=None):
+        if kernel_size is None:
+            raise ValueError("PackedAvgPool2d.from_state_dict: kernel_size is required (a state_dict holds no geometry)")
+        return cls(kernel_size=kernel_size, stride=stride, **cls._state(state_dict, prefix))
+
+    def _window(self, H, W):
+        return self.kernel, self.stride, None
+
+    def __call__(self, x):
+        xc = self._check(x)
+        H, W = xc.shape[2:]
+        if self.stride != self.kernel or H % self.kernel or W % self.kernel:
+            raise ValueError("PackedAvgPool2d: the fp32 forward takes stride == kernel_size dividing H and W; got kernel %d, stride %d "
+                             "on %d x %d (call_packed takes any)" % (self.kernel, self.stride, H, W))
+        return capi.quant_adaptive_avgpool2d(xc, self.requant(), (H // self.kernel, W // self.kernel))
+
+
+POOL_KINDS = {"relu": (PackedReLU, ("inplace",)), "maxpool": (PackedMaxPool2d, ("kernel_size", "stride", "padding")),
+              "adaptive_avgpool": (PackedAdaptiveAvgPool2d, ("output_size",))}
+
+
+def from_state_dict(state_dict, conv_geometry=None, num_heads=None, pool_geometry=None):
     """Every packed layer of a model's state_dict -> {module prefix (no trailing dot): PackedConv2d | PackedLinear |
     PackedMultiheadAttention}: what the packing loop of runner/ptq.py:106-114 / runner/qat.py:84-92 leaves behind, ready to
     run on the engine with no reference Python in the process.  A packed conv / linear is recognised by its `w_des` entry
     (6 fields = conv: n_bits, sign, OC, IC, KH, KW; 4 = linear), an attention block by `q_proj_des`.
     conv_geometry: {prefix: (stride, padding)} -- geometry is not part of the state_dict; default stride 1, padding
-    (KH - 1) // 2 ("same" for odd kernels).  num_heads: {prefix: heads} (or one int for every attention block)."""
+    (KH - 1) // 2 ("same" for odd kernels).  num_heads: {prefix: heads} (or one int for every attention block).
+    pool_geometry: {prefix: ("relu"[, inplace]) | ("maxpool", kernel_size[, stride[, padding]]) | ("adaptive_avgpool",
+    output_size)} -- a packed QuantReLU / QuantMaxPool2d / QuantAdaptiveAvgPool2d leaves only its a_quantizer entries behind,
+    which do not say what the layer is: the map names each one -> PackedReLU | PackedMaxPool2d | PackedAdaptiveAvgPool2d."""
     conv_geometry = conv_geometry or {}
     layers = {}
+    for name, (kind, *args) in (pool_geometry or {}).items():
+        if kind not in POOL_KINDS:
+            raise ValueError("%s: pool_geometry kind %r is none of %s" % (name, kind, sorted(POOL_KINDS)))
+        cls, names = POOL_KINDS[kind]
+        if len(args) > len(names):
+            raise ValueError("%s: %r takes at most %s" % (name, kind, names))
+        layers[name] = cls.from_state_dict(state_dict, name + "." if name else "", **dict(zip(names, args)))
     for key in state_dict:
         if key.endswith("w_des"):
             prefix = key[:-len("w_des")]
