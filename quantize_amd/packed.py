@@ -168,6 +168,20 @@ class PackedConv2d(_PackedConvBase):
             self._prep[key] = capi.conv_prepare(wq, self.bias, sh, xq.n_bits)
         return sh, xq, wq, self._prep[key]
 
+    # ---- the two steps of a model's fused route: codes of this layer's own quantiser in, no host read ----
+    def fp32_from_codes(self, codes, N, H, W):
+        """The fp32 output on `codes` of an N x IC x H x W input."""
+        sh, xq, wq, prep = self.operands(codes, N, H, W)
+        return capi.quantconv2d_prepared(xq, wq, self.bias, sh, prep)
+
+    def relu_codes(self, codes, N, H, W, consumer, status):
+        """relu(output) as consumer's codes: from this conv's own epilogue where the ReLU folds into consumer's clamp, else
+        fp32 + relu + quantize_pack.  The range flag accumulates in `status`."""
+        if not consumer.folds_relu:
+            return consumer.quantize_codes(torch.relu(self.fp32_from_codes(codes, N, H, W)), status)[0]
+        sh, xq, wq, prep = self.operands(codes, N, H, W)
+        return capi.quantconv2d_requant_prepared(xq, wq, self.bias, sh, prep, consumer.requant(), status=status)[0]
+
     def __call__(self, x, route="packed"):
         w = (self.weight, self.w_des, self.w_scale, self._neg_w_zero)
         if route == "packed":
@@ -233,6 +247,10 @@ class _PackedSpanConv(_PackedConvBase):
             raise RuntimeError(OUT_OF_RANGE)
         des = (consumer.a_bits, int(consumer.a_signed), N, self.OC, *self.out_hw(H, W))
         return codes, (des if status is not None else torch.tensor(des, dtype=torch.int32, device=xq.device))
+
+    def relu_codes(self, codes, N, H, W, consumer, status):
+        """As PackedConv2d.relu_codes: the ReLU is applied in this layer's own epilogue, whatever consumer's quantiser."""
+        return self.call_packed(codes, (self.a_bits, int(self.a_signed), N, self.IC, H, W), consumer, relu=True, status=status)[0]
 
 
 class PackedDepthwiseConv2d(_PackedSpanConv):

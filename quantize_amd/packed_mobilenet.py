@@ -17,14 +17,12 @@ state_dict and runs it two ways:
 
 Every fused step is bit-identical to its layers form, so the logits of the two routes agree bit for bit.  With check=False
 the fused route makes no device -> host copy: every range flag accumulates in one device int32."""
-import re
-
 import numpy as np
 import torch
 
-from . import capi
-from .packed import OUT_OF_RANGE, PackedConv2d, PackedDepthwiseConv2d, PackedLinear
-from .packed_resnet import _conv_entries, pack_codes
+from . import synthetic
+from .packed import PackedConv2d, PackedDepthwiseConv2d, PackedLinear
+from .packed_cnn import PackedCNN
 
 DEPTH = (1, 2, 2, 6, 2)          # blocks per stage of the reference's model; from_state_dict reads them from the keys
 
@@ -34,19 +32,15 @@ class _Block:
         self.name, self.dw, self.pw = name, dw, pw
 
 
-class PackedMobileNetV1:
+class PackedMobileNetV1(PackedCNN):
+    FAMILY = "MobileNetV1"
+
     def __init__(self, stem, blocks, fc):
         self.stem, self._blocks, self.fc = stem, blocks, fc
 
     @classmethod
     def from_state_dict(cls, sd, prefix=""):
-        sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
-
-        def layer(kind, name, **geometry):
-            try:
-                return kind.from_state_dict(sd, name + ".", **geometry)
-            except KeyError as e:
-                raise KeyError("packed MobileNetV1 state_dict: missing %s%s" % (prefix, e.args[0])) from None
+        sd, layer = cls._open(sd, prefix)
 
         def square(c, name, k):
             if c.KH != k or c.KW != k:
@@ -54,18 +48,10 @@ class PackedMobileNetV1:
             return c
 
         stem = square(layer(PackedConv2d, "conv1", stride=2, padding=1), "conv1", 3)
-        found = {}
-        for k in sd:
-            m = re.match(r"layer(\d+)\.(\d+)\.conv1\.w_des$", k)
-            if m:
-                found.setdefault(int(m.group(1)), set()).add(int(m.group(2)))
-        if not found or sorted(found) != list(range(1, len(found) + 1)):
-            raise KeyError("packed MobileNetV1 state_dict: stages layer1.. not found (have %s)" % sorted(found))
+        found = cls._stages(sd, r"layer(\d+)\.(\d+)\.conv1\.w_des$")
         blocks, C = [], stem.OC
         for S in sorted(found):
-            if sorted(found[S]) != list(range(len(found[S]))):
-                raise KeyError("packed MobileNetV1 state_dict: layer%d has blocks %s" % (S, sorted(found[S])))
-            for B in sorted(found[S]):
+            for B in cls._block_indices(found, S):
                 pre = "layer%d.%d" % (S, B)
                 dw = square(layer(PackedDepthwiseConv2d, pre + ".conv1", stride=2 if (B == 0 and S > 1) else 1, padding=1),
                             pre + ".conv1", 3)
@@ -88,29 +74,10 @@ class PackedMobileNetV1:
             out += [b.dw, b.pw]
         return out
 
-    def to(self, device):
-        for layer in self.convs() + [self.fc]:
-            layer.to(device)
-        return self
-
     # ---- the two routes ----
-    def __call__(self, images, route="fused", check=True):
-        return self.forward(images, route, check)[0]
-
     def forward(self, images, route="fused", check=True):
         """(logits, pooled features)."""
-        if route == "layers":
-            feat = self._layers(images)
-            pooled = capi.global_avgpool(feat)
-            return self.fc(pooled, route="packed"), pooled
-        if route != "fused":
-            raise ValueError("route must be 'fused' or 'layers'")
-        status = torch.zeros(1, dtype=torch.int32, device=images.device)
-        feat = self._fused(images.contiguous(), status)
-        pooled = capi.global_avgpool(feat)
-        logits = self.fc.call_packed(*self.fc.quantize_codes(pooled, status), status=status)
-        if check and int(status.item()) != 0:
-            raise RuntimeError(OUT_OF_RANGE)
+        logits, _, pooled = self._run(images, route, check)
         return logits, pooled
 
     def _layers(self, x, observe=None):
@@ -122,49 +89,14 @@ class PackedMobileNetV1:
             y = torch.relu(c(y, route="packed"))
         return y
 
-    @staticmethod
-    def _conv_codes(c, codes, N, H, W, consumer, status):
-        """c's output (behind its ReLU) as consumer's codes, as PackedResNet._conv_codes."""
-        sh, xq, wq, prep = c.operands(codes, N, H, W)
-        if consumer.folds_relu:
-            return capi.quantconv2d_requant_prepared(xq, wq, c.bias, sh, prep, consumer.requant(), status=status)[0]
-        y = torch.relu(capi.quantconv2d_prepared(xq, wq, c.bias, sh, prep))
-        return consumer.quantize_codes(y, status)[0]
-
     def _fused(self, images, status):
         N, _, H, W = images.shape
         codes = self.stem.quantize_codes(images, status)[0]
-        producer = self.stem
-        for i, b in enumerate(self._blocks):
-            codes = self._conv_codes(producer, codes, N, H, W, b.dw, status)
-            H, W = producer.out_hw(H, W)
-            des = (b.dw.a_bits, int(b.dw.a_signed), N, b.dw.C, H, W)
-            codes = b.dw.call_packed(codes, des, consumer=b.pw, relu=True, status=status)[0]
-            H, W = b.dw.out_hw(H, W)
-            producer = b.pw
-        sh, xq, wq, prep = producer.operands(codes, N, H, W)
-        return torch.relu(capi.quantconv2d_prepared(xq, wq, producer.bias, sh, prep))
-
-    # ---- calibration (synthetic models, tests, tools) ----
-    def calibrate(self, images):
-        """Every activation quantiser's scale from the max of what reaches it in one `layers` pass, as PackedResNet.calibrate."""
-        def observe(c, t):
-            s = (t.abs().max() if c.a_signed else t.clamp(min=0).max()) / c.a_qmax
-            c.a_scale = torch.clamp(s, min=1e-8).reshape(1)
-        with torch.no_grad():
-            pooled = capi.global_avgpool(self._layers(images, observe))
-            self.fc.a_scale = torch.clamp(pooled.clamp(min=0).max() / self.fc.a_qmax, min=1e-8).reshape(1)
-        return self
-
-    def state_dict_scales(self):
-        out = {c.name + ".a_quantizer.scale": c.a_scale for c in self.convs()}
-        out["fc.a_quantizer.scale"] = self.fc.a_scale
-        return out
-
-
-def _dw_entries(rng, C, w_bits, a_bits):
-    e = _conv_entries(rng, 1, C, 3, w_bits, a_bits, False, 1.0)          # (C, 1, 3, 3): one 9-tap filter per channel
-    return e
+        convs = self.convs()
+        for c, consumer in zip(convs[:-1], convs[1:]):       # stem -> dw -> pw -> dw -> ...: each writes the next one's codes
+            codes = c.relu_codes(codes, N, H, W, consumer, status)
+            H, W = c.out_hw(H, W)
+        return torch.relu(convs[-1].fp32_from_codes(codes, N, H, W))
 
 
 def synthetic_state_dict(num_classes=1000, w_bits=8, a_bits=8, seed=0, width=32, depth=DEPTH):
@@ -174,39 +106,24 @@ def synthetic_state_dict(num_classes=1000, w_bits=8, a_bits=8, seed=0, width=32,
     rng = np.random.RandomState(seed)
     sd = {}
 
-    def put(prefix, entries):
-        for k, v in entries.items():
-            sd[prefix + "." + k] = v
+    def conv(name, IC, OC, K, signed=False):
+        synthetic.put(sd, name, synthetic.conv_entries(rng, IC, OC, K, w_bits, a_bits, signed, 1.0))
 
-    put("conv1", _conv_entries(rng, 3, width, 3, w_bits, a_bits, True, 1.0))
+    conv("conv1", 3, width, 3, signed=True)
     C = width
     for S, nb in enumerate(depth, start=1):
         planes = width * (1 << S)
         for B in range(nb):
             pre = "layer%d.%d" % (S, B)
-            put(pre + ".conv1", _dw_entries(rng, C, w_bits, a_bits))
-            put(pre + ".conv2", _conv_entries(rng, C, planes, 1, w_bits, a_bits, False, 1.0))
+            conv(pre + ".conv1", 1, C, 3)            # depthwise, (C, 1, 3, 3): one 9-tap filter per channel
+            conv(pre + ".conv2", C, planes, 1)
             C = planes
-    lim = (1 << (w_bits - 1)) - 1
-    qf = rng.randint(-lim, lim + 1, size=(num_classes, C))
-    sd.update({"fc.weight": torch.from_numpy(pack_codes(qf, w_bits, True)),
-               "fc.w_des": torch.tensor([w_bits, 1, num_classes, C], dtype=torch.int32),
-               "fc.w_scale": torch.from_numpy((np.sqrt(1.0 / C) / lim * rng.uniform(0.8, 1.2, size=(num_classes, 1))).astype(np.float32)),
-               "fc.w_zero": torch.zeros((num_classes, 1), dtype=torch.float32),
-               "fc.bias": torch.from_numpy(rng.normal(0, 0.05, size=num_classes).astype(np.float32)),
-               "fc.a_quantizer.scale": torch.tensor([1.0], dtype=torch.float32),
-               "fc.a_quantizer.zero": torch.tensor([0.0], dtype=torch.float32),
-               "fc.a_quantizer.qmin": torch.tensor(0.0), "fc.a_quantizer.qmax": torch.tensor(float((1 << a_bits) - 1))})
+    synthetic.put(sd, "fc", synthetic.fc_entries(rng, num_classes, C, w_bits, a_bits))
     return sd
 
 
 def calibrated_state_dict(device="cuda", calib_images=None, calib_batch=4, image_size=224, **kw):
     """synthetic_state_dict on `device` with every activation quantiser calibrated by max from one `layers` pass."""
-    sd = {k: v.to(device) for k, v in synthetic_state_dict(**kw).items()}
-    if calib_images is None:
-        g = torch.Generator(device="cpu").manual_seed(kw.get("seed", 0) + 1)
-        calib_images = torch.randn(calib_batch, 3, image_size, image_size, generator=g).to(device)
-    model = PackedMobileNetV1.from_state_dict(sd).calibrate(calib_images)
-    for k, v in model.state_dict_scales().items():
-        sd[k] = v.detach().clone()
-    return sd
+    images = synthetic.calibration_images(calib_images, calib_batch, image_size, kw.get("seed", 0))
+    return synthetic.calibrated(synthetic_state_dict(**kw), device, PackedMobileNetV1.from_state_dict, images,
+                                PackedMobileNetV1.state_dict_scales)

@@ -22,14 +22,14 @@ fused step would not be exact, the fused route takes the layers route's form for
 With check=False the fused route makes no device -> host copy or synchronisation: every range flag accumulates in one
 device int32, read once at the end when check=True.
 """
-import re
-
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import capi
-from .packed import OUT_OF_RANGE, PackedConv2d, PackedGroupedConv2d, PackedLinear
+from . import capi, synthetic
+from .packed import PackedConv2d, PackedGroupedConv2d, PackedLinear
+from .packed_cnn import PackedCNN
+from .synthetic import pack_codes  # noqa: F401  (a public name of this module: earlier importers read it from here)
 
 
 class _Block:
@@ -37,17 +37,9 @@ class _Block:
         self.name, self.convs, self.downsample, self.stride = name, convs, downsample, stride
 
 
-def _stage_keys(sd):
-    found = {}
-    for k in sd:
-        m = re.match(r"layer(\d+)\.(\d+)\.conv(\d)\.w_des$", k)
-        if m:
-            found.setdefault(int(m.group(1)), {}).setdefault(int(m.group(2)), set()).add(int(m.group(3)))
-    return found
-
-
-class PackedResNet:
+class PackedResNet(PackedCNN):
     """A packed torchvision ResNet (Bottleneck: ResNet-50 / 101 / 152, BasicBlock: ResNet-18 / 34) on the engine."""
+    FAMILY = "ResNet"
 
     def __init__(self, stem, stages, fc, kind, groups=1):
         self.stem, self.stages, self.fc, self.kind, self.groups = stem, stages, fc, kind, groups
@@ -61,26 +53,21 @@ class PackedResNet:
     def from_state_dict(cls, sd, prefix=""):
         """torchvision's geometry: stem 7x7 / 2 pad 3; in a stage's first block the stride sits on the Bottleneck's conv2
         (the BasicBlock's conv1) and on the downsample; 3x3 convs pad 1, 1x1 convs pad 0."""
-        sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+        sd, layer = cls._open(sd, prefix)
 
         def conv(name, stride, padding, in_channels=None):
             """in_channels: what feeds the layer; a w_des that names fewer input channels is a grouped layer's (ResNeXt)."""
-            try:
-                if in_channels is not None and (name + ".w_des") in sd and int(sd[name + ".w_des"][3]) < in_channels:
-                    c = PackedGroupedConv2d.from_state_dict(sd, name + ".", stride=stride, padding=padding, in_channels=in_channels)
-                else:
-                    c = PackedConv2d.from_state_dict(sd, name + ".", stride=stride, padding=padding)
-            except KeyError as e:
-                raise KeyError("packed ResNet state_dict: missing %s%s" % (prefix, e.args[0])) from None
+            if in_channels is not None and (name + ".w_des") in sd and int(sd[name + ".w_des"][3]) < in_channels:
+                c = layer(PackedGroupedConv2d, name, stride=stride, padding=padding, in_channels=in_channels)
+            else:
+                c = layer(PackedConv2d, name, stride=stride, padding=padding)
             if c.KH != 2 * padding + 1 or c.KW != c.KH:
                 raise ValueError("%s: a %dx%d kernel where torchvision's ResNet has %dx%d" % (name, c.KH, c.KW, 2 * padding + 1,
                                                                                            2 * padding + 1))
             return c
 
         stem = conv("conv1", 2, 3)
-        found = _stage_keys(sd)
-        if sorted(found) != list(range(1, len(found) + 1)) or not found:
-            raise KeyError("packed ResNet state_dict: stages layer1.. not found (have %s)" % sorted(found))
+        found = cls._stages(sd, r"layer(\d+)\.(\d+)\.conv(\d)\.w_des$")
         kinds = {tuple(sorted(c)) for blocks in found.values() for c in blocks.values()}
         if kinds == {(1, 2, 3)}:
             kind = "bottleneck"
@@ -90,10 +77,8 @@ class PackedResNet:
             raise ValueError("packed ResNet state_dict: blocks with conv sets %s are neither Bottleneck nor BasicBlock" % sorted(kinds))
         stages, groups = [], set()
         for S in sorted(found):
-            if sorted(found[S]) != list(range(len(found[S]))):
-                raise KeyError("packed ResNet state_dict: layer%d has blocks %s" % (S, sorted(found[S])))
             blocks = []
-            for B in sorted(found[S]):
+            for B in cls._block_indices(found, S):
                 pre = "layer%d.%d." % (S, B)
                 s = (1 if S == 1 else 2) if B == 0 else 1
                 if kind == "bottleneck":
@@ -110,10 +95,7 @@ class PackedResNet:
                     raise KeyError("packed ResNet state_dict: missing %s%sdownsample.0.w_des" % (prefix, pre))
                 blocks.append(_Block(pre[:-1], convs, ds, s))
             stages.append(blocks)
-        try:
-            fc = PackedLinear.from_state_dict(sd, "fc.")
-        except KeyError as e:
-            raise KeyError("packed ResNet state_dict: missing %s%s" % (prefix, e.args[0])) from None
+        fc = layer(PackedLinear, "fc")
         if len(groups) > 1:
             raise ValueError("packed ResNet state_dict: the Bottlenecks' conv2 layers have different groups %s" % sorted(groups))
         return cls(stem, stages, fc, kind, groups.pop() if groups else 1)
@@ -152,36 +134,14 @@ class PackedResNet:
             res.append(capi.residual_path(sh, c.xq(codes), c.wq(), rq))
         return res
 
-    def to(self, device):
-        for layer in self.convs() + [self.fc]:
-            layer.to(device)
-        return self
-
     # ---- the two routes ----
-    def __call__(self, images, route="fused", check=True):
-        return self.forward(images, route, check)[0]
-
     def features(self, images, route="fused", check=True):
         """The layer4 feature map (fp32, N x C x 7 x 7 at 224 x 224)."""
         return self.forward(images, route, check)[1]
 
     def forward(self, images, route="fused", check=True):
         """(logits, layer4 features)."""
-        if route == "layers":
-            feat = self._layers(images)
-        elif route == "fused":
-            status = torch.zeros(1, dtype=torch.int32, device=images.device)
-            feat = self._fused(images.contiguous(), status)
-        else:
-            raise ValueError("route must be 'fused' or 'layers'")
-        pooled = capi.global_avgpool(feat)
-        if route == "layers":
-            logits = self.fc(pooled, route="packed")
-        else:
-            logits = self.fc.call_packed(*self.fc.quantize_codes(pooled, status), status=status)
-            if check and int(status.item()) != 0:
-                raise RuntimeError(OUT_OF_RANGE)
-        return logits, feat
+        return self._run(images, route, check)[:2]
 
     def _layers(self, x, observe=None):
         """observe(conv, its fp32 input) is called in front of every conv (calibration)."""
@@ -198,17 +158,6 @@ class PackedResNet:
             y = torch.relu(run(b.convs[-1], o) + identity)
         return y
 
-    def _conv_codes(self, c, codes, N, H, W, consumer, status):
-        """c's output as consumer's codes: fused into c's epilogue where the ReLU folds, else fp32 + relu + quantize_pack.
-        A grouped conv (ResNeXt's conv2) applies the ReLU in its own epilogue, whatever the consumer's quantiser."""
-        if isinstance(c, PackedGroupedConv2d):
-            return c.call_packed(codes, (c.a_bits, int(c.a_signed), N, c.IC, H, W), consumer, relu=True, status=status)[0]
-        sh, xq, wq, prep = c.operands(codes, N, H, W)
-        if consumer.folds_relu:
-            return capi.quantconv2d_requant_prepared(xq, wq, c.bias, sh, prep, consumer.requant(), status=status)[0]
-        y = torch.relu(capi.quantconv2d_prepared(xq, wq, c.bias, sh, prep))
-        return consumer.quantize_codes(y, status)[0]
-
     def _fused(self, images, status):
         N, _, H, W = images.shape
         blocks = self.blocks()
@@ -221,11 +170,10 @@ class PackedResNet:
         xin = None
         if c1.folds_relu and c1.a_bits == 8 and first.downsample is not None and first.downsample.q_key == c1.q_key:
             # stem -> layer1.0.conv1's codes (ReLU folded), then the maxpool on the codes: nothing else reads the fp32
-            s_codes = self._conv_codes(stem, codes, N, H, W, c1, status)
+            s_codes = stem.relu_codes(codes, N, H, W, c1, status)
             xcodes = capi.maxpool2d_codes(s_codes, 8, N, stem.OC, Hs, Ws, 3, 2, 1)
         else:
-            sh, xq, wq, prep = stem.operands(codes, N, H, W)
-            xin = F.max_pool2d(torch.relu(capi.quantconv2d_prepared(xq, wq, stem.bias, sh, prep)), 3, 2, 1)
+            xin = F.max_pool2d(torch.relu(stem.fp32_from_codes(codes, N, H, W)), 3, 2, 1)
             xcodes = c1.quantize_codes(xin, status)[0]
         H, W = Hp, Wp
         for i, b in enumerate(blocks):
@@ -234,13 +182,12 @@ class PackedResNet:
             if b.downsample is not None:
                 ds = b.downsample
                 dcodes = xcodes if ds.q_key == b.convs[0].q_key else ds.quantize_codes(xin, status)[0]
-                sh, xq, wq, prep = ds.operands(dcodes, N, H, W)
-                identity = capi.quantconv2d_prepared(xq, wq, ds.bias, sh, prep)
+                identity = ds.fp32_from_codes(dcodes, N, H, W)
             else:
                 identity = xin
             o, Ho, Wo = xcodes, H, W
             for c, cn in zip(b.convs[:-1], b.convs[1:]):
-                o = self._conv_codes(c, o, N, Ho, Wo, cn, status)
+                o = c.relu_codes(o, N, Ho, Wo, cn, status)
                 Ho, Wo = c.out_hw(Ho, Wo)
             last = b.convs[-1]
             # the block end: fp32 out unless the next block only reads codes (its identity is its downsample's output,
@@ -254,60 +201,11 @@ class PackedResNet:
             H, W = last.out_hw(Ho, Wo)
         return xin
 
-    # ---- calibration (synthetic models, tests, tools) ----
-    def calibrate(self, images):
-        """Set every activation quantiser's scale from the max of what reaches it in one `layers` pass (by max, as the
-        existing bottleneck test does): unsigned quantisers take max / qmax, signed ones max|x| / qmax."""
-        def observe(c, t):
-            if c.a_signed:
-                s = t.abs().max() / c.a_qmax
-            else:
-                s = t.clamp(min=0).max() / c.a_qmax
-            c.a_scale = torch.clamp(s, min=1e-8).reshape(1)
-        with torch.no_grad():
-            feat = self._layers(images, observe)
-            pooled = capi.global_avgpool(feat)
-            self.fc.a_scale = torch.clamp(pooled.clamp(min=0).max() / self.fc.a_qmax, min=1e-8).reshape(1)
-        return self
-
-    def state_dict_scales(self):
-        """{key: tensor} of every activation scale, in the state_dict's key layout."""
-        out = {c.name + ".a_quantizer.scale": c.a_scale for c in self.convs()}
-        out["fc.a_quantizer.scale"] = self.fc.a_scale
-        return out
-
 
 # ---------------------------------------------------------------------------------------------
 # Synthetic packed ResNets (tests and tools/bench_resnet_forward.py share this construction)
 # ---------------------------------------------------------------------------------------------
 ARCHS = {"resnet18": ("basic", [2, 2, 2, 2]), "resnet34": ("basic", [3, 4, 6, 3]), "resnet50": ("bottleneck", [3, 4, 6, 3])}
-
-
-def pack_codes(q, n_bits, signed):
-    """tpack on the host: integer codes -> the little-endian b-bit stream (stored value q + 2^(b-1) when signed)."""
-    q = np.asarray(q, dtype=np.int64).reshape(-1)
-    stored = (q + ((1 << (n_bits - 1)) if signed else 0)).astype(np.uint64)
-    if n_bits == 8:
-        return stored.astype(np.uint8)
-    bits = ((stored[:, None] >> np.arange(n_bits, dtype=np.uint64)) & 1).astype(np.uint8).reshape(-1)
-    return np.packbits(bits, bitorder="little")
-
-
-def _conv_entries(rng, IC, OC, K, w_bits, a_bits, a_signed, gain, groups=1):
-    lim = (1 << (w_bits - 1)) - 1
-    IC //= groups                  # the input channels a weight sees: pack() stores w_des [b, s, OC, IC / groups, KH, KW]
-    q = rng.randint(-lim, lim + 1, size=(OC, IC, K, K))
-    std_q = np.sqrt(((2 * lim + 1) ** 2 - 1) / 12.0)
-    ws = gain * np.sqrt(2.0 / (IC * K * K)) / std_q * rng.uniform(0.8, 1.2, size=OC)     # He-scaled
-    qmin, qmax = (-(1 << (a_bits - 1)), (1 << (a_bits - 1)) - 1) if a_signed else (0, (1 << a_bits) - 1)
-    return {"weight": torch.from_numpy(pack_codes(q, w_bits, True)),
-            "w_des": torch.tensor([w_bits, 1, OC, IC, K, K], dtype=torch.int32),
-            "w_scale": torch.from_numpy(ws.astype(np.float32).reshape(OC, 1, 1, 1)),
-            "w_zero": torch.zeros((OC, 1, 1, 1), dtype=torch.float32),
-            "bias": torch.from_numpy(rng.normal(0, 0.05, size=OC).astype(np.float32)),        # the folded BatchNorm's shift
-            "a_quantizer.scale": torch.tensor([1.0], dtype=torch.float32),
-            "a_quantizer.zero": torch.tensor([0.0], dtype=torch.float32),
-            "a_quantizer.qmin": torch.tensor(float(qmin)), "a_quantizer.qmax": torch.tensor(float(qmax))}
 
 
 def synthetic_state_dict(arch="resnet50", num_classes=1000, w_bits=8, a_bits=8, seed=0, width=64, groups=1, width_per_group=64):
@@ -320,11 +218,10 @@ def synthetic_state_dict(arch="resnet50", num_classes=1000, w_bits=8, a_bits=8, 
     rng = np.random.RandomState(seed)
     sd = {}
 
-    def put(prefix, entries):
-        for k, v in entries.items():
-            sd[prefix + "." + k] = v
+    def conv(name, IC, OC, K, gain=1.0, signed=False, groups=1):
+        synthetic.put(sd, name, synthetic.conv_entries(rng, IC, OC, K, w_bits, a_bits, signed, gain, groups))
 
-    put("conv1", _conv_entries(rng, 3, width, 7, w_bits, a_bits, True, 1.0))
+    conv("conv1", 3, width, 7, signed=True)
     inplanes, exp = width, (4 if kind == "bottleneck" else 1)
     for S, nb in enumerate(depth, start=1):
         planes = width * (1 << (S - 1))
@@ -332,36 +229,21 @@ def synthetic_state_dict(arch="resnet50", num_classes=1000, w_bits=8, a_bits=8, 
             pre = "layer%d.%d" % (S, B)
             if kind == "bottleneck":
                 mid = planes * width_per_group // 64 * groups
-                put(pre + ".conv1", _conv_entries(rng, inplanes, mid, 1, w_bits, a_bits, False, 1.0))
-                put(pre + ".conv2", _conv_entries(rng, mid, mid, 3, w_bits, a_bits, False, 1.0, groups))
-                put(pre + ".conv3", _conv_entries(rng, mid, planes * 4, 1, w_bits, a_bits, False, 0.3))
+                conv(pre + ".conv1", inplanes, mid, 1)
+                conv(pre + ".conv2", mid, mid, 3, groups=groups)
+                conv(pre + ".conv3", mid, planes * 4, 1, gain=0.3)
             else:
-                put(pre + ".conv1", _conv_entries(rng, inplanes, planes, 3, w_bits, a_bits, False, 1.0))
-                put(pre + ".conv2", _conv_entries(rng, planes, planes, 3, w_bits, a_bits, False, 0.3))
+                conv(pre + ".conv1", inplanes, planes, 3)
+                conv(pre + ".conv2", planes, planes, 3, gain=0.3)
             if B == 0 and (S > 1 or inplanes != planes * exp):
-                put(pre + ".downsample.0", _conv_entries(rng, inplanes, planes * exp, 1, w_bits, a_bits, False, 1.0))
+                conv(pre + ".downsample.0", inplanes, planes * exp, 1)
             inplanes = planes * exp
-    lim = (1 << (w_bits - 1)) - 1
-    qf = rng.randint(-lim, lim + 1, size=(num_classes, inplanes))
-    sd.update({"fc.weight": torch.from_numpy(pack_codes(qf, w_bits, True)),
-               "fc.w_des": torch.tensor([w_bits, 1, num_classes, inplanes], dtype=torch.int32),
-               "fc.w_scale": torch.from_numpy((np.sqrt(1.0 / inplanes) / lim * rng.uniform(0.8, 1.2, size=(num_classes, 1)))
-                                              .astype(np.float32)),
-               "fc.w_zero": torch.zeros((num_classes, 1), dtype=torch.float32),
-               "fc.bias": torch.from_numpy(rng.normal(0, 0.05, size=num_classes).astype(np.float32)),
-               "fc.a_quantizer.scale": torch.tensor([1.0], dtype=torch.float32),
-               "fc.a_quantizer.zero": torch.tensor([0.0], dtype=torch.float32),
-               "fc.a_quantizer.qmin": torch.tensor(0.0), "fc.a_quantizer.qmax": torch.tensor(float((1 << a_bits) - 1))})
+    synthetic.put(sd, "fc", synthetic.fc_entries(rng, num_classes, inplanes, w_bits, a_bits))
     return sd
 
 
 def calibrated_state_dict(arch="resnet50", device="cuda", calib_images=None, calib_batch=4, image_size=224, **kw):
     """synthetic_state_dict on `device` with every activation quantiser calibrated by max from one `layers` pass."""
-    sd = {k: v.to(device) for k, v in synthetic_state_dict(arch, **kw).items()}
-    if calib_images is None:
-        g = torch.Generator(device="cpu").manual_seed(kw.get("seed", 0) + 1)
-        calib_images = torch.randn(calib_batch, 3, image_size, image_size, generator=g).to(device)
-    model = PackedResNet.from_state_dict(sd).calibrate(calib_images)
-    for k, v in model.state_dict_scales().items():
-        sd[k] = v.detach().clone()
-    return sd
+    images = synthetic.calibration_images(calib_images, calib_batch, image_size, kw.get("seed", 0))
+    return synthetic.calibrated(synthetic_state_dict(arch, **kw), device, PackedResNet.from_state_dict, images,
+                                PackedResNet.state_dict_scales)

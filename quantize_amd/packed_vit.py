@@ -35,9 +35,9 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import capi
+from . import capi, synthetic
 from .packed import OUT_OF_RANGE, PackedConv2d, PackedLinear, PackedMultiheadAttention, quantizer_bits
-from .packed_resnet import pack_codes
+from .synthetic import pack_codes
 
 
 ATTENTION = ("torch", "engine", "engine_bf16")
@@ -398,16 +398,11 @@ def synthetic_state_dict(arch="vit_b_16", w_bits=8, a_bits=8, seed=0, **over):
     E, p, C, M = cfg["width"], cfg["patch"], 3, cfg["mlp"]
     L = (cfg["image_size"] // p) ** 2 + 1
     sd = {}
-
-    def put(prefix, entries):
-        for k, v in entries.items():
-            sd[prefix + k] = v
-
     conv = _lin_entries(rng, E, C * p * p, w_bits, True, True, a_bits)
     conv["w_des"] = torch.tensor([w_bits, 1, E, C, p, p], dtype=torch.int32)
     conv["w_scale"] = conv["w_scale"].reshape(E, 1, 1, 1)
     conv["w_zero"] = conv["w_zero"].reshape(E, 1, 1, 1)
-    put("conv_proj.", conv)
+    synthetic.put(sd, "conv_proj", conv)
     sd["class_token"] = torch.from_numpy(rng.normal(0, 0.02, size=(1, 1, E)).astype(np.float32))
     sd["encoder.pos_embedding"] = torch.from_numpy(rng.normal(0, 0.02, size=(1, L, E)).astype(np.float32))
     for i in range(cfg["depth"]):
@@ -428,13 +423,13 @@ def synthetic_state_dict(arch="vit_b_16", w_bits=8, a_bits=8, seed=0, **over):
         sd[att + "out_proj.weight"], sd[att + "out_proj_des"] = o["weight"], o["w_des"]
         sd[att + "out_proj_scale"], sd[att + "out_proj_zero"] = o["w_scale"], o["w_zero"]
         sd[att + "out_proj.bias"] = o["bias"]
-        put(pre + "mlp.0.", _lin_entries(rng, M, E, w_bits, True, True, a_bits))
+        synthetic.put(sd, pre + "mlp.0", _lin_entries(rng, M, E, w_bits, True, True, a_bits))
         f2 = _lin_entries(rng, E, M, w_bits, True, False, a_bits)
         f2["w_scale"] = f2["w_scale"] * 0.5
-        put(pre + "mlp.3.", f2)
+        synthetic.put(sd, pre + "mlp.3", f2)
     sd["encoder.ln.weight"] = torch.ones(E, dtype=torch.float32)
     sd["encoder.ln.bias"] = torch.zeros(E, dtype=torch.float32)
-    put("heads.head.", _lin_entries(rng, cfg["num_classes"], E, w_bits, True, True, a_bits))
+    synthetic.put(sd, "heads.head", _lin_entries(rng, cfg["num_classes"], E, w_bits, True, True, a_bits))
     return sd
 
 
@@ -442,12 +437,6 @@ def calibrated_state_dict(arch="vit_b_16", device="cuda", calib_images=None, cal
     """synthetic_state_dict on `device` with every activation quantiser calibrated from one `layers` pass."""
     cfg = dict(CONFIGS[arch])
     cfg.update({k: v for k, v in kw.items() if k in cfg})
-    sd = {k: v.to(device) for k, v in synthetic_state_dict(arch, **kw).items()}
-    if calib_images is None:
-        g = torch.Generator(device="cpu").manual_seed(kw.get("seed", 0) + 1)
-        s = cfg["image_size"]
-        calib_images = torch.randn(calib_batch, 3, s, s, generator=g).to(device)
-    model = PackedViT.from_state_dict(sd, cfg["heads"]).calibrate(calib_images)
-    for k, v in model.state_dict_quantizers().items():
-        sd[k] = v.detach().clone()
-    return sd
+    images = synthetic.calibration_images(calib_images, calib_batch, cfg["image_size"], kw.get("seed", 0))
+    return synthetic.calibrated(synthetic_state_dict(arch, **kw), device, lambda sd: PackedViT.from_state_dict(sd, cfg["heads"]),
+                                images, PackedViT.state_dict_quantizers)

@@ -6,13 +6,12 @@ The model: a 3x3 stride-2 stem, five stages of (depthwise 3x3, pointwise 1x1) bl
 32x32 or 64x64 images: the final planes are 1x1 or 2x2, so the mean is exact in fp32 and every image takes part in the logit
 comparison.  Every scale is a power of two, zero points are integers, biases lie on their grids, and
 K * max|q_x + z_x| * max|q_w + z_w| + |bias units| < 2^24 with K = 9 for a depthwise layer."""
-import re
-
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-from resnet_exact import BIAS_UNITS, PC_RATIO, Float64ResNet, Result, _Layer, _pack, _qrange, weight_cap  # noqa: F401
+from resnet_exact import (BIAS_UNITS, PC_RATIO, Float64ResNet, Result, _Layer, _pack, _qrange, calibrated_exact,  # noqa: F401
+                          exact_conv_entries, exact_fc_entries, images, weight_cap)
 
 DEPTH = (1, 2, 2, 6, 2)
 
@@ -26,12 +25,7 @@ class Float64MobileNetV1(Float64ResNet):
         self.exact = exact
         sd = {k: v for k, v in sd.items()}
         self.stem = _Layer(sd, "conv1", 2, 1)
-        stages = {}
-        for k in sd:
-            m = re.match(r"layer(\d+)\.(\d+)\.conv1\.w_des$", k)
-            if m:
-                stages.setdefault(int(m.group(1)), set()).add(int(m.group(2)))
-        assert stages and sorted(stages) == list(range(1, len(stages) + 1)), sorted(stages)
+        stages = self._stages(sd)
         self.blocks = []
         for S in sorted(stages):
             for B in sorted(stages[S]):
@@ -47,16 +41,6 @@ class Float64MobileNetV1(Float64ResNet):
         for _, dw, pw in self.blocks:
             out += [dw, pw]
         return out + [self.fc]
-
-    def _exact(self, t, what):
-        if self.exact:
-            Float64ResNet._exact(t, what)
-
-    def _conv(self, L, q):
-        x = (q + L.a_view(L.a_zero, q)) * L.a_view(L.a_scale, q)
-        y = F.conv2d(x, L.weights(), L.bias, L.stride, L.padding, 1, getattr(L, "groups", 1))
-        self._exact(y, L.name + " output")
-        return y
 
     def forward(self, images, calibrate=None):
         """Result for an N x 3 x H x W batch (features: the pooled (N, C) features)."""
@@ -93,25 +77,7 @@ def exact_state_dict(w_bits=8, a_bits=8, seed=0, width=8, num_classes=10, calib_
     sd = {}
 
     def conv(name, IC, OC, K, signed_in=False, depthwise=False):
-        spec = variants.get(name, {})
-        signed = signed_in or spec.get("signed", False)
-        qmin, qmax = _qrange(a_bits, signed)
-        z = float(spec.get("zero", 0))
-        a_max = int(max(abs(qmin + z), abs(qmax + z))) * (PC_RATIO if spec.get("per_channel") else 1)
-        per_group = 1 if depthwise else IC
-        cap = weight_cap(per_group * K * K, a_max, w_bits)
-        q = rng.randint(-cap, cap + 1, size=(OC, per_group, K, K))
-        target = np.sqrt(2.0 / (per_group * K * K)) / (cap / np.sqrt(3.0))
-        ws = 2.0 ** (np.round(np.log2(target)) + rng.randint(-1, 2, size=OC))
-        sd.update({name + ".weight": _pack(q, w_bits),
-                   name + ".w_des": torch.tensor([w_bits, 1, OC, per_group, K, K], dtype=torch.int32),
-                   name + ".w_scale": torch.from_numpy(ws.astype(np.float32).reshape(OC, 1, 1, 1)),
-                   name + ".w_zero": torch.zeros((OC, 1, 1, 1), dtype=torch.float32),
-                   name + ".bias": torch.from_numpy(rng.normal(0, 0.05, size=OC).astype(np.float32)),
-                   name + ".a_quantizer.scale": torch.tensor([1.0], dtype=torch.float32),
-                   name + ".a_quantizer.zero": torch.tensor([z], dtype=torch.float32),
-                   name + ".a_quantizer.qmin": torch.tensor(float(qmin)),
-                   name + ".a_quantizer.qmax": torch.tensor(float(qmax))})
+        exact_conv_entries(rng, sd, name, 1 if depthwise else IC, OC, K, 1.0, variants.get(name, {}), w_bits, a_bits, signed_in)
 
     conv("conv1", 3, width, 3, signed_in=True)
     C = width
@@ -122,30 +88,8 @@ def exact_state_dict(w_bits=8, a_bits=8, seed=0, width=8, num_classes=10, calib_
             conv(pre + ".conv1", C, C, 3, depthwise=True)
             conv(pre + ".conv2", C, planes, 1)
             C = planes
-    spec = variants.get("fc", {})
-    qmin, qmax = _qrange(a_bits, False)
-    z = float(spec.get("zero", 0))
-    cap = weight_cap(C, int(max(abs(qmin + z), abs(qmax + z))), w_bits)
-    qf = rng.randint(-cap, cap + 1, size=(num_classes, C))
-    wf = 2.0 ** (np.round(np.log2(np.sqrt(1.0 / C) / cap)) + rng.randint(-1, 2, size=(num_classes, 1)))
-    sd.update({"fc.weight": _pack(qf, w_bits),
-               "fc.w_des": torch.tensor([w_bits, 1, num_classes, C], dtype=torch.int32),
-               "fc.w_scale": torch.from_numpy(wf.astype(np.float32)),
-               "fc.w_zero": torch.zeros((num_classes, 1), dtype=torch.float32),
-               "fc.bias": torch.from_numpy(rng.normal(0, 0.05, size=num_classes).astype(np.float32)),
-               "fc.a_quantizer.scale": torch.tensor([1.0], dtype=torch.float32),
-               "fc.a_quantizer.zero": torch.tensor([z], dtype=torch.float32),
-               "fc.a_quantizer.qmin": torch.tensor(float(qmin)), "fc.a_quantizer.qmax": torch.tensor(float(qmax))})
-    if calib_images is None:
-        calib_images = images(3, image_size, seed + 1)
-    model = Float64MobileNetV1(sd)
-    model.forward(calib_images, calibrate=variants)
-    return model.write_back(sd)
-
-
-def images(n, size, seed):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    return torch.randn(n, 3, size, size, generator=g)
+    exact_fc_entries(rng, sd, num_classes, C, variants.get("fc", {}), w_bits, a_bits)
+    return calibrated_exact(Float64MobileNetV1(sd), sd, calib_images, 3, image_size, seed, variants)
 
 
 def fp32_packed_forward(sd, x):

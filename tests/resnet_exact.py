@@ -98,15 +98,12 @@ class Float64ResNet:
     in a stage's first block the stride sits on the Bottleneck's conv2 (the BasicBlock's conv1) and on the downsample; each
     block ends with relu(conv + identity); then adaptive average pooling and the fc through its own quantiser."""
 
-    def __init__(self, sd):
+    def __init__(self, sd, exact=True):
+        """exact=False: the same arithmetic without the exactness assertions (state_dicts off the exact grid: G11, G12)."""
+        self.exact = exact
         sd = {k: v for k, v in sd.items()}
         self.stem = _Layer(sd, "conv1", 2, 3)
-        stages = {}
-        for k in sd:
-            m = re.match(r"layer(\d+)\.(\d+)\.conv(\d)\.w_des$", k)
-            if m:
-                stages.setdefault(int(m.group(1)), {}).setdefault(int(m.group(2)), set()).add(int(m.group(3)))
-        assert sorted(stages) == list(range(1, len(stages) + 1)) and stages, sorted(stages)
+        stages = self._stages(sd)
         self.bottleneck = 3 in next(iter(stages[1].values()))
         self.blocks = []
         for S in sorted(stages):
@@ -121,6 +118,17 @@ class Float64ResNet:
                 self.blocks.append((pre[:-1], convs, ds))
         self.fc = _Layer(sd, "fc")
 
+    @staticmethod
+    def _stages(sd):
+        """{stage: {block: the conv numbers it has}} of the keys layerS.B.convN.w_des; the stages must be 1..n."""
+        stages = {}
+        for k in sd:
+            m = re.match(r"layer(\d+)\.(\d+)\.conv(\d)\.w_des$", k)
+            if m:
+                stages.setdefault(int(m.group(1)), {}).setdefault(int(m.group(2)), set()).add(int(m.group(3)))
+        assert sorted(stages) == list(range(1, len(stages) + 1)) and stages, sorted(stages)
+        return stages
+
     def layers(self):
         out = [self.stem]
         for _, convs, ds in self.blocks:
@@ -128,9 +136,8 @@ class Float64ResNet:
         return out + [self.fc]
 
     # ---- the arithmetic ----
-    @staticmethod
-    def _exact(t, what):
-        if not torch.equal(t, t.float().double()):
+    def _exact(self, t, what):
+        if self.exact and not torch.equal(t, t.float().double()):
             bad = (t != t.float().double()).nonzero()[0].tolist()
             raise NotExact("%s is not exact in fp32 (first at %s: %r)" % (what, bad, float(t[tuple(bad)])))
 
@@ -147,7 +154,7 @@ class Float64ResNet:
 
     def _conv(self, L, q):
         x = (q + L.a_view(L.a_zero, q)) * L.a_view(L.a_scale, q)
-        y = F.conv2d(x, L.weights(), L.bias, L.stride, L.padding)
+        y = F.conv2d(x, L.weights(), L.bias, L.stride, L.padding, 1, getattr(L, "groups", 1))
         self._exact(y, L.name + " output")
         return y
 
@@ -242,6 +249,52 @@ def _pack(q, bits):
     return torch.from_numpy(oracle.tpack(np.asarray(q, dtype=np.int64), bits, True)[0].copy())
 
 
+def images(n, size, seed):
+    """A seeded N x 3 x size x size batch (size: one side, or (H, W))."""
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    H, W = (size, size) if isinstance(size, int) else size
+    return torch.randn(n, 3, H, W, generator=g)
+
+
+def _quantizer_entries(sd, name, qmin, qmax, z):
+    sd.update({name + ".a_quantizer.scale": torch.tensor([1.0], dtype=torch.float32),
+               name + ".a_quantizer.zero": torch.tensor([z], dtype=torch.float32),
+               name + ".a_quantizer.qmin": torch.tensor(float(qmin)), name + ".a_quantizer.qmax": torch.tensor(float(qmax))})
+
+
+def exact_conv_entries(rng, sd, name, per_group, OC, K, gain, spec, w_bits, a_bits, signed_in=False):
+    """The entries of conv `name` into sd.  per_group: the input channels a weight sees (IC, IC / groups, 1 for depthwise);
+    spec: the layer's variant (exact_state_dict)."""
+    qmin, qmax = _qrange(a_bits, signed_in or spec.get("signed", False))
+    z = float(spec.get("zero", 0))
+    a_max = int(max(abs(qmin + z), abs(qmax + z))) * (PC_RATIO if spec.get("per_channel") else 1)
+    cap = weight_cap(per_group * K * K, a_max, w_bits)
+    q = rng.randint(-cap, cap + 1, size=(OC, per_group, K, K))
+    target = gain * np.sqrt(2.0 / (per_group * K * K)) / (cap / np.sqrt(3.0))        # He-scaled
+    ws = 2.0 ** (np.round(np.log2(target)) + rng.randint(-1, 2, size=OC))             # powers of two, differing per channel
+    sd.update({name + ".weight": _pack(q, w_bits),
+               name + ".w_des": torch.tensor([w_bits, 1, OC, per_group, K, K], dtype=torch.int32),
+               name + ".w_scale": torch.from_numpy(ws.astype(np.float32).reshape(OC, 1, 1, 1)),
+               name + ".w_zero": torch.zeros((OC, 1, 1, 1), dtype=torch.float32),
+               name + ".bias": torch.from_numpy(rng.normal(0, 0.05, size=OC).astype(np.float32))})
+    _quantizer_entries(sd, name, qmin, qmax, z)
+
+
+def exact_fc_entries(rng, sd, num_classes, K, spec, w_bits, a_bits):
+    """The fc's entries into sd: an unsigned quantiser behind the pooled features."""
+    qmin, qmax = _qrange(a_bits, False)
+    z = float(spec.get("zero", 0))
+    cap = weight_cap(K, int(max(abs(qmin + z), abs(qmax + z))), w_bits)
+    q = rng.randint(-cap, cap + 1, size=(num_classes, K))
+    ws = 2.0 ** (np.round(np.log2(np.sqrt(1.0 / K) / cap)) + rng.randint(-1, 2, size=(num_classes, 1)))
+    sd.update({"fc.weight": _pack(q, w_bits),
+               "fc.w_des": torch.tensor([w_bits, 1, num_classes, K], dtype=torch.int32),
+               "fc.w_scale": torch.from_numpy(ws.astype(np.float32)),
+               "fc.w_zero": torch.zeros((num_classes, 1), dtype=torch.float32),
+               "fc.bias": torch.from_numpy(rng.normal(0, 0.05, size=num_classes).astype(np.float32))})
+    _quantizer_entries(sd, "fc", qmin, qmax, z)
+
+
 def exact_state_dict(arch="resnet50", w_bits=8, a_bits=8, seed=0, width=64, num_classes=1000, calib_images=None,
                      image_size=224, variants=None):
     """A packed ResNet state_dict in synthetic_state_dict's key layout with exact fp32 arithmetic (module docstring),
@@ -257,24 +310,7 @@ def exact_state_dict(arch="resnet50", w_bits=8, a_bits=8, seed=0, width=64, num_
     sd = {}
 
     def conv(name, IC, OC, K, gain, signed_in=False):
-        spec = variants.get(name, {})
-        signed = signed_in or spec.get("signed", False)
-        qmin, qmax = _qrange(a_bits, signed)
-        z = float(spec.get("zero", 0))
-        a_max = int(max(abs(qmin + z), abs(qmax + z))) * (PC_RATIO if spec.get("per_channel") else 1)
-        cap = weight_cap(IC * K * K, a_max, w_bits)
-        q = rng.randint(-cap, cap + 1, size=(OC, IC, K, K))
-        target = gain * np.sqrt(2.0 / (IC * K * K)) / (cap / np.sqrt(3.0))        # He-scaled
-        ws = 2.0 ** (np.round(np.log2(target)) + rng.randint(-1, 2, size=OC))     # powers of two, differing per channel
-        sd.update({name + ".weight": _pack(q, w_bits),
-                   name + ".w_des": torch.tensor([w_bits, 1, OC, IC, K, K], dtype=torch.int32),
-                   name + ".w_scale": torch.from_numpy(ws.astype(np.float32).reshape(OC, 1, 1, 1)),
-                   name + ".w_zero": torch.zeros((OC, 1, 1, 1), dtype=torch.float32),
-                   name + ".bias": torch.from_numpy(rng.normal(0, 0.05, size=OC).astype(np.float32)),
-                   name + ".a_quantizer.scale": torch.tensor([1.0], dtype=torch.float32),
-                   name + ".a_quantizer.zero": torch.tensor([z], dtype=torch.float32),
-                   name + ".a_quantizer.qmin": torch.tensor(float(qmin)),
-                   name + ".a_quantizer.qmax": torch.tensor(float(qmax))})
+        exact_conv_entries(rng, sd, name, IC, OC, K, gain, variants.get(name, {}), w_bits, a_bits, signed_in)
 
     conv("conv1", 3, width, 7, 1.0, signed_in=True)
     inplanes, exp = width, (4 if kind == "bottleneck" else 1)
@@ -292,26 +328,13 @@ def exact_state_dict(arch="resnet50", w_bits=8, a_bits=8, seed=0, width=64, num_
             if B == 0 and (S > 1 or inplanes != planes * exp):
                 conv(pre + ".downsample.0", inplanes, planes * exp, 1, 1.0)
             inplanes = planes * exp
-    spec = variants.get("fc", {})
-    qmin, qmax = _qrange(a_bits, False)
-    z = float(spec.get("zero", 0))
-    cap = weight_cap(inplanes, int(max(abs(qmin + z), abs(qmax + z))), w_bits)
-    qf = rng.randint(-cap, cap + 1, size=(num_classes, inplanes))
-    wf = 2.0 ** (np.round(np.log2(np.sqrt(1.0 / inplanes) / cap)) + rng.randint(-1, 2, size=(num_classes, 1)))
-    sd.update({"fc.weight": _pack(qf, w_bits),
-               "fc.w_des": torch.tensor([w_bits, 1, num_classes, inplanes], dtype=torch.int32),
-               "fc.w_scale": torch.from_numpy(wf.astype(np.float32)),
-               "fc.w_zero": torch.zeros((num_classes, 1), dtype=torch.float32),
-               "fc.bias": torch.from_numpy(rng.normal(0, 0.05, size=num_classes).astype(np.float32)),
-               "fc.a_quantizer.scale": torch.tensor([1.0], dtype=torch.float32),
-               "fc.a_quantizer.zero": torch.tensor([z], dtype=torch.float32),
-               "fc.a_quantizer.qmin": torch.tensor(float(qmin)), "fc.a_quantizer.qmax": torch.tensor(float(qmax))})
-    if calib_images is None:
-        g = torch.Generator(device="cpu").manual_seed(seed + 1)
-        H, W = (image_size, image_size) if isinstance(image_size, int) else image_size
-        calib_images = torch.randn(2, 3, H, W, generator=g)
-    model = Float64ResNet(sd)
-    model.forward(calib_images, calibrate=variants)
+    exact_fc_entries(rng, sd, num_classes, inplanes, variants.get("fc", {}), w_bits, a_bits)
+    return calibrated_exact(Float64ResNet(sd), sd, calib_images, 2, image_size, seed, variants)
+
+
+def calibrated_exact(model, sd, calib_images, n, image_size, seed, variants):
+    """sd with the scales, zeros and snapped biases of `model` (built on sd) calibrated on calib_images, or on n seeded ones."""
+    model.forward(images(n, image_size, seed + 1) if calib_images is None else calib_images, calibrate=variants)
     return model.write_back(sd)
 
 

@@ -7,7 +7,8 @@ import torch
 
 import oracle
 from quantize_amd import capi
-from quantize_amd.packed_resnet import PackedResNet, pack_codes, synthetic_state_dict
+from quantize_amd.packed_resnet import PackedResNet, synthetic_state_dict
+from quantize_amd.synthetic import pack_codes
 
 
 def test_resnet50_layout_discovered():

@@ -9,7 +9,7 @@ import torch
 import oracle
 import pwr_instances
 from quantize_amd import capi
-from quantize_amd.packed_resnet import pack_codes
+from quantize_amd.synthetic import pack_codes
 from test_conv_gpu import _assert_conv_close
 
 pytestmark = pytest.mark.gpu

@@ -16,7 +16,7 @@ import torch.nn.functional as F
 
 from quantize_amd import capi
 from quantize_amd.packed import PackedLinear
-from quantize_amd.packed_resnet import pack_codes
+from quantize_amd.synthetic import pack_codes
 from quantize_amd.packed_vit import PackedViT, pack_vit_state_dict
 
 pytestmark = pytest.mark.gpu

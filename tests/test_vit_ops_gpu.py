@@ -15,7 +15,7 @@ import torch.nn.functional as F
 
 from quantize_amd import capi
 from quantize_amd.packed import PackedConv2d
-from quantize_amd.packed_resnet import pack_codes
+from quantize_amd.synthetic import pack_codes
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"

@@ -18,6 +18,7 @@ def main():
     ap.add_argument("--size", type=int, default=224)
     args = ap.parse_args()
     import torch
+    from forward_routes import time_routes
     from quantize_amd.packed_resnet import PackedResNet, calibrated_state_dict
     dev = "cuda:0"
     sd = calibrated_state_dict("resnet50", device=dev, image_size=args.size, calib_batch=4, groups=args.groups,
@@ -26,25 +27,9 @@ def main():
     assert model.groups == args.groups
     g = torch.Generator(device="cpu").manual_seed(3)
     x = torch.randn(args.batch, 3, args.size, args.size, generator=g).to(dev)
-    res, outs = {}, {}
-    for route in ("layers", "fused"):
-        fn = (lambda: model(x, route="fused", check=False)) if route == "fused" else (lambda: model(x, route="layers"))
-        outs[route] = fn()
-        fn()
-        ts = []
-        for _ in range(args.reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            ts.append(a.elapsed_time(b))
-        ms = sorted(ts)[len(ts) // 2]
-        res[route] = {"ms": round(ms, 3), "images_per_s": round(args.batch / (ms * 1e-3), 1)}
     print(json.dumps({"metric": "resnext50_forward", "batch": args.batch, "groups": args.groups,
                       "width_per_group": args.width_per_group, "size": args.size, "reps": args.reps,
-                      "routes_bit_equal": bool(torch.equal(outs["layers"], outs["fused"])), **res,
-                      "fused_vs_layers": round(res["layers"]["ms"] / res["fused"]["ms"], 2)}))
+                      **time_routes(model, x, args.reps)}))
 
 
 if __name__ == "__main__":
