@@ -1,5 +1,6 @@
-// qe_api.hip -- C-ABI entry points that are not tied to one kernel file:
-// error strings, version, and the conv dispatch (generic fp32 vs int8 MFMA).
+// qe_api.hip -- C-ABI entry points that are not tied to one kernel file: error strings, version, the conv dispatch (generic
+// fp32 vs int8 MFMA), the depthwise / grouped run path and the pooling module forms.  Host code only: the checks every
+// request shares are in qe_request.hpp, every kernel and its launch in the file of its family.
 #include "qe_common.h"
 #include "qe_conv_plan.hpp"
 #include "qe_conv_dw.hpp"
@@ -80,14 +81,6 @@ static int check_nparam(const qe_qparam *x, const qe_qparam *w, const qe_conv_sh
     return QE_OK;
 }
 
-static int check_qparam(const qe_qparam *q)
-{
-    if (q == nullptr || q->data == nullptr || q->scale == nullptr || q->zero == nullptr) return QE_ERR_ARG;
-    if (!(q->n_bits > 0 && q->n_bits <= 8)) return QE_ERR_NBITS;
-    if (q->n_param < 1) return QE_ERR_ARG;
-    return QE_OK;
-}
-
 // what every packed-conv entry point checks first, in this order: the shape, the input operand, the weight operand, the
 // scale counts
 static int check_packed_conv(const qe_conv_shape *sh, const qe_qparam *x, const qe_qparam *w)
@@ -130,16 +123,33 @@ extern "C" const char *qe_target_arch(void) { return "gfx950"; }
 
 // ---- packed-activation convolutions: every entry point plans once (plan_conv, qe_conv_plan.hip) and reads the plan ----
 namespace qe {
+// The plan of a dense request.  What the entry points differ in: the consumer (rq, NULL: none), the residual block end and
+// the destinations (a query passes NULL for the ones it does not know).
+static ConvPlan plan_request(const qe_conv_shape *sh, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq = nullptr,
+                             bool residual = false, const float *out = nullptr, const uint8_t *codes = nullptr)
+{
+    ConvRequest r{sh, x, w, reinterpret_cast<uintptr_t>(out), reinterpret_cast<uintptr_t>(codes)};
+    if (rq != nullptr) { r.rq_bits = rq->n_bits; r.rq_n_param = rq->n_param; }
+    r.residual = residual;
+    return plan_conv(r);
+}
 // a request that names only the operands' bits (workspace queries)
 static ConvPlan plan_bits(const qe_conv_shape *sh, int x_bits, int w_bits)
 {
     qe_qparam x{}, w{};
     x.n_bits = x_bits; x.n_param = 1;
     w.n_bits = w_bits; w.n_param = 1;
-    return plan_conv({sh, &x, &w});
+    return plan_request(sh, &x, &w);
 }
 // scratch of a run on a prepared buffer, rounded up to 256 bytes (the two-pass epilogues put the fp32 y behind it)
 static size_t scratch_bytes(const ConvPlan &p) { return (p.m.total - p.m.prep_total + 255) / 256 * 256; }
+// the fp32 y of a two-pass epilogue, behind the conv scratch; NULL: the workspace holds less than both (a non-empty output
+// has y_bytes > 0, so a NULL workspace never passes)
+static float *two_pass_y(const ConvPlan &p, void *workspace, size_t workspace_bytes)
+{
+    if (workspace == nullptr || workspace_bytes < scratch_bytes(p) + p.y_bytes) return nullptr;
+    return reinterpret_cast<float *>(static_cast<uint8_t *>(workspace) + scratch_bytes(p));
+}
 }  // namespace qe
 
 extern "C" size_t qe_quantconv2d_workspace_bytes(const qe_conv_shape *shape, int x_bits, int w_bits)
@@ -151,7 +161,7 @@ extern "C" size_t qe_quantconv2d_workspace_bytes(const qe_conv_shape *shape, int
 extern "C" int qe_quantconv2d_path(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w)
 {
     if (qe::check_shape(shape) != QE_OK || x == nullptr || w == nullptr) return 0;
-    return qe::plan_conv({shape, x, w}).route != qe::ConvRoute::Generic ? 1 : 0;
+    return qe::plan_request(shape, x, w).route != qe::ConvRoute::Generic ? 1 : 0;
 }
 
 // the plan of a request, field by field (tests, bench, profiles): decides nothing, reads no knob of its own
@@ -160,9 +170,7 @@ extern "C" int qe_quantconv2d_plan_info(const qe_conv_shape *shape, const qe_qpa
 {
     using namespace qe;
     if (check_shape(shape) != QE_OK || x == nullptr || w == nullptr || info == nullptr) return QE_ERR_ARG;
-    ConvRequest r{shape, x, w, reinterpret_cast<uintptr_t>(out), reinterpret_cast<uintptr_t>(codes)};
-    if (rq != nullptr) { r.rq_bits = rq->n_bits; r.rq_n_param = rq->n_param; }
-    const ConvPlan p = plan_conv(r);
+    const ConvPlan p = plan_request(shape, x, w, rq, false, out, codes);
     const MfmaPlan &m = p.m;
     const bool mfma = p.route == ConvRoute::Mfma;
     qe_conv_plan_info i{};
@@ -204,9 +212,9 @@ extern "C" int qe_quantconv2d(const qe_qparam *x, const qe_qparam *w, const floa
     if (rc != QE_OK) return rc;
     if (out == nullptr) return QE_ERR_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const ConvPlan p = plan_conv({shape, x, w, reinterpret_cast<uintptr_t>(out)});
+    const ConvPlan p = plan_request(shape, x, w, nullptr, false, out);
     if (p.route == ConvRoute::Generic) return launch_conv_generic(true, x->data, x, w, bias, shape, out, s);
-    return launch_conv_mfma(p, x, w, bias, shape, out, workspace, workspace_bytes, nullptr, 0, false, s, nullptr, nullptr);
+    return launch_conv_mfma(p, x, w, bias, shape, out, workspace, workspace_bytes, nullptr, 0, false, s, nullptr, nullptr, nullptr, nullptr);
 }
 
 extern "C" size_t qe_conv_prepared_bytes(const qe_conv_shape *shape, int x_bits, int w_bits)
@@ -250,43 +258,25 @@ extern "C" int qe_quantconv2d_prepared(const qe_qparam *x, const qe_qparam *w, c
     if (rc != QE_OK) return rc;
     if (out == nullptr) return QE_ERR_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const ConvPlan p = plan_conv({shape, x, w, reinterpret_cast<uintptr_t>(out)});
+    const ConvPlan p = plan_request(shape, x, w, nullptr, false, out);
     if (p.route == ConvRoute::Generic)   // per-channel activation scales: nothing is prepared
         return launch_conv_generic(true, x->data, x, w, bias, shape, out, s);
     return launch_conv_mfma(p, x, w, bias, shape, out, workspace, workspace_bytes, prepared, prepared_bytes, true, s, nullptr,
-                            nullptr);
+                            nullptr, nullptr, nullptr);
 }
 
 // ---- fused re-quantisation (conv-epilogue form) ----
-static int check_requant(const qe_requant *rq)
-{
-    if (rq == nullptr || rq->scale == nullptr || rq->zero == nullptr) return QE_ERR_ARG;
-    if (!(rq->n_bits > 0 && rq->n_bits <= 8)) return QE_ERR_NBITS;
-    if (rq->n_param < 1) return QE_ERR_ARG;
-    return QE_OK;
-}
-
-static qe::ConvPlan plan_requant(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq,
-                                 const uint8_t *out)
-{
-    qe::ConvRequest r{shape, x, w};
-    r.rq_out = reinterpret_cast<uintptr_t>(out);
-    r.rq_bits = rq->n_bits;
-    r.rq_n_param = rq->n_param;
-    return qe::plan_conv(r);
-}
-
 extern "C" int qe_quantconv2d_requant_path(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq)
 {
     if (qe::check_shape(shape) != QE_OK || x == nullptr || w == nullptr || rq == nullptr) return 0;
-    return plan_requant(shape, x, w, rq, nullptr).fused ? 1 : 0;
+    return qe::plan_request(shape, x, w, rq).fused ? 1 : 0;
 }
 
 extern "C" size_t qe_quantconv2d_requant_workspace_bytes(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w,
                                                          const qe_requant *rq)
 {
     if (qe::check_shape(shape) != QE_OK || x == nullptr || w == nullptr || rq == nullptr) return 0;
-    const qe::ConvPlan p = plan_requant(shape, x, w, rq, nullptr);
+    const qe::ConvPlan p = qe::plan_request(shape, x, w, rq);
     return p.fused ? qe::scratch_bytes(p) : qe::scratch_bytes(p) + p.y_bytes;
 }
 
@@ -301,19 +291,16 @@ extern "C" int qe_quantconv2d_requant_prepared(const qe_qparam *x, const qe_qpar
     if ((rc = check_requant(rq)) != QE_OK) return rc;
     if (out == nullptr) return QE_ERR_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const ConvPlan p = plan_requant(shape, x, w, rq, out);
+    const ConvPlan p = plan_request(shape, x, w, rq, false, nullptr, out);
     if (p.OH <= 0 || p.OW <= 0) return QE_ERR_ARG;
     if (shape->N == 0 || shape->OC == 0) return QE_OK;
-    if (p.fused) {
-        const RequantHost rh{out, rq->scale, rq->zero, rq->n_param, rq->qmin, rq->qmax, rq->n_bits, rq->sign, status};
-        return launch_conv_mfma(p, x, w, bias, shape, nullptr, workspace, workspace_bytes, prepared, prepared_bytes, true, s, &rh,
-                                nullptr);
-    }
+    if (p.fused)
+        return launch_conv_mfma(p, x, w, bias, shape, nullptr, workspace, workspace_bytes, prepared, prepared_bytes, true, s, rq,
+                                out, status, nullptr);
     // two passes: y in fp32 behind the conv scratch, then the fused quantise + pack kernel (bit-identical by construction)
-    const size_t conv_ws = scratch_bytes(p);
-    if (workspace == nullptr || workspace_bytes < conv_ws + p.y_bytes) return QE_ERR_WORKSPACE;
-    float *y = reinterpret_cast<float *>(static_cast<uint8_t *>(workspace) + conv_ws);
-    rc = qe_quantconv2d_prepared(x, w, bias, shape, prepared, prepared_bytes, y, workspace, conv_ws, stream);
+    float *y = two_pass_y(p, workspace, workspace_bytes);
+    if (y == nullptr) return QE_ERR_WORKSPACE;
+    rc = qe_quantconv2d_prepared(x, w, bias, shape, prepared, prepared_bytes, y, workspace, scratch_bytes(p), stream);
     if (rc != QE_OK) return rc;
     const int64_t plane = (int64_t)p.OH * p.OW;
     return qe_quantize_pack(y, (int64_t)shape->N * shape->OC * plane, rq->scale, rq->zero, rq->n_param, plane, rq->qmin,
@@ -321,27 +308,17 @@ extern "C" int qe_quantconv2d_requant_prepared(const qe_qparam *x, const qe_qpar
 }
 
 // ---- residual block end: out = relu(conv + identity), optionally with the consumer's codes ----
-static qe::ConvPlan plan_residual(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq,
-                                  const float *out, const uint8_t *codes)
-{
-    qe::ConvRequest r{shape, x, w, reinterpret_cast<uintptr_t>(out), reinterpret_cast<uintptr_t>(codes)};
-    r.rq_bits = rq ? rq->n_bits : 0;
-    r.rq_n_param = rq ? rq->n_param : 1;
-    r.residual = true;
-    return qe::plan_conv(r);
-}
-
 extern "C" int qe_quantconv2d_residual_path(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w, const qe_requant *rq)
 {
     if (qe::check_shape(shape) != QE_OK || x == nullptr || w == nullptr) return 0;
-    return plan_residual(shape, x, w, rq, nullptr, nullptr).fused ? 1 : 0;
+    return qe::plan_request(shape, x, w, rq, true).fused ? 1 : 0;
 }
 
 extern "C" size_t qe_quantconv2d_residual_workspace_bytes(const qe_conv_shape *shape, const qe_qparam *x, const qe_qparam *w,
                                                           const qe_requant *rq)
 {
     if (qe::check_shape(shape) != QE_OK || x == nullptr || w == nullptr) return 0;
-    const qe::ConvPlan p = plan_residual(shape, x, w, rq, nullptr, nullptr);
+    const qe::ConvPlan p = qe::plan_request(shape, x, w, rq, true);
     return p.fused ? 0 : qe::scratch_bytes(p) + p.y_bytes;   // the fused kernel reads no scratch
 }
 
@@ -360,27 +337,19 @@ extern "C" int qe_quantconv2d_residual_prepared(const qe_qparam *x, const qe_qpa
     if (((reinterpret_cast<uintptr_t>(identity) | reinterpret_cast<uintptr_t>(out)) & 15) != 0 ||
         (reinterpret_cast<uintptr_t>(codes) & 3) != 0)
         return QE_ERR_ARG;
-    const ConvPlan p = plan_residual(shape, x, w, rq, out, codes);
+    const ConvPlan p = plan_request(shape, x, w, rq, true, out, codes);
     if (p.OH <= 0 || p.OW <= 0) return QE_ERR_ARG;
     const int64_t n = (int64_t)shape->N * shape->OC * p.OH * p.OW;
-    if (out != nullptr && out != identity) {                 // in place is allowed; any other overlap is not
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(out), i0 = reinterpret_cast<uintptr_t>(identity);
-        const uintptr_t bytes = (uintptr_t)n * sizeof(float);
-        if (o0 < i0 + bytes && i0 < o0 + bytes) return QE_ERR_ARG;
-    }
+    if (!same_or_disjoint(out, identity, n * 4)) return QE_ERR_ARG;   // in place is allowed; any other overlap is not
     if (n == 0) return QE_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (p.fused) {
-        if (rq == nullptr) return launch_pwr(p, x, w, bias, out, s, nullptr, identity);
-        const RequantHost rh{codes, rq->scale, rq->zero, rq->n_param, rq->qmin, rq->qmax, rq->n_bits, rq->sign, status};
-        return launch_pwr(p, x, w, bias, out, s, &rh, identity);
-    }
+    if (p.fused) return launch_pwr(p, x, w, bias, out, s, rq, codes, status, identity);
     // two passes: the conv's fp32 y (into out, unless out is NULL or IS the identity: then behind the conv scratch), then
     // one elementwise pass y + identity -> out and codes
-    const size_t conv_ws = scratch_bytes(p);
-    if (workspace_bytes < conv_ws + p.y_bytes || (workspace == nullptr && conv_ws + p.y_bytes > 0)) return QE_ERR_WORKSPACE;
-    float *y = (out != nullptr && out != identity) ? out : reinterpret_cast<float *>(static_cast<uint8_t *>(workspace) + conv_ws);
-    rc = qe_quantconv2d_prepared(x, w, bias, shape, prepared, prepared_bytes, y, workspace, conv_ws, stream);
+    float *y = two_pass_y(p, workspace, workspace_bytes);
+    if (y == nullptr) return QE_ERR_WORKSPACE;
+    if (out != nullptr && out != identity) y = out;
+    rc = qe_quantconv2d_prepared(x, w, bias, shape, prepared, prepared_bytes, y, workspace, scratch_bytes(p), stream);
     if (rc != QE_OK) return rc;
     return launch_residual_relu_quant(y, identity, out, n, (int64_t)p.OH * p.OW, rq, codes, status, s);
 }
@@ -467,121 +436,6 @@ extern "C" int qe_quantconv2d_float_input_prepared(const float *x, const qe_qpar
     return qe::launch_conv_f32(p, x, shape, prepared, prepared_bytes, out, s);
 }
 
-// ---------------------------------------------------------------------------------------------
-// Global average pool (bench.py's top-1 tail): a workgroup copies 64 planes (64 * P contiguous floats) into LDS with
-// coalesced 16-byte loads, then 4 threads per plane add up a quarter each (P is small: 49 for ResNet-50) and the
-// quarters are combined with two shuffles.  HBM-bound: 103 MB for (256, 2048, 7, 7).
-// ---------------------------------------------------------------------------------------------
-namespace qe {
-constexpr int AP_PLANES = 64;
-__global__ __launch_bounds__(256) void global_avgpool_kernel(const float *__restrict__ x, float *__restrict__ out,
-                                                             int64_t n_planes, int P)
-{
-    extern __shared__ __attribute__((aligned(16))) float sp[];
-    const int64_t plane0 = (int64_t)blockIdx.x * AP_PLANES;
-    const int np = (int)((n_planes - plane0) < AP_PLANES ? (n_planes - plane0) : AP_PLANES);
-    const int nf = np * P;
-    const float *src = x + plane0 * P;
-    const bool al = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
-    if (al) {
-        for (int i = threadIdx.x * 4; i < nf; i += 256 * 4) {
-            if (i + 4 <= nf) *reinterpret_cast<float4 *>(sp + i) = *reinterpret_cast<const float4 *>(src + i);
-            else for (int j = i; j < nf; ++j) sp[j] = src[j];
-        }
-    } else {
-        for (int i = threadIdx.x; i < nf; i += 256) sp[i] = src[i];
-    }
-    __syncthreads();
-    const int pl = threadIdx.x >> 2, part = threadIdx.x & 3;
-    float sum = 0.0f;
-    if (pl < np) {
-        const int per = (P + 3) >> 2;
-        const int lo = part * per, hi = (lo + per < P) ? lo + per : P;
-        for (int i = lo; i < hi; ++i) sum += sp[pl * P + i];
-    }
-    sum += __shfl_xor(sum, 1);
-    sum += __shfl_xor(sum, 2);
-    if (pl < np && part == 0) out[plane0 + pl] = sum / (float)P;
-}
-}  // namespace qe
-
-extern "C" int qe_global_avgpool(const float *x, int64_t n_planes, int32_t P, float *out, qe_stream_t stream)
-{
-    using namespace qe;
-    if (n_planes < 0 || P <= 0) return QE_ERR_ARG;
-    if (n_planes == 0) return QE_OK;
-    if (x == nullptr || out == nullptr) return QE_ERR_ARG;
-    if ((size_t)AP_PLANES * P * sizeof(float) > 60 * 1024) return QE_ERR_UNSUPPORTED;   // planes of at most 240 pixels
-    const int64_t blocks = (n_planes + AP_PLANES - 1) / AP_PLANES;
-    if (blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(global_avgpool_kernel, dim3((unsigned)blocks), dim3(256), (size_t)AP_PLANES * P * sizeof(float),
-                       static_cast<hipStream_t>(stream), x, out, n_planes, (int)P);
-    QE_LAUNCH_CHECK();
-    return QE_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Max pooling of 8-bit stored codes (the stem's MaxPool2d after its quantised ReLU).  The stored code (q, or q + 128 when
-// signed) is order-preserving and the quantiser is non-decreasing, so max over codes == code of the max.  A thread makes
-// 16 consecutive outputs of the flat (N, C, OH, OW) tensor and stores them as one 16-byte piece where it can; padding
-// taps are skipped (torch pads with -inf).
-// ---------------------------------------------------------------------------------------------
-namespace qe {
-__global__ __launch_bounds__(256) void maxpool2d_codes_kernel(const uint8_t *__restrict__ x, uint8_t *__restrict__ out, int64_t n_out,
-                                                              int H, int W, int OH, int OW, int k, int stride, int pad, int vec)
-{
-    const int64_t o0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 16;
-    if (o0 >= n_out) return;
-    // the first output's (plane, row, column) once (one 64-bit division per 16 outputs), then walked along the row
-    const int64_t plane0 = o0 / ((int64_t)OH * OW);
-    const int rem = (int)(o0 - plane0 * OH * OW);
-    int oh = rem / OW, ow = rem - oh * OW;
-    const uint8_t *xp = x + plane0 * H * W;
-    uint8_t r[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        uint32_t m = 0;
-        if (o0 + j < n_out) {
-            const int h0 = oh * stride - pad, w0 = ow * stride - pad;
-            const int hlo = h0 < 0 ? 0 : h0, hhi = h0 + k < H ? h0 + k : H;
-            const int wlo = w0 < 0 ? 0 : w0, whi = w0 + k < W ? w0 + k : W;
-            for (int ih = hlo; ih < hhi; ++ih)
-                for (int iw = wlo; iw < whi; ++iw) m = max(m, (uint32_t)xp[ih * W + iw]);
-        }
-        r[j] = (uint8_t)m;
-        if (++ow == OW) {
-            ow = 0;
-            if (++oh == OH) { oh = 0; xp += (int64_t)H * W; }
-        }
-    }
-    if (vec && o0 + 16 <= n_out) {
-        uint4 v;
-        __builtin_memcpy(&v, r, 16);
-        *reinterpret_cast<uint4 *>(out + o0) = v;
-    } else {
-        for (int j = 0; j < 16 && o0 + j < n_out; ++j) out[o0 + j] = r[j];
-    }
-}
-}  // namespace qe
-
-extern "C" int qe_maxpool2d_codes(const uint8_t *x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t kernel, int32_t stride,
-                                  int32_t padding, uint8_t *out, qe_stream_t stream)
-{
-    using namespace qe;
-    if (N < 0 || C < 0 || H <= 0 || W <= 0 || kernel <= 0 || stride <= 0 || padding < 0 || 2 * padding > kernel) return QE_ERR_ARG;
-    const int OH = (H + 2 * padding - kernel) / stride + 1, OW = (W + 2 * padding - kernel) / stride + 1;
-    if (H + 2 * padding < kernel || W + 2 * padding < kernel || OH <= 0 || OW <= 0) return QE_ERR_ARG;
-    const int64_t n_out = (int64_t)N * C * OH * OW;
-    if (n_out == 0) return QE_OK;
-    if (x == nullptr || out == nullptr) return QE_ERR_ARG;
-    const int64_t blocks = (n_out + 16 * 256 - 1) / (16 * 256);
-    if (blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(maxpool2d_codes_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x, out, n_out,
-                       (int)H, (int)W, OH, OW, (int)kernel, (int)stride, (int)padding, (reinterpret_cast<uintptr_t>(out) & 15) == 0 ? 1 : 0);
-    QE_LAUNCH_CHECK();
-    return QE_OK;
-}
-
 // ---- depthwise and grouped packed convolutions (qe_conv_dw.hip, qe_conv_grp.hip) ----
 // A depthwise request is a grouped request with groups == IC == OC, so the two entry families share one request check and
 // one run path.  A family supplies what differs: its plan (every query and the launch read one plan: plan_dw / plan_grp),
@@ -622,22 +476,17 @@ static int check_span_request(bool depthwise, const qe_conv_shape *shape, int gr
     int rc = check_shape(shape);
     if (rc != QE_OK) return rc;
     if (x == nullptr || w == nullptr) return QE_ERR_ARG;
-    if (!(x->n_bits > 0 && x->n_bits <= 8) || !(w->n_bits > 0 && w->n_bits <= 8)) return QE_ERR_NBITS;
-    if (rq != nullptr && !(rq->n_bits > 0 && rq->n_bits <= 8)) return QE_ERR_NBITS;
+    if (!bits_ok(x->n_bits) || !bits_ok(w->n_bits) || (rq != nullptr && !bits_ok(rq->n_bits))) return QE_ERR_NBITS;
     if (depthwise) {
         if (shape->OC != shape->IC) return QE_ERR_UNSUPPORTED;
     } else if (groups < 1 || shape->OC < 1 || shape->IC % groups != 0 || shape->OC % groups != 0) {
         return QE_ERR_ARG;
     }
-    if (!(x->n_param == 1 || x->n_param == shape->IC) || !(w->n_param == 1 || w->n_param == shape->OC)) return QE_ERR_ARG;
-    if (rq != nullptr && !(rq->n_param == 1 || rq->n_param == shape->OC)) return QE_ERR_ARG;
+    if (!one_or_per_channel(x->n_param, shape->IC) || !one_or_per_channel(w->n_param, shape->OC)) return QE_ERR_ARG;
+    if (rq != nullptr && !one_or_per_channel(rq->n_param, shape->OC)) return QE_ERR_ARG;
     if (!depthwise && (groups == 1 || (groups == shape->IC && groups == shape->OC))) return QE_ERR_UNSUPPORTED;
     return QE_OK;
 }
-
-struct Span { uintptr_t lo, hi; };
-static Span span_of(const void *p, int64_t bytes) { return Span{reinterpret_cast<uintptr_t>(p), reinterpret_cast<uintptr_t>(p) + (uintptr_t)bytes}; }
-static bool overlaps(const Span &a, const Span &b) { return a.lo != 0 && b.lo != 0 && a.lo < b.hi && b.lo < a.hi; }
 
 // 1 = the family's fast kernels, 0 = its plain kernel, -1 = none
 template <class F>
@@ -686,12 +535,7 @@ static int run_span_conv(const qe_qparam *x, const qe_qparam *w, const float *bi
                          span_of(w->scale, 4 * (int64_t)w->n_param), span_of(w->zero, 4 * (int64_t)w->n_param),
                          span_of(bias, 4 * (int64_t)OC), span_of(rq ? rq->scale : nullptr, rq ? 4 * (int64_t)rq->n_param : 0),
                          span_of(rq ? rq->zero : nullptr, rq ? 4 * (int64_t)rq->n_param : 0)};
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 9; ++j)
-            if (overlaps(outs[i], ins[j])) return QE_ERR_ARG;
-        for (int j = i + 1; j < 3; ++j)
-            if (overlaps(outs[i], outs[j])) return QE_ERR_ARG;
-    }
+    if (!outputs_clear(outs, 3, ins, 9)) return QE_ERR_ARG;
     if (n == 0) return QE_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (p.two_pass) {
@@ -752,19 +596,19 @@ extern "C" int qe_quantconv2d_grouped(const qe_qparam *x, const qe_qparam *w, co
 // The module forms check their request here and hand it to one launcher each; the codes-domain average pool plans once
 // (plan_pool, qe_pool.hpp) and the path query and the call read that plan.
 namespace qe {
-// x, out and the layer's quantiser of a module form: n elements in, n_out out, `channels` planes' worth of scales (0: any count)
+// x, out and the layer's quantiser of a module form: n elements in, n_out out, `channels` planes' worth of scales (0: any count);
+// in_place_ok (n_in == n_out): out may be x itself
 static int check_module_form(const float *x, int64_t n_in, const qe_requant *rq, float *out, int64_t n_out, int channels, bool in_place_ok)
 {
     if (rq == nullptr || rq->scale == nullptr || rq->zero == nullptr || rq->n_param < 1) return QE_ERR_ARG;
-    if (channels > 0 && !(rq->n_param == 1 || rq->n_param == channels)) return QE_ERR_ARG;
+    if (channels > 0 && !one_or_per_channel(rq->n_param, channels)) return QE_ERR_ARG;
     if (n_out == 0) return QE_OK;
     if (x == nullptr || out == nullptr) return QE_ERR_ARG;
     if ((reinterpret_cast<uintptr_t>(x) & 3) != 0 || (reinterpret_cast<uintptr_t>(out) & 3) != 0) return QE_ERR_ARG;
     const Span o = span_of(out, n_out * 4);
-    if (!(in_place_ok && x == out) && overlaps(o, span_of(x, n_in * 4))) return QE_ERR_ARG;
-    if (overlaps(o, span_of(rq->scale, 4 * (int64_t)rq->n_param)) || overlaps(o, span_of(rq->zero, 4 * (int64_t)rq->n_param)))
-        return QE_ERR_ARG;
-    return QE_OK;
+    if (in_place_ok ? !same_or_disjoint(x, out, n_out * 4) : overlaps(o, span_of(x, n_in * 4))) return QE_ERR_ARG;
+    const Span q[2] = {span_of(rq->scale, 4 * (int64_t)rq->n_param), span_of(rq->zero, 4 * (int64_t)rq->n_param)};
+    return outputs_clear(&o, 1, q, 2) ? QE_OK : QE_ERR_ARG;
 }
 
 static PoolPlan plan_pool_request(const qe_qparam *x, int N, int C, int H, int W, int kernel, int stride, int OH, int OW, const float *out,
@@ -777,10 +621,8 @@ static PoolPlan plan_pool_request(const qe_qparam *x, int N, int C, int H, int W
 static int check_pool_request(const qe_qparam *x, int C, const qe_requant *rq)
 {
     if (x == nullptr) return QE_ERR_ARG;
-    if (!(x->n_bits > 0 && x->n_bits <= 8)) return QE_ERR_NBITS;
-    if (rq != nullptr && !(rq->n_bits > 0 && rq->n_bits <= 8)) return QE_ERR_NBITS;
-    if (!(x->n_param == 1 || x->n_param == C)) return QE_ERR_ARG;
-    if (rq != nullptr && !(rq->n_param == 1 || rq->n_param == C)) return QE_ERR_ARG;
+    if (!bits_ok(x->n_bits) || (rq != nullptr && !bits_ok(rq->n_bits))) return QE_ERR_NBITS;
+    if (!one_or_per_channel(x->n_param, C) || (rq != nullptr && !one_or_per_channel(rq->n_param, C))) return QE_ERR_ARG;
     return QE_OK;
 }
 }  // namespace qe
@@ -798,9 +640,8 @@ extern "C" int qe_quant_maxpool2d(const float *x, int32_t N, int32_t C, int32_t 
                                   int32_t padding, const qe_requant *rq, float *out, qe_stream_t stream)
 {
     using namespace qe;
-    if (N < 0 || C < 0 || H <= 0 || W <= 0 || kernel <= 0 || stride <= 0 || padding < 0 || 2 * padding > kernel) return QE_ERR_ARG;
-    const int OH = (H + 2 * padding - kernel) / stride + 1, OW = (W + 2 * padding - kernel) / stride + 1;
-    if (H + 2 * padding < kernel || W + 2 * padding < kernel || OH <= 0 || OW <= 0) return QE_ERR_ARG;
+    int OH, OW;
+    if (check_pool_window(N, C, H, W, kernel, stride, padding, OH, OW) != QE_OK) return QE_ERR_ARG;
     if ((int64_t)H * W > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
     const int64_t n_in = (int64_t)N * C * H * W, n = (int64_t)N * C * OH * OW;
     const int rc = check_module_form(x, n_in, rq, out, n, C, false);
@@ -847,12 +688,7 @@ extern "C" int qe_avgpool2d_codes(const qe_qparam *x, int32_t N, int32_t C, int3
     const Span ins[5] = {span_of(x->data, n_in), span_of(x->scale, 4 * (int64_t)x->n_param), span_of(x->zero, 4 * (int64_t)x->n_param),
                          span_of(rq ? rq->scale : nullptr, rq ? 4 * (int64_t)rq->n_param : 0),
                          span_of(rq ? rq->zero : nullptr, rq ? 4 * (int64_t)rq->n_param : 0)};
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 5; ++j)
-            if (overlaps(outs[i], ins[j])) return QE_ERR_ARG;
-        for (int j = i + 1; j < 3; ++j)
-            if (overlaps(outs[i], outs[j])) return QE_ERR_ARG;
-    }
+    if (!outputs_clear(outs, 3, ins, 5)) return QE_ERR_ARG;
     if (n == 0) return QE_OK;
     return launch_pool_codes(p, x, N, C, H, W, kernel, stride, relu, out, rq, codes, status, static_cast<hipStream_t>(stream));
 }

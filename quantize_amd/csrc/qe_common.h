@@ -2,7 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "../../include/quant_engine.h"
+#include "qe_request.hpp"          // quant_engine.h and the host-only request checks
 
 namespace qe {
 

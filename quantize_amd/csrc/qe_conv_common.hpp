@@ -53,16 +53,6 @@ inline int64_t tile_grid(int64_t n_units, int per_image, int64_t per_tile, bool 
 }
 
 // ---- fused output quantiser -------------------------------------------------------------------------------------------
-// host-side description (qe_requant of the C ABI + destination)
-struct RequantHost {
-    uint8_t *out;
-    const float *scale, *zero;
-    int n_param;
-    float qmin, qmax;
-    int n_bits, sign;
-    int32_t *status;
-};
-
 // kernel operand (qe_quantconv2d_requant): out != nullptr -> the epilogue stores the 8-bit code of
 // round(y / scale - zero).clamp(qmin, qmax) (1 byte per element, NCHW) instead of the fp32 y
 struct RqArgs {
@@ -73,26 +63,19 @@ struct RqArgs {
     int32_t *status;                   // bit 0 set when a value fails the range test (NaN, or qmin/qmax outside the code range)
 };
 
-inline RqArgs make_rq_args(const RequantHost *rq)
+// from the C ABI's operand: the 8-bit codes of rq into `codes`, the range flag into `status`; rq or codes NULL: no codes
+inline RqArgs make_rq_args(const qe_requant *rq, uint8_t *codes, int32_t *status)
 {
     RqArgs a;
     a.out = nullptr; a.scale = nullptr; a.zero = nullptr; a.status = nullptr;
     a.qmin = a.qmax = a.lo = a.hi = 0.0f; a.offset = 0;
-    if (rq != nullptr) {
-        a.out = rq->out; a.scale = rq->scale; a.zero = rq->zero;
-        a.qmin = rq->qmin; a.qmax = rq->qmax; a.status = rq->status;
-        a.offset = rq->sign ? 128u : 0u;                       // tpack.cu:108-111
-        a.lo = rq->sign ? -128.0f : 0.0f; a.hi = rq->sign ? 127.0f : 255.0f;
+    if (rq != nullptr && codes != nullptr) {
+        const CodeRange cr = code_range(8, rq->sign);          // the epilogues store whole bytes
+        a.out = codes; a.scale = rq->scale; a.zero = rq->zero;
+        a.qmin = rq->qmin; a.qmax = rq->qmax; a.status = status;
+        a.offset = cr.offset; a.lo = cr.lo; a.hi = cr.hi;
     }
     return a;
-}
-
-// the same from the C ABI's operand: the 8-bit codes of rq into `codes`; rq or codes NULL: no codes
-inline RqArgs make_rq_args(const qe_requant *rq, uint8_t *codes, int32_t *status)
-{
-    if (rq == nullptr || codes == nullptr) return make_rq_args(nullptr);
-    const RequantHost rh{codes, rq->scale, rq->zero, rq->n_param, rq->qmin, rq->qmax, rq->n_bits, rq->sign, status};
-    return make_rq_args(&rh);
 }
 
 // y -> stored 8-bit code with the arithmetic of the fused quantise+pack kernel (qe_tpack.hip tp_quantize + tp_code):

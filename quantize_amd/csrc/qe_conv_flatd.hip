@@ -408,11 +408,11 @@ static void launch_fd(const FlatdArgs &a, int64_t blocks, hipStream_t s)
 
 // p.route == Flatd: 8-wave workgroups when p.fd_w8; rq != nullptr: the re-quantising instances
 int launch_flatd(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, float *out, hipStream_t s,
-                 const RequantHost *rq)
+                 const qe_requant *rq, uint8_t *codes, int32_t *status)
 {
     const qe_conv_shape *sh = &p.run;
     FlatdArgs a;
-    a.rq = make_rq_args(rq);
+    a.rq = make_rq_args(rq, codes, status);
     a.x = static_cast<const uint8_t *>(x->data); a.w = static_cast<const uint8_t *>(w->data);
     a.x_scale = x->scale; a.x_zero = x->zero; a.w_scale = w->scale; a.w_zero = w->zero; a.bias = bias;
     a.x_sign = x->sign; a.w_sign = w->sign; a.w_per_tensor = (w->n_param == 1);

@@ -395,10 +395,10 @@ MfmaLaunch mfma_instance(const MfmaPlan &m, int KW, int split, bool rq, bool pat
 
 // use_prepared = false: workspace = [prepared part | scratch], the tables are rebuilt on every call; true: the tables are
 // in `prepared` (qe_conv_prepare) and the workspace holds the scratch only.  rq != nullptr: the plan's fused
-// re-quantisation (codes into rq->out instead of fp32 into `out`); res != nullptr: its fused residual block end.
+// re-quantisation (codes into `codes`, the range flag into `status`, instead of fp32 into `out`); res != nullptr: its fused residual block end.
 int launch_conv_mfma(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *sh,
                      float *out, void *workspace, size_t workspace_bytes, const void *prepared, size_t prepared_bytes,
-                     bool use_prepared, hipStream_t s, const RequantHost *rq, const float *res)
+                     bool use_prepared, hipStream_t s, const qe_requant *rq, uint8_t *codes, int32_t *status, const float *res)
 {
     const MfmaPlan &m = p.m;
     uint8_t *wsp = static_cast<uint8_t *>(workspace);
@@ -466,8 +466,8 @@ int launch_conv_mfma(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, 
     if (m.sub) xr.data = wsp + sub_off;
     if (m.sub_x4 || m.expand) { xr.n_bits = 8; xr.sign = 1; }
 
-    if (p.route == ConvRoute::Pwr || p.route == ConvRoute::Pwr7) return launch_pwr(p, &xr, w, bias, out, s, rq, res);
-    if (p.route == ConvRoute::Flatd) return launch_flatd(p, &xr, w, bias, out, s, rq);
+    if (p.route == ConvRoute::Pwr || p.route == ConvRoute::Pwr7) return launch_pwr(p, &xr, w, bias, out, s, rq, codes, status, res);
+    if (p.route == ConvRoute::Flatd) return launch_flatd(p, &xr, w, bias, out, s, rq, codes, status);
 
     // the MFMA families; without a prepared buffer the tables are rebuilt in the workspace first (the flat kernels with
     // 8-bit weights read the packed tensor and build their constants themselves: no tables)
@@ -494,7 +494,7 @@ int launch_conv_mfma(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, 
     a.dbg = g_mfma_dbg;
     a.w_raw = w->data; a.w_scale = w->scale; a.w_zero = w->zero; a.x_scale = xr.scale; a.bias = bias;
     a.w_bits = w->n_bits; a.w_sign = w->sign; a.w_per_tensor = (w->n_param == 1);
-    a.rq = make_rq_args(rq);
+    a.rq = make_rq_args(rq, codes, status);
     a.rq_patch = p.rq_patch ? 1 : 0;
     const MfmaLaunch launch = mfma_instance(m, rs->KW, p.split, rq != nullptr, p.rq_patch);
     if (launch == nullptr) return QE_ERR_UNSUPPORTED;       // never for a plan of plan_conv

@@ -104,16 +104,17 @@ MfmaLaunch mfma_instance(const MfmaPlan &m, int KW, int split, bool rq, bool pat
 // tap form of an instance: 1 (1x1), 9 (3x3) or 0 (any other kernel size); only the halo family branches on it
 inline int mfma_kkt(int KK, int KW) { return KK == 1 ? 1 : ((KK == 9 && KW == 3) ? 9 : 0); }
 
-// launchers of the routes (the plan was made for these operands)
+// launchers of the routes (the plan was made for these operands).  rq != NULL: the re-quantising instances, which store the
+// consumer's 8-bit codes into `codes` and the range flag into `status`
 int launch_conv_mfma(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, const qe_conv_shape *sh,
                      float *out, void *workspace, size_t workspace_bytes, const void *prepared, size_t prepared_bytes,
-                     bool use_prepared, hipStream_t s, const RequantHost *rq, const float *res);
+                     bool use_prepared, hipStream_t s, const qe_requant *rq, uint8_t *codes, int32_t *status, const float *res);
 int prepare_conv_tables(const MfmaPlan &p, const qe_qparam *w, const float *bias, const qe_conv_shape *sh, void *prepared,
                         size_t prepared_bytes, hipStream_t s);
 int launch_pwr(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, float *out, hipStream_t s,
-               const RequantHost *rq, const float *res);
+               const qe_requant *rq, uint8_t *codes, int32_t *status, const float *res);
 int launch_flatd(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, float *out, hipStream_t s,
-                 const RequantHost *rq);
+                 const qe_requant *rq, uint8_t *codes, int32_t *status);
 
 // ---- float-input convolution (fp32 activations x packed weights, qe_conv_f32.hip) -------------------------------------
 // plan_conv_f32 is the only reader of QE_F32_MFMA (0: every shape stays on the VALU kernel) and decides the rest by shape.

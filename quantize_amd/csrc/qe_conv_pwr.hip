@@ -934,12 +934,12 @@ static void launch_pwr_tile(const PwrArgs &a, bool s2, bool rq, bool res, int64_
 
 // p.route == Pwr7: 7x7 planes, p.pwr7_gi images per tile (the residual block end: the 512-channel form only)
 static void launch_pwr7(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, float *out, hipStream_t s,
-                        const RequantHost *rq, const float *res)
+                        const qe_requant *rq, uint8_t *codes, int32_t *status, const float *res)
 {
     const qe_conv_shape *sh = &p.run;
     PwrArgs a;
     a.res = res;
-    a.rq = make_rq_args(rq);
+    a.rq = make_rq_args(rq, codes, status);
     a.W_in = 7; a.PIN = 49; a.OW = 7;
     a.x = static_cast<const uint8_t *>(x->data); a.w = static_cast<const uint8_t *>(w->data);
     a.x_scale = x->scale; a.x_zero = x->zero; a.w_scale = w->scale; a.w_zero = w->zero; a.bias = bias;
@@ -960,17 +960,17 @@ static void launch_pwr7(const ConvPlan &p, const qe_qparam *x, const qe_qparam *
 
 // res != nullptr: the residual block end (RES instances, stride 1 only): out (may be NULL when rq) = relu(y + res)
 int launch_pwr(const ConvPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, float *out, hipStream_t s,
-               const RequantHost *rq, const float *res)
+               const qe_requant *rq, uint8_t *codes, int32_t *status, const float *res)
 {
     if (p.route == ConvRoute::Pwr7) {
-        launch_pwr7(p, x, w, bias, out, s, rq, res);
+        launch_pwr7(p, x, w, bias, out, s, rq, codes, status, res);
         QE_LAUNCH_CHECK();
         return QE_OK;
     }
     const qe_conv_shape *sh = &p.run;
     PwrArgs a;
     a.res = res;
-    a.rq = make_rq_args(rq);
+    a.rq = make_rq_args(rq, codes, status);
     a.x = static_cast<const uint8_t *>(x->data); a.w = static_cast<const uint8_t *>(w->data);
     a.x_scale = x->scale; a.x_zero = x->zero; a.w_scale = w->scale; a.w_zero = w->zero; a.bias = bias;
     a.x_sign = x->sign; a.w_sign = w->sign; a.w_per_tensor = (w->n_param == 1);

@@ -49,6 +49,13 @@ struct QeRq {
     unsigned offset, mask;       // stored code = (q + offset) & mask
 };
 
+// the kernel operand of the C ABI's quantiser, as qe_quantize_pack describes its codes
+inline QeRq make_qe_rq(const qe_requant &r)
+{
+    const CodeRange cr = code_range(r.n_bits, r.sign);
+    return QeRq{r.scale, r.zero, r.qmin, r.qmax, cr.lo, cr.hi, cr.offset, cr.mask};
+}
+
 // v -> stored code of a per-tensor quantiser with the arithmetic of qe_quantize_pack (bit-identical)
 __device__ __forceinline__ unsigned qe_rq_code(float v, float sc, float zr, const QeRq &q, bool &bad)
 {

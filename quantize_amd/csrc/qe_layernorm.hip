@@ -109,17 +109,6 @@ static int launch_layernorm(const LnArgs &a, hipStream_t s)
     return QE_OK;
 }
 
-static QeRq ln_rq(const qe_requant &r)
-{
-    QeRq q;
-    q.scale = r.scale; q.zero = r.zero; q.qmin = r.qmin; q.qmax = r.qmax;
-    q.offset = r.sign ? (1u << (r.n_bits - 1)) : 0u;
-    q.mask = (1u << r.n_bits) - 1u;
-    q.lo = r.sign ? -(float)(1 << (r.n_bits - 1)) : 0.0f;
-    q.hi = r.sign ? (float)((1 << (r.n_bits - 1)) - 1) : (float)((1 << r.n_bits) - 1);
-    return q;
-}
-
 // ---------------------------------------------------------------------------------------------
 // qe_quantize_patchify: a thread owns 8 consecutive elements of the patch matrix (b whole bytes of the packed stream).
 // With p % 8 == 0 the 8 elements are 8 consecutive pixels of one image row: two 16-byte loads.
@@ -217,8 +206,8 @@ extern "C" int qe_layernorm_quantize_pack(const float *x, int64_t rows, int32_t 
           reinterpret_cast<uintptr_t>(ln_out)) & 15) != 0)
         return QE_ERR_ARG;
     for (int k = 0; k < n_out; ++k) {
-        if (!(rq[k].n_bits > 0 && rq[k].n_bits <= 8)) return QE_ERR_NBITS;
-        if (codes[k] == nullptr || rq[k].scale == nullptr || rq[k].zero == nullptr || (rq[k].n_param != 1 && rq[k].n_param != E))
+        if (!bits_ok(rq[k].n_bits)) return QE_ERR_NBITS;
+        if (codes[k] == nullptr || rq[k].scale == nullptr || rq[k].zero == nullptr || !one_or_per_channel(rq[k].n_param, E))
             return QE_ERR_ARG;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -226,7 +215,7 @@ extern "C" int qe_layernorm_quantize_pack(const float *x, int64_t rows, int32_t 
     a.x = x; a.gamma = gamma; a.beta = beta; a.ln = ln_out; a.status = status; a.rows = rows; a.E = E; a.eps = eps;
     if (qe_layernorm_quantize_pack_path(rows, E, n_out, rq, codes)) {
         a.n_out = n_out;
-        for (int k = 0; k < n_out; ++k) { a.codes[k] = codes[k]; a.rq[k] = ln_rq(rq[k]); }
+        for (int k = 0; k < n_out; ++k) { a.codes[k] = codes[k]; a.rq[k] = make_qe_rq(rq[k]); }
         return launch_layernorm(a, s);
     }
     // path 0: the fp32 LayerNorm, then quantize_pack per consumer (per-column rq: channel of element i = i % E)
@@ -250,9 +239,9 @@ extern "C" int qe_quantize_patchify(const float *x, int32_t N, int32_t C, int32_
                                     int32_t *status, qe_stream_t stream)
 {
     using namespace qe;
-    if (!(n_bits > 0 && n_bits <= 8)) return QE_ERR_NBITS;
+    if (!bits_ok(n_bits)) return QE_ERR_NBITS;
     if (N < 0 || C <= 0 || H <= 0 || W <= 0 || patch <= 0 || H % patch != 0 || W % patch != 0) return QE_ERR_ARG;
-    if (n_param != 1 && n_param != C) return QE_ERR_ARG;
+    if (!one_or_per_channel(n_param, C)) return QE_ERR_ARG;
     if (N == 0) return QE_OK;
     if (x == nullptr || out == nullptr || scale == nullptr || zero == nullptr) return QE_ERR_ARG;
     PatchArgs a = {};
@@ -263,8 +252,7 @@ extern "C" int qe_quantize_patchify(const float *x, int32_t N, int32_t C, int32_
     a.n = (int64_t)N * a.PP * a.K;
     a.per_ch = n_param > 1;
     a.vec = (patch % 8) == 0 && (W % 4) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-    qe_requant r{scale, zero, n_param, qmin, qmax, n_bits, sign};
-    a.q = ln_rq(r);
+    a.q = make_qe_rq(qe_requant{scale, zero, n_param, qmin, qmax, n_bits, sign});
     a.n_bits = n_bits;
     const int64_t groups = (a.n + 7) / 8;
     const int blocks = (int)std::min<int64_t>((groups + 255) / 256, (int64_t)kNumCU * 32);

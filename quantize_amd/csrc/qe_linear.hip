@@ -1214,25 +1214,13 @@ static LinRequest bf16_input_req(const uint16_t *x, const qe_qparam *w, int64_t 
 // The checks every entry point starts with, in this order
 static int check_lin(const LinRequest &r)
 {
-    const auto check_q = [](const qe_qparam *q, int64_t n_expected) {
-        if (q == nullptr || q->data == nullptr || q->scale == nullptr || q->zero == nullptr) return QE_ERR_ARG;
-        if (!(q->n_bits > 0 && q->n_bits <= 8)) return QE_ERR_NBITS;
-        return q->n_param != 1 && q->n_param != n_expected ? QE_ERR_ARG : QE_OK;
+    const auto check_q = [](const qe_qparam *q, int64_t n_expected) -> int {
+        if (int rc = check_operand(q)) return rc;
+        return one_or_per_channel(q->n_param, n_expected) ? QE_OK : QE_ERR_ARG;
     };
     if (r.B < 0 || r.K < 0 || r.O < 0) return QE_ERR_ARG;
     if (int rc = r.f32_x || r.bf16_x ? QE_OK : check_q(r.x, r.B)) return rc;
     return check_q(r.w, r.O);
-}
-
-static QeRq make_rq(const qe_requant *rq)
-{
-    QeRq q;
-    q.scale = rq->scale; q.zero = rq->zero; q.qmin = rq->qmin; q.qmax = rq->qmax;
-    q.offset = rq->sign ? (1u << (rq->n_bits - 1)) : 0u;         // as launch_tpack_t
-    q.mask = (1u << rq->n_bits) - 1u;
-    q.lo = rq->sign ? -(float)(1 << (rq->n_bits - 1)) : 0.0f;
-    q.hi = rq->sign ? (float)((1 << (rq->n_bits - 1)) - 1) : (float)((1 << rq->n_bits) - 1);
-    return q;
 }
 
 // The kernel arguments of a request whose kernel reads fp32 activations at `xf` (r.xf, or the widened rows in the
@@ -1250,7 +1238,7 @@ static LinArgs lin_args(const LinRequest &r, const float *xf, float *out)
     a.w_bits = r.w->n_bits; a.w_sign = r.w->sign; a.w_per_tensor = r.w->n_param == 1;
     a.B = r.B; a.K = r.K; a.O = r.O; a.out = out; a.dbg = g_mfma_dbg;
     a.res = r.res; a.codes = r.codes; a.status = r.status; a.out16 = r.out16; a.post_scale = r.post_scale;
-    if (r.rq != nullptr) a.rq = make_rq(r.rq);
+    if (r.rq != nullptr) a.rq = make_qe_rq(*r.rq);
     return a;
 }
 
@@ -1324,12 +1312,6 @@ static int run_linear(const LinRequest &r, void *workspace, size_t workspace_byt
     return qe_quantize_pack_act(y, n, r.epi == LIN_CODES_GELU ? QE_ACT_GELU : QE_ACT_NONE, rq->scale, rq->zero, rq->n_param, 1,
                                 rq->qmin, rq->qmax, rq->n_bits, rq->sign, r.codes, nullptr, r.status, stream);
 }
-
-// residual and out: the same buffer or disjoint
-static bool res_overlap_ok(const float *res, const float *out, int64_t n)
-{
-    return res == out || res + n <= out || out + n <= res;
-}
 }  // namespace qe
 
 extern "C" int qe_quantlinear_path(const qe_qparam *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O)
@@ -1390,8 +1372,8 @@ extern "C" int qe_quantlinear_requant(const qe_qparam *x, const qe_qparam *w, co
 {
     using namespace qe;
     if (B < 0 || K < 0 || O < 0 || rq == nullptr || (act != QE_ACT_NONE && act != QE_ACT_GELU)) return QE_ERR_ARG;
-    if (!(rq->n_bits > 0 && rq->n_bits <= 8)) return QE_ERR_NBITS;
-    if (rq->n_param != 1 && rq->n_param != O) return QE_ERR_ARG;
+    if (!bits_ok(rq->n_bits)) return QE_ERR_NBITS;
+    if (!one_or_per_channel(rq->n_param, O)) return QE_ERR_ARG;
     const LinRequest r = requant_req(x, w, B, K, O, rq, codes, act, bias, status);
     if (int rc = check_lin(r)) return rc;
     if (B == 0 || O == 0) return QE_OK;
@@ -1416,7 +1398,7 @@ extern "C" int qe_quantlinear_residual(const qe_qparam *x, const qe_qparam *w, c
     const LinRequest r = residual_req(x, w, B, K, O, bias, residual, out);
     if (int rc = check_lin(r)) return rc;
     if (B == 0 || O == 0) return QE_OK;
-    if (residual == nullptr || out == nullptr || !res_overlap_ok(residual, out, B * (int64_t)O)) return QE_ERR_ARG;
+    if (residual == nullptr || out == nullptr || !same_or_disjoint(residual, out, B * (int64_t)O * 4)) return QE_ERR_ARG;
     return run_linear(r, workspace, workspace_bytes, stream);
 }
 
@@ -1464,7 +1446,7 @@ extern "C" int qe_quantlinear_float_input_residual(const float *x, const qe_qpar
     const LinRequest r = linf_residual_req(x, w, B, K, O, bias, residual, out);
     if (int rc = check_lin(r)) return rc;
     if (B == 0 || O == 0) return QE_OK;
-    if (x == nullptr || residual == nullptr || out == nullptr || !res_overlap_ok(residual, out, B * (int64_t)O)) return QE_ERR_ARG;
+    if (x == nullptr || residual == nullptr || out == nullptr || !same_or_disjoint(residual, out, B * (int64_t)O * 4)) return QE_ERR_ARG;
     return run_linear(r, workspace, workspace_bytes, stream);
 }
 
@@ -1492,10 +1474,8 @@ extern "C" int qe_quantlinear_bf16_input(const uint16_t *x, const qe_qparam *w, 
     if ((reinterpret_cast<uintptr_t>(x) & 1) != 0 || (reinterpret_cast<uintptr_t>(out) & 3) != 0 ||
         (reinterpret_cast<uintptr_t>(residual) & 3) != 0)
         return QE_ERR_ARG;
-    const uintptr_t xlo = reinterpret_cast<uintptr_t>(x), xhi = xlo + (uintptr_t)B * (uintptr_t)K * sizeof(uint16_t);
-    const uintptr_t olo = reinterpret_cast<uintptr_t>(out), ohi = olo + (uintptr_t)B * (uintptr_t)O * sizeof(float);
-    if (xlo < ohi && olo < xhi) return QE_ERR_ARG;
-    if (residual != nullptr && !res_overlap_ok(residual, out, B * (int64_t)O)) return QE_ERR_ARG;
+    if (overlaps(span_of(x, B * (int64_t)K * 2), span_of(out, B * (int64_t)O * 4))) return QE_ERR_ARG;
+    if (residual != nullptr && !same_or_disjoint(residual, out, B * (int64_t)O * 4)) return QE_ERR_ARG;
     return run_linear(r, workspace, workspace_bytes, stream);
 }
 

@@ -6,6 +6,9 @@
 // with the consumer's quantiser fused (rq_value of qe_conv_common.hpp, qe_rq_code of qe_elementwise.hpp: the arithmetic of
 // qe_quantize_pack), in three instances that the host-side plan (qe_pool.hpp) picks.
 //
+// At the end of the file, with their entry points: the two older pooling kernels, qe_global_avgpool (fp32 planes) and
+// qe_maxpool2d_codes (8-bit codes).
+//
 // The contracts are fp32 operation SEQUENCES (include/quant_engine.h), so nothing in this file may be contracted into an fma.
 #include "qe_pool.hpp"
 #include "qe_conv_span.hpp"
@@ -314,15 +317,8 @@ int launch_pool_codes(const PoolPlan &p, const qe_qparam *x, int N, int C, int H
     a.x = x->data; a.xs = x->scale; a.xz = x->zero; a.out = out;
     a.x_pt = x->n_param == 1; a.x_sign = x->sign; a.rq_pt = rq == nullptr || rq->n_param == 1;
     a.rq = make_rq_args(rq, codes, status);
-    a.q = QeRq{nullptr, nullptr, 0.0f, 0.0f, 0.0f, 0.0f, 0u, 0u};
+    a.q = rq != nullptr ? make_qe_rq(*rq) : QeRq{nullptr, nullptr, 0.0f, 0.0f, 0.0f, 0.0f, 0u, 0u};
     a.n_bits = rq != nullptr ? rq->n_bits : 8;
-    if (rq != nullptr) {                                                  // as qe_quantize_pack describes its codes
-        a.q.scale = rq->scale; a.q.zero = rq->zero; a.q.qmin = rq->qmin; a.q.qmax = rq->qmax;
-        a.q.offset = rq->sign ? (1u << (rq->n_bits - 1)) : 0u;
-        a.q.mask = (1u << rq->n_bits) - 1u;
-        a.q.lo = rq->sign ? -(float)(1 << (rq->n_bits - 1)) : 0.0f;
-        a.q.hi = rq->sign ? (float)((1 << (rq->n_bits - 1)) - 1) : (float)((1 << rq->n_bits) - 1);
-    }
     a.C = C; a.H = H; a.W = W; a.OH = p.OH; a.OW = p.OW; a.kernel = kernel; a.stride = stride; a.relu = relu ? 1 : 0;
     a.T = p.T; a.logT = p.logT; a.ncx = p.ncx;
     a.NP = (int64_t)N * C;
@@ -546,3 +542,117 @@ int launch_quant_adaptive_avgpool2d(const float *x, int N, int C, int H, int W, 
 }
 
 }  // namespace qe
+
+// ---------------------------------------------------------------------------------------------
+// Global average pool (bench.py's top-1 tail): a workgroup copies 64 planes (64 * P contiguous floats) into LDS with
+// coalesced 16-byte loads, then 4 threads per plane add up a quarter each (P is small: 49 for ResNet-50) and the
+// quarters are combined with two shuffles.  HBM-bound: 103 MB for (256, 2048, 7, 7).
+// ---------------------------------------------------------------------------------------------
+namespace qe {
+constexpr int AP_PLANES = 64;
+__global__ __launch_bounds__(256) void global_avgpool_kernel(const float *__restrict__ x, float *__restrict__ out,
+                                                             int64_t n_planes, int P)
+{
+    extern __shared__ __attribute__((aligned(16))) float sp[];
+    const int64_t plane0 = (int64_t)blockIdx.x * AP_PLANES;
+    const int np = (int)((n_planes - plane0) < AP_PLANES ? (n_planes - plane0) : AP_PLANES);
+    const int nf = np * P;
+    const float *src = x + plane0 * P;
+    const bool al = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
+    if (al) {
+        for (int i = threadIdx.x * 4; i < nf; i += 256 * 4) {
+            if (i + 4 <= nf) *reinterpret_cast<float4 *>(sp + i) = *reinterpret_cast<const float4 *>(src + i);
+            else for (int j = i; j < nf; ++j) sp[j] = src[j];
+        }
+    } else {
+        for (int i = threadIdx.x; i < nf; i += 256) sp[i] = src[i];
+    }
+    __syncthreads();
+    const int pl = threadIdx.x >> 2, part = threadIdx.x & 3;
+    float sum = 0.0f;
+    if (pl < np) {
+        const int per = (P + 3) >> 2;
+        const int lo = part * per, hi = (lo + per < P) ? lo + per : P;
+        for (int i = lo; i < hi; ++i) sum += sp[pl * P + i];
+    }
+    sum += __shfl_xor(sum, 1);
+    sum += __shfl_xor(sum, 2);
+    if (pl < np && part == 0) out[plane0 + pl] = sum / (float)P;
+}
+}  // namespace qe
+
+extern "C" int qe_global_avgpool(const float *x, int64_t n_planes, int32_t P, float *out, qe_stream_t stream)
+{
+    using namespace qe;
+    if (n_planes < 0 || P <= 0) return QE_ERR_ARG;
+    if (n_planes == 0) return QE_OK;
+    if (x == nullptr || out == nullptr) return QE_ERR_ARG;
+    if ((size_t)AP_PLANES * P * sizeof(float) > 60 * 1024) return QE_ERR_UNSUPPORTED;   // planes of at most 240 pixels
+    const int64_t blocks = (n_planes + AP_PLANES - 1) / AP_PLANES;
+    if (blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(global_avgpool_kernel, dim3((unsigned)blocks), dim3(256), (size_t)AP_PLANES * P * sizeof(float),
+                       static_cast<hipStream_t>(stream), x, out, n_planes, (int)P);
+    QE_LAUNCH_CHECK();
+    return QE_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Max pooling of 8-bit stored codes (the stem's MaxPool2d after its quantised ReLU).  The stored code (q, or q + 128 when
+// signed) is order-preserving and the quantiser is non-decreasing, so max over codes == code of the max.  A thread makes
+// 16 consecutive outputs of the flat (N, C, OH, OW) tensor and stores them as one 16-byte piece where it can; padding
+// taps are skipped (torch pads with -inf).
+// ---------------------------------------------------------------------------------------------
+namespace qe {
+__global__ __launch_bounds__(256) void maxpool2d_codes_kernel(const uint8_t *__restrict__ x, uint8_t *__restrict__ out, int64_t n_out,
+                                                              int H, int W, int OH, int OW, int k, int stride, int pad, int vec)
+{
+    const int64_t o0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 16;
+    if (o0 >= n_out) return;
+    // the first output's (plane, row, column) once (one 64-bit division per 16 outputs), then walked along the row
+    const int64_t plane0 = o0 / ((int64_t)OH * OW);
+    const int rem = (int)(o0 - plane0 * OH * OW);
+    int oh = rem / OW, ow = rem - oh * OW;
+    const uint8_t *xp = x + plane0 * H * W;
+    uint8_t r[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        uint32_t m = 0;
+        if (o0 + j < n_out) {
+            const int h0 = oh * stride - pad, w0 = ow * stride - pad;
+            const int hlo = h0 < 0 ? 0 : h0, hhi = h0 + k < H ? h0 + k : H;
+            const int wlo = w0 < 0 ? 0 : w0, whi = w0 + k < W ? w0 + k : W;
+            for (int ih = hlo; ih < hhi; ++ih)
+                for (int iw = wlo; iw < whi; ++iw) m = max(m, (uint32_t)xp[ih * W + iw]);
+        }
+        r[j] = (uint8_t)m;
+        if (++ow == OW) {
+            ow = 0;
+            if (++oh == OH) { oh = 0; xp += (int64_t)H * W; }
+        }
+    }
+    if (vec && o0 + 16 <= n_out) {
+        uint4 v;
+        __builtin_memcpy(&v, r, 16);
+        *reinterpret_cast<uint4 *>(out + o0) = v;
+    } else {
+        for (int j = 0; j < 16 && o0 + j < n_out; ++j) out[o0 + j] = r[j];
+    }
+}
+}  // namespace qe
+
+extern "C" int qe_maxpool2d_codes(const uint8_t *x, int32_t N, int32_t C, int32_t H, int32_t W, int32_t kernel, int32_t stride,
+                                  int32_t padding, uint8_t *out, qe_stream_t stream)
+{
+    using namespace qe;
+    int OH, OW;
+    if (check_pool_window(N, C, H, W, kernel, stride, padding, OH, OW) != QE_OK) return QE_ERR_ARG;
+    const int64_t n_out = (int64_t)N * C * OH * OW;
+    if (n_out == 0) return QE_OK;
+    if (x == nullptr || out == nullptr) return QE_ERR_ARG;
+    const int64_t blocks = (n_out + 16 * 256 - 1) / (16 * 256);
+    if (blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(maxpool2d_codes_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), x, out, n_out,
+                       (int)H, (int)W, OH, OW, (int)kernel, (int)stride, (int)padding, (reinterpret_cast<uintptr_t>(out) & 15) == 0 ? 1 : 0);
+    QE_LAUNCH_CHECK();
+    return QE_OK;
+}

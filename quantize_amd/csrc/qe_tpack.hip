@@ -260,9 +260,7 @@ static int launch_tpack_t(const void *x, int64_t n, int n_bits, int sign, uint8_
                           const TpQuant q = TpQuant{nullptr, nullptr, 0.0f, 0.0f, 1u, 1u})
 {
     const int64_t n_out = qe_packed_nbytes(n, n_bits);
-    const unsigned offset = sign ? (1u << (n_bits - 1)) : 0u;  // tpack.cu:108-111
-    const float lo = sign ? -(float)(1 << (n_bits - 1)) : 0.0f;
-    const float hi = sign ? (float)((1 << (n_bits - 1)) - 1) : (float)((1 << n_bits) - 1);
+    const CodeRange cr = code_range(n_bits, sign);             // tpack.cu:108-111
     const int64_t n_tiles = (n + TP_TILE - 1) / TP_TILE;
     const int blocks = (int)(n_tiles < TP_MAX_BLOCKS ? n_tiles : TP_MAX_BLOCKS);
     const size_t va = sizeof(Vec4<T>) > 16 ? 16 : sizeof(Vec4<T>);
@@ -272,7 +270,7 @@ static int launch_tpack_t(const void *x, int64_t n, int n_bits, int sign, uint8_
 #define QE_TP_CASE(BITS)                                                                          \
     case BITS:                                                                                    \
         hipLaunchKernelGGL((tpack_kernel<T, BITS, QM>), dim3(blocks), dim3(TP_THREADS), 0, s, xp, out, \
-                           n, n_out, offset, lo, hi, status, in_al, out_al, q);                   \
+                           n, n_out, cr.offset, cr.lo, cr.hi, status, in_al, out_al, q);          \
         break;
     switch (n_bits) {
         QE_TP_CASE(1) QE_TP_CASE(2) QE_TP_CASE(3) QE_TP_CASE(4)
@@ -296,7 +294,7 @@ extern "C" int qe_tpack(const void *x, int dtype, int64_t n, int n_bits, int sig
                         uint8_t *out, int32_t *status, qe_stream_t stream)
 {
     using namespace qe;
-    if (!(n_bits > 0 && n_bits <= 8)) return QE_ERR_NBITS;
+    if (!bits_ok(n_bits)) return QE_ERR_NBITS;
     if (n < 0) return QE_ERR_ARG;
     if (n == 0) return QE_OK;
     if (x == nullptr || out == nullptr) return QE_ERR_ARG;
@@ -319,7 +317,7 @@ extern "C" int qe_quantize_pack(const float *x, int64_t n, const float *scale, c
                                 int32_t *status, qe_stream_t stream)
 {
     using namespace qe;
-    if (!(n_bits > 0 && n_bits <= 8)) return QE_ERR_NBITS;
+    if (!bits_ok(n_bits)) return QE_ERR_NBITS;
     if (n < 0 || n_param < 1) return QE_ERR_ARG;
     if (n == 0) return QE_OK;
     if (x == nullptr || out == nullptr || scale == nullptr || zero == nullptr) return QE_ERR_ARG;
@@ -411,10 +409,8 @@ int launch_residual_relu_quant(const float *y, const float *identity, float *out
             a.q.inner = (uint32_t)inner;
         }
         a.n_bits = rq->n_bits;
-        a.offset = rq->sign ? (1u << (rq->n_bits - 1)) : 0u;     // as launch_tpack_t
-        a.mask = (1u << rq->n_bits) - 1u;
-        a.lo = rq->sign ? -(float)(1 << (rq->n_bits - 1)) : 0.0f;
-        a.hi = rq->sign ? (float)((1 << (rq->n_bits - 1)) - 1) : (float)((1 << rq->n_bits) - 1);
+        const CodeRange cr = code_range(rq->n_bits, rq->sign);
+        a.offset = cr.offset; a.mask = cr.mask; a.lo = cr.lo; a.hi = cr.hi;
     }
     a.vec = ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(identity) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
     const int64_t groups = (n + 7) / 8;
@@ -459,13 +455,13 @@ extern "C" int qe_tunpack(const uint8_t *packed, int64_t n, int n_bits, int sign
                           void *out, qe_stream_t stream)
 {
     using namespace qe;
-    if (!(n_bits > 0 && n_bits <= 8)) return QE_ERR_NBITS;
+    if (!bits_ok(n_bits)) return QE_ERR_NBITS;
     if (n < 0) return QE_ERR_ARG;
     if (n == 0) return QE_OK;
     if (packed == nullptr || out == nullptr) return QE_ERR_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t n_in = qe_packed_nbytes(n, n_bits);
-    const unsigned offset = sign ? (1u << (n_bits - 1)) : 0u;  // tpack.cu:339-342
+    const unsigned offset = code_range(n_bits, sign).offset;   // tpack.cu:339-342
     const int64_t n_tiles = (n + TP_TILE - 1) / TP_TILE;
     const int blocks = (int)(n_tiles < TP_MAX_BLOCKS ? n_tiles : TP_MAX_BLOCKS);
     const int in_al = ((uintptr_t)packed % 16) == 0;
@@ -552,13 +548,13 @@ extern "C" int qe_quantize_pack_act(const float *x, int64_t n, int32_t act, cons
                                     uint8_t *out, float *y, int32_t *status, qe_stream_t stream)
 {
     using namespace qe;
-    if (!(n_bits > 0 && n_bits <= 8)) return QE_ERR_NBITS;
+    if (!bits_ok(n_bits)) return QE_ERR_NBITS;
     if (n < 0 || n_param < 1 || (act != QE_ACT_NONE && act != QE_ACT_GELU)) return QE_ERR_ARG;
     if (n == 0) return QE_OK;
     if (x == nullptr || out == nullptr || scale == nullptr || zero == nullptr) return QE_ERR_ARG;
     if (act == QE_ACT_NONE && y == nullptr)
         return qe_quantize_pack(x, n, scale, zero, n_param, inner, qmin, qmax, n_bits, sign, out, status, stream);
-    if (y != nullptr && y != x && y < x + n && x < y + n) return QE_ERR_ARG;   // in place (y == x) or disjoint
+    if (!same_or_disjoint(y, x, n * 4)) return QE_ERR_ARG;      // in place (y == x) or disjoint; NULL y: no fp32 output
     ActEw a;
     a.x = x; a.y = y; a.codes = out; a.status = status; a.n = n;
     a.q = TpQuant{scale, zero, qmin, qmax, 1u, (uint32_t)n_param};
@@ -567,10 +563,8 @@ extern "C" int qe_quantize_pack_act(const float *x, int64_t n, int32_t act, cons
         a.q.inner = (uint32_t)inner;
     }
     a.n_bits = n_bits;
-    a.offset = sign ? (1u << (n_bits - 1)) : 0u;                 // as launch_tpack_t
-    a.mask = (1u << n_bits) - 1u;
-    a.lo = sign ? -(float)(1 << (n_bits - 1)) : 0.0f;
-    a.hi = sign ? (float)((1 << (n_bits - 1)) - 1) : (float)((1 << n_bits) - 1);
+    const CodeRange cr = code_range(n_bits, sign);
+    a.offset = cr.offset; a.mask = cr.mask; a.lo = cr.lo; a.hi = cr.hi;
     a.vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
     const int64_t groups = (n + 7) / 8;
     const int64_t want = (groups + 255) / 256;

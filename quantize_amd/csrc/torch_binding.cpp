@@ -33,7 +33,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/quant_engine.h"
+#include "qe_request.hpp"          // quant_engine.h and the stored-code range the device path packs with
 
 namespace {
 
@@ -184,21 +184,18 @@ std::vector<torch::Tensor> tpack_host(const torch::Tensor &x, int n_bits, bool s
     const int64_t n = x.numel();
     const auto xf = x.reshape({-1}).to(torch::kFloat);      // x[i].item<float>() of the reference, vectorised
     const float *src = xf.data_ptr<float>();
-    const float lo = sign ? -(float)(1 << (n_bits - 1)) : 0.0f;
-    const float hi = sign ? (float)((1 << (n_bits - 1)) - 1) : (float)((1 << n_bits) - 1);
+    const qe::CodeRange cr = qe::code_range(n_bits, sign);
     bool in_range = true;
-    for (int64_t i = 0; i < n; ++i) in_range = in_range && (src[i] >= lo && src[i] <= hi);   // NaN fails, as in CHECK_RANGE
+    for (int64_t i = 0; i < n; ++i) in_range = in_range && (src[i] >= cr.lo && src[i] <= cr.hi);   // NaN fails, as in CHECK_RANGE
     TORCH_CHECK(in_range, "The input tensor is out of range.");
 
     auto x_out = torch::empty({qe_packed_nbytes(n, n_bits)}, torch::dtype(torch::kByte));
     uint8_t *dst = x_out.data_ptr<uint8_t>();
-    const unsigned offset = sign ? (1u << (n_bits - 1)) : 0u;
-    const unsigned mask = (1u << n_bits) - 1u;
     uint64_t reg = 0;
     int fill = 0;
     int64_t o = 0;
     for (int64_t i = 0; i < n; ++i) {
-        const unsigned e = ((unsigned)(unsigned char)(signed char)src[i] + offset) & mask;
+        const unsigned e = ((unsigned)(unsigned char)(signed char)src[i] + cr.offset) & cr.mask;
         reg |= (uint64_t)e << fill;
         fill += n_bits;
         while (fill >= 8) { dst[o++] = (uint8_t)reg; reg >>= 8; fill -= 8; }
@@ -212,14 +209,13 @@ torch::Tensor tunpack_host(const torch::Tensor &x, const Des &d)
     auto x_out = torch::empty({d.numel}, torch::dtype(d.sign ? torch::kChar : torch::kByte));
     const uint8_t *src = x.data_ptr<uint8_t>();
     uint8_t *dst = static_cast<uint8_t *>(x_out.data_ptr());
-    const unsigned offset = d.sign ? (1u << (d.n_bits - 1)) : 0u;
-    const unsigned mask = (1u << d.n_bits) - 1u;
+    const qe::CodeRange cr = qe::code_range(d.n_bits, d.sign);
     uint64_t reg = 0;
     int fill = 0;
     int64_t in = 0;
     for (int64_t i = 0; i < d.numel; ++i) {
         while (fill < d.n_bits) { reg |= (uint64_t)src[in++] << fill; fill += 8; }
-        dst[i] = (uint8_t)(((unsigned)reg & mask) - offset);   // `element -= offset` in unsigned char, then (signed char)
+        dst[i] = (uint8_t)(((unsigned)reg & cr.mask) - cr.offset);   // `element -= offset` in unsigned char, then (signed char)
         reg >>= d.n_bits;
         fill -= d.n_bits;
     }

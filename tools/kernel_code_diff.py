@@ -9,7 +9,7 @@ quantize_amd/build.py's flags.  An object's code object is unbundled as tools/ke
 llvm-objdump -d.
 
 Of each kernel only the instruction lines count: no directives, no comments (an object's addresses and encodings are
-comments), no __hip_cuid_ symbol, none of the zero padding that aligns the next function.  Kernels are keyed by their
+comments), no __hip_cuid_ symbol, none of the zero padding or no-op fill behind a function's last instruction.  Kernels are keyed by their
 demangled name without the parameter list, so a renamed argument type is no difference.  The filter keeps the kernels whose key contains it.  The comparison is of text: no
 instruction is known by name.  Prints the kernels that only one side has, the kernels whose instructions differ (with the
 first differing line) and the counts; the exit status is 1 if there is any of either.
@@ -37,8 +37,10 @@ def disassemble(obj):
 
 def split_objdump(text):
     """{mangled name: [instruction lines]}: a function starts at `<address> <name>:`; what follows `//` is dropped.  The zero
-    bytes that align the NEXT function (an elided `...`, or a line whose encoding is all zero words) are no part of this one:
-    how many there are follows from the order in which the instances were emitted, so they go from the function's end."""
+    bytes that align the NEXT function (an elided `...`, or a line whose encoding is all zero words) and the `s_nop 0` fill
+    behind a function's last instruction (the section's long end fill lands behind whichever function is emitted last) are
+    no part of this one: how many there are follows from the order in which the functions were emitted, so they go from the
+    function's end.  A fill inside a function is followed by an instruction and stays."""
     out, pad, cur = {}, {}, None
     for line in text.splitlines():
         m = re.match(r"^[0-9a-f]+ <(\S+)>:$", line)
@@ -49,7 +51,7 @@ def split_objdump(text):
         if cur is not None and ins and not ins.startswith(("Disassembly of", "<")):
             cur.append(ins)
             words = line.split("//")[1].split(":")[-1].split() if "//" in line else []
-            zero = ins == "..." or (bool(words) and all(set(w) == {"0"} for w in words))
+            zero = ins in ("...", "s_nop 0") or (bool(words) and all(set(w) == {"0"} for w in words))
             pad[id(cur)] = pad.get(id(cur), 0) + 1 if zero else 0
     for cur in out.values():
         if pad.get(id(cur)):
