@@ -759,6 +759,43 @@ int qe_avgpool2d_codes(const qe_qparam *x, int32_t N, int32_t C, int32_t H, int3
                        int32_t OH, int32_t OW, int32_t relu, float *out, const qe_requant *rq, uint8_t *codes, int32_t *status,
                        qe_stream_t stream);
 
+/* ---- qe_affine_relu_quantize_pack -- the boundary between two convolutions of a pre-activation network -------------------
+ * What stands between conv2 of one WideResNet block and conv1 / convShortcut of the next (modelzoo/cnns/wideresnet.py:29-37):
+ * torch.add, an eval-mode BatchNorm2d that no producer can absorb, ReLU, and the Quantizer + tpack of each consumer, in one pass.
+ * All operations are single fp32 operations in this order, none fused:
+ *   s[n,c,p]  = x[n,c,p] + identity[n,c,p]            (identity NULL: s = x)
+ *   a[n,c,p]  = relu(s * alpha[c] + shift[c])         one multiplication, then one addition; relu(t) = t when t > 0 or t is NaN,
+ *                                                     else +0 (torch.relu)
+ *   codes[i]  = qe_quantize_pack(a, rq[i].scale, rq[i].zero, rq[i].n_param, P, ...)   for i < n_out, bit-identical
+ * x, identity   fp32 NCHW (N, C, P = H*W), 4-byte aligned.
+ * alpha, shift  device fp32[C]: the BatchNorm as the per-channel affine ATen applies in eval mode, alpha = gamma / sqrt(var + eps)
+ *               and shift = beta - mean * alpha, derived by the caller (once, on the host): no square root is part of this contract.
+ * n_out, rq[], codes[]  n_out in 0..2 host arrays: rq[i] in the MODULE's convention, n_param 1 or C, any n_bits in 1..8 and either
+ *               sign; codes[i] device, qe_packed_nbytes(N*C*P, rq[i].n_bits) bytes, any alignment.
+ * sum_out       fp32[N*C*P] or NULL: s, the residual stream the next equal-width block adds to.  It may be x or identity itself
+ *               (in place).
+ * act_out       fp32[N*C*P] or NULL: a (the network's tail takes it with n_out == 0).
+ * status        as qe_tpack; a function of the N*C*P values alone.  When it comes back set the codes of the offending elements
+ *               are unspecified.
+ * No workspace, no prepared table, one kernel launch in every form.  Asynchronous on stream; no host synchronisation.
+ * Refused before any device work, in this order: n_out outside 0..2 or rq NULL with n_out > 0 (QE_ERR_ARG); per rq[i] a NULL
+ * scale / zero (QE_ERR_ARG), n_bits outside 1..8 (QE_ERR_NBITS), n_param < 1 (QE_ERR_ARG); N, C or P <= 0; an n_param that is
+ * neither 1 nor C; a NULL x, alpha, shift or codes[i]; n_out == 0 with sum_out == act_out == NULL; an fp32 pointer or status that
+ * is not 4-byte aligned (all QE_ERR_ARG); then any overlap of an output (sum_out, act_out, codes[i], status) with an operand or
+ * another output, except sum_out == x and sum_out == identity (QE_ERR_ARG).
+ * qe_affine_relu_quantize_pack_path (host only): the instance the call launches, from the one plan the launch reads:
+ *         1 fast   every rq[i] 8-bit (or n_out == 0) and P % 16 == 0: a thread owns 16 consecutive elements of one plane (16-byte
+ *                  loads and stores at any alignment, one 16-byte store of codes per consumer, alpha / shift / scales read once);
+ *         0 plain  everything else (a sub-8-bit consumer, a ragged P): a thread owns 8 consecutive elements, whose b-bit codes
+ *                  are b whole bytes; grid-stride;
+ *        -1 none   (the call returns an error).
+ *         sum_out / act_out are looked at for being NULL only: no instance depends on an alignment. */
+int qe_affine_relu_quantize_pack_path(int32_t N, int32_t C, int32_t P, int32_t n_out, const qe_requant *rq, const float *sum_out,
+                                      const float *act_out);
+int qe_affine_relu_quantize_pack(const float *x, const float *identity, int32_t N, int32_t C, int32_t P, const float *alpha,
+                                 const float *shift, int32_t n_out, const qe_requant *rq, uint8_t *const *codes, float *sum_out,
+                                 float *act_out, int32_t *status, qe_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,9 +21,9 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 
 HIP_SOURCES = ["qe_api.hip", "qe_tpack.hip", "qe_conv_generic.hip", "qe_conv_mfma.hip", "qe_conv_plan.hip",
                "qe_conv_mfma_i0.hip", "qe_conv_mfma_i1.hip", "qe_conv_mfma_i2.hip", "qe_conv_mfma_i3.hip", "qe_conv_mfma_i4.hip", "qe_conv_mfma_i5.hip", "qe_conv_mfma_i6.hip", "qe_conv_mfma_i7.hip", "qe_conv_mfma_i8.hip", "qe_linear.hip", "qe_conv_flatd.hip", "qe_conv_f32.hip", "qe_conv_pwr.hip", "qe_layernorm.hip", "qe_attention.hip", "qe_attention_bf16.hip", "qe_attention_bf16_stored.hip",
-               "qe_attention_bf16_ctx.hip", "qe_linear_bf16in.hip", "qe_conv_dw.hip", "qe_conv_grp.hip", "qe_pool.hip"]
+               "qe_attention_bf16_ctx.hip", "qe_linear_bf16in.hip", "qe_conv_dw.hip", "qe_conv_grp.hip", "qe_pool.hip", "qe_preact.hip"]
 HIP_HEADERS = ["qe_common.h", "qe_request.hpp", "qe_conv_plan.hpp", "qe_conv_common.hpp", "qe_conv_span.hpp", "qe_conv_mfma_kernel.hpp", "qe_elementwise.hpp", "qe_attention_common.hpp",
-               "qe_attention_bf16_stored_kernel.hpp", "qe_attention_bf16_stored_body.hpp", "qe_linear_bf16in.hpp", "qe_conv_dw.hpp", "qe_conv_grp.hpp", "qe_pool.hpp", os.path.join(INCLUDE, "quant_engine.h")]
+               "qe_attention_bf16_stored_kernel.hpp", "qe_attention_bf16_stored_body.hpp", "qe_linear_bf16in.hpp", "qe_conv_dw.hpp", "qe_conv_grp.hpp", "qe_pool.hpp", "qe_preact.hpp", os.path.join(INCLUDE, "quant_engine.h")]
 ARCH = "gfx950"
 
 

@@ -94,6 +94,9 @@ PROTOTYPES = {
     "qe_quant_adaptive_avgpool2d": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _pr, _vp, _vp]),
     "qe_avgpool2d_codes_path": (_i32, [_pq] + [_i32] * 9 + [_vp, _pr, _vp]),
     "qe_avgpool2d_codes": (_i32, [_pq] + [_i32] * 9 + [_vp, _pr, _vp, _vp, _vp]),
+    # the pre-activation boundary: add + per-channel affine + ReLU + the consumers' codes
+    "qe_affine_relu_quantize_pack_path": (_i32, [_i32, _i32, _i32, _i32, _pr, _vp, _vp]),
+    "qe_affine_relu_quantize_pack": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _pr, _ppc, _vp, _vp, _vp, _vp]),
     # packed-activation convolutions
     "qe_quantconv2d_path": (_i32, [_ps, _pq, _pq]),
     "qe_quantconv2d_plan_info": (_i32, [_ps, _pq, _pq, _pr, _vp, _vp, _pi]),
@@ -603,6 +606,40 @@ def avgpool2d_codes(xq, N, C, H, W, kernel=0, stride=None, output_size=None, rel
                                    1 if relu else 0, _ptr(out), None if rq is None else ctypes.byref(rq), _ptr(codes),
                                    status.data_ptr(), _stream(stream)))
     return out, codes, status
+
+
+# qe_affine_relu_quantize_pack_path: the instance by number
+PREACT_KERNELS = ("plain", "fast")
+
+
+def affine_relu_quantize_pack_path(N, C, P, rqs=(), sum_out=256, act_out=0):
+    """qe_affine_relu_quantize_pack_path (host-only): 1 fast, 0 plain, -1 none.  sum_out / act_out: destination addresses (0:
+    not requested)."""
+    rqs = list(rqs)
+    return int(lib().qe_affine_relu_quantize_pack_path(int(N), int(C), int(P), len(rqs), _rq_array(rqs), int(sum_out) or None,
+                                                       int(act_out) or None))
+
+
+def affine_relu_quantize_pack(x, alpha, shift, identity=None, rqs=(), sum_out=None, act_out=None, codes=None, status=None, stream=None):
+    """qe_affine_relu_quantize_pack on fp32 NCHW x: s = x + identity (identity None: x), a = relu(s * alpha[c] + shift[c]), and the
+    codes of a under every quantiser in rqs (at most two capi.requant).  sum_out / act_out: None skips the output, "new" allocates
+    it, or pass a tensor (sum_out may be x or identity: in place).  Returns (list of codes, sum_out or None, act_out or None,
+    status)."""
+    import torch
+    _fp32_nchw(x)
+    N, C, H, W = x.shape
+    rqs = list(rqs)
+    if isinstance(sum_out, str):
+        sum_out = torch.empty_like(x)
+    if isinstance(act_out, str):
+        act_out = torch.empty_like(x)
+    if codes is None:
+        codes = [torch.empty(packed_nbytes(x.numel(), r.n_bits), dtype=torch.uint8, device=x.device) for r in rqs]
+    status = _status(status, x.device)
+    cp = (ctypes.c_void_p * max(1, len(codes)))(*[c.data_ptr() for c in codes])
+    check(lib().qe_affine_relu_quantize_pack(x.data_ptr(), _ptr(identity), N, C, H * W, alpha.data_ptr(), shift.data_ptr(), len(rqs),
+                                             _rq_array(rqs), cp, _ptr(sum_out), _ptr(act_out), status.data_ptr(), _stream(stream)))
+    return codes, sum_out, act_out, status
 
 
 def quantize_pack(x, scale, zero, qmin, qmax, n_bits, sign, inner=1, out=None, status=None, stream=None):

@@ -6,6 +6,7 @@
 #include "qe_conv_dw.hpp"
 #include "qe_conv_grp.hpp"
 #include "qe_pool.hpp"
+#include "qe_preact.hpp"
 
 #include <atomic>
 #include <cstring>
@@ -691,4 +692,68 @@ extern "C" int qe_avgpool2d_codes(const qe_qparam *x, int32_t N, int32_t C, int3
     if (!outputs_clear(outs, 3, ins, 5)) return QE_ERR_ARG;
     if (n == 0) return QE_OK;
     return launch_pool_codes(p, x, N, C, H, W, kernel, stride, relu, out, rq, codes, status, static_cast<hipStream_t>(stream));
+}
+
+// ---- the pre-activation boundary (qe_preact.hip): one plan (plan_preact, qe_preact.hpp) for the path query and the call ------------
+namespace qe {
+static PreactPlan plan_preact_request(int N, int C, int P, int n_out, const qe_requant *rq, const float *sum_out, const float *act_out)
+{
+    PreactRequest r{N, C, P, n_out, {0, 0}, sum_out != nullptr, act_out != nullptr};
+    for (int i = 0; i < n_out && i < PREACT_MAX_OUT; ++i) r.rq_bits[i] = rq[i].n_bits;
+    return plan_preact(r);
+}
+
+// counts and formats of a request (no address but rq's own is looked at): n_out, then each quantiser, then the sizes, then n_param
+static int check_preact_request(int N, int C, int P, int n_out, const qe_requant *rq)
+{
+    if (n_out < 0 || n_out > PREACT_MAX_OUT || (n_out > 0 && rq == nullptr)) return QE_ERR_ARG;
+    for (int i = 0; i < n_out; ++i) {
+        const int rc = check_requant(&rq[i]);
+        if (rc != QE_OK) return rc;
+    }
+    if (N <= 0 || C <= 0 || P <= 0) return QE_ERR_ARG;
+    for (int i = 0; i < n_out; ++i)
+        if (!one_or_per_channel(rq[i].n_param, C)) return QE_ERR_ARG;
+    return QE_OK;
+}
+}  // namespace qe
+
+extern "C" int qe_affine_relu_quantize_pack_path(int32_t N, int32_t C, int32_t P, int32_t n_out, const qe_requant *rq,
+                                                 const float *sum_out, const float *act_out)
+{
+    if (qe::check_preact_request(N, C, P, n_out, rq) != QE_OK) return -1;
+    return qe::plan_preact_request(N, C, P, n_out, rq, sum_out, act_out).kernel;
+}
+
+extern "C" int qe_affine_relu_quantize_pack(const float *x, const float *identity, int32_t N, int32_t C, int32_t P, const float *alpha,
+                                            const float *shift, int32_t n_out, const qe_requant *rq, uint8_t *const *codes,
+                                            float *sum_out, float *act_out, int32_t *status, qe_stream_t stream)
+{
+    using namespace qe;
+    const int rc = check_preact_request(N, C, P, n_out, rq);
+    if (rc != QE_OK) return rc;
+    if (x == nullptr || alpha == nullptr || shift == nullptr || (n_out > 0 && codes == nullptr)) return QE_ERR_ARG;
+    for (int i = 0; i < n_out; ++i)
+        if (codes[i] == nullptr) return QE_ERR_ARG;
+    const PreactPlan p = plan_preact_request(N, C, P, n_out, rq, sum_out, act_out);
+    if (p.kernel == PREACT_NONE && p.rc == QE_ERR_ARG) return p.rc;                    // no output requested
+    for (const void *f : {(const void *)x, (const void *)identity, (const void *)alpha, (const void *)shift, (const void *)sum_out,
+                          (const void *)act_out, (const void *)status})
+        if ((reinterpret_cast<uintptr_t>(f) & 3) != 0) return QE_ERR_ARG;
+    if (p.kernel == PREACT_NONE) return p.rc;
+    // sum_out may be x or identity themselves (in place); otherwise no output overlaps an operand or another output
+    const int64_t bytes = (int64_t)N * C * P * 4;
+    Span small[2 + 2 * PREACT_MAX_OUT] = {span_of(alpha, 4 * (int64_t)C), span_of(shift, 4 * (int64_t)C)};
+    Span others[2 + PREACT_MAX_OUT] = {span_of(act_out, bytes), span_of(status, 4)};
+    for (int i = 0; i < n_out; ++i) {
+        small[2 + 2 * i] = span_of(rq[i].scale, 4 * (int64_t)rq[i].n_param);
+        small[3 + 2 * i] = span_of(rq[i].zero, 4 * (int64_t)rq[i].n_param);
+        others[2 + i] = span_of(codes[i], qe_packed_nbytes(bytes / 4, rq[i].n_bits));
+    }
+    const Span big[2] = {span_of(x, bytes), span_of(identity, bytes)};
+    const Span sum = span_of(sum_out, bytes);
+    if (!outputs_clear(others, 2 + n_out, small, 2 + 2 * n_out) || !outputs_clear(others, 2 + n_out, big, 2)) return QE_ERR_ARG;
+    if (!outputs_clear(&sum, 1, small, 2 + 2 * n_out) || !outputs_clear(&sum, 1, others, 2 + n_out)) return QE_ERR_ARG;
+    if (!same_or_disjoint(sum_out, x, bytes) || !same_or_disjoint(sum_out, identity, bytes)) return QE_ERR_ARG;
+    return launch_preact(p, x, identity, N, C, P, alpha, shift, n_out, rq, codes, sum_out, act_out, status, static_cast<hipStream_t>(stream));
 }

@@ -1,4 +1,4 @@
-"""What the packed CNN runners (PackedResNet, PackedMobileNetV1) share: everything but the graph.
+"""What the packed CNN runners (PackedResNet, PackedMobileNetV1, PackedWideResNet) share: everything but the graph.
 
 A family derives from PackedCNN and supplies FAMILY (its name in from_state_dict's messages), from_state_dict, convs(),
 _layers(x, observe) and _fused(images, status) -- both return the fp32 feature map the head pools -- and its own forward,
@@ -30,23 +30,23 @@ class PackedCNN:
         return sd, layer
 
     @classmethod
-    def _stages(cls, sd, pattern):
+    def _stages(cls, sd, pattern, stage="layer"):
         """{stage: {block: the pattern's further groups as a set of ints}} of the keys matching `pattern` (groups 1 and 2:
-        stage and block index); the stages must be 1..n."""
+        stage and block index); the stages must be 1..n.  `stage`: what the family's key layout calls one (in messages)."""
         found = {}
         for k in sd:
             m = re.match(pattern, k)
             if m:
                 found.setdefault(int(m.group(1)), {}).setdefault(int(m.group(2)), set()).update(int(g) for g in m.groups()[2:])
         if not found or sorted(found) != list(range(1, len(found) + 1)):
-            raise KeyError("packed %s state_dict: stages layer1.. not found (have %s)" % (cls.FAMILY, sorted(found)))
+            raise KeyError("packed %s state_dict: stages %s1.. not found (have %s)" % (cls.FAMILY, stage, sorted(found)))
         return found
 
     @classmethod
-    def _block_indices(cls, found, S):
+    def _block_indices(cls, found, S, stage="layer"):
         """Stage S's block indices, which must be 0..n-1."""
         if sorted(found[S]) != list(range(len(found[S]))):
-            raise KeyError("packed %s state_dict: layer%d has blocks %s" % (cls.FAMILY, S, sorted(found[S])))
+            raise KeyError("packed %s state_dict: %s%d has blocks %s" % (cls.FAMILY, stage, S, sorted(found[S])))
         return sorted(found[S])
 
     def to(self, device):

@@ -51,6 +51,16 @@ def fc_entries(rng, num_classes, K, w_bits, a_bits):
             **_quantizer_entries(0, (1 << a_bits) - 1)}
 
 
+def bn_entries(rng, C):
+    """An unfolded BatchNorm2d's state_dict entries (the pre-activation families keep the BatchNorms in front of a block's
+    first conv): gamma around 1, small beta and running mean, running variance around 1."""
+    return {"weight": torch.from_numpy(rng.uniform(0.5, 1.5, size=C).astype(np.float32)),
+            "bias": torch.from_numpy(rng.normal(0, 0.1, size=C).astype(np.float32)),
+            "running_mean": torch.from_numpy(rng.normal(0, 0.1, size=C).astype(np.float32)),
+            "running_var": torch.from_numpy(rng.uniform(0.5, 1.5, size=C).astype(np.float32)),
+            "num_batches_tracked": torch.tensor(0, dtype=torch.int64)}
+
+
 def put(sd, prefix, entries):
     for k, v in entries.items():
         sd[prefix + "." + k] = v
