@@ -450,6 +450,37 @@ int qe_quantlinear_form(const qe_qparam *x, const qe_qparam *w, int64_t B, int32
  * fp32 accumulation rounding of the exact sum; QE_LIN_F32_MFMA=0 disables it). */
 int qe_quantlinear_float_input_path(const float *x, const qe_qparam *w, int64_t B, int32_t K, int32_t O);
 
+/* ---- group-quantised weights (the AWQ layout) --------------------------------------------------
+ * qe_quantlinear_grouped_float_input -- fp32 rows x packed weight codes with one scale and zero per (output row, group of
+ * group_size consecutive input channels), and an optional per-input-channel multiplier of the activations:
+ *   out[b,o] = bias[o] + sum_g  sw[o,g] * sum_{k in group g} x'[b,k] * (q_w[o,k] - zw[o,g])
+ *   x'[b,k]  = x[b,k] * x_mul[k]        (one fp32 multiply; x_mul == NULL means x' = x)
+ * x        B*K fp32 values.   x_mul  fp32[K] or NULL (for AWQ: 1 / awq_scale).
+ * w        the usual packed stream of O*K codes (little-endian bit stream, stored value q + 2^(bits-1) when signed).  Group g
+ *          covers k in [g*group_size, (g+1)*group_size); K % group_size == 0.  w->scale and w->zero are fp32 arrays of
+ *          O*(K/group_size) elements in (o, g) row-major order -- the order in which the reference's AWQ estimator yields them
+ *          from _w.reshape(-1, q_group_size) -- and w->n_param == O*(K/group_size).  Kernel convention (q - zero), as
+ *          qe_quantlinear_float_input; the zero is fractional in general (the reference computes xmin / scale unrounded).
+ * symmetric  non-zero: the caller declares that every zw[o,g] is an integer inside the stored code range ([-128, 127] signed,
+ *          [0, 255] unsigned), as a symmetric quantiser's zeros are; the fast kernel then runs the instance without the
+ *          zero-point remainder term.  Decided from this flag alone, never by reading device memory; with zeros that break
+ *          the declaration the fast kernel uses rint(zw) clamped to that range in place of zw.  0 is always correct.
+ * bias     fp32[O] or NULL.   out  B*O floats, fully written.   No workspace, no prepared tables.
+ * Non-finite activations: as declared for qe_quantlinear_float_input's MFMA kernel, on the fast kernel.
+ * Refused before any device work, in this order: a negative B, K or O (QE_ERR_ARG); a NULL w, w->data, w->scale or w->zero
+ * (QE_ERR_ARG); n_bits outside 1..8 (QE_ERR_NBITS); group_size <= 0, K % group_size != 0, n_param != O*(K/group_size); a NULL x
+ * or out with elements to read or write (all QE_ERR_ARG).
+ * _path (host-only, from the one plan the launch reads; 0 for a request the call would refuse):
+ *   1 = the fast kernel: 4- or 8-bit codes, group_size in {32, 64, 128}, K % 32 == 0, x, x_mul and w->data 16-byte aligned:
+ *       v_mfma_f32_32x32x16_bf16 on the exact three-way bf16 split of x' and codes centred on rint(zw[o,g]) per (row, group),
+ *       folded into the total with sw[o,g] at every group boundary; within fp32 accumulation rounding of the exact sum;
+ *   0 = the plain kernel: one thread per output, fp32, group by group in k order (any n_bits, group_size, K, alignment). */
+int qe_quantlinear_grouped_float_input(const float *x, const float *x_mul, const qe_qparam *w, int32_t group_size,
+                                       int32_t symmetric, const float *bias, int64_t B, int32_t K, int32_t O, float *out,
+                                       qe_stream_t stream);
+int qe_quantlinear_grouped_float_input_path(const float *x, const float *x_mul, const qe_qparam *w, int32_t group_size,
+                                            int32_t symmetric, int64_t B, int32_t K, int32_t O);
+
 /* ---- fused ViT forms ---------------------------------------------------------------------------
  * What runs between the GEMMs of a ViT encoder block (torchvision's EncoderBlock around the reference's QuantLinear /
  * QuantMultiheadAttention: x + attn(ln_1(x)), then y + mlp(ln_2(y)) with mlp = fc1, GELU, fc2) fused into the linears'

@@ -136,6 +136,8 @@ PROTOTYPES = {
     "qe_quantlinear_form": (_i32, [_pq, _pq, _i64, _i32, _i32, _i32]),
     "qe_quantlinear_float_input": (_i32, [_vp, _pq, _vp, _i64, _i32, _i32, _vp, _vp]),
     "qe_quantlinear_float_input_path": (_i32, [_vp, _pq, _i64, _i32, _i32]),
+    "qe_quantlinear_grouped_float_input": (_i32, [_vp, _vp, _pq, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "qe_quantlinear_grouped_float_input_path": (_i32, [_vp, _vp, _pq, _i32, _i32, _i64, _i32, _i32]),
     "qe_quantlinear_requant_path": (_i32, [_pq, _pq, _i64, _i32, _i32, _pr, _vp]),
     "qe_quantlinear_requant_workspace_bytes": (_sz, [_pq, _pq, _i64, _i32, _i32, _pr, _vp]),
     "qe_quantlinear_requant": (_i32, [_pq, _pq, _vp, _i64, _i32, _i32, _i32, _pr, _vp, _vp, _vp, _sz, _vp]),
@@ -746,6 +748,29 @@ def quantlinear_float_input(x, wq, bias, O, out=None, stream=None):
         out = torch.empty((B, O), dtype=torch.float32, device=x.device)
     check(lib().qe_quantlinear_float_input(x.data_ptr(), ctypes.byref(wq), _ptr(bias), int(B), int(K), int(O), out.data_ptr(),
                                            _stream(stream)))
+    return out
+
+
+def linear_grouped_float_input_path(x, wq, group_size, B, K, O, x_mul=None, symmetric=False):
+    """qe_quantlinear_grouped_float_input_path (host-only): 1 = the bf16 matrix-core kernel, 0 = the plain kernel.  x and x_mul are
+    tensors or addresses (only their alignment counts)."""
+    addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
+    return int(lib().qe_quantlinear_grouped_float_input_path(addr(x), addr(x_mul), ctypes.byref(wq), int(group_size),
+                                                             1 if symmetric else 0, int(B), int(K), int(O)))
+
+
+def quantlinear_grouped_float_input(x, wq, group_size, bias, O, x_mul=None, out=None, stream=None, symmetric=False):
+    """qe_quantlinear_grouped_float_input: fp32 rows x group-quantised packed weights (wq: scale / zero of O * K / group_size
+    elements in (o, g) order, kernel convention), x_mul an optional fp32[K] multiplier of the activations.  symmetric=True
+    declares every zero an integer inside the code range (see the header)."""
+    import torch
+    assert x.is_cuda and x.is_contiguous() and x.dtype == torch.float32 and x.dim() == 2
+    B, K = x.shape
+    if out is None:
+        out = torch.empty((B, O), dtype=torch.float32, device=x.device)
+    check(lib().qe_quantlinear_grouped_float_input(x.data_ptr(), _ptr(x_mul), ctypes.byref(wq), int(group_size),
+                                                   1 if symmetric else 0, _ptr(bias), int(B), int(K), int(O), out.data_ptr(),
+                                                   _stream(stream)))
     return out
 
 

@@ -370,6 +370,85 @@ class PackedLinear(_PackedBase):
         return codes, (des if status is not None else torch.tensor(des, dtype=torch.int32, device=xq.device))
 
 
+class PackedGroupedLinear:
+    """A linear whose weights are group-quantised as the reference's AWQ estimator lays them out (range/awq.py): groups of
+    `group_size` consecutive input channels, one scale and zero per (output row, group), and a per-input-channel awq_scale
+    the weights were multiplied by before rounding -- the activations are multiplied by its reciprocal.  The reference can
+    only simulate this layout (Quantizer.pack raises for AWQ); here it runs packed, on fp32 rows
+    (qe_quantlinear_grouped_float_input).  State: the packed stream, w_des [n_bits, sign, O, K], w_scale / w_zero of O * K /
+    group_size elements in (o, g) order in the MODULE's convention (q + zero) * scale, awq_scale [K], bias."""
+
+    def __init__(self, weight, w_des, w_scale, w_zero, w_group_size, awq_scale=None, bias=None, name=None):
+        assert weight.dtype == torch.uint8 and weight.dim() == 1, "weight must be the packed 1-D uint8 stream"
+        wd = [int(v) for v in w_des.tolist()]
+        self.weight, self.w_des, self.bias, self.name = weight, w_des, bias, name
+        self.w_bits, self.w_signed, self.O, self.K = wd[0], bool(wd[1]), wd[2], wd[3]
+        self.group_size = int(w_group_size)
+        if self.group_size <= 0 or self.K % self.group_size:
+            raise ValueError("group_size must divide in_features")
+        n = self.O * (self.K // self.group_size)
+        self.w_scale, self.w_zero = w_scale.reshape(-1).contiguous().float(), w_zero.reshape(-1).contiguous().float()
+        if self.w_scale.numel() != n or self.w_zero.numel() != n:
+            raise ValueError("w_scale and w_zero hold one element per (output row, group)")
+        self._neg_w_zero = (-self.w_zero).contiguous()        # kernel convention (q - zero)
+        # decided here, on the host, once: every zero an integer inside the stored code range -> the kernel's symmetric instance
+        lo, hi = (-128.0, 127.0) if self.w_signed else (0.0, 255.0)
+        z = self._neg_w_zero
+        self.symmetric = bool(((z == z.round()) & (z >= lo) & (z <= hi)).all())
+        self.awq_scale = None if awq_scale is None else awq_scale.reshape(-1).contiguous().float()
+        self.x_mul = None if awq_scale is None else (1.0 / self.awq_scale.double()).float().contiguous()
+        if self.x_mul is not None and self.x_mul.numel() != self.K:
+            raise ValueError("awq_scale holds one element per input channel")
+
+    @classmethod
+    def from_awq(cls, weight, cfgs, n_bits, signed, group_size, bias=None):
+        """From a float weight (O, K) and the tuple the reference's AWQ estimator returns, (scale, zero, qmin, qmax,
+        awq_scale): the codes are the reference's (w * awq_scale / scale - zero).round().clamp(qmin, qmax) per group, in fp32,
+        stored signed only where the code range is (an asymmetric quantiser's is [0, 2^bits - 1] whatever `signed`)."""
+        from .synthetic import pack_codes
+        scale, zero, qmin, qmax, awq_scale = cfgs
+        w = weight.detach().float().cpu()
+        O, K = w.shape
+        scale, zero = scale.detach().float().cpu().reshape(-1, 1), zero.detach().float().cpu().reshape(-1, 1)
+        awq_scale = awq_scale.detach().float().cpu().reshape(1, K)
+        q = ((w * awq_scale).reshape(-1, int(group_size)) / scale - zero).round().clamp(float(qmin), float(qmax))
+        stored_signed = bool(signed) and float(qmin) < 0
+        packed = torch.from_numpy(pack_codes(q.numpy().astype("int64"), int(n_bits), stored_signed))
+        des = torch.tensor([int(n_bits), int(stored_signed), O, K], dtype=torch.int32)
+        return cls(packed, des, scale, zero, group_size, awq_scale, None if bias is None else bias.detach().float().cpu())
+
+    @classmethod
+    def from_state_dict(cls, state_dict, prefix=""):
+        g = lambda k: state_dict[prefix + k]
+        return cls(g("weight"), g("w_des"), g("w_scale"), g("w_zero"), int(g("w_group_size")), state_dict.get(prefix + "awq_scale"),
+                   state_dict.get(prefix + "bias"), name=prefix.rstrip("."))
+
+    def state_dict(self):
+        sd = {"weight": self.weight, "w_des": self.w_des, "w_scale": self.w_scale, "w_zero": self.w_zero,
+              "w_group_size": torch.tensor(self.group_size, dtype=torch.int32)}
+        if self.awq_scale is not None:
+            sd["awq_scale"] = self.awq_scale
+        if self.bias is not None:
+            sd["bias"] = self.bias
+        return sd
+
+    def to(self, device):
+        for k, v in list(vars(self).items()):
+            if torch.is_tensor(v):
+                setattr(self, k, v.to(device))
+        return self
+
+    def wq(self):
+        return capi.qparam(self.weight, self.w_bits, self.w_signed, self.w_scale, self._neg_w_zero)
+
+    def __call__(self, x):
+        """fp32 rows (..., in_features) -> (..., out_features)."""
+        x2 = x.reshape(-1, x.shape[-1]).contiguous().float()
+        y = capi.quantlinear_grouped_float_input(x2, self.wq(), self.group_size, self.bias, self.O, x_mul=self.x_mul,
+                                                 symmetric=self.symmetric)
+        return y.reshape(*x.shape[:-1], self.O)
+
+
 class PackedMultiheadAttention:
     """A packed QuantMultiheadAttention's forward on the engine (modelzoo/modules/quantmultiheadattention.py:262-...).
     pack() leaves the q / k / v projection weights and out_proj.weight as packed streams with {q,k,v,out}_proj_{scale,
@@ -690,6 +769,8 @@ def from_state_dict(state_dict, conv_geometry=None, num_heads=None, pool_geometr
                 kh = int(des[4])
                 stride, padding = conv_geometry.get(name, (1, (kh - 1) // 2))
                 layers[name] = PackedConv2d.from_state_dict(state_dict, prefix, stride=stride, padding=padding)
+            elif des.numel() == 4 and prefix + "w_group_size" in state_dict:
+                layers[name] = PackedGroupedLinear.from_state_dict(state_dict, prefix)
             elif des.numel() == 4:
                 layers[name] = PackedLinear.from_state_dict(state_dict, prefix)
             else:
