@@ -481,6 +481,37 @@ int qe_quantlinear_grouped_float_input(const float *x, const float *x_mul, const
 int qe_quantlinear_grouped_float_input_path(const float *x, const float *x_mul, const qe_qparam *w, int32_t group_size,
                                             int32_t symmetric, int64_t B, int32_t K, int32_t O);
 
+/* qe_quantlinear_grouped -- packed activation codes x the same group-quantised weight codes, on the int8 matrix cores:
+ *   out[b,o] = bias[o] + sx[b] * sum_g  sw[o,g] * sum_{k in group g} (q_x[b,k] - zx[b]) * (q_w[o,k] - zw[o,g])
+ * NOTE the convention: BOTH operands use the kernel convention (q - zero), as qe_quantlinear_grouped_float_input does for
+ * its weights; qe_quantlinear itself ADDS the zero.  Zeros are fractional in general.
+ * x        a packed stream of B*K codes, row major; x->scale / x->zero indexed by the ROW as in qe_quantlinear; x->n_param is 1
+ *          or B.  (A per-input-channel multiplier cannot act inside an integer sum over k: the caller folds it into the
+ *          activation quantiser's scale, as packed.PackedGroupedLinear.quantize does.)
+ * w, group_size   exactly as for qe_quantlinear_grouped_float_input: (o, g) order, w->n_param == O*(K/group_size).
+ * x_symmetric, w_symmetric   host-side declarations, never checked by reading device memory.  w_symmetric non-zero: every
+ *          zw[o,g] equals the CENTRE of the stream, 0 for a signed stream and 2^(n_bits-1) for an unsigned one -- what a
+ *          symmetric quantiser yields; x_symmetric: the same for every zx[b].  With zeros that break a declaration the fast
+ *          kernel uses the centre in place of the zero.  0 is always correct.  The plain kernel ignores both.
+ * bias     fp32[O] or NULL.   out  B*O floats, fully written.   No workspace, no prepared tables.
+ * Arithmetic: every stored value u is read as the centred integer u - 2^(n_bits-1); inside a group the product sum, the
+ * activation code sum and the weight code sum are integers (exact in int32 and as fp32 for group_size <= 128); fp32 rounding
+ * happens only where a group is folded into the total with sw[o,g] and in the zero-point and sx / bias terms.
+ * Refused before any device work, in this order: a negative B, K or O (QE_ERR_ARG); a NULL x, x->data, x->scale or x->zero
+ * (QE_ERR_ARG); x->n_bits outside 1..8 (QE_ERR_NBITS); a NULL w, w->data, w->scale or w->zero (QE_ERR_ARG); w->n_bits outside
+ * 1..8 (QE_ERR_NBITS); group_size <= 0, K % group_size != 0, x->n_param not 1 or B, w->n_param != O*(K/group_size); a NULL out
+ * with elements to write (all QE_ERR_ARG).
+ * _path (host-only, from the one plan the launch reads; 0 for a request the call would refuse):
+ *   1 = the fast kernel: 8-bit activation codes, 4- or 8-bit weight codes, group_size in {32, 64, 128} (K is then a multiple
+ *       of 32; it need not be one of 64), x->data and w->data 16-byte aligned: v_mfma_i32_32x32x32_i8 into an int32 group
+ *       accumulator, folded into the fp32 total at every group boundary;
+ *   0 = the plain kernel: one thread per output, the same integer sums group by group in k order (any n_bits of either
+ *       operand, any group_size, K and alignment). */
+int qe_quantlinear_grouped(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric, int32_t w_symmetric,
+                           const float *bias, int64_t B, int32_t K, int32_t O, float *out, qe_stream_t stream);
+int qe_quantlinear_grouped_path(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric,
+                                int32_t w_symmetric, int64_t B, int32_t K, int32_t O);
+
 /* ---- fused ViT forms ---------------------------------------------------------------------------
  * What runs between the GEMMs of a ViT encoder block (torchvision's EncoderBlock around the reference's QuantLinear /
  * QuantMultiheadAttention: x + attn(ln_1(x)), then y + mlp(ln_2(y)) with mlp = fc1, GELU, fc2) fused into the linears'

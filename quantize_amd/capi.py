@@ -138,6 +138,8 @@ PROTOTYPES = {
     "qe_quantlinear_float_input_path": (_i32, [_vp, _pq, _i64, _i32, _i32]),
     "qe_quantlinear_grouped_float_input": (_i32, [_vp, _vp, _pq, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp]),
     "qe_quantlinear_grouped_float_input_path": (_i32, [_vp, _vp, _pq, _i32, _i32, _i64, _i32, _i32]),
+    "qe_quantlinear_grouped": (_i32, [_pq, _pq, _i32, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "qe_quantlinear_grouped_path": (_i32, [_pq, _pq, _i32, _i32, _i32, _i64, _i32, _i32]),
     "qe_quantlinear_requant_path": (_i32, [_pq, _pq, _i64, _i32, _i32, _pr, _vp]),
     "qe_quantlinear_requant_workspace_bytes": (_sz, [_pq, _pq, _i64, _i32, _i32, _pr, _vp]),
     "qe_quantlinear_requant": (_i32, [_pq, _pq, _vp, _i64, _i32, _i32, _i32, _pr, _vp, _vp, _vp, _sz, _vp]),
@@ -771,6 +773,25 @@ def quantlinear_grouped_float_input(x, wq, group_size, bias, O, x_mul=None, out=
     check(lib().qe_quantlinear_grouped_float_input(x.data_ptr(), _ptr(x_mul), ctypes.byref(wq), int(group_size),
                                                    1 if symmetric else 0, _ptr(bias), int(B), int(K), int(O), out.data_ptr(),
                                                    _stream(stream)))
+    return out
+
+
+def linear_grouped_path(xq, wq, group_size, B, K, O, x_symmetric=False, w_symmetric=False):
+    """qe_quantlinear_grouped_path (host-only): 1 = the int8 matrix-core kernel, 0 = the plain kernel."""
+    return int(lib().qe_quantlinear_grouped_path(ctypes.byref(xq), ctypes.byref(wq), int(group_size), 1 if x_symmetric else 0,
+                                                 1 if w_symmetric else 0, int(B), int(K), int(O)))
+
+
+def quantlinear_grouped(xq, wq, group_size, bias, B, K, O, out=None, stream=None, x_symmetric=False, w_symmetric=False):
+    """qe_quantlinear_grouped: packed activation codes x group-quantised packed weights, both in the kernel convention
+    (q - zero); xq: scale / zero of 1 or B elements by row, wq: of O * K / group_size elements in (o, g) order.  x_symmetric /
+    w_symmetric declare every zero of that operand equal to the centre of its stream (see the header)."""
+    import torch
+    if out is None:
+        out = torch.empty((B, O), dtype=torch.float32, device=wq._keep[0].device)
+    check(lib().qe_quantlinear_grouped(ctypes.byref(xq), ctypes.byref(wq), int(group_size), 1 if x_symmetric else 0,
+                                       1 if w_symmetric else 0, _ptr(bias), int(B), int(K), int(O), out.data_ptr(),
+                                       _stream(stream)))
     return out
 
 

@@ -375,10 +375,14 @@ class PackedGroupedLinear:
     `group_size` consecutive input channels, one scale and zero per (output row, group), and a per-input-channel awq_scale
     the weights were multiplied by before rounding -- the activations are multiplied by its reciprocal.  The reference can
     only simulate this layout (Quantizer.pack raises for AWQ); here it runs packed, on fp32 rows
-    (qe_quantlinear_grouped_float_input).  State: the packed stream, w_des [n_bits, sign, O, K], w_scale / w_zero of O * K /
-    group_size elements in (o, g) order in the MODULE's convention (q + zero) * scale, awq_scale [K], bias."""
+    (qe_quantlinear_grouped_float_input, route="float") or, with an activation quantiser, on activation codes and the int8
+    matrix cores (qe_quantlinear_grouped, route="packed").  The two routes are NOT bit-identical: the packed one quantises the
+    activations.  State: the packed stream, w_des [n_bits, sign, O, K], w_scale / w_zero of O * K / group_size elements in
+    (o, g) order in the MODULE's convention (q + zero) * scale, awq_scale [K], bias, and -- only when the layer has one --
+    the per-tensor activation quantiser a_quantizer.{scale, zero, qmin, qmax} of x / awq_scale, module convention."""
 
-    def __init__(self, weight, w_des, w_scale, w_zero, w_group_size, awq_scale=None, bias=None, name=None):
+    def __init__(self, weight, w_des, w_scale, w_zero, w_group_size, awq_scale=None, bias=None, name=None,
+                 a_scale=None, a_zero=None, a_qmin=None, a_qmax=None):
         assert weight.dtype == torch.uint8 and weight.dim() == 1, "weight must be the packed 1-D uint8 stream"
         wd = [int(v) for v in w_des.tolist()]
         self.weight, self.w_des, self.bias, self.name = weight, w_des, bias, name
@@ -399,6 +403,27 @@ class PackedGroupedLinear:
         self.x_mul = None if awq_scale is None else (1.0 / self.awq_scale.double()).float().contiguous()
         if self.x_mul is not None and self.x_mul.numel() != self.K:
             raise ValueError("awq_scale holds one element per input channel")
+        # both declarations of qe_quantlinear_grouped, decided here, on the host, once: every zero the centre of its stream
+        self.w_centred = bool((z == (0.0 if self.w_signed else float(1 << (self.w_bits - 1)))).all())
+        self.a_scale = self.a_zero = None
+        if a_scale is not None:
+            self.set_quantizer(a_scale, a_zero, a_qmin, a_qmax)
+
+    def set_quantizer(self, a_scale, a_zero, a_qmin, a_qmax):
+        """Attach the per-tensor activation quantiser of x / awq_scale: codes round(x / awq_scale / a_scale - a_zero).clamp(qmin,
+        qmax).  The per-channel multiplier cannot act inside an integer sum over k, so it moves into the quantiser's scale:
+        s_k = float(double(a_scale) * double(awq_scale[k])), built here once."""
+        self.a_scale, self.a_zero = a_scale.reshape(-1).contiguous().float(), a_zero.reshape(-1).contiguous().float()
+        if self.a_scale.numel() != 1 or self.a_zero.numel() != 1:
+            raise ValueError("the activation quantiser is per tensor")
+        self.a_qmin, self.a_qmax = float(a_qmin), float(a_qmax)
+        self.a_bits, self.a_signed = quantizer_bits(a_qmin, a_qmax)
+        dev = self.a_scale.device
+        awq = torch.ones(self.K, dtype=torch.float64) if self.awq_scale is None else self.awq_scale.double().cpu()
+        self._a_scale_k = (self.a_scale.double().cpu() * awq).float().contiguous().to(dev)
+        self._a_zero_k = self.a_zero.cpu().repeat(self.K).contiguous().to(dev)
+        self._neg_a_zero = (-self.a_zero).contiguous()       # kernel convention (q - zero)
+        self.a_centred = float(self._neg_a_zero) == (0.0 if self.a_signed else float(1 << (self.a_bits - 1)))
 
     @classmethod
     def from_awq(cls, weight, cfgs, n_bits, signed, group_size, bias=None):
@@ -420,8 +445,10 @@ class PackedGroupedLinear:
     @classmethod
     def from_state_dict(cls, state_dict, prefix=""):
         g = lambda k: state_dict[prefix + k]
+        a = {"a_" + k: state_dict[prefix + "a_quantizer." + k] for k in ("scale", "zero", "qmin", "qmax")
+             if prefix + "a_quantizer.scale" in state_dict}
         return cls(g("weight"), g("w_des"), g("w_scale"), g("w_zero"), int(g("w_group_size")), state_dict.get(prefix + "awq_scale"),
-                   state_dict.get(prefix + "bias"), name=prefix.rstrip("."))
+                   state_dict.get(prefix + "bias"), name=prefix.rstrip("."), **a)
 
     def state_dict(self):
         sd = {"weight": self.weight, "w_des": self.w_des, "w_scale": self.w_scale, "w_zero": self.w_zero,
@@ -430,6 +457,9 @@ class PackedGroupedLinear:
             sd["awq_scale"] = self.awq_scale
         if self.bias is not None:
             sd["bias"] = self.bias
+        if self.a_scale is not None:
+            sd.update({"a_quantizer.scale": self.a_scale, "a_quantizer.zero": self.a_zero,
+                       "a_quantizer.qmin": torch.tensor(self.a_qmin), "a_quantizer.qmax": torch.tensor(self.a_qmax)})
         return sd
 
     def to(self, device):
@@ -441,8 +471,37 @@ class PackedGroupedLinear:
     def wq(self):
         return capi.qparam(self.weight, self.w_bits, self.w_signed, self.w_scale, self._neg_w_zero)
 
-    def __call__(self, x):
-        """fp32 rows (..., in_features) -> (..., out_features)."""
+    def quantize(self, x):
+        """fp32 rows (..., in_features) -> (packed, des): the activation quantiser's codes of x / awq_scale, by qe_quantize_pack
+        with the per-input-channel scale s_k and the per-tensor zero repeated (inner = 1).  des is host integers."""
+        if self.a_scale is None:
+            raise ValueError("PackedGroupedLinear.quantize: the layer has no activation quantiser (set_quantizer)")
+        x2 = x.reshape(-1, x.shape[-1]).contiguous().float()
+        codes, flag = capi.quantize_pack(x2, self._a_scale_k, self._a_zero_k, self.a_qmin, self.a_qmax, self.a_bits, self.a_signed)
+        if int(flag.item()) != 0:
+            raise RuntimeError(OUT_OF_RANGE)
+        return codes, (self.a_bits, int(self.a_signed), *x.shape)
+
+    def call_packed(self, xq, x_des):
+        """Activation codes as quantize() returns them -> the fp32 (..., out_features) output on qe_quantlinear_grouped."""
+        n_bits, sign, *lead, K = _host_des(x_des)
+        if K != self.K:
+            raise ValueError("codes of %d input features for a linear of %d" % (K, self.K))
+        B = 1
+        for v in lead:
+            B *= v
+        x = capi.qparam(xq, n_bits, sign, self.a_scale, self._neg_a_zero)
+        y = capi.quantlinear_grouped(x, self.wq(), self.group_size, self.bias, B, K, self.O, x_symmetric=self.a_centred,
+                                     w_symmetric=self.w_centred)
+        return y.reshape(*lead, self.O)
+
+    def __call__(self, x, route="float"):
+        """fp32 rows (..., in_features) -> (..., out_features).  route="float": the fp32 rows themselves meet the weight codes;
+        route="packed": call_packed(*quantize(x)).  Not bit-identical: the packed route quantises the activations."""
+        if route == "packed":
+            return self.call_packed(*self.quantize(x))
+        if route != "float":
+            raise ValueError("route must be 'packed' or 'float'")
         x2 = x.reshape(-1, x.shape[-1]).contiguous().float()
         y = capi.quantlinear_grouped_float_input(x2, self.wq(), self.group_size, self.bias, self.O, x_mul=self.x_mul,
                                                  symmetric=self.symmetric)
