@@ -558,6 +558,48 @@ int qe_quantlinear_float_input_residual(const float *x, const qe_qparam *w, cons
                                         const float *residual, float *out, void *workspace, size_t workspace_bytes,
                                         qe_stream_t stream);
 
+/* qe_quantlinear_grouped_requant / qe_quantlinear_grouped_residual -- the same two fused forms of qe_quantlinear_grouped:
+ *   codes = qe_quantize_pack_act(qe_quantlinear_grouped(x, w, ..., bias, B, K, O), act, rq)   (bit for bit; B x O elements)
+ *   out   = qe_quantlinear_grouped(x, w, ..., bias, B, K, O) + residual                       (one fp32 add, bit for bit)
+ * x, w, group_size, x_symmetric, w_symmetric, bias, B, K, O exactly as for qe_quantlinear_grouped.  rq, codes, status, act as
+ * for qe_quantlinear_requant: module convention, n_param 1 or O (per output feature -- what a grouped consumer's quantiser
+ * is, with its awq_scale folded into the scale).  residual, out as for qe_quantlinear_residual: out == residual (in place) is
+ * allowed.
+ * Refused before any device work, in this order: everything qe_quantlinear_grouped refuses, in its order, up to and including
+ * w->n_param; then
+ *   _requant:  a NULL rq, rq->scale or rq->zero (QE_ERR_ARG); rq->n_bits outside 1..8 (QE_ERR_NBITS); rq->n_param not 1 or O;
+ *              act not a qe_act; a NULL codes with elements to write (all QE_ERR_ARG); status may be NULL;
+ *   _residual: a NULL residual or out with elements to write; out overlapping residual other than out == residual; out
+ *              overlapping x->data or w->data (all QE_ERR_ARG);
+ * then, for both, a workspace that is NULL, too small or not 16-byte aligned on path 0 (QE_ERR_WORKSPACE).
+ * _path (host-only, from the one plan the launch reads; 0 for a request the call would refuse):
+ *   1 = the fast kernel of qe_quantlinear_grouped (qe_quantlinear_grouped_path == 1) finishes the work in its epilogue; the
+ *       re-quantising form also needs an 8-bit rq, O % 16 == 0 and codes 16-byte aligned (NULL reads as aligned in the
+ *       queries).  The workspace is 0 bytes;
+ *   0 = two passes inside the call: qe_quantlinear_grouped into the workspace, on whichever kernel its own plan names, then
+ *       qe_quantize_pack_act, resp. the elementwise add of qe_quantlinear_residual's path 0.  Serves every request
+ *       qe_quantlinear_grouped serves.  workspace: _workspace_size() bytes, 16-byte aligned.  (_workspace_size, not
+ *       _workspace_bytes as the per-row trio has it: the grouped CONVOLUTIONS promise that no qe_*grouped*_workspace_bytes
+ *       query exists, and their export test reads that promise off every name in this header.)                          */
+int qe_quantlinear_grouped_requant_path(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric,
+                                        int32_t w_symmetric, int64_t B, int32_t K, int32_t O, const qe_requant *rq,
+                                        const uint8_t *codes);
+size_t qe_quantlinear_grouped_requant_workspace_size(const qe_qparam *x, const qe_qparam *w, int32_t group_size,
+                                                      int32_t x_symmetric, int32_t w_symmetric, int64_t B, int32_t K, int32_t O,
+                                                      const qe_requant *rq, const uint8_t *codes);
+int qe_quantlinear_grouped_requant(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric,
+                                   int32_t w_symmetric, const float *bias, int64_t B, int32_t K, int32_t O, int32_t act,
+                                   const qe_requant *rq, uint8_t *codes, int32_t *status, void *workspace,
+                                   size_t workspace_bytes, qe_stream_t stream);
+int qe_quantlinear_grouped_residual_path(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric,
+                                         int32_t w_symmetric, int64_t B, int32_t K, int32_t O);
+size_t qe_quantlinear_grouped_residual_workspace_size(const qe_qparam *x, const qe_qparam *w, int32_t group_size,
+                                                       int32_t x_symmetric, int32_t w_symmetric, int64_t B, int32_t K, int32_t O);
+int qe_quantlinear_grouped_residual(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric,
+                                    int32_t w_symmetric, const float *bias, int64_t B, int32_t K, int32_t O,
+                                    const float *residual, float *out, void *workspace, size_t workspace_bytes,
+                                    qe_stream_t stream);
+
 /* qe_quantlinear_bf16 -- qe_quantlinear with a bf16 result, for a consumer that would round it anyway (the q / k / v
  * projections in front of qe_attention_bf16_stored):
  *   out[b, o] = bf16( y[b, o] * post_scale ),   y = qe_quantlinear(x, w, bias, B, K, O)      (B x O row-major bf16 bit patterns)

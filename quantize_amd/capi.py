@@ -140,6 +140,12 @@ PROTOTYPES = {
     "qe_quantlinear_grouped_float_input_path": (_i32, [_vp, _vp, _pq, _i32, _i32, _i64, _i32, _i32]),
     "qe_quantlinear_grouped": (_i32, [_pq, _pq, _i32, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp]),
     "qe_quantlinear_grouped_path": (_i32, [_pq, _pq, _i32, _i32, _i32, _i64, _i32, _i32]),
+    "qe_quantlinear_grouped_requant_path": (_i32, [_pq, _pq, _i32, _i32, _i32, _i64, _i32, _i32, _pr, _vp]),
+    "qe_quantlinear_grouped_requant_workspace_size": (_sz, [_pq, _pq, _i32, _i32, _i32, _i64, _i32, _i32, _pr, _vp]),
+    "qe_quantlinear_grouped_requant": (_i32, [_pq, _pq, _i32, _i32, _i32, _vp, _i64, _i32, _i32, _i32, _pr, _vp, _vp, _vp, _sz, _vp]),
+    "qe_quantlinear_grouped_residual_path": (_i32, [_pq, _pq, _i32, _i32, _i32, _i64, _i32, _i32]),
+    "qe_quantlinear_grouped_residual_workspace_size": (_sz, [_pq, _pq, _i32, _i32, _i32, _i64, _i32, _i32]),
+    "qe_quantlinear_grouped_residual": (_i32, [_pq, _pq, _i32, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "qe_quantlinear_requant_path": (_i32, [_pq, _pq, _i64, _i32, _i32, _pr, _vp]),
     "qe_quantlinear_requant_workspace_bytes": (_sz, [_pq, _pq, _i64, _i32, _i32, _pr, _vp]),
     "qe_quantlinear_requant": (_i32, [_pq, _pq, _vp, _i64, _i32, _i32, _i32, _pr, _vp, _vp, _vp, _sz, _vp]),
@@ -792,6 +798,57 @@ def quantlinear_grouped(xq, wq, group_size, bias, B, K, O, out=None, stream=None
     check(lib().qe_quantlinear_grouped(ctypes.byref(xq), ctypes.byref(wq), int(group_size), 1 if x_symmetric else 0,
                                        1 if w_symmetric else 0, _ptr(bias), int(B), int(K), int(O), out.data_ptr(),
                                        _stream(stream)))
+    return out
+
+
+def _grouped_args(xq, wq, group_size, x_symmetric, w_symmetric):
+    return (ctypes.byref(xq), ctypes.byref(wq), int(group_size), 1 if x_symmetric else 0, 1 if w_symmetric else 0)
+
+
+def linear_grouped_requant_path(xq, wq, group_size, B, K, O, rq, codes=None, x_symmetric=False, w_symmetric=False):
+    """qe_quantlinear_grouped_requant_path (host-only): 1 = the int8 matrix-core kernel stores the codes itself, 0 = two passes
+    inside the call.  codes=None asks for a 16-byte aligned buffer (torch allocations are)."""
+    return int(lib().qe_quantlinear_grouped_requant_path(*_grouped_args(xq, wq, group_size, x_symmetric, w_symmetric), int(B), int(K),
+                                                         int(O), ctypes.byref(rq), _ptr(codes)))
+
+
+def quantlinear_grouped_requant(xq, wq, group_size, bias, B, K, O, rq, act=None, codes=None, status=None, workspace=None,
+                                stream=None, x_symmetric=False, w_symmetric=False):
+    """qe_quantlinear_grouped_requant: the consumer's codes of act(quantlinear_grouped(...)) (B x O elements; rq per tensor or
+    per output feature).  Returns (codes, status)."""
+    import torch
+    dev = wq._keep[0].device
+    if codes is None:
+        codes = torch.empty(packed_nbytes(B * O, rq.n_bits), dtype=torch.uint8, device=dev)
+    status = _status(status, dev)
+    g = _grouped_args(xq, wq, group_size, x_symmetric, w_symmetric)
+    need = int(lib().qe_quantlinear_grouped_requant_workspace_size(*g, int(B), int(K), int(O), ctypes.byref(rq), codes.data_ptr()))
+    ws = _given_ws(workspace, need, dev)
+    check(lib().qe_quantlinear_grouped_requant(*g, _ptr(bias), int(B), int(K), int(O), ACTS[act], ctypes.byref(rq), codes.data_ptr(),
+                                               status.data_ptr(), *_prep(ws), _stream(stream)))
+    return codes, status
+
+
+def linear_grouped_residual_path(xq, wq, group_size, B, K, O, x_symmetric=False, w_symmetric=False):
+    """qe_quantlinear_grouped_residual_path (host-only): 1 = the int8 matrix-core kernel adds the residual in its epilogue."""
+    return int(lib().qe_quantlinear_grouped_residual_path(*_grouped_args(xq, wq, group_size, x_symmetric, w_symmetric), int(B), int(K),
+                                                          int(O)))
+
+
+def quantlinear_grouped_residual(xq, wq, group_size, bias, B, K, O, residual, out=None, workspace=None, stream=None,
+                                 x_symmetric=False, w_symmetric=False):
+    """qe_quantlinear_grouped_residual: out = quantlinear_grouped(...) + residual (out=None: a new tensor; out=residual: in
+    place)."""
+    import torch
+    assert residual.is_contiguous() and residual.dtype == torch.float32 and residual.numel() == B * O
+    dev = residual.device
+    if out is None:
+        out = torch.empty((B, O), dtype=torch.float32, device=dev)
+    g = _grouped_args(xq, wq, group_size, x_symmetric, w_symmetric)
+    need = int(lib().qe_quantlinear_grouped_residual_workspace_size(*g, int(B), int(K), int(O)))
+    ws = _given_ws(workspace, need, dev)
+    check(lib().qe_quantlinear_grouped_residual(*g, _ptr(bias), int(B), int(K), int(O), residual.data_ptr(), out.data_ptr(),
+                                                *_prep(ws), _stream(stream)))
     return out
 
 

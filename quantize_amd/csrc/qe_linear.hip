@@ -1274,7 +1274,7 @@ __global__ __launch_bounds__(256) void add_residual_kernel(const float *y, const
     for (int64_t i = 4 * n4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = y[i] + res[i];
 }
 
-static int launch_add_residual(const float *y, const float *res, float *out, int64_t n, hipStream_t s)
+int launch_add_residual(const float *y, const float *res, float *out, int64_t n, hipStream_t s)
 {
     if (n <= 0) return QE_OK;
     const ElementwiseGrid g = elementwise_grid(n, 4, reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(res) |

@@ -48,5 +48,7 @@ inline ElementwiseGrid elementwise_grid(int64_t n, int width, uintptr_t addrs)
 void launch_linear_bf16in(const LinBf16Args &a, bool residual, int64_t blocks, hipStream_t s);
 // out[i] = fp32 of the bf16 bit pattern x[i] (exact): path 0 of qe_quantlinear_bf16_input
 void launch_widen_bf16(const uint16_t *x, float *out, int64_t n, hipStream_t s);
+// out = y + res, one fp32 add per element (qe_linear.hip): path 0 of every residual form, the grouped linear's included
+int launch_add_residual(const float *y, const float *res, float *out, int64_t n, hipStream_t s);
 
 }  // namespace qe

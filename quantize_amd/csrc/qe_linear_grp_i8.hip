@@ -29,7 +29,22 @@
 // condition.
 //
 // Plain kernel (everything else): one thread per output, group by group in k order: the three integer sums, then the fold.
+//
+// Fused forms (qe_quantlinear_grouped_residual, qe_quantlinear_grouped_requant): two more epilogues of the fast kernel, a
+// template parameter, all of it behind the barrier that frees the stage buffers.  GQ_RES adds a residual to y in both store
+// arms; on the float4 arm a tile's residual pieces are requested before its patch transposition, with the store's own row
+// mapping, so out == residual is safe.  GQ_CODES / GQ_CODES_GELU store the consumer's 8-bit codes of y / gelu(y) with
+// qe_elementwise.hpp's functions (the ones qe_quantize_pack_act runs): the feature is on the lane, so a per-feature quantiser
+// is ONE scale and one zero in a register per column tile, as sw and zw are in the K loop.  The codes skip the fp32 patch:
+// the four waves write bytes into one [128][128]-byte image of the workgroup's tile in the free stage buffers -- its 16-byte
+// pieces XOR-swizzled by 2 ((row >> 2) & 3), which sends the two half waves of a byte write (rows 4 apart, 32 consecutive
+// bytes each) to disjoint banks -- and after one barrier 256 threads store the image as 16-byte pieces, 128 contiguous bytes
+// per row.  GELU runs in a loop that is not unrolled (one erf body per 32 x 32 tile): the lane parks its 16 values of the
+// tile in a private LDS column behind the image and reads them back by loop index.  Where the fused instance is not
+// eligible the entry points run two passes: qe_quantlinear_grouped into the workspace, then qe_quantize_pack_act or the add.
 #include "qe_common.h"
+#include "qe_elementwise.hpp"
+#include "qe_linear_bf16in.hpp"     // launch_add_residual: the elementwise add of qe_quantlinear_residual's path 0
 
 namespace qe {
 
@@ -53,6 +68,12 @@ struct LinGrpI8Args {
     int G, NG;              // group size, groups per row (K / G)
     int64_t B;
     int K, O;
+    // the fused epilogues (unused by GQ_F32)
+    const float *res;       // GQ_RES: out = y + res (res == out allowed)
+    uint8_t *codes;         // GQ_CODES*: B x O stored 8-bit codes of y / gelu(y)
+    int32_t *status;        // GQ_CODES*: bit 0 set when a code fails the range test (NaN included)
+    int rq_per_col;         // GQ_CODES*: one scale and zero per output feature (else one of each)
+    QeRq rq;
 };
 
 // stored u of an n_bits stream -> the centred integer u - 2^(bits-1)
@@ -112,7 +133,17 @@ __device__ __forceinline__ void widen_nibbles(uint32_t w, uint32_t &lo, uint32_t
     hi = (__builtin_amdgcn_perm(o, e, 0x07030602u) + 0x78787878u) ^ 0x80808080u;
 }
 
-template <int WB, bool WZ, bool XZ>
+// Epilogue of the fast kernel, a template parameter and never a runtime branch: y (GQ_F32), y + res (GQ_RES), the consumer's
+// 8-bit codes of y / gelu(y) (GQ_CODES, GQ_CODES_GELU).
+enum { GQ_F32 = 0, GQ_RES = 1, GQ_CODES = 2, GQ_CODES_GELU = 3 };
+template <int EPI> constexpr bool gq_codes() { return EPI == GQ_CODES || EPI == GQ_CODES_GELU; }
+// byte (row rl, column cl) of the [128][128] code image; piece pc of row rl is at gq_img(rl, 16 * pc)
+__device__ __forceinline__ int gq_img(int rl, int cl)
+{
+    return rl * GQ_T + 16 * ((cl >> 4) ^ (((rl >> 2) & 3) << 1)) + (cl & 15);
+}
+
+template <int WB, bool WZ, bool XZ, int EPI>
 __global__ __launch_bounds__(256, 2) void linear_grp_i8_mfma_kernel(const LinGrpI8Args a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lsm[];
@@ -324,12 +355,68 @@ __global__ __launch_bounds__(256, 2) void linear_grp_i8_mfma_kernel(const LinGrp
         }
     }
     __syncthreads();                                      // every wave is done with the stage buffers; T is complete
+    if constexpr (gq_codes<EPI>()) {
+        // The feature is on the lane: the consumer's scale and zero of this lane's column are one register each per column
+        // tile (a clamped address beyond O, as the bias).  Bytes into the image, one barrier, 16-byte pieces out.
+        uint8_t *img = lsm;
+        float *mine = reinterpret_cast<float *>(lsm + GQ_T * GQ_T) + wave * (16 * 64) + lane;      // GELU: [16][64] per wave
+        bool bad = false;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int cl = wn * 64 + j * 32 + col, c = n0 + cl, cc = min(c, a.O - 1);
+            const float bias = a.bias != nullptr ? a.bias[cc] : 0.0f;
+            const float sc = a.rq.scale[a.rq_per_col ? cc : 0], zr = a.rq.zero[a.rq_per_col ? cc : 0];
+            const float tj = XZ ? tcol[cl] : 0.0f;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int rl0 = wm * 64 + i * 32 + 4 * h;
+                float v[16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int rl = rl0 + (r & 3) + 8 * (r >> 2);
+                    const float t = XZ ? fmaf(-rzx[rl], tj, acco[i][j][r]) : acco[i][j][r];
+                    v[r] = fmaf(rsx[rl], t, bias);
+                }
+                if constexpr (EPI == GQ_CODES_GELU) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) mine[r * 64] = v[r];
+#pragma unroll 1
+                    for (int r = 0; r < 16; ++r) {
+                        const int rl = rl0 + (r & 3) + 8 * (r >> 2);
+                        bool b1 = false;
+                        img[gq_img(rl, cl)] = (uint8_t)qe_rq_code(qe_gelu(mine[r * 64]), sc, zr, a.rq, b1);
+                        bad |= b1 && m0 + rl < a.B && c < a.O;
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int rl = rl0 + (r & 3) + 8 * (r >> 2);
+                        bool b1 = false;
+                        img[gq_img(rl, cl)] = (uint8_t)qe_rq_code(v[r], sc, zr, a.rq, b1);
+                        bad |= b1 && m0 + rl < a.B && c < a.O;
+                    }
+                }
+            }
+        }
+        __syncthreads();                                  // the image is complete
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int p = tid + 256 * k, rl = p >> 3, pc = p & 7;
+            const uint4 v = *reinterpret_cast<const uint4 *>(img + gq_img(rl, 16 * pc));
+            const int64_t row = m0 + rl;
+            const int c16 = n0 + 16 * pc;                 // O % 16 == 0: a piece lies wholly below O or wholly beyond it
+            if (row < a.B && c16 < a.O) *reinterpret_cast<uint4 *>(a.codes + row * a.O + c16) = v;
+        }
+        if (__builtin_amdgcn_ballot_w64(bad) != 0ull && lane == 0 && a.status != nullptr) atomicOr(a.status, 1);
+        return;
+    }
     // D has the batch row on the register and the feature on the lane.  Each wave turns its 32 x 32 tiles through a private
     // LDS patch (the stage buffers are free now) and writes 8 rows x 128 contiguous bytes per store instruction.  (A wave's
     // own LDS operations complete in order: its reads see its writes, a later tile's writes cannot overtake them.)
     float *patch = reinterpret_cast<float *>(lsm) + wave * (32 * 36);
     const int rrow = lane >> 3, rq = lane & 7;
-    const bool vec4 = (a.O & 3) == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0;
+    const bool vec4 = (a.O & 3) == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0 &&
+                      (EPI != GQ_RES || (reinterpret_cast<uintptr_t>(a.res) & 15) == 0);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int c = n0 + wn * 64 + j * 32 + col;
@@ -347,13 +434,22 @@ __global__ __launch_bounds__(256, 2) void linear_grp_i8_mfma_kernel(const LinGrp
                 v[r] = fmaf(rsx[rl], t, bias);
             }
             if (vec4) {
+                const int c4 = n0 + wn * 64 + j * 32 + 4 * rq;       // O % 4 == 0: a piece lies wholly below O or wholly beyond it
+                float4 r4v[4] = {};                       // GQ_RES: the tile's residual pieces, in flight under the transposition
+                if constexpr (EPI == GQ_RES) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int64_t row = row0 + 8 * k + rrow;
+                        if (row < a.B && c4 < a.O) r4v[k] = *reinterpret_cast<const float4 *>(a.res + row * a.O + c4);
+                    }
+                }
 #pragma unroll
                 for (int r = 0; r < 16; ++r) patch[((r & 3) + 8 * (r >> 2) + 4 * h) * 36 + col] = v[r];
-                const int c4 = n0 + wn * 64 + j * 32 + 4 * rq;       // O % 4 == 0: a piece lies wholly below O or wholly beyond it
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const int rt = 8 * k + rrow;
-                    const float4 o4 = *reinterpret_cast<const float4 *>(patch + rt * 36 + 4 * rq);
+                    float4 o4 = *reinterpret_cast<const float4 *>(patch + rt * 36 + 4 * rq);
+                    if constexpr (EPI == GQ_RES) { o4.x += r4v[k].x; o4.y += r4v[k].y; o4.z += r4v[k].z; o4.w += r4v[k].w; }
                     const int64_t row = row0 + rt;
                     if (row < a.B && c4 < a.O) *reinterpret_cast<float4 *>(a.out + row * a.O + c4) = o4;
                 }
@@ -361,7 +457,7 @@ __global__ __launch_bounds__(256, 2) void linear_grp_i8_mfma_kernel(const LinGrp
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int64_t row = row0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                    if (row < a.B && c < a.O) a.out[row * a.O + c] = v[r];
+                    if (row < a.B && c < a.O) a.out[row * a.O + c] = EPI == GQ_RES ? v[r] + a.res[row * a.O + c] : v[r];
                 }
             }
         }
@@ -369,18 +465,23 @@ __global__ __launch_bounds__(256, 2) void linear_grp_i8_mfma_kernel(const LinGrp
 }
 
 // ---------------------------------------------------------------------------------------------
-// Host side: one plan, read by the path query and by the launch.  No HIP call in it.
+// Host side: one plan, read by the path and workspace queries and by the launch.  No HIP call in it.
 // ---------------------------------------------------------------------------------------------
 struct LinGrpI8Plan {
     int fast;               // 1: linear_grp_i8_mfma_kernel, 0: linear_grp_i8_plain_kernel
     int w4, wz, xz;         // the fast kernel's instance
     int64_t blocks;
+    int epi;                // the epilogue the kernel runs: the request's on a fused plan, GQ_F32 on a two-pass plan
+    int two_pass;           // a fused form's request the kernel cannot finish: y into the workspace, then the elementwise pass
+    size_t ws;              // workspace bytes (y of a two-pass plan)
 };
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-// a validated request (check_grp_i8)
-LinGrpI8Plan plan_grp_i8(const qe_qparam *x, const qe_qparam *w, int G, int x_symmetric, int w_symmetric, int64_t B, int K, int O)
+// a validated request (check_grp_i8; check_grp_rq for the re-quantising form).  epi: the form asked for; rq and codes (its
+// address alone; NULL reads as aligned) belong to GQ_CODES*
+LinGrpI8Plan plan_grp_i8(const qe_qparam *x, const qe_qparam *w, int G, int x_symmetric, int w_symmetric, int64_t B, int K, int O,
+                         int epi = GQ_F32, const qe_requant *rq = nullptr, const void *codes = nullptr)
 {
     LinGrpI8Plan p = {};
     p.fast = x->n_bits == 8 && (w->n_bits == 4 || w->n_bits == 8) && (G == 32 || G == 64 || G == 128) && K > 0 &&
@@ -389,6 +490,11 @@ LinGrpI8Plan plan_grp_i8(const qe_qparam *x, const qe_qparam *w, int G, int x_sy
     p.wz = w_symmetric == 0;
     p.xz = x_symmetric == 0;
     p.blocks = p.fast ? ceil_div64(B, GQ_T) * ceil_div64(O, GQ_T) : ceil_div64(B * O, 256);
+    const bool codes_form = epi == GQ_CODES || epi == GQ_CODES_GELU;
+    const bool fused = p.fast && (!codes_form || (rq->n_bits == 8 && O % 16 == 0 && aligned16(codes)));
+    p.two_pass = epi != GQ_F32 && !fused;
+    p.epi = p.two_pass ? (int)GQ_F32 : epi;
+    p.ws = p.two_pass ? (size_t)B * (size_t)O * sizeof(float) : 0;
     return p;
 }
 
@@ -402,10 +508,24 @@ int check_grp_i8(const qe_qparam *x, const qe_qparam *w, int G, int64_t B, int K
     return (int64_t)w->n_param == (int64_t)O * (K / G) ? QE_OK : QE_ERR_ARG;
 }
 
+// ... then the consumer's quantiser and the activation of the re-quantising form
+int check_grp_rq(const qe_requant *rq, int act, int O)
+{
+    if (int rc = check_requant(rq)) return rc;
+    if (!one_or_per_channel(rq->n_param, O)) return QE_ERR_ARG;
+    return act == QE_ACT_NONE || act == QE_ACT_GELU ? QE_OK : QE_ERR_ARG;
+}
+
 template <int WB, bool WZ, bool XZ>
 void launch_grp_i8(const LinGrpI8Plan &p, const LinGrpI8Args &a, hipStream_t s)
 {
-    launch_instance<&linear_grp_i8_mfma_kernel<WB, WZ, XZ>>((unsigned)p.blocks, 256, GQ_LDS, 0, s, a);
+    const unsigned blocks = (unsigned)p.blocks;
+    switch (p.epi) {
+    case GQ_RES: launch_instance<&linear_grp_i8_mfma_kernel<WB, WZ, XZ, GQ_RES>>(blocks, 256, GQ_LDS, 0, s, a); break;
+    case GQ_CODES: launch_instance<&linear_grp_i8_mfma_kernel<WB, WZ, XZ, GQ_CODES>>(blocks, 256, GQ_LDS, 0, s, a); break;
+    case GQ_CODES_GELU: launch_instance<&linear_grp_i8_mfma_kernel<WB, WZ, XZ, GQ_CODES_GELU>>(blocks, 256, GQ_LDS, 0, s, a); break;
+    default: launch_instance<&linear_grp_i8_mfma_kernel<WB, WZ, XZ, GQ_F32>>(blocks, 256, GQ_LDS, 0, s, a); break;
+    }
 }
 
 template <int WB>
@@ -413,6 +533,27 @@ void launch_grp_i8_bits(const LinGrpI8Plan &p, const LinGrpI8Args &a, hipStream_
 {
     if (p.wz) { if (p.xz) launch_grp_i8<WB, true, true>(p, a, s); else launch_grp_i8<WB, true, false>(p, a, s); }
     else { if (p.xz) launch_grp_i8<WB, false, true>(p, a, s); else launch_grp_i8<WB, false, false>(p, a, s); }
+}
+
+// The kernel of a plan on a validated, non-empty request.  `a` carries the destination of the plan's epilogue.
+int run_grp_i8(const LinGrpI8Plan &p, LinGrpI8Args a, const qe_qparam *x, const qe_qparam *w, int G, const float *bias, int64_t B,
+               int K, int O, hipStream_t s)
+{
+    if (p.blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
+    a.x = x->data; a.w = w->data; a.x_scale = x->scale; a.x_zero = x->zero; a.w_scale = w->scale; a.w_zero = w->zero;
+    a.bias = bias;
+    a.x_bits = x->n_bits; a.x_sign = x->sign; a.x_per_row = x->n_param != 1; a.w_bits = w->n_bits; a.w_sign = w->sign;
+    a.G = G; a.NG = K / G; a.B = B; a.K = K; a.O = O;
+    if (!p.fast) hipLaunchKernelGGL(linear_grp_i8_plain_kernel, dim3((unsigned)p.blocks), dim3(256), 0, s, a);
+    else if (p.w4) launch_grp_i8_bits<4>(p, a, s);
+    else launch_grp_i8_bits<8>(p, a, s);
+    QE_LAUNCH_CHECK();
+    return QE_OK;
+}
+
+bool workspace_ok(const LinGrpI8Plan &p, const void *workspace, size_t workspace_bytes)
+{
+    return p.ws == 0 || (workspace != nullptr && workspace_bytes >= p.ws && aligned16(workspace));
 }
 
 }  // namespace
@@ -436,16 +577,93 @@ extern "C" int qe_quantlinear_grouped(const qe_qparam *x, const qe_qparam *w, in
     if (out == nullptr && B * O > 0) return QE_ERR_ARG;
     if (B == 0 || O == 0) return QE_OK;
     const LinGrpI8Plan p = plan_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O);
-    if (p.blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
     LinGrpI8Args a = {};
-    a.x = x->data; a.w = w->data; a.x_scale = x->scale; a.x_zero = x->zero; a.w_scale = w->scale; a.w_zero = w->zero;
-    a.bias = bias; a.out = out;
-    a.x_bits = x->n_bits; a.x_sign = x->sign; a.x_per_row = x->n_param != 1; a.w_bits = w->n_bits; a.w_sign = w->sign;
-    a.G = group_size; a.NG = K / group_size; a.B = B; a.K = K; a.O = O;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!p.fast) hipLaunchKernelGGL(linear_grp_i8_plain_kernel, dim3((unsigned)p.blocks), dim3(256), 0, s, a);
-    else if (p.w4) launch_grp_i8_bits<4>(p, a, s);
-    else launch_grp_i8_bits<8>(p, a, s);
-    QE_LAUNCH_CHECK();
-    return QE_OK;
+    a.out = out;
+    return run_grp_i8(p, a, x, w, group_size, bias, B, K, O, static_cast<hipStream_t>(stream));
 }
+
+// Fused forms (include/quant_engine.h): the consumer's codes of y / gelu(y), and y + residual.  Path 1 is the fast kernel with
+// the epilogue compiled in, path 0 the plan's two passes: y into the workspace on whichever kernel the plain plan names, then
+// qe_quantize_pack_act or the elementwise add.
+extern "C" int qe_quantlinear_grouped_requant_path(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric,
+                                                   int32_t w_symmetric, int64_t B, int32_t K, int32_t O, const qe_requant *rq,
+                                                   const uint8_t *codes)
+{
+    using namespace qe;
+    if (check_grp_i8(x, w, group_size, B, K, O) != QE_OK || check_grp_rq(rq, QE_ACT_NONE, O) != QE_OK) return 0;
+    return !plan_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O, GQ_CODES, rq, codes).two_pass;
+}
+
+extern "C" size_t qe_quantlinear_grouped_requant_workspace_size(const qe_qparam *x, const qe_qparam *w, int32_t group_size,
+                                                                 int32_t x_symmetric, int32_t w_symmetric, int64_t B, int32_t K,
+                                                                 int32_t O, const qe_requant *rq, const uint8_t *codes)
+{
+    using namespace qe;
+    if (check_grp_i8(x, w, group_size, B, K, O) != QE_OK || check_grp_rq(rq, QE_ACT_NONE, O) != QE_OK) return 0;
+    return plan_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O, GQ_CODES, rq, codes).ws;
+}
+
+extern "C" int qe_quantlinear_grouped_requant(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric,
+                                              int32_t w_symmetric, const float *bias, int64_t B, int32_t K, int32_t O, int32_t act,
+                                              const qe_requant *rq, uint8_t *codes, int32_t *status, void *workspace,
+                                              size_t workspace_bytes, qe_stream_t stream)
+{
+    using namespace qe;
+    if (int rc = check_grp_i8(x, w, group_size, B, K, O)) return rc;
+    if (int rc = check_grp_rq(rq, act, O)) return rc;
+    if (codes == nullptr && B * O > 0) return QE_ERR_ARG;
+    if (B == 0 || O == 0) return QE_OK;
+    const int epi = act == QE_ACT_GELU ? GQ_CODES_GELU : GQ_CODES;
+    const LinGrpI8Plan p = plan_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O, epi, rq, codes);
+    if (!workspace_ok(p, workspace, workspace_bytes)) return QE_ERR_WORKSPACE;
+    LinGrpI8Args a = {};
+    a.out = static_cast<float *>(workspace);
+    a.codes = codes; a.status = status; a.rq_per_col = rq->n_param != 1; a.rq = make_qe_rq(*rq);
+    if (int rc = run_grp_i8(p, a, x, w, group_size, bias, B, K, O, static_cast<hipStream_t>(stream))) return rc;
+    if (!p.two_pass) return QE_OK;
+    // per-feature rq: channel = output feature o, element (b, o) -> (i / 1) % O
+    return qe_quantize_pack_act(a.out, B * (int64_t)O, act, rq->scale, rq->zero, rq->n_param, 1, rq->qmin, rq->qmax, rq->n_bits,
+                                rq->sign, codes, nullptr, status, stream);
+}
+
+extern "C" int qe_quantlinear_grouped_residual_path(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric,
+                                                    int32_t w_symmetric, int64_t B, int32_t K, int32_t O)
+{
+    using namespace qe;
+    if (check_grp_i8(x, w, group_size, B, K, O) != QE_OK) return 0;
+    return !plan_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O, GQ_RES).two_pass;
+}
+
+extern "C" size_t qe_quantlinear_grouped_residual_workspace_size(const qe_qparam *x, const qe_qparam *w, int32_t group_size,
+                                                                  int32_t x_symmetric, int32_t w_symmetric, int64_t B, int32_t K,
+                                                                  int32_t O)
+{
+    using namespace qe;
+    if (check_grp_i8(x, w, group_size, B, K, O) != QE_OK) return 0;
+    return plan_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O, GQ_RES).ws;
+}
+
+extern "C" int qe_quantlinear_grouped_residual(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric,
+                                               int32_t w_symmetric, const float *bias, int64_t B, int32_t K, int32_t O,
+                                               const float *residual, float *out, void *workspace, size_t workspace_bytes,
+                                               qe_stream_t stream)
+{
+    using namespace qe;
+    if (int rc = check_grp_i8(x, w, group_size, B, K, O)) return rc;
+    if ((residual == nullptr || out == nullptr) && B * O > 0) return QE_ERR_ARG;
+    if (B == 0 || O == 0) return QE_OK;
+    const int64_t n = B * (int64_t)O;
+    const Span so = span_of(out, n * 4);
+    if (!same_or_disjoint(residual, out, n * 4) || overlaps(so, span_of(x->data, qe_packed_nbytes(B * (int64_t)K, x->n_bits))) ||
+        overlaps(so, span_of(w->data, qe_packed_nbytes((int64_t)O * K, w->n_bits))))
+        return QE_ERR_ARG;
+    const LinGrpI8Plan p = plan_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O, GQ_RES);
+    if (!workspace_ok(p, workspace, workspace_bytes)) return QE_ERR_WORKSPACE;
+    LinGrpI8Args a = {};
+    a.out = p.two_pass ? static_cast<float *>(workspace) : out;
+    a.res = residual;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = run_grp_i8(p, a, x, w, group_size, bias, B, K, O, s)) return rc;
+    return p.two_pass ? launch_add_residual(a.out, residual, out, n, s) : QE_OK;
+}
+

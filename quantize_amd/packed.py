@@ -482,18 +482,54 @@ class PackedGroupedLinear:
             raise RuntimeError(OUT_OF_RANGE)
         return codes, (self.a_bits, int(self.a_signed), *x.shape)
 
-    def call_packed(self, xq, x_des):
-        """Activation codes as quantize() returns them -> the fp32 (..., out_features) output on qe_quantlinear_grouped."""
+    def xq(self, codes, n_bits=None, signed=None):
+        """A code stream of this layer's activation quantiser as the operand of qe_quantlinear_grouped: the per-tensor scale
+        (awq_scale lives in the codes) and the zero in the kernel convention."""
+        if self.a_scale is None:
+            raise ValueError("PackedGroupedLinear.xq: the layer has no activation quantiser (set_quantizer)")
+        return capi.qparam(codes, self.a_bits if n_bits is None else n_bits, self.a_signed if signed is None else signed,
+                           self.a_scale, self._neg_a_zero)
+
+    def requant(self):
+        """This layer's activation quantiser as a producer must apply it (the epilogue of the layer that feeds this one, or
+        qe_layernorm_quantize_pack): per input channel, scale s_k = a_scale * awq_scale[k] and the per-tensor zero repeated,
+        module convention, n_param == in_features."""
+        if self.a_scale is None:
+            raise ValueError("PackedGroupedLinear.requant: the layer has no activation quantiser (set_quantizer)")
+        return capi.requant(self._a_scale_k, self._a_zero_k, self.a_qmin, self.a_qmax, self.a_bits, self.a_signed)
+
+    def _operands(self, xq, x_des):
         n_bits, sign, *lead, K = _host_des(x_des)
         if K != self.K:
             raise ValueError("codes of %d input features for a linear of %d" % (K, self.K))
         B = 1
         for v in lead:
             B *= v
-        x = capi.qparam(xq, n_bits, sign, self.a_scale, self._neg_a_zero)
-        y = capi.quantlinear_grouped(x, self.wq(), self.group_size, self.bias, B, K, self.O, x_symmetric=self.a_centred,
-                                     w_symmetric=self.w_centred)
+        return self.xq(xq, n_bits, sign), lead, B, dict(x_symmetric=self.a_centred, w_symmetric=self.w_centred)
+
+    def call_packed(self, xq, x_des):
+        """Activation codes as quantize() returns them -> the fp32 (..., out_features) output on qe_quantlinear_grouped."""
+        x, lead, B, sym = self._operands(xq, x_des)
+        y = capi.quantlinear_grouped(x, self.wq(), self.group_size, self.bias, B, self.K, self.O, **sym)
         return y.reshape(*lead, self.O)
+
+    def call_packed_residual(self, xq, x_des, residual, out=None):
+        """call_packed(xq, x_des) + residual, the add in the kernel's epilogue where it can be (qe_quantlinear_grouped_residual):
+        bit-identical to the two steps.  residual: contiguous fp32 of rows x out_features elements; out=residual: in place."""
+        x, lead, B, sym = self._operands(xq, x_des)
+        return capi.quantlinear_grouped_residual(x, self.wq(), self.group_size, self.bias, B, self.K, self.O, residual, out=out, **sym)
+
+    def call_packed_requant(self, xq, x_des, consumer_rq, act=None, status=None):
+        """The consumer's codes of act(call_packed(xq, x_des)) (act None or "gelu"), stored by this layer's kernel itself where
+        it can (qe_quantlinear_grouped_requant): bit-identical to capi.quantize_pack_act of the fp32 output.  consumer_rq: the
+        consumer's requant() (per tensor or per output feature of this layer).  Returns (codes, des) with des on the host;
+        status: a device int32 the range flag accumulates in (None: raise when the codes are out of range)."""
+        x, lead, B, sym = self._operands(xq, x_des)
+        codes, flag = capi.quantlinear_grouped_requant(x, self.wq(), self.group_size, self.bias, B, self.K, self.O, consumer_rq,
+                                                       act=act, status=status, **sym)
+        if status is None and int(flag.item()) != 0:
+            raise RuntimeError(OUT_OF_RANGE)
+        return codes, (consumer_rq.n_bits, int(consumer_rq.sign), *lead, self.O)
 
     def __call__(self, x, route="float"):
         """fp32 rows (..., in_features) -> (..., out_features).  route="float": the fp32 rows themselves meet the weight codes;

@@ -25,6 +25,8 @@ the bf16 kernel would have rounded to anyway, so logits and block outputs are bi
 ctx="bf16" (on top of qkv="bf16") has the attention kernel write its context as bf16 rows as well (qe_attention_bf16_ctx: the
 fp32 context rounded once) and out_proj read them as stored (qe_quantlinear_bf16_input, residual add in its epilogue): one
 rounding of the context to 8 significant bits, so NOT bit-identical to ctx="fp32".
+An MLP linear whose state carries `w_group_size` is group-quantised (AWQ layout, packed.PackedGroupedLinear) and runs on
+qe_quantlinear_grouped and its two fused forms in the same places; a block may mix grouped and per-row linears.
 The C entry points take their two-pass form wherever the fused form is not eligible (sub-8-bit or per-channel consumer codes, non-MFMA shapes, QE_LIN_EPI=0), so every step of
 the fused route exists for every model the layers route runs.  With check=False the fused route makes no device -> host
 copy or synchronisation: every range flag accumulates in one device int32, read once at the end when check=True.
@@ -36,7 +38,7 @@ import torch
 import torch.nn.functional as F
 
 from . import capi, synthetic
-from .packed import OUT_OF_RANGE, PackedConv2d, PackedLinear, PackedMultiheadAttention, quantizer_bits
+from .packed import OUT_OF_RANGE, PackedConv2d, PackedGroupedLinear, PackedLinear, PackedMultiheadAttention, quantizer_bits
 from .synthetic import pack_codes
 
 
@@ -135,8 +137,10 @@ class PackedViT:
             attn = PackedMultiheadAttention.from_state_dict(sd, pre + "self_attention.", num_heads)
             ln1 = (need(pre + "ln_1.weight"), need(pre + "ln_1.bias"))
             ln2 = (need(pre + "ln_2.weight"), need(pre + "ln_2.bias"))
-            blocks.append(_Block(pre[:-1], ln1, attn, ln2, PackedLinear.from_state_dict(sd, pre + "mlp.0."),
-                                 PackedLinear.from_state_dict(sd, pre + "mlp.3.")))
+            # an MLP linear with w_group_size beside its weights is group-quantised (PackedGroupedLinear.state_dict's keys)
+            fc1, fc2 = ((PackedGroupedLinear if pre + m + "w_group_size" in sd else PackedLinear).from_state_dict(sd, pre + m)
+                        for m in ("mlp.0.", "mlp.3."))
+            blocks.append(_Block(pre[:-1], ln1, attn, ln2, fc1, fc2))
         ln = (need("encoder.ln.weight"), need("encoder.ln.bias"))
         need("heads.head.w_des")
         head = PackedLinear.from_state_dict(sd, "heads.head.")
@@ -252,9 +256,18 @@ class PackedViT:
             x = capi.quantlinear_bf16_input(c, b.attn.out_wq(), b.attn.out_bias, E, residual=x, out=x)
         else:
             x = capi.quantlinear_float_input_residual(c, b.attn.out_wq(), b.attn.out_bias, E, x, out=x)
+        # the MLP, per layer: a group-quantised linear (PackedGroupedLinear) runs the grouped kernel's fused forms, a per-row one
+        # the per-row kernels'; each side only supplies requant() (its quantiser as the producer applies it: per input channel
+        # for a grouped layer) and xq()
         c1 = capi.layernorm_quantize_pack(x, b.ln2[0], b.ln2[1], self.eps, [b.fc1.requant()], status=status)[0][0]
-        c2 = capi.quantlinear_requant(b.fc1.xq(c1), b.fc1.wq(), b.fc1.bias, rows, b.fc1.K, b.fc1.O, b.fc2.requant(), act="gelu",
-                                      status=status)[0]
+        if isinstance(b.fc1, PackedGroupedLinear):
+            c2 = b.fc1.call_packed_requant(c1, (b.fc1.a_bits, int(b.fc1.a_signed), rows, b.fc1.K), b.fc2.requant(), act="gelu",
+                                           status=status)[0]
+        else:
+            c2 = capi.quantlinear_requant(b.fc1.xq(c1), b.fc1.wq(), b.fc1.bias, rows, b.fc1.K, b.fc1.O, b.fc2.requant(), act="gelu",
+                                          status=status)[0]
+        if isinstance(b.fc2, PackedGroupedLinear):
+            return b.fc2.call_packed_residual(c2, (b.fc2.a_bits, int(b.fc2.a_signed), rows, b.fc2.K), x, out=x)
         return capi.quantlinear_residual(b.fc2.xq(c2), b.fc2.wq(), b.fc2.bias, rows, b.fc2.K, b.fc2.O, x, out=x)
 
     # ---- calibration (synthetic models, tests, tools) ----
@@ -262,13 +275,21 @@ class PackedViT:
         """Set every activation quantiser from what reaches it in one `layers` pass: signed ones max|x| / qmax, the
         unsigned ones (fc2's, after the GELU) asymmetric over [min, max] with zero = round(min / scale)."""
         def set_q(m, t):
+            grouped = isinstance(m, PackedGroupedLinear)
+            if grouped and m.x_mul is not None:      # its quantiser sees x / awq_scale
+                t = t * m.x_mul
             if m.a_signed:
-                m.a_scale = torch.clamp(t.abs().max() / m.a_qmax, min=1e-8).reshape(1)
+                s, z = torch.clamp(t.abs().max() / m.a_qmax, min=1e-8).reshape(1), torch.zeros(1, device=t.device)
             else:
                 lo, hi = t.min(), t.max()
-                s = torch.clamp((hi - lo) / (m.a_qmax - m.a_qmin), min=1e-8)
-                m.a_scale = s.reshape(1)
-                m.a_zero = torch.round(lo / s).reshape(1)
+                s = torch.clamp((hi - lo) / (m.a_qmax - m.a_qmin), min=1e-8).reshape(1)
+                z = torch.round(lo / s).reshape(1)
+            if grouped:
+                m.set_quantizer(s, z, m.a_qmin, m.a_qmax)
+            elif m.a_signed:
+                m.a_scale = s
+            else:
+                m.a_scale, m.a_zero = s, z
         with torch.no_grad():
             N = images.shape[0]
             x = self.embed(images, "layers", None, observe=set_q)
@@ -388,13 +409,44 @@ def _lin_entries(rng, O, K, w_bits, bias, signed_act=True, a_bits=8):
     return e
 
 
-def synthetic_state_dict(arch="vit_b_16", w_bits=8, a_bits=8, seed=0, **over):
+def _grouped_lin_entries(rng, O, K, w_bits, G, bias, signed_act=True, a_bits=8):
+    """_lin_entries with group-quantised weights in PackedGroupedLinear.state_dict's keys: unsigned codes, one scale and one
+    fractional zero per (output row, group of G input channels), and a non-trivial awq_scale per input channel."""
+    half = 1 << (w_bits - 1)
+    q = rng.randint(0, 2 * half, size=(O, K))
+    std_q = np.sqrt(((2 * half) ** 2 - 1) / 12.0)
+    ws = np.sqrt(1.0 / K) / std_q * rng.uniform(0.8, 1.2, size=(O, K // G))
+    qmin, qmax = (-(1 << (a_bits - 1)), (1 << (a_bits - 1)) - 1) if signed_act else (0, (1 << a_bits) - 1)
+    e = {"weight": torch.from_numpy(pack_codes(q, w_bits, False)),
+         "w_des": torch.tensor([w_bits, 0, O, K], dtype=torch.int32),
+         "w_scale": torch.from_numpy(ws.astype(np.float32)),
+         "w_zero": torch.from_numpy((0.5 - half + rng.uniform(-0.5, 0.5, size=(O, K // G))).astype(np.float32)),
+         "w_group_size": torch.tensor(G, dtype=torch.int32),
+         "awq_scale": torch.from_numpy(rng.uniform(0.5, 2.0, size=K).astype(np.float32)),
+         "a_quantizer.scale": torch.tensor([1.0], dtype=torch.float32),
+         "a_quantizer.zero": torch.tensor([0.0], dtype=torch.float32),
+         "a_quantizer.qmin": torch.tensor(float(qmin)), "a_quantizer.qmax": torch.tensor(float(qmax))}
+    if bias:
+        e["bias"] = torch.from_numpy(rng.normal(0, 0.02, size=O).astype(np.float32))
+    return e
+
+
+def synthetic_state_dict(arch="vit_b_16", w_bits=8, a_bits=8, seed=0, mlp_group_size=None, mlp_w_bits=None, mlp_grouped=(True, True),
+                         **over):
     """A packed ViT state_dict in the key layout pack() leaves (host tensors, activation scales not calibrated: 1.0).
     Random b-bit weights scaled to unit gain, LayerNorm affine parameters near (1, 0); every activation quantiser signed
-    per tensor except fc2's (after the GELU): unsigned and asymmetric once calibrated.  See calibrated_state_dict."""
+    per tensor except fc2's (after the GELU): unsigned and asymmetric once calibrated.  See calibrated_state_dict.
+    mlp_group_size: the MLP linears (mlp_grouped: which of fc1, fc2) are group-quantised with that group size and mlp_w_bits
+    (default w_bits) bit codes, in PackedGroupedLinear's layout; None: every linear per-row, the dict unchanged."""
     cfg = dict(CONFIGS[arch])
     cfg.update(over)
     rng = np.random.RandomState(seed)
+
+    def mlp(which, O, K, signed_act):
+        if mlp_group_size is None or not mlp_grouped[which]:
+            return _lin_entries(rng, O, K, w_bits, True, signed_act, a_bits)
+        return _grouped_lin_entries(rng, O, K, mlp_w_bits or w_bits, int(mlp_group_size), True, signed_act, a_bits)
+
     E, p, C, M = cfg["width"], cfg["patch"], 3, cfg["mlp"]
     L = (cfg["image_size"] // p) ** 2 + 1
     sd = {}
@@ -423,8 +475,8 @@ def synthetic_state_dict(arch="vit_b_16", w_bits=8, a_bits=8, seed=0, **over):
         sd[att + "out_proj.weight"], sd[att + "out_proj_des"] = o["weight"], o["w_des"]
         sd[att + "out_proj_scale"], sd[att + "out_proj_zero"] = o["w_scale"], o["w_zero"]
         sd[att + "out_proj.bias"] = o["bias"]
-        synthetic.put(sd, pre + "mlp.0", _lin_entries(rng, M, E, w_bits, True, True, a_bits))
-        f2 = _lin_entries(rng, E, M, w_bits, True, False, a_bits)
+        synthetic.put(sd, pre + "mlp.0", mlp(0, M, E, True))
+        f2 = mlp(1, E, M, False)
         f2["w_scale"] = f2["w_scale"] * 0.5
         synthetic.put(sd, pre + "mlp.3", f2)
     sd["encoder.ln.weight"] = torch.ones(E, dtype=torch.float32)
