@@ -600,6 +600,39 @@ int qe_quantlinear_grouped_residual(const qe_qparam *x, const qe_qparam *w, int3
                                     const float *residual, float *out, void *workspace, size_t workspace_bytes,
                                     qe_stream_t stream);
 
+/* qe_quantconv2d_awq -- a convolution on packed activation codes whose weights are group-quantised as the reference's AWQ
+ * range estimator lays out a 4-D weight (range/awq.py: one scale and one zero per output channel and group of group_size
+ * consecutive input channels, all taps):
+ *   out[n,o,oh,ow] = act( bias[o] + sx * sum_g sw[o,g] * sum_{c in group g} sum_{kh,kw inside the image}
+ *                         (q_x[n,c,ih,iw] - zx) * (q_w[o,c,kh,kw] - zw[o,g]) )
+ * BOTH operands use the kernel convention (q - zero); zeros are fractional in general.  A tap that falls in the padding
+ * contributes nothing.  act is the identity, or max(., 0) with NaN passed through when relu != 0.
+ * x        a packed NCHW stream of N*IC*H*W codes, x->n_param == 1.  (A per-input-channel multiplier cannot act inside an
+ *          integer sum over c: the caller folds it into the activation quantiser's scale, as packed.PackedAwqConv2d.quantize
+ *          does.)
+ * w        a packed OIHW stream of OC*IC*KH*KW codes; w->scale / w->zero hold OC*(IC/group_size) elements in (o, g) order.
+ * x_symmetric, w_symmetric   host-side declarations with the meaning they have in qe_quantlinear_grouped: every zero equals
+ *          the CENTRE of its stream.  The plain kernel ignores them; 0 is always correct.
+ * bias     fp32[OC] or NULL.   out  N*OC*OH*OW floats (NCHW), fully written.   No workspace, no prepared tables.
+ * Arithmetic: every stored value u is read as the centred integer u - 2^(n_bits-1).  Inside a group the product sum, the
+ * activation code sum and the weight code sum are integers: exact in int32, and exact as fp32 while group_size*KH*KW <= 1024,
+ * which always holds on the fast path.  fp32 rounds only where a group is folded into the total with sw[o,g] and in the zero,
+ * sx and bias terms.
+ * Refused before any device work, in this order: a NULL shape; a non-positive N, IC, H, W, OC, KH, KW or stride, a negative
+ * padding, an OH or OW below 1 (all QE_ERR_ARG); then as qe_quantlinear_grouped: a NULL x, x->data, x->scale or x->zero
+ * (QE_ERR_ARG); x->n_bits outside 1..8 (QE_ERR_NBITS); the same two for w; group_size <= 0, IC % group_size != 0,
+ * x->n_param != 1, w->n_param != OC*(IC/group_size); a NULL out (all QE_ERR_ARG).
+ * _path (host-only, from the one plan the launch reads; 0 for a request the call would refuse):
+ *   1 = the fast kernel: KH = KW = 1, stride 1, padding 0, 8-bit activation codes, 4- or 8-bit weight codes, group_size in
+ *       {32, 64, 128}, w->data 16-byte aligned; any N, OC and plane H*W, any alignment of x->data and out:
+ *       v_mfma_i32_32x32x32_i8 into an int32 group accumulator, folded into the fp32 total at every group boundary;
+ *   0 = the plain kernel: one thread per output, the same integer sums group by group (any kernel size, stride, padding,
+ *       n_bits of either operand, group_size and alignment). */
+int qe_quantconv2d_awq(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric, int32_t w_symmetric,
+                       const float *bias, const qe_conv_shape *shape, int32_t relu, float *out, qe_stream_t stream);
+int qe_quantconv2d_awq_path(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric,
+                            int32_t w_symmetric, const qe_conv_shape *shape);
+
 /* qe_quantlinear_bf16 -- qe_quantlinear with a bf16 result, for a consumer that would round it anyway (the q / k / v
  * projections in front of qe_attention_bf16_stored):
  *   out[b, o] = bf16( y[b, o] * post_scale ),   y = qe_quantlinear(x, w, bias, B, K, O)      (B x O row-major bf16 bit patterns)

@@ -146,6 +146,9 @@ PROTOTYPES = {
     "qe_quantlinear_grouped_residual_path": (_i32, [_pq, _pq, _i32, _i32, _i32, _i64, _i32, _i32]),
     "qe_quantlinear_grouped_residual_workspace_size": (_sz, [_pq, _pq, _i32, _i32, _i32, _i64, _i32, _i32]),
     "qe_quantlinear_grouped_residual": (_i32, [_pq, _pq, _i32, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    # group-quantised (AWQ) packed convolutions
+    "qe_quantconv2d_awq": (_i32, [_pq, _pq, _i32, _i32, _i32, _vp, _ps, _i32, _vp, _vp]),
+    "qe_quantconv2d_awq_path": (_i32, [_pq, _pq, _i32, _i32, _i32, _ps]),
     "qe_quantlinear_requant_path": (_i32, [_pq, _pq, _i64, _i32, _i32, _pr, _vp]),
     "qe_quantlinear_requant_workspace_bytes": (_sz, [_pq, _pq, _i64, _i32, _i32, _pr, _vp]),
     "qe_quantlinear_requant": (_i32, [_pq, _pq, _vp, _i64, _i32, _i32, _i32, _pr, _vp, _vp, _vp, _sz, _vp]),
@@ -849,6 +852,22 @@ def quantlinear_grouped_residual(xq, wq, group_size, bias, B, K, O, residual, ou
     ws = _given_ws(workspace, need, dev)
     check(lib().qe_quantlinear_grouped_residual(*g, _ptr(bias), int(B), int(K), int(O), residual.data_ptr(), out.data_ptr(),
                                                 *_prep(ws), _stream(stream)))
+    return out
+
+
+def conv_awq_path(xq, wq, group_size, sh, x_symmetric=False, w_symmetric=False):
+    """qe_quantconv2d_awq_path (host-only): 1 = the int8 matrix-core kernel (1x1 / stride 1 / padding 0), 0 = the plain kernel."""
+    return int(lib().qe_quantconv2d_awq_path(*_grouped_args(xq, wq, group_size, x_symmetric, w_symmetric), ctypes.byref(sh)))
+
+
+def quantconv2d_awq(xq, wq, group_size, bias, sh, relu=False, out=None, stream=None, x_symmetric=False, w_symmetric=False):
+    """qe_quantconv2d_awq: packed NCHW activation codes (per-tensor xq) x group-quantised packed OIHW weights (wq: scale / zero of
+    OC * IC / group_size elements in (o, g) order), both in the kernel convention (q - zero).  Returns the fp32 NCHW output."""
+    import torch
+    if out is None:
+        out = torch.empty((sh.N, sh.OC) + out_hw(sh), dtype=torch.float32, device=wq._keep[0].device)
+    check(lib().qe_quantconv2d_awq(*_grouped_args(xq, wq, group_size, x_symmetric, w_symmetric), _ptr(bias), ctypes.byref(sh),
+                                   1 if relu else 0, out.data_ptr(), _stream(stream)))
     return out
 
 

@@ -544,6 +544,86 @@ class PackedGroupedLinear:
         return y.reshape(*x.shape[:-1], self.O)
 
 
+class PackedAwqConv2d(PackedGroupedLinear):
+    """A convolution whose weights are group-quantised as the reference's AWQ estimator lays out a 4-D weight (range/awq.py):
+    one scale and zero per (output channel, group of `group_size` consecutive input channels, all taps) and a per-input-channel
+    awq_scale the weights were multiplied by before rounding.  The reference can only simulate such a layer; here it runs
+    packed on qe_quantconv2d_awq: activation codes in, fp32 NCHW out.  State: PackedGroupedLinear's keys with w_des [n_bits,
+    sign, OC, IC, KH, KW], w_scale / w_zero of OC * IC / group_size elements in (o, g) order, plus the geometry (stride,
+    padding).  The activation quantiser (set_quantizer) is the per-tensor one of x / awq_scale[c]."""
+
+    def __init__(self, weight, w_des, w_scale, w_zero, w_group_size, awq_scale=None, bias=None, name=None, stride=1, padding=0, **a):
+        if w_des.numel() != 6:
+            raise ValueError("w_des of a convolution holds 6 fields: n_bits, sign, OC, IC, KH, KW")
+        super().__init__(weight, w_des, w_scale, w_zero, w_group_size, awq_scale, bias, name, **a)     # O = OC, K = IC
+        self.KH, self.KW = (int(v) for v in w_des.tolist()[4:])
+        self.stride, self.padding = int(stride), int(padding)
+
+    @classmethod
+    def from_awq(cls, weight, cfgs, n_bits, signed, group_size, bias=None, stride=1, padding=0):
+        """From a float weight (OC, IC, KH, KW) and the tuple the reference's AWQ estimator returns, (scale, zero, qmin, qmax,
+        awq_scale): the codes are the reference's (w * awq_scale / scale - zero).round().clamp(qmin, qmax) per group of
+        group_size channels x all taps, in fp32, stored signed only where the code range is."""
+        from .synthetic import pack_codes
+        scale, zero, qmin, qmax, awq_scale = cfgs
+        w = weight.detach().float().cpu()
+        OC, IC, KH, KW = w.shape
+        scale, zero = scale.detach().float().cpu().reshape(-1, 1), zero.detach().float().cpu().reshape(-1, 1)
+        awq_scale = awq_scale.detach().float().cpu().reshape(1, IC, 1, 1)
+        q = ((w * awq_scale).reshape(-1, int(group_size) * KH * KW) / scale - zero).round().clamp(float(qmin), float(qmax))
+        stored_signed = bool(signed) and float(qmin) < 0
+        packed = torch.from_numpy(pack_codes(q.numpy().astype("int64"), int(n_bits), stored_signed))
+        des = torch.tensor([int(n_bits), int(stored_signed), OC, IC, KH, KW], dtype=torch.int32)
+        return cls(packed, des, scale, zero, group_size, awq_scale, None if bias is None else bias.detach().float().cpu(),
+                   stride=stride, padding=padding)
+
+    @classmethod
+    def from_state_dict(cls, state_dict, prefix="", stride=None, padding=None):
+        """stride / padding: the state_dict's own entries unless given."""
+        g = lambda k, given: int(state_dict[prefix + k]) if given is None else given
+        a = {"a_" + k: state_dict[prefix + "a_quantizer." + k] for k in ("scale", "zero", "qmin", "qmax")
+             if prefix + "a_quantizer.scale" in state_dict}
+        return cls(*(state_dict[prefix + k] for k in ("weight", "w_des", "w_scale", "w_zero")), int(state_dict[prefix + "w_group_size"]),
+                   state_dict.get(prefix + "awq_scale"), state_dict.get(prefix + "bias"), name=prefix.rstrip("."),
+                   stride=g("stride", stride), padding=g("padding", padding), **a)
+
+    def state_dict(self):
+        return dict(super().state_dict(), stride=torch.tensor(self.stride, dtype=torch.int32),
+                    padding=torch.tensor(self.padding, dtype=torch.int32))
+
+    def dequantised_weight(self, codes):
+        """(codes + zero) * scale / awq_scale of integer codes (OC, IC, KH, KW): the reference's simulated weight."""
+        q = codes.float().reshape(-1, self.group_size * self.KH * self.KW)
+        w = ((q + self.w_zero.reshape(-1, 1)) * self.w_scale.reshape(-1, 1)).reshape(self.O, self.K, self.KH, self.KW)
+        return w if self.awq_scale is None else w / self.awq_scale.reshape(1, -1, 1, 1)
+
+    def quantize(self, x):
+        """fp32 NCHW -> (packed, des): the activation quantiser's codes of x / awq_scale[c], by qe_quantize_pack with the
+        per-input-channel scale s_c = float(double(a_scale) * double(awq_scale[c])), n_param = C, inner = H * W."""
+        if self.a_scale is None:
+            raise ValueError("PackedAwqConv2d.quantize: the layer has no activation quantiser (set_quantizer)")
+        x = x.contiguous().float()
+        codes, flag = capi.quantize_pack(x, self._a_scale_k, self._a_zero_k, self.a_qmin, self.a_qmax, self.a_bits, self.a_signed,
+                                         inner=x.shape[2] * x.shape[3])
+        if int(flag.item()) != 0:
+            raise RuntimeError(OUT_OF_RANGE)
+        return codes, (self.a_bits, int(self.a_signed), *x.shape)
+
+    def call_packed(self, xq, x_des, relu=False):
+        """Activation codes as quantize() returns them -> the fp32 (N, OC, OH, OW) output on qe_quantconv2d_awq."""
+        n_bits, sign, N, C, H, W = _host_des(x_des)
+        if C != self.K:
+            raise ValueError("codes of %d input channels for a convolution of %d" % (C, self.K))
+        sh = capi.conv_shape(N, C, H, W, self.O, self.KH, self.KW, self.stride, self.padding)
+        return capi.quantconv2d_awq(self.xq(xq, n_bits, sign), self.wq(), self.group_size, self.bias, sh, relu=relu,
+                                    x_symmetric=self.a_centred, w_symmetric=self.w_centred)
+
+    def __call__(self, x, relu=False):
+        return self.call_packed(*self.quantize(x), relu=relu)
+
+    call_packed_residual = call_packed_requant = None         # the linear's fused forms: a convolution has none yet
+
+
 class PackedMultiheadAttention:
     """A packed QuantMultiheadAttention's forward on the engine (modelzoo/modules/quantmultiheadattention.py:262-...).
     pack() leaves the q / k / v projection weights and out_proj.weight as packed streams with {q,k,v,out}_proj_{scale,
@@ -837,8 +917,8 @@ POOL_KINDS = {"relu": (PackedReLU, ("inplace",)), "maxpool": (PackedMaxPool2d, (
 
 
 def from_state_dict(state_dict, conv_geometry=None, num_heads=None, pool_geometry=None):
-    """Every packed layer of a model's state_dict -> {module prefix (no trailing dot): PackedConv2d | PackedLinear |
-    PackedMultiheadAttention}: what the packing loop of runner/ptq.py:106-114 / runner/qat.py:84-92 leaves behind, ready to
+    """Every packed layer of a model's state_dict -> {module prefix (no trailing dot): PackedConv2d | PackedAwqConv2d | PackedLinear |
+    PackedGroupedLinear | PackedMultiheadAttention}: what the packing loop of runner/ptq.py:106-114 / runner/qat.py:84-92 leaves behind, ready to
     run on the engine with no reference Python in the process.  A packed conv / linear is recognised by its `w_des` entry
     (6 fields = conv: n_bits, sign, OC, IC, KH, KW; 4 = linear), an attention block by `q_proj_des`.
     conv_geometry: {prefix: (stride, padding)} -- geometry is not part of the state_dict; default stride 1, padding
@@ -860,7 +940,9 @@ def from_state_dict(state_dict, conv_geometry=None, num_heads=None, pool_geometr
             prefix = key[:-len("w_des")]
             name = prefix[:-1] if prefix.endswith(".") else prefix
             des = state_dict[key]
-            if des.numel() == 6:
+            if des.numel() == 6 and prefix + "w_group_size" in state_dict:
+                layers[name] = PackedAwqConv2d.from_state_dict(state_dict, prefix, *conv_geometry.get(name, (None, None)))
+            elif des.numel() == 6:
                 kh = int(des[4])
                 stride, padding = conv_geometry.get(name, (1, (kh - 1) // 2))
                 layers[name] = PackedConv2d.from_state_dict(state_dict, prefix, stride=stride, padding=padding)
