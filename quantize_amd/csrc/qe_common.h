@@ -62,5 +62,6 @@ __device__ __forceinline__ int unpack_elem(const uint8_t *__restrict__ p, int64_
 
 __host__ __device__ inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }      // (NULL reads as aligned)
 
 }  // namespace qe

@@ -4,7 +4,8 @@
 //                         (q_x[n,c,ih,iw] - zx) (q_w[o,c,kh,kw] - zw[o,g]) )
 //
 // Group g covers the input channels [g G, (g + 1) G) and all taps; sw / zw are fp32 arrays of OC (IC / G) elements in (o, g)
-// order; sx / zx are one element each.  Two kernels and one host plan in a unit of its own: no other code object moves.
+// order; sx / zx are one element each.  Two kernels and one host plan in a unit of its own: no other code object moves.  The
+// host layer of the family and the device leaves it has in common with qe_linear_grp_i8.hip are qe_grp_common.hpp's.
 //
 // Both kernels read every stored value u as the CENTRED integer u - 2^(bits-1) (qe_linear_grp_i8.hip): with the residual
 // zeros z' = zero - (signed ? 0 : 2^(bits-1)) and x_c, w_c the centred codes, over the n taps of a group inside the image
@@ -44,9 +45,22 @@
 //
 // Plain kernel (everything else: any kernel size, stride, padding, code width, group size, alignment): one thread per
 // output, group by group: the three integer sums over the taps inside the image, then the fold.
-#include "qe_conv_awq.hpp"
+#include "qe_grp_common.hpp"         // the host layer and the device leaves shared with qe_linear_grp_i8.hip
 
 namespace qe {
+
+// the kernel argument: both kernels read the same block
+struct ConvAwqArgs {
+    const uint8_t *x, *w;      // packed NCHW activation codes, packed OIHW weight codes
+    const float *x_scale, *x_zero, *w_scale, *w_zero, *bias;
+    float *out;                // [N][OC][OH][OW] fp32
+    int x_bits, x_sign, w_bits, w_sign;
+    int G, NG;                 // input channels per group, groups per output channel (IC / G)
+    int N, IC, H, W, OC, KH, KW, stride, padding, OH, OW;
+    int P;                     // fast kernel: the plane, H * W
+    int tiles;                 // fast kernel: pixel tiles per image
+    int relu;
+};
 
 namespace {
 
@@ -55,10 +69,6 @@ typedef int v4i_a __attribute__((ext_vector_type(4)));
 typedef int v16i_a __attribute__((ext_vector_type(16)));
 typedef float v16f_a __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ int centred_elem(const uint8_t *__restrict__ p, int64_t i, int n_bits)
-{
-    return unpack_elem(p, i, n_bits, 0) - (1 << (n_bits - 1));
-}
 __device__ __forceinline__ float awq_act(float v, int relu) { return (!relu || v > 0.0f || v != v) ? v : 0.0f; }   // NaN passes
 
 // ---------------------------------------------------------------------------------------------
@@ -106,24 +116,6 @@ __global__ __launch_bounds__(256) void conv_awq_plain_kernel(const ConvAwqArgs a
 // Fast kernel.  WB: bits of a stored weight code (4 | 8).  WZ: residual weight zeros (Sx and the zw' term).  XZ: residual
 // activation zeros (T and the zx' term).  T: pixels of a tile (64 | 128).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint4 xor80(uint4 v)
-{
-    return make_uint4(v.x ^ 0x80808080u, v.y ^ 0x80808080u, v.z ^ 0x80808080u, v.w ^ 0x80808080u);
-}
-__device__ __forceinline__ int dot_ones(uint4 v)          // the sum of 16 int8
-{
-    int s = __builtin_amdgcn_sdot4((int)v.x, 0x01010101, 0, false);
-    s = __builtin_amdgcn_sdot4((int)v.y, 0x01010101, s, false);
-    s = __builtin_amdgcn_sdot4((int)v.z, 0x01010101, s, false);
-    return __builtin_amdgcn_sdot4((int)v.w, 0x01010101, s, false);
-}
-// 8 nibbles (low first) of `w` -> 8 bytes of u - 8
-__device__ __forceinline__ void widen_nibbles(uint32_t w, uint32_t &lo, uint32_t &hi)
-{
-    const uint32_t e = w & 0x0f0f0f0fu, o = (w >> 4) & 0x0f0f0f0fu;          // codes 0 2 4 6, codes 1 3 5 7
-    lo = (__builtin_amdgcn_perm(o, e, 0x05010400u) + 0x78787878u) ^ 0x80808080u;   // u + 0x78 <= 0x87: no carry; ^ 0x80: u - 8
-    hi = (__builtin_amdgcn_perm(o, e, 0x07030602u) + 0x78787878u) ^ 0x80808080u;
-}
 // 16 bytes at src, any alignment; the bytes at and beyond x_hi (the tensor's end) are not read and come back 0
 __device__ __forceinline__ uint4 load16_any(const uint8_t *src, const uint8_t *x_hi)
 {
@@ -196,7 +188,7 @@ __global__ __launch_bounds__(256, 2) void conv_awq_mfma_kernel(const ConvAwqArgs
         plds[i] = c * PITCH + 16 * sg;
     }
     // weights, 8-bit: thread <-> (column r4 + 64 i, 16-byte piece p4 of the stage's 64 k); 4-bit: thread <-> (column wc,
-    // k-step whh): 16 bytes = 32 codes
+    // k-step whh): 16 bytes = 32 codes  (twin: linear_grp_i8_mfma_kernel's weight path, here and in fetch and stage)
     const int p4 = tid & 3, r4 = tid >> 2;
     const int wc = tid >> 1, whh = tid & 1;
     const uint8_t *wrow[2];
@@ -300,7 +292,7 @@ __global__ __launch_bounds__(256, 2) void conv_awq_mfma_kernel(const ConvAwqArgs
         for (int ks = 0; ks < 2; ++ks) {
             const int step = 2 * st + ks;
             fold[ks] = step < n_steps && (step & gmask) == gmask;
-            if (fold[ks]) {
+            if (fold[ks]) {                               // (twin: linear_grp_i8_mfma_kernel's group-boundary fetch)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     gsw[ks][j] = a.w_scale[og[j] + (step >> gsh)];
@@ -340,7 +332,7 @@ __global__ __launch_bounds__(256, 2) void conv_awq_mfma_kernel(const ConvAwqArgs
                     __builtin_amdgcn_wave_barrier();      // (a wave's own LDS operations complete in order)
                 }
 #pragma unroll
-                for (int i = 0; i < MI; ++i) {
+                for (int i = 0; i < MI; ++i) {            // (twin: qe_grp_common.hpp's grp_fold, which the two linear kernels share)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         float s = 0.0f;
@@ -359,7 +351,7 @@ __global__ __launch_bounds__(256, 2) void conv_awq_mfma_kernel(const ConvAwqArgs
         }
         if (more) stage(st + 1);
     }
-    if constexpr (XZ) {                                   // T: the threads of a column add their shares
+    if constexpr (XZ) {                                   // T: the threads of a column add their shares (twin: linear_grp_i8_mfma_kernel's)
         if constexpr (WB == 8) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
@@ -425,7 +417,8 @@ __global__ __launch_bounds__(256, 2) void conv_awq_mfma_kernel(const ConvAwqArgs
 // ---------------------------------------------------------------------------------------------
 struct ConvAwqPlan {
     int fast;               // 1: conv_awq_mfma_kernel, 0: conv_awq_plain_kernel
-    int w4, wz, xz, t64;    // the fast kernel's instance
+    GrpI8Instance inst;     // the fast kernel's instance ...
+    int t64;                // ... and its tile width
     int OH, OW, tiles;
     int64_t blocks;
 };
@@ -444,12 +437,9 @@ ConvAwqPlan plan_conv_awq(const qe_qparam *x, const qe_qparam *w, int G, int x_s
     ConvAwqPlan p = {};
     p.OH = (sh->H + 2 * sh->padding - sh->KH) / sh->stride + 1;
     p.OW = (sh->W + 2 * sh->padding - sh->KW) / sh->stride + 1;
-    p.fast = sh->KH == 1 && sh->KW == 1 && sh->stride == 1 && sh->padding == 0 && x->n_bits == 8 &&
-             (w->n_bits == 4 || w->n_bits == 8) && (G == 32 || G == 64 || G == 128) &&
-             (reinterpret_cast<uintptr_t>(w->data) & 15) == 0 && (int64_t)sh->H * sh->W <= (1 << 30);
-    p.w4 = w->n_bits == 4;
-    p.wz = w_symmetric == 0;
-    p.xz = x_symmetric == 0;
+    p.fast = grp_weights_fast(w, G) && sh->KH == 1 && sh->KW == 1 && sh->stride == 1 && sh->padding == 0 && x->n_bits == 8 &&
+             (int64_t)sh->H * sh->W <= (1 << 30);
+    p.inst = grp_i8_instance(w, x_symmetric, w_symmetric);
     const int64_t P = (int64_t)sh->H * sh->W;
     p.t64 = awq_tile64(P);
     p.tiles = (int)ceil_div64(P, p.t64 ? 64 : 128);
@@ -464,10 +454,8 @@ int check_conv_awq(const qe_qparam *x, const qe_qparam *w, int G, const qe_conv_
         sh->padding < 0 || sh->H + 2 * sh->padding < sh->KH || sh->W + 2 * sh->padding < sh->KW)
         return QE_ERR_ARG;
     if (int rc = check_operand(x)) return rc;
-    if (int rc = check_operand(w)) return rc;
-    if (G <= 0 || sh->IC % G != 0) return QE_ERR_ARG;
-    if (x->n_param != 1) return QE_ERR_ARG;
-    return (int64_t)w->n_param == (int64_t)sh->OC * (sh->IC / G) ? QE_OK : QE_ERR_ARG;
+    if (int rc = check_grp_weights(w, G, sh->IC, sh->OC)) return rc;
+    return x->n_param == 1 ? QE_OK : QE_ERR_ARG;
 }
 
 template <int WB, bool WZ, bool XZ>
@@ -476,13 +464,6 @@ void launch_conv_awq(const ConvAwqPlan &p, const ConvAwqArgs &a, hipStream_t s)
     const unsigned blocks = (unsigned)p.blocks;
     if (p.t64) launch_instance<&conv_awq_mfma_kernel<WB, WZ, XZ, 64>>(blocks, 256, CaGeom<64>::LDS, 0, s, a);
     else launch_instance<&conv_awq_mfma_kernel<WB, WZ, XZ, 128>>(blocks, 256, CaGeom<128>::LDS, 0, s, a);
-}
-
-template <int WB>
-void launch_conv_awq_bits(const ConvAwqPlan &p, const ConvAwqArgs &a, hipStream_t s)
-{
-    if (p.wz) { if (p.xz) launch_conv_awq<WB, true, true>(p, a, s); else launch_conv_awq<WB, true, false>(p, a, s); }
-    else { if (p.xz) launch_conv_awq<WB, false, true>(p, a, s); else launch_conv_awq<WB, false, false>(p, a, s); }
 }
 
 }  // namespace
@@ -505,19 +486,16 @@ extern "C" int qe_quantconv2d_awq(const qe_qparam *x, const qe_qparam *w, int32_
     if (int rc = check_conv_awq(x, w, group_size, shape)) return rc;
     if (out == nullptr) return QE_ERR_ARG;
     const ConvAwqPlan p = plan_conv_awq(x, w, group_size, x_symmetric, w_symmetric, shape);
-    if (p.blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
     ConvAwqArgs a = {};
-    a.x = x->data; a.w = w->data; a.x_scale = x->scale; a.x_zero = x->zero; a.w_scale = w->scale; a.w_zero = w->zero;
-    a.bias = bias; a.out = out;
-    a.x_bits = x->n_bits; a.x_sign = x->sign; a.w_bits = w->n_bits; a.w_sign = w->sign;
-    a.G = group_size; a.NG = shape->IC / group_size;
+    fill_grp_operands(a, x, w, bias, group_size, shape->IC);
+    a.out = out;
     a.N = shape->N; a.IC = shape->IC; a.H = shape->H; a.W = shape->W; a.OC = shape->OC; a.KH = shape->KH; a.KW = shape->KW;
     a.stride = shape->stride; a.padding = shape->padding; a.OH = p.OH; a.OW = p.OW;
     a.P = p.fast ? shape->H * shape->W : 0; a.tiles = p.tiles; a.relu = relu != 0;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!p.fast) hipLaunchKernelGGL(conv_awq_plain_kernel, dim3((unsigned)p.blocks), dim3(256), 0, s, a);
-    else if (p.w4) launch_conv_awq_bits<4>(p, a, s);
-    else launch_conv_awq_bits<8>(p, a, s);
-    QE_LAUNCH_CHECK();
-    return QE_OK;
+    return launch_grp<&conv_awq_plain_kernel>(p.fast, p.blocks, a, s, [&] {
+        dispatch_grp_i8(p.inst, [&](auto wb, auto wz, auto xz) {
+            launch_conv_awq<decltype(wb)::value, decltype(wz)::value, decltype(xz)::value>(p, a, s);
+        });
+    });
 }

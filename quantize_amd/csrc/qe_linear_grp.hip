@@ -3,7 +3,8 @@
 //   out[b,o] = bias[o] + sum_g sw[o,g] * sum_{k in group g} x'[b,k] (q_w[o,k] - zw[o,g]),   x'[b,k] = x[b,k] x_mul[k]
 //
 // Group g covers k in [g G, (g + 1) G); sw / zw are fp32 arrays of O (K / G) elements in (o, g) order.  Two kernels and one
-// host plan; nothing else of the library is touched (a unit of its own, so that no other code object moves).
+// host plan in a unit of its own, so that no other code object moves; the weight operand's check, its side of fast
+// eligibility and the launch tail are qe_grp_common.hpp's, shared with the two int8 units.
 //
 // Fast kernel (4- and 8-bit codes, G in {32, 64, 128}, K % 32 == 0, 16-byte aligned streams): linear_f32_mfma_kernel's
 // arithmetic per GROUP.  x' is split exactly into three bf16 parts, the codes are centred on c = linf_centre(zw[o,g]) per (row,
@@ -22,7 +23,7 @@
 // no load sits under a per-lane condition.
 //
 // Plain kernel (everything else): one thread per output, fp32, group by group in k order.
-#include "qe_common.h"
+#include "qe_grp_common.hpp"
 #include "qe_linear_bf16in.hpp"      // linf_centre
 
 namespace qe {
@@ -229,20 +230,7 @@ __global__ __launch_bounds__(256, 2) void linear_grp_mfma_kernel(const LinGrpArg
         }
         if (fold) {
             const float *sxr = sxg + ((st >> gsh) & 1) * LG_T + wm * 64 + 4 * h;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float s = 0.0f;
-                    if constexpr (SX) s = sxr[i * 32 + (r & 3) + 8 * (r >> 2)];
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        const float t = SX ? fmaf(-gdz[j], s, accg[i][j][r]) : accg[i][j][r];
-                        acco[i][j][r] = fmaf(gsw[j], t, acco[i][j][r]);
-                        accg[i][j][r] = 0.0f;
-                    }
-                }
-            }
+            grp_fold<SX>(accg, acco, gsw, gdz, [&](int i, int r) { return sxr[i * 32 + (r & 3) + 8 * (r >> 2)]; });
         }
         if (more) stage(st + 1);
     }
@@ -250,6 +238,7 @@ __global__ __launch_bounds__(256, 2) void linear_grp_mfma_kernel(const LinGrpArg
     // D has the batch row on the register and the feature on the lane.  Each wave turns its 32 x 32 tiles through a private
     // LDS patch (the stage buffers are free now) and writes 8 rows x 128 contiguous bytes per store instruction.  (A wave's
     // own LDS operations complete in order: its reads see its writes, a later tile's writes cannot overtake them.)
+    // (twin: linear_grp_i8_mfma_kernel's patch store)
     float *patch = reinterpret_cast<float *>(lsm) + wave * (32 * 36);
     const int rrow = lane >> 3, rq = lane & 7;
     const bool vec4 = (a.O & 3) == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0;
@@ -291,14 +280,11 @@ struct LinGrpPlan {
     int64_t blocks;
 };
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // a validated request (check_grp); a query leaves the pointers it does not know null, which reads as aligned
 LinGrpPlan plan_grp(const float *x, const float *x_mul, const qe_qparam *w, int G, int symmetric, int64_t B, int K, int O)
 {
     LinGrpPlan p = {};
-    p.fast = (w->n_bits == 4 || w->n_bits == 8) && (G == 32 || G == 64 || G == 128) && K > 0 && K % LG_K == 0 &&
-             aligned16(x) && aligned16(x_mul) && aligned16(w->data);
+    p.fast = grp_weights_fast(w, G) && K > 0 && K % LG_K == 0 && aligned16(x) && aligned16(x_mul);
     p.w4 = w->n_bits == 4;
     p.sx = symmetric == 0;
     p.blocks = p.fast ? ceil_div64(B, LG_T) * ceil_div64(O, LG_T) : ceil_div64(B * O, 256);
@@ -308,15 +294,7 @@ LinGrpPlan plan_grp(const float *x, const float *x_mul, const qe_qparam *w, int 
 int check_grp(const qe_qparam *w, int G, int64_t B, int K, int O)
 {
     if (B < 0 || K < 0 || O < 0) return QE_ERR_ARG;
-    if (int rc = check_operand(w)) return rc;
-    if (G <= 0 || K % G != 0) return QE_ERR_ARG;
-    return (int64_t)w->n_param == (int64_t)O * (K / G) ? QE_OK : QE_ERR_ARG;
-}
-
-template <int WB, bool SX>
-void launch_grp_mfma(const LinGrpPlan &p, const LinGrpArgs &a, hipStream_t s)
-{
-    launch_instance<&linear_grp_mfma_kernel<WB, SX>>((unsigned)p.blocks, 256, LG_LDS, LG_LDS, s, a);
+    return check_grp_weights(w, G, K, O);
 }
 
 }  // namespace
@@ -340,14 +318,13 @@ extern "C" int qe_quantlinear_grouped_float_input(const float *x, const float *x
     if ((x == nullptr && B * K > 0) || (out == nullptr && B * O > 0)) return QE_ERR_ARG;
     if (B == 0 || O == 0) return QE_OK;
     const LinGrpPlan p = plan_grp(x, x_mul, w, group_size, symmetric, B, K, O);
-    if (p.blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
     LinGrpArgs a = {};
     a.x = x; a.x_mul = x_mul; a.w = w->data; a.w_scale = w->scale; a.w_zero = w->zero; a.bias = bias; a.out = out;
     a.w_bits = w->n_bits; a.w_sign = w->sign; a.G = group_size; a.NG = K / group_size; a.B = B; a.K = K; a.O = O;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!p.fast) hipLaunchKernelGGL(linear_grp_plain_kernel, dim3((unsigned)p.blocks), dim3(256), 0, s, a);
-    else if (p.w4) { if (p.sx) launch_grp_mfma<4, true>(p, a, s); else launch_grp_mfma<4, false>(p, a, s); }
-    else { if (p.sx) launch_grp_mfma<8, true>(p, a, s); else launch_grp_mfma<8, false>(p, a, s); }
-    QE_LAUNCH_CHECK();
-    return QE_OK;
+    return launch_grp<&linear_grp_plain_kernel>(p.fast, p.blocks, a, s, [&] {
+        dispatch_flag(p.w4, [&](auto w4) { dispatch_flag(p.sx, [&](auto sx) {
+            launch_instance<&linear_grp_mfma_kernel<decltype(w4)::value ? 4 : 8, decltype(sx)::value>>((unsigned)p.blocks, 256, LG_LDS, LG_LDS, s, a);
+        }); });
+    });
 }

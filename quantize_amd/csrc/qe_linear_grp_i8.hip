@@ -3,7 +3,8 @@
 //   out[b,o] = bias[o] + sx[b] sum_g sw[o,g] sum_{k in group g} (q_x[b,k] - zx[b]) (q_w[o,k] - zw[o,g])
 //
 // Group g covers k in [g G, (g + 1) G); sw / zw are fp32 arrays of O (K / G) elements in (o, g) order; sx / zx are indexed by
-// the row (1 or B of them).  Two kernels and one host plan in a unit of its own: no other code object moves.
+// the row (1 or B of them).  Two kernels and one host plan in a unit of its own: no other code object moves.  The host
+// layer of the family and the device leaves it has in common with qe_conv_awq.hip are qe_grp_common.hpp's.
 //
 // Both kernels read every stored value u as the CENTRED integer u - 2^(bits-1).  A signed and an unsigned stream then differ
 // only in the residual zero z' = zero - (signed ? 0 : 2^(bits-1)), and with x_c, w_c the centred codes
@@ -42,7 +43,7 @@
 // per row.  GELU runs in a loop that is not unrolled (one erf body per 32 x 32 tile): the lane parks its 16 values of the
 // tile in a private LDS column behind the image and reads them back by loop index.  Where the fused instance is not
 // eligible the entry points run two passes: qe_quantlinear_grouped into the workspace, then qe_quantize_pack_act or the add.
-#include "qe_common.h"
+#include "qe_grp_common.hpp"         // the host layer and the device leaves shared with qe_conv_awq.hip and qe_linear_grp.hip
 #include "qe_elementwise.hpp"
 #include "qe_linear_bf16in.hpp"     // launch_add_residual: the elementwise add of qe_quantlinear_residual's path 0
 
@@ -76,12 +77,6 @@ struct LinGrpI8Args {
     QeRq rq;
 };
 
-// stored u of an n_bits stream -> the centred integer u - 2^(bits-1)
-__device__ __forceinline__ int centred_elem(const uint8_t *__restrict__ p, int64_t i, int n_bits)
-{
-    return unpack_elem(p, i, n_bits, 0) - (1 << (n_bits - 1));
-}
-
 // ---------------------------------------------------------------------------------------------
 // Plain kernel: thread <-> output (b, o), o fastest.
 // ---------------------------------------------------------------------------------------------
@@ -114,25 +109,6 @@ __global__ __launch_bounds__(256) void linear_grp_i8_plain_kernel(const LinGrpI8
 // Fast kernel.  WB: bits of a stored weight code (4 | 8).  WZ: residual weight zeros (Sx and the zw' term).  XZ: residual
 // activation zeros (T and the zx' term).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint4 xor80(uint4 v)
-{
-    return make_uint4(v.x ^ 0x80808080u, v.y ^ 0x80808080u, v.z ^ 0x80808080u, v.w ^ 0x80808080u);
-}
-__device__ __forceinline__ int dot_ones(uint4 v)          // the sum of 16 int8
-{
-    int s = __builtin_amdgcn_sdot4((int)v.x, 0x01010101, 0, false);
-    s = __builtin_amdgcn_sdot4((int)v.y, 0x01010101, s, false);
-    s = __builtin_amdgcn_sdot4((int)v.z, 0x01010101, s, false);
-    return __builtin_amdgcn_sdot4((int)v.w, 0x01010101, s, false);
-}
-// 8 nibbles (low first) of `w` -> 8 bytes of u - 8
-__device__ __forceinline__ void widen_nibbles(uint32_t w, uint32_t &lo, uint32_t &hi)
-{
-    const uint32_t e = w & 0x0f0f0f0fu, o = (w >> 4) & 0x0f0f0f0fu;          // codes 0 2 4 6, codes 1 3 5 7
-    lo = (__builtin_amdgcn_perm(o, e, 0x05010400u) + 0x78787878u) ^ 0x80808080u;   // u + 0x78 <= 0x87: no carry; ^ 0x80: u - 8
-    hi = (__builtin_amdgcn_perm(o, e, 0x07030602u) + 0x78787878u) ^ 0x80808080u;
-}
-
 // Epilogue of the fast kernel, a template parameter and never a runtime branch: y (GQ_F32), y + res (GQ_RES), the consumer's
 // 8-bit codes of y / gelu(y) (GQ_CODES, GQ_CODES_GELU).
 enum { GQ_F32 = 0, GQ_RES = 1, GQ_CODES = 2, GQ_CODES_GELU = 3 };
@@ -181,6 +157,7 @@ __global__ __launch_bounds__(256, 2) void linear_grp_i8_mfma_kernel(const LinGrp
         xrow[i] = a.x + ((m0 + r < a.B) ? m0 + r : a.B - 1) * a.K;
     }
     // weights, 8-bit: the same map on columns; 4-bit: thread <-> (column wc, k-step whh): 16 bytes = 32 codes
+    // (twin: conv_awq_mfma_kernel's weight path, here and in fetch and stage)
     const int wc = tid >> 1, whh = tid & 1;
     const uint8_t *wrow[2];
     int64_t tog[2];                                       // the staged columns in the (o, g) arrays (T)
@@ -297,7 +274,7 @@ __global__ __launch_bounds__(256, 2) void linear_grp_i8_mfma_kernel(const LinGrp
         for (int ks = 0; ks < 2; ++ks) {
             const int step = 2 * st + ks;
             fold[ks] = step < n_steps && (step & gmask) == gmask;
-            if (fold[ks]) {
+            if (fold[ks]) {                               // (twin: conv_awq_mfma_kernel's group-boundary fetch)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     gsw[ks][j] = a.w_scale[og[j] + (step >> gsh)];
@@ -322,26 +299,12 @@ __global__ __launch_bounds__(256, 2) void linear_grp_i8_mfma_kernel(const LinGrp
             }
             if (fold[ks]) {
                 const int *sxr = sxg + ((st & 1) * 2 + ks) * GQ_T + wm * 64 + 4 * h;
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        float s = 0.0f;
-                        if constexpr (WZ) s = (float)sxr[i * 32 + (r & 3) + 8 * (r >> 2)];
-#pragma unroll
-                        for (int j = 0; j < 2; ++j) {
-                            const float p = (float)accg[i][j][r];
-                            const float t = WZ ? fmaf(-gdz[ks][j], s, p) : p;
-                            acco[i][j][r] = fmaf(gsw[ks][j], t, acco[i][j][r]);
-                            accg[i][j][r] = 0;
-                        }
-                    }
-                }
+                grp_fold<WZ>(accg, acco, gsw[ks], gdz[ks], [&](int i, int r) { return (float)sxr[i * 32 + (r & 3) + 8 * (r >> 2)]; });
             }
         }
         if (more) stage(st + 1);
     }
-    if constexpr (XZ) {                                   // T: the threads of a column add their shares
+    if constexpr (XZ) {                                   // T: the threads of a column add their shares (twin: conv_awq_mfma_kernel's)
         if constexpr (WB == 8) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
@@ -413,6 +376,7 @@ __global__ __launch_bounds__(256, 2) void linear_grp_i8_mfma_kernel(const LinGrp
     // D has the batch row on the register and the feature on the lane.  Each wave turns its 32 x 32 tiles through a private
     // LDS patch (the stage buffers are free now) and writes 8 rows x 128 contiguous bytes per store instruction.  (A wave's
     // own LDS operations complete in order: its reads see its writes, a later tile's writes cannot overtake them.)
+    // (twin: linear_grp_mfma_kernel's patch store)
     float *patch = reinterpret_cast<float *>(lsm) + wave * (32 * 36);
     const int rrow = lane >> 3, rq = lane & 7;
     const bool vec4 = (a.O & 3) == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0 &&
@@ -469,14 +433,12 @@ __global__ __launch_bounds__(256, 2) void linear_grp_i8_mfma_kernel(const LinGrp
 // ---------------------------------------------------------------------------------------------
 struct LinGrpI8Plan {
     int fast;               // 1: linear_grp_i8_mfma_kernel, 0: linear_grp_i8_plain_kernel
-    int w4, wz, xz;         // the fast kernel's instance
+    GrpI8Instance inst;     // the fast kernel's instance
     int64_t blocks;
     int epi;                // the epilogue the kernel runs: the request's on a fused plan, GQ_F32 on a two-pass plan
     int two_pass;           // a fused form's request the kernel cannot finish: y into the workspace, then the elementwise pass
     size_t ws;              // workspace bytes (y of a two-pass plan)
 };
-
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // a validated request (check_grp_i8; check_grp_rq for the re-quantising form).  epi: the form asked for; rq and codes (its
 // address alone; NULL reads as aligned) belong to GQ_CODES*
@@ -484,11 +446,8 @@ LinGrpI8Plan plan_grp_i8(const qe_qparam *x, const qe_qparam *w, int G, int x_sy
                          int epi = GQ_F32, const qe_requant *rq = nullptr, const void *codes = nullptr)
 {
     LinGrpI8Plan p = {};
-    p.fast = x->n_bits == 8 && (w->n_bits == 4 || w->n_bits == 8) && (G == 32 || G == 64 || G == 128) && K > 0 &&
-             aligned16(x->data) && aligned16(w->data);
-    p.w4 = w->n_bits == 4;
-    p.wz = w_symmetric == 0;
-    p.xz = x_symmetric == 0;
+    p.fast = grp_weights_fast(w, G) && x->n_bits == 8 && K > 0 && aligned16(x->data);
+    p.inst = grp_i8_instance(w, x_symmetric, w_symmetric);
     p.blocks = p.fast ? ceil_div64(B, GQ_T) * ceil_div64(O, GQ_T) : ceil_div64(B * O, 256);
     const bool codes_form = epi == GQ_CODES || epi == GQ_CODES_GELU;
     const bool fused = p.fast && (!codes_form || (rq->n_bits == 8 && O % 16 == 0 && aligned16(codes)));
@@ -502,10 +461,8 @@ int check_grp_i8(const qe_qparam *x, const qe_qparam *w, int G, int64_t B, int K
 {
     if (B < 0 || K < 0 || O < 0) return QE_ERR_ARG;
     if (int rc = check_operand(x)) return rc;
-    if (int rc = check_operand(w)) return rc;
-    if (G <= 0 || K % G != 0) return QE_ERR_ARG;
-    if (!one_or_per_channel(x->n_param, B)) return QE_ERR_ARG;
-    return (int64_t)w->n_param == (int64_t)O * (K / G) ? QE_OK : QE_ERR_ARG;
+    if (int rc = check_grp_weights(w, G, K, O)) return rc;
+    return one_or_per_channel(x->n_param, B) ? QE_OK : QE_ERR_ARG;
 }
 
 // ... then the consumer's quantiser and the activation of the re-quantising form
@@ -528,27 +485,37 @@ void launch_grp_i8(const LinGrpI8Plan &p, const LinGrpI8Args &a, hipStream_t s)
     }
 }
 
-template <int WB>
-void launch_grp_i8_bits(const LinGrpI8Plan &p, const LinGrpI8Args &a, hipStream_t s)
+// One form's request, validated and planned in one place for its path query, its workspace query and its run.  epi: the form
+// (GQ_CODES stands for both code forms in a query); rq, act and codes belong to the code forms.  rc != QE_OK: no plan.
+struct LinGrpI8Request {
+    const qe_qparam *x, *w;
+    int G;
+    int64_t B;
+    int K, O;
+    int rc;
+    LinGrpI8Plan plan;
+};
+
+LinGrpI8Request request_grp_i8(const qe_qparam *x, const qe_qparam *w, int G, int x_symmetric, int w_symmetric, int64_t B, int K, int O,
+                               int epi = GQ_F32, const qe_requant *rq = nullptr, int act = QE_ACT_NONE, const void *codes = nullptr)
 {
-    if (p.wz) { if (p.xz) launch_grp_i8<WB, true, true>(p, a, s); else launch_grp_i8<WB, true, false>(p, a, s); }
-    else { if (p.xz) launch_grp_i8<WB, false, true>(p, a, s); else launch_grp_i8<WB, false, false>(p, a, s); }
+    LinGrpI8Request r = {x, w, G, B, K, O, check_grp_i8(x, w, G, B, K, O), {}};
+    if (r.rc == QE_OK && (epi == GQ_CODES || epi == GQ_CODES_GELU)) r.rc = check_grp_rq(rq, act, O);
+    if (r.rc == QE_OK) r.plan = plan_grp_i8(x, w, G, x_symmetric, w_symmetric, B, K, O, epi, rq, codes);
+    return r;
 }
 
-// The kernel of a plan on a validated, non-empty request.  `a` carries the destination of the plan's epilogue.
-int run_grp_i8(const LinGrpI8Plan &p, LinGrpI8Args a, const qe_qparam *x, const qe_qparam *w, int G, const float *bias, int64_t B,
-               int K, int O, hipStream_t s)
+// The kernel of a request's plan; the request is valid and not empty.  `a` carries the destination of the plan's epilogue.
+int run_grp_i8(const LinGrpI8Request &r, LinGrpI8Args a, const float *bias, hipStream_t s)
 {
-    if (p.blocks > 0x7fffffffLL) return QE_ERR_UNSUPPORTED;
-    a.x = x->data; a.w = w->data; a.x_scale = x->scale; a.x_zero = x->zero; a.w_scale = w->scale; a.w_zero = w->zero;
-    a.bias = bias;
-    a.x_bits = x->n_bits; a.x_sign = x->sign; a.x_per_row = x->n_param != 1; a.w_bits = w->n_bits; a.w_sign = w->sign;
-    a.G = G; a.NG = K / G; a.B = B; a.K = K; a.O = O;
-    if (!p.fast) hipLaunchKernelGGL(linear_grp_i8_plain_kernel, dim3((unsigned)p.blocks), dim3(256), 0, s, a);
-    else if (p.w4) launch_grp_i8_bits<4>(p, a, s);
-    else launch_grp_i8_bits<8>(p, a, s);
-    QE_LAUNCH_CHECK();
-    return QE_OK;
+    const LinGrpI8Plan &p = r.plan;
+    fill_grp_operands(a, r.x, r.w, bias, r.G, r.K);
+    a.x_per_row = r.x->n_param != 1; a.B = r.B; a.K = r.K; a.O = r.O;
+    return launch_grp<&linear_grp_i8_plain_kernel>(p.fast, p.blocks, a, s, [&] {
+        dispatch_grp_i8(p.inst, [&](auto wb, auto wz, auto xz) {
+            launch_grp_i8<decltype(wb)::value, decltype(wz)::value, decltype(xz)::value>(p, a, s);
+        });
+    });
 }
 
 bool workspace_ok(const LinGrpI8Plan &p, const void *workspace, size_t workspace_bytes)
@@ -563,9 +530,8 @@ bool workspace_ok(const LinGrpI8Plan &p, const void *workspace, size_t workspace
 extern "C" int qe_quantlinear_grouped_path(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric,
                                            int32_t w_symmetric, int64_t B, int32_t K, int32_t O)
 {
-    using namespace qe;
-    if (check_grp_i8(x, w, group_size, B, K, O) != QE_OK) return 0;
-    return plan_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O).fast;
+    const qe::LinGrpI8Request r = qe::request_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O);
+    return r.rc == QE_OK && r.plan.fast;
 }
 
 extern "C" int qe_quantlinear_grouped(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric,
@@ -573,13 +539,13 @@ extern "C" int qe_quantlinear_grouped(const qe_qparam *x, const qe_qparam *w, in
                                       qe_stream_t stream)
 {
     using namespace qe;
-    if (int rc = check_grp_i8(x, w, group_size, B, K, O)) return rc;
+    const LinGrpI8Request r = request_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O);
+    if (r.rc != QE_OK) return r.rc;
     if (out == nullptr && B * O > 0) return QE_ERR_ARG;
     if (B == 0 || O == 0) return QE_OK;
-    const LinGrpI8Plan p = plan_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O);
     LinGrpI8Args a = {};
     a.out = out;
-    return run_grp_i8(p, a, x, w, group_size, bias, B, K, O, static_cast<hipStream_t>(stream));
+    return run_grp_i8(r, a, bias, static_cast<hipStream_t>(stream));
 }
 
 // Fused forms (include/quant_engine.h): the consumer's codes of y / gelu(y), and y + residual.  Path 1 is the fast kernel with
@@ -589,18 +555,16 @@ extern "C" int qe_quantlinear_grouped_requant_path(const qe_qparam *x, const qe_
                                                    int32_t w_symmetric, int64_t B, int32_t K, int32_t O, const qe_requant *rq,
                                                    const uint8_t *codes)
 {
-    using namespace qe;
-    if (check_grp_i8(x, w, group_size, B, K, O) != QE_OK || check_grp_rq(rq, QE_ACT_NONE, O) != QE_OK) return 0;
-    return !plan_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O, GQ_CODES, rq, codes).two_pass;
+    const qe::LinGrpI8Request r = qe::request_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O, qe::GQ_CODES, rq, QE_ACT_NONE, codes);
+    return r.rc == QE_OK && !r.plan.two_pass;
 }
 
 extern "C" size_t qe_quantlinear_grouped_requant_workspace_size(const qe_qparam *x, const qe_qparam *w, int32_t group_size,
                                                                  int32_t x_symmetric, int32_t w_symmetric, int64_t B, int32_t K,
                                                                  int32_t O, const qe_requant *rq, const uint8_t *codes)
 {
-    using namespace qe;
-    if (check_grp_i8(x, w, group_size, B, K, O) != QE_OK || check_grp_rq(rq, QE_ACT_NONE, O) != QE_OK) return 0;
-    return plan_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O, GQ_CODES, rq, codes).ws;
+    const qe::LinGrpI8Request r = qe::request_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O, qe::GQ_CODES, rq, QE_ACT_NONE, codes);
+    return r.rc == QE_OK ? r.plan.ws : 0;
 }
 
 extern "C" int qe_quantlinear_grouped_requant(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric,
@@ -609,18 +573,17 @@ extern "C" int qe_quantlinear_grouped_requant(const qe_qparam *x, const qe_qpara
                                               size_t workspace_bytes, qe_stream_t stream)
 {
     using namespace qe;
-    if (int rc = check_grp_i8(x, w, group_size, B, K, O)) return rc;
-    if (int rc = check_grp_rq(rq, act, O)) return rc;
+    const LinGrpI8Request r = request_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O,
+                                             act == QE_ACT_GELU ? GQ_CODES_GELU : GQ_CODES, rq, act, codes);
+    if (r.rc != QE_OK) return r.rc;
     if (codes == nullptr && B * O > 0) return QE_ERR_ARG;
     if (B == 0 || O == 0) return QE_OK;
-    const int epi = act == QE_ACT_GELU ? GQ_CODES_GELU : GQ_CODES;
-    const LinGrpI8Plan p = plan_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O, epi, rq, codes);
-    if (!workspace_ok(p, workspace, workspace_bytes)) return QE_ERR_WORKSPACE;
+    if (!workspace_ok(r.plan, workspace, workspace_bytes)) return QE_ERR_WORKSPACE;
     LinGrpI8Args a = {};
     a.out = static_cast<float *>(workspace);
     a.codes = codes; a.status = status; a.rq_per_col = rq->n_param != 1; a.rq = make_qe_rq(*rq);
-    if (int rc = run_grp_i8(p, a, x, w, group_size, bias, B, K, O, static_cast<hipStream_t>(stream))) return rc;
-    if (!p.two_pass) return QE_OK;
+    if (int rc = run_grp_i8(r, a, bias, static_cast<hipStream_t>(stream))) return rc;
+    if (!r.plan.two_pass) return QE_OK;
     // per-feature rq: channel = output feature o, element (b, o) -> (i / 1) % O
     return qe_quantize_pack_act(a.out, B * (int64_t)O, act, rq->scale, rq->zero, rq->n_param, 1, rq->qmin, rq->qmax, rq->n_bits,
                                 rq->sign, codes, nullptr, status, stream);
@@ -629,18 +592,16 @@ extern "C" int qe_quantlinear_grouped_requant(const qe_qparam *x, const qe_qpara
 extern "C" int qe_quantlinear_grouped_residual_path(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric,
                                                     int32_t w_symmetric, int64_t B, int32_t K, int32_t O)
 {
-    using namespace qe;
-    if (check_grp_i8(x, w, group_size, B, K, O) != QE_OK) return 0;
-    return !plan_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O, GQ_RES).two_pass;
+    const qe::LinGrpI8Request r = qe::request_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O, qe::GQ_RES);
+    return r.rc == QE_OK && !r.plan.two_pass;
 }
 
 extern "C" size_t qe_quantlinear_grouped_residual_workspace_size(const qe_qparam *x, const qe_qparam *w, int32_t group_size,
                                                                   int32_t x_symmetric, int32_t w_symmetric, int64_t B, int32_t K,
                                                                   int32_t O)
 {
-    using namespace qe;
-    if (check_grp_i8(x, w, group_size, B, K, O) != QE_OK) return 0;
-    return plan_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O, GQ_RES).ws;
+    const qe::LinGrpI8Request r = qe::request_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O, qe::GQ_RES);
+    return r.rc == QE_OK ? r.plan.ws : 0;
 }
 
 extern "C" int qe_quantlinear_grouped_residual(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric,
@@ -649,7 +610,8 @@ extern "C" int qe_quantlinear_grouped_residual(const qe_qparam *x, const qe_qpar
                                                qe_stream_t stream)
 {
     using namespace qe;
-    if (int rc = check_grp_i8(x, w, group_size, B, K, O)) return rc;
+    const LinGrpI8Request r = request_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O, GQ_RES);
+    if (r.rc != QE_OK) return r.rc;
     if ((residual == nullptr || out == nullptr) && B * O > 0) return QE_ERR_ARG;
     if (B == 0 || O == 0) return QE_OK;
     const int64_t n = B * (int64_t)O;
@@ -657,13 +619,13 @@ extern "C" int qe_quantlinear_grouped_residual(const qe_qparam *x, const qe_qpar
     if (!same_or_disjoint(residual, out, n * 4) || overlaps(so, span_of(x->data, qe_packed_nbytes(B * (int64_t)K, x->n_bits))) ||
         overlaps(so, span_of(w->data, qe_packed_nbytes((int64_t)O * K, w->n_bits))))
         return QE_ERR_ARG;
-    const LinGrpI8Plan p = plan_grp_i8(x, w, group_size, x_symmetric, w_symmetric, B, K, O, GQ_RES);
+    const LinGrpI8Plan &p = r.plan;
     if (!workspace_ok(p, workspace, workspace_bytes)) return QE_ERR_WORKSPACE;
     LinGrpI8Args a = {};
     a.out = p.two_pass ? static_cast<float *>(workspace) : out;
     a.res = residual;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (int rc = run_grp_i8(p, a, x, w, group_size, bias, B, K, O, s)) return rc;
+    if (int rc = run_grp_i8(r, a, bias, s)) return rc;
     return p.two_pass ? launch_add_residual(a.out, residual, out, n, s) : QE_OK;
 }
 

@@ -3,7 +3,7 @@ streams, then tap by tap and group by group.  Both operands in the kernel conven
 contributes nothing.  A plain helper module."""
 import numpy as np
 
-from linear_grouped_ref import decode
+from awq_cases import decoded
 
 
 def out_hw(c):
@@ -12,10 +12,7 @@ def out_hw(c):
 
 def _operands(c):
     """Decoded codes and parameters of a case dict, float64: qx (N, IC, H, W), qw (OC, IC, KH, KW), sx, zx scalars, sw / zw (OC, NG)."""
-    xs, ws = (c["N"], c["IC"], c["H"], c["W"]), (c["OC"], c["IC"], c["KH"], c["KW"])
-    qx = decode(c["x_stream"], int(np.prod(xs)), c["x_bits"], c["x_signed"]).reshape(xs).astype(np.float64)
-    qw = decode(c["w_stream"], int(np.prod(ws)), c["w_bits"], c["w_signed"]).reshape(ws).astype(np.float64)
-    sw, zw = (np.asarray(c[k], np.float64).reshape(c["OC"], c["IC"] // c["G"]) for k in ("sw", "zw"))
+    qx, qw, sw, zw = decoded(c, (c["N"], c["IC"], c["H"], c["W"]), (c["OC"], c["IC"], c["KH"], c["KW"]), c["IC"] // c["G"])
     return qx, qw, float(np.asarray(c["sx"]).reshape(-1)[0]), float(np.asarray(c["zx"]).reshape(-1)[0]), sw, zw
 
 

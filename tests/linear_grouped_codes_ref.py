@@ -2,16 +2,14 @@
 streams, then a plain double loop over groups.  Both operands in the kernel convention (q - zero).  A plain helper module."""
 import numpy as np
 
-from linear_grouped_ref import decode
+from awq_cases import decoded
 
 
 def _operands(c):
     """The decoded codes and the parameters of a case dict, in float64: qx (B, K), qw (O, K), sx / zx (B, 1), sw / zw (O, NG)."""
-    B, K, O, NG = c["B"], c["K"], c["O"], c["K"] // c["G"]
-    qx = decode(c["x_stream"], B * K, c["x_bits"], c["x_signed"]).reshape(B, K).astype(np.float64)
-    qw = decode(c["w_stream"], O * K, c["w_bits"], c["w_signed"]).reshape(O, K).astype(np.float64)
+    B, K, O = c["B"], c["K"], c["O"]
+    qx, qw, sw, zw = decoded(c, (B, K), (O, K), K // c["G"])
     sx, zx = (np.broadcast_to(np.asarray(c[k], np.float64).reshape(-1, 1), (B, 1)) for k in ("sx", "zx"))
-    sw, zw = (np.asarray(c[k], np.float64).reshape(O, NG) for k in ("sw", "zw"))
     return qx, qw, sx, zx, sw, zw
 
 

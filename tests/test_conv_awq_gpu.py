@@ -13,20 +13,13 @@ from quantize_amd import capi
 from quantize_amd.synthetic import pack_codes
 
 import awq_conv_ref as ref
+from awq_cases import codes as _codes
 from arena import FILLS, Arena, same_bytes
 from conftest import conv_tolerance
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g16_awq_conv.npz")
 PLANES = ((1, 1), (7, 7), (10, 13), (14, 14))          # P = 1, 49, 130, 196
-
-
-def _codes(rng, shape, bits, sym, mean):
-    """(stream, signed, centre): a symmetric operand has signed codes (centre 0), an asymmetric one unsigned codes (centre
-    2^(bits-1)); `mean` shifts the centred codes (a non-zero mean: the cancellation regime of the zero-point terms)."""
-    half = 1 << (bits - 1)
-    q = np.clip(np.rint(rng.randn(*shape) * half / 3 + mean), -half, half - 1).astype(np.int64) + (0 if sym else half)
-    return pack_codes(q, bits, sym), sym, 0 if sym else half
 
 
 def _case(seed, w_bits, G, IC, N, OC, hw, wsym, xsym, relu=False, x_bits=8, k=1, stride=1, padding=0):

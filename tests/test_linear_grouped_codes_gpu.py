@@ -14,35 +14,13 @@ from quantize_amd import capi
 from quantize_amd.synthetic import pack_codes
 
 import linear_grouped_codes_ref as ref
+from awq_cases import linear_case as _case
 from linear_grouped_ref import g15_layer
 from arena import FILLS, Arena, same_bytes
 from conftest import conv_tolerance
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g15_awq_linear.npz")
-
-
-def _codes(rng, shape, bits, sym, mean):
-    """(stream, signed, centre): a symmetric operand has signed codes (centre 0), an asymmetric one unsigned codes (centre
-    2^(bits-1)); `mean` shifts the centred codes (a non-zero mean: the cancellation regime of the zero-point terms)."""
-    half = 1 << (bits - 1)
-    q = np.clip(np.rint(rng.randn(*shape) * half / 3 + mean), -half, half - 1).astype(np.int64) + (0 if sym else half)
-    return pack_codes(q, bits, sym), sym, 0 if sym else half
-
-
-def _case(seed, w_bits, G, K, B, O, wsym, xsym, per_row, x_bits=8):
-    """Random operands.  Symmetric: zeros at the stream's centre; asymmetric: the centre plus a fraction in (-0.5, 0.5)."""
-    rng = np.random.RandomState(seed)
-    NG, n_x = K // G, B if per_row else 1
-    c = dict(w_bits=w_bits, x_bits=x_bits, G=G, K=K, B=B, O=O, wsym=wsym, xsym=xsym)
-    c["x_stream"], c["x_signed"], cx = _codes(rng, (B, K), x_bits, xsym, (1 << x_bits) / 8)
-    c["w_stream"], c["w_signed"], cw = _codes(rng, (O, K), w_bits, wsym, 0)
-    c["sx"] = (rng.uniform(0.5, 1.5, size=n_x) * 2.0 ** (5 - x_bits)).astype(np.float32)
-    c["zx"] = (cx + (0 if xsym else 1) * rng.uniform(-0.5, 0.5, size=n_x)).astype(np.float32)
-    c["sw"] = (rng.uniform(0.5, 1.5, size=O * NG) * 2.0 ** (4 - w_bits) / np.sqrt(K)).astype(np.float32)
-    c["zw"] = (cw + (0 if wsym else 1) * rng.uniform(-0.5, 0.5, size=O * NG)).astype(np.float32)
-    c["bias"] = rng.randn(O).astype(np.float32)
-    return c
 
 
 def _run(c, out_off=0, x_off=0, place=None):

@@ -12,7 +12,7 @@ from quantize_amd import capi, packed_vit, synthetic
 import linear_grouped_codes_ref as ref
 from arena import FILLS, Arena, same_bytes
 from conftest import conv_tolerance
-from test_linear_grouped_codes_gpu import _case          # the operand generator of the plain entry point's tests
+from awq_cases import linear_case as _case               # the operand generator of the plain entry point's tests
 
 pytestmark = pytest.mark.gpu
 QMIN, QMAX = -16.0, 255.0          # unsigned stored codes with a clamp below their range: a clamped negative code trips the flag
