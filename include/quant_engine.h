@@ -633,6 +633,44 @@ int qe_quantconv2d_awq(const qe_qparam *x, const qe_qparam *w, int32_t group_siz
 int qe_quantconv2d_awq_path(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric,
                             int32_t w_symmetric, const qe_conv_shape *shape);
 
+/* qe_quantconv2d_awq_fused -- qe_quantconv2d_awq with a layer's end fused into it: the residual add, the ReLU and the
+ * consumer's activation quantiser, fp32 and / or codes out.
+ *   y     = qe_quantconv2d_awq(x, w, ..., bias, shape, relu = 0)                        (bit for bit)
+ *   v     = y + identity                      one fp32 add, when identity != NULL (fp32, shaped like the output)
+ *   out   = relu ? max(v, 0) with NaN passing : v         (fp32 NCHW; may be NULL with rq: codes only)
+ *   codes = qe_quantize_pack(out, rq->scale, rq->zero, rq->n_param, OH*OW, ...)            (bit for bit; with rq)
+ * out is bit-identical to torch.relu(qe_quantconv2d_awq(...) + identity) and to its variants without the add or the ReLU.
+ * x, w, group_size, x_symmetric, w_symmetric, bias, shape exactly as for qe_quantconv2d_awq.
+ * rq       the consumer's quantiser in the MODULE's convention (qe_quantconv2d_requant_prepared); n_param 1 or OC.  A
+ *          per-channel rq is what an AWQ consumer has: its awq_scale folded into a per-input-channel scale.
+ * status   may be NULL; as qe_quantconv2d_requant_prepared: the flag is a function of the N*OC*OH*OW values alone -- a NaN
+ *          always raises it, a clamp raises it only where the bound lies outside the code range, lanes that compute on tile
+ *          padding never do.
+ * out == identity (in place) is allowed.  out, identity and codes may have any alignment their element type allows.
+ * Sub-8-bit rq codes: two planes can share a byte of the stream, so the kernels do not pack them: with out != NULL the call
+ *          runs the kernel into out and then qe_quantize_pack on it; with out == NULL it returns QE_ERR_UNSUPPORTED.
+ * No workspace and no prepared tables.  Asynchronous on stream; no host synchronisation, allocation or free.
+ * Refused before any device work, in this order: everything qe_quantconv2d_awq refuses, in its order, up to and including
+ * w->n_param; out and codes both NULL, codes without rq or rq without codes, a NULL rq->scale or rq->zero (QE_ERR_ARG);
+ * rq->n_bits outside 1..8 (QE_ERR_NBITS); rq->n_param not 1 or OC (QE_ERR_ARG); an output (out, codes, status) overlapping
+ * an operand (x, w, their scales and zeros, bias, rq's arrays, identity) or another output, other than out == identity
+ * (QE_ERR_ARG); then sub-8-bit codes without out (QE_ERR_UNSUPPORTED).
+ * _path (host-only, from the one plan the launch reads; the operands of the call without bias and stream):
+ *   1 = the fast kernel of qe_quantconv2d_awq (qe_quantconv2d_awq_path == 1) finishes the work in its epilogue; rq NULL or
+ *       8-bit.  16-byte, dword or byte code stores and 16-byte or element identity loads are chosen inside the kernel;
+ *   0 = the plain kernel (one thread per output does the add, the ReLU, the stores and the flag): every geometry
+ *       qe_quantconv2d_awq serves on its path 0; and every sub-8-bit rq with out, on whichever kernel the geometry names,
+ *       followed by qe_quantize_pack;
+ *  -1 = a request the call refuses.
+ *   The path depends neither on the alignment of out, identity or codes nor on the plane. */
+int qe_quantconv2d_awq_fused(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric,
+                             int32_t w_symmetric, const float *bias, const qe_conv_shape *shape, const float *identity,
+                             int32_t relu, float *out, const qe_requant *rq, uint8_t *codes, int32_t *status,
+                             qe_stream_t stream);
+int qe_quantconv2d_awq_fused_path(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric,
+                                  int32_t w_symmetric, const qe_conv_shape *shape, const float *identity, int32_t relu,
+                                  const float *out, const qe_requant *rq, const uint8_t *codes, const int32_t *status);
+
 /* qe_quantlinear_bf16 -- qe_quantlinear with a bf16 result, for a consumer that would round it anyway (the q / k / v
  * projections in front of qe_attention_bf16_stored):
  *   out[b, o] = bf16( y[b, o] * post_scale ),   y = qe_quantlinear(x, w, bias, B, K, O)      (B x O row-major bf16 bit patterns)

@@ -149,6 +149,8 @@ PROTOTYPES = {
     # group-quantised (AWQ) packed convolutions
     "qe_quantconv2d_awq": (_i32, [_pq, _pq, _i32, _i32, _i32, _vp, _ps, _i32, _vp, _vp]),
     "qe_quantconv2d_awq_path": (_i32, [_pq, _pq, _i32, _i32, _i32, _ps]),
+    "qe_quantconv2d_awq_fused": (_i32, [_pq, _pq, _i32, _i32, _i32, _vp, _ps, _vp, _i32, _vp, _pr, _vp, _vp, _vp]),
+    "qe_quantconv2d_awq_fused_path": (_i32, [_pq, _pq, _i32, _i32, _i32, _ps, _vp, _i32, _vp, _pr, _vp, _vp]),
     "qe_quantlinear_requant_path": (_i32, [_pq, _pq, _i64, _i32, _i32, _pr, _vp]),
     "qe_quantlinear_requant_workspace_bytes": (_sz, [_pq, _pq, _i64, _i32, _i32, _pr, _vp]),
     "qe_quantlinear_requant": (_i32, [_pq, _pq, _vp, _i64, _i32, _i32, _i32, _pr, _vp, _vp, _vp, _sz, _vp]),
@@ -869,6 +871,38 @@ def quantconv2d_awq(xq, wq, group_size, bias, sh, relu=False, out=None, stream=N
     check(lib().qe_quantconv2d_awq(*_grouped_args(xq, wq, group_size, x_symmetric, w_symmetric), _ptr(bias), ctypes.byref(sh),
                                    1 if relu else 0, out.data_ptr(), _stream(stream)))
     return out
+
+
+def conv_awq_fused_path(xq, wq, group_size, sh, identity=None, relu=False, out=None, rq=None, codes=None, status=None,
+                        x_symmetric=False, w_symmetric=False):
+    """qe_quantconv2d_awq_fused_path (host-only): 1 = the int8 matrix-core kernel finishes the work in its epilogue, 0 = the plain
+    kernel (and sub-8-bit codes through out), -1 = a request the call refuses.  identity / out / codes / status: the call's
+    destinations as tensors or addresses (the query reads their overlaps; their alignment does not enter)."""
+    adr = lambda t: (int(t) or None) if isinstance(t, int) else _ptr(t)
+    return int(lib().qe_quantconv2d_awq_fused_path(*_grouped_args(xq, wq, group_size, x_symmetric, w_symmetric), ctypes.byref(sh),
+                                                   adr(identity), 1 if relu else 0, adr(out), None if rq is None else ctypes.byref(rq),
+                                                   adr(codes), adr(status)))
+
+
+def quantconv2d_awq_fused(xq, wq, group_size, bias, sh, identity=None, relu=False, out=None, rq=None, codes=None, status=None,
+                          stream=None, x_symmetric=False, w_symmetric=False):
+    """qe_quantconv2d_awq_fused: v = [relu](quantconv2d_awq(...) [+ identity]) as fp32 `out` and / or, with rq, as the consumer's
+    codes.  out: a tensor (identity itself: in place), "new" to allocate one, or None: codes only (allocated all the same when
+    there is no rq).  Sub-8-bit codes need out.  Returns (out or None, codes or None, status int32[1] tensor)."""
+    import torch
+    dev = wq._keep[0].device
+    OH, OW = out_hw(sh)
+    if identity is not None:
+        assert identity.is_contiguous() and identity.dtype == torch.float32 and identity.numel() == sh.N * sh.OC * OH * OW
+    if isinstance(out, str) or (out is None and rq is None):
+        out = torch.empty((sh.N, sh.OC, OH, OW), dtype=torch.float32, device=dev)
+    if rq is not None and codes is None:
+        codes = torch.empty(packed_nbytes(sh.N * sh.OC * OH * OW, rq.n_bits), dtype=torch.uint8, device=dev)
+    status = _status(status, dev)
+    check(lib().qe_quantconv2d_awq_fused(*_grouped_args(xq, wq, group_size, x_symmetric, w_symmetric), _ptr(bias), ctypes.byref(sh),
+                                         _ptr(identity), 1 if relu else 0, _ptr(out), None if rq is None else ctypes.byref(rq),
+                                         _ptr(codes), status.data_ptr(), _stream(stream)))
+    return out, codes, status
 
 
 def global_avgpool(x, out=None, stream=None):

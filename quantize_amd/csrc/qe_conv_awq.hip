@@ -45,9 +45,32 @@
 //
 // Plain kernel (everything else: any kernel size, stride, padding, code width, group size, alignment): one thread per
 // output, group by group: the three integer sums over the taps inside the image, then the fold.
+//
+// Fused forms (qe_quantconv2d_awq_fused): two more epilogues of the fast kernel, one more plain kernel, the same K loop.
+//   CA_CODES     act(y) as fp32 (optional) and / or as the consumer's 8-bit codes (optional), no identity
+//   CA_END       act(y + identity): a residual block's end; out and codes each optional
+// The fp32 kernels keep their instruction streams: the fused forms are two more template arguments of the same kernels
+// (the form, and the argument block extended by what the epilogue reads), everything they add stands behind an
+// `if constexpr` on them, and the defaults instantiate the text that was there before.  (Sharing the K loop as a device
+// function moves the fp32 instances' instruction streams, as DESIGN.md records for grp_fold.)
+//   * Quantiser: D has the output channel on the LANE, so the consumer's scale and zero (per tensor, or per output channel --
+//     what an AWQ consumer's quantiser is once its awq_scale is folded in) are one register each per column tile, loaded
+//     from a clamped address as the bias is.  qe_rq_code is qe_quantize_pack's arithmetic: IEEE division, subtraction,
+//     rint, clamp, range test.
+//   * Code store: a lane holds four dwords of codes of a 32 x 32 tile, at pixels 8 gq + 4 h.  Two v_permlane32_swap
+//     between lane and lane ^ 32 leave pixels 0 .. 15 in the h = 0 lane and 16 .. 31 in the h = 1 lane: one 16-byte store per
+//     lane (P % 16 == 0, codes 16-byte aligned), four dword stores (P % 4 == 0, codes 4-byte aligned), or sixteen bytes.
+//     No LDS pass and no barrier: the patch stays free for the fp32 tile of the same step.
+//   * Identity: read with the access pattern out is written with -- 8 channel rows x 128 bytes per instruction into the
+//     wave's patch, quads picked up from it (P % 4 == 0, identity and out 16-byte aligned), single elements otherwise.  The
+//     loads of a tile are issued before that tile's sx / bias arithmetic.
+//   * Flag: the lanes' range flags are ORed over the wave (ballot); at most one atomicOr per wave, only when it is set.
 #include "qe_grp_common.hpp"         // the host layer and the device leaves shared with qe_linear_grp_i8.hip
+#include "qe_elementwise.hpp"        // qe_rq_code: the quantiser of qe_quantize_pack
 
 namespace qe {
+
+enum { CA_F32 = 0, CA_CODES = 1, CA_END = 2 };            // the epilogue forms
 
 // the kernel argument: both kernels read the same block
 struct ConvAwqArgs {
@@ -62,6 +85,15 @@ struct ConvAwqArgs {
     int relu;
 };
 
+// the kernel argument of the fused kernels: the block above (out may be NULL), then what the epilogue adds
+struct ConvAwqFusedArgs : ConvAwqArgs {
+    const float *identity;     // CA_END: fp32, shaped like out (may be out itself)
+    uint8_t *codes;            // [N][OC][OH][OW] stored 8-bit codes, or NULL
+    int32_t *status;           // bit 0 set when a code fails the range test (NaN included), or NULL
+    int rq_per_col;            // one scale and zero per output channel (else one of each)
+    QeRq rq;
+};
+
 namespace {
 
 typedef int v2i_a __attribute__((ext_vector_type(2)));
@@ -74,7 +106,10 @@ __device__ __forceinline__ float awq_act(float v, int relu) { return (!relu || v
 // ---------------------------------------------------------------------------------------------
 // Plain kernel: thread <-> output (n, o, oh, ow), ow fastest.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void conv_awq_plain_kernel(const ConvAwqArgs a)
+// A = ConvAwqFusedArgs: the fused forms on the plain route: per output the add, the ReLU, the fp32 store, one byte store for
+// an 8-bit code and an atomic OR for the flag.  The thread that writes out[idx] has read identity[idx]: in place is safe.
+template <class A = ConvAwqArgs>
+__global__ __launch_bounds__(256) void conv_awq_plain_kernel(const A a)
 {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (int64_t)a.N * a.OC * a.OH * a.OW) return;
@@ -108,6 +143,19 @@ __global__ __launch_bounds__(256) void conv_awq_plain_kernel(const ConvAwqArgs a
         float f = fmaf(-zwr, (float)s_x, (float)p);
         f = fmaf(-zxr, fmaf(-(float)taps, zwr, (float)s_w), f);
         acc = fmaf(sw, f, acc);
+    }
+    if constexpr (std::is_same<A, ConvAwqFusedArgs>::value) {
+        float v = fmaf(sx, acc, a.bias != nullptr ? a.bias[o] : 0.0f);
+        if (a.identity != nullptr) v = v + a.identity[idx];
+        v = awq_act(v, a.relu);
+        if (a.out != nullptr) a.out[idx] = v;
+        if (a.codes != nullptr) {
+            bool bad = false;
+            const int ci = a.rq_per_col ? o : 0;
+            a.codes[idx] = (uint8_t)qe_rq_code(v, a.rq.scale[ci], a.rq.zero[ci], a.rq, bad);
+            if (bad && a.status != nullptr) atomicOr(a.status, 1);
+        }
+        return;
     }
     a.out[idx] = awq_act(fmaf(sx, acc, a.bias != nullptr ? a.bias[o] : 0.0f), a.relu);
 }
@@ -148,8 +196,9 @@ template <int T> struct CaGeom {
     static_assert(((T / 32 + 1) & 1) == 1 && PPT >= 1, "tile width");
 };
 
-template <int WB, bool WZ, bool XZ, int T>
-__global__ __launch_bounds__(256, 2) void conv_awq_mfma_kernel(const ConvAwqArgs a)
+// EPI: the epilogue form; A: ConvAwqFusedArgs for a fused form.  (The defaults are the fp32 kernel as it always was.)
+template <int WB, bool WZ, bool XZ, int T, int EPI = CA_F32, class A = ConvAwqArgs>
+__global__ __launch_bounds__(256, 2) void conv_awq_mfma_kernel(const A a)
 {
     using Gm = CaGeom<T>;
     constexpr int MI = Gm::MI, PITCH = Gm::PITCH, SEGS = Gm::SEGS, PPT = Gm::PPT;
@@ -373,6 +422,128 @@ __global__ __launch_bounds__(256, 2) void conv_awq_mfma_kernel(const ConvAwqArgs
     const float zxr = a.x_zero[0] - (a.x_sign ? 0.0f : 128.0f);
     float *patch = reinterpret_cast<float *>(lsm) + wave * (32 * 36);
     const int rrow = lane >> 3, rq = lane & 7;
+    if constexpr (EPI != CA_F32) {
+        // Every branch on has_out / has_codes / vec4 / cform is wave-uniform.  In place (out == identity): a tile belongs to
+        // one wave; in the patch arm the lane that stores the piece (row 8 k + rrow, pixels q0 + 4 rq ..) is the lane that
+        // loaded it, and what it stores comes out of the patch, which holds the sums only after every load of the tile has
+        // landed in it; in the element arm a lane reads and writes the same elements.  So each element is read before it
+        // is written, by the same lane.
+        const bool has_out = a.out != nullptr, has_codes = a.codes != nullptr;
+        const int64_t img = n * OC * P;
+        const bool vec4 = (P & 3) == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0 &&
+                          (EPI != CA_END || (reinterpret_cast<uintptr_t>(a.identity) & 15) == 0);
+        const uintptr_t cad = reinterpret_cast<uintptr_t>(a.codes);
+        const int cform = ((P & 15) == 0 && (cad & 15) == 0) ? 2 : ((P & 3) == 0 && (cad & 3) == 0) ? 1 : 0;
+        bool bad = false;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int c0 = n0 + wn * 64 + j * 32, c = c0 + col, cc = min(c, OC - 1);
+            const float bias = a.bias != nullptr ? a.bias[cc] : 0.0f;
+            const float tj = XZ ? tcol[wn * 64 + j * 32 + col] : 0.0f;
+            float sc = 1.0f, zr = 0.0f;                   // the consumer's quantiser of this lane's channel
+            if (has_codes) { sc = a.rq.scale[a.rq_per_col ? cc : 0]; zr = a.rq.zero[a.rq_per_col ? cc : 0]; }
+#pragma unroll
+            for (int i = 0; i < MI; ++i) {
+                const int q0 = p0 + wm * (T / 2) + i * 32;    // + (r & 3) + 8 (r >> 2) + 4 h: register r's pixel
+                float v[16];
+                if constexpr (EPI == CA_END) {
+                    const float *idn = a.identity + img;
+                    if (vec4) {
+                        float4 ld[4];                     // requested first: in flight under the sx / bias arithmetic
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            const int row = 8 * k + rrow, px = q0 + 4 * rq;
+                            ld[k] = (c0 + row < OC && px < P) ? *reinterpret_cast<const float4 *>(idn + (int64_t)(c0 + row) * P + px)
+                                                              : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                        }
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) v[r] = fmaf(sx, XZ ? fmaf(-zxr, tj, acco[i][j][r]) : acco[i][j][r], bias);
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) *reinterpret_cast<float4 *>(patch + (8 * k + rrow) * 36 + 4 * rq) = ld[k];
+                        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                        for (int gq = 0; gq < 4; ++gq) {
+                            const float4 t = *reinterpret_cast<const float4 *>(patch + col * 36 + 8 * gq + 4 * h);
+                            v[4 * gq] = v[4 * gq] + t.x; v[4 * gq + 1] = v[4 * gq + 1] + t.y;
+                            v[4 * gq + 2] = v[4 * gq + 2] + t.z; v[4 * gq + 3] = v[4 * gq + 3] + t.w;
+                        }
+                        __builtin_amdgcn_wave_barrier();
+                    } else {
+                        float id[16];
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const int px = q0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                            id[r] = (c < OC && px < P) ? idn[(int64_t)c * P + px] : 0.0f;
+                        }
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) v[r] = fmaf(sx, XZ ? fmaf(-zxr, tj, acco[i][j][r]) : acco[i][j][r], bias) + id[r];
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) v[r] = fmaf(sx, XZ ? fmaf(-zxr, tj, acco[i][j][r]) : acco[i][j][r], bias);
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) v[r] = awq_act(v[r], a.relu);
+                if (has_out) {                            // (twin: the fp32 form's two store arms below)
+                    float *outn = a.out + img;
+                    if (vec4) {
+#pragma unroll
+                        for (int gq = 0; gq < 4; ++gq)
+                            *reinterpret_cast<float4 *>(patch + col * 36 + 8 * gq + 4 * h) = make_float4(v[4 * gq], v[4 * gq + 1], v[4 * gq + 2], v[4 * gq + 3]);
+                        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            const int row = 8 * k + rrow, px = q0 + 4 * rq;
+                            const float4 o4 = *reinterpret_cast<const float4 *>(patch + row * 36 + 4 * rq);
+                            if (c0 + row < OC && px < P) *reinterpret_cast<float4 *>(outn + (int64_t)(c0 + row) * P + px) = o4;
+                        }
+                        __builtin_amdgcn_wave_barrier();
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const int px = q0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                            if (c < OC && px < P) outn[(int64_t)c * P + px] = v[r];
+                        }
+                    }
+                }
+                if (has_codes) {
+                    unsigned cw[4];                       // cw[gq]: the codes of pixels q0 + 8 gq + 4 h .. + 3, low byte first
+#pragma unroll
+                    for (int gq = 0; gq < 4; ++gq) {
+                        cw[gq] = 0u;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            bool b1 = false;
+                            cw[gq] |= qe_rq_code(v[4 * gq + e], sc, zr, a.rq, b1) << (8 * e);
+                            bad |= b1 && c < OC && q0 + 8 * gq + 4 * h + e < P;       // lanes on tile padding never raise the flag
+                        }
+                    }
+                    // lanes [32, 64) of the first operand <-> lanes [0, 32) of the second: afterwards the h = 0 lane holds the
+                    // dwords of pixels 0, 4, 8, 12 and the h = 1 lane those of pixels 16, 20, 24, 28
+                    const auto s0 = __builtin_amdgcn_permlane32_swap(cw[0], cw[2], false, false);
+                    const auto s1 = __builtin_amdgcn_permlane32_swap(cw[1], cw[3], false, false);
+                    const unsigned pk[4] = {s0[0], s0[1], s1[0], s1[1]};
+                    const int px0 = q0 + 16 * h;
+                    uint8_t *dst = a.codes + img + (int64_t)c * P + px0;     // (formed, not touched, beyond OC or P)
+                    if (c < OC) {
+                        if (cform == 2) {                 // P % 16 == 0: a piece lies wholly inside the plane or beyond it
+                            if (px0 < P) *reinterpret_cast<uint4 *>(dst) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
+                        } else if (cform == 1) {          // P % 4 == 0: so does a dword
+#pragma unroll
+                            for (int k = 0; k < 4; ++k)
+                                if (px0 + 4 * k < P) *reinterpret_cast<unsigned *>(dst + 4 * k) = pk[k];
+                        } else {
+#pragma unroll
+                            for (int b = 0; b < 16; ++b)
+                                if (px0 + b < P) dst[b] = (uint8_t)(pk[b >> 2] >> (8 * (b & 3)));
+                        }
+                    }
+                }
+            }
+        }
+        if (has_codes && __builtin_amdgcn_ballot_w64(bad) != 0ull && lane == 0 && a.status != nullptr) atomicOr(a.status, 1);
+        return;
+    }
     const bool vec4 = (P & 3) == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0;
     float *outn = a.out + n * OC * P;
 #pragma unroll
@@ -413,14 +584,17 @@ __global__ __launch_bounds__(256, 2) void conv_awq_mfma_kernel(const ConvAwqArgs
 }
 
 // ---------------------------------------------------------------------------------------------
-// Host side: one plan, read by the path query and by the launch.  No HIP call in it.
+// Host side: one plan, read by the path queries and by the launches.  No HIP call in it.
 // ---------------------------------------------------------------------------------------------
 struct ConvAwqPlan {
-    int fast;               // 1: conv_awq_mfma_kernel, 0: conv_awq_plain_kernel
+    int fast;               // 1: conv_awq_mfma_kernel, 0: conv_awq_plain_kernel (a fused form: their fused twins)
     GrpI8Instance inst;     // the fast kernel's instance ...
     int t64;                // ... and its tile width
     int OH, OW, tiles;
     int64_t blocks;
+    int epi;                // CA_F32 (qe_quantconv2d_awq) | CA_CODES | CA_END
+    int two_pass;           // a fused form with sub-8-bit codes: the kernel writes out, qe_quantize_pack packs it
+    int path;               // what the fused path query answers: 1 the fast kernel finishes the work, 0 otherwise
 };
 
 // The tile width, from P alone: 64-pixel tiles where they save at least an eighth of the pixels the 128-pixel tiles would
@@ -431,10 +605,14 @@ bool awq_tile64(int64_t P)
     return (pad128 - pad64) * 8 >= pad128;
 }
 
-// a validated request (check_conv_awq)
-ConvAwqPlan plan_conv_awq(const qe_qparam *x, const qe_qparam *w, int G, int x_symmetric, int w_symmetric, const qe_conv_shape *sh)
+// a validated request (check_conv_awq; check_conv_awq_fused for a fused form).  epi: the form asked for; rq: its quantiser or
+// NULL.  No address enters: alignment selects a store arm inside the kernel.
+ConvAwqPlan plan_conv_awq(const qe_qparam *x, const qe_qparam *w, int G, int x_symmetric, int w_symmetric, const qe_conv_shape *sh,
+                          int epi = CA_F32, const qe_requant *rq = nullptr)
 {
     ConvAwqPlan p = {};
+    p.epi = epi;
+    p.two_pass = rq != nullptr && rq->n_bits < 8;
     p.OH = (sh->H + 2 * sh->padding - sh->KH) / sh->stride + 1;
     p.OW = (sh->W + 2 * sh->padding - sh->KW) / sh->stride + 1;
     p.fast = grp_weights_fast(w, G) && sh->KH == 1 && sh->KW == 1 && sh->stride == 1 && sh->padding == 0 && x->n_bits == 8 &&
@@ -444,6 +622,7 @@ ConvAwqPlan plan_conv_awq(const qe_qparam *x, const qe_qparam *w, int G, int x_s
     p.t64 = awq_tile64(P);
     p.tiles = (int)ceil_div64(P, p.t64 ? 64 : 128);
     p.blocks = p.fast ? (int64_t)sh->N * p.tiles * ceil_div64(sh->OC, CA_OCT) : ceil_div64((int64_t)sh->N * sh->OC * p.OH * p.OW, 256);
+    p.path = p.fast && !p.two_pass;
     return p;
 }
 
@@ -464,6 +643,66 @@ void launch_conv_awq(const ConvAwqPlan &p, const ConvAwqArgs &a, hipStream_t s)
     const unsigned blocks = (unsigned)p.blocks;
     if (p.t64) launch_instance<&conv_awq_mfma_kernel<WB, WZ, XZ, 64>>(blocks, 256, CaGeom<64>::LDS, 0, s, a);
     else launch_instance<&conv_awq_mfma_kernel<WB, WZ, XZ, 128>>(blocks, 256, CaGeom<128>::LDS, 0, s, a);
+}
+
+template <int WB, bool WZ, bool XZ>
+void launch_conv_awq_fused(const ConvAwqPlan &p, const ConvAwqFusedArgs &f, hipStream_t s)
+{
+    const unsigned blocks = (unsigned)p.blocks;
+    dispatch_flag(p.epi == CA_END, [&](auto end) {
+        constexpr int EPI = decltype(end)::value ? CA_END : CA_CODES;
+        if (p.t64) launch_instance<&conv_awq_mfma_kernel<WB, WZ, XZ, 64, EPI, ConvAwqFusedArgs>>(blocks, 256, CaGeom<64>::LDS, 0, s, f);
+        else launch_instance<&conv_awq_mfma_kernel<WB, WZ, XZ, 128, EPI, ConvAwqFusedArgs>>(blocks, 256, CaGeom<128>::LDS, 0, s, f);
+    });
+}
+
+// the kernel argument of either entry point from its plan
+void fill_conv_awq(ConvAwqArgs &a, const ConvAwqPlan &p, const qe_qparam *x, const qe_qparam *w, const float *bias, int G,
+                   const qe_conv_shape *shape, int relu, float *out)
+{
+    fill_grp_operands(a, x, w, bias, G, shape->IC);
+    a.out = out;
+    a.N = shape->N; a.IC = shape->IC; a.H = shape->H; a.W = shape->W; a.OC = shape->OC; a.KH = shape->KH; a.KW = shape->KW;
+    a.stride = shape->stride; a.padding = shape->padding; a.OH = p.OH; a.OW = p.OW;
+    a.P = p.fast ? shape->H * shape->W : 0; a.tiles = p.tiles; a.relu = relu != 0;
+}
+
+// A fused request: the code the call returns for it and, when that is QE_OK, the plan the call and the path query read.
+struct ConvAwqFusedRequest {
+    int rc;
+    ConvAwqPlan plan;
+};
+
+// The order decides which code a caller sees: the plain entry point's checks, the destinations and the quantiser's
+// pointers, its width, its count, the overlaps; then what no kernel serves.
+ConvAwqFusedRequest request_conv_awq_fused(const qe_qparam *x, const qe_qparam *w, int G, int x_symmetric, int w_symmetric,
+                                           const float *bias, const qe_conv_shape *sh, const float *identity, const float *out,
+                                           const qe_requant *rq, const uint8_t *codes, const int32_t *status)
+{
+    ConvAwqFusedRequest r = {};
+    if ((r.rc = check_conv_awq(x, w, G, sh)) != QE_OK) return r;
+    r.rc = QE_ERR_ARG;
+    if ((out == nullptr && codes == nullptr) || (codes != nullptr) != (rq != nullptr)) return r;
+    if (rq != nullptr) {
+        if ((r.rc = check_requant(rq)) != QE_OK) return r;
+        r.rc = QE_ERR_ARG;
+        if (!one_or_per_channel(rq->n_param, sh->OC)) return r;
+    }
+    r.plan = plan_conv_awq(x, w, G, x_symmetric, w_symmetric, sh, identity != nullptr ? CA_END : CA_CODES, rq);
+    const int64_t n_in = (int64_t)sh->N * sh->IC * sh->H * sh->W, n = (int64_t)sh->N * sh->OC * r.plan.OH * r.plan.OW;
+    const Span outs[3] = {span_of(out, n * 4), span_of(codes, rq ? qe_packed_nbytes(n, rq->n_bits) : 0), span_of(status, 4)};
+    const Span ins[9] = {span_of(x->data, qe_packed_nbytes(n_in, x->n_bits)),
+                         span_of(w->data, qe_packed_nbytes((int64_t)sh->OC * sh->IC * sh->KH * sh->KW, w->n_bits)),
+                         span_of(x->scale, 4), span_of(x->zero, 4),
+                         span_of(w->scale, 4 * (int64_t)w->n_param), span_of(w->zero, 4 * (int64_t)w->n_param),
+                         span_of(bias, 4 * (int64_t)sh->OC), span_of(rq ? rq->scale : nullptr, rq ? 4 * (int64_t)rq->n_param : 0),
+                         span_of(rq ? rq->zero : nullptr, rq ? 4 * (int64_t)rq->n_param : 0)};
+    if (!outputs_clear(outs, 3, ins, 9)) return r;
+    // the identity: an operand to codes and status, and to out unless it IS out
+    const Span id = span_of(identity, n * 4);
+    if (overlaps(outs[1], id) || overlaps(outs[2], id) || (out != nullptr && !same_or_disjoint(out, identity, n * 4))) return r;
+    r.rc = r.plan.two_pass && out == nullptr ? QE_ERR_UNSUPPORTED : QE_OK;
+    return r;
 }
 
 }  // namespace
@@ -487,15 +726,48 @@ extern "C" int qe_quantconv2d_awq(const qe_qparam *x, const qe_qparam *w, int32_
     if (out == nullptr) return QE_ERR_ARG;
     const ConvAwqPlan p = plan_conv_awq(x, w, group_size, x_symmetric, w_symmetric, shape);
     ConvAwqArgs a = {};
-    fill_grp_operands(a, x, w, bias, group_size, shape->IC);
-    a.out = out;
-    a.N = shape->N; a.IC = shape->IC; a.H = shape->H; a.W = shape->W; a.OC = shape->OC; a.KH = shape->KH; a.KW = shape->KW;
-    a.stride = shape->stride; a.padding = shape->padding; a.OH = p.OH; a.OW = p.OW;
-    a.P = p.fast ? shape->H * shape->W : 0; a.tiles = p.tiles; a.relu = relu != 0;
+    fill_conv_awq(a, p, x, w, bias, group_size, shape, relu, out);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return launch_grp<&conv_awq_plain_kernel>(p.fast, p.blocks, a, s, [&] {
+    return launch_grp<&conv_awq_plain_kernel<>>(p.fast, p.blocks, a, s, [&] {
         dispatch_grp_i8(p.inst, [&](auto wb, auto wz, auto xz) {
             launch_conv_awq<decltype(wb)::value, decltype(wz)::value, decltype(xz)::value>(p, a, s);
         });
     });
+}
+
+extern "C" int qe_quantconv2d_awq_fused_path(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric,
+                                             int32_t w_symmetric, const qe_conv_shape *shape, const float *identity, int32_t relu,
+                                             const float *out, const qe_requant *rq, const uint8_t *codes, const int32_t *status)
+{
+    (void)relu;                                           // (the ReLU is a runtime select in every kernel)
+    const qe::ConvAwqFusedRequest r = qe::request_conv_awq_fused(x, w, group_size, x_symmetric, w_symmetric, nullptr, shape, identity,
+                                                                 out, rq, codes, status);
+    return r.rc == QE_OK ? r.plan.path : -1;
+}
+
+extern "C" int qe_quantconv2d_awq_fused(const qe_qparam *x, const qe_qparam *w, int32_t group_size, int32_t x_symmetric,
+                                        int32_t w_symmetric, const float *bias, const qe_conv_shape *shape, const float *identity,
+                                        int32_t relu, float *out, const qe_requant *rq, uint8_t *codes, int32_t *status,
+                                        qe_stream_t stream)
+{
+    using namespace qe;
+    const ConvAwqFusedRequest r = request_conv_awq_fused(x, w, group_size, x_symmetric, w_symmetric, bias, shape, identity, out, rq,
+                                                         codes, status);
+    if (r.rc != QE_OK) return r.rc;
+    const ConvAwqPlan &p = r.plan;
+    ConvAwqFusedArgs f = {};
+    fill_conv_awq(f, p, x, w, bias, group_size, shape, relu, out);
+    f.identity = identity;
+    if (rq != nullptr && !p.two_pass) {
+        f.codes = codes; f.status = status; f.rq_per_col = rq->n_param != 1; f.rq = make_qe_rq(*rq);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int rc = launch_grp<&conv_awq_plain_kernel<ConvAwqFusedArgs>>(p.fast, p.blocks, f, s, [&] {
+        dispatch_grp_i8(p.inst, [&](auto wb, auto wz, auto xz) {
+            launch_conv_awq_fused<decltype(wb)::value, decltype(wz)::value, decltype(xz)::value>(p, f, s);
+        });
+    });
+    if (rc != QE_OK || !p.two_pass) return rc;
+    return qe_quantize_pack(out, (int64_t)shape->N * shape->OC * p.OH * p.OW, rq->scale, rq->zero, rq->n_param, (int64_t)p.OH * p.OW,
+                            rq->qmin, rq->qmax, rq->n_bits, rq->sign, codes, status, stream);
 }

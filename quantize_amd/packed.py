@@ -548,7 +548,8 @@ class PackedAwqConv2d(PackedGroupedLinear):
     """A convolution whose weights are group-quantised as the reference's AWQ estimator lays out a 4-D weight (range/awq.py):
     one scale and zero per (output channel, group of `group_size` consecutive input channels, all taps) and a per-input-channel
     awq_scale the weights were multiplied by before rounding.  The reference can only simulate such a layer; here it runs
-    packed on qe_quantconv2d_awq: activation codes in, fp32 NCHW out.  State: PackedGroupedLinear's keys with w_des [n_bits,
+    packed on qe_quantconv2d_awq: activation codes in, fp32 NCHW out -- or, through call_packed's keywords, with the residual add,
+    the ReLU and the consumer's codes from the same kernel (qe_quantconv2d_awq_fused).  State: PackedGroupedLinear's keys with w_des [n_bits,
     sign, OC, IC, KH, KW], w_scale / w_zero of OC * IC / group_size elements in (o, g) order, plus the geometry (stride,
     padding).  The activation quantiser (set_quantizer) is the per-tensor one of x / awq_scale[c]."""
 
@@ -609,19 +610,35 @@ class PackedAwqConv2d(PackedGroupedLinear):
             raise RuntimeError(OUT_OF_RANGE)
         return codes, (self.a_bits, int(self.a_signed), *x.shape)
 
-    def call_packed(self, xq, x_des, relu=False):
-        """Activation codes as quantize() returns them -> the fp32 (N, OC, OH, OW) output on qe_quantconv2d_awq."""
+    def call_packed(self, xq, x_des, relu=False, consumer=None, identity=None, out=None, status=None):
+        """Activation codes as quantize() returns them -> the fp32 (N, OC, OH, OW) output on qe_quantconv2d_awq.  With any of the
+        other keywords the layer's end is fused into the kernel (qe_quantconv2d_awq_fused), bit-identical to the separate steps:
+        identity: fp32, shaped like the output: [relu](output + identity), a residual block's end; out=identity: in place.
+        consumer: the Packed* layer that reads the result: returns the (packed, des) pair of ITS activation quantiser
+        (consumer.requant(): a PackedAwqConv2d's is per channel, its awq_scale folded in) with des as host integers; sub-8-bit
+        codes go through an fp32 tensor inside the call.  out: where the fp32 result goes when the caller wants it too.
+        status: a device int32 the range flag accumulates in (None: raise when the codes are out of range)."""
         n_bits, sign, N, C, H, W = _host_des(x_des)
         if C != self.K:
             raise ValueError("codes of %d input channels for a convolution of %d" % (C, self.K))
         sh = capi.conv_shape(N, C, H, W, self.O, self.KH, self.KW, self.stride, self.padding)
-        return capi.quantconv2d_awq(self.xq(xq, n_bits, sign), self.wq(), self.group_size, self.bias, sh, relu=relu,
-                                    x_symmetric=self.a_centred, w_symmetric=self.w_centred)
+        x, sym = self.xq(xq, n_bits, sign), dict(x_symmetric=self.a_centred, w_symmetric=self.w_centred)
+        if consumer is None and identity is None and out is None:
+            return capi.quantconv2d_awq(x, self.wq(), self.group_size, self.bias, sh, relu=relu, **sym)
+        if consumer is not None and out is None and consumer.a_bits < 8:
+            out = "new"
+        y, codes, flag = capi.quantconv2d_awq_fused(x, self.wq(), self.group_size, self.bias, sh, identity=identity, relu=relu, out=out,
+                                                    rq=None if consumer is None else consumer.requant(), status=status, **sym)
+        if consumer is None:
+            return y
+        if status is None and int(flag.item()) != 0:
+            raise RuntimeError(OUT_OF_RANGE)
+        return codes, (consumer.a_bits, int(consumer.a_signed), N, self.O, *capi.out_hw(sh))
 
     def __call__(self, x, relu=False):
         return self.call_packed(*self.quantize(x), relu=relu)
 
-    call_packed_residual = call_packed_requant = None         # the linear's fused forms: a convolution has none yet
+    call_packed_residual = call_packed_requant = None         # the linear's method names: a convolution's forms are call_packed's keywords
 
 
 class PackedMultiheadAttention:

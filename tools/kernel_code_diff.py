@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the gfx950 device code of two builds, kernel by kernel.
 
-  tools/kernel_code_diff.py <old> <new> [name filter]
+  tools/kernel_code_diff.py <old> <new> [name filter] [--rename REGEX=REPLACEMENT ...]
 
 <old> and <new> are each a directory of object files (quantize_amd/_ext/obj of a build: compared object by object, by file
 name), one object file, or one assembly file written by `hipcc --offload-arch=gfx950 --cuda-device-only -S` with
@@ -11,7 +11,9 @@ llvm-objdump -d.
 Of each kernel only the instruction lines count: no directives, no comments (an object's addresses and encodings are
 comments), no __hip_cuid_ symbol, none of the zero padding or no-op fill behind a function's last instruction.  Kernels are keyed by their
 demangled name without the parameter list, so a renamed argument type is no difference.  The filter keeps the kernels whose key contains it.  The comparison is of text: no
-instruction is known by name.  Prints the kernels that only one side has, the kernels whose instructions differ (with the
+instruction is known by name.  --rename rewrites the keys of <old> (re.sub, after the filter) for a kernel that gained template
+arguments with defaults: `--rename '(mfma_kernel<.*)>$=\\1, 0, qe::ConvAwqArgs>'` pairs conv_awq_mfma_kernel<4, false, false, 64>
+with conv_awq_mfma_kernel<4, false, false, 64, 0, qe::ConvAwqArgs>.  Prints the kernels that only one side has, the kernels whose instructions differ (with the
 first differing line) and the counts; the exit status is 1 if there is any of either.
 """
 import os
@@ -109,12 +111,16 @@ def pairs(old, new):
 
 
 def main(argv):
+    renames = [a.split("=", 1) for i, a in enumerate(argv) if i and argv[i - 1] == "--rename"]
+    argv = [a for i, a in enumerate(argv) if a != "--rename" and (not i or argv[i - 1] != "--rename")]
     if len(argv) not in (3, 4):
         sys.exit(__doc__)
     flt = argv[3] if len(argv) == 4 else ""
     total = only = differ = 0
     for label, old, new in pairs(argv[1], argv[2]):
         a = kernels(old, flt) if old else {}
+        for pat, repl in renames:
+            a = {re.sub(pat, repl, k): v for k, v in a.items()}
         b = kernels(new, flt) if new else {}
         if not a and not b:
             continue
