@@ -481,6 +481,37 @@ int qe_quantlinear_grouped_float_input(const float *x, const float *x_mul, const
 int qe_quantlinear_grouped_float_input_path(const float *x, const float *x_mul, const qe_qparam *w, int32_t group_size,
                                             int32_t symmetric, int64_t B, int32_t K, int32_t O);
 
+/* qe_quantlinear_grouped_bf16_input -- bf16 rows x the same group-quantised weight codes ("W4A16"), read as stored:
+ *   out[b,o] = bias[o] + sum_g  sw[o,g] * sum_{k in group g} x'[b,k] * (q_w[o,k] - zw[o,g])   (+ residual[b,o])
+ *   x'[b,k]  = x[b,k]                                  when x_mul == NULL
+ *   x'[b,k]  = bf16_rne( float(x[b,k]) * x_mul[k] )    otherwise: one fp32 multiply, rounded once (to nearest even) to bf16
+ * x        B*K bf16 bit patterns, contiguous (as qe_quantlinear_bf16_input takes them); the values they denote are exact.
+ * x_mul    fp32[K] or NULL.  The rounding of x' is the declared difference from qe_quantlinear_grouped_float_input: it is what
+ *          a bf16 producer that had folded 1 / awq_scale into its rows would have stored, and it keeps every operand of the
+ *          matrix cores a single bf16.
+ * w, group_size, symmetric, bias, out (B*O floats, fully written)   exactly as for qe_quantlinear_grouped_float_input.
+ * residual NULL: none; given, B*O floats added with one fp32 add: the with-residual result is the no-residual result plus
+ *          residual, bit for bit.  out == residual (in place) is allowed.   No workspace, no prepared tables.
+ * Non-finite activations: as declared for qe_quantlinear_bf16_input, on the fast kernel: a NaN or inf in a row of x makes
+ * that row's outputs non-finite (NaN where a chain of fp32 operations keeps inf) and no other row's.
+ * Refused before any device work, in the order of qe_quantlinear_grouped_float_input (negative sizes, the weight operand,
+ * group_size and n_param, a NULL x or out with elements to read or write); then, with QE_ERR_ARG: an x that is not 2-byte
+ * aligned, an out or residual that is not 4-byte aligned, an out that overlaps x, a residual that overlaps out without
+ * being out.
+ * _path (host-only, from the one plan the launch reads; 0 for a request the call would refuse):
+ *   1 = the fast kernel: 4- or 8-bit codes, group_size in {32, 64, 128}, K % 32 == 0, x, x_mul and w->data 16-byte aligned (any
+ *       B and O, any 4-byte aligned out and residual): a row of x' is the matrix cores' operand -- one
+ *       v_mfma_f32_32x32x16_bf16 per product where the fp32-row kernel's three-way split issues three -- against codes
+ *       centred on rint(zw[o,g]) per (row, group), folded into the total with sw[o,g] at every group boundary.  Every product
+ *       is exact in fp32; the fp32 accumulation and the fp32 group sums of x' round: within the parity rule of the exact sum,
+ *       NOT bit-identical to the fp32-row entry point on the widened rows;
+ *   0 = the plain kernel: one thread per output, fp32, group by group in k order (any n_bits, group_size, K, alignment). */
+int qe_quantlinear_grouped_bf16_input(const uint16_t *x, const float *x_mul, const qe_qparam *w, int32_t group_size,
+                                      int32_t symmetric, const float *bias, int64_t B, int32_t K, int32_t O,
+                                      const float *residual, float *out, qe_stream_t stream);
+int qe_quantlinear_grouped_bf16_input_path(const uint16_t *x, const float *x_mul, const qe_qparam *w, int32_t group_size,
+                                           int32_t symmetric, int64_t B, int32_t K, int32_t O);
+
 /* qe_quantlinear_grouped -- packed activation codes x the same group-quantised weight codes, on the int8 matrix cores:
  *   out[b,o] = bias[o] + sx[b] * sum_g  sw[o,g] * sum_{k in group g} (q_x[b,k] - zx[b]) * (q_w[o,k] - zw[o,g])
  * NOTE the convention: BOTH operands use the kernel convention (q - zero), as qe_quantlinear_grouped_float_input does for

@@ -138,6 +138,8 @@ PROTOTYPES = {
     "qe_quantlinear_float_input_path": (_i32, [_vp, _pq, _i64, _i32, _i32]),
     "qe_quantlinear_grouped_float_input": (_i32, [_vp, _vp, _pq, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp]),
     "qe_quantlinear_grouped_float_input_path": (_i32, [_vp, _vp, _pq, _i32, _i32, _i64, _i32, _i32]),
+    "qe_quantlinear_grouped_bf16_input": (_i32, [_vp, _vp, _pq, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "qe_quantlinear_grouped_bf16_input_path": (_i32, [_vp, _vp, _pq, _i32, _i32, _i64, _i32, _i32]),
     "qe_quantlinear_grouped": (_i32, [_pq, _pq, _i32, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp]),
     "qe_quantlinear_grouped_path": (_i32, [_pq, _pq, _i32, _i32, _i32, _i64, _i32, _i32]),
     "qe_quantlinear_grouped_requant_path": (_i32, [_pq, _pq, _i32, _i32, _i32, _i64, _i32, _i32, _pr, _vp]),
@@ -1042,6 +1044,32 @@ def quantlinear_bf16_input(x, wq, bias, O, residual=None, out=None, workspace=No
     ws = _given_ws(workspace, need, x.device)
     check(lib().qe_quantlinear_bf16_input(x.data_ptr(), ctypes.byref(wq), _ptr(bias), int(B), int(K), int(O), _ptr(residual),
                                           out.data_ptr(), *_prep(ws), _stream(stream)))
+    return out
+
+
+def linear_grouped_bf16_input_path(x, wq, group_size, B, K, O, x_mul=None, symmetric=False):
+    """qe_quantlinear_grouped_bf16_input_path (host-only): 1 = the bf16-row matrix-core kernel, 0 = the plain kernel or a request
+    the call would refuse.  x and x_mul are tensors or addresses (only their alignment counts)."""
+    addr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()
+    return int(lib().qe_quantlinear_grouped_bf16_input_path(addr(x), addr(x_mul), ctypes.byref(wq), int(group_size),
+                                                            1 if symmetric else 0, int(B), int(K), int(O)))
+
+
+def quantlinear_grouped_bf16_input(x, wq, group_size, bias, O, x_mul=None, symmetric=False, residual=None, out=None, stream=None):
+    """qe_quantlinear_grouped_bf16_input: quantlinear_grouped_float_input's operands on a contiguous torch.bfloat16 (B, K) tensor,
+    read in place; with an x_mul the activations are bf16(x * x_mul), rounded to nearest even (see the header).  residual:
+    contiguous fp32 of B * O elements, one fp32 add (out=residual: in place).  Anything else as x raises ValueError."""
+    import torch
+    _check_bf16_rows(x)
+    B, K = x.shape
+    if residual is not None:
+        assert residual.is_contiguous() and residual.dtype == torch.float32 and residual.numel() == B * O
+    if out is None:
+        out = torch.empty((B, O), dtype=torch.float32, device=x.device)
+    assert out.is_contiguous() and out.dtype == torch.float32 and out.numel() == B * O
+    check(lib().qe_quantlinear_grouped_bf16_input(x.data_ptr(), _ptr(x_mul), ctypes.byref(wq), int(group_size),
+                                                  1 if symmetric else 0, _ptr(bias), int(B), int(K), int(O), _ptr(residual),
+                                                  out.data_ptr(), _stream(stream)))
     return out
 
 

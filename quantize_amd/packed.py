@@ -531,13 +531,26 @@ class PackedGroupedLinear:
             raise RuntimeError(OUT_OF_RANGE)
         return codes, (consumer_rq.n_bits, int(consumer_rq.sign), *lead, self.O)
 
+    def call_bf16_residual(self, x, residual, out=None):
+        """__call__(x) + residual on torch.bfloat16 rows, the add in the kernel's epilogue (qe_quantlinear_grouped_bf16_input):
+        bit-identical to the two steps.  residual: contiguous fp32 of rows x out_features elements; out=residual: in place."""
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        return capi.quantlinear_grouped_bf16_input(x2, self.wq(), self.group_size, self.bias, self.O, x_mul=self.x_mul,
+                                                   symmetric=self.symmetric, residual=residual, out=out)
+
     def __call__(self, x, route="float"):
-        """fp32 rows (..., in_features) -> (..., out_features).  route="float": the fp32 rows themselves meet the weight codes;
-        route="packed": call_packed(*quantize(x)).  Not bit-identical: the packed route quantises the activations."""
+        """fp32 or bf16 rows (..., in_features) -> fp32 (..., out_features).  route="float": the rows themselves meet the weight
+        codes -- torch.bfloat16 rows as they are stored (qe_quantlinear_grouped_bf16_input: with an awq_scale the activations
+        are bf16(x / awq_scale)), anything else as fp32; route="packed": call_packed(*quantize(x)).  Not bit-identical: the
+        packed route quantises the activations."""
         if route == "packed":
             return self.call_packed(*self.quantize(x))
         if route != "float":
             raise ValueError("route must be 'packed' or 'float'")
+        if x.dtype == torch.bfloat16:
+            y = capi.quantlinear_grouped_bf16_input(x.reshape(-1, x.shape[-1]).contiguous(), self.wq(), self.group_size, self.bias,
+                                                    self.O, x_mul=self.x_mul, symmetric=self.symmetric)
+            return y.reshape(*x.shape[:-1], self.O)
         x2 = x.reshape(-1, x.shape[-1]).contiguous().float()
         y = capi.quantlinear_grouped_float_input(x2, self.wq(), self.group_size, self.bias, self.O, x_mul=self.x_mul,
                                                  symmetric=self.symmetric)
